@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- train samples/sec of the SCoRe hot path on MI355X.
 
-  python bench.py [--gpus N] [--steps K] [--warmup W] [--config cfg3]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--config cfg3] [--dump-outputs DIR] [--full]
   (N > 1: either launched by `python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...`, or called
    plainly -- `python bench.py --gpus N` then starts that launcher itself as a child process, before touching the GPU)
 
@@ -9,12 +9,18 @@ A "step" is one full training step of SCORE (score.py:101-116: forward, backward
 whole table and all dense variables) on one synthetic Tmall-shaped batch whose int32 index tensors are
 already resident in HBM.  Prints ONE JSON line (rank 0).
 
+A plain run does only what the headline needs: it sets up, warms up, times K steps, writes the last timed step's outputs
+if --dump-outputs is given (last_step_outputs: the same arguments give the same inputs in every run, so two builds can be
+compared output for output) and prints the line: `value`, `ms_per_step` and the workload's description.  Everything
+below besides `value` -- the per-step distribution, the stage table, the synchronous-train leg, the side measurements,
+rooflines, CPU baselines and the small-shape legs -- runs only with --full.
+
 `value` is the STEADY STATE of a long run: every table row carries Adam moments (dense ApplyAdam then owes every
 row an update every step -- in a short run from a fresh optimizer only the rows touched so far).  The table
 optimizer is the time-tiled one (score_amd/csrc/adam_tiled.hip: bit-identical to the per-step sweep, which
 `value_dense_adam_sweep` times in the same process; updates still owed after the last step are applied inside
 the timed region), all other state as the loader produces it (length = T - 2 for every sample, mirroring the reference's
-train split 9 of 11, graph_loader.py:382; the slices every sample masks are skipped).  Beside it, in the same
+train split 9 of 11, graph_loader.py:382; the slices every sample masks are skipped).  With --full, beside it in the same
 line and measured in the same process: `value_best_case` (fresh optimizer state), `value_all_slices` (nothing
 skipped), `ingestion` (device-side batch assembly inside the loop; nested Python lists as the reference feeds
 them), `roofline` (the fused embedding-gather + co-attention forward kernel -- the dominant HBM-bound kernel -- on a
@@ -271,6 +277,36 @@ def stream_copy_ceiling(model, n_bytes=1 << 30, iters=10):
                     "3 x %d launches by HIP events" % (n_bytes >> 20, n_bytes >> 20, iters)}
 
 
+DUMP_TABLE_ROWS = 8192           # table rows in the dump: a fixed sample, the same rows in every run of a config
+DUMP_MAX_DENSE = 4 << 20         # dense variables beyond this many are sampled the same way (the dump stays far below 64 MB)
+
+
+def last_step_outputs(inner, B, loss, sharded):
+    """What the timed path computed in its last step, as a caller of that step receives it: the loss, the predictions of its
+    forward pass (the unsharded workspace's y_pred; the sharded step keeps them per rank), the dense variables and a fixed
+    seeded sample of embedding-table rows after the optimizer (for a sharded run: rank 0's shard).  float32 host arrays."""
+    out = {"loss": np.asarray([loss], dtype=np.float32)}
+    if not sharded:
+        lay, ws = inner._workspace(B)
+        out["y_pred"] = ws[lay.y_pred:lay.y_pred + B].float().cpu().numpy()
+    w = inner.w.detach().float()
+    if w.numel() > DUMP_MAX_DENSE:
+        idx = np.sort(np.random.default_rng(1).choice(w.numel(), DUMP_MAX_DENSE, replace=False))
+        w = w[torch.from_numpy(idx).to(w.device)]
+    out["dense_params"] = w.cpu().numpy()
+    table = inner.table
+    n_rows = int(table.shape[0])
+    rows = np.sort(np.random.default_rng(0).choice(n_rows, min(n_rows, DUMP_TABLE_ROWS), replace=False))
+    out["table_rows_sample"] = table[torch.from_numpy(rows).to(table.device)].float().cpu().numpy()
+    return out
+
+
+def dump_outputs(path, arrays):
+    os.makedirs(path, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), np.ascontiguousarray(a, dtype=np.float32))
+
+
 class Heartbeat(object):
     """Several ranks: a hung collective must not eat the driver's whole timeout in silence.  A daemon thread prints one
     line per rank to stderr every `every` seconds (phase, step, the communicator's last collective) and, when the main
@@ -438,9 +474,16 @@ def main():
     ap.add_argument("--warmup", type=int, default=10)
     ap.add_argument("--config", default="cfg3")
     ap.add_argument("--batches", type=int, default=8, help="distinct pre-staged batches cycled through")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="the whole line: per-step distribution, stage table, synchronous-train leg, side measurements, "
+                         "rooflines, CPU baselines and small-shape legs beside the headline.  Without it: set-up, warm-up, "
+                         "the timed steps, --dump-outputs, the headline line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed as DIR/<name>.npy (float32): loss, y_pred, "
+                         "dense_params and a fixed sample of table rows (last_step_outputs)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="(--full) no CPU baselines")
     ap.add_argument("--no-side", action="store_true",
-                    help="skip the side measurements (best case, all slices, gather probe, ingestion): headline only")
+                    help="(--full) skip the side measurements (best case, all slices, gather probe, ingestion)")
     ap.add_argument("--force-sharded", action="store_true",
                     help="use the row-sharded all-to-all path even with one rank (exercises RCCL plumbing)")
     ap.add_argument("--no-prefetch", dest="prefetch", action="store_false",
@@ -490,7 +533,7 @@ def main():
                     help="(internal) run ONE small-shape leg on CONFIG in this process and print its JSON: the default run starts "
                          "one child process per leg")
     ap.add_argument("--no-small-shapes", action="store_true",
-                    help="skip the two short legs on cfg-2 and the reference's Tmall-default shape (`small_shapes`, the LAST key of the line)")
+                    help="(--full) skip the two short legs on cfg-2 and the reference's Tmall-default shape (`small_shapes`, the LAST key of the line)")
     ap.add_argument("--lr", type=float, default=1e-3)
     ap.add_argument("--reg-lambda", type=float, default=1e-4)
     args = ap.parse_args()
@@ -671,8 +714,9 @@ def main():
         return (model.fwd_events, model.bwd_events) + tuple(torch.cuda.Event(enable_timing=True) for _ in range(4))
     # Inside the timed region only the dominant kernel is bracketed (the fused gather: two events on every E-th step,
     # `roofline_bench_workload`'s live launch duration); the full stage table -- eleven events per step, +0.07 ms on a step that
-    # carries them (round 4: per-step marks, 1.35 vs 1.27 ms) -- comes from a few extra steps right behind the timed region
-    for i in range(args.steps):
+    # carries them (round 4: per-step marks, 1.35 vs 1.27 ms) -- comes from a few extra steps right behind the timed region.
+    # A plain run (no --full) records no timing event at all: its steps are the model's own, nothing else
+    for i in range(args.steps if args.full else 0):
         if i % every:
             continue
         if args.stage_events_timed:
@@ -680,7 +724,8 @@ def main():
         else:
             model.enable_stage_events(True)
             events[i] = (model.fwd_events[:2] + [None, None, None], None, None, None, None, None)
-    step_marks = [torch.cuda.Event(enable_timing=True) for _ in range(args.steps + 1)]     # one record per step: ms_per_step_p50
+    step_marks = ([torch.cuda.Event(enable_timing=True) for _ in range(args.steps + 1)]     # one record per step: ms_per_step_p50
+                  if args.full else None)
     # The interpreter's cyclic garbage collector: a generation-2 pass over the ~10^6 objects torch has alive takes 50 - 70
     # ms, and when one lands inside a host-bound timed loop (the small shapes: 300 steps of 0.38 ms) it alone adds 0.13 -
     # 0.2 ms per step to the mean (measured: bench line 0.53 vs 0.385 ms/step at the reference's own shape; which run gets
@@ -694,7 +739,7 @@ def main():
     gc.freeze()
     beat("warmup")
     run_steps(max(args.warmup - 1, 0))
-    if args.warmup > 0 and not graph:
+    if args.warmup > 0 and not graph and args.full:
         # the last warm-up step carries stage events like every `every`-th timed step does: the first step that records
         # timing events pays a one-time 15 ms in the HIP runtime (measured), which is warm-up, not a step
         warm_ev = {-1: full_event_set()}
@@ -712,13 +757,97 @@ def main():
     #  profiles/r04_probes.md --: inside it only its first and last step are marked; the per-step distribution comes from a
     #  separate stretch of steps right behind it.  --step-marks-timed restores a mark per timed step)
     mark_every_step = args.step_marks_timed
-    fb = run_steps(args.steps, 0, None if graph else events, step_marks)
+    fb = run_steps(args.steps, 0, None if (graph or not args.full) else events, step_marks)
     finish_adam()                  # inside the timed region: no update is left owing when the clock stops
-    ev_tail = torch.cuda.Event(enable_timing=True)
-    ev_tail.record()
+    if args.full:
+        ev_tail = torch.cuda.Event(enable_timing=True)
+        ev_tail.record()
     barrier()
     dt = time.perf_counter() - t0
     beat("after")
+
+    def step_loss(fb):
+        """the loss the caller of the step receives (a captured step's run_steps returns no workspace: the model's own is it)"""
+        if sharded:
+            return float((fb[0][1] + args.reg_lambda * fb[0][2]).item())
+        lay_, ws_ = fb if fb is not None else inner._workspace(B)
+        return float(ws_[lay_.loss].item())
+
+    def max_over_ranks(dt):
+        """the step time of record is the MAX over ranks; every rank's own time rides in the same all_gather"""
+        if dist is None:
+            return dt, [dt], 1
+        n = dist.get_world_size()
+        mine = torch.tensor([dt], dtype=torch.float64, device="cuda" if backend == "nccl" else "cpu")
+        got = [torch.zeros_like(mine) for _ in range(n)]
+        dist.all_gather(got, mine)
+        dt_ranks = [float(t.item()) for t in got]
+        return max(dt_ranks), dt_ranks, n
+
+    # (before anything else runs: --full's extra steps change the model and the workspace)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, last_step_outputs(inner, B, step_loss(fb), sharded))
+    A = int(getattr(batches[0], "active_slices", 0)) or T      # slices the gather really reads
+    ms_what = ("ms_per_step = wall clock of the timed region (barrier to barrier, the optimizer's flush included) / steps: the "
+               "figure `value` is computed from")
+
+    def config_block(loss, live_row_frac):
+        return {"workload": "%s: SCORE full train step (fwd + bwd + dense TF-Adam), N=%d rows, T=%d, K=%d, "
+                            "D=%d, H=%d, Fu=%d, Fi=%d, per-GPU batch %d (global %d), keep_prob 0.8, "
+                            "%d distinct pre-staged batches, length=%d for every sample (slices >= length are "
+                            "masked by the model and skipped)" % (args.config, kw["feature_size"], T, K, D, kw["hidden_size"],
+                                                                Fu, Fi, B, B * world_size, len(batches), A),
+                "optimizer_state": ("fresh (best case): only rows touched during the run carry Adam moments"
+                                    if args.fresh_state else
+                                    "steady state: every table row carries Adam moments (live_row_frac 1.0), so dense "
+                                    "ApplyAdam owes every row an update every step"),
+                "table_optimizer": (("time-tiled ApplyAdam, window %d (include/score_hip.h: the zero-gradient update of a "
+                                     "row is applied when the row is next read, or once per window, in step order: "
+                                     "bit-identical to the per-step sweep, tests/test_gpu_adam_tiled.py; every update "
+                                     "still owed when the timed steps end is applied INSIDE the timed region); "
+                                     "value_dense_adam_sweep is the same run with the per-step sweep") % inner.adam_window
+                                    if tiled else "dense ApplyAdam sweep over the live rows every step"),
+                "live_row_frac": live_row_frac,
+                "table": "row-sharded row%%G over %d GPU(s)" % world_size if world_size > 1 else "single GPU",
+                "final_loss": loss}
+
+    def finish():
+        if hb is not None:
+            hb.stop()
+        if dist is not None:
+            dist.destroy_process_group()
+
+    if not args.full:
+        tiled = tiled and bool(inner._tiled_on())
+        dt, dt_ranks, ranks_seen = max_over_ranks(dt)
+        if rank != 0:
+            finish()
+            return
+        loss = step_loss(fb)
+        live_row_frac = int((inner.table_flags > 0).sum().item()) / float(inner.table.shape[0])
+        finish()
+        print_line({
+            "metric": "train samples/sec @ batch=1024",
+            "value": B * world_size * args.steps / dt,
+            "unit": "samples/s",
+            "n_gpus": world_size,
+            "steps": args.steps,
+            "warmup": args.warmup,
+            "ms_per_step": dt / args.steps * 1e3,
+            "ms_per_step_what": ms_what + "; with several ranks, the slowest rank's",
+            "ms_per_step_ranks": {"min": min(dt_ranks) / args.steps * 1e3, "max": max(dt_ranks) / args.steps * 1e3},
+            "rccl_ranks": ranks_seen if (dist is not None and backend == "nccl") else 0,
+            "higher_is_better": True,
+            "scaling": "strong" if strong else "weak",
+            "vs_baseline": None,
+            "dtype": "f32",
+            "data": "synthetic",
+            "launch": "one captured hipGraph per step (SCOREBASE.enable_graph)" if args.graph else "eager launches",
+            "config": config_block(loss, live_row_frac),
+            "measured": "headline only (set-up, warm-up, the timed steps); --full adds the per-step distribution, stage table, "
+                        "synchronous-train leg, side measurements, rooflines, CPU baselines and small-shape legs"})
+        return
+
     steps_by_events_ms = step_marks[0].elapsed_time(step_marks[args.steps])
     if mark_every_step:
         per_step_ms = [step_marks[i].elapsed_time(step_marks[i + 1]) for i in range(args.steps)]
@@ -758,16 +887,7 @@ def main():
     else:
         gather_ms = [v[0][0].elapsed_time(v[0][1]) for v in events.values()]
     model.enable_stage_events(False)
-    dt_ranks = [dt]
-    ranks_seen = 1
-    if dist is not None:
-        # the step time of record is the MAX over ranks; every rank's own time rides in the same all_gather
-        ranks_seen = dist.get_world_size()
-        mine = torch.tensor([dt], dtype=torch.float64, device="cuda" if backend == "nccl" else "cpu")
-        got = [torch.zeros_like(mine) for _ in range(ranks_seen)]
-        dist.all_gather(got, mine)
-        dt_ranks = [float(t.item()) for t in got]
-        dt = max(dt_ranks)
+    dt, dt_ranks, ranks_seen = max_over_ranks(dt)
     coll_table = None
     if dist is not None and hasattr(getattr(model, "comm", None), "timing_summary"):
         mine_t = {k: {kk: round(vv, 4) for kk, vv in v.items()} for k, v in model.comm.timing_summary().items()}
@@ -776,10 +896,7 @@ def main():
             dist.all_gather_object(coll_table, mine_t)
         else:
             coll_table = [mine_t]
-    if sharded:
-        loss = float((fb[0][1] + args.reg_lambda * fb[0][2]).item())
-    else:
-        loss = float(fb[1][fb[0].loss].item())
+    loss = step_loss(fb)
 
     ev_sets = list(events.values())
 
@@ -805,7 +922,6 @@ def main():
             except Exception:
                 pass
         stages["adam_catchup_batch_rows"] = float(np.mean(vals)) if vals else None
-    A = int(getattr(batches[0], "active_slices", 0)) or T      # slices the gather really reads
     ev_overhead_ms = event_pair_overhead_ms()
     ab, R = alg_bytes_per_sample(A, K, D, Fu, Fi)
     ab_full, _ = alg_bytes_per_sample(T, K, D, Fu, Fi)
@@ -1007,10 +1123,7 @@ def main():
             side["ingestion"] = {"error": repr(e)}
 
     if rank != 0:
-        if hb is not None:
-            hb.stop()
-        if dist is not None:
-            dist.destroy_process_group()
+        finish()
         return
     beat("report")
     try:
@@ -1071,8 +1184,7 @@ def main():
         "ms_per_step_p10_p90": [float(np.percentile(per_step_ms, 10)), float(np.percentile(per_step_ms, 90))],
         "timed_region_ms": {"wall": dt * 1e3, "steps_by_events": steps_by_events_ms, "optimizer_flush_by_events": flush_ms,
                             "first_steps_of_the_marked_stretch": [round(x, 4) for x in per_step_ms[:6]]},
-        "ms_per_step_what": "ms_per_step = wall clock of the timed region (barrier to barrier, the optimizer's flush included) "
-                            "/ steps: the figure `value` is computed from.  p50 / p10 / p90: per-step durations, " + p50_what + " (rank 0)",
+        "ms_per_step_what": ms_what + ".  p50 / p10 / p90: per-step durations, " + p50_what + " (rank 0)",
         "value_sync_train": B * world_size * n_sync / dt_sync,
         "value_sync_train_what": "the reference's own call, one after the other: loss = model.train(sess, batch_data, lr, "
                                  "reg_lambda) (score.py:101-116) with its per-step loss read-back, %d steps on the same "
@@ -1097,24 +1209,7 @@ def main():
                   "vectors and TensorFlow cannot run here, so the oracle itself is unpinned (DESIGN.md section 2)",
         "launch": ("one captured hipGraph per step (SCOREBASE.enable_graph); stages_ms from eager steps outside the timed loop"
                    if args.graph else "eager launches"),
-        "config": {"workload": "%s: SCORE full train step (fwd + bwd + dense TF-Adam), N=%d rows, T=%d, K=%d, "
-                               "D=%d, H=%d, Fu=%d, Fi=%d, per-GPU batch %d (global %d), keep_prob 0.8, "
-                               "%d distinct pre-staged batches, length=%d for every sample (slices >= length are "
-                               "masked by the model and skipped)" % (args.config, N, T, K, D, kw["hidden_size"], Fu, Fi,
-                                                                   B, B * world_size, len(batches), A),
-                   "optimizer_state": ("fresh (best case): only rows touched during the run carry Adam moments"
-                                       if args.fresh_state else
-                                       "steady state: every table row carries Adam moments (live_row_frac 1.0), so dense "
-                                       "ApplyAdam owes every row an update every step"),
-                   "table_optimizer": (("time-tiled ApplyAdam, window %d (include/score_hip.h: the zero-gradient update of a "
-                                        "row is applied when the row is next read, or once per window, in step order: "
-                                        "bit-identical to the per-step sweep, tests/test_gpu_adam_tiled.py; every update "
-                                        "still owed when the timed steps end is applied INSIDE the timed region); "
-                                        "value_dense_adam_sweep is the same run with the per-step sweep") % inner.adam_window
-                                       if tiled else "dense ApplyAdam sweep over the live rows every step"),
-                   "live_row_frac": headline_live_frac,
-                   "table": "row-sharded row%%G over %d GPU(s)" % world_size if world_size > 1 else "single GPU",
-                   "final_loss": loss},
+        "config": config_block(loss, headline_live_frac),
         "roofline": roofline,
         "roofline_bench_workload": bench_block,
         "roofline_other": {
@@ -1175,13 +1270,14 @@ def main():
                                                                        budget_s=8.0, max_steps=3)
     else:
         out["cpu_baseline"] = None
-    if hb is not None:
-        hb.stop()
-    if dist is not None:
-        dist.destroy_process_group()
+    finish()
     if small is not None:
         # LAST key of the line: the driver's record keeps the line's last 2,000 characters
         out["small_shapes"] = small
+    print_line(out)
+
+
+def print_line(out):
     # RCCL prints its version banner through C stdio: flush it first so the JSON is the LAST line
     try:
         import ctypes

@@ -6,9 +6,14 @@ vectors of its own, so these fixtures are produced from THIS repo's CPU
 restatement (oracle/score_oracle.py, Oracle B fp32, cross-checked here against
 the literal fp64 Oracle A).  Parity is therefore "unpinned" by the reference.
 
-Run:  python tests/golden/make_golden.py     (CPU, ~1 min; needs no GPU)
+Run:  python tests/golden/make_golden.py [g1] [g3] [g2]     (CPU, ~1 min; needs no GPU; default: all three)
+
+The vectors are computed in tests/helpers.py's reproducible mode (MKL_CBWR=COMPATIBLE, one thread, IEEE sqrt in
+TFAdam): the bits the tests pin are then the same on every x86 host.  Without that environment the script runs itself
+again in a child process that has it.
 """
 import os
+import subprocess
 import sys
 
 import numpy as np
@@ -16,8 +21,10 @@ import torch
 
 ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "tests"))
 from oracle import score_oracle as so          # noqa: E402
 from score_amd.synth import make_world         # noqa: E402
+import helpers                                 # noqa: E402
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 NAMES = ("user_1hop", "user_2hop", "item_1hop", "item_2hop",
@@ -146,6 +153,9 @@ def g2():
 
 
 if __name__ == "__main__":
-    g1()
-    g3()
-    g2()
+    if any(os.environ.get(k) != v for k, v in helpers.REPRODUCIBLE_ENV.items()):
+        sys.exit(subprocess.call([sys.executable, os.path.abspath(__file__)] + sys.argv[1:],
+                                 env=dict(os.environ, **helpers.REPRODUCIBLE_ENV)))
+    helpers.reproducible_mode()
+    for name in sys.argv[1:] or ["g1", "g3", "g2"]:
+        {"g1": g1, "g3": g3, "g2": g2}[name]()

@@ -1,11 +1,39 @@
 """Shared test helpers: golden loading, oracle config construction."""
 import os
+import subprocess
+import sys
 
 import numpy as np
 
 from oracle import score_oracle as so
 
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
+
+# The oracle is torch on the CPU, and the float32 results of torch's CPU kernels depend on the host: MKL picks its GEMM and
+# vector-math code by CPU vendor and instruction set, so an Intel and an AMD host differ in the last bits of the same call.
+# What the G1 / G3 goldens pin bit for bit is therefore computed -- by tests/golden/make_golden.py and by the tests that
+# reproduce it -- in a process that fixes that choice before MKL's first call: MKL's conditional numerical reproducibility
+# mode, one thread.  There TFAdam's square root is also the IEEE one its ApplyAdam restatement stands for (torch takes a
+# float32 sqrt through MKL's vector math, which does not round it correctly on every host).
+REPRODUCIBLE_ENV = {"MKL_CBWR": "COMPATIBLE", "MKL_NUM_THREADS": "1", "OMP_NUM_THREADS": "1"}
+
+
+def reproducible_mode():
+    """First thing in a process started with REPRODUCIBLE_ENV (run_reproducibly, tests/golden/make_golden.py)."""
+    import torch
+    assert all(os.environ.get(k) == v for k, v in REPRODUCIBLE_ENV.items()), "start the process with REPRODUCIBLE_ENV"
+    torch.set_num_threads(1)
+    torch.sqrt = lambda x: torch.from_numpy(np.sqrt(x.numpy()))       # (TFAdam's only torch.sqrt: IEEE, as ApplyAdam)
+
+
+def run_reproducibly(code, timeout=600):
+    """Run `code` in a fresh interpreter in reproducible_mode(), with tests/ and the repository on its path."""
+    here = os.path.dirname(os.path.abspath(__file__))
+    prelude = ("import sys\nsys.path[:0] = [%r, %r]\nimport helpers\nhelpers.reproducible_mode()\n"
+               % (here, os.path.dirname(here)))
+    out = subprocess.run([sys.executable] + (["-s"] if sys.flags.no_user_site else []) + ["-c", prelude + code],
+                         capture_output=True, text=True, timeout=timeout, env=dict(os.environ, **REPRODUCIBLE_ENV))
+    assert out.returncode == 0, out.stderr[-2000:]
 NAMES = ("user_1hop", "user_2hop", "item_1hop", "item_2hop",
          "target_user", "target_item", "label", "length")
 

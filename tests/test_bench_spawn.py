@@ -51,3 +51,19 @@ def test_visible_gpus_counts_without_hip(tmp_path, monkeypatch):
     # this container has no KFD driver: no device can be opened, whatever the environment says
     if not os.path.isdir("/sys/class/kfd/kfd/topology/nodes"):
         assert bench.visible_gpus() == 0
+
+
+def test_full_and_dump_outputs_are_options():
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--help"], capture_output=True, text=True,
+                         timeout=300, cwd=ROOT)
+    assert out.returncode == 0 and "--full" in out.stdout and "--dump-outputs DIR" in out.stdout, out.stderr[-500:]
+
+
+def test_dump_outputs_writes_float32_npy(tmp_path):
+    sys.path.insert(0, ROOT)
+    import numpy as np
+    import bench
+    bench.dump_outputs(str(tmp_path / "d"), {"loss": np.asarray([0.5], dtype=np.float64), "y_pred": np.arange(4.0)})
+    assert sorted(p.name for p in (tmp_path / "d").iterdir()) == ["loss.npy", "y_pred.npy"]
+    y = np.load(tmp_path / "d" / "y_pred.npy")
+    assert y.dtype == np.float32 and y.tolist() == [0.0, 1.0, 2.0, 3.0]

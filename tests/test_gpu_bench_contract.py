@@ -1,10 +1,12 @@
-"""bench.py's output contract: ONE JSON line with the driver's keys, the `roofline` and `cpu_baseline` objects, and the
-round-2 companions of the steady-state headline (a short run; the CPU leg is bounded by its own budget)."""
+"""bench.py's output contract: ONE JSON line with the driver's keys; with --full also the `roofline` and `cpu_baseline`
+objects and the round-2 companions of the steady-state headline (a short run; the CPU leg is bounded by its own budget);
+without it the headline alone, and --dump-outputs writes what the last timed step computed."""
 import json
 import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 pytestmark = pytest.mark.gpu
@@ -20,7 +22,7 @@ def _run(*args, **env):
 
 
 def test_default_line_carries_the_contract():
-    j = _run("--steps", "12", "--warmup", "3", "--config", "cfg2", "--probe-rows", "2000000")
+    j = _run("--full", "--steps", "12", "--warmup", "3", "--config", "cfg2", "--probe-rows", "2000000")
     for k, v in (("metric", "train samples/sec @ batch=1024"), ("unit", "samples/s"), ("n_gpus", 1), ("steps", 12), ("warmup", 3),
                  ("higher_is_better", True), ("scaling", "weak"), ("vs_baseline", None), ("dtype", "f32"), ("data", "synthetic")):
         assert j[k] == v, (k, j[k])
@@ -56,7 +58,7 @@ def test_default_line_carries_the_contract():
 def test_cfg3_line_carries_the_panel_gemm_block():
     # the headline workload: the GRU input projections run as whole-N panels (csrc/gemm_panel.hip); the line prices the
     # kernel against the dense bf16 matrix peak, measured alone through the C-ABI op on operands of the workload's shape
-    j = _run("--steps", "10", "--warmup", "3", "--no-cpu-baseline", "--probe-rows", "2000000")
+    j = _run("--full", "--steps", "10", "--warmup", "3", "--no-cpu-baseline", "--probe-rows", "2000000")
     gp = j["roofline_other"]["gru input projections (gemm_panel_kernel)"]
     assert gp["bound"] == "mfma" and gp["unit"] == "TFLOP/s" and gp["peak"] == 2500.0 and 0 < gp["frac"] <= 1.0
     assert abs(gp["frac"] - gp["achieved"] / gp["peak"]) < 1e-9 and abs(gp["achieved"] - 6 * gp["fp32_equivalent_tflops"]) < 1e-6 * gp["achieved"]
@@ -65,23 +67,55 @@ def test_cfg3_line_carries_the_panel_gemm_block():
 
 
 def test_flags_change_what_they_say():
-    j = _run("--steps", "6", "--warmup", "2", "--config", "cfg2", "--no-cpu-baseline", "--no-side", "--fresh-state")
+    j = _run("--full", "--steps", "6", "--warmup", "2", "--config", "cfg2", "--no-cpu-baseline", "--no-side", "--fresh-state")
     assert j["cpu_baseline"] is None and "value_best_case" not in j and j["config"]["live_row_frac"] < 1.0
-    j = _run("--steps", "6", "--warmup", "2", "--config", "cfg2", "--no-cpu-baseline", "--no-side", "--graph")
+    j = _run("--full", "--steps", "6", "--warmup", "2", "--config", "cfg2", "--no-cpu-baseline", "--no-side", "--graph")
     assert j["launch"].startswith("one captured hipGraph") and j["value"] > 0
-    j = _run("--steps", "4", "--warmup", "1", "--config", "cfg2", "--no-cpu-baseline", "--force-sharded", "--global-batch", "256")
+    j = _run("--full", "--steps", "4", "--warmup", "1", "--config", "cfg2", "--no-cpu-baseline", "--force-sharded", "--global-batch", "256")
     assert j["scaling"] == "strong" and j["n_gpus"] == 1 and "value_best_case" not in j
 
 
 def test_time_tiled_optimizer_line():
     """the headline's table optimizer (on by default from 256 MB of sweep traffic; forced here on the small shape) and
     the per-step sweep it replaces, timed in the same process"""
-    j = _run("--steps", "20", "--warmup", "3", "--config", "cfg2", "--no-cpu-baseline", SCORE_ADAM_TILED_MIN_BYTES="0")
+    j = _run("--full", "--steps", "20", "--warmup", "3", "--config", "cfg2", "--no-cpu-baseline", SCORE_ADAM_TILED_MIN_BYTES="0")
     assert j["config"]["table_optimizer"].startswith("time-tiled ApplyAdam, window 24")
     assert j["value_dense_adam_sweep"] > 0 and j["stages_ms"]["adam_catchup_batch_rows"] > 0
     assert any(k.startswith("adam_touched") for k in j["roofline_other"])
-    j = _run("--steps", "6", "--warmup", "2", "--config", "cfg2", "--no-cpu-baseline", "--no-side", SCORE_ADAM_WINDOW="0")
+    j = _run("--full", "--steps", "6", "--warmup", "2", "--config", "cfg2", "--no-cpu-baseline", "--no-side", SCORE_ADAM_WINDOW="0")
     assert j["config"]["table_optimizer"].startswith("dense ApplyAdam sweep") and "adam_catchup_batch_rows" not in j["stages_ms"]
+
+
+
+def test_plain_line_is_the_headline_and_dumps_the_last_step(tmp_path):
+    """no --full: set-up, warm-up, the timed steps and the line -- the headline keys, nothing measured beside them.
+    --dump-outputs: the last timed step's loss, predictions, dense variables and a fixed sample of table rows as float32
+    .npy files; a second run with the same arguments has the same inputs and computes the same"""
+    args = ("--steps", "7", "--warmup", "2", "--config", "cfg2")
+    j = _run(*args, "--dump-outputs", str(tmp_path / "a"))
+    for k, v in (("metric", "train samples/sec @ batch=1024"), ("unit", "samples/s"), ("n_gpus", 1), ("steps", 7), ("warmup", 2),
+                 ("higher_is_better", True), ("scaling", "weak"), ("dtype", "f32"), ("data", "synthetic")):
+        assert j[k] == v, (k, j[k])
+    assert j["value"] > 0 and abs(j["value"] - 256 / (j["ms_per_step"] * 1e-3)) < 1e-6 * j["value"]
+    assert j["config"]["workload"].startswith("cfg2") and j["config"]["live_row_frac"] == 1.0
+    for k in ("roofline", "roofline_bench_workload", "cpu_baseline", "stages_ms", "ms_per_step_p50", "value_sync_train",
+              "value_best_case", "ingestion", "small_shapes"):
+        assert k not in j, k
+    _run(*args, "--dump-outputs", str(tmp_path / "b"))
+    names = {"loss": (1,), "y_pred": (256,), "dense_params": None, "table_rows_sample": (8192, 16)}
+    assert sorted(p.name for p in (tmp_path / "a").iterdir()) == sorted(n + ".npy" for n in names)
+    total = 0
+    for n, shape in names.items():
+        a, b = np.load(tmp_path / "a" / (n + ".npy")), np.load(tmp_path / "b" / (n + ".npy"))
+        assert a.dtype == np.float32 and (shape is None or a.shape == shape) and a.shape == b.shape, (n, a.dtype, a.shape)
+        assert np.isfinite(a).all(), n
+        assert np.allclose(a, b, rtol=1e-5, atol=1e-6), (n, float(np.abs(a.astype(np.float64) - b).max()))
+        total += a.nbytes
+    assert total < 64 << 20
+    y = np.load(tmp_path / "a" / "y_pred.npy")
+    assert ((y >= 0) & (y <= 1)).all()
+    loss = float(np.load(tmp_path / "a" / "loss.npy")[0])
+    assert abs(loss - j["config"]["final_loss"]) <= 1e-6 * max(1.0, abs(loss))
 
 
 def test_gpus_n_starts_its_own_ranks():
@@ -93,7 +127,7 @@ def test_gpus_n_starts_its_own_ranks():
     import torch
     if torch.cuda.device_count() < 2:
         assert out.returncode == 2 and "2 GPU" not in out.stdout and "GPU(s) visible" in out.stderr, out.stderr[-500:]
-    j = _run("--gpus", "2", "--steps", "4", "--warmup", "1", "--config", "cfg2", SCORE_BENCH_DEVICE="0", SCORE_DIST_BACKEND="gloo")
+    j = _run("--full", "--gpus", "2", "--steps", "4", "--warmup", "1", "--config", "cfg2", SCORE_BENCH_DEVICE="0", SCORE_DIST_BACKEND="gloo")
     assert j["n_gpus"] == 2 and j["dist"]["backend"] == "gloo" and j["dist"]["world_size"] == 2 and j["rccl_ranks"] == 0
     # the all-to-all form was settled at set-up, and every rank reports its collectives
     assert "gloo" in j["dist"]["a2a_probe"]["form"] and len(j["dist"]["collectives_ms"]) == 2
@@ -153,5 +187,5 @@ def test_one_rank_through_rccl_equals_unsharded():
         assert abs(x - y) <= 1e-6 * max(1.0, abs(x)), (j["unsharded"], j["sharded"])
     assert j["max_dpred"] < 1e-5 and j["max_dtable"] < 1e-5, j
     # and bench.py itself through that path says so in its line
-    b = _run("--steps", "6", "--warmup", "2", "--config", "cfg2", "--no-cpu-baseline", "--force-sharded")
+    b = _run("--full", "--steps", "6", "--warmup", "2", "--config", "cfg2", "--no-cpu-baseline", "--force-sharded")
     assert b["rccl_ranks"] == 1 and b["dist"]["backend"] == "nccl" and b["n_gpus"] == 1

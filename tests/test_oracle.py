@@ -5,7 +5,7 @@ import pytest
 import torch
 
 from oracle import score_oracle as so
-from helpers import load_golden, random_batch
+from helpers import load_golden, random_batch, run_reproducibly
 
 GOLD = ["g1_tiny_score", "g1_tiny_ria", "g1_tiny_rca", "g1_tiny_score_user", "g1_tiny_score_item", "g1_tiny_rrn",
         "g3_edge_f34_b3", "g3_edge_f11_b6", "g3_edge_f12_b2"]
@@ -78,17 +78,42 @@ def test_fd_gradients_fp64():
             assert abs(fd - an) < 1e-6 + 1e-4 * abs(fd), (name, fi, fd, an)
 
 
+@pytest.fixture(scope="module")
+def reproduced(tmp_path_factory):
+    """The oracle on the goldens' inputs in the mode they were made in (helpers.REPRODUCIBLE_ENV: the same bits on every
+    host): forward + gradients of every GOLD case, and TFAdam from g1_tiny_score's parameters -- one step with its stored
+    gradients, then one with zero gradients."""
+    path = str(tmp_path_factory.mktemp("oracle") / "reproduced.npz")
+    run_reproducibly(
+        "import numpy as np\n"
+        "from oracle import score_oracle as so\n"
+        "out = {}\n"
+        "for name in %r:\n"
+        "    cfg, P, b, z = helpers.load_golden(name)\n"
+        "    o, g = so.loss_and_grads(cfg, P, b, 5e-4 if name.startswith('g1') else 1e-4)\n"
+        "    out[name + '|logit'] = o['logit'].detach().numpy()\n"
+        "    out.update({name + '|grad/' + k: v for k, v in g.items()})\n"
+        "cfg, P, b, z = helpers.load_golden('g1_tiny_score')\n"
+        "opt = so.TFAdam(P)\n"
+        "p = {k: v.copy() for k, v in P.items()}\n"
+        "opt.step(p, {k: z['grad/' + k] for k in P}, 1e-3)\n"
+        "out.update({'adam1|' + k: v.copy() for k, v in p.items()})\n"
+        "opt.step(p, {k: np.zeros_like(v) for k, v in P.items()}, 1e-3)\n"
+        "out.update({'adam2|' + k: v for k, v in p.items()})\n"
+        "np.savez(%r, **out)\n" % (GOLD, path))
+    return dict(np.load(path))
+
+
 @pytest.mark.parametrize("name", GOLD)
-def test_golden_reproduction(name):
+def test_golden_reproduction(name, reproduced):
     cfg, P, b, z = load_golden(name)
-    out, grads = so.loss_and_grads(cfg, P, b, 5e-4 if name.startswith("g1") else 1e-4)
-    assert np.array_equal(out["logit"].detach().numpy(), z["fwd/logit"])
-    for k in grads:
-        assert np.allclose(grads[k], z["grad/" + k], rtol=1e-6, atol=1e-8), k
+    assert np.array_equal(reproduced[name + "|logit"], z["fwd/logit"])
+    for k in P:
+        assert np.allclose(reproduced[name + "|grad/" + k], z["grad/" + k], rtol=1e-6, atol=1e-8), k
     assert np.all(z["grad/emb_mtx"][0] == 0)
 
 
-def test_tf_adam_dense_semantics():
+def test_tf_adam_dense_semantics(reproduced):
     # fact 4 / assumption 10: a row touched once keeps moving with zero gradient;
     # a never-touched row never moves; row 0 never moves.
     cfg, P, b, z = load_golden("g1_tiny_score")
@@ -97,17 +122,10 @@ def test_tf_adam_dense_semantics():
     assert len(never) > 0
     assert np.array_equal(z["step3/emb_mtx"][never], P["emb_mtx"][never])
     assert np.array_equal(z["step3/emb_mtx"][0], P["emb_mtx"][0])
-    params = {k: z["step1/" + k].copy() for k in P}
-    opt = so.TFAdam(P)
-    g1 = {k: z["grad/" + k] for k in P}
-    p2 = {k: v.copy() for k, v in P.items()}
-    opt.step(p2, g1, 1e-3)
+    # TFAdam one step from the stored gradients, then one with zero gradients (the `reproduced` fixture)
     for k in P:
-        assert np.array_equal(p2[k], params[k]), k
-    zero = {k: np.zeros_like(v) for k, v in P.items()}
-    before = p2["emb_mtx"].copy()
-    opt.step(p2, zero, 1e-3)
-    moved = np.abs(p2["emb_mtx"] - before).sum(axis=1) > 0
+        assert np.array_equal(reproduced["adam1|" + k], z["step1/" + k]), k
+    moved = np.abs(reproduced["adam2|emb_mtx"] - reproduced["adam1|emb_mtx"]).sum(axis=1) > 0
     t = touched[touched != 0]
     assert moved[t].all() and not moved[never].any() and not moved[0]
 

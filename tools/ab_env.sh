@@ -5,7 +5,7 @@ cd $GRAFT_REPO_ROOT
 for i in $(seq 1 $N); do
   for mode in base switch; do
     if [ $mode = switch ]; then export $V; else unset ${V%%=*}; fi
-    python3 bench.py --no-cpu-baseline --no-side "$@" 2>/dev/null | tail -1 | python3 -c "
+    python3 bench.py --full --no-cpu-baseline --no-side "$@" 2>/dev/null | tail -1 | python3 -c "
 import json,sys; j=json.loads(sys.stdin.read()); print('$mode', round(j['value']), round(j['ms_per_step'],4), {k:round(v,3) for k,v in j['stages_ms'].items() if v})"
   done
 done

@@ -3,7 +3,7 @@
 #   tools/kernel_timeline.sh <outdir-under-gpurun_out> <bench args...>
 R=$GRAFT_REPO_ROOT; O=$R/gpurun_out/$1; shift
 mkdir -p $O; cd /tmp; export TMPDIR=/tmp
-rocprofv3 --kernel-trace --output-format csv -d $O/tr -- python3 $R/bench.py --no-cpu-baseline --no-side --steps 40 --warmup 10 "$@" > $O/run.log 2>&1
+rocprofv3 --kernel-trace --output-format csv -d $O/tr -- python3 $R/bench.py --full --no-cpu-baseline --no-side --steps 40 --warmup 10 "$@" > $O/run.log 2>&1
 find $O -name "*.db" -delete
 python3 - $O <<'PY'
 import csv, glob, sys

@@ -8,7 +8,7 @@ bargs=$1; shift
 for ctr in "$@"; do
   d=/tmp/pmck_$(echo $ctr | tr ' ' '_' | cut -c1-60)
   rm -rf $d
-  rocprofv3 --pmc $ctr --kernel-trace --output-format csv -d $d -- python3 bench.py --no-cpu-baseline --no-side $bargs > /tmp/pmck.log 2>&1
+  rocprofv3 --pmc $ctr --kernel-trace --output-format csv -d $d -- python3 bench.py --full --no-cpu-baseline --no-side $bargs > /tmp/pmck.log 2>&1
   f=$(find $d -name "*counter_collection.csv" | head -1)
   if [ -n "$f" ]; then
     python3 - "$f" "$pat" <<'PY'

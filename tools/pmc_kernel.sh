@@ -6,7 +6,7 @@ pat=$1; shift
 for ctr in "$@"; do
   d=/tmp/pmck_$(echo $ctr | tr ' ' '_')
   rm -rf $d
-  rocprofv3 --pmc $ctr --kernel-trace --output-format csv -d $d -- python3 bench.py --steps 4 --warmup 2 --no-cpu-baseline > /tmp/pmck.log 2>&1
+  rocprofv3 --pmc $ctr --kernel-trace --output-format csv -d $d -- python3 bench.py --full --steps 4 --warmup 2 --no-cpu-baseline > /tmp/pmck.log 2>&1
   f=$(find $d -name "*counter_collection.csv" | head -1)
   if [ -n "$f" ]; then
     python3 - "$f" "$pat" <<'PY'
