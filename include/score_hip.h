@@ -68,7 +68,11 @@ typedef struct {
 /* model_type values (train_score.py:170-179 selects the class by name) */
 enum { SCORE_MODEL_SCORE = 0, SCORE_MODEL_RIA = 1, SCORE_MODEL_RCA = 2,
        SCORE_MODEL_SCORE_USER = 3, SCORE_MODEL_SCORE_ITEM = 4,
-       SCORE_MODEL_RRN = 5 /* slice_models/slice_model.py:155-174: summed 1-hop sets -> GRUs -> head */ };
+       SCORE_MODEL_RRN = 5 /* slice_models/slice_model.py:155-174: summed 1-hop sets -> GRUs -> head */,
+       /* slice_models/slice_model.py:177-203: summed 1-hop sets -> two relu denses per side -> GRUs -> bilinear two-way
+        * softmax of the final states.  Its arithmetic reads user_1hop and item_1hop only; the other four index tensors are
+        * still read and checked for ids outside the table (their rows get a zero gradient), as for RRN. */
+       SCORE_MODEL_GCMC = 6 };
 
 /* Constructor arguments of SCOREBASE.__init__ (score.py:12-13). */
 typedef struct {

@@ -1,6 +1,6 @@
 // Whole-path orchestration: parameter/workspace layout and the forward / backward
-// launch sequences of SCORE and its ablations (score.py:188-369) on one stream.
-// Host code only; every kernel lives in embed/gemm/gru/head.hip.
+// launch sequences of SCORE and its ablations (score.py:188-369) and of the slice baselines RRN and GCMC
+// (slice_model.py:155-203) on one stream.  Host code only; every kernel lives in embed/gemm/gru/head/gcmc.hip.
 #include <string.h>
 #include <stdlib.h>
 #include <stdio.h>
@@ -20,8 +20,8 @@ struct Dims {
   int64_t N;
   int D, H, T, K, Fu, Fi, mt;
   int Du, Di, I, Dq, NI, Dk, Dhead, nstate;
-  int Is[2];       // GRU input width per side (user, item): I, except RRN (its 1-hop sums only)
-  bool coattn, attn;
+  int Is[2];       // GRU input width per side (user, item): I, except RRN / GCMC (their 1-hop sums only)
+  bool coattn, attn, gcmc;
   int off_u, off_i, off_ti, off_tu;  // columns of head_inp
 };
 
@@ -30,16 +30,18 @@ int make_dims(const score_config_t* c, Dims* d) {
   d->N = c->feature_size; d->D = c->eb_dim; d->H = c->hidden_size; d->T = c->max_time_len;
   d->K = c->obj_per_time_slice; d->Fu = c->user_fnum; d->Fi = c->item_fnum; d->mt = c->model_type;
   if (d->N <= 0 || d->D <= 0 || (d->D & 3) || d->D > 256 || d->H <= 0 || d->T <= 0 || d->K <= 0 || d->K > 32 ||
-      d->Fu <= 0 || d->Fi <= 0 || d->mt < 0 || d->mt > SCORE_MODEL_RRN)
+      d->Fu <= 0 || d->Fi <= 0 || d->mt < 0 || d->mt > SCORE_MODEL_GCMC)
     return SCORE_E_SHAPE;
   d->Du = d->Fu * d->D; d->Di = d->Fi * d->D; d->I = d->Di + d->Du; d->Dq = d->Du + d->Di;
-  const bool rrn = d->mt == SCORE_MODEL_RRN;
+  d->gcmc = d->mt == SCORE_MODEL_GCMC;
+  const bool rrn = d->mt == SCORE_MODEL_RRN || d->gcmc;      // (GCMC starts from RRN's two 1-hop sums, slice_model.py:184-187)
   d->coattn = d->mt != SCORE_MODEL_RCA && !rrn;
   d->attn = d->mt != SCORE_MODEL_RIA && !rrn;
   d->NI = (d->mt == SCORE_MODEL_RCA || d->mt == SCORE_MODEL_RIA || rrn) ? 0 : 4 * d->K;
   // RRN (slice_model.py:159-160): user side = sum_k user_1hop (item features), item side = sum_k item_1hop
   d->Is[0] = rrn ? d->Di : d->I;
   d->Is[1] = rrn ? d->Du : d->I;
+  if (d->gcmc && d->H > 256) return SCORE_E_SHAPE;            // (its head kernels, gcmc.hip)
   d->Dk = d->attn ? 2 * d->H + d->NI : 0;
   d->nstate = (d->mt == SCORE_MODEL_SCORE_USER || d->mt == SCORE_MODEL_SCORE_ITEM) ? 1 : 2;
   d->Dhead = d->nstate * d->H + d->Di + d->Du;
@@ -49,6 +51,9 @@ int make_dims(const score_config_t* c, Dims* d) {
   d->off_tu = d->off_ti + d->Di;
   return 0;
 }
+
+// the GRUs' input rows of side sd and their stride: the [B*T, I] gather output, or GCMC's Z = relu(relu(S Wa) Wc) [B*T, Dx]
+static inline int x_ld(const Dims& d, int sd) { return d.gcmc ? d.Is[sd] : d.I; }
 
 // time slices actually computed for a batch (score_batch_t.active_slices): every [B*T, .] activation of the
 // pass is laid out [B * TA, .]; the workspace regions keep their full-T sizes and offsets
@@ -65,6 +70,7 @@ struct Params {  // float offsets into the flat buffer
   int64_t gk[2], gb[2], ck[2], cb[2];  // gates/candidate kernel/bias per GRU (0 user side, 1 item side)
   int64_t at_w[4], at_b[4];
   int64_t bn_g, bn_b, fc_w[3], fc_b[3];
+  int64_t gm_a[2], gm_c[2], gm_4, gm_5;  // GCMC: per side dense (Wa) and dense_2 / dense_3 (Wc); the head's dense_4, dense_5
   int64_t n_floats, n_reg;
 };
 
@@ -86,7 +92,14 @@ int build_layout_raw(const Dims& d, score_param_entry_t* out, int max_entries, P
     add(k, i, o, 1, 2); add(bb, o, 0, 0, 0);
   };
   if (d.coattn) { dense(3 * d.Di, 1); dense(3 * d.Du, 1); }
+  // GCMC (slice_model.py:182-201): dense .. dense_3 (per-side relu denses, no bias), gru1 / gru2, dense_4 / dense_5 (the head)
+  const int Dx[2] = {d.Di, d.Du};
+  if (d.gcmc) {
+    add("dense/kernel", Dx[0], Dx[0], 1, 2); add("dense_1/kernel", Dx[1], Dx[1], 1, 2);
+    add("dense_2/kernel", Dx[0], Dx[0], 1, 2); add("dense_3/kernel", Dx[1], Dx[1], 1, 2);
+  }
   const char* sides[2] = {"gru_user_side", "gru_item_side"};
+  if (d.gcmc) { sides[0] = "gru1"; sides[1] = "gru2"; }
   for (int s = 0; s < 2; ++s) {
     char b[64];
     snprintf(b, 64, "%s/gru_cell/gates/kernel", sides[s]); add(b, d.Is[s] + d.H, 2 * d.H, 1, 2);
@@ -95,11 +108,15 @@ int build_layout_raw(const Dims& d, score_param_entry_t* out, int max_entries, P
     snprintf(b, 64, "%s/gru_cell/candidate/bias", sides[s]); add(b, d.H, 0, 0, 0);
   }
   if (d.attn) { dense(d.Dq, d.Dk); dense(4 * d.Dk, AT1); dense(AT1, AT2); dense(AT2, 1); }
-  add("bn1/gamma", d.Dhead, 0, 1, 1);
-  add("bn1/beta", d.Dhead, 0, 1, 0);
-  add("fc1/kernel", d.Dhead, FC1, 1, 2); add("fc1/bias", FC1, 0, 0, 0);
-  add("fc2/kernel", FC1, FC2, 1, 2); add("fc2/bias", FC2, 0, 0, 0);
-  add("fc3/kernel", FC2, 1, 1, 2); add("fc3/bias", 1, 0, 0, 0);
+  if (d.gcmc) {
+    add("dense_4/kernel", d.H, d.H, 1, 2); add("dense_5/kernel", d.H, d.H, 1, 2);
+  } else {
+    add("bn1/gamma", d.Dhead, 0, 1, 1);
+    add("bn1/beta", d.Dhead, 0, 1, 0);
+    add("fc1/kernel", d.Dhead, FC1, 1, 2); add("fc1/bias", FC1, 0, 0, 0);
+    add("fc2/kernel", FC1, FC2, 1, 2); add("fc2/bias", FC2, 0, 0, 0);
+    add("fc3/kernel", FC2, 1, 1, 2); add("fc3/bias", 1, 0, 0, 0);
+  }
   // offsets: regularised tensors first, then the rest; every tensor 16-B aligned.  The
   // regularised region is padded with zeros that stay zero (zero grad, zero l2 term).
   int64_t off[32];
@@ -125,8 +142,15 @@ int build_layout_raw(const Dims& d, score_param_entry_t* out, int max_entries, P
   }
   int i = 0;
   if (d.coattn) { for (int c = 0; c < 2; ++c) { P->ca_w[c] = off[i++]; P->ca_b[c] = off[i++]; } }
+  if (d.gcmc) { P->gm_a[0] = off[i++]; P->gm_a[1] = off[i++]; P->gm_c[0] = off[i++]; P->gm_c[1] = off[i++]; }
   for (int s = 0; s < 2; ++s) { P->gk[s] = off[i++]; P->gb[s] = off[i++]; P->ck[s] = off[i++]; P->cb[s] = off[i++]; }
   if (d.attn) { for (int a = 0; a < 4; ++a) { P->at_w[a] = off[i++]; P->at_b[a] = off[i++]; } }
+  if (d.gcmc) {
+    P->gm_4 = off[i++]; P->gm_5 = off[i++];
+    P->bn_g = P->bn_b = 0;
+    for (int f = 0; f < 3; ++f) P->fc_w[f] = P->fc_b[f] = 0;
+    return n;
+  }
   P->bn_g = off[i++]; P->bn_b = off[i++];
   for (int f = 0; f < 3; ++f) { P->fc_w[f] = off[i++]; P->fc_b[f] = off[i++]; }
   return n;
@@ -177,6 +201,9 @@ struct WS {
   int64_t ca_slab, ca_slab_floats, cs_part, cs_part_floats, wxcat;
   int64_t pimg_x[2], pimg_d[2];      // weight fragment images of the panel GEMMs (gemm_panel.hip): projection, input gradient
   int64_t psimg;                     // weight images of the per-sample whole-model kernels (persample.h)
+  // GCMC only (-1 otherwise): per side A = relu(S Wa), Z = relu(A Wc) and the gradients at their pre-activations, [B*T, Dx];
+  // the head's p = h_i W4 | n = h_i W5 [2][B, H], g = dL/da [B], and gpos = g h_u | gneg = -g h_u [2][B, H]
+  int64_t gcmc_a[2], gcmc_z[2], gcmc_dz[2], gcmc_da[2], gcmc_pn, gcmc_g, gcmc_gu;
   int64_t scratch_floats, total;
 };
 
@@ -293,6 +320,18 @@ void build_ws_raw(const Dims& d, int B, WS* w) {
     w->partial_floats = 2 * nw * d.D + 8 + 2 * nw;
   }
   w->partials = take(w->partial_floats);
+  // (at the end, and for GCMC only: the other model types' layouts stay what they were)
+  if (d.gcmc) {
+    const int Dx[2] = {d.Di, d.Du};
+    for (int s = 0; s < 2; ++s) {
+      w->gcmc_a[s] = take(BT * Dx[s]); w->gcmc_z[s] = take(BT * Dx[s]);
+      w->gcmc_dz[s] = take(BT * Dx[s]); w->gcmc_da[s] = take(BT * Dx[s]);
+    }
+    w->gcmc_pn = take(2 * (int64_t)B * d.H); w->gcmc_g = take(B); w->gcmc_gu = take(2 * (int64_t)B * d.H);
+  } else {
+    for (int s = 0; s < 2; ++s) w->gcmc_a[s] = w->gcmc_z[s] = w->gcmc_dz[s] = w->gcmc_da[s] = -1;
+    w->gcmc_pn = w->gcmc_g = w->gcmc_gu = -1;
+  }
   w->total = cur;
 }
 
@@ -512,9 +551,13 @@ extern "C" int score_workspace_field(const score_config_t* cfg, int32_t B, const
       {"dquery", w.dquery, -1}, {"dgru", w.dgru[0], w.dgru[1]}, {"dinfo", w.dinfo, -1}, {"dxproj", w.dxproj[0], w.dxproj[1]},
       {"rh", w.rh[0], w.rh[1]}, {"hprev", w.hprev[0], w.hprev[1]}, {"dxside", w.dxside[0], w.dxside[1]},
       {"dzsum", w.dzsum[0], w.dzsum[1]}, {"pcoef", w.pcoef[0], w.pcoef[1]}, {"dzcoef", w.dzcoef[0], w.dzcoef[1]},
-      {"dtgt", w.dtgt, -1}, {"S", w.S, -1}, {"ca_slab", w.ca_slab, -1}, {"psimg", w.psimg, -1}};
+      {"dtgt", w.dtgt, -1}, {"S", w.S, -1}, {"ca_slab", w.ca_slab, -1}, {"psimg", w.psimg, -1},
+      {"gcmc_a", w.gcmc_a[0], w.gcmc_a[1]}, {"gcmc_z", w.gcmc_z[0], w.gcmc_z[1]}, {"gcmc_dz", w.gcmc_dz[0], w.gcmc_dz[1]},
+      {"gcmc_da", w.gcmc_da[0], w.gcmc_da[1]}, {"gcmc_pn", w.gcmc_pn, w.gcmc_pn + (int64_t)B * d.H}, {"gcmc_g", w.gcmc_g, -1},
+      {"gcmc_gu", w.gcmc_gu, w.gcmc_gu + (int64_t)B * d.H}};
   for (auto& e : tab)
     if (strcmp(e.n, name) == 0) {
+      if (e.a < 0) return SCORE_E_BADARG;       // (a region of another model type)
       *offset = e.a;
       if (second) *second = e.b;
       return 0;
@@ -590,8 +633,9 @@ extern "C" int score_index_plan(const score_config_t* cfg, const score_state_t* 
 // streams' work is small beside these products: 20.3 -> 19.8 ms/step with both.
 static bool panel_gemms(const Dims& d, const score_state_t* st, int BT, int which) {
   if (st->gemm_mode != 1 || (st->debug_flags & 8) || d.Is[0] != d.Is[1]) return false;
+  if (which == 1 && d.gcmc) return false;      // (GCMC's input gradients take Z's relu mask in the epilogue: the tiled kernels)
   const int ns = panel_x_splits(d.H);
-  return which == 0 ? ns > 0 && score_gemm_panel_ok(2 * ns, BT, 3 * d.H / ns, d.Is[0], d.I, 3 * d.H, nullptr)
+  return which == 0 ? ns > 0 && score_gemm_panel_ok(2 * ns, BT, 3 * d.H / ns, d.Is[0], x_ld(d, 0), 3 * d.H, nullptr)
                     : ((st->debug_flags & 16) || (int64_t)BT >= 65536) && panel_d_splits(d.Is[0]) > 0 &&
                           score_gemm_panel_ok(2 * panel_d_splits(d.Is[0]), BT, d.Is[0] / panel_d_splits(d.Is[0]), 3 * d.H, 3 * d.H, d.I, nullptr);
 }
@@ -979,6 +1023,19 @@ extern "C" int score_forward(const score_config_t* cfg, const score_state_t* st,
   }
   if (st->gather_done_event) HIPTRY(hipEventRecord((hipEvent_t)st->gather_done_event, s));
   EV(1);
+  // GCMC (slice_model.py:182-190): per side A = relu(S Wa), Z = relu(A Wc), S the 1-hop sum the gather left in xside.  TF applies
+  // Wa to every neighbour and sums; summing first is the same by linearity, with K times fewer flops
+  const float* xin[2] = {ws + w.xside[0], ws + w.xside[1]};
+  if (d.gcmc) {
+    for (int sd = 0; sd < 2; ++sd) {
+      const int Dx = d.Is[sd];
+      G(gemm_mode_call(x3, 0, BT, Dx, Dx, ws + w.xside[sd], d.I, W + P.gm_a[sd], Dx, ws + w.gcmc_a[sd], Dx, nullptr, GF_RELU, 1.f,
+                       nullptr, 0, scratch, w.scratch_floats, s));
+      G(gemm_mode_call(x3, 0, BT, Dx, Dx, ws + w.gcmc_a[sd], Dx, W + P.gm_c[sd], Dx, ws + w.gcmc_z[sd], Dx, nullptr, GF_RELU, 1.f,
+                       nullptr, 0, scratch, w.scratch_floats, s));
+      xin[sd] = ws + w.gcmc_z[sd];
+    }
+  }
   // GRUs (:205-208): hoisted x-projection, then the persistent recurrence
   {
     GruArgs ga;
@@ -989,7 +1046,7 @@ extern "C" int score_forward(const score_config_t* cfg, const score_state_t* st,
     if (d.Is[0] == d.Is[1]) {    // both sides' projections in ONE grouped launch (each with its own bias row)
       const float* c0 = ws + w.wxcat;
       const float* c1 = c0 + (int64_t)(d.I + 1) * 3 * H;
-      const float* Ax[2] = {ws + w.xside[0], ws + w.xside[1]};
+      const float* Ax[2] = {xin[0], xin[1]};
       const float* Bx[2] = {c0, c1};
       float* Cx[2] = {ws + w.xproj[0], ws + w.xproj[1]};
       const float* bx[2] = {c0 + (int64_t)d.Is[0] * 3 * H, c1 + (int64_t)d.Is[1] * 3 * H};
@@ -1001,9 +1058,9 @@ extern "C" int score_forward(const score_config_t* cfg, const score_state_t* st,
           const int side = g / ns, h = g % ns;
           pg[g].A = Ax[side]; pg[g].img = ws + w.pimg_x[side] + h * per; pg[g].C = Cx[side] + h * Nh; pg[g].bias = bx[side] + h * Nh;
         }
-        G(score_gemm_panel(2 * ns, pg, BT, Nh, d.Is[0], d.I, 3 * H, s));
+        G(score_gemm_panel(2 * ns, pg, BT, Nh, d.Is[0], x_ld(d, 0), 3 * H, s));
       } else {
-        G(score_gemm_same_shape(0, 2, BT, 3 * H, d.Is[0], Ax, d.I, Bx, 3 * H, Cx, 3 * H, GF_BIAS, x3 != 0, scratch,
+        G(score_gemm_same_shape(0, 2, BT, 3 * H, d.Is[0], Ax, x_ld(d, 0), Bx, 3 * H, Cx, 3 * H, GF_BIAS, x3 != 0, scratch,
                                 w.scratch_floats, s, bx));
       }
     }
@@ -1012,7 +1069,7 @@ extern "C" int score_forward(const score_config_t* cfg, const score_state_t* st,
       // x . [Wx_gates | Wx_cand] + [b_gates | b_cand]: one GEMM per side on the concatenated copy
       const float* cat = ws + w.wxcat + (int64_t)sd * (d.I + 1) * 3 * H;
       if (d.Is[0] != d.Is[1])
-        G(gemm_mode_call(x3, 0, BT, 3 * H, d.Is[sd], ws + w.xside[sd], d.I, cat, 3 * H, xp, 3 * H, cat + (int64_t)d.Is[sd] * 3 * H,
+        G(gemm_mode_call(x3, 0, BT, 3 * H, d.Is[sd], xin[sd], x_ld(d, sd), cat, 3 * H, xp, 3 * H, cat + (int64_t)d.Is[sd] * 3 * H,
                          GF_BIAS, 1.f, nullptr, 0, scratch, w.scratch_floats, s));
       GruSide& g = ga.s[sd];
       g.xproj = xp; g.Wg = W + P.gk[sd] + (int64_t)d.Is[sd] * 2 * H; g.ldwg = 2 * H;
@@ -1052,7 +1109,7 @@ extern "C" int score_forward(const score_config_t* cfg, const score_state_t* st,
                                    d.off_u, d.off_i, s));
     }
     }     // (... else the separate launches above)
-  } else {
+  } else if (!d.gcmc) {
     // RIA: final GRU states feed the head (:244-249)
     G(score_launch_copy2d(B, H, ws + w.gru_final[0], H, ws + w.head_inp, d.Dhead, s));
     G(score_launch_copy2d(B, H, ws + w.gru_final[1], H, ws + w.head_inp + H, d.Dhead, s));
@@ -1063,6 +1120,22 @@ extern "C" int score_forward(const score_config_t* cfg, const score_state_t* st,
   const int dflag = keep_prob < 1.f ? GF_DROP : 0;
   const int Bg = st->global_batch > 0 ? st->global_batch : B;
   if (!d.attn) HIPTRY(hipStreamWaitEvent(s, sd->join, 0));     // (with attention the join was waited for there)
+  if (d.gcmc) {
+    // GCMC (:199-203): y = exp(a) / (exp(a) + exp(c)) of the final states, its log-loss term and dL/da (gcmc.hip); no dropout,
+    // keep_prob has no effect.  The loss reduction as behind the fused head
+    G(score_launch_gcmc_head_fwd(B, H, ws + w.gru_final[0], ws + w.gru_final[1], W + P.gm_4, W + P.gm_5, bt->label, ws + w.y_pred,
+                                 ws + w.lossb, ws + w.gcmc_pn, ws + w.gcmc_pn + (int64_t)B * H, ws + w.gcmc_g, Bg, s));
+    hipStream_t ls = s;
+    if (st->loss_done_event) {
+      HIPTRY(hipEventRecord(sd->fork, s));
+      HIPTRY(hipStreamWaitEvent(sd->st, sd->fork, 0));
+      ls = sd->st;
+    }
+    G(score_launch_loss_final(B, ws + w.lossb, ws + w.loss, reg_lambda, ws + w.part, Bg, ls, st->id_status));
+    if (st->loss_done_event) HIPTRY(hipEventRecord((hipEvent_t)st->loss_done_event, ls));
+    EV(4);
+    return 0;
+  }
   // the whole head in one launch (head_fused.hip); shapes it does not cover take the layer-by-layer path
   int hrc = !head_fused ? SCORE_E_SHAPE
                 : score_launch_head_fwd_fused(B, d.Dhead, FC1, FC2, ws + w.head_inp, W + P.bn_g, W + P.bn_b, rs, W + P.fc_w[0],
@@ -1150,36 +1223,45 @@ extern "C" int score_backward(const score_config_t* cfg, const score_state_t* st
   if (he != hipSuccess) return (int)he;
 
   EV(0);
-  // ---- head (score.py:68-81)
-  // fc3: dW = f2^T dlogit, db = sum dlogit, dz2 = [f2>0] dlogit w3 / keep
-  G(gemm_queue_add(&gq, FC2, 1, B, ws + w.f2, FC2, ws + w.dlogit, 1, gw + P.fc_w[2], 1));
-  G(colsum_queue_add(&cq, ws + w.dlogit, B, 1, 1, gw + P.fc_b[2], 0));
-  if (fl.head_unfused || !score_head_fwd_fused_fits(B, d.Dhead, FC1, FC2))     // (else score_forward's fused head wrote dz2)
-    G(score_launch_outer_relu_bwd(B, FC2, ws + w.dlogit, W + P.fc_w[2], ws + w.f2, keep_prob, ws + w.dz2, s));
-  // fc2
-  G(gemm_queue_add(&gq, FC1, FC2, B, ws + w.f1, FC1, ws + w.dz2, FC2, gw + P.fc_w[1], FC2));
-  G(colsum_queue_add(&cq, ws + w.dz2, B, FC2, FC2, gw + P.fc_b[1], 0));
-  const float rs = (float)(1.0 / sqrt(1.0 + 1e-3));
-  // dz1, d bn1, d head input and bn1's d gamma terms: one launch (head_fused.hip) ...
-  int hbrc = fl.head_unfused ? SCORE_E_SHAPE
-                 : score_launch_head_bwd_fused(B, d.Dhead, FC1, FC2, ws + w.dz2, W + P.fc_w[1], ws + w.f1, keep_prob,
-                                               W + P.fc_w[0], ws + w.head_inp, W + P.bn_g, rs, ws + w.dz1, ws + w.dbn,
-                                               ws + w.dhead, ws + w.dgstage, s);
-  if (hbrc != 0 && hbrc != SCORE_E_SHAPE) return hbrc;
-  if (hbrc == SCORE_E_SHAPE)      // ... or layer by layer
-    G(gemm_mode_call(x3, 1, B, FC1, FC2, ws + w.dz2, FC2, W + P.fc_w[1], FC2, ws + w.dz1, FC1, nullptr, GF_RELUGRAD, keep_prob,
-                     reinterpret_cast<const uint8_t*>(ws + w.f1), 0, scratch, SF, s));   // relu/dropout mask of fc1 in the epilogue
-  // fc1 + bn1
-  G(gemm_queue_add(&gq, d.Dhead, FC1, B, ws + w.bn, d.Dhead, ws + w.dz1, FC1, gw + P.fc_w[0], FC1));
-  G(colsum_queue_add(&cq, ws + w.dz1, B, FC1, FC1, gw + P.fc_b[0], 0));
-  if (hbrc == SCORE_E_SHAPE) {
-    G(gemm_mode_call(x3, 1, B, d.Dhead, FC1, ws + w.dz1, FC1, W + P.fc_w[0], FC1, ws + w.dbn, d.Dhead, nullptr, 0, 1.f,
-                 nullptr, 0, scratch, SF, s));
-    G(score_launch_bn_bwd(B, d.Dhead, ws + w.head_inp, W + P.bn_g, rs, ws + w.dbn, ws + w.dhead, gw + P.bn_g,
-                          gw + P.bn_b, ws + w.dgstage, scratch, SF, &cq, s));
-  } else {                        // (bn1's d gamma / d beta: column sums of what the fused kernel wrote)
-    G(colsum_queue_add(&cq, ws + w.dgstage, B, d.Dhead, d.Dhead, gw + P.bn_g, 0));
-    G(colsum_queue_add(&cq, ws + w.dbn, B, d.Dhead, d.Dhead, gw + P.bn_b, 0));
+  if (d.gcmc) {
+    // ---- GCMC's head (slice_model.py:199-201): dh_u, dh_i into dfinal, and the rows +-g h_u whose products with h_i are
+    // dW4 / dW5 (gcmc.hip)
+    G(score_launch_gcmc_head_bwd(B, H, ws + w.gru_final[0], W + P.gm_4, W + P.gm_5, ws + w.gcmc_pn, ws + w.gcmc_pn + (int64_t)B * H,
+                                 ws + w.gcmc_g, ws + w.dfinal[0], ws + w.dfinal[1], ws + w.gcmc_gu, ws + w.gcmc_gu + (int64_t)B * H, s));
+    G(gemm_queue_add(&gq, H, H, B, ws + w.gru_final[1], H, ws + w.gcmc_gu, H, gw + P.gm_4, H));
+    G(gemm_queue_add(&gq, H, H, B, ws + w.gru_final[1], H, ws + w.gcmc_gu + (int64_t)B * H, H, gw + P.gm_5, H));
+  } else {
+    // ---- head (score.py:68-81)
+    // fc3: dW = f2^T dlogit, db = sum dlogit, dz2 = [f2>0] dlogit w3 / keep
+    G(gemm_queue_add(&gq, FC2, 1, B, ws + w.f2, FC2, ws + w.dlogit, 1, gw + P.fc_w[2], 1));
+    G(colsum_queue_add(&cq, ws + w.dlogit, B, 1, 1, gw + P.fc_b[2], 0));
+    if (fl.head_unfused || !score_head_fwd_fused_fits(B, d.Dhead, FC1, FC2))     // (else score_forward's fused head wrote dz2)
+      G(score_launch_outer_relu_bwd(B, FC2, ws + w.dlogit, W + P.fc_w[2], ws + w.f2, keep_prob, ws + w.dz2, s));
+    // fc2
+    G(gemm_queue_add(&gq, FC1, FC2, B, ws + w.f1, FC1, ws + w.dz2, FC2, gw + P.fc_w[1], FC2));
+    G(colsum_queue_add(&cq, ws + w.dz2, B, FC2, FC2, gw + P.fc_b[1], 0));
+    const float rs = (float)(1.0 / sqrt(1.0 + 1e-3));
+    // dz1, d bn1, d head input and bn1's d gamma terms: one launch (head_fused.hip) ...
+    int hbrc = fl.head_unfused ? SCORE_E_SHAPE
+                   : score_launch_head_bwd_fused(B, d.Dhead, FC1, FC2, ws + w.dz2, W + P.fc_w[1], ws + w.f1, keep_prob,
+                                                 W + P.fc_w[0], ws + w.head_inp, W + P.bn_g, rs, ws + w.dz1, ws + w.dbn,
+                                                 ws + w.dhead, ws + w.dgstage, s);
+    if (hbrc != 0 && hbrc != SCORE_E_SHAPE) return hbrc;
+    if (hbrc == SCORE_E_SHAPE)      // ... or layer by layer
+      G(gemm_mode_call(x3, 1, B, FC1, FC2, ws + w.dz2, FC2, W + P.fc_w[1], FC2, ws + w.dz1, FC1, nullptr, GF_RELUGRAD, keep_prob,
+                       reinterpret_cast<const uint8_t*>(ws + w.f1), 0, scratch, SF, s));   // relu/dropout mask of fc1 in the epilogue
+    // fc1 + bn1
+    G(gemm_queue_add(&gq, d.Dhead, FC1, B, ws + w.bn, d.Dhead, ws + w.dz1, FC1, gw + P.fc_w[0], FC1));
+    G(colsum_queue_add(&cq, ws + w.dz1, B, FC1, FC1, gw + P.fc_b[0], 0));
+    if (hbrc == SCORE_E_SHAPE) {
+      G(gemm_mode_call(x3, 1, B, d.Dhead, FC1, ws + w.dz1, FC1, W + P.fc_w[0], FC1, ws + w.dbn, d.Dhead, nullptr, 0, 1.f,
+                   nullptr, 0, scratch, SF, s));
+      G(score_launch_bn_bwd(B, d.Dhead, ws + w.head_inp, W + P.bn_g, rs, ws + w.dbn, ws + w.dhead, gw + P.bn_g,
+                            gw + P.bn_b, ws + w.dgstage, scratch, SF, &cq, s));
+    } else {                        // (bn1's d gamma / d beta: column sums of what the fused kernel wrote)
+      G(colsum_queue_add(&cq, ws + w.dgstage, B, d.Dhead, d.Dhead, gw + P.bn_g, 0));
+      G(colsum_queue_add(&cq, ws + w.dbn, B, d.Dhead, d.Dhead, gw + P.bn_b, 0));
+    }
   }
 
   EV(1);
@@ -1240,9 +1322,9 @@ extern "C" int score_backward(const score_config_t* cfg, const score_state_t* st
                                   nullptr, ws + w.dgru[0], ws + w.dgru[1], ws + w.dinfo, ws + w.dq, s));
     }
   } else {
-    // RIA: gradient enters through the final states only; atten_info is unused downstream
+    // RIA: gradient enters through the final states only; atten_info is unused downstream (GCMC: the head kernel wrote dfinal)
     for (int sd = 0; sd < 2; ++sd) {
-      G(score_launch_copy2d(B, H, ws + w.dhead + sd * H, d.Dhead, ws + w.dfinal[sd], H, s));
+      if (!d.gcmc) G(score_launch_copy2d(B, H, ws + w.dhead + sd * H, d.Dhead, ws + w.dfinal[sd], H, s));
       dfinal[sd] = ws + w.dfinal[sd];
       he = hipMemsetAsync(ws + w.dgru[sd], 0, (int64_t)BT * H * sizeof(float), s);
       if (he != hipSuccess) return (int)he;
@@ -1316,8 +1398,9 @@ extern "C" int score_backward(const score_config_t* cfg, const score_state_t* st
     // on the concatenated layout, then split into the two variables' gradients
     const float* cat = ws + w.wxcat + (int64_t)sd * (d.I + 1) * 3 * H;
     // x rows of the two kernels straight into their gradients (same A panel, the column tiles of [dgates | dcand])
-    G(gemm_queue_add(&gq, d.Is[sd], 2 * H, BT, ws + w.xside[sd], d.I, dxp, 3 * H, gw + P.gk[sd], 2 * H));
-    G(gemm_queue_add(&gq, d.Is[sd], H, BT, ws + w.xside[sd], d.I, dxp + 2 * H, 3 * H, gw + P.ck[sd], H));
+    const float* xin = d.gcmc ? ws + w.gcmc_z[sd] : ws + w.xside[sd];
+    G(gemm_queue_add(&gq, d.Is[sd], 2 * H, BT, xin, x_ld(d, sd), dxp, 3 * H, gw + P.gk[sd], 2 * H));
+    G(gemm_queue_add(&gq, d.Is[sd], H, BT, xin, x_ld(d, sd), dxp + 2 * H, 3 * H, gw + P.ck[sd], H));
     G(gemm_queue_add(&gq, H, 2 * H, BT, ws + w.hprev[sd], H, dxp, 3 * H, gw + P.gk[sd] + (int64_t)d.Is[sd] * 2 * H, 2 * H));
     G(gemm_queue_add(&gq, H, H, BT, ws + w.rh[sd], H, dxp + 2 * H, 3 * H, gw + P.ck[sd] + (int64_t)d.Is[sd] * H, H));
     if (gru_bias_rows > 0) {     // (the recurrence left per-workgroup column sums of dxproj: a few dozen rows instead of B*T)
@@ -1333,11 +1416,26 @@ extern "C" int score_backward(const score_config_t* cfg, const score_state_t* st
       he = hipMemsetAsync(ws + w.dxside[sd], 0, (int64_t)BT * d.I * sizeof(float), s);
       if (he != hipSuccess) return (int)he;
     }
-    if (d.Is[0] != d.Is[1])
+    if (d.gcmc) {
+      // GCMC's two denses (slice_model.py:186-190): dZ [Z>0] = (dxproj Wx^T) [Z>0] -> dWc = A^T (.) ; dA = (.) Wc^T [A>0] ->
+      // dWa = S^T dA ; dS = dA Wa^T, the gradient of the 1-hop sum (its 2-hop columns stay zero, as for RRN)
+      const int Dx = d.Is[sd];
+      float* dz = ws + w.gcmc_dz[sd];
+      float* da = ws + w.gcmc_da[sd];
+      G(gemm_mode_call(x3, 1, BT, Dx, 3 * H, dxp, 3 * H, cat, 3 * H, dz, Dx, nullptr, GF_RELUGRAD, 1.f,
+                       reinterpret_cast<const uint8_t*>(ws + w.gcmc_z[sd]), 0, scratch, SF, s));
+      G(gemm_queue_add(&gq, Dx, Dx, BT, ws + w.gcmc_a[sd], Dx, dz, Dx, gw + P.gm_c[sd], Dx));
+      G(gemm_mode_call(x3, 1, BT, Dx, Dx, dz, Dx, W + P.gm_c[sd], Dx, da, Dx, nullptr, GF_RELUGRAD, 1.f,
+                       reinterpret_cast<const uint8_t*>(ws + w.gcmc_a[sd]), 0, scratch, SF, s));
+      G(gemm_queue_add(&gq, Dx, Dx, BT, ws + w.xside[sd], d.I, da, Dx, gw + P.gm_a[sd], Dx));
+      G(gemm_mode_call(x3, 1, BT, Dx, Dx, da, Dx, W + P.gm_a[sd], Dx, ws + w.dxside[sd], d.I, nullptr, 0, 1.f, nullptr, 0,
+                       scratch, SF, s));
+    } else if (d.Is[0] != d.Is[1]) {
       G(gemm_mode_call(x3, 1, BT, d.Is[sd], 3 * H, dxp, 3 * H, cat, 3 * H, ws + w.dxside[sd], d.I, nullptr, 0, 1.f, nullptr, 0,
                        scratch, SF, s));
+    }
   }
-  if (d.Is[0] == d.Is[1]) {      // both sides' d x in ONE grouped launch: 2 x 576 tiles fill 512 slots better than twice 576
+  if (d.Is[0] == d.Is[1] && !d.gcmc) {      // both sides' d x in ONE grouped launch: 2 x 576 tiles fill 512 slots better than twice 576
     const float* Ad[2] = {ws + w.dxproj[0], ws + w.dxproj[1]};
     const float* Bd[2] = {ws + w.wxcat, ws + w.wxcat + (int64_t)(d.I + 1) * 3 * H};
     float* Cd[2] = {ws + w.dxside[0], ws + w.dxside[1]};
@@ -1412,6 +1510,9 @@ extern "C" int score_backward(const score_config_t* cfg, const score_state_t* st
   // (the occurrence sort's event, which the row scatter below needs: waited for HERE, next to the wait above -- every wait or record
   //  between two launches costs the launch stream a bubble of ~6 us, two adjacent ones cost one)
   if (!atomic && st->plan_done_event) HIPTRY(hipStreamWaitEvent(s, (hipEvent_t)st->plan_done_event, 0));
+  if (d.gcmc) {     // (GCMC reads no target row: their gradient is zero)
+    if (!atomic) HIPTRY(hipMemsetAsync(ws + w.dtgt, 0, (int64_t)B * d.Dq * sizeof(float), s));
+  } else
   G(score_launch_target_bwd(grad_table, d.D, d.Fu, d.Fi, B, T, bt->target_user, bt->target_item,
                             d.attn ? ws + w.dquery : nullptr, d.Dq, ws + w.dhead, d.Dhead, d.off_ti, d.off_tu,
                             ws + w.query, d.coattn ? W + P.ca_w[0] : nullptr, d.coattn ? W + P.ca_w[1] : nullptr,

@@ -251,3 +251,11 @@ int score_gru_fwd_x3(GruArgs& a, int nsides, hipStream_t s);
 int score_gru_bwd_x3(GruArgs& a, int nsides, hipStream_t s);
 int score_gru_fwd_multi(GruArgs& a, int nsides, hipStream_t s);
 int score_gru_bwd_multi(GruArgs& a, int nsides, hipStream_t s);
+// gcmc.hip: the GCMC slice baseline's bilinear two-way softmax head (slice_model.py:199-201), H <= 256.  Forward: y, the
+// per-sample log-loss term, and p = h_i W4, n = h_i W5, g = dL/da saved for the backward; backward: dh_u, dh_i and the rows
+// gpos = g h_u, gneg = -g h_u of the dense gradients dW4 = h_i^T gpos, dW5 = h_i^T gneg
+int score_launch_gcmc_head_fwd(int B, int H, const float* hu, const float* hi, const float* W4, const float* W5,
+                               const int32_t* label, float* y, float* lossb, float* p, float* n, float* g, int Bglobal,
+                               hipStream_t s);
+int score_launch_gcmc_head_bwd(int B, int H, const float* hu, const float* W4, const float* W5, const float* p, const float* n,
+                               const float* g, float* dhu, float* dhi, float* gpos, float* gneg, hipStream_t s);

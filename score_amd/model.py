@@ -1763,4 +1763,12 @@ class RRN(SCOREBASE):
     model_type = "RRN"
 
 
-MODELS = {"SCORE": SCORE, "RIA": RIA, "RCA": RCA, "SCORE_USER": SCORE_USER, "SCORE_ITEM": SCORE_ITEM, "RRN": RRN}
+class GCMC(SCOREBASE):
+    """slice_models/slice_model.py:177-203: per side, the summed 1-hop set through two relu denses without bias (dense /
+    dense_2 on the user side, dense_1 / dense_3 on the item side), a GRU (gru1 / gru2) over the slices, and the bilinear
+    two-way softmax of the final states, y = exp(a) / (exp(a) + exp(c)) with a = <h_i dense_4, h_u>, c = <h_i dense_5, h_u>.
+    Same constructor and train/eval/save/restore as RRN (SliceBaseModel, :11-152); no dropout, so keep_prob has no effect."""
+    model_type = "GCMC"
+
+
+MODELS = {"SCORE": SCORE, "RIA": RIA, "RCA": RCA, "SCORE_USER": SCORE_USER, "SCORE_ITEM": SCORE_ITEM, "RRN": RRN, "GCMC": GCMC}
