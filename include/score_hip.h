@@ -72,7 +72,17 @@ enum { SCORE_MODEL_SCORE = 0, SCORE_MODEL_RIA = 1, SCORE_MODEL_RCA = 2,
        /* slice_models/slice_model.py:177-203: summed 1-hop sets -> two relu denses per side -> GRUs -> bilinear two-way
         * softmax of the final states.  Its arithmetic reads user_1hop and item_1hop only; the other four index tensors are
         * still read and checked for ids outside the table (their rows get a zero gradient), as for RRN. */
-       SCORE_MODEL_GCMC = 6 };
+       SCORE_MODEL_GCMC = 6,
+       /* point_models/point_model.py:9-138 (GRU4Rec): the flat user history through two GRUs stacked in depth (gru1 -> gru2,
+        * :129-132), layer 2's final state + the target rows -> the same bn1 / fc head, log-loss and L2 filter.  obj_per_time_slice
+        * must be 1.  The batch rides in score_batch_t: user_1hop = user_seq seen as [B,T,1,Fi], length = user_seq_length (values
+        * above T behave as T), target_user / target_item / label as they are.  user_2hop, item_1hop and item_2hop do not exist in
+        * this model: the caller passes zero-filled tensors of their shapes (row 0 is the masked row: no arithmetic, no gradient);
+        * they are still enumerated by the index plan.  Workspace pairs (score_workspace_field: gru_out, gates, xproj, dxproj, rh,
+        * hprev): index 0 = layer 1, 1 = layer 2.  At H in {16, 32, 64} the two recurrences run as ONE kernel each way
+        * (csrc/gru_stack.hip: layer 2 one step behind layer 1, its input handed over in LDS); other H, and debug_flags bit 13,
+        * run them one layer per launch with the projection GEMM between them. */
+       SCORE_MODEL_GRU4REC = 7 };
 
 /* Constructor arguments of SCOREBASE.__init__ (score.py:12-13). */
 typedef struct {
@@ -80,7 +90,7 @@ typedef struct {
   int32_t eb_dim;              /* D: multiple of 4, <= 256                        */
   int32_t hidden_size;         /* H                                               */
   int32_t max_time_len;        /* T                                               */
-  int32_t obj_per_time_slice;  /* K <= 32                                         */
+  int32_t obj_per_time_slice;  /* K <= 32 (SCORE_MODEL_GRU4REC: 1)                */
   int32_t user_fnum;           /* Fu                                              */
   int32_t item_fnum;           /* Fi                                              */
   int32_t model_type;          /* SCORE_MODEL_*                                   */
@@ -409,7 +419,9 @@ typedef struct {
                            a suspected stream race is compared against -- score_amd.model inlines its own streams too);
                            bit 14 (16384) = (layer-by-layer pass) the recurrences' weight-gradient products at the END of the
                            launch stream's chain, behind the row scatter (the round-5 placement), instead of on the side stream
-                           beside the co-attention backward and the scatter (round 6; same bits).  Bit 13 is unused.
+                           beside the co-attention backward and the scatter (round 6; same bits); bit 13 (8192) =
+                           (SCORE_MODEL_GRU4REC) the two stacked recurrences one layer per launch with the projection GEMM between
+                           them (the composed form: what H outside {16, 32, 64} runs anyway) instead of csrc/gru_stack.hip.
                            The ONLY switches of the launch sequence: the library reads no environment variable       */
   uint8_t* row_flags;   /* optional [n_table_rows] row state of the dense table optimizer (see
                            score_adam_rows): score_backward (scatter_mode 0) marks every row it

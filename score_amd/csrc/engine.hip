@@ -1,6 +1,7 @@
 // Whole-path orchestration: parameter/workspace layout and the forward / backward
 // launch sequences of SCORE and its ablations (score.py:188-369) and of the slice baselines RRN and GCMC
-// (slice_model.py:155-203) on one stream.  Host code only; every kernel lives in embed/gemm/gru/head/gcmc.hip.
+// (slice_model.py:155-203) and of the point baseline GRU4Rec (point_model.py:123-138) on one stream.  Host code only; every
+// kernel lives in embed/gemm/gru/gru_stack/head/gcmc.hip.
 #include <string.h>
 #include <stdlib.h>
 #include <stdio.h>
@@ -22,6 +23,8 @@ struct Dims {
   int Du, Di, I, Dq, NI, Dk, Dhead, nstate;
   int Is[2];       // GRU input width per side (user, item): I, except RRN / GCMC (their 1-hop sums only)
   bool coattn, attn, gcmc;
+  bool g4r;        // GRU4Rec: "side" 0 is layer 1 (input: the gathered user_seq rows, Di wide), "side" 1 layer 2 (input: layer 1's outputs, H wide)
+  int Ic;          // row capacity of a side's block of the concatenated [Wx_gates | Wx_cand] copy: I (GRU4Rec: max(I, H))
   int off_u, off_i, off_ti, off_tu;  // columns of head_inp
 };
 
@@ -30,22 +33,26 @@ int make_dims(const score_config_t* c, Dims* d) {
   d->N = c->feature_size; d->D = c->eb_dim; d->H = c->hidden_size; d->T = c->max_time_len;
   d->K = c->obj_per_time_slice; d->Fu = c->user_fnum; d->Fi = c->item_fnum; d->mt = c->model_type;
   if (d->N <= 0 || d->D <= 0 || (d->D & 3) || d->D > 256 || d->H <= 0 || d->T <= 0 || d->K <= 0 || d->K > 32 ||
-      d->Fu <= 0 || d->Fi <= 0 || d->mt < 0 || d->mt > SCORE_MODEL_GCMC)
+      d->Fu <= 0 || d->Fi <= 0 || d->mt < 0 || d->mt > SCORE_MODEL_GRU4REC)
     return SCORE_E_SHAPE;
   d->Du = d->Fu * d->D; d->Di = d->Fi * d->D; d->I = d->Di + d->Du; d->Dq = d->Du + d->Di;
   d->gcmc = d->mt == SCORE_MODEL_GCMC;
-  const bool rrn = d->mt == SCORE_MODEL_RRN || d->gcmc;      // (GCMC starts from RRN's two 1-hop sums, slice_model.py:184-187)
+  d->g4r = d->mt == SCORE_MODEL_GRU4REC;
+  if (d->g4r && d->K != 1) return SCORE_E_SHAPE;              // (user_seq rides as a [B, T, 1, Fi] set)
+  // (GCMC starts from RRN's two 1-hop sums, slice_model.py:184-187; GRU4Rec's user_seq rows are RRN's "sum" over a one-element set)
+  const bool rrn = d->mt == SCORE_MODEL_RRN || d->gcmc || d->g4r;
   d->coattn = d->mt != SCORE_MODEL_RCA && !rrn;
   d->attn = d->mt != SCORE_MODEL_RIA && !rrn;
   d->NI = (d->mt == SCORE_MODEL_RCA || d->mt == SCORE_MODEL_RIA || rrn) ? 0 : 4 * d->K;
   // RRN (slice_model.py:159-160): user side = sum_k user_1hop (item features), item side = sum_k item_1hop
   d->Is[0] = rrn ? d->Di : d->I;
-  d->Is[1] = rrn ? d->Du : d->I;
+  d->Is[1] = d->g4r ? d->H : rrn ? d->Du : d->I;
+  d->Ic = d->g4r && d->H > d->I ? d->H : d->I;
   if (d->gcmc && d->H > 256) return SCORE_E_SHAPE;            // (its head kernels, gcmc.hip)
   d->Dk = d->attn ? 2 * d->H + d->NI : 0;
-  d->nstate = (d->mt == SCORE_MODEL_SCORE_USER || d->mt == SCORE_MODEL_SCORE_ITEM) ? 1 : 2;
+  d->nstate = (d->mt == SCORE_MODEL_SCORE_USER || d->mt == SCORE_MODEL_SCORE_ITEM || d->g4r) ? 1 : 2;
   d->Dhead = d->nstate * d->H + d->Di + d->Du;
-  d->off_u = d->mt == SCORE_MODEL_SCORE_ITEM ? -1 : 0;
+  d->off_u = d->mt == SCORE_MODEL_SCORE_ITEM ? -1 : 0;       // (GRU4Rec: layer 2's final state sits where SCORE_USER's state does)
   d->off_i = d->mt == SCORE_MODEL_SCORE_USER ? -1 : (d->mt == SCORE_MODEL_SCORE_ITEM ? 0 : d->H);
   d->off_ti = d->nstate * d->H;       // [..., target_item, target_user]  (score.py:217)
   d->off_tu = d->off_ti + d->Di;
@@ -53,7 +60,8 @@ int make_dims(const score_config_t* c, Dims* d) {
 }
 
 // the GRUs' input rows of side sd and their stride: the [B*T, I] gather output, or GCMC's Z = relu(relu(S Wa) Wc) [B*T, Dx]
-static inline int x_ld(const Dims& d, int sd) { return d.gcmc ? d.Is[sd] : d.I; }
+// (GRU4Rec's layer 2 reads layer 1's outputs [B*T, H])
+static inline int x_ld(const Dims& d, int sd) { return d.gcmc ? d.Is[sd] : (d.g4r && sd == 1) ? d.H : d.I; }
 
 // time slices actually computed for a batch (score_batch_t.active_slices): every [B*T, .] activation of the
 // pass is laid out [B * TA, .]; the workspace regions keep their full-T sizes and offsets
@@ -99,7 +107,7 @@ int build_layout_raw(const Dims& d, score_param_entry_t* out, int max_entries, P
     add("dense_2/kernel", Dx[0], Dx[0], 1, 2); add("dense_3/kernel", Dx[1], Dx[1], 1, 2);
   }
   const char* sides[2] = {"gru_user_side", "gru_item_side"};
-  if (d.gcmc) { sides[0] = "gru1"; sides[1] = "gru2"; }
+  if (d.gcmc || d.g4r) { sides[0] = "gru1"; sides[1] = "gru2"; }     // (GRU4Rec, point_model.py:129-132: the two stacked layers)
   for (int s = 0; s < 2; ++s) {
     char b[64];
     snprintf(b, 64, "%s/gru_cell/gates/kernel", sides[s]); add(b, d.Is[s] + d.H, 2 * d.H, 1, 2);
@@ -270,7 +278,7 @@ void build_ws_raw(const Dims& d, int B, WS* w) {
   w->ca_slab = take(w->ca_slab_floats);
   w->cs_part_floats = 1 << 21;
   w->cs_part = take(w->cs_part_floats);
-  w->wxcat = take(2 * (int64_t)(d.I + 1) * 3 * d.H);
+  w->wxcat = take(2 * (int64_t)(d.Ic + 1) * 3 * d.H);
   for (int sd = 0; sd < 2; ++sd) {
     const int ns = panel_x_splits(d.H);
     w->pimg_x[sd] = take(ns ? ns * score_gemm_panel_image_floats(3 * d.H / ns, d.Is[sd]) : 0);
@@ -466,6 +474,94 @@ static inline int gemm_mode_call(int x3, int tr, int M, int N, int K, const floa
     }                                                                        \
   } while (0)
 
+// ---------------------------------------------------------------- GRU4Rec's two stacked recurrences (point_model.py:129-132)
+// The stacked kernel (gru_stack.hip: both layers in one launch, layer 2 one step behind layer 1) or, with debug_flags bit 13
+// (8192) and at every H it does not cover, the COMPOSED form: layer 1's recurrence, the GEMM that projects its outputs, layer 2's
+// recurrence -- the kernels of the other model types, one layer per launch -- and the mirror image backward.
+static bool g4r_stacked(const Dims& d, const score_state_t* st) {
+  return !(st->debug_flags & 8192) && !(st->debug_flags & 1) && score_gru_stack_ok(d.H);
+}
+static void g4r_gru_args(const Dims& d, const WS& w, const score_state_t* st, const score_batch_t* bt, int T, int x3, GruArgs* ga) {
+  float* ws = st->workspace;
+  memset(ga, 0, sizeof(*ga));
+  ga->B = bt->B; ga->T = T; ga->H = d.H; ga->length = bt->length; ga->nw8 = 1;
+  ga->tmp = ws + w.gru_tmp; ga->tmp_floats = w.gru_tmp_floats; ga->x3 = x3 != 0; ga->x3_rec = ga->x3 && !(st->debug_flags & 4);
+  ga->stepwise = (st->debug_flags & 1) != 0;
+}
+// one layer's GruSide: the h rows of its kernels, its saved outputs / gates and its backward regions
+static void g4r_side(const Dims& d, const Params& P, const WS& w, const score_state_t* st, int l, GruSide* g) {
+  float* ws = st->workspace;
+  const float* W = st->w;
+  const int H = d.H;
+  memset(g, 0, sizeof(*g));
+  g->xproj = ws + w.xproj[l]; g->Wg = W + P.gk[l] + (int64_t)d.Is[l] * 2 * H; g->ldwg = 2 * H;
+  g->Wc = W + P.ck[l] + (int64_t)d.Is[l] * H; g->ldwc = H;
+  g->out = ws + w.gru_out[l]; g->ldo = H; g->gates = ws + w.gates[l]; g->final_state = l ? ws + w.gru_final[1] : nullptr;
+  g->dxproj = ws + w.dxproj[l]; g->rh = ws + w.rh[l]; g->hprev = ws + w.hprev[l];
+}
+static void g4r_stack_args(const Dims& d, const Params& P, const WS& w, const score_state_t* st, const score_batch_t* bt, int T,
+                           GruStackArgs* a) {
+  const float* W = st->w;
+  memset(a, 0, sizeof(*a));
+  a->B = bt->B; a->T = T; a->H = d.H; a->length = bt->length;
+  for (int l = 0; l < 2; ++l) g4r_side(d, P, w, st, l, &a->l[l]);
+  a->Wg2 = W + P.gk[1]; a->Wc2 = W + P.ck[1]; a->bg2 = W + P.gb[1]; a->bc2 = W + P.cb[1];
+}
+static int g4r_grus_fwd(const Dims& d, const Params& P, const WS& w, const score_state_t* st, const score_batch_t* bt, int T, int x3,
+                        hipStream_t s) {
+  float* ws = st->workspace;
+  const int B = bt->B, H = d.H, BT = B * T;
+  float* scratch = ws + w.scratch;
+  const float* cat[2] = {ws + w.wxcat, ws + w.wxcat + (int64_t)(d.Ic + 1) * 3 * H};
+  // layer 1's hoisted projection of the gathered rows: x . [Wx_gates | Wx_cand] + [b_gates | b_cand]
+  G(gemm_mode_call(x3, 0, BT, 3 * H, d.Di, ws + w.xside[0], d.I, cat[0], 3 * H, ws + w.xproj[0], 3 * H, cat[0] + (int64_t)d.Di * 3 * H,
+                   GF_BIAS, 1.f, nullptr, 0, scratch, w.scratch_floats, s));
+  if (g4r_stacked(d, st)) {
+    GruStackArgs a;
+    g4r_stack_args(d, P, w, st, bt, T, &a);
+    return score_gru_stack_fwd(a, s);
+  }
+  for (int l = 0; l < 2; ++l) {
+    if (l == 1)     // layer 2's input rows are layer 1's outputs (zero past the length)
+      G(gemm_mode_call(x3, 0, BT, 3 * H, H, ws + w.gru_out[0], H, cat[1], 3 * H, ws + w.xproj[1], 3 * H, cat[1] + (int64_t)H * 3 * H,
+                       GF_BIAS, 1.f, nullptr, 0, scratch, w.scratch_floats, s));
+    GruArgs ga;
+    g4r_gru_args(d, w, st, bt, T, x3, &ga);
+    g4r_side(d, P, w, st, l, &ga.s[0]);
+    G(score_gru_fwd_multi(ga, 1, s));
+  }
+  return 0;
+}
+// dfinal2: dL/d layer 2's final state [B, H].  Leaves both layers' dxproj / rh / hprev rows for the queued weight-gradient
+// products; *bias_rows as GruArgs.bias_slab_rows
+static int g4r_grus_bwd(const Dims& d, const Params& P, const WS& w, const score_state_t* st, const score_batch_t* bt, int T, int x3,
+                        const float* dfinal2, int* bias_rows, hipStream_t s) {
+  float* ws = st->workspace;
+  const int B = bt->B, H = d.H, BT = B * T;
+  *bias_rows = 0;
+  if (g4r_stacked(d, st)) {
+    GruStackArgs a;
+    g4r_stack_args(d, P, w, st, bt, T, &a);
+    a.l[1].dfinal = dfinal2;
+    return score_gru_stack_bwd(a, s);
+  }
+  const float* cat1 = ws + w.wxcat + (int64_t)(d.Ic + 1) * 3 * H;
+  for (int l = 1; l >= 0; --l) {
+    GruArgs ga;
+    g4r_gru_args(d, w, st, bt, T, x3, &ga);
+    GruSide& g = ga.s[0];
+    g4r_side(d, P, w, st, l, &g);
+    g.dout = ws + w.dgru[l]; g.lddo = H; g.dfinal = l ? dfinal2 : nullptr;       // (dgru[1]: zeros, only the final state is read)
+    g.bias_slab = (2 * ((int64_t)B / 16 + 1) * 3 * H <= w.gru_tmp_floats) ? ws + w.gru_tmp + (int64_t)l * (B / 16 + 1) * 3 * H : nullptr;
+    G(score_gru_bwd_multi(ga, 1, s));
+    *bias_rows = ga.bias_slab_rows;
+    if (l == 1)     // layer 2's input gradient is layer 1's dout: [dgates | dcand] . [Wx_gates | Wx_cand]^T
+      G(gemm_mode_call(x3, 1, BT, H, 3 * H, ws + w.dxproj[1], 3 * H, cat1, 3 * H, ws + w.dgru[0], H, nullptr, 0, 1.f, nullptr, 0,
+                       ws + w.scratch, w.scratch_floats, s));
+  }
+  return 0;
+}
+
 }  // namespace
 
 extern "C" int score_context_create(void** ctx) {
@@ -632,7 +728,7 @@ extern "C" int score_index_plan(const score_config_t* cfg, const score_state_t* 
 // same: profiles/r04_probes.md).  At cfg-5's sizes the other
 // streams' work is small beside these products: 20.3 -> 19.8 ms/step with both.
 static bool panel_gemms(const Dims& d, const score_state_t* st, int BT, int which) {
-  if (st->gemm_mode != 1 || (st->debug_flags & 8) || d.Is[0] != d.Is[1]) return false;
+  if (st->gemm_mode != 1 || (st->debug_flags & 8) || d.Is[0] != d.Is[1] || d.g4r) return false;
   if (which == 1 && d.gcmc) return false;      // (GCMC's input gradients take Z's relu mask in the epilogue: the tiled kernels)
   const int ns = panel_x_splits(d.H);
   return which == 0 ? ns > 0 && score_gemm_panel_ok(2 * ns, BT, 3 * d.H / ns, d.Is[0], x_ld(d, 0), 3 * d.H, nullptr)
@@ -960,13 +1056,13 @@ extern "C" int score_forward(const score_config_t* cfg, const score_state_t* st,
   // partial sums (three launches before round 4: the reference's own batch sizes are bound by the host's launch calls)
   const int64_t weff_stride = align_up64(2 * (int64_t)d.Dk * AT1 + 48, 4);     // replicas of the folded attention weight (build_ws)
   G(score_launch_weight_prep(W + P.gk[0], W + P.ck[0], W + P.gb[0], W + P.cb[0], W + P.gk[1], W + P.ck[1], W + P.gb[1],
-                             W + P.cb[1], d.Is[0], d.Is[1], d.I, H, ws + w.wxcat, d.Dk, AT1, d.attn ? W + P.at_w[1] : nullptr,
+                             W + P.cb[1], d.Is[0], d.Is[1], d.Ic, H, ws + w.wxcat, d.Dk, AT1, d.attn ? W + P.at_w[1] : nullptr,
                              ws + w.weff, ws + w.wq, SCORE_WEFF_COPIES, weff_stride, W, P.n_reg, ws + w.part, sd->st));
   // the panel form of the projections and of their input gradients (gemm_panel.hip) takes the weights as fragment images:
   // written here, once per step, behind the concatenated copies (the backward pass reuses them as it reuses the copies)
   const bool panel_x = panel_gemms(d, st, BT, 0), panel_d = panel_gemms(d, st, BT, 1);
   {
-    const float* cats[2] = {ws + w.wxcat, ws + w.wxcat + (int64_t)(d.I + 1) * 3 * H};
+    const float* cats[2] = {ws + w.wxcat, ws + w.wxcat + (int64_t)(d.Ic + 1) * 3 * H};
     if (panel_x) {
       const int ns = panel_x_splits(H), Nh = 3 * H / ns;
       const int64_t per = score_gemm_panel_image_floats(Nh, d.Is[0]);
@@ -1037,6 +1133,10 @@ extern "C" int score_forward(const score_config_t* cfg, const score_state_t* st,
     }
   }
   // GRUs (:205-208): hoisted x-projection, then the persistent recurrence
+  if (d.g4r) {
+    HIPTRY(hipStreamWaitEvent(s, wx_ev, 0));
+    G(g4r_grus_fwd(d, P, w, st, bt, T, x3, s));
+  } else
   {
     GruArgs ga;
     memset(&ga, 0, sizeof(ga));
@@ -1045,7 +1145,7 @@ extern "C" int score_forward(const score_config_t* cfg, const score_state_t* st,
     HIPTRY(hipStreamWaitEvent(s, wx_ev, 0));
     if (d.Is[0] == d.Is[1]) {    // both sides' projections in ONE grouped launch (each with its own bias row)
       const float* c0 = ws + w.wxcat;
-      const float* c1 = c0 + (int64_t)(d.I + 1) * 3 * H;
+      const float* c1 = c0 + (int64_t)(d.Ic + 1) * 3 * H;
       const float* Ax[2] = {xin[0], xin[1]};
       const float* Bx[2] = {c0, c1};
       float* Cx[2] = {ws + w.xproj[0], ws + w.xproj[1]};
@@ -1067,7 +1167,7 @@ extern "C" int score_forward(const score_config_t* cfg, const score_state_t* st,
     for (int sd = 0; sd < 2; ++sd) {
       float* xp = ws + w.xproj[sd];
       // x . [Wx_gates | Wx_cand] + [b_gates | b_cand]: one GEMM per side on the concatenated copy
-      const float* cat = ws + w.wxcat + (int64_t)sd * (d.I + 1) * 3 * H;
+      const float* cat = ws + w.wxcat + (int64_t)sd * (d.Ic + 1) * 3 * H;
       if (d.Is[0] != d.Is[1])
         G(gemm_mode_call(x3, 0, BT, 3 * H, d.Is[sd], xin[sd], x_ld(d, sd), cat, 3 * H, xp, 3 * H, cat + (int64_t)d.Is[sd] * 3 * H,
                          GF_BIAS, 1.f, nullptr, 0, scratch, w.scratch_floats, s));
@@ -1109,6 +1209,9 @@ extern "C" int score_forward(const score_config_t* cfg, const score_state_t* st,
                                    d.off_u, d.off_i, s));
     }
     }     // (... else the separate launches above)
+  } else if (d.g4r) {
+    // GRU4Rec (point_model.py:134): layer 2's final state feeds the head
+    G(score_launch_copy2d(B, H, ws + w.gru_final[1], H, ws + w.head_inp, d.Dhead, s));
   } else if (!d.gcmc) {
     // RIA: final GRU states feed the head (:244-249)
     G(score_launch_copy2d(B, H, ws + w.gru_final[0], H, ws + w.head_inp, d.Dhead, s));
@@ -1324,7 +1427,13 @@ extern "C" int score_backward(const score_config_t* cfg, const score_state_t* st
   } else {
     // RIA: gradient enters through the final states only; atten_info is unused downstream (GCMC: the head kernel wrote dfinal)
     for (int sd = 0; sd < 2; ++sd) {
-      if (!d.gcmc) G(score_launch_copy2d(B, H, ws + w.dhead + sd * H, d.Dhead, ws + w.dfinal[sd], H, s));
+      if (d.g4r) {      // GRU4Rec: the head reads layer 2's final state only; layer 1's dout comes from layer 2's backward
+        if (sd == 0) continue;
+        G(score_launch_copy2d(B, H, ws + w.dhead, d.Dhead, ws + w.dfinal[1], H, s));
+        dfinal[1] = ws + w.dfinal[1];
+        if (g4r_stacked(d, st)) continue;       // (the stacked kernel reads no dout of layer 2; the composed form's kernel does)
+      }
+      else if (!d.gcmc) G(score_launch_copy2d(B, H, ws + w.dhead + sd * H, d.Dhead, ws + w.dfinal[sd], H, s));
       dfinal[sd] = ws + w.dfinal[sd];
       he = hipMemsetAsync(ws + w.dgru[sd], 0, (int64_t)BT * H * sizeof(float), s);
       if (he != hipSuccess) return (int)he;
@@ -1372,6 +1481,9 @@ extern "C" int score_backward(const score_config_t* cfg, const score_state_t* st
     if (q_on_side) G(colsum_queue_flush(&cq, ws + w.cs_part, w.cs_part_floats / 2, side->st));
     HIPTRY(hipEventRecord(side->join, side->st));
   }
+  if (d.g4r) {
+    G(g4r_grus_bwd(d, P, w, st, bt, T, x3, dfinal[1], &gru_bias_rows, s));
+  } else
   {
     GruArgs ga;
     memset(&ga, 0, sizeof(ga));
@@ -1396,9 +1508,9 @@ extern "C" int score_backward(const score_config_t* cfg, const score_state_t* st
     float* dxp = ws + w.dxproj[sd];
     // kernels are [x ; h] row blocks (TF GRUCell): x rows first.  x part of both kernels in one product
     // on the concatenated layout, then split into the two variables' gradients
-    const float* cat = ws + w.wxcat + (int64_t)sd * (d.I + 1) * 3 * H;
+    const float* cat = ws + w.wxcat + (int64_t)sd * (d.Ic + 1) * 3 * H;
     // x rows of the two kernels straight into their gradients (same A panel, the column tiles of [dgates | dcand])
-    const float* xin = d.gcmc ? ws + w.gcmc_z[sd] : ws + w.xside[sd];
+    const float* xin = d.gcmc ? ws + w.gcmc_z[sd] : (d.g4r && sd == 1) ? ws + w.gru_out[0] : ws + w.xside[sd];
     G(gemm_queue_add(&gq, d.Is[sd], 2 * H, BT, xin, x_ld(d, sd), dxp, 3 * H, gw + P.gk[sd], 2 * H));
     G(gemm_queue_add(&gq, d.Is[sd], H, BT, xin, x_ld(d, sd), dxp + 2 * H, 3 * H, gw + P.ck[sd], H));
     G(gemm_queue_add(&gq, H, 2 * H, BT, ws + w.hprev[sd], H, dxp, 3 * H, gw + P.gk[sd] + (int64_t)d.Is[sd] * 2 * H, 2 * H));
@@ -1412,11 +1524,15 @@ extern "C" int score_backward(const score_config_t* cfg, const score_state_t* st
       G(colsum_queue_add(&cq, dxp + 2 * H, BT, H, 3 * H, gw + P.cb[sd], 0));
     }
     // d x = [dgates | dcand] . [Wx_gates | Wx_cand]^T
-    if (d.Is[sd] != d.I) {   // RRN: the 2-hop columns of this side carry no gradient
+    if (d.Is[sd] != d.I || d.g4r) {   // RRN: the 2-hop columns of this side carry no gradient (GRU4Rec: nor does any of "side" 1's)
       he = hipMemsetAsync(ws + w.dxside[sd], 0, (int64_t)BT * d.I * sizeof(float), s);
       if (he != hipSuccess) return (int)he;
     }
-    if (d.gcmc) {
+    if (d.g4r) {      // (layer 1's input gradient, for the row scatter; layer 2's went to layer 1 above)
+      if (sd == 0)
+        G(gemm_mode_call(x3, 1, BT, d.Di, 3 * H, dxp, 3 * H, cat, 3 * H, ws + w.dxside[0], d.I, nullptr, 0, 1.f, nullptr, 0,
+                         scratch, SF, s));
+    } else if (d.gcmc) {
       // GCMC's two denses (slice_model.py:186-190): dZ [Z>0] = (dxproj Wx^T) [Z>0] -> dWc = A^T (.) ; dA = (.) Wc^T [A>0] ->
       // dWa = S^T dA ; dS = dA Wa^T, the gradient of the 1-hop sum (its 2-hop columns stay zero, as for RRN)
       const int Dx = d.Is[sd];
@@ -1435,9 +1551,9 @@ extern "C" int score_backward(const score_config_t* cfg, const score_state_t* st
                        scratch, SF, s));
     }
   }
-  if (d.Is[0] == d.Is[1] && !d.gcmc) {      // both sides' d x in ONE grouped launch: 2 x 576 tiles fill 512 slots better than twice 576
+  if (d.Is[0] == d.Is[1] && !d.gcmc && !d.g4r) {      // both sides' d x in ONE grouped launch: 2 x 576 tiles fill 512 slots better than twice 576
     const float* Ad[2] = {ws + w.dxproj[0], ws + w.dxproj[1]};
-    const float* Bd[2] = {ws + w.wxcat, ws + w.wxcat + (int64_t)(d.I + 1) * 3 * H};
+    const float* Bd[2] = {ws + w.wxcat, ws + w.wxcat + (int64_t)(d.Ic + 1) * 3 * H};
     float* Cd[2] = {ws + w.dxside[0], ws + w.dxside[1]};
     if (panel_gemms(d, st, BT, 1)) {      // (the images were written by the forward pass, like the concatenated copies)
       const int ns = panel_d_splits(d.Is[0]), Nh = d.Is[0] / ns;

@@ -259,3 +259,18 @@ int score_launch_gcmc_head_fwd(int B, int H, const float* hu, const float* hi, c
                                hipStream_t s);
 int score_launch_gcmc_head_bwd(int B, int H, const float* hu, const float* W4, const float* W5, const float* p, const float* n,
                                const float* g, float* dhu, float* dhi, float* gpos, float* gneg, hipStream_t s);
+// gru_stack.hip: GRU4Rec's two GRUs stacked in depth (point_model.py:129-132) as ONE persistent kernel each way, H in
+// {16, 32, 64}.  l[0] = layer 1 as for score_gru_*_multi (xproj hoisted; Wg / Wc the h rows of its kernels), l[1] = layer 2's
+// saved regions only: its input is layer 1's state, handed over in LDS one step later, against the WHOLE kernels Wg2 [2H, 2H] /
+// Wc2 [2H, H] (TF's [x, h] row order) and the biases bg2 [2H] / bc2 [H] -- no projection buffer, no GEMM, no launch boundary.
+// Backward: l[1].dfinal = dL/d layer 2's final state; layer 2's input gradient reaches layer 1 through LDS; both layers'
+// dxproj / rh / hprev rows are written as score_gru_bwd_multi writes them.
+struct GruStackArgs {
+  GruSide l[2];
+  const float* Wg2; const float* Wc2; const float* bg2; const float* bc2;
+  const int32_t* length;
+  int B, T, H;
+};
+bool score_gru_stack_ok(int H);
+int score_gru_stack_fwd(GruStackArgs& a, hipStream_t s);
+int score_gru_stack_bwd(GruStackArgs& a, hipStream_t s);

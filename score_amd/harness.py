@@ -64,7 +64,9 @@ def evaluate(model, batches, reg_lambda, sess=None, neg_sample_num=TEST_NEG_SAMP
         preds += pred
         labels += label
         losses.append(loss)
-        ids = batch_data[5]
+        # the target item ids: batch_data[5] of the slice models' 8-tuple (train_score.py:152), batch_data[3] of a point model's
+        # 5-tuple (train_time_point_models.py:146) -- the model says which; a DeviceBatch holds them as its tensor 5
+        ids = batch_data.tensors[5] if hasattr(batch_data, "tensors") else batch_data[getattr(model, "target_item_field", 5)]
         if hasattr(ids, "cpu"):                   # device batches (DeviceGraphLoader) hand tensors over
             ids = ids.cpu().numpy()
         target_iids += np.array(ids)[:, 0].tolist()

@@ -59,6 +59,30 @@ def batch_shapes(cfg, B):
     return ((B, T, K, Fi), (B, T, K, Fu), (B, T, K, Fu), (B, T, K, Fi), (B, Fu), (B, Fi), (B,), (B,))
 
 
+class FeedSpec(object):
+    """How a model's feed tuple fills the eight tensors of score_batch_t.  slots[i] = (position in the feed tuple or None,
+    the field's name there, its shape there as a function of (cfg, B)) for tensor i of BATCH_FIELDS; a tensor without a
+    source is zero-filled (ids of the masked row 0: no arithmetic, no gradient).  `what` names the tuple in error messages."""
+
+    def __init__(self, n, what, slots):
+        self.n, self.what, self.slots = n, what, slots
+
+    def shapes(self, cfg, B):
+        lib = batch_shapes(cfg, B)
+        return [tuple(sl[2](cfg, B)) if sl[0] is not None else lib[i] for i, sl in enumerate(self.slots)]
+
+
+SLICE_FEED = FeedSpec(8, "the 8-tuple of graph_loader.py:383",
+                      [(i, BATCH_FIELDS[i], (lambda cfg, B, i=i: batch_shapes(cfg, B)[i])) for i in range(8)])
+# point_model.py:88-112, data_loader.py:87: (user_seq [B,T,Fi], user_seq_length [B], target_user [B,Fu], target_item [B,Fi],
+# label [B]).  user_seq rides as user_1hop [B,T,1,Fi]; the three tensors that do not exist in a point model are zeros
+POINT_FEED = FeedSpec(5, "the 5-tuple of point_models/data_loader.py:87",
+                      [(0, "user_seq", lambda cfg, B: (B, cfg.max_time_len, cfg.item_fnum)), (None, None, None), (None, None, None),
+                       (None, None, None), (2, "target_user", lambda cfg, B: (B, cfg.user_fnum)),
+                       (3, "target_item", lambda cfg, B: (B, cfg.item_fnum)), (4, "label", lambda cfg, B: (B,)),
+                       (1, "user_seq_length", lambda cfg, B: (B,))])
+
+
 def carve_batch(flat, shapes):
     """the eight int32 tensors of a batch as views of one flat buffer (every tensor 16-B aligned)"""
     out, off = [], 0
@@ -81,26 +105,34 @@ class DeviceBatch(object):
     def __init__(self, model, batch_data):
         if isinstance(batch_data, DeviceBatch):
             raise TypeError("already a DeviceBatch")
-        if len(batch_data) != 8:
-            raise ValueError("batch_data must be the 8-tuple of graph_loader.py:383")
+        spec = model.feed_spec
+        if len(batch_data) != spec.n:
+            raise ValueError("batch_data must be %s" % spec.what)
         max_len = None
         on_device = all(torch.is_tensor(x) and x.device.type == "cuda" for x in batch_data)
-        B = int(batch_data[6].shape[0]) if hasattr(batch_data[6], "shape") else len(batch_data[6])
+        lab = batch_data[spec.slots[6][0]]
+        B = int(lab.shape[0]) if hasattr(lab, "shape") else len(lab)
         if B == 0:
             raise ValueError("empty batch")
-        shapes = batch_shapes(model.cfg, B)
+        shapes = batch_shapes(model.cfg, B)            # of the eight device tensors
+        fshapes = spec.shapes(model.cfg, B)            # of their sources in the feed tuple (the same element order)
+        src_of = [sl[0] for sl in spec.slots]
         self.B = B
         n_flat = flat_batch_size(shapes)
 
         def bad(i, got):
-            return ValueError("batch_data[%d] (%s) has shape %s, expected %s" % (i, BATCH_FIELDS[i], tuple(got), shapes[i]))
+            return ValueError("batch_data[%d] (%s) has shape %s, expected %s" % (src_of[i], spec.slots[i][1], tuple(got), fshapes[i]))
         if on_device:
             self.flat = torch.empty((n_flat,), dtype=torch.int32, device=model.device)
             self.tensors = carve_batch(self.flat, shapes)
-            for i, (dst, src) in enumerate(zip(self.tensors, batch_data)):
-                if tuple(src.shape) != shapes[i]:
+            for i, dst in enumerate(self.tensors):
+                if src_of[i] is None:
+                    dst.zero_()
+                    continue
+                src = batch_data[src_of[i]]
+                if tuple(src.shape) != fshapes[i]:
                     raise bad(i, src.shape)
-                dst.copy_(src)                              # (dtype / device conversion included)
+                dst.view(fshapes[i]).copy_(src)             # (dtype / device conversion included)
             max_len = int(self.tensors[7].max().item())     # one read-back per batch object
         else:
             # the whole feed tuple into ONE pinned int32 staging buffer, then one asynchronous copy to the device.  Nested
@@ -108,22 +140,27 @@ class DeviceBatch(object):
             # walked in C (_listpack: ~15x faster than np.asarray on lists, and on several native threads without the
             # GIL -- the walk is one cache miss per boxed int); arrays / host tensors are copied
             pinned, slot = model._staging(B, n_flat)
-            views = carve_batch(pinned, shapes)
+            views = [v.view(fs) for v, fs in zip(carve_batch(pinned, shapes), fshapes)]
             lp = _lib.listpack()
             nthreads = int(getattr(model, "feed_threads", 1))
             try:
-                listed = [i for i, x in enumerate(batch_data) if lp is not None and isinstance(x, (list, tuple))]
+                listed = [i for i in range(8) if src_of[i] is not None and lp is not None
+                          and isinstance(batch_data[src_of[i]], (list, tuple))]
                 if listed:      # every list-shaped tensor of the tuple in ONE threaded region (threads are created once)
                     try:
-                        lp.pack_many([(batch_data[i], views[i].numpy(), shapes[i]) for i in listed], nthreads)
+                        lp.pack_many([(batch_data[src_of[i]], views[i].numpy(), fshapes[i]) for i in listed], nthreads)
                     except ValueError as e:
                         i = listed[getattr(e, "tensor_index", 0)]
-                        raise bad(i, np.asarray(batch_data[i]).shape)
-                for i, (dst, x) in enumerate(zip(views, batch_data)):
+                        raise bad(i, np.asarray(batch_data[src_of[i]]).shape)
+                for i, dst in enumerate(views):
                     if i in listed:
                         continue
+                    if src_of[i] is None:
+                        dst.zero_()
+                        continue
+                    x = batch_data[src_of[i]]
                     a = x.cpu().numpy() if torch.is_tensor(x) else np.asarray(x)
-                    if tuple(a.shape) != shapes[i]:
+                    if tuple(a.shape) != fshapes[i]:
                         raise bad(i, a.shape)
                     dst.copy_(torch.from_numpy(np.ascontiguousarray(a.astype(np.int32, copy=False))))
                 max_len = int(views[7].max()) if B else 0
@@ -163,6 +200,7 @@ def active_slices(model, max_len):
 
 class SCOREBASE(object):
     model_type = None
+    feed_spec = SLICE_FEED
 
     def __init__(self, feature_size, eb_dim, hidden_size, max_time_len, obj_per_time_slice,
                  user_fnum, item_fnum, seed=1111, device=None):
@@ -1663,7 +1701,8 @@ class SCOREBASE(object):
             self._adam_dirty = self._tiled is not None and self._tiled_ready     # (a suppressed flush left rows behind)
             self._flags_marked = True           # state-2 marks of the suppressed steps: gone before the next backward
             self._drop_row_marks()
-            names = ["batch_data[%d] (%s)" % (i, BATCH_FIELDS[i]) for i in range(6) if bits >> i & 1]
+            sl = self.feed_spec.slots         # (a bit names a tensor of score_batch_t: reported by its place in the model's own feed tuple)
+            names = ["batch_data[%d] (%s)" % (sl[i][0], sl[i][1]) for i in range(6) if bits >> i & 1 and sl[i][0] is not None]
             raise ValueError("feature id outside [0, %d) in %s (tf.nn.embedding_lookup would raise: score.py:51-66); "
                              "no variable was updated%s"
                              % (int(self.cfg.feature_size), ", ".join(names),
@@ -1771,4 +1810,21 @@ class GCMC(SCOREBASE):
     model_type = "GCMC"
 
 
-MODELS = {"SCORE": SCORE, "RIA": RIA, "RCA": RCA, "SCORE_USER": SCORE_USER, "SCORE_ITEM": SCORE_ITEM, "RRN": RRN, "GCMC": GCMC}
+class GRU4Rec(SCOREBASE):
+    """point_models/point_model.py:123-138 (base class :9-121): the flat user history user_seq [B, T, Fi] through two GRUs
+    stacked in depth (gru1 -> gru2, both masked by user_seq_length), layer 2's final state + target_item + target_user through
+    the same bn1 / fc1 / fc2 / fc3 head, log-loss with the L2 name filter, Adam.  The reference's constructor (no
+    obj_per_time_slice) and train / eval / save / restore; batch_data is the 5-tuple of point_models/data_loader.py:87,
+    (user_seq, user_seq_length, target_user, target_item, label), as nested lists, arrays or device tensors.  The target item
+    ids are batch_data[3] (harness.evaluate reads `target_item_field`)."""
+    model_type = "GRU4Rec"
+    feed_spec = POINT_FEED
+    target_item_field = 3
+
+    def __init__(self, feature_size, eb_dim, hidden_size, max_time_len, user_fnum, item_fnum, seed=1111, device=None):
+        SCOREBASE.__init__(self, feature_size, eb_dim, hidden_size, max_time_len, 1, user_fnum, item_fnum, seed=seed,
+                           device=device)
+
+
+MODELS = {"SCORE": SCORE, "RIA": RIA, "RCA": RCA, "SCORE_USER": SCORE_USER, "SCORE_ITEM": SCORE_ITEM, "RRN": RRN, "GCMC": GCMC,
+          "GRU4Rec": GRU4Rec}
