@@ -7,6 +7,7 @@ import math
 import numpy as np
 import torch
 
+from helpers import check_dropped
 from oracle.score_oracle import TFAdam, _gru, batch_to_arrays
 
 LOGLOSS_EPS = 1e-7          # tf.losses.log_loss's default epsilon
@@ -109,13 +110,14 @@ def loss_and_grads(c, params, batch, reg_lambda, dtype=torch.float64):
     return out, {k: (v.grad if v.grad is not None else torch.zeros_like(v)).detach().numpy() for k, v in P.items()}
 
 
-def away_from_relu_kinks(c, params, batch, thr=1e-5):
+def away_from_relu_kinks(c, params, batch, thr=1e-5, max_dropped=None):
     """The batch without the samples that have a live relu pre-activation within thr of 0 (and not exactly 0): the gradient
-    of a relu network jumps there (tests/helpers.py away_from_relu_kinks).  At most a quarter of the batch may go."""
+    of a relu network jumps there (tests/helpers.py away_from_relu_kinks).  At most max_dropped samples may go (default: a quarter
+    of the batch)."""
     with torch.no_grad():
         per = forward(c, to_torch(params), batch)["relu_margin_per_sample"]
     keep = np.nonzero(per > thr)[0]
-    assert keep.size >= max(1, (3 * per.size) // 4), "more than a quarter of the batch sits on a relu kink: %r" % (per,)
+    check_dropped(per.size, keep.size, max_dropped)
     return {k: np.ascontiguousarray(np.asarray(v)[keep]) for k, v in batch.items()}, keep
 
 

@@ -8,6 +8,7 @@ import math
 import numpy as np
 import torch
 
+from helpers import check_dropped
 from oracle.score_oracle import TFAdam, _gru
 
 LOGLOSS_EPS = 1e-7          # tf.losses.log_loss's default epsilon
@@ -134,13 +135,14 @@ def loss_and_grads(c, params, batch, reg_lambda, keep_prob=1.0, dropout_masks=No
     return out, {k: (v.grad if v.grad is not None else torch.zeros_like(v)).detach().numpy() for k, v in P.items()}
 
 
-def away_from_relu_kinks(c, params, batch, thr=1e-5, keep_prob=1.0, dropout_masks=None):
+def away_from_relu_kinks(c, params, batch, thr=1e-5, keep_prob=1.0, dropout_masks=None, max_dropped=None):
     """The batch without the samples that have an fc1 / fc2 pre-activation within thr of 0: the gradient of a relu network
-    jumps there (tests/helpers.py away_from_relu_kinks).  At most a quarter of the batch may go.  -> (batch, masks, kept)"""
+    jumps there (tests/helpers.py away_from_relu_kinks).  At most max_dropped samples may go (default: a quarter of the batch).
+    -> (batch, masks, kept)"""
     with torch.no_grad():
         per = forward(c, to_torch(params), batch, 0.0, keep_prob, dropout_masks)["relu_margin_per_sample"]
     keep = np.nonzero(per > thr)[0]
-    assert keep.size >= max(1, (3 * per.size) // 4), "more than a quarter of the batch sits on a relu kink: %r" % (per,)
+    check_dropped(per.size, keep.size, max_dropped)
     b = {k: np.ascontiguousarray(np.asarray(v)[keep]) for k, v in batch.items()}
     dm = [np.ascontiguousarray(np.asarray(m)[keep]) for m in dropout_masks] if dropout_masks is not None else None
     return b, dm, keep

@@ -134,6 +134,8 @@ def test_device_only_events_order_streams():
     ev = _lib.DevEvent()
     x = torch.zeros(1 << 22, device=dev)
     y = torch.zeros_like(x)
+    lo, hi = torch.full((40,), -1.0, device=dev), torch.full((40,), -1.0, device=dev)
+    torch.cuda.synchronize()
     for i in range(1, 41):
         with torch.cuda.stream(a):
             x.fill_(float(i))
@@ -141,9 +143,15 @@ def test_device_only_events_order_streams():
         b.wait_event(ev)                       # (torch calls ev.wait(b))
         with torch.cuda.stream(b):
             y.copy_(x)
+            # what the consumer saw in THIS iteration, kept on the device: the last iteration alone sits behind a full
+            # synchronise, and the ordinary events of wait_stream below would hide a device-only event that orders nothing
+            torch.amin(x, 0, keepdim=True, out=lo[i - 1:i])
+            torch.amax(x, 0, keepdim=True, out=hi[i - 1:i])
         a.wait_stream(b)                       # (the next fill must not overtake the copy)
     torch.cuda.synchronize()
     assert float(y.min()) == 40.0 and float(y.max()) == 40.0
+    want = torch.arange(1, 41, dtype=torch.float32)
+    assert torch.equal(lo.cpu(), want) and torch.equal(hi.cpu(), want), (lo.cpu().tolist(), hi.cpu().tolist())
     ev.record()
     ev.synchronize()
     assert ev.query()

@@ -9,6 +9,7 @@ import numpy as np
 import pytest
 import torch
 
+import baseline_cases as bc
 import gru4rec_ref as gr
 from gru4rec_ref import batch_tuple
 from test_gpu_model import close
@@ -77,7 +78,7 @@ def test_forward_backward_against_restatement(D, H, T, Fu, Fi, B):
     P = gr.init_params(c, 3)
     b = _batches(c, B, 1, D + H + T)[0]
     b["label"] = (np.arange(B) % 2).astype(np.int32)
-    b, _, kept = gr.away_from_relu_kinks(c, P, b)
+    b, _, kept = gr.away_from_relu_kinks(c, P, b, max_dropped=max(2, B // 50))
     print("kept", kept.size, "of", B)
     out, go = gr.loss_and_grads(c, P, b, 0.0)
     want = (float(out["loss"].detach()), out["y_pred"].detach().numpy(), out["o1"].detach().numpy(), out["o2"].detach().numpy(), go)
@@ -87,6 +88,118 @@ def test_forward_backward_against_restatement(D, H, T, Fu, Fi, B):
     _check(composed, *want, "bit 13")
     # ... and the two forms against each other (they sum in different orders: not bit for bit)
     _check(stacked, composed["loss"], composed["y"], composed["o1"], composed["o2"], composed["grads"], "default vs bit 13")
+
+
+def _want(c, P, b):
+    out, go = gr.loss_and_grads(c, P, b, 0.0)
+    return out, (float(out["loss"].detach()), out["y_pred"].detach().numpy(), out["o1"].detach().numpy(), out["o2"].detach().numpy(), go)
+
+
+def _both_forms(c, P, b, want):
+    """both forms of the recurrences against the restatement and against each other (_check: loss, y, o1, o2, every gradient)"""
+    stacked = _pass(c, P, b, 0)
+    composed = _pass(c, P, b, COMPOSED)
+    _check(stacked, *want, "default")
+    _check(composed, *want, "bit 13")
+    _check(stacked, composed["loss"], composed["y"], composed["o1"], composed["o2"], composed["grads"], "default vs bit 13")
+    for got in (stacked, composed):
+        assert all(np.isfinite(v).all() for v in got["grads"].values()) and np.isfinite(got["loss"])
+    return stacked, composed
+
+
+@pytest.mark.parametrize("D,H,T,Fu,Fi,B,ML,seed", bc.G4R_SHORT)
+def test_short_batches_against_restatement(D, H, T, Fu, Fi, B, ML, seed):
+    """active_slices < T: the gather, the hoisted projection, both recurrences, the workspace and every backward product are
+    laid out on TA = max(length) slices.  Also the stacked form's workgroup edges (16 samples each): B = 1, 15, 16, 17, 31.
+    (tests/test_gru4rec_cpu.py proves the inputs: longest sample below T, batch size after the kink filter.)"""
+    c, P, b, kept, _ = bc.g4r_case(D, H, T, Fu, Fi, B, ML, seed)
+    Bk = len(b["label"])
+    print("kept", Bk, "of", B, "longest", int(b["user_seq_length"].max()))
+    m = _model(c, P)
+    assert m.device_batch(batch_tuple(b)).active_slices == int(b["user_seq_length"].max()) < c.T
+    out, want = _want(c, P, b)
+    stacked, _ = _both_forms(c, P, b, want)
+    assert stacked["o1"].shape[1] == int(b["user_seq_length"].max())
+    # the same batch with every slice computed: the skip changes the sums' shapes, not the result
+    m_all = _model(c, P)
+    m_all.skip_masked_slices = False
+    assert m_all.device_batch(batch_tuple(b)).active_slices == 0
+    lay, ws = m_all.forward_backward(batch_tuple(b), 0.0, 1.0)
+    la, ya = float(ws[lay.loss].item()), ws[lay.y_pred:lay.y_pred + Bk].cpu().numpy()
+    assert abs(stacked["loss"] - la) < 2e-6 * max(1.0, abs(la)), (stacked["loss"], la)
+    assert np.abs(stacked["y"] - ya).max() < 2e-6 * max(1.0, float(np.abs(ya).max()))
+    # eval() on the short batch
+    for flags in (0, COMPOSED):
+        pg, lab, _ = _model(c, P, flags).eval(None, batch_tuple(b), 1e-4)
+        po, lab_o, _ = gr.RefModel(c, P).eval(None, batch_tuple(b), 1e-4)
+        assert lab == lab_o and np.abs(np.asarray(pg) - np.asarray(po)).max() < 1e-4
+
+
+def test_samples_of_length_zero_against_restatement():
+    """dynamic_rnn with sequence_length 0: zero outputs and a zero final state.  Three samples of the batch (the first, one in
+    the middle, the last), the rest ragged; the table rows only they name get no gradient."""
+    c, P, b, kept, B = bc.g4r_case(*bc.G4R_ZERO_LEN, zero_len=True)
+    zero = np.nonzero(b["user_seq_length"] == 0)[0]
+    assert zero.size == 3 and zero[0] == 0 and zero[-1] == len(b["label"]) - 1
+    out, want = _want(c, P, b)
+    for got in _both_forms(c, P, b, want):
+        assert not got["o1"][zero].any() and not got["o2"][zero].any()
+        assert not got["grads"]["emb_mtx"][c.N - bc.FRESH:].any() and not got["grads"]["emb_mtx"][0].any()
+
+
+@pytest.mark.parametrize("shape,scale", bc.G4R_SATURATED)
+def test_saturated_recurrences_against_restatement(shape, scale):
+    """The table scaled until layer 1's states reach |h| > 0.999 (the fast sigmoid / tanh forms of gru_stack.hip and gru.hip at
+    the ends of their range), fc3 scaled down so that every prediction stays in [1e-3, 1 - 1e-3]: beyond that the reference's
+    own float32 log(1 - y + 1e-7) loses its precision and float64 stops being a fair yardstick (test_gru4rec_cpu.py asserts
+    both conditions on the restatement).  The bounds are the unsaturated ones."""
+    c, P, b, kept, B = bc.g4r_case(*shape, scale=scale)
+    out, want = _want(c, P, b)
+    assert float(out["o1"].detach().abs().max()) > 0.999
+    _both_forms(c, P, b, want)
+
+
+_TRAJ = {}
+
+
+def _reference_trajectory():
+    """the restatement's side of the trajectory tests, once for both forms"""
+    if not _TRAJ:
+        c = gr.Cfg(20011, *TMALL)
+        P = gr.init_params(c, 4)
+        bs = bc.g4r_trajectory(c)
+        ref = gr.RefModel(c, P)
+        losses = [ref.train(None, batch_tuple(b), 1e-3, 1e-4, keep_prob=1.0) for b in bs]
+        _TRAJ.update(c=c, P=P, bs=bs, losses=losses, params=ref.params, evals=[ref.eval(None, batch_tuple(b), 1e-4)[0] for b in (bs[0], bs[1])])
+    return _TRAJ
+
+
+@pytest.mark.parametrize("flags", [0, COMPOSED])
+def test_trajectory_whose_shape_changes_every_step(flags):
+    """Twelve train() steps on ONE model object whose B and active slices change from step to step, every "smaller after
+    larger" transition among them: the workspace is reused under a different layout each time (and parts of it are relied on
+    to hold zeros), and so are the per-shape caches.  Default configuration: two streams, time-tiled optimizer where it applies."""
+    t = _reference_trajectory()
+    c, bs = t["c"], t["bs"]
+    m = _model(c, t["P"], flags)
+    seen = []
+    for step, (b, lo) in enumerate(zip(bs, t["losses"])):
+        seen.append((len(b["label"]), m.device_batch(batch_tuple(b)).active_slices))
+        lg = m.train(None, batch_tuple(b), 1e-3, 1e-4, keep_prob=1.0)
+        print(step, seen[-1], lg, lo)
+        assert abs(lg - lo) < 2e-5 * max(1.0, abs(lo)), (step, seen[-1], lg, lo)
+    assert seen == [(B, 0 if ml is None else ml) for B, ml in bc.G4R_TRAJECTORY]
+    for b, po in zip((bs[0], bs[1]), t["evals"]):
+        pg, _, _ = m.eval(None, batch_tuple(b), 1e-4)
+        assert np.abs(np.asarray(pg) - np.asarray(po)).max() < 1e-4
+    got, steps = m.get_params(), len(bs)
+    assert set(got) == set(t["params"])
+    # the bound of test_gpu_gcmc.py::test_virtual_ranks_match_single_device, on the same two bodies: the dense variables, the table
+    dense = sorted(k for k in got if k != "emb_mtx")
+    for what, keys in (("dense", dense), ("emb_mtx", ["emb_mtx"])):
+        d = np.concatenate([np.abs(got[k].reshape(-1) - t["params"][k].reshape(-1)) for k in keys])
+        print(what, float((d <= 3e-6).mean()), float(d.max()))
+        assert (d <= 3e-6).mean() > 0.999 and d.max() <= 2.2 * steps * 1e-3, what
 
 
 def test_form_taken_per_hidden_size():
@@ -181,7 +294,7 @@ def test_one_step_with_explicit_dropout_masks(flags):
     b = _batches(c, B, 1, 21)[0]
     rng = np.random.default_rng(22)
     masks = [(rng.random((B, 200)) < 0.8).astype(np.uint8), (rng.random((B, 80)) < 0.8).astype(np.uint8)]
-    b, masks, kept = gr.away_from_relu_kinks(c, P, b, keep_prob=0.8, dropout_masks=masks)
+    b, masks, kept = gr.away_from_relu_kinks(c, P, b, keep_prob=0.8, dropout_masks=masks, max_dropped=max(2, B // 50))
     print("kept", kept.size, "of", B)
     # (reg_lambda 0: get_grads() is the data term's gradient; the L2 term's is added by the optimizer step, test above)
     out, go = gr.loss_and_grads(c, P, b, 0.0, 0.8, masks)

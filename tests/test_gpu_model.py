@@ -248,6 +248,48 @@ def test_masked_slices_skipped_vs_oracle(mt):
     assert np.array_equal(m_all.get_params()["emb_mtx"][dead_only], P["emb_mtx"][dead_only])
 
 
+@pytest.mark.parametrize("flags", [0, 512])
+def test_samples_of_length_zero_vs_oracle(flags):
+    """length == 0 (legal for dynamic_rnn: zero outputs, zero final state): three samples of the batch -- the first, one in the
+    middle, the last -- the rest ragged.  The attention then takes a softmax over an all-masked row (uniform in TF, over zero
+    outputs).  The per-sample form (flags 0) and the layered one (bit 9) against the oracle: loss, predictions, every gradient,
+    two optimizer steps.  (The oracle alone drops none of these 64 samples at the kink filter: counted on the CPU; cap 0 + 2.)"""
+    from helpers import away_from_relu_kinks
+    cfg = so.Cfg(4000, 16, 32, 8, 6, 3, 4, "SCORE")
+    rng = np.random.default_rng(29)
+    P = so.init_params(cfg, 4)
+    B = 64
+    b = random_batch(rng, cfg, B)
+    b["label"] = (np.arange(B) % 2).astype(np.int32)
+    b["length"][[0, B // 2, B - 1]] = 0
+    b, _, keep = away_from_relu_kinks(cfg, P, b, max_dropped=2)
+    Bk = keep.size
+    zero = np.nonzero(b["length"] == 0)[0]
+    assert zero.size == 3 and zero[0] == 0 and zero[-1] == Bk - 1 and int(b["length"].max()) == cfg.T
+    m = make_model(cfg, P)
+    m.debug_flags = flags
+    assert m.persample_form(Bk, 0) == (flags == 0)
+    lay, ws = m.forward_backward(batch_tuple(b), 0.0, 1.0)
+    loss, y = float(ws[lay.loss].item()), ws[lay.y_pred:lay.y_pred + Bk].cpu().numpy()
+    g = m.get_grads()
+    oo, go = so.loss_and_grads(cfg, P, b, 0.0)
+    want = float(oo["loss"].detach())
+    assert abs(loss - want) < 2e-5 * max(1.0, abs(want)), (loss, want)
+    assert np.abs(y - oo["y_pred"].detach().numpy()).max() < LOGIT_TOL
+    for k in go:
+        assert np.isfinite(g[k]).all(), k
+        ok, err = close(g[k].reshape(np.asarray(go[k]).shape), go[k], rtol=2e-4, atol=2e-6)
+        assert ok, (k, err)
+    om = so.OracleModel(cfg.N, cfg.D, cfg.H, cfg.T, cfg.K, cfg.Fu, cfg.Fi, "SCORE", params={k: v.copy() for k, v in P.items()})
+    for _ in range(2):
+        lg = m.train(None, batch_tuple(b), 1e-3, 1e-4, keep_prob=1.0)
+        lo = om.train(None, batch_tuple(b), 1e-3, 1e-4, keep_prob=1.0)
+        assert abs(lg - lo) < 2e-5 * max(1.0, abs(lo)), (lg, lo)
+    pg, _, _ = m.eval(None, batch_tuple(b), 1e-4)
+    po, _, _ = om.eval(None, batch_tuple(b), 1e-4)
+    assert np.abs(np.asarray(pg) - np.asarray(po)).max() < LOGIT_TOL
+
+
 def test_fused_and_layerwise_paths_agree():
     # the one-launch head (head_fused.hip) and attention tail against the layer-by-layer paths they replace (still
     # taken for shapes the fused kernels do not cover): same predictions, loss and gradients

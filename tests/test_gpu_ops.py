@@ -399,6 +399,121 @@ def test_gru_fwd_bwd(B, T, H):
     assert np.allclose(d[:, :2 * H].sum(0).numpy(), bg.grad.numpy(), rtol=2e-4, atol=5e-5)
 
 
+# pre-activations from exactly 0 to far beyond where __expf overflows (88.7) or flushes (-87.3 -> -103.9), both signs
+SATURATION_GRID = np.unique(np.concatenate([s * np.array([0, 1e-6, 1e-3, 0.1, 1, 5, 10, 20, 44, 87, 89, 104, 1e4]) for s in (1, -1)]))
+
+
+def _grid_xproj(B, T, H):
+    """[B, T, 3H] float32: every (x_u, x_c) pair of the grid over the B * H elements of a step, x_r cycling through the grid
+    at another stride; the same rows at every step"""
+    n = SATURATION_GRID.size
+    assert B * H >= n * n
+    e = np.arange(B * H).reshape(B, H)
+    xr, xu, xc = SATURATION_GRID[(7 * e + 3) % n], SATURATION_GRID[(e // n) % n], SATURATION_GRID[e % n]
+    x = np.concatenate([xr, xu, xc], 1).astype(np.float32)
+    return np.ascontiguousarray(np.repeat(x[:, None, :], T, 1))
+
+
+# one H per kernel family score_gru_fwd / score_gru_bwd dispatch to: the register form (16, 32, 64), the bf16x3 form (128) and
+# the state-in-LDS form every other H takes (20; 256, which inside the model is the streaming kernel's width)
+@pytest.mark.parametrize("B,H", [(48, 16), (20, 32), (10, 64), (20, 128), (35, 20), (3, 256)])
+def test_gru_activations_over_the_saturation_grid(B, H):
+    """With T = 1 and the zero initial state the recurrence is an element-wise evaluator, whatever the weights:
+    out = final = (1 - sigmoid(x_u)) tanh(x_c), and for g = dout + dfinal: dx_c = g (1 - u)(1 - c^2), dx_u = -g c u (1 - u),
+    dx_r = 0 (the state is zero -- in particular no NaN from inf * 0).  Against float64 numpy, at the bounds of
+    test_gru_fwd_bwd; everything finite on the whole grid."""
+    lib = _lib.load()
+    rng = np.random.default_rng(H)
+    T = 1
+    xp = _grid_xproj(B, T, H)
+    Wg = dev((rng.standard_normal((H, 2 * H)) / np.sqrt(H)).astype(np.float32))
+    Wc = dev((rng.standard_normal((H, H)) / np.sqrt(H)).astype(np.float32))
+    dl = dev(np.ones(B, dtype=np.int32))
+    dxp = dev(xp.reshape(B * T, 3 * H))
+    out = torch.zeros((B * T, H), device="cuda")
+    gates = torch.zeros((B * T, 3 * H), device="cuda")
+    fin = torch.zeros((B, H), device="cuda")
+    _lib.check(lib.score_gru_fwd(B, T, H, P(dxp), P(Wg), 2 * H, P(Wc), H, P(dl), P(out), H, P(gates), P(fin), stream()), "gru_fwd")
+    torch.cuda.synchronize()
+    x64 = xp.reshape(B, 3 * H).astype(np.float64)
+    with np.errstate(over="ignore"):
+        u = 1.0 / (1.0 + np.exp(-x64[:, H:2 * H]))
+    c = np.tanh(x64[:, 2 * H:])
+    want = (1.0 - u) * c
+    o, f = out.cpu().numpy(), fin.cpu().numpy()
+    print("max |out - want|", float(np.abs(o - want).max()))
+    assert np.isfinite(o).all() and np.isfinite(f).all() and np.isfinite(gates.cpu().numpy()).all()
+    assert np.allclose(o, want, rtol=1e-5, atol=2e-6) and np.allclose(f, want, rtol=1e-5, atol=2e-6)
+    go = rng.standard_normal((B, H)).astype(np.float32)
+    gf = rng.standard_normal((B, H)).astype(np.float32)
+    dgo, dgf = dev(go), dev(gf)
+    dxproj = torch.full((B * T, 3 * H), float("nan"), device="cuda")
+    rh = torch.zeros((B * T, H), device="cuda")
+    hprev = torch.zeros((B * T * H + 3 * H * H,), device="cuda")
+    _lib.check(lib.score_gru_bwd(B, T, H, P(Wg), 2 * H, P(Wc), H, P(dl), P(out), H, P(gates), P(dgo), H, P(dgf),
+                                 P(dxproj), P(rh), P(hprev), stream()), "gru_bwd")
+    torch.cuda.synchronize()
+    d = dxproj.cpu().numpy()
+    g = go.astype(np.float64) + gf
+    assert np.isfinite(d).all()
+    for what, got, wantd in (("dx_c", d[:, 2 * H:], g * (1 - u) * (1 - c * c)), ("dx_u", d[:, H:2 * H], -g * c * u * (1 - u))):
+        err = np.abs(got - wantd) - 2e-4 * np.abs(wantd)
+        i = np.unravel_index(np.argmax(err), err.shape)
+        print(what, "worst: got", got[i], "want", wantd[i], "at x_u", x64[:, H:2 * H][i], "x_c", x64[:, 2 * H:][i], "g", g[i])
+        assert np.allclose(got, wantd, rtol=2e-4, atol=2e-5), what
+    assert not d[:, :H].any()
+    assert not rh.cpu().numpy().any() and not hprev[:B * T * H].cpu().numpy().any()
+
+
+@pytest.mark.parametrize("B,H", [(48, 16), (20, 32), (10, 64), (20, 128), (35, 20), (3, 256)])
+def test_gru_three_steps_over_the_saturation_grid(B, H):
+    """The same grid at each of three steps: the carried state is driven to +-1 and the recurrent products matter.  Against the
+    oracle's _gru in float64 (x enters through selector kernels, so that x . Wx is the grid itself), ragged lengths."""
+    lib = _lib.load()
+    rng = np.random.default_rng(H + 1)
+    T = 3
+    xp = _grid_xproj(B, T, H)
+    Wgh = (rng.standard_normal((H, 2 * H)) / np.sqrt(H)).astype(np.float32)
+    Wch = (rng.standard_normal((H, H)) / np.sqrt(H)).astype(np.float32)
+    length = rng.integers(1, T + 1, B)
+    length[0] = T
+    eye = np.eye(3 * H)
+    x = torch.tensor(xp.astype(np.float64), requires_grad=True)
+    Wg64 = torch.tensor(np.concatenate([eye[:, :2 * H], Wgh.astype(np.float64)], 0))
+    Wc64 = torch.tensor(np.concatenate([eye[:, 2 * H:], Wch.astype(np.float64)], 0))
+    outs, hfin = so._gru(x, torch.as_tensor(length), Wg64, torch.zeros(2 * H, dtype=torch.float64), Wc64,
+                         torch.zeros(H, dtype=torch.float64), H)
+    go = torch.tensor(rng.standard_normal((B, T, H)).astype(np.float32))
+    gf = torch.tensor(rng.standard_normal((B, H)).astype(np.float32))
+    ((outs * go.double()).sum() + (hfin * gf.double()).sum()).backward()
+    assert float(outs.detach().abs().max()) > 0.999999
+    Wg, Wc, dl = dev(Wgh), dev(Wch), dev(length.astype(np.int32))
+    dxp = dev(xp.reshape(B * T, 3 * H))
+    out = torch.zeros((B * T, H), device="cuda")
+    gates = torch.zeros((B * T, 3 * H), device="cuda")
+    fin = torch.zeros((B, H), device="cuda")
+    _lib.check(lib.score_gru_fwd(B, T, H, P(dxp), P(Wg), 2 * H, P(Wc), H, P(dl), P(out), H, P(gates), P(fin), stream()), "gru_fwd")
+    torch.cuda.synchronize()
+    o, f = out.cpu().numpy(), fin.cpu().numpy()
+    want = outs.detach().numpy().reshape(B * T, H)
+    print("max |out - want|", float(np.abs(o - want).max()))
+    assert np.isfinite(o).all() and np.isfinite(f).all()
+    assert np.allclose(o, want, rtol=1e-5, atol=2e-6)
+    assert np.allclose(f, hfin.detach().numpy(), rtol=1e-5, atol=2e-6)
+    dgo, dgf = dev(go), dev(gf)
+    dxproj = torch.full((B * T, 3 * H), float("nan"), device="cuda")
+    rh = torch.zeros((B * T, H), device="cuda")
+    hprev = torch.zeros((B * T * H + 3 * H * H,), device="cuda")
+    _lib.check(lib.score_gru_bwd(B, T, H, P(Wg), 2 * H, P(Wc), H, P(dl), P(out), H, P(gates), P(dgo), H, P(dgf),
+                                 P(dxproj), P(rh), P(hprev), stream()), "gru_bwd")
+    torch.cuda.synchronize()
+    d = dxproj.cpu().numpy()
+    wantd = x.grad.numpy().reshape(B * T, 3 * H)
+    print("max |dxproj - want|", float(np.abs(d - wantd).max()), "of", float(np.abs(wantd).max()))
+    assert np.isfinite(d).all()
+    assert np.allclose(d, wantd, rtol=2e-4, atol=2e-5)
+
+
 def test_adam_matches_tf_form():
     lib = _lib.load()
     rng = np.random.default_rng(1)

@@ -47,12 +47,20 @@ def _run(m, b, flags, lam=1e-4, keep=1.0, masks=None):
     return out
 
 
-def _forms_and_oracle(shape, mt, seed, adam_steps=2):
+# What the oracle's forward pass alone (on the CPU, no GPU involved) drops from these tests' inputs at thr = 1e-5; the cap handed to
+# away_from_relu_kinks is that count plus 2, not the helper's default quarter of the batch.  (shape index, model type) -> samples
+# dropped, for test_forms_agree_and_match_the_oracle (every case not listed: 0) ...
+DROPPED_FORMS = {(0, "SCORE"): 1, (1, "SCORE_USER"): 1, (1, "SCORE_ITEM"): 1, (3, "SCORE"): 1, (4, "SCORE_USER"): 1, (5, "SCORE"): 5}
+# ... and (seed, shape index) -> samples dropped, for test_forms_match_the_oracle_on_arbitrary_seeds (not listed: 0)
+DROPPED_ARBITRARY = {(17, 0): 1, (101, 0): 2, (2024, 0): 1, (555, 0): 2, (555, 4): 1}
+
+
+def _forms_and_oracle(shape, mt, seed, adam_steps=2, counted=0):
     N, D, H, T, K, Fu, Fi, B, maxlen = shape
     cfg = so.Cfg(N, D, H, T, K, Fu, Fi, mt)
     P = so.init_params(cfg, 5)
     b_all = _batch(cfg, B, maxlen, seed)
-    b, _, keep = away_from_relu_kinks(cfg, P, b_all)
+    b, _, keep = away_from_relu_kinks(cfg, P, b_all, max_dropped=counted + 2)
     m = make_model(cfg, P)
     ref = _run(m, b, 512)
     for flags in (0, 1024, 2048):
@@ -91,14 +99,14 @@ def _forms_and_oracle(shape, mt, seed, adam_steps=2):
 def test_forms_agree_and_match_the_oracle(shape, mt):
     if mt != "SCORE" and shape[7] > 100:
         pytest.skip("the ablations' head wiring is covered at the smaller batches")
-    _forms_and_oracle(shape, mt, 1000 + 37 * SHAPES.index(shape) + len(mt))
+    _forms_and_oracle(shape, mt, 1000 + 37 * SHAPES.index(shape) + len(mt), counted=DROPPED_FORMS.get((SHAPES.index(shape), mt), 0))
 
 
 @pytest.mark.parametrize("seed", ARBITRARY_SEEDS)
 def test_forms_match_the_oracle_on_arbitrary_seeds(seed):
     """the reference's Tmall shape (B = 200: ~2 * 10^5 relu units per batch) and the odd-width shape, five seeds nobody chose"""
-    _forms_and_oracle(SHAPES[0], "SCORE", seed, adam_steps=0)
-    _forms_and_oracle(SHAPES[4], "SCORE", seed, adam_steps=1)
+    _forms_and_oracle(SHAPES[0], "SCORE", seed, adam_steps=0, counted=DROPPED_ARBITRARY.get((seed, 0), 0))
+    _forms_and_oracle(SHAPES[4], "SCORE", seed, adam_steps=1, counted=DROPPED_ARBITRARY.get((seed, 4), 0))
 
 
 def test_the_switch_switches_and_dropout_is_the_same_mask():

@@ -132,7 +132,9 @@ def test_cfg2_exact_shape_one_step_vs_oracle(seed):
     P = so.init_params(cfg, 11)
     pool = [dict(zip(NAMES, world.batch(B, s_))) for s_ in (seed, seed + 100)]
     pool = {k: np.concatenate([np.asarray(p_[k]) for p_ in pool]) for k in NAMES}
-    b, _, keep = away_from_relu_kinks(cfg, P, pool)
+    # what the oracle's forward pass alone (on the CPU) drops from the pool of 512 at thr = 1e-5, per seed; the cap is that plus 2
+    counted = {7: 6, 1: 5, 2: 6, 3: 5, 4: 2}
+    b, _, keep = away_from_relu_kinks(cfg, P, pool, max_dropped=counted[seed] + 2)
     assert keep.size >= B
     b = {k: np.ascontiguousarray(v[:B]) for k, v in b.items()}
     m = make_model(cfg, P)

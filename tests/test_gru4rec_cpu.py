@@ -155,3 +155,80 @@ def test_models_table_and_sharded_refusal():
     from score_amd.dist import ShardedSCORE
     with pytest.raises(ValueError, match="GRU4Rec"):
         ShardedSCORE(100, 16, 32, 50, 1, 3, 4, comm=object(), model_type="GRU4Rec")
+
+
+def _transitions(traj, T):
+    """(B falls, TA falls) pairs seen between consecutive steps of a (B, longest or None) list"""
+    ta = [T if ml is None else ml for _, ml in traj]
+    return {(traj[i + 1][0] < traj[i][0], ta[i + 1] < ta[i]) for i in range(len(traj) - 1)}
+
+
+def test_inputs_of_the_gpu_edge_tests_have_the_properties_they_are_run_for():
+    """tests/test_gpu_gru4rec.py's new inputs, rebuilt from the same constructors (tests/baseline_cases.py) and judged on the
+    float64 restatement alone: each assertion is the property whose absence made the older inputs blind."""
+    import baseline_cases as bc
+    # short batches: the longest sample is below T; the kink filter takes at most cap(B); the batch that remains sits where it
+    # was meant to against the stacked kernel's 16 samples per workgroup
+    sizes = {}
+    for D, H, T, Fu, Fi, B, ML, seed in bc.G4R_SHORT:
+        c, P, b, kept, _ = bc.g4r_case(D, H, T, Fu, Fi, B, ML, seed)
+        Bk, longest = len(b["label"]), int(b["user_seq_length"].max())
+        assert 1 <= longest <= ML < T and int(b["user_seq_length"].min()) >= 1
+        assert B - Bk <= bc.cap(B) and (Bk == B or B > 17)
+        assert Bk == B if B % 16 == 0 else Bk % 16 != 0            # a full last workgroup only where one was meant
+        sizes.setdefault(H, set()).add(Bk)
+    stacked = set().union(*(v for h, v in sizes.items() if h in (16, 32, 64)))
+    assert {1, 15, 16, 17} <= stacked and any(16 < x < 32 for x in stacked) and 48 in sizes         # (48: the composed form only)
+    assert any(s[6] == 1 for s in bc.G4R_SHORT)                    # layer 2 one step behind a one-step layer 1
+    # length 0: three samples, first / middle / last after the filter; zero outputs and final state; finite loss and gradients;
+    # nothing on the rows only they name
+    c, P, b, kept, B = bc.g4r_case(*bc.G4R_ZERO_LEN, zero_len=True)
+    zero = np.nonzero(b["user_seq_length"] == 0)[0]
+    assert B - len(kept) <= bc.cap(B) and zero.size == 3 and zero[0] == 0 and zero[-1] == len(kept) - 1
+    assert int(b["user_seq_length"].max()) > 1 and np.unique(b["user_seq_length"]).size > 5           # (the rest: ragged)
+    out, g = gr.loss_and_grads(c, P, b, 0.0)
+    for k in ("o1", "o2", "h2"):
+        assert not out[k].detach().numpy()[zero].any(), k
+    assert np.isfinite(float(out["loss"].detach())) and all(np.isfinite(v).all() for v in g.values())
+    fresh = np.arange(c.N - bc.FRESH, c.N)
+    assert np.isin(b["user_seq"][zero], fresh).all() and not np.isin(b["user_seq"][b["user_seq_length"] > 0], fresh).any()
+    assert not np.isin(b["target_user"], fresh).any() and not np.isin(b["target_item"], fresh).any()
+    assert not g["emb_mtx"][fresh].any() and np.abs(g["emb_mtx"]).max() > 0
+    # saturation: the recurrences' states reach 1, the predictions stay where float64 is a fair yardstick for the loss
+    for shape, scale in bc.G4R_SATURATED:
+        c, P, b, kept, B = bc.g4r_case(*shape, scale=scale)
+        assert B - len(kept) <= bc.cap(B)
+        with torch.no_grad():
+            out = gr.forward(c, gr.to_torch(P), b)
+        y = out["y_pred"].numpy()
+        assert float(out["o1"].abs().max()) > 0.999 and 1e-3 <= y.min() and y.max() <= 1 - 1e-3, (shape, y.min(), y.max())
+    # the trajectory: every batch has the listed size and longest sample, and B and TA each fall (alone and together) on the way
+    c = gr.Cfg(20011, 16, 32, 50, 3, 4)
+    bs = bc.g4r_trajectory(c)
+    assert [(len(b["label"]), int(b["user_seq_length"].max())) for b in bs] == [(B, ml or c.T) for B, ml in bc.G4R_TRAJECTORY]
+    assert {(True, True), (True, False), (False, True)} <= _transitions(bc.G4R_TRAJECTORY, c.T)
+    assert len(bs) >= 12 and (1, 1) in bc.G4R_TRAJECTORY
+
+
+def test_kink_filter_takes_no_more_than_its_cap_from_the_committed_inputs():
+    """the inputs of the older parity tests under the tighter cap max(2, B // 50): what the restatement alone drops (counted
+    here, never on a GPU): 1, 0, 1, 1, 0, 1, 0, 0 of the eight shapes"""
+    import test_gpu_gru4rec as tg
+    dropped = []
+    for D, H, T, Fu, Fi, B in tg.SHAPES:
+        c = gr.Cfg(3000, D, H, T, Fu, Fi)
+        P = gr.init_params(c, 3)
+        b = tg._batches(c, B, 1, D + H + T)[0]
+        b["label"] = (np.arange(B) % 2).astype(np.int32)
+        _, _, kept = gr.away_from_relu_kinks(c, P, b, max_dropped=max(2, B // 50))
+        dropped.append(B - kept.size)
+    assert dropped == [1, 0, 1, 1, 0, 1, 0, 0], dropped
+    c = gr.Cfg(3000, *tg.TMALL)
+    b = tg._batches(c, 200, 1, 21)[0]
+    rng = np.random.default_rng(22)
+    masks = [(rng.random((200, 200)) < 0.8).astype(np.uint8), (rng.random((200, 80)) < 0.8).astype(np.uint8)]
+    _, _, kept = gr.away_from_relu_kinks(c, gr.init_params(c, 3), b, keep_prob=0.8, dropout_masks=masks, max_dropped=4)
+    # the argument itself: the cap holds, the default is the old quarter
+    with pytest.raises(AssertionError):
+        gr.away_from_relu_kinks(c, gr.init_params(c, 3), b, thr=0.05, max_dropped=4)
+    gr.away_from_relu_kinks(c, gr.init_params(c, 3), b, thr=1e-4)
