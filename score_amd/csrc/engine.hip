@@ -232,6 +232,8 @@ static int64_t ps_image_region_floats(const Dims& d) {
   return im.total;
 }
 
+// distance between the replicas of the folded first attention layer's weight (head.hip)
+static inline int64_t weff_copy_stride(const Dims& d) { return align_up64(2 * (int64_t)d.Dk * AT1 + 48, 4); }
 void build_ws_raw(const Dims& d, int B, WS* w) {
   int64_t cur = 0;
   auto take = [&](int64_t n) { int64_t o = cur; cur = align_up64(cur + (n > 0 ? n : 4), 4); return o; };
@@ -249,7 +251,7 @@ void build_ws_raw(const Dims& d, int B, WS* w) {
   for (int s = 0; s < 2; ++s) w->gates[s] = take(BT * 3 * d.H);
   w->q = take((int64_t)B * d.Dk);
   w->ainp = take(BT * 2 * d.Dk);
-  w->weff = take(SCORE_WEFF_COPIES * align_up64(2 * (int64_t)d.Dk * AT1 + 48, 4)); w->wq = take((int64_t)d.Dk * AT1); w->qz = take((int64_t)B * AT1);
+  w->weff = take(SCORE_WEFF_COPIES * weff_copy_stride(d)); w->wq = take((int64_t)d.Dk * AT1); w->qz = take((int64_t)B * AT1);
   w->a1 = take(BT * AT1); w->a2 = take(BT * AT2);
   w->bn = take((int64_t)B * d.Dhead);
   w->f1 = take((int64_t)B * FC1); w->f2 = take((int64_t)B * FC2);
@@ -430,30 +432,48 @@ static int side_stream(const score_state_t* st, SideStream** out) {
   *out = &sd;
   return 0;
 }
-// debug_flags bit 12 (4096): no second stream at all -- everything the passes would fork runs on the caller's stream, in
-// launch order (the context's events are still recorded and waited for: on one stream those are no-ops).  What a
+// A/B switches of the launch sequence: score_state_t.debug_flags only (round 4: the environment switches of rounds 1 - 3 --
+// SCORE_WGRAD_SIDE / _EARLY, SCORE_PANEL_DX, SCORE_GEMM_TILED, SCORE_GRU_STEPWISE, SCORE_GRU_BIAS_COLSUM, SCORE_HEAD_UNFUSED,
+// SCORE_ATTN_*_UNFUSED -- were decided A/Bs or duplicates of a flag bit, and a process-wide switch read once cannot be
+// flipped by the test that wants to compare the two paths).  include/score_hip.h describes the bits; flags_of is the one
+// place that reads them.
+enum {
+  DF_GRU_STEPWISE = 1, DF_HEAD_FUSED_ANY_B = 2, DF_GRU_F32_REC = 4, DF_NO_PANEL = 8, DF_PANEL_DX = 16, DF_SORT_LIB = 32,
+  DF_HEAD_UNFUSED = 64, DF_ATTN_UNFUSED = 128, DF_SORT_OWN = 256, DF_NO_PS = 512, DF_PS_FWD_ONLY = 1024, DF_PS_BWD_ONLY = 2048,
+  DF_ONE_STREAM = 4096, DF_G4R_COMPOSED = 8192, DF_PRODUCTS_LATE = 16384
+};
+struct Flags {
+  bool gru_stepwise, head_fused_any_b, gru_f32_rec, no_panel, panel_dx, sort_lib, head_unfused, attn_unfused, sort_own, no_ps,
+      ps_fwd_only, ps_bwd_only, one_stream, g4r_composed, products_late;
+};
+static inline Flags flags_of(const score_state_t* st) {
+  auto on = [st](int bit) { return (st->debug_flags & bit) != 0; };
+  Flags o;
+  o.gru_stepwise = on(DF_GRU_STEPWISE); o.head_fused_any_b = on(DF_HEAD_FUSED_ANY_B); o.gru_f32_rec = on(DF_GRU_F32_REC);
+  o.no_panel = on(DF_NO_PANEL); o.panel_dx = on(DF_PANEL_DX); o.sort_lib = on(DF_SORT_LIB); o.sort_own = on(DF_SORT_OWN);
+  o.head_unfused = on(DF_HEAD_UNFUSED); o.attn_unfused = on(DF_ATTN_UNFUSED); o.no_ps = on(DF_NO_PS);
+  o.ps_fwd_only = on(DF_PS_FWD_ONLY); o.ps_bwd_only = on(DF_PS_BWD_ONLY); o.one_stream = on(DF_ONE_STREAM);
+  o.g4r_composed = on(DF_G4R_COMPOSED); o.products_late = on(DF_PRODUCTS_LATE);
+  return o;
+}
+// Flags.one_stream (debug_flags bit 12): no second stream at all -- everything the passes would fork runs on the caller's
+// stream, in launch order (the context's events are still recorded and waited for: on one stream those are no-ops).  What a
 // suspected stream race is compared against.
 static int side_stream(const score_state_t* st, hipStream_t s, SideStream** out) {
   SideStream* real = nullptr;
   SCORE_TRY(side_stream(st, &real));
-  if (!st || !(st->debug_flags & 4096)) { *out = real; return 0; }
+  if (!st || !flags_of(st).one_stream) { *out = real; return 0; }
   static thread_local SideStream inl;
   const hipStream_t was = inl.fwd_on;
   inl = *real; inl.st = s; inl.fwd_on = was;
   *out = &inl;
   return 0;
 }
-// A/B switches of the launch sequence: score_state_t.debug_flags only (round 4: the environment switches of rounds 1 - 3 --
-// SCORE_WGRAD_SIDE / _EARLY, SCORE_PANEL_DX, SCORE_GEMM_TILED, SCORE_GRU_STEPWISE, SCORE_GRU_BIAS_COLSUM, SCORE_HEAD_UNFUSED,
-// SCORE_ATTN_*_UNFUSED -- were decided A/Bs or duplicates of a flag bit, and a process-wide switch read once cannot be
-// flipped by the test that wants to compare the two paths)
-struct Flags { bool head_unfused, attn_unfused, gru_stepwise; };
-static inline Flags flags_of(const score_state_t* st) {
-  Flags f;
-  f.head_unfused = (st->debug_flags & 64) != 0;
-  f.attn_unfused = (st->debug_flags & 128) != 0;
-  f.gru_stepwise = (st->debug_flags & 1) != 0;
-  return f;
+// the side stream behind everything `s` holds so far
+static inline int fork_side(SideStream* side, hipStream_t s) {
+  HIPTRY(hipEventRecord(side->fork, s));
+  HIPTRY(hipStreamWaitEvent(side->st, side->fork, 0));
+  return 0;
 }
 
 #define G(call) SCORE_TRY(call)
@@ -466,99 +486,311 @@ static inline int gemm_mode_call(int x3, int tr, int M, int N, int K, const floa
                     s);
 }
 // optional stage boundary events (hipEvent_t handles) recorded on the launch stream
-#define EV(i)                                                                \
-  do {                                                                       \
-    if (stage_events && stage_events[i]) {                                   \
-      hipError_t ee__ = hipEventRecord((hipEvent_t)stage_events[i], s);      \
-      if (ee__ != hipSuccess) return (int)ee__;                              \
-    }                                                                        \
-  } while (0)
+#define EV(i) \
+  do { if (stage_events && stage_events[i]) HIPTRY(hipEventRecord((hipEvent_t)stage_events[i], s)); } while (0)
+
+// ---------------------------------------------------------------- what a pass and its helpers share
+// ids at or past this row count are out of range (the kernels compare 32-bit ids)
+static inline uint32_t clamp_rows(int64_t n) { return (uint32_t)(n < 0x80000000ll ? n : 0x80000000ll); }
+static inline int global_batch(const score_state_t* st, int B) { return st->global_batch > 0 ? st->global_batch : B; }
+
+struct Pass {
+  Dims d; Params P; WS w; Flags fl;
+  const score_state_t* st; const score_batch_t* bt;
+  int B, T, BT, H;           // T: the time slices computed (active_T)
+  int x3, Bg;                // GF_X3 under score_state_t.gemm_mode 1; the batch the loss is averaged over
+  uint32_t n_rows;           // score_state_t.n_table_rows, clamped
+  int64_t weff_stride;
+  float rs;                  // bn1 at inference statistics: 1 / sqrt(1 + eps)
+  float* ws; const float* W; float* scratch;
+  hipStream_t s;             // the launch stream
+};
+// c->d comes from make_dims; st / bt have passed the entry point's argument checks
+static int pass_fill(Pass* c, const score_state_t* st, const score_batch_t* bt, void* stream) {
+  const Dims& d = c->d;
+  build_layout(d, nullptr, 0, &c->P);
+  c->st = st; c->bt = bt; c->fl = flags_of(st);
+  c->B = bt->B; c->T = active_T(d, bt); c->H = d.H; c->BT = c->B * c->T;
+  build_ws(d, c->B, &c->w);
+  if (c->w.total * 4 > st->workspace_bytes) return SCORE_E_WORKSPACE;
+  c->x3 = st->gemm_mode == 1 ? GF_X3 : 0; c->Bg = global_batch(st, c->B); c->n_rows = clamp_rows(st->n_table_rows);
+  c->weff_stride = weff_copy_stride(d); c->rs = (float)(1.0 / sqrt(1.0 + 1e-3));
+  c->ws = st->workspace; c->W = st->w; c->scratch = c->ws + c->w.scratch;
+  c->s = (hipStream_t)stream;
+  return 0;
+}
+// side sd's block of the concatenated [Wx_gates | Wx_cand ; b_gates | b_cand] copy (score_launch_weight_prep)
+static inline const float* wxcat(const Pass& c, int sd) { return c.ws + c.w.wxcat + (int64_t)sd * (c.d.Ic + 1) * 3 * c.H; }
+// what the step derives from the weights alone, in ONE launch: the [Wx_gates | Wx_cand] copies for the hoisted GRU input
+// projections, the folded first attention layer (dense_3 on [q, k, q-k, q*k], head.hip) and the L2 norm's partial sums
+// (three launches before round 4: the reference's own batch sizes are bound by the host's launch calls)
+static int weight_prep(const Pass& c, hipStream_t on) {
+  const Dims& d = c.d; const Params& P = c.P; const WS& w = c.w; const float* W = c.W;
+  return score_launch_weight_prep(W + P.gk[0], W + P.ck[0], W + P.gb[0], W + P.cb[0], W + P.gk[1], W + P.ck[1], W + P.gb[1],
+                                  W + P.cb[1], d.Is[0], d.Is[1], d.Ic, d.H, c.ws + w.wxcat, d.Dk, AT1,
+                                  d.attn ? W + P.at_w[1] : nullptr, c.ws + w.weff, c.ws + w.wq, SCORE_WEFF_COPIES, c.weff_stride, W,
+                                  P.n_reg, c.ws + w.part, on);
+}
+
+// ---------------------------------------------------------------- the recurrences' argument blocks
+static void gru_header(const Pass& c, GruArgs* ga) {
+  memset(ga, 0, sizeof(*ga));
+  ga->B = c.B; ga->T = c.T; ga->H = c.H; ga->length = c.bt->length;
+  ga->nw8 = 1;     // H = 128: two waves per SIMD hide the LDS/epilogue latency (measured -0.08 ms/step)
+  ga->tmp = c.ws + c.w.gru_tmp; ga->tmp_floats = c.w.gru_tmp_floats;
+  ga->x3 = c.x3 != 0; ga->x3_rec = ga->x3 && !c.fl.gru_f32_rec; ga->stepwise = c.fl.gru_stepwise;
+}
+// a side's h rows of its kernels, its saved outputs and gates: what both directions read
+static void gru_side(const Pass& c, int sd, GruSide* g) {
+  const int H = c.H;
+  g->Wg = c.W + c.P.gk[sd] + (int64_t)c.d.Is[sd] * 2 * H; g->ldwg = 2 * H;
+  g->Wc = c.W + c.P.ck[sd] + (int64_t)c.d.Is[sd] * H; g->ldwc = H;
+  g->out = c.ws + c.w.gru_out[sd]; g->ldo = H; g->gates = c.ws + c.w.gates[sd];
+}
+// the rows a backward recurrence leaves for the queued weight-gradient products
+static void gru_side_saved(const Pass& c, int sd, GruSide* g) {
+  g->dxproj = c.ws + c.w.dxproj[sd]; g->rh = c.ws + c.w.rh[sd]; g->hprev = c.ws + c.w.hprev[sd];
+}
+// per-workgroup column sums of dxproj (the recurrence's bias gradients), where the kernel that runs provides them; one row per
+// 16 samples at most: far inside the scratch that only the other recurrence kernels use (null: no room)
+static float* gru_bias_slab(const Pass& c, int sd) {
+  const int64_t stride = (int64_t)(c.B / 16 + 1) * 3 * c.H;
+  return 2 * stride <= c.w.gru_tmp_floats ? c.ws + c.w.gru_tmp + sd * stride : nullptr;
+}
+// a one-layer-per-launch backward recurrence's side: dL/d out, dL/d final state (or null) and everything it writes
+static void gru_side_bwd(const Pass& c, int sd, const float* dfinal, GruSide* g) {
+  g->dout = c.ws + c.w.dgru[sd]; g->lddo = c.H; g->dfinal = dfinal;
+  gru_side_saved(c, sd, g);
+  g->bias_slab = gru_bias_slab(c, sd);
+}
 
 // ---------------------------------------------------------------- GRU4Rec's two stacked recurrences (point_model.py:129-132)
-// The stacked kernel (gru_stack.hip: both layers in one launch, layer 2 one step behind layer 1) or, with debug_flags bit 13
-// (8192) and at every H it does not cover, the COMPOSED form: layer 1's recurrence, the GEMM that projects its outputs, layer 2's
+// The stacked kernel (gru_stack.hip: both layers in one launch, layer 2 one step behind layer 1) or, with Flags.g4r_composed
+// and at every H it does not cover, the COMPOSED form: layer 1's recurrence, the GEMM that projects its outputs, layer 2's
 // recurrence -- the kernels of the other model types, one layer per launch -- and the mirror image backward.
-static bool g4r_stacked(const Dims& d, const score_state_t* st) {
-  return !(st->debug_flags & 8192) && !(st->debug_flags & 1) && score_gru_stack_ok(d.H);
+static bool g4r_stacked(const Dims& d, const Flags& fl) {
+  return !fl.g4r_composed && !fl.gru_stepwise && score_gru_stack_ok(d.H);
 }
-static void g4r_gru_args(const Dims& d, const WS& w, const score_state_t* st, const score_batch_t* bt, int T, int x3, GruArgs* ga) {
-  float* ws = st->workspace;
-  memset(ga, 0, sizeof(*ga));
-  ga->B = bt->B; ga->T = T; ga->H = d.H; ga->length = bt->length; ga->nw8 = 1;
-  ga->tmp = ws + w.gru_tmp; ga->tmp_floats = w.gru_tmp_floats; ga->x3 = x3 != 0; ga->x3_rec = ga->x3 && !(st->debug_flags & 4);
-  ga->stepwise = (st->debug_flags & 1) != 0;
+// one layer's GruSide in either form and direction (no dout, no bias slab: the stacked kernel takes neither); layer 2 alone
+// has a final state
+static void g4r_side(const Pass& c, int l, GruSide* g) {
+  gru_side(c, l, g);
+  g->xproj = c.ws + c.w.xproj[l]; g->final_state = l ? c.ws + c.w.gru_final[1] : nullptr;
+  gru_side_saved(c, l, g);
 }
-// one layer's GruSide: the h rows of its kernels, its saved outputs / gates and its backward regions
-static void g4r_side(const Dims& d, const Params& P, const WS& w, const score_state_t* st, int l, GruSide* g) {
-  float* ws = st->workspace;
-  const float* W = st->w;
-  const int H = d.H;
-  memset(g, 0, sizeof(*g));
-  g->xproj = ws + w.xproj[l]; g->Wg = W + P.gk[l] + (int64_t)d.Is[l] * 2 * H; g->ldwg = 2 * H;
-  g->Wc = W + P.ck[l] + (int64_t)d.Is[l] * H; g->ldwc = H;
-  g->out = ws + w.gru_out[l]; g->ldo = H; g->gates = ws + w.gates[l]; g->final_state = l ? ws + w.gru_final[1] : nullptr;
-  g->dxproj = ws + w.dxproj[l]; g->rh = ws + w.rh[l]; g->hprev = ws + w.hprev[l];
-}
-static void g4r_stack_args(const Dims& d, const Params& P, const WS& w, const score_state_t* st, const score_batch_t* bt, int T,
-                           GruStackArgs* a) {
-  const float* W = st->w;
+static void g4r_stack_args(const Pass& c, GruStackArgs* a) {
   memset(a, 0, sizeof(*a));
-  a->B = bt->B; a->T = T; a->H = d.H; a->length = bt->length;
-  for (int l = 0; l < 2; ++l) g4r_side(d, P, w, st, l, &a->l[l]);
-  a->Wg2 = W + P.gk[1]; a->Wc2 = W + P.ck[1]; a->bg2 = W + P.gb[1]; a->bc2 = W + P.cb[1];
+  a->B = c.B; a->T = c.T; a->H = c.H; a->length = c.bt->length;
+  for (int l = 0; l < 2; ++l) g4r_side(c, l, &a->l[l]);
+  a->Wg2 = c.W + c.P.gk[1]; a->Wc2 = c.W + c.P.ck[1]; a->bg2 = c.W + c.P.gb[1]; a->bc2 = c.W + c.P.cb[1];
 }
-static int g4r_grus_fwd(const Dims& d, const Params& P, const WS& w, const score_state_t* st, const score_batch_t* bt, int T, int x3,
-                        hipStream_t s) {
-  float* ws = st->workspace;
-  const int B = bt->B, H = d.H, BT = B * T;
-  float* scratch = ws + w.scratch;
-  const float* cat[2] = {ws + w.wxcat, ws + w.wxcat + (int64_t)(d.Ic + 1) * 3 * H};
+static int g4r_grus_fwd(const Pass& c) {
+  const Dims& d = c.d; const WS& w = c.w; float* ws = c.ws; hipStream_t s = c.s;
+  const int H = c.H, BT = c.BT;
   // layer 1's hoisted projection of the gathered rows: x . [Wx_gates | Wx_cand] + [b_gates | b_cand]
-  G(gemm_mode_call(x3, 0, BT, 3 * H, d.Di, ws + w.xside[0], d.I, cat[0], 3 * H, ws + w.xproj[0], 3 * H, cat[0] + (int64_t)d.Di * 3 * H,
-                   GF_BIAS, 1.f, nullptr, 0, scratch, w.scratch_floats, s));
-  if (g4r_stacked(d, st)) {
+  G(gemm_mode_call(c.x3, 0, BT, 3 * H, d.Di, ws + w.xside[0], d.I, wxcat(c, 0), 3 * H, ws + w.xproj[0], 3 * H,
+                   wxcat(c, 0) + (int64_t)d.Di * 3 * H, GF_BIAS, 1.f, nullptr, 0, c.scratch, w.scratch_floats, s));
+  if (g4r_stacked(d, c.fl)) {
     GruStackArgs a;
-    g4r_stack_args(d, P, w, st, bt, T, &a);
+    g4r_stack_args(c, &a);
     return score_gru_stack_fwd(a, s);
   }
   for (int l = 0; l < 2; ++l) {
     if (l == 1)     // layer 2's input rows are layer 1's outputs (zero past the length)
-      G(gemm_mode_call(x3, 0, BT, 3 * H, H, ws + w.gru_out[0], H, cat[1], 3 * H, ws + w.xproj[1], 3 * H, cat[1] + (int64_t)H * 3 * H,
-                       GF_BIAS, 1.f, nullptr, 0, scratch, w.scratch_floats, s));
+      G(gemm_mode_call(c.x3, 0, BT, 3 * H, H, ws + w.gru_out[0], H, wxcat(c, 1), 3 * H, ws + w.xproj[1], 3 * H,
+                       wxcat(c, 1) + (int64_t)H * 3 * H, GF_BIAS, 1.f, nullptr, 0, c.scratch, w.scratch_floats, s));
     GruArgs ga;
-    g4r_gru_args(d, w, st, bt, T, x3, &ga);
-    g4r_side(d, P, w, st, l, &ga.s[0]);
+    gru_header(c, &ga);
+    g4r_side(c, l, &ga.s[0]);
     G(score_gru_fwd_multi(ga, 1, s));
   }
   return 0;
 }
 // dfinal2: dL/d layer 2's final state [B, H].  Leaves both layers' dxproj / rh / hprev rows for the queued weight-gradient
 // products; *bias_rows as GruArgs.bias_slab_rows
-static int g4r_grus_bwd(const Dims& d, const Params& P, const WS& w, const score_state_t* st, const score_batch_t* bt, int T, int x3,
-                        const float* dfinal2, int* bias_rows, hipStream_t s) {
-  float* ws = st->workspace;
-  const int B = bt->B, H = d.H, BT = B * T;
+static int g4r_grus_bwd(const Pass& c, const float* dfinal2, int* bias_rows) {
+  const WS& w = c.w; const int H = c.H;
   *bias_rows = 0;
-  if (g4r_stacked(d, st)) {
+  if (g4r_stacked(c.d, c.fl)) {
     GruStackArgs a;
-    g4r_stack_args(d, P, w, st, bt, T, &a);
+    g4r_stack_args(c, &a);
     a.l[1].dfinal = dfinal2;
-    return score_gru_stack_bwd(a, s);
+    return score_gru_stack_bwd(a, c.s);
   }
-  const float* cat1 = ws + w.wxcat + (int64_t)(d.Ic + 1) * 3 * H;
   for (int l = 1; l >= 0; --l) {
     GruArgs ga;
-    g4r_gru_args(d, w, st, bt, T, x3, &ga);
-    GruSide& g = ga.s[0];
-    g4r_side(d, P, w, st, l, &g);
-    g.dout = ws + w.dgru[l]; g.lddo = H; g.dfinal = l ? dfinal2 : nullptr;       // (dgru[1]: zeros, only the final state is read)
-    g.bias_slab = (2 * ((int64_t)B / 16 + 1) * 3 * H <= w.gru_tmp_floats) ? ws + w.gru_tmp + (int64_t)l * (B / 16 + 1) * 3 * H : nullptr;
-    G(score_gru_bwd_multi(ga, 1, s));
+    gru_header(c, &ga);
+    g4r_side(c, l, &ga.s[0]);
+    gru_side_bwd(c, l, l ? dfinal2 : nullptr, &ga.s[0]);       // (dgru[1]: zeros, only the final state is read)
+    G(score_gru_bwd_multi(ga, 1, c.s));
     *bias_rows = ga.bias_slab_rows;
     if (l == 1)     // layer 2's input gradient is layer 1's dout: [dgates | dcand] . [Wx_gates | Wx_cand]^T
-      G(gemm_mode_call(x3, 1, BT, H, 3 * H, ws + w.dxproj[1], 3 * H, cat1, 3 * H, ws + w.dgru[0], H, nullptr, 0, 1.f, nullptr, 0,
-                       ws + w.scratch, w.scratch_floats, s));
+      G(gemm_mode_call(c.x3, 1, c.BT, H, 3 * H, c.ws + w.dxproj[1], 3 * H, wxcat(c, 1), 3 * H, c.ws + w.dgru[0], H, nullptr, 0, 1.f,
+                       nullptr, 0, c.scratch, w.scratch_floats, c.s));
   }
+  return 0;
+}
+
+// ---------------------------------------------------------------- the two co-attention calls
+// 1: (user_1hop, item_2hop, target_item) ; 2: (user_2hop, item_1hop, target_user)  (score.py:196-197)
+// user_side = [user_1hop_seq | user_2hop_seq], item_side = [item_1hop_seq | item_2hop_seq]   (:200-201)
+// What the forward and the backward pass share; col1 / col2 / info_col[i]: where call i's two outputs start in a row of
+// the user side, of the item side and of atten_info -- each pass points its own regions there
+struct CoattnCols { int col1[2], col2[2], info_col[2]; };
+static void coattn_args(const Pass& c, CoattnArgs* ca, CoattnCols* k) {
+  const Dims& d = c.d;
+  memset(ca, 0, sizeof(*ca));
+  ca->table = c.st->table; ca->K = d.K; ca->T = c.T; ca->Tidx = d.T; ca->mode = d.coattn ? 0 : 1; ca->n_rows = c.n_rows;
+  const int32_t* idx1[2] = {c.bt->user_1hop, c.bt->user_2hop};
+  const int32_t* idx2[2] = {c.bt->item_2hop, c.bt->item_1hop};
+  for (int i = 0; i < 2; ++i) {
+    CoattnCall& cc = ca->c[i];
+    cc.idx1 = idx1[i]; cc.idx2 = idx2[i]; cc.W = d.coattn ? c.W + c.P.ca_w[i] : nullptr; cc.rsave = c.ws + c.w.rsave[i];
+    cc.ld1 = d.I; cc.ld2 = d.I; cc.ldi = 4 * d.K; cc.F = i ? d.Fu : d.Fi;
+    k->col1[i] = i ? d.Di : 0; k->col2[i] = i ? 0 : d.Du; k->info_col[i] = i * 2 * d.K;
+  }
+}
+
+// ---------------------------------------------------------------- panel GEMM groups (gemm_panel.hip)
+// The two sides' GRU input projections (which = 0: [BT, Is] . cat -> 3H columns) or their input gradients (which = 1:
+// [BT, 3H] . cat^T -> Is columns), each side's output columns as `ns` column halves: group g is side g / ns, half g % ns.
+// src: the block of the concatenated copy a group's image is made of (trans: as score_gemm_panel_prep takes it)
+struct PanelGroups { int n, Nh, K, trans, lda, ldc; const float* src[4]; float* img[4]; PanelGroup pg[4]; };
+static void panel_groups(const Pass& c, int which, const float* const* A, float* const* C, PanelGroups* p) {
+  const Dims& d = c.d; const int H = c.H;
+  const int ns = which == 0 ? panel_x_splits(H) : panel_d_splits(d.Is[0]);
+  p->n = 2 * ns; p->Nh = (which == 0 ? 3 * H : d.Is[0]) / ns; p->K = which == 0 ? d.Is[0] : 3 * H; p->trans = which == 0;
+  p->lda = which == 0 ? x_ld(d, 0) : 3 * H; p->ldc = which == 0 ? 3 * H : d.I;
+  const int64_t per = score_gemm_panel_image_floats(p->Nh, p->K);
+  for (int g = 0; g < p->n; ++g) {
+    const int side = g / ns, half = g % ns;
+    const float* cat = wxcat(c, side);
+    p->src[g] = which == 0 ? cat + half * p->Nh : cat + (int64_t)half * p->Nh * 3 * H;
+    p->img[g] = c.ws + (which == 0 ? c.w.pimg_x : c.w.pimg_d)[side] + half * per;
+    PanelGroup& pg = p->pg[g];
+    pg.A = A ? A[side] : nullptr; pg.img = p->img[g]; pg.C = C ? C[side] + half * p->Nh : nullptr;
+    pg.bias = which == 0 ? cat + (int64_t)d.Is[side] * 3 * H + half * p->Nh : nullptr;    // (each side's own bias row)
+  }
+}
+// the weights as fragment images
+static int panel_prep(const Pass& c, int which, hipStream_t on) {
+  PanelGroups p;
+  panel_groups(c, which, nullptr, nullptr, &p);
+  return score_gemm_panel_prep(p.n, p.src, 3 * c.H, p.trans, p.Nh, p.K, p.img, on);
+}
+static int panel_launch(const Pass& c, int which, const float* const* A, float* const* C) {
+  PanelGroups p;
+  panel_groups(c, which, A, C, &p);
+  return score_gemm_panel(p.n, p.pg, c.BT, p.Nh, p.K, p.lda, p.ldc, c.s);
+}
+
+// ---------------------------------------------------------------- the loss reduction behind a head
+// One workgroup, no reader inside the step: with score_state_t.loss_done_event it runs on the side stream, so the backward
+// pass's first launch follows the head directly
+static int loss_tail(const Pass& c, SideStream* sd, float reg_lambda) {
+  const WS& w = c.w;
+  hipStream_t ls = c.s;
+  if (c.st->loss_done_event) { G(fork_side(sd, c.s)); ls = sd->st; }
+  G(score_launch_loss_final(c.B, c.ws + w.lossb, c.ws + w.loss, reg_lambda, c.ws + w.part, c.Bg, ls, c.st->id_status));
+  if (c.st->loss_done_event) HIPTRY(hipEventRecord((hipEvent_t)c.st->loss_done_event, ls));
+  return 0;
+}
+
+// ---------------------------------------------------------------- embedding rows (score.py:51-66): the sorted pull-form scatter
+// plan: the workspace that holds this batch's sorted occurrences (score_index_plan wrote them there): the pass's own, or
+// score_state_t.plan_workspace -- the plan sorted into ANOTHER workspace of the same layout, a step ahead.  Everything else,
+// the unique positions of scatter_mode 2 among it, is read from the pass's own workspace.
+static int row_scatter(const Pass& c, float* plan, float* grad_table) {
+  const Dims& d = c.d; const Params& P = c.P; const WS& w = c.w; float* ws = c.ws; const float* W = c.W;
+  PullArgs pa;
+  memset(&pa, 0, sizeof(pa));
+  pa.D = d.D; pa.K = d.K; pa.zero_is_dummy = 1;
+  pa.flags = c.st->scatter_mode == 0 ? c.st->row_flags : nullptr;
+  pa.uid = c.st->scatter_mode == 2 ? reinterpret_cast<const uint32_t*>(ws + w.uid) : nullptr;
+  const float invK = 1.0f / (float)d.K;
+  const float* Gm[6] = {ws + w.dxside[0], ws + w.dxside[1], ws + w.dxside[0], ws + w.dxside[1], ws + w.dtgt, ws + w.dtgt};
+  const int ldg[6] = {d.I, d.I, d.I, d.I, d.Dq, d.Dq};
+  const int gcol[6] = {0, d.Du, d.Di, 0, 0, d.Du};
+  for (int g = 0; g < 6; ++g) { pa.G[g] = Gm[g]; pa.ldg[g] = ldg[g]; pa.gcol[g] = gcol[g]; pa.constA[g] = 1.0f; }
+  if (d.coattn) {
+    pa.cA[0] = ws + w.pcoef[0]; pa.cA[2] = ws + w.pcoef[1];
+    pa.constA[1] = invK; pa.constA[3] = invK;
+    pa.cB[0] = pa.cB[1] = ws + w.dzcoef[0]; pa.cB[2] = pa.cB[3] = ws + w.dzcoef[1];
+    pa.Wv[0] = W + P.ca_w[0] + d.Di; pa.Wv[1] = W + P.ca_w[0] + 2 * d.Di;
+    pa.Wv[2] = W + P.ca_w[1] + d.Du; pa.Wv[3] = W + P.ca_w[1] + 2 * d.Du;
+  }
+  const int64_t n_occ = (int64_t)c.B * (2 * (int64_t)c.T * d.K * (d.Fu + d.Fi) + d.Fu + d.Fi);   // what score_index_plan enumerated
+  return score_launch_pull(pa, reinterpret_cast<uint32_t*>(plan + w.keys_out), reinterpret_cast<uint32_t*>(plan + w.vals_out),
+                           n_occ + 1, grad_table, ws + w.partials, w.partial_floats, c.s);
+}
+
+// ---------------------------------------------------------------- the queued weight gradients and column sums of a backward pass
+// Weight gradients C = X^T dY and bias gradients (column sums) have no consumer inside a pass: queued, issued together.  BOTH
+// forms of the backward pass queue through these functions, in this order -- head, attention denses, query projection, the
+// recurrence sides: the order within gq and within cq decides the grouping of the launches and the split-K slab of each
+// product, and with them the bits.  Queueing is host bookkeeping; what is queued must be final when its queue is flushed.
+struct GradQueues { GemmQueue gq; ColsumJobs cq; };
+static inline void queues_init(GradQueues* q) { q->gq.n = 0; q->cq.n = 0; q->cq.part_used = 0; }
+// build_fc_net (score.py:68-81).  bn1_sums: bn1's d gamma / d beta as column sums of what a fused kernel wrote (the
+// layer-by-layer pass's score_launch_bn_bwd queues its own, at this place in cq)
+static int queue_head(const Pass& c, GradQueues* q, float* gw, bool bn1_sums) {
+  const Dims& d = c.d; const Params& P = c.P; const WS& w = c.w; float* ws = c.ws; const int B = c.B;
+  // fc3: dW = f2^T dlogit, db = sum dlogit
+  G(gemm_queue_add(&q->gq, FC2, 1, B, ws + w.f2, FC2, ws + w.dlogit, 1, gw + P.fc_w[2], 1));
+  G(colsum_queue_add(&q->cq, ws + w.dlogit, B, 1, 1, gw + P.fc_b[2], 0));
+  // fc2
+  G(gemm_queue_add(&q->gq, FC1, FC2, B, ws + w.f1, FC1, ws + w.dz2, FC2, gw + P.fc_w[1], FC2));
+  G(colsum_queue_add(&q->cq, ws + w.dz2, B, FC2, FC2, gw + P.fc_b[1], 0));
+  // fc1 + bn1
+  G(gemm_queue_add(&q->gq, d.Dhead, FC1, B, ws + w.bn, d.Dhead, ws + w.dz1, FC1, gw + P.fc_w[0], FC1));
+  G(colsum_queue_add(&q->cq, ws + w.dz1, B, FC1, FC1, gw + P.fc_b[0], 0));
+  if (bn1_sums) {
+    G(colsum_queue_add(&q->cq, ws + w.dgstage, B, d.Dhead, d.Dhead, gw + P.bn_g, 0));
+    G(colsum_queue_add(&q->cq, ws + w.dbn, B, d.Dhead, d.Dhead, gw + P.bn_b, 0));
+  }
+  return 0;
+}
+// the temporal attention's denses (score.py:169-186)
+static int queue_attn(const Pass& c, GradQueues* q, float* gw) {
+  const Dims& d = c.d; const Params& P = c.P; const WS& w = c.w; float* ws = c.ws; const int B = c.B, BT = c.BT;
+  // dense_5 (40 -> 1): dW = a2^T ds ; db = sum ds
+  G(gemm_queue_add(&q->gq, AT2, 1, BT, ws + w.a2, AT2, ws + w.ds, 1, gw + P.at_w[3], 1));
+  G(colsum_queue_add(&q->cq, ws + w.ds, BT, 1, 1, gw + P.at_b[3], 0));
+  // dense_4 (80 -> 40); da2 is already relu-masked
+  G(gemm_queue_add(&q->gq, AT1, AT2, BT, ws + w.a1, AT1, ws + w.da2, AT2, gw + P.at_w[2], AT2));
+  G(colsum_queue_add(&q->cq, ws + w.da2, BT, AT2, AT2, gw + P.at_b[2], 0));
+  // dense_3 (4Dk -> 80), folded: weight gradient from [k, q*k]^T da1 and q^T sum_t da1 (adzsum); gw + P.at_w[1] is assembled
+  // from dweff / dwq after the queue is flushed
+  G(gemm_queue_add(&q->gq, 2 * d.Dk, AT1, BT, ws + w.ainp, 2 * d.Dk, ws + w.da1, AT1, ws + w.dweff, AT1));
+  G(colsum_queue_add(&q->cq, ws + w.da1, BT, AT1, AT1, gw + P.at_b[1], 0));
+  G(gemm_queue_add(&q->gq, d.Dk, AT1, B, ws + w.q, d.Dk, ws + w.adzsum, AT1, ws + w.dwq, AT1));
+  return 0;
+}
+// dense_2, the query projection
+static int queue_query(const Pass& c, GradQueues* q, float* gw) {
+  const Dims& d = c.d; const Params& P = c.P; const WS& w = c.w;
+  G(gemm_queue_add(&q->gq, d.Dq, d.Dk, c.B, c.ws + w.query, d.Dq, c.ws + w.dq, d.Dk, gw + P.at_w[0], d.Dk));
+  G(colsum_queue_add(&q->cq, c.ws + w.dq, c.B, d.Dk, d.Dk, gw + P.at_b[0], 0));
+  return 0;
+}
+// One recurrence's kernels and biases.  The kernels are [x ; h] row blocks (TF GRUCell), x rows first: the x rows of the two
+// kernels straight into their gradients (same A panel, the column tiles of [dgates | dcand]), then the h rows.  The input rows
+// are x_ld(d, sd) wide with Is[sd] columns read; the per-sample pass runs only model types where both are d.I and the rows
+// are the gather's.  bias_rows > 0: the recurrence left per-workgroup column sums of dxproj (gru_bias_slab): a few dozen rows
+// instead of B*T
+static int queue_gru_side(const Pass& c, GradQueues* q, float* gw, int sd, int bias_rows) {
+  const Dims& d = c.d; const Params& P = c.P; const WS& w = c.w; float* ws = c.ws;
+  const int H = c.H, BT = c.BT, Is = d.Is[sd], ld = x_ld(d, sd);
+  float* dxp = ws + w.dxproj[sd];
+  const float* xin = d.gcmc ? ws + w.gcmc_z[sd] : (d.g4r && sd == 1) ? ws + w.gru_out[0] : ws + w.xside[sd];
+  G(gemm_queue_add(&q->gq, Is, 2 * H, BT, xin, ld, dxp, 3 * H, gw + P.gk[sd], 2 * H));
+  G(gemm_queue_add(&q->gq, Is, H, BT, xin, ld, dxp + 2 * H, 3 * H, gw + P.ck[sd], H));
+  G(gemm_queue_add(&q->gq, H, 2 * H, BT, ws + w.hprev[sd], H, dxp, 3 * H, gw + P.gk[sd] + (int64_t)Is * 2 * H, 2 * H));
+  G(gemm_queue_add(&q->gq, H, H, BT, ws + w.rh[sd], H, dxp + 2 * H, 3 * H, gw + P.ck[sd] + (int64_t)Is * H, H));
+  const float* rows = bias_rows > 0 ? gru_bias_slab(c, sd) : dxp;
+  const int nrows = bias_rows > 0 ? bias_rows : BT;
+  G(colsum_queue_add(&q->cq, rows, nrows, 2 * H, 3 * H, gw + P.gb[sd], 0));
+  G(colsum_queue_add(&q->cq, rows + 2 * H, nrows, H, 3 * H, gw + P.cb[sd], 0));
   return 0;
 }
 
@@ -674,6 +906,7 @@ extern "C" int score_index_plan(const score_config_t* cfg, const score_state_t* 
   if (BT > (1 << 21) || d.Fu > 8 || d.Fi > 8) return SCORE_E_SHAPE;
   hipStream_t s = (hipStream_t)stream;
   float* ws = st->workspace;
+  const Flags fl = flags_of(st);
   PlanFillArgs pf;
   memset(&pf, 0, sizeof(pf));
   const int32_t* idx[6] = {bt->user_1hop, bt->item_2hop, bt->user_2hop, bt->item_1hop, bt->target_user,
@@ -686,7 +919,7 @@ extern "C" int score_index_plan(const score_config_t* cfg, const score_state_t* 
     off += (g < 4 ? (int64_t)BT * d.K : (int64_t)B) * Fs[g];
   }
   pf.off[6] = off; pf.K = d.K; pf.G = n_shards; pf.T = d.T; pf.TA = TA;
-  pf.n_rows = (uint32_t)(d.N < 0x80000000ll ? d.N : 0x80000000ll); pf.id_status = st->id_status;
+  pf.n_rows = clamp_rows(d.N); pf.id_status = st->id_status;
   // key = row (1 shard) or (owner = row % G) << shift | (row / G)
   const int64_t rows_local = cdiv64(d.N, n_shards);
   int shift = 1;
@@ -701,7 +934,7 @@ extern "C" int score_index_plan(const score_config_t* cfg, const score_state_t* 
   uint32_t* keys_out = reinterpret_cast<uint32_t*>(ws + w.keys_out);
   uint32_t* vals_out = reinterpret_cast<uint32_t*>(ws + w.vals_out);
   G(score_launch_plan(pf, key_bits, keys_in, vals_in, keys_out, vals_out, ws + w.sort_temp,
-                      (size_t)w.sort_temp_bytes, s, (st->debug_flags & 32) ? 1 : (st->debug_flags & 256) ? 2 : 0));
+                      (size_t)w.sort_temp_bytes, s, fl.sort_lib ? 1 : fl.sort_own ? 2 : 0));
   if (n_shards > 1 || dedup) {
     PlanRemapArgs ra;
     memset(&ra, 0, sizeof(ra));
@@ -718,7 +951,7 @@ extern "C" int score_index_plan(const score_config_t* cfg, const score_state_t* 
 
 // do the two sides' GRU input projections (which = 0) / their input gradients (which = 1) take the panel form?  Same
 // answer in the forward pass (which writes the weight images) and in the backward pass (which uses them).
-// The input gradients: from 64 K rows per side (cfg-5), or with debug_flags bit 4.  The kernel itself is 30 % faster there
+// The input gradients: from 64 K rows per side (cfg-5), or with Flags.panel_dx.  The kernel itself is 30 % faster there
 // too (71 vs 101 us at cfg-3), but a panel workgroup owns its CU (8 waves x 256 registers), and the backward pass has
 // ~350 us of other streams' work to place -- the side stream's query branch and early weight gradients, the optimizer's
 // window slice -- which the tiled kernel lets run beside it and a one-round panel kernel pushes into the co-attention
@@ -728,12 +961,13 @@ extern "C" int score_index_plan(const score_config_t* cfg, const score_state_t* 
 // same: profiles/r04_probes.md).  At cfg-5's sizes the other
 // streams' work is small beside these products: 20.3 -> 19.8 ms/step with both.
 static bool panel_gemms(const Dims& d, const score_state_t* st, int BT, int which) {
-  if (st->gemm_mode != 1 || (st->debug_flags & 8) || d.Is[0] != d.Is[1] || d.g4r) return false;
+  const Flags fl = flags_of(st);
+  if (st->gemm_mode != 1 || fl.no_panel || d.Is[0] != d.Is[1] || d.g4r) return false;
   if (which == 1 && d.gcmc) return false;      // (GCMC's input gradients take Z's relu mask in the epilogue: the tiled kernels)
-  const int ns = panel_x_splits(d.H);
+  const int ns = panel_x_splits(d.H), nd = panel_d_splits(d.Is[0]);
   return which == 0 ? ns > 0 && score_gemm_panel_ok(2 * ns, BT, 3 * d.H / ns, d.Is[0], x_ld(d, 0), 3 * d.H, nullptr)
-                    : ((st->debug_flags & 16) || (int64_t)BT >= 65536) && panel_d_splits(d.Is[0]) > 0 &&
-                          score_gemm_panel_ok(2 * panel_d_splits(d.Is[0]), BT, d.Is[0] / panel_d_splits(d.Is[0]), 3 * d.H, 3 * d.H, d.I, nullptr);
+                    : (fl.panel_dx || (int64_t)BT >= 65536) && nd > 0 &&
+                          score_gemm_panel_ok(2 * nd, BT, d.Is[0] / nd, 3 * d.H, 3 * d.H, d.I, nullptr);
 }
 
 extern "C" int score_gemm_forms(const score_config_t* cfg, const score_state_t* st, int32_t B, int32_t active_slices,
@@ -752,27 +986,25 @@ extern "C" int score_gemm_forms(const score_config_t* cfg, const score_state_t* 
 // ---------------------------------------------------------------- per-sample whole-model path (persample.h)
 // The reference's own shapes (train_score.py:15-16, 285-372: D = 16, H = 32, B = 100 / 200) are bound by launch latency,
 // not by bytes or flops: score_forward / score_backward then run ONE kernel each (a workgroup per sample) plus the
-// weight-gradient products and the row scatter.  debug_flags bit 9 (512): never; bit 10 (1024): the forward pass only;
-// bit 11 (2048): the backward pass only (A/B and parity tests compare the forms).
+// weight-gradient products and the row scatter.  Flags.no_ps: never; ps_fwd_only: the forward pass only; ps_bwd_only: the
+// backward pass only (A/B and parity tests compare the forms).
 namespace {
 struct PsPlan { PsShape s; PsImages im; };
 
 bool ps_path(const Dims& d, const score_state_t* st, const score_batch_t* bt, int TA, PsPlan* pp) {
-  if ((st->debug_flags & 512) || st->scatter_mode == 1) return false;
+  if (flags_of(st).no_ps || st->scatter_mode == 1) return false;
   if (!d.coattn || !d.attn) return false;                     // SCORE, SCORE_USER, SCORE_ITEM
-  const int Bg = st->global_batch > 0 ? st->global_batch : bt->B;
-  if (ps_plan_shape(bt->B, TA, d.T, d.K, d.D, d.Fu, d.Fi, d.H, d.NI, d.Dk, d.Dhead, d.off_u, d.off_i, d.off_ti, d.off_tu, Bg,
-                    &pp->s) != 0)
+  if (ps_plan_shape(bt->B, TA, d.T, d.K, d.D, d.Fu, d.Fi, d.H, d.NI, d.Dk, d.Dhead, d.off_u, d.off_i, d.off_ti, d.off_tu,
+                    global_batch(st, bt->B), &pp->s) != 0)
     return false;
   ps_plan_images(pp->s, &pp->im);
   return true;
 }
 
-// the step's weight images, the L2 partial sums and (optionally) a cleared dense-gradient buffer: one launch
-int ps_prep(const Dims& d, const Params& P, const WS& w, const PsPlan& pp, const score_state_t* st, float* zero, int64_t zero_floats,
-            hipStream_t s) {
-  const float* W = st->w;
-  float* img = st->workspace + w.psimg;
+// the step's weight images and the L2 partial sums: one launch
+int ps_prep(const Pass& c, const PsPlan& pp) {
+  const Dims& d = c.d; const Params& P = c.P; const float* W = c.W;
+  float* img = c.ws + c.w.psimg;
   const int H = d.H, I = d.I, Dk = d.Dk, Dh = d.Dhead;
   PsPrepArgs pa;
   memset(&pa, 0, sizeof(pa));
@@ -796,36 +1028,28 @@ int ps_prep(const Dims& d, const Params& P, const WS& w, const PsPlan& pp, const
   job(W + P.at_w[0], nullptr, pp.im.q2t, Dk, I, Dk, PS_SRC_PLAIN, 1, 0);
   for (int sd = 0; sd < 2; ++sd) job(W + P.gk[sd], W + P.ck[sd], pp.im.wxt[sd], 3 * H, I, 0, PS_SRC_WXCAT, 1, H);
   pa.njobs = n;
-  pa.wreg = W; pa.n_reg = P.n_reg; pa.part = st->workspace + w.part;
-  pa.zero = zero; pa.zero_floats = zero_floats;
-  return score_launch_ps_prep(pa, s);
+  pa.wreg = W; pa.n_reg = P.n_reg; pa.part = c.ws + c.w.part;
+  return score_launch_ps_prep(pa, c.s);
 }
 
-int forward_ps(const Dims& d, const Params& P, const WS& w, const PsPlan& pp, const score_state_t* st, const score_batch_t* bt,
-               float reg_lambda, float keep_prob, const uint8_t* mask0, const uint8_t* mask1, uint64_t seed,
-               void* const* stage_events, hipStream_t s) {
-  float* ws = st->workspace;
-  const int B = bt->B;
-  G(ps_prep(d, P, w, pp, st, nullptr, 0, s));
-  if (st->debug_flags & 1024) {      // (the layer-by-layer backward pass that follows reads the concatenated / folded copies)
-    const float* W = st->w;
-    const int64_t weff_stride = align_up64(2 * (int64_t)d.Dk * AT1 + 48, 4);
-    G(score_launch_weight_prep(W + P.gk[0], W + P.ck[0], W + P.gb[0], W + P.cb[0], W + P.gk[1], W + P.ck[1], W + P.gb[1],
-                               W + P.cb[1], d.Is[0], d.Is[1], d.I, d.H, ws + w.wxcat, d.Dk, AT1, W + P.at_w[1], ws + w.weff,
-                               ws + w.wq, SCORE_WEFF_COPIES, weff_stride, W, P.n_reg, ws + w.part, s));
-  }
+int forward_ps(const Pass& c, const PsPlan& pp, float reg_lambda, float keep_prob, const uint8_t* mask0, const uint8_t* mask1,
+               uint64_t seed, void* const* stage_events) {
+  const Params& P = c.P; const WS& w = c.w; const score_state_t* st = c.st; const score_batch_t* bt = c.bt;
+  float* ws = c.ws; hipStream_t s = c.s;
+  G(ps_prep(c, pp));
+  // (the layer-by-layer backward pass that follows reads the concatenated / folded copies)
+  if (c.fl.ps_fwd_only) G(weight_prep(c, s));
   EV(0);
   PsFwdArgs a;
   memset(&a, 0, sizeof(a));
   a.s = pp.s; a.im = pp.im; a.img = ws + w.psimg;
   a.idx1[0] = bt->user_1hop; a.idx2[0] = bt->item_2hop; a.idx1[1] = bt->user_2hop; a.idx2[1] = bt->item_1hop;
   a.tu = bt->target_user; a.ti = bt->target_item; a.label = bt->label; a.length = bt->length;
-  a.table = st->table; a.n_rows = (uint32_t)(st->n_table_rows < 0x80000000ll ? st->n_table_rows : 0x80000000ll);
-  a.id_status = st->id_status; a.W = st->w;
-  for (int c = 0; c < 2; ++c) {
-    a.ca_w[c] = P.ca_w[c]; a.ca_b[c] = P.ca_b[c]; a.gk[c] = P.gk[c]; a.gb[c] = P.gb[c]; a.ck[c] = P.ck[c]; a.cb[c] = P.cb[c];
-    a.xside[c] = ws + w.xside[c]; a.rsave[c] = ws + w.rsave[c]; a.gates[c] = ws + w.gates[c]; a.gru_out[c] = ws + w.gru_out[c];
-    a.gru_final[c] = ws + w.gru_final[c];
+  a.table = st->table; a.n_rows = c.n_rows; a.id_status = st->id_status; a.W = st->w;
+  for (int i = 0; i < 2; ++i) {
+    a.ca_w[i] = P.ca_w[i]; a.ca_b[i] = P.ca_b[i]; a.gk[i] = P.gk[i]; a.gb[i] = P.gb[i]; a.ck[i] = P.ck[i]; a.cb[i] = P.cb[i];
+    a.xside[i] = ws + w.xside[i]; a.rsave[i] = ws + w.rsave[i]; a.gates[i] = ws + w.gates[i]; a.gru_out[i] = ws + w.gru_out[i];
+    a.gru_final[i] = ws + w.gru_final[i];
   }
   for (int i = 0; i < 4; ++i) a.at_b[i] = P.at_b[i];
   a.at_w5 = P.at_w[3]; a.bn_g = P.bn_g; a.bn_b = P.bn_b;
@@ -834,13 +1058,12 @@ int forward_ps(const Dims& d, const Params& P, const WS& w, const PsPlan& pp, co
   a.query = ws + w.query; a.head_inp = ws + w.head_inp; a.info = ws + w.info; a.q = ws + w.q; a.ainp = ws + w.ainp;
   a.a1 = ws + w.a1; a.a2 = ws + w.a2; a.att_score = ws + w.att_score; a.bn = ws + w.bn; a.f1 = ws + w.f1; a.f2 = ws + w.f2;
   a.logit = ws + w.logit; a.y = ws + w.y_pred; a.lossb = ws + w.lossb; a.dlogit = ws + w.dlogit; a.dz2 = ws + w.dz2;
-  a.keep = keep_prob; a.rs = (float)(1.0 / sqrt(1.0 + 1e-3)); a.drop = keep_prob < 1.f ? 1 : 0;
+  a.keep = keep_prob; a.rs = c.rs; a.drop = keep_prob < 1.f ? 1 : 0;
   a.mask0 = mask0; a.mask1 = mask1; a.seed0 = seed; a.seed1 = seed ^ 0x5DEECE66Dull;
   a.seed_dev = st->step_scalars ? &st->step_scalars->drop_seed : nullptr;
-  const int Bg = st->global_batch > 0 ? st->global_batch : B;
   a.loss = ws + w.loss; a.loss_host = st->loss_host; a.part = ws + w.part;
   a.done = reinterpret_cast<unsigned int*>(ws + w.part) + 256;
-  a.lambda = reg_lambda; a.inv_bglobal = 1.0f / (float)Bg;
+  a.lambda = reg_lambda; a.inv_bglobal = 1.0f / (float)c.Bg;
   G(score_launch_ps_fwd(a, s));
   if (st->gather_done_event) HIPTRY(hipEventRecord((hipEvent_t)st->gather_done_event, s));
   EV(1); EV(2); EV(3);
@@ -850,12 +1073,9 @@ int forward_ps(const Dims& d, const Params& P, const WS& w, const PsPlan& pp, co
   return 0;
 }
 
-int backward_ps(const Dims& d, const Params& P, const WS& w, const PsPlan& pp, const score_state_t* st, const score_batch_t* bt,
-                float keep_prob, float* gw, float* grad_table, void* const* stage_events, hipStream_t s) {
-  float* ws = st->workspace;
-  const float* W = st->w;
-  const int B = bt->B, T = pp.s.A, H = d.H, BT = B * T;
-  const int x3 = st->gemm_mode == 1 ? GF_X3 : 0;
+int backward_ps(const Pass& c, const PsPlan& pp, float keep_prob, float* gw, float* grad_table, void* const* stage_events) {
+  const Dims& d = c.d; const Params& P = c.P; const WS& w = c.w; const score_state_t* st = c.st; const score_batch_t* bt = c.bt;
+  float* ws = c.ws; const int B = c.B; hipStream_t s = c.s;
   SideStream* side = nullptr;
   G(side_stream(st, s, &side));
   side->fwd_on = nullptr;
@@ -867,20 +1087,18 @@ int backward_ps(const Dims& d, const Params& P, const WS& w, const PsPlan& pp, c
   // (no memset of grad_w: every float of it is overwritten by this pass -- each variable of SCORE / SCORE_USER / SCORE_ITEM gets a
   //  gradient, every product and column sum stores rather than accumulates -- except the alignment padding between the tensors,
   //  which the backward kernel's first workgroup clears)
-  if (st->debug_flags & 2048) G(ps_prep(d, P, w, pp, st, nullptr, 0, s));      // (after a layer-by-layer forward pass: no images yet)
+  if (c.fl.ps_bwd_only) G(ps_prep(c, pp));      // (after a layer-by-layer forward pass: no images yet)
   EV(0);
   PsBwdArgs a;
   memset(&a, 0, sizeof(a));
   a.s = pp.s; a.im = pp.im; a.img = ws + w.psimg;
   a.idx1[0] = bt->user_1hop; a.idx2[0] = bt->item_2hop; a.idx1[1] = bt->user_2hop; a.idx2[1] = bt->item_1hop;
-  a.length = bt->length; a.table = st->table;
-  a.n_rows = (uint32_t)(st->n_table_rows < 0x80000000ll ? st->n_table_rows : 0x80000000ll);
-  a.W = W;
-  for (int c = 0; c < 2; ++c) {
-    a.ca_w[c] = P.ca_w[c]; a.gk[c] = P.gk[c]; a.ck[c] = P.ck[c];
-    a.rsave[c] = ws + w.rsave[c]; a.gates[c] = ws + w.gates[c]; a.gru_out[c] = ws + w.gru_out[c];
-    a.dxproj[c] = ws + w.dxproj[c]; a.rh[c] = ws + w.rh[c]; a.hprev[c] = ws + w.hprev[c]; a.dxside[c] = ws + w.dxside[c];
-    a.pcoef[c] = ws + w.pcoef[c]; a.dzcoef[c] = ws + w.dzcoef[c];
+  a.length = bt->length; a.table = st->table; a.n_rows = c.n_rows; a.W = c.W;
+  for (int i = 0; i < 2; ++i) {
+    a.ca_w[i] = P.ca_w[i]; a.gk[i] = P.gk[i]; a.ck[i] = P.ck[i];
+    a.rsave[i] = ws + w.rsave[i]; a.gates[i] = ws + w.gates[i]; a.gru_out[i] = ws + w.gru_out[i];
+    a.dxproj[i] = ws + w.dxproj[i]; a.rh[i] = ws + w.rh[i]; a.hprev[i] = ws + w.hprev[i]; a.dxside[i] = ws + w.dxside[i];
+    a.pcoef[i] = ws + w.pcoef[i]; a.dzcoef[i] = ws + w.dzcoef[i];
   }
   a.at_w5 = P.at_w[3]; a.bn_g = P.bn_g;
   a.query = ws + w.query; a.head_inp = ws + w.head_inp; a.info = ws + w.info; a.q = ws + w.q; a.ainp = ws + w.ainp;
@@ -888,7 +1106,7 @@ int backward_ps(const Dims& d, const Params& P, const WS& w, const PsPlan& pp, c
   a.dz1 = ws + w.dz1; a.dbn = ws + w.dbn; a.dgstage = ws + w.dgstage; a.ds = ws + w.ds; a.da2 = ws + w.da2; a.da1 = ws + w.da1;
   a.adzsum = ws + w.adzsum; a.dq = ws + w.dq; a.dtgt = ws + w.dtgt; a.S = ws + w.S;
   a.caslab[0] = ws + w.ca_slab; a.caslab[1] = ws + w.ca_slab + (int64_t)B * 2 * d.Di;
-  a.keep = keep_prob; a.rs = (float)(1.0 / sqrt(1.0 + 1e-3));
+  a.keep = keep_prob; a.rs = c.rs;
   {
     score_param_entry_t ent[32];
     Params Pl;
@@ -912,37 +1130,15 @@ int backward_ps(const Dims& d, const Params& P, const WS& w, const PsPlan& pp, c
   }
   EV(1); EV(2); EV(3);
 
-  // every weight gradient X^T dY and column sum of the pass, from what the kernel left in the workspace
-  ColsumJobs cq;
-  cq.n = 0; cq.part_used = 0;
-  GemmQueue gq;
-  gq.n = 0;
-  G(gemm_queue_add(&gq, FC2, 1, B, ws + w.f2, FC2, ws + w.dlogit, 1, gw + P.fc_w[2], 1));
-  G(colsum_queue_add(&cq, ws + w.dlogit, B, 1, 1, gw + P.fc_b[2], 0));
-  G(gemm_queue_add(&gq, FC1, FC2, B, ws + w.f1, FC1, ws + w.dz2, FC2, gw + P.fc_w[1], FC2));
-  G(colsum_queue_add(&cq, ws + w.dz2, B, FC2, FC2, gw + P.fc_b[1], 0));
-  G(gemm_queue_add(&gq, d.Dhead, FC1, B, ws + w.bn, d.Dhead, ws + w.dz1, FC1, gw + P.fc_w[0], FC1));
-  G(colsum_queue_add(&cq, ws + w.dz1, B, FC1, FC1, gw + P.fc_b[0], 0));
-  G(colsum_queue_add(&cq, ws + w.dgstage, B, d.Dhead, d.Dhead, gw + P.bn_g, 0));
-  G(colsum_queue_add(&cq, ws + w.dbn, B, d.Dhead, d.Dhead, gw + P.bn_b, 0));
-  G(gemm_queue_add(&gq, AT2, 1, BT, ws + w.a2, AT2, ws + w.ds, 1, gw + P.at_w[3], 1));
-  G(colsum_queue_add(&cq, ws + w.ds, BT, 1, 1, gw + P.at_b[3], 0));
-  G(gemm_queue_add(&gq, AT1, AT2, BT, ws + w.a1, AT1, ws + w.da2, AT2, gw + P.at_w[2], AT2));
-  G(colsum_queue_add(&cq, ws + w.da2, BT, AT2, AT2, gw + P.at_b[2], 0));
-  G(gemm_queue_add(&gq, 2 * d.Dk, AT1, BT, ws + w.ainp, 2 * d.Dk, ws + w.da1, AT1, ws + w.dweff, AT1));
-  G(colsum_queue_add(&cq, ws + w.da1, BT, AT1, AT1, gw + P.at_b[1], 0));
-  G(gemm_queue_add(&gq, d.Dk, AT1, B, ws + w.q, d.Dk, ws + w.adzsum, AT1, ws + w.dwq, AT1));
-  G(gemm_queue_add(&gq, d.Dq, d.Dk, B, ws + w.query, d.Dq, ws + w.dq, d.Dk, gw + P.at_w[0], d.Dk));
-  G(colsum_queue_add(&cq, ws + w.dq, B, d.Dk, d.Dk, gw + P.at_b[0], 0));
-  for (int sd = 0; sd < 2; ++sd) {
-    float* dxp = ws + w.dxproj[sd];
-    G(gemm_queue_add(&gq, d.I, 2 * H, BT, ws + w.xside[sd], d.I, dxp, 3 * H, gw + P.gk[sd], 2 * H));
-    G(gemm_queue_add(&gq, d.I, H, BT, ws + w.xside[sd], d.I, dxp + 2 * H, 3 * H, gw + P.ck[sd], H));
-    G(gemm_queue_add(&gq, H, 2 * H, BT, ws + w.hprev[sd], H, dxp, 3 * H, gw + P.gk[sd] + (int64_t)d.I * 2 * H, 2 * H));
-    G(gemm_queue_add(&gq, H, H, BT, ws + w.rh[sd], H, dxp + 2 * H, 3 * H, gw + P.ck[sd] + (int64_t)d.I * H, H));
-    G(colsum_queue_add(&cq, dxp, BT, 2 * H, 3 * H, gw + P.gb[sd], 0));
-    G(colsum_queue_add(&cq, dxp + 2 * H, BT, H, 3 * H, gw + P.cb[sd], 0));
-  }
+  // every weight gradient X^T dY and column sum of the pass, from what the kernel left in the workspace (bn1's sums as behind
+  // a fused head; the recurrences' bias gradients from the full dxproj rows: the kernel writes no bias slab)
+  GradQueues q;
+  queues_init(&q);
+  ColsumJobs& cq = q.cq;
+  G(queue_head(c, &q, gw, true));
+  G(queue_attn(c, &q, gw));
+  G(queue_query(c, &q, gw));
+  for (int sd = 0; sd < 2; ++sd) G(queue_gru_side(c, &q, gw, sd, 0));
   // the co-attention denses: [w_t | w_1 | w_2] -- w_t from the target rows weighted by S, w_1 | w_2 from the per-sample slabs
   G(colsum_queue_add(&cq, a.caslab[0], B, 2 * d.Di, 2 * d.Di, gw + P.ca_w[0] + d.Di, 0));
   G(colsum_queue_add(&cq, a.caslab[1], B, 2 * d.Du, 2 * d.Du, gw + P.ca_w[1] + d.Du, 0));
@@ -959,37 +1155,20 @@ int backward_ps(const Dims& d, const Params& P, const WS& w, const PsPlan& pp, c
     int cs_done = 0;
     // (all products on the f32 kernel here: at the CCMR shape -- 7,600 (b, t) rows -- the bf16x3 family would take four of them as a
     //  launch of its own IN FRONT of this one, on the chain to the dense ApplyAdam: 0.3582 vs 0.3566 ms, two alternating pairs)
-    G(gemm_queue_flush(&gq, 0, ws + w.dwslab, w.dwslab_floats, fs, &rg, &cq, ws + w.cs_part, w.cs_part_floats, &cs_done));
+    G(gemm_queue_flush(&q.gq, 0, ws + w.dwslab, w.dwslab_floats, fs, &rg, &cq, ws + w.cs_part, w.cs_part_floats, &cs_done));
     W1Fold wf;
     memset(&wf, 0, sizeof(wf));
     wf.Dk = d.Dk; wf.NA = AT1; wf.dweff = ws + w.dweff; wf.dwq = ws + w.dwq; wf.gW1 = gw + P.at_w[1];
     G(score_launch_finish(&rg, &cq, ws + w.cs_part, w.cs_part_floats, fs, cs_done, &wf));
     if (fin_side) HIPTRY(hipEventRecord((hipEvent_t)st->grads_done_event, fs));
   }
-  // ---- embedding rows (score.py:51-66): the sorted pull-form scatter
+  // ---- embedding rows.  The plan: in score_state_t.plan_workspace whenever the caller names one.  No scatter-mode test here:
+  // this pass never runs under scatter_mode 1 (ps_path), the header defines the field for mode 0 only, and the project's own
+  // callers set it there only (score_amd/model.py; step.hip passes none).  The test of the layer-by-layer pass would matter
+  // for a sharded (mode 2) caller that sorts into a second buffer: the unique positions would then have to come from that
+  // buffer too (row_scatter reads them from the pass's own workspace).
   if (st->plan_done_event) HIPTRY(hipStreamWaitEvent(s, (hipEvent_t)st->plan_done_event, 0));
-  {
-    PullArgs pa;
-    memset(&pa, 0, sizeof(pa));
-    pa.D = d.D; pa.K = d.K; pa.zero_is_dummy = 1;
-    pa.flags = st->scatter_mode == 0 ? st->row_flags : nullptr;
-    pa.uid = st->scatter_mode == 2 ? reinterpret_cast<const uint32_t*>(ws + w.uid) : nullptr;
-    const float invK = 1.0f / (float)d.K;
-    const float* Gm[6] = {ws + w.dxside[0], ws + w.dxside[1], ws + w.dxside[0], ws + w.dxside[1], ws + w.dtgt, ws + w.dtgt};
-    const int ldg[6] = {d.I, d.I, d.I, d.I, d.Dq, d.Dq};
-    const int gcol[6] = {0, d.Du, d.Di, 0, 0, d.Du};
-    for (int g = 0; g < 6; ++g) { pa.G[g] = Gm[g]; pa.ldg[g] = ldg[g]; pa.gcol[g] = gcol[g]; pa.constA[g] = 1.0f; }
-    pa.cA[0] = ws + w.pcoef[0]; pa.cA[2] = ws + w.pcoef[1];
-    pa.constA[1] = invK; pa.constA[3] = invK;
-    pa.cB[0] = pa.cB[1] = ws + w.dzcoef[0]; pa.cB[2] = pa.cB[3] = ws + w.dzcoef[1];
-    pa.Wv[0] = W + P.ca_w[0] + d.Di; pa.Wv[1] = W + P.ca_w[0] + 2 * d.Di;
-    pa.Wv[2] = W + P.ca_w[1] + d.Du; pa.Wv[3] = W + P.ca_w[1] + 2 * d.Du;
-    const int64_t n_occ = (int64_t)B * (2 * (int64_t)T * d.K * (d.Fu + d.Fi) + d.Fu + d.Fi);
-    // (score_state_t.plan_workspace: the plan of this batch sorted into ANOTHER workspace of the same layout, a step ahead)
-    float* pw = st->plan_workspace ? st->plan_workspace : ws;
-    G(score_launch_pull(pa, reinterpret_cast<uint32_t*>(pw + w.keys_out), reinterpret_cast<uint32_t*>(pw + w.vals_out), n_occ + 1,
-                        grad_table, ws + w.partials, w.partial_floats, s));
-  }
+  G(row_scatter(c, st->plan_workspace ? st->plan_workspace : ws, grad_table));
   EV(4);
   EV(5);
   // (the forward pass put its loss reduction on the side stream: loss[] is final on `stream` behind this pass -- it ran beside
@@ -1014,36 +1193,29 @@ extern "C" int score_forward(const score_config_t* cfg, const score_state_t* st,
                              float reg_lambda, float keep_prob, const uint8_t* drop_mask0,
                              const uint8_t* drop_mask1, uint64_t drop_seed, void* const* stage_events,
                              void* stream) {
-  Dims d;
-  SCORE_TRY(make_dims(cfg, &d));
+  Pass c;
+  SCORE_TRY(make_dims(cfg, &c.d));
   if (!st || !bt || !st->table || !st->w || !st->workspace || bt->B <= 0) return SCORE_E_BADARG;
   if (!bt->user_1hop || !bt->user_2hop || !bt->item_1hop || !bt->item_2hop || !bt->target_user ||
       !bt->target_item || !bt->label || !bt->length)
     return SCORE_E_BADARG;
   if (!(keep_prob > 0.f) || keep_prob > 1.f) return SCORE_E_BADARG;
-  Params P;
-  build_layout(d, nullptr, 0, &P);
-  const int B = bt->B, T = active_T(d, bt), H = d.H, BT = B * T;   // T: the time slices computed
-  WS w;
-  build_ws(d, B, &w);
-  if (w.total * 4 > st->workspace_bytes) return SCORE_E_WORKSPACE;
-  hipStream_t s = (hipStream_t)stream;
+  SCORE_TRY(pass_fill(&c, st, bt, stream));
+  const Dims& d = c.d; const Params& P = c.P; const WS& w = c.w; const Flags& fl = c.fl;
+  const int B = c.B, T = c.T, H = c.H, BT = c.BT, x3 = c.x3, Bg = c.Bg;
+  hipStream_t s = c.s;
   {
     PsPlan pp;       // the reference's own shapes: the whole pass as one kernel per sample (persample.h)
-    if (!(st->debug_flags & 2048) && ps_path(d, st, bt, T, &pp))
-      return forward_ps(d, P, w, pp, st, bt, reg_lambda, keep_prob, drop_mask0, drop_mask1, drop_seed, stage_events, s);
+    if (!fl.ps_bwd_only && ps_path(d, st, bt, T, &pp))
+      return forward_ps(c, pp, reg_lambda, keep_prob, drop_mask0, drop_mask1, drop_seed, stage_events);
   }
-  float* ws = st->workspace;
-  const float* W = st->w;
-  float* scratch = ws + w.scratch;
-  const int x3 = st->gemm_mode == 1 ? GF_X3 : 0;
+  float* ws = c.ws; const float* W = c.W; float* scratch = c.scratch;
 
   // side stream: the target rows, the L2 norm of the weights (needs no batch), then the attention's query branch (target rows and
   // weights only) -- beside the gather and the GRUs
   SideStream* sd = nullptr;
   G(side_stream(st, s, &sd));
-  HIPTRY(hipEventRecord(sd->fork, s));
-  HIPTRY(hipStreamWaitEvent(sd->st, sd->fork, 0));
+  G(fork_side(sd, s));
   sd->fwd_on = s;       // (score_backward on this stream next finds the side stream already behind everything before this pass)
   // target rows -> query [tu | ti] and head_inp [.., ti, tu]      (score.py:62-66, 210, 217).  On the side stream since round 6:
   // its readers on `stream` -- the attention, the head -- are behind the side stream's join anyway, and the fused gather, which
@@ -1051,40 +1223,13 @@ extern "C" int score_forward(const score_config_t* cfg, const score_state_t* st,
   // (four interleaved pairs at cfg-3: 886.5 k vs 881.3 k samples/s)
   G(score_launch_target_fwd(st->table, d.D, d.Fu, d.Fi, B, bt->target_user, bt->target_item, ws + w.query, d.Dq,
                             ws + w.head_inp, d.Dhead, d.off_ti, d.off_tu, sd->st, st->n_table_rows, st->id_status));
-  // what the step derives from the weights alone, in ONE launch off the main stream: the [Wx_gates | Wx_cand] copies for the
-  // hoisted GRU input projections, the folded first attention layer (dense_3 on [q, k, q-k, q*k], head.hip) and the L2 norm's
-  // partial sums (three launches before round 4: the reference's own batch sizes are bound by the host's launch calls)
-  const int64_t weff_stride = align_up64(2 * (int64_t)d.Dk * AT1 + 48, 4);     // replicas of the folded attention weight (build_ws)
-  G(score_launch_weight_prep(W + P.gk[0], W + P.ck[0], W + P.gb[0], W + P.cb[0], W + P.gk[1], W + P.ck[1], W + P.gb[1],
-                             W + P.cb[1], d.Is[0], d.Is[1], d.Ic, H, ws + w.wxcat, d.Dk, AT1, d.attn ? W + P.at_w[1] : nullptr,
-                             ws + w.weff, ws + w.wq, SCORE_WEFF_COPIES, weff_stride, W, P.n_reg, ws + w.part, sd->st));
+  G(weight_prep(c, sd->st));       // (off the main stream)
   // the panel form of the projections and of their input gradients (gemm_panel.hip) takes the weights as fragment images:
   // written here, once per step, behind the concatenated copies (the backward pass reuses them as it reuses the copies)
-  const bool panel_x = panel_gemms(d, st, BT, 0), panel_d = panel_gemms(d, st, BT, 1);
-  {
-    const float* cats[2] = {ws + w.wxcat, ws + w.wxcat + (int64_t)(d.Ic + 1) * 3 * H};
-    if (panel_x) {
-      const int ns = panel_x_splits(H), Nh = 3 * H / ns;
-      const int64_t per = score_gemm_panel_image_floats(Nh, d.Is[0]);
-      const float* bs[4];
-      float* ix[4];
-      for (int g = 0; g < 2 * ns; ++g) { bs[g] = cats[g / ns] + (g % ns) * Nh; ix[g] = ws + w.pimg_x[g / ns] + (g % ns) * per; }
-      G(score_gemm_panel_prep(2 * ns, bs, 3 * H, 1, Nh, d.Is[0], ix, sd->st));
-    }
-    if (panel_d) {
-      const int ns = panel_d_splits(d.Is[0]), Nh = d.Is[0] / ns;
-      const int64_t per = score_gemm_panel_image_floats(Nh, 3 * H);
-      const float* bs[4];
-      float* id[4];
-      for (int g = 0; g < 2 * ns; ++g) { bs[g] = cats[g / ns] + (int64_t)(g % ns) * Nh * 3 * H; id[g] = ws + w.pimg_d[g / ns] + (g % ns) * per; }
-      G(score_gemm_panel_prep(2 * ns, bs, 3 * H, 0, Nh, 3 * H, id, sd->st));
-    }
-  }
-  hipEvent_t wx_ev = sd->wx;
-  HIPTRY(hipEventRecord(wx_ev, sd->st));
-  const Flags fl = flags_of(st);
-  const bool head_fused = !fl.head_unfused;
-  if (!d.attn) HIPTRY(hipEventRecord(sd->join, sd->st));
+  const bool panel_x = panel_gemms(d, st, BT, 0);
+  if (panel_x) G(panel_prep(c, 0, sd->st));
+  if (panel_gemms(d, st, BT, 1)) G(panel_prep(c, 1, sd->st));
+  HIPTRY(hipEventRecord(sd->wx, sd->st));
   if (d.attn) {
     float* scratch2 = ws + w.scratch2;
     G(gemm_mode_call(x3, 0, B, d.Dk, d.Dq, ws + w.query, d.Dq, W + P.at_w[0], d.Dk, ws + w.q, d.Dk, W + P.at_b[0], GF_BIAS,
@@ -1093,28 +1238,22 @@ extern "C" int score_forward(const score_config_t* cfg, const score_state_t* st,
     // a1 = relu([k, q*k] . Weff + (q . Wq + b)[sample])
     G(gemm_mode_call(x3, 0, B, AT1, d.Dk, ws + w.q, d.Dk, ws + w.wq, AT1, ws + w.qz, AT1, W + P.at_b[1], GF_BIAS, 1.f,
                      nullptr, 0, scratch2, w.scratch_floats, sd->st));
-    HIPTRY(hipEventRecord(sd->join, sd->st));
   }
-  // co-attention 1: (user_1hop, item_2hop, target_item) ; 2: (user_2hop, item_1hop, target_user)  (:196-197)
-  // user_side = [user_1hop_seq | user_2hop_seq], item_side = [item_1hop_seq | item_2hop_seq]   (:200-201)
+  HIPTRY(hipEventRecord(sd->join, sd->st));
   EV(0);
   {
     CoattnArgs ca;
-    memset(&ca, 0, sizeof(ca));
-    ca.table = st->table; ca.K = d.K; ca.T = T; ca.Tidx = d.T; ca.mode = d.coattn ? 0 : 1;
-    ca.n_rows = (uint32_t)(st->n_table_rows < 0x80000000ll ? st->n_table_rows : 0x80000000ll); ca.id_status = st->id_status;
+    CoattnCols k;
+    coattn_args(c, &ca, &k);
+    ca.id_status = st->id_status;
     ca.c[0].bit1 = 0; ca.c[0].bit2 = 3; ca.c[1].bit1 = 1; ca.c[1].bit2 = 2;      // positions in the feed tuple (graph_loader.py:383)
-    const int ldi = 4 * d.K;
-    CoattnCall& c0 = ca.c[0];
-    c0.idx1 = bt->user_1hop; c0.idx2 = bt->item_2hop; c0.tgt = ws + w.query + d.Du; c0.ldt = d.Dq; c0.tidx = bt->target_item;
-    c0.W = d.coattn ? W + P.ca_w[0] : nullptr; c0.bias = d.coattn ? W + P.ca_b[0] : nullptr;
-    c0.out1 = ws + w.xside[0]; c0.ld1 = d.I; c0.out2 = ws + w.xside[1] + d.Du; c0.ld2 = d.I;
-    c0.info = ws + w.info; c0.ldi = ldi; c0.rsave = ws + w.rsave[0]; c0.F = d.Fi;
-    CoattnCall& c1 = ca.c[1];
-    c1.idx1 = bt->user_2hop; c1.idx2 = bt->item_1hop; c1.tgt = ws + w.query; c1.ldt = d.Dq; c1.tidx = bt->target_user;
-    c1.W = d.coattn ? W + P.ca_w[1] : nullptr; c1.bias = d.coattn ? W + P.ca_b[1] : nullptr;
-    c1.out1 = ws + w.xside[0] + d.Di; c1.ld1 = d.I; c1.out2 = ws + w.xside[1]; c1.ld2 = d.I;
-    c1.info = ws + w.info + 2 * d.K; c1.ldi = ldi; c1.rsave = ws + w.rsave[1]; c1.F = d.Fu;
+    const int32_t* tidx[2] = {bt->target_item, bt->target_user};
+    for (int i = 0; i < 2; ++i) {
+      CoattnCall& cc = ca.c[i];
+      cc.tgt = ws + w.query + (i ? 0 : d.Du); cc.ldt = d.Dq; cc.tidx = tidx[i];
+      cc.bias = d.coattn ? W + P.ca_b[i] : nullptr;
+      cc.out1 = ws + w.xside[0] + k.col1[i]; cc.out2 = ws + w.xside[1] + k.col2[i]; cc.info = ws + w.info + k.info_col[i];
+    }
     G(score_coattn_fwd_multi(ca, 2, d.D, B, s));
   }
   if (st->gather_done_event) HIPTRY(hipEventRecord((hipEvent_t)st->gather_done_event, s));
@@ -1133,48 +1272,31 @@ extern "C" int score_forward(const score_config_t* cfg, const score_state_t* st,
     }
   }
   // GRUs (:205-208): hoisted x-projection, then the persistent recurrence
+  HIPTRY(hipStreamWaitEvent(s, sd->wx, 0));
   if (d.g4r) {
-    HIPTRY(hipStreamWaitEvent(s, wx_ev, 0));
-    G(g4r_grus_fwd(d, P, w, st, bt, T, x3, s));
-  } else
-  {
+    G(g4r_grus_fwd(c));
+  } else {
     GruArgs ga;
-    memset(&ga, 0, sizeof(ga));
-    ga.B = B; ga.T = T; ga.H = H; ga.length = bt->length; ga.nw8 = 1;
-    ga.tmp = ws + w.gru_tmp; ga.tmp_floats = w.gru_tmp_floats; ga.x3 = x3 != 0; ga.x3_rec = ga.x3 && !(st->debug_flags & 4); ga.stepwise = fl.gru_stepwise;   // H = 128: two waves per SIMD hide the LDS/epilogue latency (measured -0.08 ms/step)
-    HIPTRY(hipStreamWaitEvent(s, wx_ev, 0));
+    gru_header(c, &ga);
+    float* xp[2] = {ws + w.xproj[0], ws + w.xproj[1]};
     if (d.Is[0] == d.Is[1]) {    // both sides' projections in ONE grouped launch (each with its own bias row)
-      const float* c0 = ws + w.wxcat;
-      const float* c1 = c0 + (int64_t)(d.Ic + 1) * 3 * H;
-      const float* Ax[2] = {xin[0], xin[1]};
-      const float* Bx[2] = {c0, c1};
-      float* Cx[2] = {ws + w.xproj[0], ws + w.xproj[1]};
-      const float* bx[2] = {c0 + (int64_t)d.Is[0] * 3 * H, c1 + (int64_t)d.Is[1] * 3 * H};
       if (panel_x) {
-        const int ns = panel_x_splits(H), Nh = 3 * H / ns;
-        const int64_t per = score_gemm_panel_image_floats(Nh, d.Is[0]);
-        PanelGroup pg[4];
-        for (int g = 0; g < 2 * ns; ++g) {
-          const int side = g / ns, h = g % ns;
-          pg[g].A = Ax[side]; pg[g].img = ws + w.pimg_x[side] + h * per; pg[g].C = Cx[side] + h * Nh; pg[g].bias = bx[side] + h * Nh;
-        }
-        G(score_gemm_panel(2 * ns, pg, BT, Nh, d.Is[0], x_ld(d, 0), 3 * H, s));
+        G(panel_launch(c, 0, xin, xp));
       } else {
-        G(score_gemm_same_shape(0, 2, BT, 3 * H, d.Is[0], Ax, x_ld(d, 0), Bx, 3 * H, Cx, 3 * H, GF_BIAS, x3 != 0, scratch,
+        const float* Bx[2] = {wxcat(c, 0), wxcat(c, 1)};
+        const float* bx[2] = {Bx[0] + (int64_t)d.Is[0] * 3 * H, Bx[1] + (int64_t)d.Is[1] * 3 * H};
+        G(score_gemm_same_shape(0, 2, BT, 3 * H, d.Is[0], xin, x_ld(d, 0), Bx, 3 * H, xp, 3 * H, GF_BIAS, x3 != 0, scratch,
                                 w.scratch_floats, s, bx));
       }
     }
     for (int sd = 0; sd < 2; ++sd) {
-      float* xp = ws + w.xproj[sd];
       // x . [Wx_gates | Wx_cand] + [b_gates | b_cand]: one GEMM per side on the concatenated copy
-      const float* cat = ws + w.wxcat + (int64_t)sd * (d.Ic + 1) * 3 * H;
+      const float* cat = wxcat(c, sd);
       if (d.Is[0] != d.Is[1])
-        G(gemm_mode_call(x3, 0, BT, 3 * H, d.Is[sd], xin[sd], x_ld(d, sd), cat, 3 * H, xp, 3 * H, cat + (int64_t)d.Is[sd] * 3 * H,
+        G(gemm_mode_call(x3, 0, BT, 3 * H, d.Is[sd], xin[sd], x_ld(d, sd), cat, 3 * H, xp[sd], 3 * H, cat + (int64_t)d.Is[sd] * 3 * H,
                          GF_BIAS, 1.f, nullptr, 0, scratch, w.scratch_floats, s));
-      GruSide& g = ga.s[sd];
-      g.xproj = xp; g.Wg = W + P.gk[sd] + (int64_t)d.Is[sd] * 2 * H; g.ldwg = 2 * H;
-      g.Wc = W + P.ck[sd] + (int64_t)d.Is[sd] * H; g.ldwc = H;
-      g.out = ws + w.gru_out[sd]; g.ldo = H; g.gates = ws + w.gates[sd]; g.final_state = ws + w.gru_final[sd];
+      gru_side(c, sd, &ga.s[sd]);
+      ga.s[sd].xproj = xp[sd]; ga.s[sd].final_state = ws + w.gru_final[sd];
     }
     G(score_gru_fwd_multi(ga, 2, s));
   }
@@ -1188,7 +1310,7 @@ extern "C" int score_forward(const score_config_t* cfg, const score_state_t* st,
                                                 ws + w.info, ws + w.weff, ws + w.qz, W + P.at_w[2], W + P.at_b[2],
                                                 W + P.at_w[3], W + P.at_b[3], bt->length, ws + w.ainp, ws + w.a1, ws + w.a2,
                                                 ws + w.att_score, ws + w.head_inp, d.Dhead, d.off_u, d.off_i, s,
-                                                SCORE_WEFF_COPIES, weff_stride);
+                                                SCORE_WEFF_COPIES, c.weff_stride);
     if (frc != 0 && frc != SCORE_E_SHAPE) return frc;
     if (frc == SCORE_E_SHAPE) {
     G(score_launch_attn_build_inp(B, T, H, d.NI, ws + w.q, ws + w.gru_out[0], ws + w.gru_out[1], ws + w.info,
@@ -1219,49 +1341,31 @@ extern "C" int score_forward(const score_config_t* cfg, const score_state_t* st,
   }
   EV(3);
   // build_fc_net (:68-76)
-  const float rs = (float)(1.0 / sqrt(1.0 + 1e-3));
   const int dflag = keep_prob < 1.f ? GF_DROP : 0;
-  const int Bg = st->global_batch > 0 ? st->global_batch : B;
   if (!d.attn) HIPTRY(hipStreamWaitEvent(s, sd->join, 0));     // (with attention the join was waited for there)
   if (d.gcmc) {
     // GCMC (:199-203): y = exp(a) / (exp(a) + exp(c)) of the final states, its log-loss term and dL/da (gcmc.hip); no dropout,
-    // keep_prob has no effect.  The loss reduction as behind the fused head
+    // keep_prob has no effect
     G(score_launch_gcmc_head_fwd(B, H, ws + w.gru_final[0], ws + w.gru_final[1], W + P.gm_4, W + P.gm_5, bt->label, ws + w.y_pred,
                                  ws + w.lossb, ws + w.gcmc_pn, ws + w.gcmc_pn + (int64_t)B * H, ws + w.gcmc_g, Bg, s));
-    hipStream_t ls = s;
-    if (st->loss_done_event) {
-      HIPTRY(hipEventRecord(sd->fork, s));
-      HIPTRY(hipStreamWaitEvent(sd->st, sd->fork, 0));
-      ls = sd->st;
-    }
-    G(score_launch_loss_final(B, ws + w.lossb, ws + w.loss, reg_lambda, ws + w.part, Bg, ls, st->id_status));
-    if (st->loss_done_event) HIPTRY(hipEventRecord((hipEvent_t)st->loss_done_event, ls));
+    G(loss_tail(c, sd, reg_lambda));
     EV(4);
     return 0;
   }
   // the whole head in one launch (head_fused.hip); shapes it does not cover take the layer-by-layer path
-  int hrc = !head_fused ? SCORE_E_SHAPE
-                : score_launch_head_fwd_fused(B, d.Dhead, FC1, FC2, ws + w.head_inp, W + P.bn_g, W + P.bn_b, rs, W + P.fc_w[0],
+  int hrc = fl.head_unfused ? SCORE_E_SHAPE
+                : score_launch_head_fwd_fused(B, d.Dhead, FC1, FC2, ws + w.head_inp, W + P.bn_g, W + P.bn_b, c.rs, W + P.fc_w[0],
                                               W + P.fc_b[0], W + P.fc_w[1], W + P.fc_b[1], W + P.fc_w[2], W + P.fc_b[2],
                                               keep_prob, drop_mask0, drop_mask1, drop_seed, drop_seed ^ 0x5DEECE66Dull,
                                               bt->label, ws + w.bn, ws + w.f1, ws + w.f2, ws + w.logit, ws + w.y_pred,
                                               ws + w.lossb, ws + w.dlogit, Bg, s,
                                               st->step_scalars ? &st->step_scalars->drop_seed : nullptr, ws + w.dz2,
-                                              (st->debug_flags & 2) ? 1 : 0);
+                                              fl.head_fused_any_b ? 1 : 0);
   if (hrc == 0) {
-    // (dz2 came with the head.)  The loss reduction is one workgroup and has no reader inside the step: with
-    // score_state_t.loss_done_event it runs on the side stream, so the backward pass's first launch follows the head directly
-    hipStream_t ls = s;
-    if (st->loss_done_event) {
-      HIPTRY(hipEventRecord(sd->fork, s));
-      HIPTRY(hipStreamWaitEvent(sd->st, sd->fork, 0));
-      ls = sd->st;
-    }
-    G(score_launch_loss_final(B, ws + w.lossb, ws + w.loss, reg_lambda, ws + w.part, Bg, ls, st->id_status));
-    if (st->loss_done_event) HIPTRY(hipEventRecord((hipEvent_t)st->loss_done_event, ls));
+    G(loss_tail(c, sd, reg_lambda));       // (dz2 came with the head)
   } else if (hrc == SCORE_E_SHAPE) {
     if (st->step_scalars && keep_prob < 1.f) return SCORE_E_SHAPE;   // the layer-by-layer path takes its seed by value
-    G(score_launch_bn_fwd(B, d.Dhead, ws + w.head_inp, W + P.bn_g, W + P.bn_b, rs, ws + w.bn, s));
+    G(score_launch_bn_fwd(B, d.Dhead, ws + w.head_inp, W + P.bn_g, W + P.bn_b, c.rs, ws + w.bn, s));
     G(gemm_mode_call(x3, 0, B, FC1, d.Dhead, ws + w.bn, d.Dhead, W + P.fc_w[0], FC1, ws + w.f1, FC1, W + P.fc_b[0],
                  GF_BIAS | GF_RELU | dflag, keep_prob, drop_mask0, drop_seed, scratch, w.scratch_floats, s));
     G(gemm_mode_call(x3, 0, B, FC2, FC1, ws + w.f1, FC1, W + P.fc_w[1], FC2, ws + w.f2, FC2, W + P.fc_b[1],
@@ -1281,33 +1385,25 @@ extern "C" int score_forward(const score_config_t* cfg, const score_state_t* st,
 extern "C" int score_backward(const score_config_t* cfg, const score_state_t* st, const score_batch_t* bt,
                               float keep_prob, float* gw, float* grad_table, void* const* stage_events,
                               void* stream) {
-  Dims d;
-  SCORE_TRY(make_dims(cfg, &d));
+  Pass c;
+  SCORE_TRY(make_dims(cfg, &c.d));
   if (!st || !bt || !st->table || !st->w || !st->workspace || !gw || !grad_table || bt->B <= 0)
     return SCORE_E_BADARG;
-  Params P;
-  build_layout(d, nullptr, 0, &P);
-  const int B = bt->B, T = active_T(d, bt), H = d.H, BT = B * T;   // T: the time slices computed
-  WS w;
-  build_ws(d, B, &w);
-  if (w.total * 4 > st->workspace_bytes) return SCORE_E_WORKSPACE;
-  hipStream_t s = (hipStream_t)stream;
+  SCORE_TRY(pass_fill(&c, st, bt, stream));
+  const Dims& d = c.d; const Params& P = c.P; const WS& w = c.w; const Flags& fl = c.fl;
+  const int B = c.B, T = c.T, H = c.H, BT = c.BT, x3 = c.x3;
+  hipStream_t s = c.s;
   {
     PsPlan pp;
-    if (!(st->debug_flags & 1024) && ps_path(d, st, bt, T, &pp))
-      return backward_ps(d, P, w, pp, st, bt, keep_prob, gw, grad_table, stage_events, s);
+    if (!fl.ps_fwd_only && ps_path(d, st, bt, T, &pp))
+      return backward_ps(c, pp, keep_prob, gw, grad_table, stage_events);
   }
-  float* ws = st->workspace;
-  const float* W = st->w;
-  float* scratch = ws + w.scratch;
+  float* ws = c.ws; const float* W = c.W; float* scratch = c.scratch;
   const int64_t SF = w.scratch_floats;
-  const int x3 = st->gemm_mode == 1 ? GF_X3 : 0;
-  const Flags fl = flags_of(st);
-  ColsumJobs cq;
-  cq.n = 0; cq.part_used = 0;
-  // weight gradients C = X^T dY have no consumer inside the pass: queued, issued together at its end
-  GemmQueue gq;
-  gq.n = 0;
+  GradQueues q;
+  queues_init(&q);
+  GemmQueue& gq = q.gq;
+  ColsumJobs& cq = q.cq;
   // The dense gradient starts from zero (some of its pieces are accumulated, some variables of some model types get
   // none).  Nothing on the main stream writes it before the side stream's join below -- every weight / bias
   // gradient is queued -- so the fill runs on the side stream, off the chain of dependent launches.
@@ -1318,12 +1414,8 @@ extern "C" int score_backward(const score_config_t* cfg, const score_state_t* st
   //  the head's forward and backward costs the launch stream a ~6-us bubble; only a caller that skipped the forward pays it.)
   const bool forked = side->fwd_on == s;
   side->fwd_on = nullptr;
-  if (!forked) {
-    HIPTRY(hipEventRecord(side->fork, s));
-    HIPTRY(hipStreamWaitEvent(side->st, side->fork, 0));
-  }
-  hipError_t he = hipMemsetAsync(gw, 0, P.n_floats * sizeof(float), side->st);
-  if (he != hipSuccess) return (int)he;
+  if (!forked) G(fork_side(side, s));
+  HIPTRY(hipMemsetAsync(gw, 0, P.n_floats * sizeof(float), side->st));
 
   EV(0);
   if (d.gcmc) {
@@ -1335,35 +1427,24 @@ extern "C" int score_backward(const score_config_t* cfg, const score_state_t* st
     G(gemm_queue_add(&gq, H, H, B, ws + w.gru_final[1], H, ws + w.gcmc_gu + (int64_t)B * H, H, gw + P.gm_5, H));
   } else {
     // ---- head (score.py:68-81)
-    // fc3: dW = f2^T dlogit, db = sum dlogit, dz2 = [f2>0] dlogit w3 / keep
-    G(gemm_queue_add(&gq, FC2, 1, B, ws + w.f2, FC2, ws + w.dlogit, 1, gw + P.fc_w[2], 1));
-    G(colsum_queue_add(&cq, ws + w.dlogit, B, 1, 1, gw + P.fc_b[2], 0));
+    // fc3: dz2 = [f2>0] dlogit w3 / keep
     if (fl.head_unfused || !score_head_fwd_fused_fits(B, d.Dhead, FC1, FC2))     // (else score_forward's fused head wrote dz2)
       G(score_launch_outer_relu_bwd(B, FC2, ws + w.dlogit, W + P.fc_w[2], ws + w.f2, keep_prob, ws + w.dz2, s));
-    // fc2
-    G(gemm_queue_add(&gq, FC1, FC2, B, ws + w.f1, FC1, ws + w.dz2, FC2, gw + P.fc_w[1], FC2));
-    G(colsum_queue_add(&cq, ws + w.dz2, B, FC2, FC2, gw + P.fc_b[1], 0));
-    const float rs = (float)(1.0 / sqrt(1.0 + 1e-3));
     // dz1, d bn1, d head input and bn1's d gamma terms: one launch (head_fused.hip) ...
     int hbrc = fl.head_unfused ? SCORE_E_SHAPE
                    : score_launch_head_bwd_fused(B, d.Dhead, FC1, FC2, ws + w.dz2, W + P.fc_w[1], ws + w.f1, keep_prob,
-                                                 W + P.fc_w[0], ws + w.head_inp, W + P.bn_g, rs, ws + w.dz1, ws + w.dbn,
+                                                 W + P.fc_w[0], ws + w.head_inp, W + P.bn_g, c.rs, ws + w.dz1, ws + w.dbn,
                                                  ws + w.dhead, ws + w.dgstage, s);
     if (hbrc != 0 && hbrc != SCORE_E_SHAPE) return hbrc;
-    if (hbrc == SCORE_E_SHAPE)      // ... or layer by layer
+    // (bn1's d gamma / d beta behind the fused kernel: column sums of what it wrote)
+    G(queue_head(c, &q, gw, hbrc == 0));
+    if (hbrc == SCORE_E_SHAPE) {     // ... or layer by layer
       G(gemm_mode_call(x3, 1, B, FC1, FC2, ws + w.dz2, FC2, W + P.fc_w[1], FC2, ws + w.dz1, FC1, nullptr, GF_RELUGRAD, keep_prob,
                        reinterpret_cast<const uint8_t*>(ws + w.f1), 0, scratch, SF, s));   // relu/dropout mask of fc1 in the epilogue
-    // fc1 + bn1
-    G(gemm_queue_add(&gq, d.Dhead, FC1, B, ws + w.bn, d.Dhead, ws + w.dz1, FC1, gw + P.fc_w[0], FC1));
-    G(colsum_queue_add(&cq, ws + w.dz1, B, FC1, FC1, gw + P.fc_b[0], 0));
-    if (hbrc == SCORE_E_SHAPE) {
       G(gemm_mode_call(x3, 1, B, d.Dhead, FC1, ws + w.dz1, FC1, W + P.fc_w[0], FC1, ws + w.dbn, d.Dhead, nullptr, 0, 1.f,
                    nullptr, 0, scratch, SF, s));
-      G(score_launch_bn_bwd(B, d.Dhead, ws + w.head_inp, W + P.bn_g, rs, ws + w.dbn, ws + w.dhead, gw + P.bn_g,
+      G(score_launch_bn_bwd(B, d.Dhead, ws + w.head_inp, W + P.bn_g, c.rs, ws + w.dbn, ws + w.dhead, gw + P.bn_g,
                             gw + P.bn_b, ws + w.dgstage, scratch, SF, &cq, s));
-    } else {                        // (bn1's d gamma / d beta: column sums of what the fused kernel wrote)
-      G(colsum_queue_add(&cq, ws + w.dgstage, B, d.Dhead, d.Dhead, gw + P.bn_g, 0));
-      G(colsum_queue_add(&cq, ws + w.dbn, B, d.Dhead, d.Dhead, gw + P.bn_b, 0));
     }
   }
 
@@ -1371,6 +1452,7 @@ extern "C" int score_backward(const score_config_t* cfg, const score_state_t* st
   const float* dfinal[2] = {nullptr, nullptr};
   if (d.attn) {
     // ---- temporal attention (score.py:169-186, 214-215)
+    G(queue_attn(c, &q, gw));
     // pooling / softmax / dense_5 backward and, in the same launch, dense_4's (da1 with dense_3's relu mask)
     // (on small batches the fused attention backward below does this part too -- one launch less: 0.0218 -> 0.0183 ms for
     //  the stage at the reference's own shape; at cfg-3, where a workgroup per four samples serialises what 1024 small
@@ -1383,25 +1465,14 @@ extern "C" int score_backward(const score_config_t* cfg, const score_state_t* st
                                                d.off_i, ws + w.ds, ws + w.da2, s, AT1, W + P.at_w[2], ws + w.a1, ws + w.da1);
     if (prc != 0 && prc != SCORE_E_SHAPE) return prc;
     const bool da1_done = prc == 0;
-    if (!da1_done)
+    if (!da1_done) {
       G(score_launch_attn_pool_bwd(B, T, H, AT2, ws + w.a2, W + P.at_w[3], bt->length, ws + w.gru_out[0],
                                    ws + w.gru_out[1], ws + w.att_score, ws + w.dhead, d.Dhead, d.off_u, d.off_i,
                                    ws + w.ds, ws + w.da2, s));
-    // dense_5 (40 -> 1): dW = a2^T ds ; db = sum ds
-    G(gemm_queue_add(&gq, AT2, 1, BT, ws + w.a2, AT2, ws + w.ds, 1, gw + P.at_w[3], 1));
-    G(colsum_queue_add(&cq, ws + w.ds, BT, 1, 1, gw + P.at_b[3], 0));
-    // dense_4 (80 -> 40); da2 is already relu-masked
-    G(gemm_queue_add(&gq, AT1, AT2, BT, ws + w.a1, AT1, ws + w.da2, AT2, gw + P.at_w[2], AT2));
-    G(colsum_queue_add(&cq, ws + w.da2, BT, AT2, AT2, gw + P.at_b[2], 0));
-    if (!da1_done)
       G(gemm_mode_call(x3, 1, BT, AT1, AT2, ws + w.da2, AT2, W + P.at_w[2], AT2, ws + w.da1, AT1, nullptr, GF_RELUGRAD, 1.f,
                        reinterpret_cast<const uint8_t*>(ws + w.a1), 0, scratch, SF, s));    // relu mask of dense_3 in the epilogue
-    // dense_3 (4Dk -> 80), folded: weight gradient from [k, q*k]^T da1 and q^T sum_t da1
-    G(gemm_queue_add(&gq, 2 * d.Dk, AT1, BT, ws + w.ainp, 2 * d.Dk, ws + w.da1, AT1, ws + w.dweff, AT1));
-    G(colsum_queue_add(&cq, ws + w.da1, BT, AT1, AT1, gw + P.at_b[1], 0));
+    }
     // (sum_t da1 -> adzsum feeds the query branch only: computed on the side stream below)
-    G(gemm_queue_add(&gq, d.Dk, AT1, B, ws + w.q, d.Dk, ws + w.adzsum, AT1, ws + w.dwq, AT1));
-    // (gw + P.at_w[1] is assembled from dweff / dwq after the queue is flushed)
     // d inp = da1 . Weff^T and its way into d (states, atten_info, q): one launch where the shape allows (head_fused.hip).
     // dq = sum_t d(q*k).k here; the per-sample q-term gradient dzsum . Wq^T is added, and the query projection's
     // backward runs, on the side stream below (beside the recurrence: only the target rows consume them)
@@ -1431,15 +1502,13 @@ extern "C" int score_backward(const score_config_t* cfg, const score_state_t* st
         if (sd == 0) continue;
         G(score_launch_copy2d(B, H, ws + w.dhead, d.Dhead, ws + w.dfinal[1], H, s));
         dfinal[1] = ws + w.dfinal[1];
-        if (g4r_stacked(d, st)) continue;       // (the stacked kernel reads no dout of layer 2; the composed form's kernel does)
+        if (g4r_stacked(d, fl)) continue;       // (the stacked kernel reads no dout of layer 2; the composed form's kernel does)
       }
       else if (!d.gcmc) G(score_launch_copy2d(B, H, ws + w.dhead + sd * H, d.Dhead, ws + w.dfinal[sd], H, s));
       dfinal[sd] = ws + w.dfinal[sd];
-      he = hipMemsetAsync(ws + w.dgru[sd], 0, (int64_t)BT * H * sizeof(float), s);
-      if (he != hipSuccess) return (int)he;
+      HIPTRY(hipMemsetAsync(ws + w.dgru[sd], 0, (int64_t)BT * H * sizeof(float), s));
     }
-    he = hipMemsetAsync(ws + w.dinfo, 0, (int64_t)BT * 4 * d.K * sizeof(float), s);
-    if (he != hipSuccess) return (int)he;
+    HIPTRY(hipMemsetAsync(ws + w.dinfo, 0, (int64_t)BT * 4 * d.K * sizeof(float), s));
   }
 
   EV(2);
@@ -1448,8 +1517,7 @@ extern "C" int score_backward(const score_config_t* cfg, const score_state_t* st
   // the weight gradients queued so far (head, attention) have everything they need: beside the recurrence
   const int64_t slab_half = (w.dwslab_floats / 4) & ~(int64_t)3;        // region of the first one
   {
-    HIPTRY(hipEventRecord(side->fork, s));
-    HIPTRY(hipStreamWaitEvent(side->st, side->fork, 0));
+    G(fork_side(side, s));
     // Sharded path (scatter_mode 2): the caller runs several streams of its own (plan prefetch, gradient exchange,
     // two communicators) and the hardware queues are shared -- measured there, this side stream's kernels run 2-4x
     // slower and the join below stalls the scatter (0.27 -> 0.40 ms): the query branch stays on the main stream
@@ -1461,18 +1529,14 @@ extern "C" int score_backward(const score_config_t* cfg, const score_state_t* st
       // dq += dzsum . Wq^T ; dense_2 (query projection): dW, db queued, d query = dq . W^T
       G(gemm_mode_call(x3, 1, B, d.Dk, AT1, ws + w.adzsum, AT1, ws + w.wq, AT1, ws + w.dq, d.Dk, nullptr, GF_ACC, 1.f, nullptr,
                        0, scratch2, SF, qs));
-      G(gemm_queue_add(&gq, d.Dq, d.Dk, B, ws + w.query, d.Dq, ws + w.dq, d.Dk, gw + P.at_w[0], d.Dk));
-      G(colsum_queue_add(&cq, ws + w.dq, B, d.Dk, d.Dk, gw + P.at_b[0], 0));
+      G(queue_query(c, &q, gw));
       G(gemm_mode_call(x3, 1, B, d.Dq, d.Dk, ws + w.dq, d.Dk, W + P.at_w[0], d.Dk, ws + w.dquery, d.Dq, nullptr, 0, 1.f,
                        nullptr, 0, scratch2, SF, qs));
       // d query is what the main stream needs from here (target_bwd_kernel): its own event, so that the wait there does not
       // also sit behind the weight-gradient products and column sums that follow on this stream (at the small shapes the
       // side chain is as long as the main one: the scatter stage waited ~30 us for it)
       if (q_on_side) HIPTRY(hipEventRecord(side->wx, side->st));
-      if (!q_on_side) {       // dq is final on the main stream: the side stream (its weight-gradient product) follows it
-        HIPTRY(hipEventRecord(side->fork, s));
-        HIPTRY(hipStreamWaitEvent(side->st, side->fork, 0));
-      }
+      else G(fork_side(side, s));       // dq is final on the main stream: the side stream (its weight-gradient product) follows it
     }
     G(gemm_queue_flush(&gq, x3 != 0, ws + w.dwslab, slab_half, side->st));
     // the folded first attention layer's gradient from the two products just reduced (head.hip): here, off the launch stream
@@ -1482,52 +1546,24 @@ extern "C" int score_backward(const score_config_t* cfg, const score_state_t* st
     HIPTRY(hipEventRecord(side->join, side->st));
   }
   if (d.g4r) {
-    G(g4r_grus_bwd(d, P, w, st, bt, T, x3, dfinal[1], &gru_bias_rows, s));
-  } else
-  {
+    G(g4r_grus_bwd(c, dfinal[1], &gru_bias_rows));
+  } else {
     GruArgs ga;
-    memset(&ga, 0, sizeof(ga));
-    ga.B = B; ga.T = T; ga.H = H; ga.length = bt->length; ga.nw8 = 1;
-    ga.tmp = ws + w.gru_tmp; ga.tmp_floats = w.gru_tmp_floats; ga.x3 = x3 != 0; ga.x3_rec = ga.x3 && !(st->debug_flags & 4); ga.stepwise = fl.gru_stepwise;   // H = 128: two waves per SIMD hide the LDS/epilogue latency (measured -0.08 ms/step)
+    gru_header(c, &ga);
     for (int sd = 0; sd < 2; ++sd) {
-      GruSide& g = ga.s[sd];
-      g.Wg = W + P.gk[sd] + (int64_t)d.Is[sd] * 2 * H; g.ldwg = 2 * H;
-      g.Wc = W + P.ck[sd] + (int64_t)d.Is[sd] * H; g.ldwc = H;
-      g.out = ws + w.gru_out[sd]; g.ldo = H; g.gates = ws + w.gates[sd];
-      g.dout = ws + w.dgru[sd]; g.lddo = H; g.dfinal = dfinal[sd];
-      g.dxproj = ws + w.dxproj[sd]; g.rh = ws + w.rh[sd]; g.hprev = ws + w.hprev[sd];
-      // per-workgroup column sums of dxproj (the recurrence's bias gradients), where the kernel that runs provides them;
-      // one row per 16 samples at most: far inside the scratch that only the other recurrence kernels use
-      g.bias_slab = (2 * ((int64_t)B / 16 + 1) * 3 * H <= w.gru_tmp_floats) ? ws + w.gru_tmp + (int64_t)sd * (B / 16 + 1) * 3 * H
-                                                                          : nullptr;
+      gru_side(c, sd, &ga.s[sd]);
+      gru_side_bwd(c, sd, dfinal[sd], &ga.s[sd]);
     }
     G(score_gru_bwd_multi(ga, 2, s));
     gru_bias_rows = ga.bias_slab_rows;
   }
   for (int sd = 0; sd < 2; ++sd) {
     float* dxp = ws + w.dxproj[sd];
-    // kernels are [x ; h] row blocks (TF GRUCell): x rows first.  x part of both kernels in one product
-    // on the concatenated layout, then split into the two variables' gradients
-    const float* cat = ws + w.wxcat + (int64_t)sd * (d.Ic + 1) * 3 * H;
-    // x rows of the two kernels straight into their gradients (same A panel, the column tiles of [dgates | dcand])
-    const float* xin = d.gcmc ? ws + w.gcmc_z[sd] : (d.g4r && sd == 1) ? ws + w.gru_out[0] : ws + w.xside[sd];
-    G(gemm_queue_add(&gq, d.Is[sd], 2 * H, BT, xin, x_ld(d, sd), dxp, 3 * H, gw + P.gk[sd], 2 * H));
-    G(gemm_queue_add(&gq, d.Is[sd], H, BT, xin, x_ld(d, sd), dxp + 2 * H, 3 * H, gw + P.ck[sd], H));
-    G(gemm_queue_add(&gq, H, 2 * H, BT, ws + w.hprev[sd], H, dxp, 3 * H, gw + P.gk[sd] + (int64_t)d.Is[sd] * 2 * H, 2 * H));
-    G(gemm_queue_add(&gq, H, H, BT, ws + w.rh[sd], H, dxp + 2 * H, 3 * H, gw + P.ck[sd] + (int64_t)d.Is[sd] * H, H));
-    if (gru_bias_rows > 0) {     // (the recurrence left per-workgroup column sums of dxproj: a few dozen rows instead of B*T)
-      const float* slab = ws + w.gru_tmp + (int64_t)sd * (B / 16 + 1) * 3 * H;
-      G(colsum_queue_add(&cq, slab, gru_bias_rows, 2 * H, 3 * H, gw + P.gb[sd], 0));
-      G(colsum_queue_add(&cq, slab + 2 * H, gru_bias_rows, H, 3 * H, gw + P.cb[sd], 0));
-    } else {
-      G(colsum_queue_add(&cq, dxp, BT, 2 * H, 3 * H, gw + P.gb[sd], 0));
-      G(colsum_queue_add(&cq, dxp + 2 * H, BT, H, 3 * H, gw + P.cb[sd], 0));
-    }
+    const float* cat = wxcat(c, sd);
+    G(queue_gru_side(c, &q, gw, sd, gru_bias_rows));
     // d x = [dgates | dcand] . [Wx_gates | Wx_cand]^T
-    if (d.Is[sd] != d.I || d.g4r) {   // RRN: the 2-hop columns of this side carry no gradient (GRU4Rec: nor does any of "side" 1's)
-      he = hipMemsetAsync(ws + w.dxside[sd], 0, (int64_t)BT * d.I * sizeof(float), s);
-      if (he != hipSuccess) return (int)he;
-    }
+    if (d.Is[sd] != d.I || d.g4r)     // RRN: the 2-hop columns of this side carry no gradient (GRU4Rec: nor does any of "side" 1's)
+      HIPTRY(hipMemsetAsync(ws + w.dxside[sd], 0, (int64_t)BT * d.I * sizeof(float), s));
     if (d.g4r) {      // (layer 1's input gradient, for the row scatter; layer 2's went to layer 1 above)
       if (sd == 0)
         G(gemm_mode_call(x3, 1, BT, d.Di, 3 * H, dxp, 3 * H, cat, 3 * H, ws + w.dxside[0], d.I, nullptr, 0, 1.f, nullptr, 0,
@@ -1553,24 +1589,16 @@ extern "C" int score_backward(const score_config_t* cfg, const score_state_t* st
   }
   if (d.Is[0] == d.Is[1] && !d.gcmc && !d.g4r) {      // both sides' d x in ONE grouped launch: 2 x 576 tiles fill 512 slots better than twice 576
     const float* Ad[2] = {ws + w.dxproj[0], ws + w.dxproj[1]};
-    const float* Bd[2] = {ws + w.wxcat, ws + w.wxcat + (int64_t)(d.Ic + 1) * 3 * H};
     float* Cd[2] = {ws + w.dxside[0], ws + w.dxside[1]};
     if (panel_gemms(d, st, BT, 1)) {      // (the images were written by the forward pass, like the concatenated copies)
-      const int ns = panel_d_splits(d.Is[0]), Nh = d.Is[0] / ns;
-      const int64_t per = score_gemm_panel_image_floats(Nh, 3 * H);
-      PanelGroup pg[4];
-      for (int g = 0; g < 2 * ns; ++g) {
-        const int side_ = g / ns, h = g % ns;
-        pg[g].A = Ad[side_]; pg[g].img = ws + w.pimg_d[side_] + h * per; pg[g].C = Cd[side_] + h * Nh; pg[g].bias = nullptr;
-      }
-      G(score_gemm_panel(2 * ns, pg, BT, Nh, 3 * H, 3 * H, d.I, s));
+      G(panel_launch(c, 1, Ad, Cd));
     } else {
+      const float* Bd[2] = {wxcat(c, 0), wxcat(c, 1)};
       G(score_gemm_same_shape(1, 2, BT, d.Is[0], 3 * H, Ad, 3 * H, Bd, 3 * H, Cd, d.I, 0, x3 != 0, scratch, SF, s));
     }
   }
 
   // ---- co-attention + embedding rows (score.py:147-167, 196-201, 51-66)
-  const int64_t slab_used = slab_half;
   // The recurrences' weight-gradient products (X^T dY: eight products, K = B*T) need what the backward recurrence has written and
   // nothing else, and nothing inside the pass reads them.  Round 6: issued HERE on the side stream -- behind the head's / attention's
   // products, which end about where the input-gradient product below does -- so the matrix-bound launch runs beside the co-attention
@@ -1578,51 +1606,40 @@ extern "C" int score_backward(const score_config_t* cfg, const score_state_t* st
   // (profiles/r05_cfg3_sequence.txt), instead of at the END of the launch stream's chain in front of the table's touched-row update
   // (125 us there beside the look-ahead catch-up; 65 us alone).  The join recorded behind them is the one the launch stream waits
   // for behind the scatter (below), so whatever the caller queues next on the launch stream is also behind their last read of the
-  // workspace.  debug_flags bit 14 (16384): the round-5 placement (A/B).  The sharded path keeps that placement too: its caller
-  // runs the gradient exchange on streams of its own beside the scatter (score_amd/dist.py).
-  ReduceGroup rg;
-  rg.n = rg.blocks = 0;
-  const bool products_early = side != nullptr && st->scatter_mode != 2 && !(st->debug_flags & 16384) && gq.n > 0;
+  // workspace.  Flags.products_late (debug_flags bit 14): the round-5 placement (A/B).  The sharded path keeps that placement too:
+  // its caller runs the gradient exchange on streams of its own beside the scatter (score_amd/dist.py).
+  ReduceGroup rg; rg.n = rg.blocks = 0;
+  const bool products_early = st->scatter_mode != 2 && !fl.products_late && gq.n > 0;
   // ... and with them the finishers of the dense gradient (slab reduce, column sums), when the caller takes them on the side stream
   // (score_state_t.grads_done_event): forked behind target_bwd_kernel, the last launch that feeds them, instead of behind the row
   // scatter -- they ran beside the table's touched-row update, 58 + 28 us there against 20 + 12 alone, with the dense ApplyAdam and
   // through it the next forward pass waiting for them
-  const bool fin_side = st->grads_done_event != nullptr && side != nullptr;
+  const bool fin_side = st->grads_done_event != nullptr;
   const bool fin_early = products_early && fin_side;
   // (the fork HERE, behind the input-gradient product, and not one launch later beside the waits in front of target_bwd_kernel,
   //  where it would cost the launch stream no packet of its own: 872 k vs 884 k samples/s, profiles/r06_probes.md)
   if (products_early) {
-    HIPTRY(hipEventRecord(side->fork, s));
-    HIPTRY(hipStreamWaitEvent(side->st, side->fork, 0));
-    G(gemm_queue_flush(&gq, x3 != 0, ws + w.dwslab + slab_used, w.dwslab_floats - slab_used, side->st, &rg));
+    G(fork_side(side, s));
+    G(gemm_queue_flush(&gq, x3 != 0, ws + w.dwslab + slab_half, w.dwslab_floats - slab_half, side->st, &rg));
     HIPTRY(hipEventRecord(side->join, side->st));
   }
   EV(3);
   const bool atomic = st->scatter_mode == 1;
-  float* pw_ = (st->plan_workspace && st->scatter_mode == 0) ? st->plan_workspace : ws;      // (see score_state_t.plan_workspace)
-  uint32_t* keys_out = reinterpret_cast<uint32_t*>(pw_ + w.keys_out);
-  uint32_t* vals_out = reinterpret_cast<uint32_t*>(pw_ + w.vals_out);
   {
     CoattnArgs ca;
-    memset(&ca, 0, sizeof(ca));
-    ca.table = st->table; ca.gtable = grad_table; ca.K = d.K; ca.T = T; ca.Tidx = d.T; ca.mode = d.coattn ? 0 : 1;
-    ca.n_rows = (uint32_t)(st->n_table_rows < 0x80000000ll ? st->n_table_rows : 0x80000000ll);
-    const int ldi = 4 * d.K;
-    CoattnCall& c0 = ca.c[0];
-    c0.idx1 = bt->user_1hop; c0.idx2 = bt->item_2hop; c0.W = d.coattn ? W + P.ca_w[0] : nullptr;
-    c0.rsave = ws + w.rsave[0]; c0.g1 = ws + w.dxside[0]; c0.ld1 = d.I; c0.g2 = ws + w.dxside[1] + d.Du;
-    c0.ld2 = d.I; c0.ginfo = ws + w.dinfo; c0.ldi = ldi; c0.dzsum = ws + w.dzsum[0]; c0.F = d.Fi;
-    c0.pcoef = ws + w.pcoef[0]; c0.dzcoef = ws + w.dzcoef[0];
-    CoattnCall& c1 = ca.c[1];
-    c1.idx1 = bt->user_2hop; c1.idx2 = bt->item_1hop; c1.W = d.coattn ? W + P.ca_w[1] : nullptr;
-    c1.rsave = ws + w.rsave[1]; c1.g1 = ws + w.dxside[0] + d.Di; c1.ld1 = d.I; c1.g2 = ws + w.dxside[1];
-    c1.ld2 = d.I; c1.ginfo = ws + w.dinfo + 2 * d.K; c1.ldi = ldi; c1.dzsum = ws + w.dzsum[1]; c1.F = d.Fu;
-    c1.pcoef = ws + w.pcoef[1]; c1.dzcoef = ws + w.dzcoef[1];
+    CoattnCols k;
+    coattn_args(c, &ca, &k);
+    ca.gtable = grad_table;
+    for (int i = 0; i < 2; ++i) {
+      CoattnCall& cc = ca.c[i];
+      cc.g1 = ws + w.dxside[0] + k.col1[i]; cc.g2 = ws + w.dxside[1] + k.col2[i]; cc.ginfo = ws + w.dinfo + k.info_col[i];
+      cc.dzsum = ws + w.dzsum[i]; cc.pcoef = ws + w.pcoef[i]; cc.dzcoef = ws + w.dzcoef[i];
+    }
     float* dWs[2] = {d.coattn ? gw + P.ca_w[0] : nullptr, d.coattn ? gw + P.ca_w[1] : nullptr};
     if (atomic || d.coattn)   // RCA in pull mode has nothing to prepare: every row gradient is G itself
       G(score_coattn_bwd_multi(ca, 2, d.D, B, dWs, ws + w.ca_slab, w.ca_slab_floats, atomic ? 1 : 0, &cq, s));
   }
-  if (side && d.attn && st->scatter_mode != 2) HIPTRY(hipStreamWaitEvent(s, side->wx, 0));     // d query comes from the side stream
+  if (d.attn && st->scatter_mode != 2) HIPTRY(hipStreamWaitEvent(s, side->wx, 0));     // d query comes from the side stream
   // (the occurrence sort's event, which the row scatter below needs: waited for HERE, next to the wait above -- every wait or record
   //  between two launches costs the launch stream a bubble of ~6 us, two adjacent ones cost one)
   if (!atomic && st->plan_done_event) HIPTRY(hipStreamWaitEvent(s, (hipEvent_t)st->plan_done_event, 0));
@@ -1636,53 +1653,31 @@ extern "C" int score_backward(const score_config_t* cfg, const score_state_t* st
                             d.coattn ? gw + P.ca_b[0] : nullptr, d.coattn ? gw + P.ca_w[1] : nullptr,
                             d.coattn ? gw + P.ca_b[1] : nullptr, atomic ? nullptr : ws + w.dtgt, scratch, SF, &cq, &gq,
                             s, st->n_table_rows));
+  float* cs_part2 = ws + w.cs_part + w.cs_part_floats / 2;      // the column sums' second half: the first was flushed beside the GRUs
+  const int64_t cs_part2_floats = w.cs_part_floats - w.cs_part_floats / 2;
   if (fin_early) {
-    HIPTRY(hipEventRecord(side->fork, s));
-    HIPTRY(hipStreamWaitEvent(side->st, side->fork, 0));
-    G(score_launch_finish(&rg, &cq, ws + w.cs_part + w.cs_part_floats / 2, w.cs_part_floats - w.cs_part_floats / 2, side->st, 0));
+    G(fork_side(side, s));
+    G(score_launch_finish(&rg, &cq, cs_part2, cs_part2_floats, side->st, 0));
     HIPTRY(hipEventRecord((hipEvent_t)st->grads_done_event, side->st));
     HIPTRY(hipEventRecord(side->join, side->st));      // (what the launch stream waits for behind the scatter, below)
   }
-  if (!atomic) {
-    PullArgs pa;
-    memset(&pa, 0, sizeof(pa));
-    pa.D = d.D; pa.K = d.K; pa.zero_is_dummy = 1;
-    pa.flags = st->scatter_mode == 0 ? st->row_flags : nullptr;
-    pa.uid = st->scatter_mode == 2 ? reinterpret_cast<const uint32_t*>(ws + w.uid) : nullptr;
-    const float invK = 1.0f / (float)d.K;
-    const float* Gm[6] = {ws + w.dxside[0], ws + w.dxside[1], ws + w.dxside[0], ws + w.dxside[1], ws + w.dtgt,
-                          ws + w.dtgt};
-    const int ldg[6] = {d.I, d.I, d.I, d.I, d.Dq, d.Dq};
-    const int gcol[6] = {0, d.Du, d.Di, 0, 0, d.Du};
-    for (int g = 0; g < 6; ++g) { pa.G[g] = Gm[g]; pa.ldg[g] = ldg[g]; pa.gcol[g] = gcol[g]; pa.constA[g] = 1.0f; }
-    if (d.coattn) {
-      pa.cA[0] = ws + w.pcoef[0]; pa.cA[2] = ws + w.pcoef[1];
-      pa.constA[1] = invK; pa.constA[3] = invK;
-      pa.cB[0] = pa.cB[1] = ws + w.dzcoef[0]; pa.cB[2] = pa.cB[3] = ws + w.dzcoef[1];
-      pa.Wv[0] = W + P.ca_w[0] + d.Di; pa.Wv[1] = W + P.ca_w[0] + 2 * d.Di;
-      pa.Wv[2] = W + P.ca_w[1] + d.Du; pa.Wv[3] = W + P.ca_w[1] + 2 * d.Du;
-    }
-    const int64_t n_occ = (int64_t)B * (2 * (int64_t)T * d.K * (d.Fu + d.Fi) + d.Fu + d.Fi);   // what score_index_plan enumerated
-    G(score_launch_pull(pa, keys_out, vals_out, n_occ + 1, grad_table, ws + w.partials, w.partial_floats, s));
-  }
+  // the plan: in score_state_t.plan_workspace under scatter_mode 0, as the header defines the field
+  if (!atomic) G(row_scatter(c, (st->plan_workspace && st->scatter_mode == 0) ? st->plan_workspace : ws, grad_table));
   EV(4);
   // the remaining weight-gradient products of the pass, then the gradients assembled from them
-  if (side) HIPTRY(hipStreamWaitEvent(s, side->join, 0));
+  HIPTRY(hipStreamWaitEvent(s, side->join, 0));
   // The finishers of the dense gradient -- the split-K slab reduce and the column sums: TWO small launches behind the products
   // (score_launch_finish; four dependent ones before round 4, the folded attention layer's gradient among them -- that one now
   // follows the side stream's products, above) -- have ONE consumer, the dense variables' ApplyAdam.  A caller that passes
   // score_state_t.grads_done_event gets them on the side stream (idle by now: the launch stream has just waited for its join)
   // behind the products, and the event recorded behind them: it may run the table's touched-row update, which needs the row
   // gradients only, on the launch stream meanwhile, and waits for the event before anything reads grad_w.
-  hipStream_t fs = fin_side ? side->st : s;
-  if (!products_early) G(gemm_queue_flush(&gq, x3 != 0, ws + w.dwslab + slab_used, w.dwslab_floats - slab_used, s, &rg));
+  if (!products_early) G(gemm_queue_flush(&gq, x3 != 0, ws + w.dwslab + slab_half, w.dwslab_floats - slab_half, s, &rg));
   EV(5);
   if (fin_early) return 0;
-  if (fin_side) {
-    HIPTRY(hipEventRecord(side->fork, s));
-    HIPTRY(hipStreamWaitEvent(fs, side->fork, 0));
-  }
-  G(score_launch_finish(&rg, &cq, ws + w.cs_part + w.cs_part_floats / 2, w.cs_part_floats - w.cs_part_floats / 2, fs, 0));
+  if (fin_side) G(fork_side(side, s));
+  hipStream_t fs = fin_side ? side->st : s;
+  G(score_launch_finish(&rg, &cq, cs_part2, cs_part2_floats, fs, 0));
   if (fin_side) HIPTRY(hipEventRecord((hipEvent_t)st->grads_done_event, fs));
   return 0;
 }
