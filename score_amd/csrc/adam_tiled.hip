@@ -45,8 +45,6 @@ __device__ __forceinline__ uint32_t tiled_row_step(const TiledArgs& a, int64_t r
   return __hip_atomic_load(&a.step[row], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 
-__device__ __forceinline__ int tiled_lane() { return (int)__builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u)); }
-
 // Sub-group `sg` of the wave takes the sg-th set bit of `mask` (a lane index), and the first `nper` set bits
 // leave the mask.  `mask` is wave-uniform, so is the loop.
 __device__ __forceinline__ int tiled_pick(uint64_t& mask, int sg, int nper) {
@@ -172,7 +170,7 @@ __device__ __forceinline__ uint32_t tiled_applied(const TiledArgs& a, uint32_t s
 // `drop` (score_adam_unmark) or a set guard word: nothing is applied (tiled_unmark_row).  Virtual block blk of nblk.
 template <int SCAN_V>
 __device__ __forceinline__ void adam_touched_body(const TiledArgs& a, uint32_t step, float alpha, int drop, int blk, int nblk) {
-  const int lane = tiled_lane();
+  const int lane = lane_id();
   const int64_t stride = (int64_t)nblk * blockDim.x;
   if (drop || tiled_guarded(a)) {
     const uint32_t applied = drop ? step - 1 : tiled_applied(a, step);
@@ -271,7 +269,7 @@ __global__ __launch_bounds__(256) void adam_touched_rows_kernel(const TiledArgs 
 __global__ __launch_bounds__(256) void adam_catchup_rows_kernel(const TiledArgs a, int64_t row_begin, int64_t row_end,
                                                                 uint32_t upto) {
   if (tiled_guarded(a)) return;
-  const int lane = tiled_lane();
+  const int lane = lane_id();
   const float areg = a.ring[(upto - (uint32_t)lane) % SCORE_ADAM_RING];
   const int64_t stride = (int64_t)gridDim.x * blockDim.x;
   for (int64_t base = row_begin + ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) - lane; base < row_end; base += stride) {
@@ -318,7 +316,7 @@ __global__ __launch_bounds__(256) void adam_catchup_marked_kernel(const TiledArg
       if (a.flags[r] == 3) a.flags[r] = 1;
     return;
   }
-  const int lane = tiled_lane();
+  const int lane = lane_id();
   const float areg = a.ring[(upto - (uint32_t)lane) % SCORE_ADAM_RING];
   const int64_t stride = (int64_t)gridDim.x * blockDim.x;
   for (int64_t base = (((int64_t)blockIdx.x * blockDim.x + threadIdx.x) - lane) * SCAN_V; base < a.n_rows; base += stride * SCAN_V) {

@@ -44,7 +44,28 @@ __device__ __forceinline__ float4 ld4_global(const float* p) {
   const score_v4f v = *(const __attribute__((address_space(1))) score_v4f*)p;
   return make_float4(v.x, v.y, v.z, v.w);
 }
-__device__ __forceinline__ float ld1_global(const float* p) { return *(const __attribute__((address_space(1))) float*)p; }
+typedef __attribute__((address_space(1))) float gfloat;     // (an integer cast back to a plain pointer would be a flat access)
+__device__ __forceinline__ float ld1_global(const float* p) { return *(const gfloat*)p; }
+// base + a uniform byte offset as a 64-bit address pinned in scalar registers (readfirstlane): the saddr of a global
+// access whose per-lane part is a 32-bit offset
+__device__ __forceinline__ uint64_t uni_addr(const void* base, int64_t uni) {
+  const uint64_t p = reinterpret_cast<uint64_t>(base) + (uint64_t)uni;
+  const uint32_t lo = __builtin_amdgcn_readfirstlane((uint32_t)p), hi = __builtin_amdgcn_readfirstlane((uint32_t)(p >> 32));
+  return ((uint64_t)hi << 32) | lo;
+}
+__device__ __forceinline__ int lane_id() { return (int)__builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u)); }
+// row inside a 32x32 MFMA tile of accumulator element r of a lane of half kh = lane >> 5 (the column is lane & 31)
+#define ACC32_ROW(r, kh) (((r) & 3) + 8 * ((r) >> 2) + 4 * (kh))
+// bf16x3: the exact 3-way split of an fp32 value (truncation): the three bf16 bit patterns sit in the upper halves of h, m, l
+__device__ __forceinline__ void split3(float x, uint32_t& h, uint32_t& m, uint32_t& l) {
+  const uint32_t xb = __float_as_uint(x);
+  h = xb & 0xFFFF0000u;
+  const float r1 = x - __uint_as_float(h);
+  m = __float_as_uint(r1) & 0xFFFF0000u;
+  l = __float_as_uint(r1 - __uint_as_float(m));       // (pack2 keeps the upper half only)
+}
+// pack the upper halves of two fp32 words (= two bf16) into one dword, first element low: one v_perm_b32
+__device__ __forceinline__ uint32_t pack2(uint32_t a, uint32_t b) { return __builtin_amdgcn_perm(b, a, 0x07060302u); }
 __device__ __forceinline__ float dot4(float4 a, float4 b) {
   return fmaf(a.w, b.w, fmaf(a.z, b.z, fmaf(a.y, b.y, a.x * b.x)));
 }
@@ -149,7 +170,7 @@ __device__ __forceinline__ void group_sum_n(float (&v)[N], int gs) {
     for (int n = 0; n < N; ++n) v[n] += dpp_f32<0x140>(v[n]);    // row_mirror: lane i <-> 15 - i
   }
   if (gs >= 32) {
-    const int lane = (int)__builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u));
+    const int lane = lane_id();
     const int a16 = (lane ^ 16) << 2, a32 = (lane ^ 32) << 2;
     float t[N];
 #pragma unroll

@@ -14,7 +14,6 @@
 
 namespace {
 
-enum { GF_BIAS = 1, GF_RELU = 2, GF_ACC = 4, GF_DROP = 8, GF_X3 = 16, GF_RELUGRAD = 64 };
 const int FC1 = 200, FC2 = 80, AT1 = 80, AT2 = 40;
 
 struct Dims {

@@ -11,6 +11,7 @@
 // backward pass row j by lane j.  Every sum runs in a fixed order: the results are the same bits on every run.
 #include "common.h"
 #include "kernels.h"
+#include "cell.h"
 
 #define GCMC_NT 256
 #define GCMC_PER 8        // samples per thread
@@ -74,7 +75,7 @@ __global__ __launch_bounds__(GCMC_NT) void gcmc_head_fwd_kernel(int B, int H, co
       const float lab = (float)label[b];
       const float eps = 1e-7f;
       y[b] = pr;
-      lossb[b] = -lab * logf(pr + eps) - (1.0f - lab) * logf(1.0f - pr + eps);
+      lossb[b] = logloss_term(pr, lab);
       const float dp = (-lab / (pr + eps) + (1.0f - lab) / (1.0f - pr + eps)) * inv_bglobal;
       g_out[b] = dp * pr * (1.0f - pr);
     }

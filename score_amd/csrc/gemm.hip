@@ -17,30 +17,7 @@ typedef float f32x16 __attribute__((ext_vector_type(16)));
 #define GEMM_SPLITK_MIN_CHUNK 128   // ... and never into chunks shorter than this (tools/gemm_small_ab.py)
 #endif
 
-enum { F_BIAS = 1, F_RELU = 2, F_ACC = 4, F_DROP = 8, F_X3 = 16, F_X3F = 32, F_RELUGRAD = 64 };
 #define KF_MASK (15 | 64 | 0x7FFF0000)   // what the kernels see: epilogue bits + the bias row group
-
-// bias element of (row, col): one bias row, or one per group of g = flags >> 16 output rows
-__device__ __forceinline__ int64_t bias_index(int flags, int row, int col, int N) {
-  const int g = flags >> 16;
-  return g ? (int64_t)(row / g) * N + col : col;
-}
-
-__device__ __forceinline__ float epilogue(float v, int row, int col, int N, const float* bias, int flags,
-                                          float keep, const uint8_t* mask, uint64_t seed) {
-  if (flags & F_BIAS) v += bias[bias_index(flags, row, col, N)];
-  if (flags & F_RELU) v = fmaxf(v, 0.f);
-  if (flags & F_DROP) {
-    uint64_t e = (uint64_t)row * (uint64_t)N + (uint64_t)col;
-    bool on = mask ? (mask[e] != 0) : (hash_uniform(seed, e) < keep);
-    v = on ? v / keep : 0.f;  // tf.nn.dropout: x / keep_prob * binary mask
-  }
-  if (flags & F_RELUGRAD) {   // backward of relu (+dropout): `mask` carries the layer's fp32 output Y [M,N]
-    const float y = reinterpret_cast<const float*>(mask)[(int64_t)row * N + col];
-    v = y > 0.f ? v / keep : 0.f;
-  }
-  return v;
-}
 
 // TRANS 0: A[M,K] (lda) , B[K,N] (ldb)
 // TRANS 1: A[M,K] (lda) , B[N,K] (ldb)  -> C = A . B^T
@@ -187,9 +164,9 @@ __device__ __forceinline__ void gemm_f32_body(const GemmGroup& grp, int blk, con
         if (slab) {
           slab[((int64_t)bz * M + row) * N + col] = acc[i][j][r];
         } else {
-          float v = epilogue(acc[i][j][r], row, col, N, pr.bias ? pr.bias : bias, flags, keep, mask, seed);
+          float v = gemm_epilogue(acc[i][j][r], row, col, N, pr.bias ? pr.bias : bias, flags, keep, mask, seed);
           float* dst = C + (int64_t)row * ldc + col;
-          *dst = (flags & F_ACC) ? *dst + v : v;
+          *dst = (flags & GF_ACC) ? *dst + v : v;
         }
       }
     }
@@ -217,9 +194,9 @@ __global__ void splitk_reduce_kernel(const float* __restrict__ slab, int nsplit,
     for (int q = 0; q < 8; ++q) s += v[q];
   }
   for (; z < nsplit; ++z) s += slab[(int64_t)z * stride + i];
-  float v = epilogue(s, row, col, N, bias, flags, keep, mask, seed);
+  float v = gemm_epilogue(s, row, col, N, bias, flags, keep, mask, seed);
   float* dst = C + (int64_t)row * ldc + col;
-  *dst = (flags & F_ACC) ? *dst + v : v;
+  *dst = (flags & GF_ACC) ? *dst + v : v;
 }
 
 // every split-K slab set of a flushed queue in one launch: C = sum_z slab[z]  (slab order)
@@ -257,9 +234,9 @@ extern "C" int score_gemm(int32_t trans, int32_t M, int32_t N, int32_t K, const 
                           float* scratch, int64_t scratch_floats, void* stream) {
   if (!A || !Bm || !C || M <= 0 || N <= 0 || K <= 0) return SCORE_E_BADARG;
   if (trans < 0 || trans > 2) return SCORE_E_BADARG;
-  if ((flags & F_BIAS) && !bias) return SCORE_E_BADARG;
+  if ((flags & GF_BIAS) && !bias) return SCORE_E_BADARG;
   if (flags < 0) return SCORE_E_BADARG;
-  if ((flags & F_RELUGRAD) && (!drop_mask || (flags & F_DROP))) return SCORE_E_BADARG;
+  if ((flags & GF_RELUGRAD) && (!drop_mask || (flags & GF_DROP))) return SCORE_E_BADARG;
   hipStream_t s = (hipStream_t)stream;
   // k-contiguous operands are staged with 16-B loads: need K % 4 == 0, ld % 4 == 0, 16-B aligned base
   const bool a_kc = trans != 2, b_kc = trans == 1;
@@ -273,7 +250,7 @@ extern "C" int score_gemm(int32_t trans, int32_t M, int32_t N, int32_t K, const 
                         (trans == 1 && M >= 4096 && N >= 256) ||
                         (trans == 2 && (int64_t)M * N >= 32768 && K >= 4096);
   const bool x3_force = (flags & 32) != 0;     // tests: take the bf16x3 kernel whenever it is legal
-  if ((flags & (F_X3 | 32)) && x3_ok && M >= 64 && N >= 32 && K >= 32 && (x3_shape || x3_force)) {
+  if ((flags & (GF_X3 | 32)) && x3_ok && M >= 64 && N >= 32 && K >= 32 && (x3_shape || x3_force)) {
     // fp32-accurate product on the bf16 matrix cores (gemm_bf16x3.hip): (64*wm) x 128 x 32 tiles.
     // Pick the tile height by how many tiles the busiest CU gets (co-resident blocks share its matrix
     // pipe, so what counts is tiles per CU, not per residency slot); a 64-row tile costs ~57 % of a
@@ -375,8 +352,8 @@ extern "C" int score_gemm(int32_t trans, int32_t M, int32_t N, int32_t K, const 
 int score_gemm_same_shape(int trans, int nprob, int M, int N, int K, const float* const* A, int lda,
                           const float* const* B, int ldb, float* const* C, int ldc, int flags, int x3, float* scratch,
                           int64_t scratch_floats, hipStream_t s, const float* const* bias) {
-  if (nprob <= 0 || nprob > GEMM_GROUP_MAX || trans < 0 || trans > 2 || (flags & ~(F_ACC | F_BIAS))) return SCORE_E_BADARG;
-  if ((flags & F_BIAS) && !bias) return SCORE_E_BADARG;
+  if (nprob <= 0 || nprob > GEMM_GROUP_MAX || trans < 0 || trans > 2 || (flags & ~(GF_ACC | GF_BIAS))) return SCORE_E_BADARG;
+  if ((flags & GF_BIAS) && !bias) return SCORE_E_BADARG;
   bool al = (lda & 3) == 0 && (ldb & 3) == 0;
   for (int i = 0; i < nprob; ++i)
     al = al && (reinterpret_cast<uintptr_t>(A[i]) & 15) == 0 && (reinterpret_cast<uintptr_t>(B[i]) & 15) == 0;
@@ -406,7 +383,7 @@ int score_gemm_same_shape(int trans, int nprob, int M, int N, int K, const float
     // (with a K too short to split the separate launches gain nothing: the small shapes' projections -- 2 x 58 tiles, K = 112
     //  at the reference's own shape -- go out together below)
     for (int i = 0; i < nprob; ++i)
-      SCORE_TRY(score_gemm(trans, M, N, K, A[i], lda, B[i], ldb, C[i], ldc, bias ? bias[i] : nullptr, flags | (x3 ? F_X3 : 0),
+      SCORE_TRY(score_gemm(trans, M, N, K, A[i], lda, B[i], ldb, C[i], ldc, bias ? bias[i] : nullptr, flags | (x3 ? GF_X3 : 0),
                            1.f, nullptr, 0, scratch, scratch_floats, s));
     return 0;
   }
@@ -747,17 +724,6 @@ int score_launch_finish(const ReduceGroup* rg, ColsumJobs* q, float* part, int64
   SCORE_CHECK_LAUNCH();
   q->n = 0;
   q->part_used = 0;
-  return 0;
-}
-
-// the first stage alone (the queue stays: score_launch_finish(..., stage1_done = 1) runs the second stage and empties it)
-int colsum_queue_stage1(const ColsumJobs* q, float* part, int64_t part_floats, hipStream_t s) {
-  if (!q || q->n == 0) return 0;
-  if (q->part_used > part_floats) return SCORE_E_WORKSPACE;
-  int gx = 1;
-  for (int i = 0; i < q->n; ++i) gx = max(gx, (q->job[i].N + q->job[i].cols - 1) / q->job[i].cols);
-  hipLaunchKernelGGL(colsum_multi_stage1, dim3(gx, COLSUM_MAX_PARTS, q->n), dim3(256), 0, s, *q, part);
-  SCORE_CHECK_LAUNCH();
   return 0;
 }
 

@@ -26,40 +26,6 @@ typedef float f32x16 __attribute__((ext_vector_type(16)));
 #define TBK 32
 #define TLD 40   // bf16 per LDS row (32 + 8 pad)
 
-enum { XF_BIAS = 1, XF_RELU = 2, XF_ACC = 4, XF_DROP = 8, XF_RELUGRAD = 64 };
-
-__device__ __forceinline__ float x3_epilogue(float v, int row, int col, int N, const float* bias, int flags,
-                                             float keep, const uint8_t* mask, uint64_t seed) {
-  if (flags & XF_BIAS) {
-    const int g = flags >> 16;   // bias row group (score_gemm)
-    v += bias[g ? (int64_t)(row / g) * N + col : col];
-  }
-  if (flags & XF_RELU) v = fmaxf(v, 0.f);
-  if (flags & XF_DROP) {
-    uint64_t e = (uint64_t)row * (uint64_t)N + (uint64_t)col;
-    bool on = mask ? (mask[e] != 0) : (hash_uniform(seed, e) < keep);
-    v = on ? v / keep : 0.f;
-  }
-  if (flags & XF_RELUGRAD) {   // backward of relu (+dropout): `mask` carries the layer's fp32 output Y [M,N]
-    const float y = reinterpret_cast<const float*>(mask)[(int64_t)row * N + col];
-    v = y > 0.f ? v / keep : 0.f;
-  }
-  return v;
-}
-
-// exact 3-way split: returns the three bf16 bit patterns (upper halves of fp32 words)
-__device__ __forceinline__ void split3(float x, uint32_t& h, uint32_t& m, uint32_t& l) {
-  uint32_t xb = __float_as_uint(x);
-  h = xb & 0xFFFF0000u;
-  float r1 = x - __uint_as_float(h);
-  uint32_t rb = __float_as_uint(r1);
-  m = rb & 0xFFFF0000u;
-  float r2 = r1 - __uint_as_float(m);
-  l = __float_as_uint(r2);       // (pack2 keeps the upper half only)
-}
-// pack the upper halves of two fp32 words (= two bf16) into one dword, first element low: one v_perm_b32
-__device__ __forceinline__ uint32_t pack2(uint32_t a, uint32_t b) { return __builtin_amdgcn_perm(b, a, 0x07060302u); }
-
 // WM = 32-row MFMA tiles per wave along M: block tile (64*WM) x 128
 template <int TRANS, int WM>
 __global__ __launch_bounds__(256, 2) void gemm_bf16x3_kernel(const GemmGroup grp, const float* __restrict__ bias, int flags,
@@ -346,7 +312,7 @@ __global__ __launch_bounds__(256, 2) void gemm_bf16x3_kernel(const GemmGroup grp
       const float* bsrc = pr.bias ? pr.bias : bias;
       const int bg = flags >> 16;
       float eb[16], ey[16], ec[16];
-      const bool has_b = !slab && (flags & XF_BIAS), has_y = !slab && (flags & XF_RELUGRAD), has_c = !slab && (flags & XF_ACC);
+      const bool has_b = !slab && (flags & GF_BIAS), has_y = !slab && (flags & GF_RELUGRAD), has_c = !slab && (flags & GF_ACC);
       int rows[16];
 #pragma unroll
       for (int r = 0; r < 16; ++r) rows[r] = min(bm + wm * 32 * WM + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * kh, M - 1);
@@ -380,8 +346,8 @@ __global__ __launch_bounds__(256, 2) void gemm_bf16x3_kernel(const GemmGroup grp
         } else {
           float v = acc[i][j][r];
           if (has_b) v += eb[r];
-          if (flags & XF_RELU) v = fmaxf(v, 0.f);
-          if (flags & XF_DROP) {
+          if (flags & GF_RELU) v = fmaxf(v, 0.f);
+          if (flags & GF_DROP) {
             const uint64_t e = (uint64_t)row * (uint64_t)N + (uint64_t)col;
             const bool on = mask ? (mask[e] != 0) : (hash_uniform(seed, e) < keep);
             v = on ? v / keep : 0.f;

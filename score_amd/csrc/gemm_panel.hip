@@ -34,20 +34,6 @@ typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
 typedef __attribute__((address_space(1))) f32x4 gfloat4;      // (an integer cast back to a plain pointer would be a flat access)
 typedef __attribute__((address_space(1))) u32x4 guint4;
 
-// exact 3-way split (truncation): the three bf16 bit patterns sit in the upper halves of h, m, l
-__device__ __forceinline__ void split3(float x, uint32_t& h, uint32_t& m, uint32_t& l) {
-  const uint32_t xb = __float_as_uint(x);
-  h = xb & 0xFFFF0000u;
-  const float r1 = x - __uint_as_float(h);
-  m = __float_as_uint(r1) & 0xFFFF0000u;
-  l = __float_as_uint(r1 - __uint_as_float(m));
-}
-__device__ __forceinline__ uint32_t pack2(uint32_t a, uint32_t b) { return __builtin_amdgcn_perm(b, a, 0x07060302u); }
-__device__ __forceinline__ uint64_t uni64(const void* p_) {      // a uniform pointer pinned in scalar registers
-  const uint64_t p = reinterpret_cast<uint64_t>(p_);
-  const uint32_t lo = __builtin_amdgcn_readfirstlane((uint32_t)p), hi = __builtin_amdgcn_readfirstlane((uint32_t)(p >> 32));
-  return ((uint64_t)hi << 32) | lo;
-}
 // 64-B LDS rows of four 16-B chunks: chunk ^= {0,3,2,1}[(row >> 2) & 3] -- conflict-free for the 16-lane groups of
 // ds_read_b128 ({0-3,12-15,20-27}, ...) on the 16x16x32 fragment (lane l: row l % 16, chunk l / 16) and for ds_write_b64
 __device__ __forceinline__ int swz(int row) { return (0x6C >> (((row >> 2) & 3) * 2)) & 3; }
@@ -105,7 +91,7 @@ __global__ __launch_bounds__(512, 1) void gemm_panel_kernel(const PanelArgs a) {
 #pragma unroll
   for (int i = 0; i < NRD; ++i) asrc[i] = (uint32_t)((min(arow + 64 * i, rows_here - 1) * a.lda + aj * 4) * 4);
   const uint32_t adst = (uint32_t)(arow * 64 + (((aj >> 1) ^ swz(arow)) * 16) + (aj & 1) * 8);
-  const uint64_t abase = uni64(G.A + (int64_t)bm * a.lda);
+  const uint64_t abase = uni_addr(G.A + (int64_t)bm * a.lda, 0);
   f32x4 areg[NRD];
   auto a_load = [&](int t) {
     const uint64_t b = abase + (uint64_t)t * 128;
@@ -138,7 +124,7 @@ __global__ __launch_bounds__(512, 1) void gemm_panel_kernel(const PanelArgs a) {
   // this wave's weight fragments: uniform base per (k-tile, n-block, plane) + lane * 16.  (A wave past the last column
   // multiplies the image's zero padding: the same instruction stream for every wave)
   const int jb0 = wave * NBW;
-  const uint64_t bbase = uni64(G.img) + (uint64_t)jb0 * 3 * 1024;
+  const uint64_t bbase = uni_addr(G.img, 0) + (uint64_t)jb0 * 3 * 1024;
   const uint64_t bstep = (uint64_t)a.NB * 3 * 1024;       // bytes per k-tile
   const uint32_t boff = (uint32_t)lane * 16;
   bf16x8 bf[NBW][3];
@@ -231,7 +217,7 @@ __global__ __launch_bounds__(512, 1) void gemm_panel_kernel(const PanelArgs a) {
 #pragma unroll
   for (int n = 0; n < NBW; ++n) {
     bias[n] = f32x4{0.f, 0.f, 0.f, 0.f};
-    if (BIAS) bias[n] = *(const gfloat4*)(uni64(G.bias) + (uint64_t)(min((jb0 + n) * 16, a.N - 16) + 4 * lq) * 4);
+    if (BIAS) bias[n] = *(const gfloat4*)(uni_addr(G.bias, 0) + (uint64_t)(min((jb0 + n) * 16, a.N - 16) + 4 * lq) * 4);
   }
   constexpr int RND = NCOL / 128;                             // float4 per row / 32 lanes
   const int srow = tid >> 5, sc4 = tid & 31;                  // this thread's row of the m-block and first float4 of it
@@ -239,7 +225,7 @@ __global__ __launch_bounds__(512, 1) void gemm_panel_kernel(const PanelArgs a) {
   uint32_t scol[RND];                                         //  lanes there store the last real one again)
 #pragma unroll
   for (int i = 0; i < RND; ++i) scol[i] = (uint32_t)min(sc4 + 32 * i, nq - 1) * 4;
-  const uint64_t cbase = uni64(G.C + (int64_t)bm * a.ldc);
+  const uint64_t cbase = uni_addr(G.C + (int64_t)bm * a.ldc, 0);
   const uint32_t wofs = (uint32_t)(lc * CS + jb0 * 16 + 4 * lq);
   __syncthreads();                                            // every wave is done with the stages
 #pragma unroll

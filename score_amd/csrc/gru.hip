@@ -8,6 +8,7 @@
 // h' = u*h + (1-u)*c.  The x-part (x.Wx + b) is hoisted into one big GEMM: `xproj`.
 #include "common.h"
 #include "kernels.h"
+#include "cell.h"
 
 #include <string.h>
 typedef float f32x16 __attribute__((ext_vector_type(16)));
@@ -46,8 +47,7 @@ __device__ __forceinline__ f32x16 tile_matmul(const float* __restrict__ Ash, int
   }
   return acc;
 }
-// accumulator element r of lane -> (row, col) inside the 32x32 tile
-#define ACC_ROW(r, lane) (((r) & 3) + 8 * ((r) >> 2) + 4 * ((lane) >> 5))
+// accumulator element r of lane -> (row ACC32_ROW(r, lane >> 5), col) inside the 32x32 tile
 #define ACC_COL(lane) ((lane) & 31)
 
 __global__ __launch_bounds__(256) void gru_fwd_kernel(int B, int T, int H, const float* __restrict__ xproj,
@@ -74,7 +74,7 @@ __global__ __launch_bounds__(256) void gru_fwd_kernel(int B, int T, int H, const
       if (j < 2 * H) {
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
-          const int i = ACC_ROW(r, lane);
+          const int i = ACC32_ROW(r, lane >> 5);
           const int b = b0 + i;
           if (b >= B) continue;
           const int64_t row = (int64_t)b * T + t;
@@ -93,14 +93,14 @@ __global__ __launch_bounds__(256) void gru_fwd_kernel(int B, int T, int H, const
       if (j < H) {
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
-          const int i = ACC_ROW(r, lane);
+          const int i = ACC32_ROW(r, lane >> 5);
           const int b = b0 + i;
           if (b >= B) continue;
           const int64_t row = (int64_t)b * T + t;
           float c = tanhf(acc[r] + xproj[row * 3 * H + 2 * H + j]);
           gates[row * 3 * H + 2 * H + j] = c;
           float u = us[i * ld + j], h = hs[i * ld + j];
-          float hn = u * h + (1.0f - u) * c;
+          float hn = gru_blend(u, h, c);
           bool live = t < length[b];
           out[row * ldo + j] = live ? hn : 0.f;   // dynamic_rnn: zero output past the length
           hs[i * ld + j] = live ? hn : h;         // ... and the state is carried through
@@ -181,9 +181,9 @@ __global__ __launch_bounds__(256) void gru_bwd_kernel(int B, int T, int H, const
         if (live) {
           float u = gates[row * 3 * H + H + j], c = gates[row * 3 * H + 2 * H + j];
           float d = dh[i * ld + j] + dout[row * lddo + j];
-          float du = d * (hp - c), dc = d * (1.0f - u);
-          v_dpu = du * u * (1.0f - u);
-          v_dpc = dc * (1.0f - c * c);
+          const float dc = gru_dc(d, u), du = gru_du(d, hp, c);
+          v_dpu = gru_dpu(du, u, true);
+          v_dpc = gru_dpc(dc, c, true);
           dh[i * ld + j] = d * u;
         }
         dxproj[row * 3 * H + H + j] = v_dpu;
@@ -200,7 +200,7 @@ __global__ __launch_bounds__(256) void gru_bwd_kernel(int B, int T, int H, const
       if (j < H) {
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
-          const int i = ACC_ROW(r, lane);
+          const int i = ACC32_ROW(r, lane >> 5);
           const int b = b0 + i;
           float v_dpr = 0.f;
           if (b < B) {
@@ -211,7 +211,7 @@ __global__ __launch_bounds__(256) void gru_bwd_kernel(int B, int T, int H, const
               rr = gates[row * 3 * H + j];
               hp = t > 0 ? out[(row - 1) * ldo + j] : 0.f;
               float drh = acc[r];
-              v_dpr = drh * hp * rr * (1.0f - rr);
+              v_dpr = gru_dpr(drh, hp, rr, true);
               dh[i * ld + j] += drh * rr;
             }
             dxproj[row * 3 * H + j] = v_dpr;
@@ -229,7 +229,7 @@ __global__ __launch_bounds__(256) void gru_bwd_kernel(int B, int T, int H, const
       if (j < H) {
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
-          const int i = ACC_ROW(r, lane);
+          const int i = ACC32_ROW(r, lane >> 5);
           dh[i * ld + j] += acc[r];
         }
       }
@@ -306,11 +306,6 @@ typedef float f32x4 __attribute__((ext_vector_type(4)));
 #else
 #define GR_XLOAD(e) (e)
 #endif
-// fast transcendental forms for the recurrence epilogues (v_exp_f32 / v_rcp_f32; abs error ~1e-7; __frcp_rn would be
-// the ten-instruction correctly rounded division)
-__device__ __forceinline__ float sigmoid_fast(float x) { return __builtin_amdgcn_rcpf(1.0f + __expf(-x)); }
-__device__ __forceinline__ float tanh_fast(float x) { return 1.0f - 2.0f * __builtin_amdgcn_rcpf(__expf(2.0f * x) + 1.0f); }
-
 
 // The time loops have no predicated memory operation at all (rows past the batch duplicate the last sample, see
 // below).  That matters beyond the saved compares: with loads and stores under exec-mask branches the compiler's
@@ -414,7 +409,7 @@ __global__ __launch_bounds__(64 * NW) void gru_fwd_reg_kernel(const GruArgs a) {
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
         const int i = lq * 4 + r;
-        const float g = sigmoid_fast(acc[tt][r] + xg[tt][r]);
+        const float g = gru_sigmoid(acc[tt][r] + xg[tt][r]);
         if (rok[r]) GR_STORE(sd.gates[(rowb[r] + t) * 3 * H + j], g);
         if (j < H) rhs[i * LD + j] = g * hs[i * LD + j];
         else us[i * LD + (j - H)] = g;
@@ -447,9 +442,9 @@ __global__ __launch_bounds__(64 * NW) void gru_fwd_reg_kernel(const GruArgs a) {
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
         const int i = lq * 4 + r;
-        const float c = tanh_fast(acc2[tt][r] + xc[tt][r]);
+        const float c = gru_tanh(acc2[tt][r] + xc[tt][r]);
         const float u = us[i * LD + j], h = hs[i * LD + j];
-        const float hn = u * h + (1.0f - u) * c;
+        const float hn = gru_blend(u, h, c);
         const bool live = t < len[r];
         if (rok[r]) {
           const int64_t row = rowb[r] + t;
@@ -582,9 +577,9 @@ __global__ __launch_bounds__(64 * NW) void gru_bwd_reg_kernel(const GruArgs a) {
         const float u = n_u[tt][r], c = n_c[tt][r];      // (a dead step's results are discarded by `live`)
         const float dold = dh[i * LD + j];
         const float d = dold + n_do[tt][r];
-        const float du = d * (c_hp[tt][r] - c), dc = d * (1.0f - u);
-        const float v_dpu = live ? du * u * (1.0f - u) : 0.f;
-        const float v_dpc = live ? dc * (1.0f - c * c) : 0.f;
+        const float dc = gru_dc(d, u), du = gru_du(d, c_hp[tt][r], c);
+        const float v_dpu = gru_dpu(du, u, live);
+        const float v_dpc = gru_dpc(dc, c, live);
         dh[i * LD + j] = live ? d * u : dold;
         if (rok[r]) {
           const int64_t row = rowb[r] + t;
@@ -625,7 +620,7 @@ __global__ __launch_bounds__(64 * NW) void gru_bwd_reg_kernel(const GruArgs a) {
           const bool live = t < len[r];
           const float rr = live ? n_r[tt][r] : 0.f, hp = c_hp[tt][r];   // both 0 past the length
           const float drh = acc[tt][r];
-          const float v_dpr = live ? drh * hp * rr * (1.0f - rr) : 0.f;
+          const float v_dpr = gru_dpr(drh, hp, rr, live);
           dh[i * LD + j] += live ? drh * rr : 0.f;
           if (rok[r]) {
             const int64_t row = rowb[r] + t;
@@ -703,7 +698,7 @@ __global__ void gru_step_out_kernel(const GruStepArgs a, int first) {
   const float c = tanhf(pre + sd.xproj[row * 3 * a.H + 2 * a.H + j]);
   sd.gates[row * 3 * a.H + 2 * a.H + j] = c;
   const float u = sd.gates[row * 3 * a.H + a.H + j], h = first ? 0.f : sd.hstate[i];
-  const float hn = u * h + (1.0f - u) * c;
+  const float hn = gru_blend(u, h, c);
   const bool live = a.t < a.length[b];
   sd.out[row * sd.ldo + j] = live ? hn : 0.f;     // dynamic_rnn: zero output past the length
   sd.hstate[i] = live ? hn : h;                   // ... and the state is carried through
@@ -722,9 +717,9 @@ __global__ void gru_bstep_a_kernel(const GruStepArgs a) {
   if (live) {
     const float u = sd.gates[row * 3 * H + H + j], c = sd.gates[row * 3 * H + 2 * H + j];
     const float d = sd.dh[i] + sd.dout[row * sd.lddo + j];
-    const float du = d * (hp - c), dc = d * (1.0f - u);
-    v_dpu = du * u * (1.0f - u);
-    v_dpc = dc * (1.0f - c * c);
+    const float dc = gru_dc(d, u), du = gru_du(d, hp, c);
+    v_dpu = gru_dpu(du, u, true);
+    v_dpc = gru_dpc(dc, c, true);
     sd.dh[i] = d * u;
   }
   sd.dxproj[row * 3 * H + H + j] = v_dpu;
@@ -745,7 +740,7 @@ __global__ void gru_bstep_b_kernel(const GruStepArgs a) {
     rr = sd.gates[row * 3 * H + j];
     hp = t > 0 ? sd.out[(row - 1) * sd.ldo + j] : 0.f;
     const float drh = sd.drh[i];
-    v_dpr = drh * hp * rr * (1.0f - rr);
+    v_dpr = gru_dpr(drh, hp, rr, true);
     sd.dh[i] += drh * rr;
   }
   sd.dxproj[row * 3 * H + j] = v_dpr;
@@ -829,28 +824,44 @@ static int gru_bwd_steps(GruArgs& a, int nsides, hipStream_t s) {
 }
 
 static bool gru_reg_ok(int H) { return H == 16 || H == 32 || H == 64 || H == 128; }
-// (the H = 128 recurrences on the f32-input MFMA instead of the bf16x3 form: score_state_t.debug_flags bit 2 -> GruArgs.x3_rec)
-static bool gru_x3_allowed() { return true; }
+
+// Which recurrence family runs, decided once for both directions: the backward reads the buffers in the layout the forward's
+// family saved.  (The H = 128 recurrences on the f32-input MFMA instead of the bf16x3 form: score_state_t.debug_flags bit 2 ->
+// GruArgs.x3_rec = 0.)
+enum GruFamily { GRU_X3, GRU_REG, GRU_STREAM, GRU_STEPS, GRU_PER_SIDE };
+struct GruRoute { GruFamily family; int nw; };      // nw: waves per workgroup of the register kernels (the forward's)
+static GruRoute gru_route(const GruArgs& a, int nsides) {
+  const int H = a.H;
+  if (a.x3_rec && score_gru_x3_ok(H, a.nw8)) return {GRU_X3, 0};
+  if (gru_reg_ok(H)) return {GRU_REG, H == 128 && a.nw8 ? 8 : 4};
+  if (!a.stepwise && score_gru_stream_ok(H) && a.tmp && a.tmp_floats >= score_gru_stream_tmp_floats(H, nsides))
+    return {GRU_STREAM, 0};
+  if (a.tmp && a.tmp_floats >= 10 * (int64_t)a.B * H && (nsides == 1 || (a.s[0].ldwg == a.s[1].ldwg && a.s[0].ldwc == a.s[1].ldwc)))
+    return {GRU_STEPS, 0};
+  return {GRU_PER_SIDE, 0};
+}
 
 int score_gru_fwd_multi(GruArgs& a, int nsides, hipStream_t s) {
   const int H = a.H;
-  if (a.x3_rec && gru_x3_allowed() && score_gru_x3_ok(H, a.nw8)) return score_gru_fwd_x3(a, nsides, s);
-  if (gru_reg_ok(H)) {
-    dim3 grid(nsides * ((a.B + RRB - 1) / RRB));
+  const GruRoute rt = gru_route(a, nsides);
+  switch (rt.family) {
+    case GRU_X3: return score_gru_fwd_x3(a, nsides, s);
+    case GRU_REG: {
+      dim3 grid(nsides * ((a.B + RRB - 1) / RRB));
 #define LF(Hv, NWv) hipLaunchKernelGGL((gru_fwd_reg_kernel<Hv, NWv>), grid, dim3(64 * NWv), 0, s, a)
-    if (H == 16) LF(16, 4);
-    else if (H == 32) LF(32, 4);
-    else if (H == 64) LF(64, 4);
-    else if (a.nw8) LF(128, 8);
-    else LF(128, 4);
+      if (H == 16) LF(16, 4);
+      else if (H == 32) LF(32, 4);
+      else if (H == 64) LF(64, 4);
+      else if (rt.nw == 8) LF(128, 8);
+      else LF(128, 4);
 #undef LF
-    SCORE_CHECK_LAUNCH();
-    return 0;
+      SCORE_CHECK_LAUNCH();
+      return 0;
+    }
+    case GRU_STREAM: return score_gru_fwd_stream(a, nsides, s);
+    case GRU_STEPS: return gru_fwd_steps(a, nsides, s);
+    case GRU_PER_SIDE: break;
   }
-  if (!a.stepwise && score_gru_stream_ok(H) && a.tmp && a.tmp_floats >= score_gru_stream_tmp_floats(H, nsides))
-    return score_gru_fwd_stream(a, nsides, s);
-  if (a.tmp && a.tmp_floats >= 10 * (int64_t)a.B * H && (nsides == 1 || (a.s[0].ldwg == a.s[1].ldwg && a.s[0].ldwc == a.s[1].ldwc)))
-    return gru_fwd_steps(a, nsides, s);
   for (int i = 0; i < nsides; ++i) {
     const GruSide& sd = a.s[i];
     SCORE_TRY(score_gru_fwd(a.B, a.T, H, sd.xproj, sd.Wg, sd.ldwg, sd.Wc, sd.ldwc, a.length, sd.out, sd.ldo,
@@ -861,26 +872,28 @@ int score_gru_fwd_multi(GruArgs& a, int nsides, hipStream_t s) {
 
 int score_gru_bwd_multi(GruArgs& a, int nsides, hipStream_t s) {
   const int H = a.H;
-  if (a.x3_rec && gru_x3_allowed() && score_gru_x3_ok(H, a.nw8)) return score_gru_bwd_x3(a, nsides, s);
-  if (gru_reg_ok(H)) {
-    dim3 grid(nsides * ((a.B + RRB - 1) / RRB));
+  const GruRoute rt = gru_route(a, nsides);
+  switch (rt.family) {
+    case GRU_X3: return score_gru_bwd_x3(a, nsides, s);
+    case GRU_REG: {
+      dim3 grid(nsides * ((a.B + RRB - 1) / RRB));
 #define LB(Hv, NWv) hipLaunchKernelGGL((gru_bwd_reg_kernel<Hv, NWv>), grid, dim3(64 * NWv), 0, s, a)
-    if (H == 16) LB(16, 4);
-    else if (H == 32) {     // two waves from 20 slices on: a shorter step, a longer prologue (each wave holds twice the weights) -- the CCMR
-      if (a.T >= 20) LB(32, 2);     // shape (T = 40) 0.5174 -> 0.5064 ms/step, cfg-2 (T = 10) 0.272 -> 0.278; the forward keeps four
-      else LB(32, 4);
-    }
-    else if (H == 64) LB(64, 4);
-    else if (a.nw8) LB(128, 8);
-    else LB(128, 4);
+      if (H == 16) LB(16, 4);
+      else if (H == 32) {     // two waves from 20 slices on: a shorter step, a longer prologue (each wave holds twice the weights) -- the CCMR
+        if (a.T >= 20) LB(32, 2);     // shape (T = 40) 0.5174 -> 0.5064 ms/step, cfg-2 (T = 10) 0.272 -> 0.278; the forward keeps four
+        else LB(32, 4);
+      }
+      else if (H == 64) LB(64, 4);
+      else if (rt.nw == 8) LB(128, 8);
+      else LB(128, 4);
 #undef LB
-    SCORE_CHECK_LAUNCH();
-    return 0;
+      SCORE_CHECK_LAUNCH();
+      return 0;
+    }
+    case GRU_STREAM: return score_gru_bwd_stream(a, nsides, s);
+    case GRU_STEPS: return gru_bwd_steps(a, nsides, s);
+    case GRU_PER_SIDE: break;
   }
-  if (!a.stepwise && score_gru_stream_ok(H) && a.tmp && a.tmp_floats >= score_gru_stream_tmp_floats(H, nsides))
-    return score_gru_bwd_stream(a, nsides, s);
-  if (a.tmp && a.tmp_floats >= 10 * (int64_t)a.B * H && (nsides == 1 || (a.s[0].ldwg == a.s[1].ldwg && a.s[0].ldwc == a.s[1].ldwc)))
-    return gru_bwd_steps(a, nsides, s);
   for (int i = 0; i < nsides; ++i) {
     const GruSide& sd = a.s[i];
     SCORE_TRY(score_gru_bwd(a.B, a.T, H, sd.Wg, sd.ldwg, sd.Wc, sd.ldwc, a.length, sd.out, sd.ldo, sd.gates,

@@ -15,6 +15,7 @@
 #include <string.h>
 #include "common.h"
 #include "kernels.h"
+#include "cell.h"
 
 namespace {
 
@@ -23,8 +24,6 @@ typedef float f32x4 __attribute__((ext_vector_type(4)));
 #define SNW 4       // waves per layer
 #define ST_MFMA(a, b, c) __builtin_amdgcn_mfma_f32_16x16x4f32((a), (b), (c), 0, 0, 0)
 
-__device__ __forceinline__ float st_sigmoid(float x) { return __builtin_amdgcn_rcpf(1.0f + __expf(-x)); }
-__device__ __forceinline__ float st_tanh(float x) { return 1.0f - 2.0f * __builtin_amdgcn_rcpf(__expf(2.0f * x) + 1.0f); }
 __device__ __forceinline__ float st_elem(const float4& v, int i) { return i == 0 ? v.x : i == 1 ? v.y : i == 2 ? v.z : v.w; }
 
 // acc[tt] += A[16 x KN] . w[tt]: K is dealt to the four lane quarters in contiguous runs of KN / 4 (quarter lq owns
@@ -187,7 +186,7 @@ __global__ __launch_bounds__(128 * SNW) void gru_stack_fwd_kernel(const GruStack
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
           const int i = lq * 4 + r;
-          const float g = st_sigmoid(acc[tt][r] + xg[tt][r]);
+          const float g = gru_sigmoid(acc[tt][r] + xg[tt][r]);
           sd.gates[(rowb[r] + t) * 3 * H + j] = g;
           if (j < H) rh[i * LD + j] = g * hrd[i * LD + j];
           else uu[i * LD + (j - H)] = g;
@@ -214,9 +213,9 @@ __global__ __launch_bounds__(128 * SNW) void gru_stack_fwd_kernel(const GruStack
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
           const int i = lq * 4 + r;
-          const float c = st_tanh(acc[tt][r] + xc[tt][r]);
+          const float c = gru_tanh(acc[tt][r] + xc[tt][r]);
           const float u = uu[i * LD + j], h = hrd[i * LD + j];
-          const float hn = u * h + (1.0f - u) * c;
+          const float hn = gru_blend(u, h, c);
           const bool live = t < len[r];
           const int64_t row = rowb[r] + t;
           sd.gates[row * 3 * H + 2 * H + j] = c;
@@ -359,6 +358,8 @@ __global__ __launch_bounds__(128 * SNW) void gru_stack_bwd_kernel(const GruStack
           const float dold = dh[i * LD + j];
           // dL/d out[t]: layer 1's comes from layer 2's step t (zero past the length); nothing but the final state reads layer 2's
           const float d = layer ? dold : dold + d1[i * LD + j];
+          // cell.h's gru_du / gru_dc / gru_dpu / gru_dpc, spelled out: through the helpers the compiler allocates the H = 32
+          // kernel's address registers differently, and it is kept byte for byte as it was measured
           const float du = d * (c_hp[tt][r] - c), dc = d * (1.0f - u);
           const float v_dpu = live ? du * u * (1.0f - u) : 0.f;
           const float v_dpc = live ? dc * (1.0f - c * c) : 0.f;
@@ -392,7 +393,7 @@ __global__ __launch_bounds__(128 * SNW) void gru_stack_bwd_kernel(const GruStack
           const bool live = t < len[r];
           const float rr = live ? n_r[tt][r] : 0.f, hp = c_hp[tt][r];   // both 0 past the length
           const float drh = acc[tt][r];
-          const float v_dpr = live ? drh * hp * rr * (1.0f - rr) : 0.f;
+          const float v_dpr = gru_dpr(drh, hp, rr, live);
           dh[i * LD + j] += live ? drh * rr : 0.f;
           const int64_t row = rowb[r] + t;
           sd.dxproj[row * 3 * H + j] = v_dpr;

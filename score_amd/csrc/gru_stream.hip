@@ -17,20 +17,12 @@
 // Arithmetic is that of gru.hip's kernels (exact fp32 products, v_exp/v_rcp sigmoid and tanh).
 #include "common.h"
 #include "kernels.h"
+#include "cell.h"
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 #define SMB 32                       // batch rows per workgroup
 #define SNW 8                        // waves per workgroup
-// accumulator element r of a lane -> row inside the 32x32 tile; the column is lane & 31
-#define SACC_ROWC(r) (((r) & 3) + 8 * ((r) >> 2))          // + 4 * (lane >> 5)
-
-#if defined(GSP_DIVRCP)
-#define GS_RCP(x) __frcp_rn(x)              // correctly rounded: a ten-instruction division sequence
-#else
-#define GS_RCP(x) __builtin_amdgcn_rcpf(x)  // v_rcp_f32 (1 ulp)
-#endif
-__device__ __forceinline__ float s_sigmoid(float x) { return GS_RCP(1.0f + __expf(-x)); }
-__device__ __forceinline__ float s_tanh(float x) { return 1.0f - 2.0f * GS_RCP(__expf(2.0f * x) + 1.0f); }
+// accumulator element r of a lane of half kh -> row ACC32_ROW(r, kh) inside the 32x32 tile; the column is lane & 31
 
 // out[ct][sg][lane][e] = B(k, col), k = (lane >> 5) * (K / 2) + 4 * sg + e, col = ct * 32 + (lane & 31);
 // B(k, col) = W[k * ldw + col] (trans 0: h . W) or W[col * ldw + k] (trans 1: g . W^T).
@@ -138,27 +130,21 @@ __device__ __forceinline__ void stream_matmul(f32x16 (&acc)[NT], const float* __
 // loop is an s_waitcnt vmcnt(0) that also drains the weight ring.  readfirstlane pins the uniform part.
 // Batches that are not whole 32-row tiles clamp the row (rows past the batch read the last one's, never stored):
 // the clamped offset of either lane half is uniform too, a lane selects its half's.
-typedef __attribute__((address_space(1))) float gs_gfloat;
-__device__ __forceinline__ uint64_t gs_uni(const void* base, int64_t uni) {
-  const uint64_t p = reinterpret_cast<uint64_t>(base) + (uint64_t)uni;
-  const uint32_t lo = __builtin_amdgcn_readfirstlane((uint32_t)p), hi = __builtin_amdgcn_readfirstlane((uint32_t)(p >> 32));
-  return ((uint64_t)hi << 32) | lo;
-}
 struct GsRows {            // rows of this lane's 16 accumulator elements inside its workgroup's 32
   int kh, nv, T;
   // address of (accumulator row r, time step t, column col0 + j) in an array of row stride `stride` floats
   template <bool FULL> __device__ __forceinline__ uint64_t at(const void* base, int r, int t, int stride, int col0, int j) const {
     if (FULL) {            // row and step in the uniform part; the lane part is fixed for the launch
-      return gs_uni(base, ((int64_t)(SACC_ROWC(r) * T + t) * stride + col0) * 4) + ((uint32_t)(4 * kh * T) * (uint32_t)stride + (uint32_t)j) * 4u;
+      return uni_addr(base, ((int64_t)(ACC32_ROW(r, 0) * T + t) * stride + col0) * 4) + ((uint32_t)(4 * kh * T) * (uint32_t)stride + (uint32_t)j) * 4u;
     } else {               // clamped row of either lane half as two uniform offsets, selected per lane
-      const uint32_t a0 = (uint32_t)((min(SACC_ROWC(r), nv - 1) * T + t) * stride) * 4u;
-      const uint32_t a1 = (uint32_t)((min(4 + SACC_ROWC(r), nv - 1) * T + t) * stride) * 4u;
-      return gs_uni(base, (int64_t)col0 * 4) + ((kh ? a1 : a0) + (uint32_t)j * 4u);
+      const uint32_t a0 = (uint32_t)((min(ACC32_ROW(r, 0), nv - 1) * T + t) * stride) * 4u;
+      const uint32_t a1 = (uint32_t)((min(ACC32_ROW(r, 1), nv - 1) * T + t) * stride) * 4u;
+      return uni_addr(base, (int64_t)col0 * 4) + ((kh ? a1 : a0) + (uint32_t)j * 4u);
     }
   }
 };
-#define GS_LD(addr) GS_XLOADV(*(const gs_gfloat*)(addr))
-#define GS_ST(addr, v) GS_STORE(*(gs_gfloat*)(addr), (v))
+#define GS_LD(addr) GS_XLOADV(*(const gfloat*)(addr))
+#define GS_ST(addr, v) GS_STORE(*(gfloat*)(addr), (v))
 
 // ---------------------------------------------------------------------------------------------- forward
 // frag: per side [WgF (2H*H) | WcF (H*H) | WcTF (H*H) | WgTF (2H*H)] floats, side stride 6*H*H.
@@ -187,7 +173,7 @@ __global__ __launch_bounds__(64 * SNW) void gru_fwd_stream_kernel(const GruArgs 
   const GsRows rw = {kh, min(SMB, a.B - b0), T};
   unsigned rokm = 0;
 #pragma unroll
-  for (int r = 0; r < 16; ++r) rokm |= (FULL || 4 * kh + SACC_ROWC(r) < rw.nv) ? (1u << r) : 0u;
+  for (int r = 0; r < 16; ++r) rokm |= (FULL || ACC32_ROW(r, kh) < rw.nv) ? (1u << r) : 0u;
   const int j = wave * 32 + li;                    // this lane's column of r, u, c and h
   const int ldo = sd.ldo;
   const float* xp = sd.xproj + (int64_t)b0 * T * 3 * H;
@@ -207,7 +193,7 @@ __global__ __launch_bounds__(64 * SNW) void gru_fwd_stream_kernel(const GruArgs 
   for (int t = 0; t < T; ++t) {
     unsigned livem = 0;
 #pragma unroll
-    for (int r = 0; r < 16; ++r) livem |= (t < lens[4 * kh + SACC_ROWC(r)]) ? (1u << r) : 0u;
+    for (int r = 0; r < 16; ++r) livem |= (t < lens[ACC32_ROW(r, kh)]) ? (1u << r) : 0u;
     // ---- gates = sigmoid(xproj[:, :2H] + h . Wg)
     float xg[2][16];
 #pragma unroll
@@ -224,8 +210,8 @@ __global__ __launch_bounds__(64 * SNW) void gru_fwd_stream_kernel(const GruArgs 
     stream_prologue<1, SPF1>(bqc, fc);            // the candidate product's first fragments: under this epilogue and the barrier
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
-      const int i = 4 * kh + SACC_ROWC(r);
-      const float g = s_sigmoid(acc[0][r] + xg[0][r]);
+      const int i = ACC32_ROW(r, kh);
+      const float g = gru_sigmoid(acc[0][r] + xg[0][r]);
       if (rokm & (1u << r)) GS_ST(rw.at<FULL>(gp, r, t, 3 * H, 0, j), g);
       rhs[i * LD + j] = g * h[r];
     }
@@ -238,7 +224,7 @@ __global__ __launch_bounds__(64 * SNW) void gru_fwd_stream_kernel(const GruArgs 
       xc[r] = GS_LD(rw.at<FULL>(xp, r, t, 3 * H, 2 * H, j));
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
-      u[r] = s_sigmoid(acc[1][r] + xg[1][r]);
+      u[r] = gru_sigmoid(acc[1][r] + xg[1][r]);
       if (rokm & (1u << r)) GS_ST(rw.at<FULL>(gp, r, t, 3 * H, H, j), u[r]);
     }
     f32x16 acc2[1];
@@ -248,9 +234,9 @@ __global__ __launch_bounds__(64 * SNW) void gru_fwd_stream_kernel(const GruArgs 
     stream_prologue<2, SPF2>(bqg, fg);            // the next step's gate product
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
-      const int i = 4 * kh + SACC_ROWC(r);
-      const float c = s_tanh(acc2[0][r] + xc[r]);
-      const float hn = u[r] * h[r] + (1.0f - u[r]) * c;
+      const int i = ACC32_ROW(r, kh);
+      const float c = gru_tanh(acc2[0][r] + xc[r]);
+      const float hn = gru_blend(u[r], h[r], c);
       const bool live = (livem >> r) & 1u;
       if (rokm & (1u << r)) {
         GS_ST(rw.at<FULL>(gp, r, t, 3 * H, 2 * H, j), c);
@@ -264,7 +250,7 @@ __global__ __launch_bounds__(64 * SNW) void gru_fwd_stream_kernel(const GruArgs 
   if (sd.final_state) {
 #pragma unroll
     for (int r = 0; r < 16; ++r)
-      if (rokm & (1u << r)) sd.final_state[(int64_t)(b0 + 4 * kh + SACC_ROWC(r)) * H + j] = h[r];
+      if (rokm & (1u << r)) sd.final_state[(int64_t)(b0 + ACC32_ROW(r, kh)) * H + j] = h[r];
   }
 }
 
@@ -296,7 +282,7 @@ __global__ __launch_bounds__(64 * SNW) void gru_bwd_stream_kernel(const GruArgs 
   const GsRows rw = {kh, min(SMB, a.B - b0), T};
   unsigned rokm = 0;
 #pragma unroll
-  for (int r = 0; r < 16; ++r) rokm |= (FULL || 4 * kh + SACC_ROWC(r) < rw.nv) ? (1u << r) : 0u;
+  for (int r = 0; r < 16; ++r) rokm |= (FULL || ACC32_ROW(r, kh) < rw.nv) ? (1u << r) : 0u;
   const int ldo = sd.ldo, lddo = sd.lddo;
   const float* gp = sd.gates + (int64_t)b0 * T * 3 * H;
   const float* op = sd.out + (int64_t)b0 * T * ldo;
@@ -312,7 +298,7 @@ __global__ __launch_bounds__(64 * SNW) void gru_bwd_stream_kernel(const GruArgs 
   float dh[16];
 #pragma unroll
   for (int r = 0; r < 16; ++r)
-    dh[r] = (sd.dfinal && (rokm & (1u << r))) ? sd.dfinal[(int64_t)(b0 + 4 * kh + SACC_ROWC(r)) * H + j] : 0.f;
+    dh[r] = (sd.dfinal && (rokm & (1u << r))) ? sd.dfinal[(int64_t)(b0 + ACC32_ROW(r, kh)) * H + j] : 0.f;
   float n_u[16], n_c[16], n_hp[16], n_do[16];
   auto prefetch = [&](int t) {
     const int tc = max(t, 0), tp = max(t - 1, 0);          // (h_prev of t = 0 is never used)
@@ -335,15 +321,15 @@ __global__ __launch_bounds__(64 * SNW) void gru_bwd_stream_kernel(const GruArgs 
     // ---- phase 1 (elementwise): dpu, dpc ; dh <- dh_tot * u
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
-      const int i = 4 * kh + SACC_ROWC(r);
+      const int i = ACC32_ROW(r, kh);
       const bool live = t < lens[i];
       livem |= live ? (1u << r) : 0u;
       const float u = live ? n_u[r] : 0.f, c = live ? n_c[r] : 0.f;
       c_hp[r] = (live && t > 0) ? n_hp[r] : 0.f;
       const float d = dh[r] + (live ? n_do[r] : 0.f);
-      const float du = d * (c_hp[r] - c), dc = d * (1.0f - u);
-      const float v_dpu = live ? du * u * (1.0f - u) : 0.f;
-      const float v_dpc = live ? dc * (1.0f - c * c) : 0.f;
+      const float dc = gru_dc(d, u), du = gru_du(d, c_hp[r], c);
+      const float v_dpu = gru_dpu(du, u, live);
+      const float v_dpc = gru_dpc(dc, c, live);
       dh[r] = live ? d * u : dh[r];
       if (rokm & (1u << r)) {
         GS_ST(rw.at<FULL>(hpp, r, t, H, 0, j), c_hp[r]);
@@ -366,11 +352,11 @@ __global__ __launch_bounds__(64 * SNW) void gru_bwd_stream_kernel(const GruArgs 
       stream_prologue<1, SPF1>(bqg, fg);           // phase 3's under this epilogue and the barrier
 #pragma unroll
       for (int r = 0; r < 16; ++r) {
-        const int i = 4 * kh + SACC_ROWC(r);
+        const int i = ACC32_ROW(r, kh);
         const bool live = (livem >> r) & 1u;
         const float rr = live ? c_r[r] : 0.f, hp = c_hp[r];       // both 0 past the length
         const float drh = acc[0][r];
-        const float v_dpr = live ? drh * hp * rr * (1.0f - rr) : 0.f;
+        const float v_dpr = gru_dpr(drh, hp, rr, live);
         dh[r] += live ? drh * rr : 0.f;
         if (rokm & (1u << r)) {
           GS_ST(rw.at<FULL>(dxp, r, t, 3 * H, 0, j), v_dpr);

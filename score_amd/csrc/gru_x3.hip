@@ -15,6 +15,10 @@
 #include <algorithm>
 #include "common.h"
 #include "kernels.h"
+#if defined(XGP_DIVRCP)      // tools/gru_x3_probe.py: the correctly rounded reciprocal in the epilogues
+#define SCORE_GRU_RCP(x) __frcp_rn(x)
+#endif
+#include "cell.h"
 
 namespace {
 
@@ -40,23 +44,6 @@ constexpr int XLD2 = 2 * XH + 8;      //                      a [16][2H] plane
 #else
 #define XG_LOAD(e) (e)
 #endif
-#if defined(XGP_DIVRCP)
-#define XG_RCP(x) __frcp_rn(x)              // correctly rounded: a ten-instruction division sequence
-#else
-#define XG_RCP(x) __builtin_amdgcn_rcpf(x)  // v_rcp_f32 (1 ulp)
-#endif
-__device__ __forceinline__ float x_sigmoid(float x) { return XG_RCP(1.0f + __expf(-x)); }
-__device__ __forceinline__ float x_tanh(float x) { return 1.0f - 2.0f * XG_RCP(__expf(2.0f * x) + 1.0f); }
-
-// exact 3-way split (truncation): the three bf16 bit patterns sit in the upper halves of h, m, l
-__device__ __forceinline__ void split3(float x, uint32_t& h, uint32_t& m, uint32_t& l) {
-  const uint32_t xb = __float_as_uint(x);
-  h = xb & 0xFFFF0000u;
-  const float r1 = x - __uint_as_float(h);
-  m = __float_as_uint(r1) & 0xFFFF0000u;
-  l = __float_as_uint(r1 - __uint_as_float(m));
-}
-__device__ __forceinline__ uint32_t pack2(uint32_t a, uint32_t b) { return __builtin_amdgcn_perm(b, a, 0x07060302u); }
 
 // eight consecutive-k fp32 values -> the three planes of one 16x16x32 operand fragment
 __device__ __forceinline__ void split8(const float (&x)[8], bf16x8 (&out)[3]) {
@@ -103,14 +90,8 @@ __device__ __forceinline__ f32x4 mfma6(const bf16x8 (&a)[3], const bf16x8 (&b)[3
 // fixed for the whole launch (row and column), i.e. the saddr + voffset form of global_load / global_store.  With
 // 64-bit per-lane pointers the compiler kept one induction variable per array and row alive across the time loop
 // (~70 VGPRs), spilt weight fragments to make room and reloaded them behind s_waitcnt vmcnt(0) every phase.
-// (readfirstlane pins the uniform part in scalar registers and keeps loop strength reduction from folding the
-// time step back into per-lane 64-bit induction variables)
-__device__ __forceinline__ uint64_t uni_addr(const void* base, int64_t uni) {
-  const uint64_t p = reinterpret_cast<uint64_t>(base) + (uint64_t)uni;
-  const uint32_t lo = __builtin_amdgcn_readfirstlane((uint32_t)p), hi = __builtin_amdgcn_readfirstlane((uint32_t)(p >> 32));
-  return ((uint64_t)hi << 32) | lo;
-}
-typedef __attribute__((address_space(1))) float gfloat;     // (an integer cast back to a plain pointer would be a flat access)
+// (common.h's uni_addr: readfirstlane pins the uniform part in scalar registers and keeps loop strength reduction from
+// folding the time step back into per-lane 64-bit induction variables)
 __device__ __forceinline__ float ldg(const float* base, int64_t uni, uint32_t voff) {
   return XG_LOAD(*(const gfloat*)(uni_addr(base, uni) + voff));
 }
@@ -205,7 +186,7 @@ __global__ __launch_bounds__(64 * XNW) void gru_fwd_x3_kernel(const GruArgs a) {
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
       const int i = lq * 4 + r;
-      const float rg = x_sigmoid(ar[r] + x[0][r]);
+      const float rg = gru_sigmoid(ar[r] + x[0][r]);
       if (rok[r]) XG_STORE(*stp(sd.gates, u3, rb3[r]), rg);
       put3(rp, PS, i * XLD + j, rg * h[r]);
     }
@@ -221,7 +202,7 @@ __global__ __launch_bounds__(64 * XNW) void gru_fwd_x3_kernel(const GruArgs a) {
       for (int s = 0; s < XKS; ++s) get3(rp, PS, aoff + 32 * s, af[s]);
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
-        u[r] = x_sigmoid(au[r] + x[1][r]);
+        u[r] = gru_sigmoid(au[r] + x[1][r]);
         if (rok[r]) XG_STORE(*stp(sd.gates, u3 + H * 4, rb3[r]), u[r]);
       }
       fetch_x(1, t + 1);
@@ -231,8 +212,8 @@ __global__ __launch_bounds__(64 * XNW) void gru_fwd_x3_kernel(const GruArgs a) {
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
       const int i = lq * 4 + r;
-      const float c = x_tanh(ac[r] + x[2][r]);
-      const float hn = u[r] * h[r] + (1.0f - u[r]) * c;
+      const float c = gru_tanh(ac[r] + x[2][r]);
+      const float hn = gru_blend(u[r], h[r], c);
       const bool live = t < len[r];
       if (rok[r]) {
         XG_STORE(*stp(sd.gates, u3 + 2 * H * 4, rb3[r]), c);
@@ -347,9 +328,9 @@ __global__ __launch_bounds__(64 * XNW) void gru_bwd_x3_kernel(const GruArgs a) {
       const bool live = t < len[r];
       const float u = n_u[r], c = n_c[r];
       const float d = dh[r] + n_do[r];
-      const float du = d * (c_hp[r] - c), dc = d * (1.0f - u);
-      const float v_dpu = live ? du * u * (1.0f - u) : 0.f;
-      const float v_dpc = live ? dc * (1.0f - c * c) : 0.f;
+      const float dc = gru_dc(d, u), du = gru_du(d, c_hp[r], c);
+      const float v_dpu = gru_dpu(du, u, live);
+      const float v_dpc = gru_dpc(dc, c, live);
       dh[r] = live ? d * u : dh[r];
       su += r < nreal ? v_dpu : 0.f;
       sc += r < nreal ? v_dpc : 0.f;
@@ -381,7 +362,7 @@ __global__ __launch_bounds__(64 * XNW) void gru_bwd_x3_kernel(const GruArgs a) {
         const bool live = t < len[r];
         const float rr = live ? n_r[r] : 0.f, hp = c_hp[r];
         const float drh = acc[r];
-        const float v_dpr = live ? drh * hp * rr * (1.0f - rr) : 0.f;
+        const float v_dpr = gru_dpr(drh, hp, rr, live);
         dh[r] += live ? drh * rr : 0.f;
         sr += r < nreal ? v_dpr : 0.f;
         if (rok[r]) {

@@ -4,6 +4,7 @@
 #include <stdlib.h>
 #include "common.h"
 #include "kernels.h"
+#include "cell.h"
 
 // The first attention layer acts on inp = [q, k, q-k, q*k] (score.py:173-174), k = [user_rep | item_rep |
 // atten_info], q broadcast over the T slices.  With W1 = [Wa; Wb; Wc; Wd] (Dk rows each)
@@ -24,18 +25,6 @@ __device__ __forceinline__ void attn_fold_w1_body(int blk, int Dk, int NA, const
     weff[c * copy_stride + Dk * NA + i] = wd;
   }
   wq[i] = wa + wc;
-}
-__global__ __launch_bounds__(256) void attn_fold_w1_kernel(int Dk, int NA, const float* __restrict__ W1, float* __restrict__ weff,
-                                                           float* __restrict__ wq, int copies, int64_t copy_stride) {
-  attn_fold_w1_body(blockIdx.x, Dk, NA, W1, weff, wq, copies, copy_stride);
-}
-
-int score_launch_attn_fold_w1(int Dk, int NA, const float* W1, float* weff, float* wq, hipStream_t s, int copies,
-                              int64_t copy_stride) {
-  hipLaunchKernelGGL(attn_fold_w1_kernel, dim3((Dk * NA + 255) / 256), dim3(256), 0, s, Dk, NA, W1, weff, wq, copies,
-                     copy_stride);
-  SCORE_CHECK_LAUNCH();
-  return 0;
 }
 
 // inp2 = [k, q*k]
@@ -438,12 +427,10 @@ __global__ void head_out_kernel(int B, int NF, const float* __restrict__ f2, con
   float z = acc + b3[0];
   float p = sigmoidf_(z);
   float lab = (float)label[b];
-  const float eps = 1e-7f;
   logit[b] = z;
   y[b] = p;
-  lossb[b] = -lab * logf(p + eps) - (1.0f - lab) * logf(1.0f - p + eps);
-  float dp = (-lab / (p + eps) + (1.0f - lab) / (1.0f - p + eps)) / (float)Bglobal;
-  dlogit[b] = dp * p * (1.0f - p);
+  lossb[b] = logloss_term(p, lab);
+  dlogit[b] = logloss_dlogit(p, lab, Bglobal);
 }
 
 #define L2_PARTS 256
@@ -464,14 +451,6 @@ __device__ __forceinline__ void sumsq_stage1_body(int blk, int nblk, const float
     __syncthreads();
   }
   if (threadIdx.x == 0) part[blk] = sh[0];
-}
-__global__ __launch_bounds__(256) void sumsq_stage1(const float* __restrict__ x, int64_t n, float* __restrict__ part) {
-  sumsq_stage1_body(blockIdx.x, gridDim.x, x, n, part);
-}
-int score_launch_l2_partials(const float* wreg, int64_t n_reg, float* part /* L2_PARTS floats */, hipStream_t s) {
-  hipLaunchKernelGGL(sumsq_stage1, dim3(L2_PARTS), dim3(256), 0, s, wreg, n_reg, part);
-  SCORE_CHECK_LAUNCH();
-  return 0;
 }
 // one block: loss[1] = sum_b lossb / Bglobal, loss[2] = 0.5 * sum(parts), loss[0] = loss[1] + lambda*loss[2]
 // (fixed-order tree sums: reproducible)
@@ -503,7 +482,7 @@ __global__ __launch_bounds__(256) void loss_final_kernel(const float* __restrict
 
 int score_launch_head_out(int B, int NF, const float* f2, const float* w3, const float* b3, const int32_t* label,
                           float* logit, float* y, float* lossb, float* dlogit, float* loss, float lambda,
-                          const float* part /* L2_PARTS sums of squares from score_launch_l2_partials */, int Bglobal,
+                          const float* part /* L2_PARTS sums of squares from score_launch_weight_prep */, int Bglobal,
                           hipStream_t s, const int32_t* id_status) {
   // Bglobal = samples the mean is taken over (the local batch, or the global batch when data-parallel)
   hipLaunchKernelGGL(head_out_kernel, dim3((B + 63) / 64), dim3(64), 0, s, B, NF, f2, w3, b3, label, logit, y,
@@ -581,7 +560,6 @@ __device__ __forceinline__ void gru_wxcat_body(int blk, const WxcatArgs& a) {
   else v = j < 2 * H ? gb[j] : cb[j - 2 * H];
   a.cat[i] = v;
 }
-__global__ __launch_bounds__(256) void gru_wxcat_kernel(const WxcatArgs a) { gru_wxcat_body(blockIdx.x, a); }
 
 // The per-step transforms of the WEIGHTS -- the concatenated [Wx_gates | Wx_cand] copies, the folded first attention layer
 // (optional) and the partial sums of squares of the regularised range -- in ONE launch (round 4: three launches before; the
@@ -609,15 +587,6 @@ int score_launch_weight_prep(const float* gk0, const float* ck0, const float* gb
   a.b_fold = W1 ? (Dk * NA + 255) / 256 : 0;
   a.wreg = wreg; a.n_reg = n_reg; a.part = part;
   hipLaunchKernelGGL(weight_prep_kernel, dim3(a.b_wx + a.b_fold + L2_PARTS), dim3(256), 0, s, a);
-  SCORE_CHECK_LAUNCH();
-  return 0;
-}
-int score_launch_gru_wxcat(const float* gk0, const float* ck0, const float* gb0, const float* cb0, const float* gk1,
-                           const float* ck1, const float* gb1, const float* cb1, int I0, int I1, int Imax, int H,
-                           float* cat, hipStream_t s) {
-  int64_t n = 2 * (int64_t)(Imax + 1) * 3 * H;
-  hipLaunchKernelGGL(gru_wxcat_kernel, dim3((unsigned)cdiv64(n, 256)), dim3(256), 0, s,
-                     WxcatArgs{gk0, ck0, gb0, cb0, gk1, ck1, gb1, cb1, I0, I1, Imax, H, cat});
   SCORE_CHECK_LAUNCH();
   return 0;
 }

@@ -10,6 +10,7 @@
 // 64-B runs per 16 lanes) are fetched a 16-step chunk ahead.
 #include "common.h"
 #include "kernels.h"
+#include "cell.h"
 
 typedef float hf_f32x4 __attribute__((ext_vector_type(4)));
 
@@ -91,17 +92,6 @@ struct HeadFwdArgs {
   int phase;
 };
 
-__device__ __forceinline__ float hf_act(float v, float bias, int drop, float keep, const uint8_t* mask, uint64_t seed,
-                                        int row, int col, int N) {
-  v = fmaxf(v + bias, 0.f);                             // dense(activation=relu)
-  if (drop) {                                           // tf.nn.dropout: x / keep * Bernoulli(keep)  (same element
-    const uint64_t e = (uint64_t)row * (uint64_t)N + (uint64_t)col;      // numbering as the GEMM epilogue's)
-    const bool on = mask ? (mask[e] != 0) : (hash_uniform(seed, e) < keep);
-    v = on ? v / keep : 0.f;
-  }
-  return v;
-}
-
 __global__ __launch_bounds__(64 * HF_NW) void head_fwd_fused_kernel(const HeadFwdArgs a) {
   extern __shared__ float sm[];
   const uint64_t seed0 = a.seed_dev ? *a.seed_dev : a.seed0;
@@ -180,7 +170,7 @@ __global__ __launch_bounds__(64 * HF_NW) void head_fwd_fused_kernel(const HeadFw
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
           const int row = b0 + lq * 4 + r;
-          const float v = hf_act(acc[0][r], bias, a.drop, a.keep, a.mask0, seed0, row, col, N1);
+          const float v = relu_dropout(acc[0][r], bias, a.drop, a.keep, a.mask0, seed0, row, col, N1);
           if (row < a.B) a.f1[(int64_t)row * N1 + col] = v;
         }
       }
@@ -211,7 +201,7 @@ __global__ __launch_bounds__(64 * HF_NW) void head_fwd_fused_kernel(const HeadFw
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
         const int i = lq * 4 + r, row = b0 + i;
-        const float v = hf_act(acc[t][r], bias, a.drop, a.keep, a.mask0, seed0, row, col, N1);
+        const float v = relu_dropout(acc[t][r], bias, a.drop, a.keep, a.mask0, seed0, row, col, N1);
         f1s[i * LD1 + col] = v;
         if (row < a.B) a.f1[(int64_t)row * N1 + col] = v;
       }
@@ -233,7 +223,7 @@ __global__ __launch_bounds__(64 * HF_NW) void head_fwd_fused_kernel(const HeadFw
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
         const int i = lq * 4 + r, row = b0 + i;
-        const float v = hf_act(acc[0][r], bias, a.drop, a.keep, a.mask1, seed1, row, col, N2);
+        const float v = relu_dropout(acc[0][r], bias, a.drop, a.keep, a.mask1, seed1, row, col, N2);
         f2s[i * LD2 + col] = v;
         if (row < a.B) a.f2[(int64_t)row * N2 + col] = v;
       }
@@ -253,12 +243,10 @@ __global__ __launch_bounds__(64 * HF_NW) void head_fwd_fused_kernel(const HeadFw
       const float z = s + a.b3[0];
       const float p = sigmoidf_(z);
       const float lab = (float)a.label[row];
-      const float eps = 1e-7f;
       a.logit[row] = z;
       a.y[row] = p;
-      a.lossb[row] = -lab * logf(p + eps) - (1.0f - lab) * logf(1.0f - p + eps);
-      const float dp = (-lab / (p + eps) + (1.0f - lab) / (1.0f - p + eps)) / (float)a.Bglobal;
-      const float dl = dp * p * (1.0f - p);
+      a.lossb[row] = logloss_term(p, lab);
+      const float dl = logloss_dlogit(p, lab, a.Bglobal);
       a.dlogit[row] = dl;
       xs[i] = dl;                       // (bn1's tile is dead by now)
     }
@@ -296,7 +284,7 @@ struct AttnFwdArgs {
   const float* Weff; const float* qz;
   const float* W4; const float* b4; const float* w5; const float* b5; const int32_t* length;
   float* inp; float* a1; float* a2; float* score; float* head; int ldh, off_u, off_i;
-  int wcopies; int64_t wstride;   // replicas of Weff (head.hip: attn_fold_w1_kernel)
+  int wcopies; int64_t wstride;   // replicas of Weff (head.hip: attn_fold_w1_body)
 };
 
 __device__ __forceinline__ void af_build(const AttnFwdArgs& a, float* __restrict__ xs, int LD, int Kp, int row0,

@@ -14,6 +14,30 @@ struct GemmProb {
   int M, N, K, lda, ldb, ldc, k_chunk, gx, gy, nblocks;    // nblocks = gx*gy*gz; the launch gives it align8(nblocks)
 };
 struct GemmGroup { int n; int total_blocks; GemmProb p[GEMM_GROUP_MAX]; };
+// score_gemm's flag bits (include/score_hip.h) as every GEMM kernel and the engine spell them; GF_X3F: bf16x3 forced (A/B);
+// flags >> 16: the bias row group
+enum { GF_BIAS = 1, GF_RELU = 2, GF_ACC = 4, GF_DROP = 8, GF_X3 = 16, GF_X3F = 32, GF_RELUGRAD = 64 };
+// bias element of (row, col): one bias row, or one per group of g = flags >> 16 output rows
+__device__ __forceinline__ int64_t bias_index(int flags, int row, int col, int N) {
+  const int g = flags >> 16;
+  return g ? (int64_t)(row / g) * N + col : col;
+}
+// what the f32 and the bf16x3 kernels do to an output element before they store it
+__device__ __forceinline__ float gemm_epilogue(float v, int row, int col, int N, const float* bias, int flags,
+                                               float keep, const uint8_t* mask, uint64_t seed) {
+  if (flags & GF_BIAS) v += bias[bias_index(flags, row, col, N)];
+  if (flags & GF_RELU) v = fmaxf(v, 0.f);
+  if (flags & GF_DROP) {
+    uint64_t e = (uint64_t)row * (uint64_t)N + (uint64_t)col;
+    bool on = mask ? (mask[e] != 0) : (hash_uniform(seed, e) < keep);
+    v = on ? v / keep : 0.f;  // tf.nn.dropout: x / keep_prob * binary mask
+  }
+  if (flags & GF_RELUGRAD) {   // backward of relu (+dropout): `mask` carries the layer's fp32 output Y [M,N]
+    const float y = reinterpret_cast<const float*>(mask)[(int64_t)row * N + col];
+    v = y > 0.f ? v / keep : 0.f;
+  }
+  return v;
+}
 int score_launch_gemm_bf16x3(int trans, int wm, const GemmGroup& g, const float* bias, int flags, float keep,
                              const uint8_t* mask, uint64_t seed, hipStream_t s);
 // deferred weight-gradient products C = A^T . B (layout 2) of a backward pass: queued while the pass runs
@@ -48,7 +72,6 @@ int colsum_queue_flush(ColsumJobs* q, float* part, int64_t part_floats, hipStrea
 // independent of each other, each workgroup does what its index says.  Same arithmetic, same order as the separate launches.
 // w1: the folded first attention layer's gradient computed by the same launch from the dweff / dwq products' slabs
 // (instead of score_launch_attn_w1_grad behind it); stage1_done: see gemm_queue_flush
-int colsum_queue_stage1(const ColsumJobs* q, float* part, int64_t part_floats, hipStream_t s);
 struct W1Fold { int Dk, NA; const float* dweff; const float* dwq; float* gW1; const float* slab_e; const float* slab_q; int ns_e, ns_q; };
 int score_launch_finish(const ReduceGroup* rg, ColsumJobs* q, float* part, int64_t part_floats, hipStream_t s, int stage1_done = 0,
                         const W1Fold* w1 = nullptr);
@@ -109,8 +132,6 @@ int score_launch_attn_inp_bwd(int B, int T, int H, int NI, const float* dinp, co
                               const float* ir, const float* info, const float* score, const float* dhead, int ldh,
                               int off_u, int off_i, const float* dqd, float* dur, float* dir, float* dinfo, float* dq,
                               hipStream_t s);
-int score_launch_attn_fold_w1(int Dk, int NA, const float* W1, float* weff, float* wq, hipStream_t s, int copies = 1,
-                              int64_t copy_stride = 0);
 int score_launch_attn_inp_bwd_fused(int B, int T, int H, int NI, int N1, const float* da1, const float* Weff, const float* q,
                                     const float* ur, const float* ir, const float* info, const float* score,
                                     const float* dhead, int ldh, int off_u, int off_i, float* dur, float* dir, float* dinfo,
@@ -118,7 +139,7 @@ int score_launch_attn_inp_bwd_fused(int B, int T, int H, int NI, int N1, const f
                                     const float* w5 = nullptr, const float* W4 = nullptr, const int32_t* length = nullptr,
                                     float* ds = nullptr, float* da2 = nullptr, float* da1_out = nullptr);
 bool score_attn_inp_bwd_fused_fits(int B, int T, int H, int NI, int N1, int N2, int ldh, int off_u, int off_i, bool pool);
-#define SCORE_WEFF_COPIES 8       /* replicas of the folded attention weight (head.hip: attn_fold_w1_kernel) */
+#define SCORE_WEFF_COPIES 8       /* replicas of the folded attention weight (head.hip: attn_fold_w1_body) */
 int score_launch_attn_dzsum(int B, int T, int NA, const float* dz, float* dzsum, hipStream_t s);
 int score_launch_attn_w1_grad(int Dk, int NA, const float* dweff, const float* dwq, float* gW1, hipStream_t s);
 int score_launch_bn_fwd(int B, int Dh, const float* x, const float* gamma, const float* beta, float rs, float* y,
@@ -126,7 +147,6 @@ int score_launch_bn_fwd(int B, int Dh, const float* x, const float* gamma, const
 int score_launch_bn_bwd(int B, int Dh, const float* x, const float* gamma, float rs, const float* dy, float* dx,
                         float* dgamma, float* dbeta, float* tmp, float* scratch, int64_t scratch_floats,
                         ColsumJobs* cq, hipStream_t s);
-int score_launch_l2_partials(const float* wreg, int64_t n_reg, float* part /* 256 floats */, hipStream_t s);
 // the per-step transforms of the weights in one launch: [Wx_gates | Wx_cand] copies, the folded first attention layer
 // (W1 = null: none), the L2 partial sums
 int score_launch_weight_prep(const float* gk0, const float* ck0, const float* gb0, const float* cb0, const float* gk1,
@@ -157,9 +177,6 @@ int score_launch_attn_fwd_fused(int B, int T, int H, int NI, int N1, int N2, con
                                 hipStream_t s, int weff_copies = 1, int64_t weff_copy_stride = 0);
 int score_launch_outer_relu_bwd(int B, int NF, const float* dlogit, const float* w, const float* f, float keep,
                                 float* dz, hipStream_t s);
-int score_launch_gru_wxcat(const float* gk0, const float* ck0, const float* gb0, const float* cb0, const float* gk1,
-                           const float* ck1, const float* gb1, const float* cb1, int I0, int I1, int Imax, int H,
-                           float* cat, hipStream_t s);
 int score_launch_copy2d(int64_t rows, int cols, const float* src, int lds_, float* dst, int ldd, hipStream_t s);
 
 // scatter.hip: occurrence sort ("index plan") and the pull-form gradient scatter

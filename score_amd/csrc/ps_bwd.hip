@@ -362,9 +362,9 @@ __global__ __launch_bounds__(PS_NT) void ps_bwd_kernel(const PsBwdArgs a) {
       ndo = dgb[tp * H + j];
       const bool live = t < len;
       const float d = dh + dout;
-      const float du = d * (hp - cnd), dc = d * (1.0f - u);
-      const float dpu = live ? du * u * (1.0f - u) : 0.f;
-      const float dpc = live ? dc * (1.0f - cnd * cnd) : 0.f;
+      const float dc = gru_dc(d, u), du = gru_du(d, hp, cnd);
+      const float dpu = gru_dpu(du, u, live);
+      const float dpc = gru_dpc(dc, cnd, live);
       dh = live ? d * u : dh;
       float p0 = 0.f, p1 = 0.f;
 #pragma unroll
@@ -375,7 +375,7 @@ __global__ __launch_bounds__(PS_NT) void ps_bwd_kernel(const PsBwdArgs a) {
         p1 = fmaf(x1, wct[k + 1], p1);
       }
       const float drh = p0 + p1;
-      const float dpr = live ? drh * hp * r * (1.0f - r) : 0.f;
+      const float dpr = gru_dpr(drh, hp, r, live);
       dh = live ? fmaf(drh, r, dh) : dh;
       float q0 = 0.f, q1 = 0.f;
 #pragma unroll

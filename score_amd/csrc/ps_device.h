@@ -1,6 +1,7 @@
 // Device helpers shared by the per-sample whole-model kernels (ps_fwd.hip, ps_bwd.hip); see persample.h.
 #pragma once
 #include "persample.h"
+#include "cell.h"
 
 typedef float ps_f32x4 __attribute__((ext_vector_type(4)));
 
@@ -219,9 +220,6 @@ __device__ __forceinline__ void ps_touch_use(const PsTouch& t, float* sink) {
   if (acc == 1.2345678e-30f) *sink = acc;        // (never true for finite weights' sums in practice; keeps the loads)
 }
 
-// fast transcendental forms of the recurrence epilogues (v_exp_f32 / v_rcp_f32, as csrc/gru.hip's register kernels)
-__device__ __forceinline__ float ps_sigmoid(float x) { return __builtin_amdgcn_rcpf(1.0f + __expf(-x)); }
-__device__ __forceinline__ float ps_tanh(float x) { return 1.0f - 2.0f * __builtin_amdgcn_rcpf(__expf(2.0f * x) + 1.0f); }
 // LDS traffic between the lanes of ONE wave: the wave's LDS operations execute in program order, this only keeps the
 // compiler from moving them across
 __device__ __forceinline__ void ps_wave_sync() {

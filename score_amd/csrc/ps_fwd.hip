@@ -194,17 +194,6 @@ __device__ __forceinline__ void ps_gather(const PsFwdArgs& a, const PsLds& L, fl
   }
 }
 
-__device__ __forceinline__ float ps_act(float v, float bias, int drop, float keep, const uint8_t* mask, uint64_t seed, int row,
-                                        int col, int N) {
-  v = fmaxf(v + bias, 0.f);                             // dense(activation=relu)
-  if (drop) {                                           // tf.nn.dropout: x / keep * Bernoulli(keep); element numbering of
-    const uint64_t e = (uint64_t)row * (uint64_t)N + (uint64_t)col;      // head_fused.hip / the GEMM epilogue
-    const bool on = mask ? (mask[e] != 0) : (hash_uniform(seed, e) < keep);
-    v = on ? v / keep : 0.f;
-  }
-  return v;
-}
-
 template <int KMAX, int MT>
 __global__ __launch_bounds__(PS_NT) void ps_fwd_kernel(const PsFwdArgs a) {
   extern __shared__ float sm[];
@@ -340,7 +329,7 @@ __global__ __launch_bounds__(PS_NT) void ps_fwd_kernel(const PsFwdArgs a) {
         ar0 = fmaf(h0, wr[k], ar0); au0 = fmaf(h0, wu[k], au0);
         ar1 = fmaf(h1, wr[k + 1], ar1); au1 = fmaf(h1, wu[k + 1], au1);
       }
-      const float r = ps_sigmoid(ar0 + ar1), u = ps_sigmoid(au0 + au1);
+      const float r = gru_sigmoid(ar0 + ar1), u = gru_sigmoid(au0 + au1);
       const float rh = r * h;
       float ac0 = xc, ac1 = 0.f;
 #pragma unroll
@@ -350,8 +339,8 @@ __global__ __launch_bounds__(PS_NT) void ps_fwd_kernel(const PsFwdArgs a) {
         ac0 = fmaf(g0, wc[k], ac0);
         ac1 = fmaf(g1, wc[k + 1], ac1);
       }
-      const float cnd = ps_tanh(ac0 + ac1);
-      const float hn = u * h + (1.0f - u) * cnd;
+      const float cnd = gru_tanh(ac0 + ac1);
+      const float hn = gru_blend(u, h, cnd);
       const bool live = t < len;
       const float o = live ? hn : 0.f;         // dynamic_rnn: zero output past the length, state carried through
       h = live ? hn : h;
@@ -499,7 +488,7 @@ __global__ __launch_bounds__(PS_NT) void ps_fwd_kernel(const PsFwdArgs a) {
     for (int i = 0; i < 2; ++i) {
       const int col = (wave + 8 * i) * 16 + lc;
       if (lq == 0 && col < 200) {
-        const float v = ps_act(fo[i], W[a.fc_b[0] + col], a.drop, a.keep, a.mask0, seed0, b, col, 200);
+        const float v = relu_dropout(fo[i], W[a.fc_b[0] + col], a.drop, a.keep, a.mask0, seed0, b, col, 200);
         sm[L.f1s + col] = v;
         a.f1[(int64_t)b * 200 + col] = v;
       }
@@ -514,7 +503,7 @@ __global__ __launch_bounds__(PS_NT) void ps_fwd_kernel(const PsFwdArgs a) {
     ps_gemv<1>(fo, sm + L.f1s, tl, 13, lane);
     const int col = wave * 16 + lc;
     if (lq == 0 && wave < 5) {
-      const float v = ps_act(fo[0], W[a.fc_b[1] + col], a.drop, a.keep, a.mask1, seed1, b, col, 80);
+      const float v = relu_dropout(fo[0], W[a.fc_b[1] + col], a.drop, a.keep, a.mask1, seed1, b, col, 80);
       sm[L.f2s + col] = v;
       a.f2[(int64_t)b * 80 + col] = v;
     }
@@ -528,7 +517,9 @@ __global__ __launch_bounds__(PS_NT) void ps_fwd_kernel(const PsFwdArgs a) {
     const float z = wave_sum(part) + W[a.fc_b[2]];
     const float p = sigmoidf_(z);
     const float lab = (float)a.label[b];
-    const float eps = 1e-7f;
+    // cell.h's logloss_term / logloss_dlogit, spelled out: through the helpers the compiler orders this kernel's code
+    // differently, and it is kept byte for byte as it was measured
+    const float eps = SCORE_LOGLOSS_EPS;
     const float dp = (-lab / (p + eps) + (1.0f - lab) / (1.0f - p + eps)) / (float)s.Bglobal;
     const float dl = dp * p * (1.0f - p);
     if (lane == 0) {
