@@ -82,7 +82,22 @@ enum { SCORE_MODEL_SCORE = 0, SCORE_MODEL_RIA = 1, SCORE_MODEL_RCA = 2,
         * hprev): index 0 = layer 1, 1 = layer 2.  At H in {16, 32, 64} the two recurrences run as ONE kernel each way
         * (csrc/gru_stack.hip: layer 2 one step behind layer 1, its input handed over in LDS); other H, and debug_flags bit 13,
         * run them one layer per launch with the projection GEMM between them. */
-       SCORE_MODEL_GRU4REC = 7 };
+       SCORE_MODEL_GRU4REC = 7,
+       /* point_models/point_model.py:140-164 (Caser): two one-filter convolutions over the flat user history X [T, C],
+        * C = item_fnum * eb_dim -- the horizontal one ([50, C], VALID, max over the T - 49 positions: one scalar h per sample; 50
+        * is the reference's constant, so max_time_len >= 50) and the vertical one ([T, 1]: v [C]) followed by a dense on a
+        * trailing axis of size 1 (one scalar weight and bias: v2 = v wd + bd) -- then [h | v2 | target_item | target_user]
+        * through the same bn1 / fc head, log-loss and L2 filter.  hidden_size is accepted and ignored, obj_per_time_slice must
+        * be 1, and the batch rides in score_batch_t as for SCORE_MODEL_GRU4REC, except that length is NOT read (the reference's
+        * graph does not use user_seq_length: every one of the T positions is computed and gets gradient; active_slices is
+        * ignored too).  The head input is held padded to a multiple of four floats, [h, 0, 0, 0 | v2 | target_item |
+        * target_user]: bn1/gamma, bn1/beta and fc1/kernel have 4 + 2 Di + Du rows in score_param_layout, rows 1..3 being pad
+        * rows that the caller initialises to zero and that training then leaves at zero (zero gradient, zero L2 term, zero
+        * Adam update); the variables TF has are the rows 0, 4, 5, ...  conv2d/kernel is [50, C], conv2d_1/kernel [T, 1],
+        * dense/kernel [1, 1].  Workspace fields (score_workspace_field): caser_hwin [B, T - 49] the window sums + bias,
+        * caser_arg [B] (int32) the first position of the maximum, caser_v [B, C] v before the scalar dense.  Kernels:
+        * csrc/caser.hip. */
+       SCORE_MODEL_CASER = 8 };
 
 /* Constructor arguments of SCOREBASE.__init__ (score.py:12-13). */
 typedef struct {
@@ -90,7 +105,7 @@ typedef struct {
   int32_t eb_dim;              /* D: multiple of 4, <= 256                        */
   int32_t hidden_size;         /* H                                               */
   int32_t max_time_len;        /* T                                               */
-  int32_t obj_per_time_slice;  /* K <= 32 (SCORE_MODEL_GRU4REC: 1)                */
+  int32_t obj_per_time_slice;  /* K <= 32 (SCORE_MODEL_GRU4REC / _CASER: 1)        */
   int32_t user_fnum;           /* Fu                                              */
   int32_t item_fnum;           /* Fi                                              */
   int32_t model_type;          /* SCORE_MODEL_*                                   */
@@ -103,7 +118,7 @@ typedef struct {
   int64_t offset;              /* in floats, into the flat buffer                 */
   int32_t rows, cols;          /* cols == 0 for vectors                           */
   int32_t regularised;         /* build_l2norm name filter, score.py:91-94        */
-  int32_t init;                /* 0 zeros, 1 ones, 2 glorot-uniform               */
+  int32_t init;                /* 0 zeros, 1 ones, 2 glorot-uniform, 3 glorot-uniform with TF's convolution fans: fan_in = fan_out = rows * cols */
 } score_param_entry_t;
 
 /* Layout of the flat dense-parameter buffer: regularised tensors first

@@ -1,7 +1,7 @@
 // Whole-path orchestration: parameter/workspace layout and the forward / backward
 // launch sequences of SCORE and its ablations (score.py:188-369) and of the slice baselines RRN and GCMC
-// (slice_model.py:155-203) and of the point baseline GRU4Rec (point_model.py:123-138) on one stream.  Host code only; every
-// kernel lives in embed/gemm/gru/gru_stack/head/gcmc.hip.
+// (slice_model.py:155-203) and of the point baselines GRU4Rec and Caser (point_model.py:123-164) on one stream.  Host code only;
+// every kernel lives in embed/gemm/gru/gru_stack/head/gcmc/caser.hip.
 #include <string.h>
 #include <stdlib.h>
 #include <stdio.h>
@@ -15,6 +15,7 @@
 namespace {
 
 const int FC1 = 200, FC2 = 80, AT1 = 80, AT2 = 40;
+const int CASER_L = SCORE_CASER_L, CASER_HPAD = SCORE_CASER_HPAD;       // kernels.h
 
 struct Dims {
   int64_t N;
@@ -23,6 +24,7 @@ struct Dims {
   int Is[2];       // GRU input width per side (user, item): I, except RRN / GCMC (their 1-hop sums only)
   bool coattn, attn, gcmc;
   bool g4r;        // GRU4Rec: "side" 0 is layer 1 (input: the gathered user_seq rows, Di wide), "side" 1 layer 2 (input: layer 1's outputs, H wide)
+  bool caser;      // Caser: no recurrence at all (H = 0 here, whatever the config says); C = Di columns of xside[0] are its X
   int Ic;          // row capacity of a side's block of the concatenated [Wx_gates | Wx_cand] copy: I (GRU4Rec: max(I, H))
   int off_u, off_i, off_ti, off_tu;  // columns of head_inp
 };
@@ -32,14 +34,19 @@ int make_dims(const score_config_t* c, Dims* d) {
   d->N = c->feature_size; d->D = c->eb_dim; d->H = c->hidden_size; d->T = c->max_time_len;
   d->K = c->obj_per_time_slice; d->Fu = c->user_fnum; d->Fi = c->item_fnum; d->mt = c->model_type;
   if (d->N <= 0 || d->D <= 0 || (d->D & 3) || d->D > 256 || d->H <= 0 || d->T <= 0 || d->K <= 0 || d->K > 32 ||
-      d->Fu <= 0 || d->Fi <= 0 || d->mt < 0 || d->mt > SCORE_MODEL_GRU4REC)
+      d->Fu <= 0 || d->Fi <= 0 || d->mt < 0 || d->mt > SCORE_MODEL_CASER)
     return SCORE_E_SHAPE;
   d->Du = d->Fu * d->D; d->Di = d->Fi * d->D; d->I = d->Di + d->Du; d->Dq = d->Du + d->Di;
   d->gcmc = d->mt == SCORE_MODEL_GCMC;
   d->g4r = d->mt == SCORE_MODEL_GRU4REC;
-  if (d->g4r && d->K != 1) return SCORE_E_SHAPE;              // (user_seq rides as a [B, T, 1, Fi] set)
+  d->caser = d->mt == SCORE_MODEL_CASER;
+  if ((d->g4r || d->caser) && d->K != 1) return SCORE_E_SHAPE;      // (user_seq rides as a [B, T, 1, Fi] set)
+  if (d->caser) {
+    if (d->T < CASER_L) return SCORE_E_SHAPE;                 // (conv2d's VALID window, point_model.py:147: TF refuses the graph)
+    d->H = 0;                                                 // hidden_size: accepted and ignored -- no GRU variable, workspace or launch
+  }
   // (GCMC starts from RRN's two 1-hop sums, slice_model.py:184-187; GRU4Rec's user_seq rows are RRN's "sum" over a one-element set)
-  const bool rrn = d->mt == SCORE_MODEL_RRN || d->gcmc || d->g4r;
+  const bool rrn = d->mt == SCORE_MODEL_RRN || d->gcmc || d->g4r || d->caser;
   d->coattn = d->mt != SCORE_MODEL_RCA && !rrn;
   d->attn = d->mt != SCORE_MODEL_RIA && !rrn;
   d->NI = (d->mt == SCORE_MODEL_RCA || d->mt == SCORE_MODEL_RIA || rrn) ? 0 : 4 * d->K;
@@ -49,11 +56,18 @@ int make_dims(const score_config_t* c, Dims* d) {
   d->Ic = d->g4r && d->H > d->I ? d->H : d->I;
   if (d->gcmc && d->H > 256) return SCORE_E_SHAPE;            // (its head kernels, gcmc.hip)
   d->Dk = d->attn ? 2 * d->H + d->NI : 0;
-  d->nstate = (d->mt == SCORE_MODEL_SCORE_USER || d->mt == SCORE_MODEL_SCORE_ITEM || d->g4r) ? 1 : 2;
+  d->nstate = d->caser ? 0 : (d->mt == SCORE_MODEL_SCORE_USER || d->mt == SCORE_MODEL_SCORE_ITEM || d->g4r) ? 1 : 2;
   d->Dhead = d->nstate * d->H + d->Di + d->Du;
   d->off_u = d->mt == SCORE_MODEL_SCORE_ITEM ? -1 : 0;       // (GRU4Rec: layer 2's final state sits where SCORE_USER's state does)
   d->off_i = d->mt == SCORE_MODEL_SCORE_USER ? -1 : (d->mt == SCORE_MODEL_SCORE_ITEM ? 0 : d->H);
   d->off_ti = d->nstate * d->H;       // [..., target_item, target_user]  (score.py:217)
+  if (d->caser) {
+    // [h, 0, 0, 0 | v2 (Di) | target_item | target_user]: TF's 1 + 2 Di + Du columns with h padded to four floats, so that the
+    // target kernels' 16-byte accesses at off_ti / off_tu and the head kernels' vector path (Dhead % 4 == 0) hold
+    d->Dhead = CASER_HPAD + 2 * d->Di + d->Du;
+    d->off_u = d->off_i = -1;
+    d->off_ti = CASER_HPAD + d->Di;
+  }
   d->off_tu = d->off_ti + d->Di;
   return 0;
 }
@@ -64,8 +78,9 @@ static inline int x_ld(const Dims& d, int sd) { return d.gcmc ? d.Is[sd] : (d.g4
 
 // time slices actually computed for a batch (score_batch_t.active_slices): every [B*T, .] activation of the
 // pass is laid out [B * TA, .]; the workspace regions keep their full-T sizes and offsets
+// (Caser reads no length: all T positions, whatever the batch says)
 static inline int active_T(const Dims& d, const score_batch_t* bt) {
-  const int a = bt->active_slices;
+  const int a = d.caser ? 0 : bt->active_slices;
   return (a > 0 && a < d.T) ? a : d.T;
 }
 
@@ -78,6 +93,7 @@ struct Params {  // float offsets into the flat buffer
   int64_t at_w[4], at_b[4];
   int64_t bn_g, bn_b, fc_w[3], fc_b[3];
   int64_t gm_a[2], gm_c[2], gm_4, gm_5;  // GCMC: per side dense (Wa) and dense_2 / dense_3 (Wc); the head's dense_4, dense_5
+  int64_t cs_wh, cs_bh, cs_wv, cs_bv, cs_wd, cs_bd;  // Caser: conv2d (horizontal), conv2d_1 (vertical), dense (the scalar one)
   int64_t n_floats, n_reg;
 };
 
@@ -107,7 +123,14 @@ int build_layout_raw(const Dims& d, score_param_entry_t* out, int max_entries, P
   }
   const char* sides[2] = {"gru_user_side", "gru_item_side"};
   if (d.gcmc || d.g4r) { sides[0] = "gru1"; sides[1] = "gru2"; }     // (GRU4Rec, point_model.py:129-132: the two stacked layers)
-  for (int s = 0; s < 2; ++s) {
+  // Caser (point_model.py:147-157): conv2d [50, C, 1, 1], conv2d_1 [T, 1, 1, 1] (init 3: glorot with TF's convolution fans,
+  // fan_in = fan_out = rows * cols), dense [1, 1]
+  if (d.caser) {
+    add("conv2d/kernel", CASER_L, d.Di, 1, 3); add("conv2d/bias", 1, 0, 0, 0);
+    add("conv2d_1/kernel", d.T, 1, 1, 3); add("conv2d_1/bias", 1, 0, 0, 0);
+    dense(1, 1);
+  }
+  for (int s = 0; s < 2 && !d.caser; ++s) {
     char b[64];
     snprintf(b, 64, "%s/gru_cell/gates/kernel", sides[s]); add(b, d.Is[s] + d.H, 2 * d.H, 1, 2);
     snprintf(b, 64, "%s/gru_cell/gates/bias", sides[s]); add(b, 2 * d.H, 0, 0, 1);
@@ -150,6 +173,10 @@ int build_layout_raw(const Dims& d, score_param_entry_t* out, int max_entries, P
   int i = 0;
   if (d.coattn) { for (int c = 0; c < 2; ++c) { P->ca_w[c] = off[i++]; P->ca_b[c] = off[i++]; } }
   if (d.gcmc) { P->gm_a[0] = off[i++]; P->gm_a[1] = off[i++]; P->gm_c[0] = off[i++]; P->gm_c[1] = off[i++]; }
+  if (d.caser) {
+    P->cs_wh = off[i++]; P->cs_bh = off[i++]; P->cs_wv = off[i++]; P->cs_bv = off[i++]; P->cs_wd = off[i++]; P->cs_bd = off[i++];
+    for (int s = 0; s < 2; ++s) P->gk[s] = P->gb[s] = P->ck[s] = P->cb[s] = 0;
+  } else
   for (int s = 0; s < 2; ++s) { P->gk[s] = off[i++]; P->gb[s] = off[i++]; P->ck[s] = off[i++]; P->cb[s] = off[i++]; }
   if (d.attn) { for (int a = 0; a < 4; ++a) { P->at_w[a] = off[i++]; P->at_b[a] = off[i++]; } }
   if (d.gcmc) {
@@ -211,6 +238,9 @@ struct WS {
   // GCMC only (-1 otherwise): per side A = relu(S Wa), Z = relu(A Wc) and the gradients at their pre-activations, [B*T, Dx];
   // the head's p = h_i W4 | n = h_i W5 [2][B, H], g = dL/da [B], and gpos = g h_u | gneg = -g h_u [2][B, H]
   int64_t gcmc_a[2], gcmc_z[2], gcmc_dz[2], gcmc_da[2], gcmc_pn, gcmc_g, gcmc_gu;
+  // Caser only (-1 otherwise): the window sums [B, T - 49], the first position of their maximum [B] (int32), v before the scalar
+  // dense [B, C]
+  int64_t caser_hwin, caser_arg, caser_v;
   int64_t scratch_floats, total;
 };
 
@@ -281,9 +311,9 @@ void build_ws_raw(const Dims& d, int B, WS* w) {
   w->cs_part = take(w->cs_part_floats);
   w->wxcat = take(2 * (int64_t)(d.Ic + 1) * 3 * d.H);
   for (int sd = 0; sd < 2; ++sd) {
-    const int ns = panel_x_splits(d.H);
+    const int ns = d.H > 0 ? panel_x_splits(d.H) : 0;      // (Caser: no recurrence, no projection)
     w->pimg_x[sd] = take(ns ? ns * score_gemm_panel_image_floats(3 * d.H / ns, d.Is[sd]) : 0);
-    const int nd = panel_d_splits(d.Is[sd]);
+    const int nd = d.H > 0 ? panel_d_splits(d.Is[sd]) : 0;
     w->pimg_d[sd] = take(nd ? nd * score_gemm_panel_image_floats(d.Is[sd] / nd, 3 * d.H) : 0);
   }
   w->psimg = take(ps_image_region_floats(d));
@@ -340,6 +370,11 @@ void build_ws_raw(const Dims& d, int B, WS* w) {
   } else {
     for (int s = 0; s < 2; ++s) w->gcmc_a[s] = w->gcmc_z[s] = w->gcmc_dz[s] = w->gcmc_da[s] = -1;
     w->gcmc_pn = w->gcmc_g = w->gcmc_gu = -1;
+  }
+  if (d.caser) {
+    w->caser_hwin = take((int64_t)B * (d.T - CASER_L + 1)); w->caser_arg = take(B); w->caser_v = take((int64_t)B * d.Di);
+  } else {
+    w->caser_hwin = w->caser_arg = w->caser_v = -1;
   }
   w->total = cur;
 }
@@ -630,6 +665,21 @@ static int g4r_grus_bwd(const Pass& c, const float* dfinal2, int* bias_rows) {
   return 0;
 }
 
+// ---------------------------------------------------------------- Caser's two convolutions (point_model.py:147-160, caser.hip)
+// X = the gathered user_seq rows: columns [0, Di) of xside[0]; the backward pass writes every column of dxside[0] (zeros past Di)
+static void caser_args(const Pass& c, float* gw, CaserArgs* a) {
+  const Dims& d = c.d; const Params& P = c.P; const WS& w = c.w; float* ws = c.ws; const float* W = c.W;
+  memset(a, 0, sizeof(*a));
+  a->B = c.B; a->T = d.T; a->C = d.Di; a->ldx = d.I; a->ldh = d.Dhead;
+  a->X = ws + w.xside[0]; a->Wh = W + P.cs_wh; a->bh = W + P.cs_bh; a->Wv = W + P.cs_wv; a->bv = W + P.cs_bv;
+  a->wd = W + P.cs_wd; a->bd = W + P.cs_bd;
+  a->head = ws + w.head_inp; a->hwin = ws + w.caser_hwin; a->arg = reinterpret_cast<int32_t*>(ws + w.caser_arg); a->v = ws + w.caser_v;
+  a->dhead = ws + w.dhead; a->dX = ws + w.dxside[0];
+  if (gw) {
+    a->gWh = gw + P.cs_wh; a->gbh = gw + P.cs_bh; a->gWv = gw + P.cs_wv; a->gbv = gw + P.cs_bv; a->gwd = gw + P.cs_wd; a->gbd = gw + P.cs_bd;
+  }
+}
+
 // ---------------------------------------------------------------- the two co-attention calls
 // 1: (user_1hop, item_2hop, target_item) ; 2: (user_2hop, item_1hop, target_user)  (score.py:196-197)
 // user_side = [user_1hop_seq | user_2hop_seq], item_side = [item_1hop_seq | item_2hop_seq]   (:200-201)
@@ -881,7 +931,8 @@ extern "C" int score_workspace_field(const score_config_t* cfg, int32_t B, const
       {"dtgt", w.dtgt, -1}, {"S", w.S, -1}, {"ca_slab", w.ca_slab, -1}, {"psimg", w.psimg, -1},
       {"gcmc_a", w.gcmc_a[0], w.gcmc_a[1]}, {"gcmc_z", w.gcmc_z[0], w.gcmc_z[1]}, {"gcmc_dz", w.gcmc_dz[0], w.gcmc_dz[1]},
       {"gcmc_da", w.gcmc_da[0], w.gcmc_da[1]}, {"gcmc_pn", w.gcmc_pn, w.gcmc_pn + (int64_t)B * d.H}, {"gcmc_g", w.gcmc_g, -1},
-      {"gcmc_gu", w.gcmc_gu, w.gcmc_gu + (int64_t)B * d.H}};
+      {"gcmc_gu", w.gcmc_gu, w.gcmc_gu + (int64_t)B * d.H}, {"caser_hwin", w.caser_hwin, -1}, {"caser_arg", w.caser_arg, -1},
+      {"caser_v", w.caser_v, -1}};
   for (auto& e : tab)
     if (strcmp(e.n, name) == 0) {
       if (e.a < 0) return SCORE_E_BADARG;       // (a region of another model type)
@@ -961,7 +1012,7 @@ extern "C" int score_index_plan(const score_config_t* cfg, const score_state_t* 
 // streams' work is small beside these products: 20.3 -> 19.8 ms/step with both.
 static bool panel_gemms(const Dims& d, const score_state_t* st, int BT, int which) {
   const Flags fl = flags_of(st);
-  if (st->gemm_mode != 1 || fl.no_panel || d.Is[0] != d.Is[1] || d.g4r) return false;
+  if (st->gemm_mode != 1 || fl.no_panel || d.Is[0] != d.Is[1] || d.g4r || d.caser) return false;
   if (which == 1 && d.gcmc) return false;      // (GCMC's input gradients take Z's relu mask in the epilogue: the tiled kernels)
   const int ns = panel_x_splits(d.H), nd = panel_d_splits(d.Is[0]);
   return which == 0 ? ns > 0 && score_gemm_panel_ok(2 * ns, BT, 3 * d.H / ns, d.Is[0], x_ld(d, 0), 3 * d.H, nullptr)
@@ -1271,10 +1322,16 @@ extern "C" int score_forward(const score_config_t* cfg, const score_state_t* st,
     }
   }
   // GRUs (:205-208): hoisted x-projection, then the persistent recurrence
-  HIPTRY(hipStreamWaitEvent(s, sd->wx, 0));
-  if (d.g4r) {
+  if (d.caser) {
+    // Caser has none: both convolutions, the max over the windows and the scalar dense in ONE launch, straight into head_inp
+    CaserArgs a;
+    caser_args(c, nullptr, &a);
+    G(score_caser_fwd(a, s));
+  } else if (d.g4r) {
+    HIPTRY(hipStreamWaitEvent(s, sd->wx, 0));
     G(g4r_grus_fwd(c));
   } else {
+    HIPTRY(hipStreamWaitEvent(s, sd->wx, 0));
     GruArgs ga;
     gru_header(c, &ga);
     float* xp[2] = {ws + w.xproj[0], ws + w.xproj[1]};
@@ -1333,7 +1390,7 @@ extern "C" int score_forward(const score_config_t* cfg, const score_state_t* st,
   } else if (d.g4r) {
     // GRU4Rec (point_model.py:134): layer 2's final state feeds the head
     G(score_launch_copy2d(B, H, ws + w.gru_final[1], H, ws + w.head_inp, d.Dhead, s));
-  } else if (!d.gcmc) {
+  } else if (!d.gcmc && !d.caser) {
     // RIA: final GRU states feed the head (:244-249)
     G(score_launch_copy2d(B, H, ws + w.gru_final[0], H, ws + w.head_inp, d.Dhead, s));
     G(score_launch_copy2d(B, H, ws + w.gru_final[1], H, ws + w.head_inp + H, d.Dhead, s));
@@ -1496,7 +1553,7 @@ extern "C" int score_backward(const score_config_t* cfg, const score_state_t* st
     }
   } else {
     // RIA: gradient enters through the final states only; atten_info is unused downstream (GCMC: the head kernel wrote dfinal)
-    for (int sd = 0; sd < 2; ++sd) {
+    for (int sd = 0; sd < 2 && !d.caser; ++sd) {       // (Caser: no state; dhead itself is what caser.hip reads)
       if (d.g4r) {      // GRU4Rec: the head reads layer 2's final state only; layer 1's dout comes from layer 2's backward
         if (sd == 0) continue;
         G(score_launch_copy2d(B, H, ws + w.dhead, d.Dhead, ws + w.dfinal[1], H, s));
@@ -1544,7 +1601,16 @@ extern "C" int score_backward(const score_config_t* cfg, const score_state_t* st
     if (q_on_side) G(colsum_queue_flush(&cq, ws + w.cs_part, w.cs_part_floats / 2, side->st));
     HIPTRY(hipEventRecord(side->join, side->st));
   }
-  if (d.g4r) {
+  if (d.caser) {
+    // Caser: d X into dxside[0] on the launch stream (dxside[1] carries nothing) and, beside it on the side stream -- behind the
+    // head's backward since the fork above, and behind the fill of grad_w --, the six variables' gradients, each batch sum in a
+    // fixed order; the join is recorded again behind them
+    HIPTRY(hipMemsetAsync(ws + w.dxside[1], 0, (int64_t)BT * d.I * sizeof(float), s));
+    CaserArgs a;
+    caser_args(c, gw, &a);
+    G(score_caser_bwd(a, s, side->st));
+    HIPTRY(hipEventRecord(side->join, side->st));
+  } else if (d.g4r) {
     G(g4r_grus_bwd(c, dfinal[1], &gru_bias_rows));
   } else {
     GruArgs ga;
@@ -1556,7 +1622,7 @@ extern "C" int score_backward(const score_config_t* cfg, const score_state_t* st
     G(score_gru_bwd_multi(ga, 2, s));
     gru_bias_rows = ga.bias_slab_rows;
   }
-  for (int sd = 0; sd < 2; ++sd) {
+  for (int sd = 0; sd < 2 && !d.caser; ++sd) {
     float* dxp = ws + w.dxproj[sd];
     const float* cat = wxcat(c, sd);
     G(queue_gru_side(c, &q, gw, sd, gru_bias_rows));
@@ -1586,7 +1652,7 @@ extern "C" int score_backward(const score_config_t* cfg, const score_state_t* st
                        scratch, SF, s));
     }
   }
-  if (d.Is[0] == d.Is[1] && !d.gcmc && !d.g4r) {      // both sides' d x in ONE grouped launch: 2 x 576 tiles fill 512 slots better than twice 576
+  if (d.Is[0] == d.Is[1] && !d.gcmc && !d.g4r && !d.caser) {      // both sides' d x in ONE grouped launch: 2 x 576 tiles fill 512 slots better than twice 576
     const float* Ad[2] = {ws + w.dxproj[0], ws + w.dxproj[1]};
     float* Cd[2] = {ws + w.dxside[0], ws + w.dxside[1]};
     if (panel_gemms(d, st, BT, 1)) {      // (the images were written by the forward pass, like the concatenated copies)

@@ -291,3 +291,19 @@ struct GruStackArgs {
 bool score_gru_stack_ok(int H);
 int score_gru_stack_fwd(GruStackArgs& a, hipStream_t s);
 int score_gru_stack_bwd(GruStackArgs& a, hipStream_t s);
+// caser.hip: the Caser point baseline's two one-filter convolutions (point_model.py:147-160) over X [B, T, C] (rows of stride
+// ldx).  Forward, one launch: hwin[b, p] = sum_{i < 50, c} X[b, p + i, c] Wh[i, c] + bh, h = max_p hwin (arg: its first position),
+// v[b, c] = sum_t X[b, t, c] Wv[t] + bv, v2 = v wd + bd; head row b (stride ldh) <- [h, 0, 0, 0 | v2].  Backward, two launches:
+// dX (every one of its ldx columns: zeros past C) on `s`; the six variables' gradients, summed over the batch in a fixed order,
+// on `sp` -- they read dhead, X, arg and v only, so the two may run side by side.
+#define SCORE_CASER_L 50          /* conv2d's kernel height: the reference's constant, not max_time_len */
+#define SCORE_CASER_HPAD 4        /* h's place in the head input, padded to one 16-byte group */
+struct CaserArgs {
+  int B, T, C, ldx, ldh;
+  const float* X; const float* Wh; const float* bh; const float* Wv; const float* bv; const float* wd; const float* bd;
+  float* head; float* hwin; int32_t* arg; float* v;
+  const float* dhead; float* dX;
+  float* gWh; float* gbh; float* gWv; float* gbv; float* gwd; float* gbd;
+};
+int score_caser_fwd(const CaserArgs& a, hipStream_t s);
+int score_caser_bwd(const CaserArgs& a, hipStream_t s, hipStream_t sp);

@@ -192,7 +192,7 @@ def active_slices(model, max_len):
     sample's length are masked out of the result by the model itself (dynamic_rnn's sequence_length,
     score.py:205-208; the attention mask, :182-185) and are not gathered or computed.  0 = all T."""
     T = int(model.cfg.max_time_len)
-    if not getattr(model, "skip_masked_slices", True):
+    if not getattr(model, "skip_masked_slices", True) or not getattr(model, "reads_length", True):
         return 0
     a = min(max(int(max_len), 1), T)
     return 0 if a >= T else a
@@ -201,6 +201,8 @@ def active_slices(model, max_len):
 class SCOREBASE(object):
     model_type = None
     feed_spec = SLICE_FEED
+    reads_length = True          # False: the model's graph does not use the length tensor -- every slice is computed (Caser)
+    head_pad_vars = ()           # variables whose rows 1..3 exist in the library's layout only (Caser's padded head input)
 
     def __init__(self, feature_size, eb_dim, hidden_size, max_time_len, obj_per_time_slice,
                  user_fnum, item_fnum, seed=1111, device=None):
@@ -574,12 +576,17 @@ class SCOREBASE(object):
         for e in self.entries:
             v = self._view(self.w, e)
             if e[5] == 2:
-                lim = math.sqrt(6.0 / (e[2] + e[3]))
+                lim = math.sqrt(6.0 / (e[2] - (3 if e[0] in self.head_pad_vars else 0) + e[3]))     # (TF's fan_in: without pad rows)
+                v.uniform_(-lim, lim, generator=gen)
+            elif e[5] == 3:       # glorot-uniform with TF's convolution fans: fan_in = fan_out = the receptive field, rows * cols
+                lim = math.sqrt(6.0 / (2 * e[2] * max(e[3], 1)))
                 v.uniform_(-lim, lim, generator=gen)
             elif e[5] == 1:
                 v.fill_(1.0)
             else:
                 v.zero_()
+            if e[0] in self.head_pad_vars:
+                v[1:4].zero_()    # the pad rows: zero now, and a fixed point of training from here on
 
     def _table_host(self):
         """the rows of emb_mtx this object holds, as the variable stores them (row 0 with its masked value)"""
@@ -595,17 +602,32 @@ class SCOREBASE(object):
         self.table.copy_(torch.from_numpy(emb))
         self.table[0].zero_()
 
-    def _set_dense(self, params):
+    # Where a dense variable -- or its gradient, or one of its Adam slots -- crosses the Python boundary (get_params, set_params,
+    # get_grads, save, restore), it has TF's name and TF's shape.  For most models that is the library's own shape; a model whose
+    # library layout differs (Caser) overrides this pair.
+    def _export(self, name, a):
+        """library layout -> TF's array (a: ndarray as _view shapes it)"""
+        return a
+
+    def _import(self, name, a, shape):
+        """TF's array -> float32 ndarray of the library's `shape`"""
+        return np.ascontiguousarray(np.asarray(a, dtype=np.float32).reshape(shape))
+
+    def _export_all(self, flat):
+        return {e[0]: self._export(e[0], self._view(flat, e).cpu().numpy().copy()) for e in self.entries}
+
+    def _import_all(self, flat, arrays, suffix=""):
         for e in self.entries:
-            v = self._view(self.w, e)
-            a = np.asarray(params[e[0]], dtype=np.float32).reshape(tuple(v.shape))
-            v.copy_(torch.from_numpy(a))
+            v = self._view(flat, e)
+            v.copy_(torch.from_numpy(self._import(e[0], arrays[e[0] + suffix], tuple(v.shape))))
+
+    def _set_dense(self, params):
+        self._import_all(self.w, params)
 
     def get_params(self):
         """dict TF variable name -> ndarray (emb_mtx carries its masked row 0 value)."""
         out = {"emb_mtx": self._table_host()}
-        for e in self.entries:
-            out[e[0]] = self._view(self.w, e).cpu().numpy().copy()
+        out.update(self._export_all(self.w))
         return out
 
     def set_params(self, params):
@@ -646,7 +668,7 @@ class SCOREBASE(object):
 
     def get_dense_grads(self):
         """Gradients of the dense variables only (no [N, D] host copy of the table's)."""
-        return {e[0]: self._view(self.w_g, e).cpu().numpy().copy() for e in self.entries}
+        return self._export_all(self.w_g)
 
     def get_grads(self):
         out = {"emb_mtx": self.dense_table_grad().cpu().numpy()}
@@ -1744,13 +1766,11 @@ class SCOREBASE(object):
             # powers ahead of the variables.  Raises (and takes the suppressed steps off the count) instead of writing it.
             self.check_ids()
         blob = {"emb_mtx": self._table_host()}
-        for e in self.entries:
-            blob[e[0]] = self._view(self.w, e).cpu().numpy().copy()
+        blob.update(self._export_all(self.w))
         tm, tv = self.table_m.cpu().numpy(), self.table_v.cpu().numpy()
         blob["emb_mtx/Adam"], blob["emb_mtx/Adam_1"] = tm, tv
-        for e in self.entries:
-            blob[e[0] + "/Adam"] = self._view(self.w_m, e).cpu().numpy()
-            blob[e[0] + "/Adam_1"] = self._view(self.w_v, e).cpu().numpy()
+        for flat, suffix in ((self.w_m, "/Adam"), (self.w_v, "/Adam_1")):
+            blob.update({k + suffix: a for k, a in self._export_all(flat).items()})
         blob["beta1_power"] = self.beta1_power
         blob["beta2_power"] = self.beta2_power
         blob["global_step"] = np.int64(self.step)
@@ -1763,12 +1783,11 @@ class SCOREBASE(object):
     def restore(self, sess, path):
         z = np.load(path + ".npz")
         self._table_load(z["emb_mtx"])
-        self._set_dense({e[0]: z[e[0]] for e in self.entries})
+        self._set_dense(z)
         self.table_m.copy_(torch.from_numpy(z["emb_mtx/Adam"]))
         self.table_v.copy_(torch.from_numpy(z["emb_mtx/Adam_1"]))
-        for e in self.entries:
-            self._view(self.w_m, e).copy_(torch.from_numpy(z[e[0] + "/Adam"]).view_as(self._view(self.w_m, e)))
-            self._view(self.w_v, e).copy_(torch.from_numpy(z[e[0] + "/Adam_1"]).view_as(self._view(self.w_v, e)))
+        self._import_all(self.w_m, z, "/Adam")
+        self._import_all(self.w_v, z, "/Adam_1")
         self.refresh_row_flags()
         self.beta1_power = np.float32(z["beta1_power"])
         self.beta2_power = np.float32(z["beta2_power"])
@@ -1826,5 +1845,42 @@ class GRU4Rec(SCOREBASE):
                            device=device)
 
 
+class Caser(GRU4Rec):
+    """point_models/point_model.py:140-164: the flat user history X = user_seq [B, T, Fi * D] through two one-filter convolutions
+    -- conv2d, [50, C] with VALID padding and a max over its T - 49 positions (50 is the reference's constant: max_time_len < 50
+    has no graph, ValueError), and conv2d_1, [T, 1], followed by a dense on a trailing axis of size 1 -- then [h | v2 |
+    target_item | target_user] through the same head, loss and optimizer as GRU4Rec, whose constructor, feed tuple and
+    train / eval / save / restore it shares.  hidden_size is accepted and ignored, as in the reference.  user_seq_length is
+    validated and NOT used, as in the reference: the positions the loader padded (by repeating the last item) take part in
+    both filters and get gradient, so every batch computes all T positions and skip_masked_slices has no effect.
+
+    The library holds the head input padded to a multiple of four floats, [h, 0, 0, 0 | ...]: bn1/gamma, bn1/beta and
+    fc1/kernel have three pad rows (1..3) there, zero from initialisation on.  At this boundary every variable, gradient and
+    Adam slot has TF's name and TF's shape (_export / _import)."""
+    model_type = "Caser"
+    reads_length = False
+    head_pad_vars = ("bn1/gamma", "bn1/beta", "fc1/kernel")
+    CONV_L = 50
+
+    def __init__(self, feature_size, eb_dim, hidden_size, max_time_len, user_fnum, item_fnum, seed=1111, device=None):
+        if int(max_time_len) < self.CONV_L:
+            raise ValueError("Caser: max_time_len = %d is below conv2d's kernel height %d (VALID padding: TF builds no graph)"
+                             % (int(max_time_len), self.CONV_L))
+        GRU4Rec.__init__(self, feature_size, eb_dim, hidden_size, max_time_len, user_fnum, item_fnum, seed=seed, device=device)
+
+    def _export(self, name, a):
+        if name in self.head_pad_vars:
+            return np.ascontiguousarray(np.delete(a, (1, 2, 3), axis=0))
+        if name in ("conv2d/kernel", "conv2d_1/kernel"):
+            return a.reshape(a.shape[0], -1, 1, 1)           # TF's [height, width, in, out]
+        return a
+
+    def _import(self, name, a, shape):
+        a = np.asarray(a, dtype=np.float32)
+        if name in self.head_pad_vars:
+            a = np.insert(a, (1, 1, 1), 0.0, axis=0)         # three zero rows behind row 0
+        return np.ascontiguousarray(a.reshape(shape))
+
+
 MODELS = {"SCORE": SCORE, "RIA": RIA, "RCA": RCA, "SCORE_USER": SCORE_USER, "SCORE_ITEM": SCORE_ITEM, "RRN": RRN, "GCMC": GCMC,
-          "GRU4Rec": GRU4Rec}
+          "GRU4Rec": GRU4Rec, "Caser": Caser}

@@ -1,9 +1,10 @@
-"""ms per training step (and per evaluation call) of the GRU4Rec point baseline (point_models/point_model.py:123-138) through
+"""ms per training step (and per evaluation call) of a point baseline (point_models/point_model.py:123-164: GRU4Rec, Caser) through
 the reference's train() / eval signatures, at the reference's point-model shapes (train_time_point_models.py:15-35, 353-354):
 Tmall, N = 1,529,672, D = 16, H = 32, T = 50, Fu = 3, Fi = 4,
   train100: B = 100      train200: B = 200      eval1000: forward only (eval_async), B = 1000
 each in both forms of the two stacked recurrences: "stacked" (csrc/gru_stack.hip, one kernel each way) and "composed"
 (debug_flags bit 13: one layer per launch with the projection GEMM between them -- kernels the other model types run too).
+--model Caser times the Caser baseline (form "caser": csrc/caser.hip) against GRU4Rec's stacked form, alternating, same protocol.
 Every (case, form) runs in a fresh process: `warmup` untimed steps, then `steps` timed ones over a few pre-staged device
 batches (random ids; history lengths as the loader reports them, up to 300, so most samples run all T steps), wall clock
 between two device synchronisations.  With --pairs n the two forms alternate n times.
@@ -11,6 +12,7 @@ between two device synchronisations.  With --pairs n the two forms alternate n t
     python tools/point_step_time.py                          # three cases x two forms, one JSON line each
     python tools/point_step_time.py --pairs 3                # ... three alternating pairs per case
     python tools/point_step_time.py --case train200 --form composed --steps 200 --warmup 20
+    python tools/point_step_time.py --model Caser --pairs 3  # three cases, (GRU4Rec stacked, Caser) alternating three times
     python tools/point_step_time.py --case train200 --form stacked --profile-steps 30     # no timing: a short run for a profiler
 """
 import argparse
@@ -23,18 +25,20 @@ import time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 TMALL = dict(N=1529672, D=16, H=32, T=50, Fu=3, Fi=4)
 CASES = {"train100": dict(B=100, train=True), "train200": dict(B=200, train=True), "eval1000": dict(B=1000, train=False)}
-FORMS = {"stacked": 0, "composed": 8192}
+FORMS = {"stacked": 0, "composed": 8192, "caser": 0}                    # debug_flags of a form
+FORM_MODEL = {"stacked": "GRU4Rec", "composed": "GRU4Rec", "caser": "Caser"}
+PAIRS = {"GRU4Rec": ("stacked", "composed"), "Caser": ("stacked", "caser")}     # what --model alternates
 
 
 def run_one(case, form, steps, warmup, n_batches=4, H=None):
     sys.path.insert(0, ROOT)
     import torch
-    from score_amd.model import GRU4Rec
+    from score_amd.model import MODELS
     s = dict(TMALL, **CASES[case])
     if H:
         s["H"] = H
     torch.cuda.set_device(0)
-    m = GRU4Rec(s["N"], s["D"], s["H"], s["T"], s["Fu"], s["Fi"])
+    m = MODELS[FORM_MODEL[form]](s["N"], s["D"], s["H"], s["T"], s["Fu"], s["Fi"])
     m.debug_flags = FORMS[form]
     g = torch.Generator(device="cuda").manual_seed(7)
     dev = dict(device="cuda", dtype=torch.int32, generator=g)
@@ -56,7 +60,7 @@ def run_one(case, form, steps, warmup, n_batches=4, H=None):
         step(i)
     torch.cuda.synchronize()
     ms = (time.perf_counter() - t0) * 1e3 / steps
-    return dict(model="GRU4Rec", case=case, form=form, ms_per_step=round(ms, 4), steps=steps, warmup=warmup, **s)
+    return dict(model=FORM_MODEL[form], case=case, form=form, ms_per_step=round(ms, 4), steps=steps, warmup=warmup, **s)
 
 
 def main():
@@ -65,7 +69,8 @@ def main():
     ap.add_argument("--form", choices=tuple(FORMS))
     ap.add_argument("--steps", type=int, default=200)
     ap.add_argument("--warmup", type=int, default=20)
-    ap.add_argument("--pairs", type=int, default=1, help="alternating (stacked, composed) pairs per case")
+    ap.add_argument("--model", choices=tuple(PAIRS), default="GRU4Rec", help="the model whose two forms (Caser: GRU4Rec stacked and Caser) alternate")
+    ap.add_argument("--pairs", type=int, default=1, help="alternating pairs per case")
     ap.add_argument("--hidden", type=int, default=0, help="another hidden size than the reference's 32")
     ap.add_argument("--profile-steps", type=int, default=0, help="run this many steps after the warm-up and print nothing timed")
     ap.add_argument("--timeout", type=int, default=240, help="seconds per fresh process")
@@ -77,9 +82,10 @@ def main():
         print(json.dumps(r), flush=True)
         return
     for case in (a.case,) if a.case else tuple(CASES):
+        first, second = PAIRS[a.model]
         res = {f: [] for f in FORMS}
         for _ in range(a.pairs):
-            for form in (a.form,) if a.form else tuple(FORMS):
+            for form in (a.form,) if a.form else (first, second):
                 p = subprocess.run([sys.executable, os.path.abspath(__file__), "--case", case, "--form", form, "--steps", str(a.steps),
                                     "--warmup", str(a.warmup), "--hidden", str(a.hidden)], capture_output=True, text=True,
                                    timeout=a.timeout)
@@ -89,10 +95,10 @@ def main():
                 r = json.loads(p.stdout.strip().splitlines()[-1])
                 res[form].append(r["ms_per_step"])
                 print(json.dumps(r), flush=True)
-        if res["stacked"] and res["composed"]:
-            print("%s: stacked %s ms, composed %s ms; stacked faster in %d of %d pairs"
-                  % (case, res["stacked"], res["composed"], sum(x < y for x, y in zip(res["stacked"], res["composed"])),
-                     len(res["stacked"])), flush=True)
+        if res[first] and res[second]:
+            print("%s: %s %s ms, %s %s ms; %s faster in %d of %d pairs"
+                  % (case, first, res[first], second, res[second], first, sum(x < y for x, y in zip(res[first], res[second])),
+                     len(res[first])), flush=True)
 
 
 if __name__ == "__main__":
