@@ -97,7 +97,24 @@ enum { SCORE_MODEL_SCORE = 0, SCORE_MODEL_RIA = 1, SCORE_MODEL_RCA = 2,
         * dense/kernel [1, 1].  Workspace fields (score_workspace_field): caser_hwin [B, T - 49] the window sums + bias,
         * caser_arg [B] (int32) the first position of the maximum, caser_v [B, C] v before the scalar dense.  Kernels:
         * csrc/caser.hip. */
-       SCORE_MODEL_CASER = 8 };
+       SCORE_MODEL_CASER = 8,
+       /* point_models/point_model.py:200-249 (DELF) on PointBaseModel (:9-63): two histories -- user_seq [B, T, Fi] (the items of
+        * the target user) and item_seq [B, T, Fu] (the users of the target item), each with its own length -- through a masked,
+        * target-conditioned attention: key_t = tanh(X_t W + b) (dense [Ci, Ci] on user_seq, dense_1 [Cu, Cu] on item_seq; Ci =
+        * item_fnum * eb_dim, Cu = user_fnum * eb_dim), s_t = <q, key_t> for t < length and -2^32 + 1 past it, a = softmax_t(s),
+        * rep = sum_t a_t X_t (the value is X, not the key); q = target_item for user_seq (-> ru) and target_user for item_seq
+        * (-> ri).  Then four fusion MLPs relu(relu(. A + a) B + b), 10 and 4 wide, over [tu|ti], [ru|ri], [tu|ri], [ti|ru]
+        * (dense_2 .. dense_9), their sum f, y = sigmoid(f w + c) (dense_10), log-loss, and the L2 filter over all eleven kernels.
+        * No bn1 / fc head, no dropout (keep_prob has no effect), hidden_size accepted and ignored, obj_per_time_slice must be 1,
+        * Ci and Cu <= 128 (SCORE_E_SHAPE beyond).  The batch: user_1hop = user_seq as [B, T, 1, Fi], item_1hop = item_seq as
+        * [B, T, 1, Fu], user_2hop / item_2hop zeros, length = user_seq_length, length2 = item_seq_length; a length >= T means all
+        * T positions, a length <= 0 masks every position (then a = 1 / T over all T: tf.sequence_mask + softmax).  active_slices =
+        * A promises BOTH lengths <= A (and no length <= 0, whose sample reads all T rows).  Workspace fields
+        * (score_workspace_field, each a per-side pair): delf_key [B*T, C] tanh keys (live rows), delf_att [B, T] attention weights,
+        * delf_rep [B, C] ru / ri, delf_ds [B, T] and delf_dpre [B*T, C] the gradients at the scores and at tanh's argument;
+        * delf_act / delf_dact [B, 64]: [h1 (4 x 10) | h2 (4 x 4) | f (4) | pad] and the pre-activation gradients.  Kernels:
+        * csrc/delf.hip, one launch each way. */
+       SCORE_MODEL_DELF = 9 };
 
 /* Constructor arguments of SCOREBASE.__init__ (score.py:12-13). */
 typedef struct {
@@ -105,7 +122,7 @@ typedef struct {
   int32_t eb_dim;              /* D: multiple of 4, <= 256                        */
   int32_t hidden_size;         /* H                                               */
   int32_t max_time_len;        /* T                                               */
-  int32_t obj_per_time_slice;  /* K <= 32 (SCORE_MODEL_GRU4REC / _CASER: 1)        */
+  int32_t obj_per_time_slice;  /* K <= 32 (SCORE_MODEL_GRU4REC / _CASER / _DELF: 1) */
   int32_t user_fnum;           /* Fu                                              */
   int32_t item_fnum;           /* Fi                                              */
   int32_t model_type;          /* SCORE_MODEL_*                                   */
@@ -147,6 +164,8 @@ typedef struct {
                                   weight (:182-185), so loss, predictions and every gradient are
                                   unchanged; samples with length[b] > A are treated as length A.
                                   The index tensors keep their [B,T,K,F] strides.                   */
+  const int32_t* length2;      /* [B] SCORE_MODEL_DELF only: item_seq_length, the mask of item_1hop's T positions (length is
+                                  user_seq_length, the mask of user_1hop's).  NULL for every other model type: none reads it. */
 } score_batch_t;
 
 /* Named float offsets into the workspace (for tests / introspection). */

@@ -10,7 +10,7 @@ import os
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "lib", "libscore_hip.so")
 
-MODEL_TYPES = {"SCORE": 0, "RIA": 1, "RCA": 2, "SCORE_USER": 3, "SCORE_ITEM": 4, "RRN": 5, "GCMC": 6, "GRU4Rec": 7, "Caser": 8}
+MODEL_TYPES = {"SCORE": 0, "RIA": 1, "RCA": 2, "SCORE_USER": 3, "SCORE_ITEM": 4, "RRN": 5, "GCMC": 6, "GRU4Rec": 7, "Caser": 8, "DELF": 9}
 
 c_f = C.c_void_p   # device float*
 c_i = C.c_void_p   # device int32*
@@ -30,7 +30,7 @@ class ParamEntry(C.Structure):
 class Batch(C.Structure):
     _fields_ = [("user_1hop", c_i), ("user_2hop", c_i), ("item_1hop", c_i), ("item_2hop", c_i),
                 ("target_user", c_i), ("target_item", c_i), ("label", c_i), ("length", c_i),
-                ("B", C.c_int32), ("active_slices", C.c_int32)]
+                ("B", C.c_int32), ("active_slices", C.c_int32), ("length2", c_i)]     # (length2: DELF's item_seq_length; NULL otherwise)
 
 
 class Workspace(C.Structure):

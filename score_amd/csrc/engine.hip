@@ -1,7 +1,7 @@
 // Whole-path orchestration: parameter/workspace layout and the forward / backward
 // launch sequences of SCORE and its ablations (score.py:188-369) and of the slice baselines RRN and GCMC
-// (slice_model.py:155-203) and of the point baselines GRU4Rec and Caser (point_model.py:123-164) on one stream.  Host code only;
-// every kernel lives in embed/gemm/gru/gru_stack/head/gcmc/caser.hip.
+// (slice_model.py:155-203) and of the point baselines GRU4Rec, Caser and DELF (point_model.py:123-164, 200-249) on one stream.
+// Host code only; every kernel lives in embed/gemm/gru/gru_stack/head/gcmc/caser/delf.hip.
 #include <string.h>
 #include <stdlib.h>
 #include <stdio.h>
@@ -25,6 +25,7 @@ struct Dims {
   bool coattn, attn, gcmc;
   bool g4r;        // GRU4Rec: "side" 0 is layer 1 (input: the gathered user_seq rows, Di wide), "side" 1 layer 2 (input: layer 1's outputs, H wide)
   bool caser;      // Caser: no recurrence at all (H = 0 here, whatever the config says); C = Di columns of xside[0] are its X
+  bool delf;       // DELF: no recurrence and no bn1 / fc head (H = 0 here); X of side 0 = Di columns of xside[0], of side 1 = Du columns of xside[1]
   int Ic;          // row capacity of a side's block of the concatenated [Wx_gates | Wx_cand] copy: I (GRU4Rec: max(I, H))
   int off_u, off_i, off_ti, off_tu;  // columns of head_inp
 };
@@ -34,19 +35,24 @@ int make_dims(const score_config_t* c, Dims* d) {
   d->N = c->feature_size; d->D = c->eb_dim; d->H = c->hidden_size; d->T = c->max_time_len;
   d->K = c->obj_per_time_slice; d->Fu = c->user_fnum; d->Fi = c->item_fnum; d->mt = c->model_type;
   if (d->N <= 0 || d->D <= 0 || (d->D & 3) || d->D > 256 || d->H <= 0 || d->T <= 0 || d->K <= 0 || d->K > 32 ||
-      d->Fu <= 0 || d->Fi <= 0 || d->mt < 0 || d->mt > SCORE_MODEL_CASER)
+      d->Fu <= 0 || d->Fi <= 0 || d->mt < 0 || d->mt > SCORE_MODEL_DELF)
     return SCORE_E_SHAPE;
   d->Du = d->Fu * d->D; d->Di = d->Fi * d->D; d->I = d->Di + d->Du; d->Dq = d->Du + d->Di;
   d->gcmc = d->mt == SCORE_MODEL_GCMC;
   d->g4r = d->mt == SCORE_MODEL_GRU4REC;
   d->caser = d->mt == SCORE_MODEL_CASER;
-  if ((d->g4r || d->caser) && d->K != 1) return SCORE_E_SHAPE;      // (user_seq rides as a [B, T, 1, Fi] set)
+  d->delf = d->mt == SCORE_MODEL_DELF;
+  if ((d->g4r || d->caser || d->delf) && d->K != 1) return SCORE_E_SHAPE;      // (user_seq rides as a [B, T, 1, Fi] set)
+  if (d->delf) {
+    if (d->Di > SCORE_DELF_CMAX || d->Du > SCORE_DELF_CMAX) return SCORE_E_SHAPE;      // (the widths delf.hip covers)
+    d->H = 0;                                                 // hidden_size: accepted and ignored, as for Caser
+  }
   if (d->caser) {
     if (d->T < CASER_L) return SCORE_E_SHAPE;                 // (conv2d's VALID window, point_model.py:147: TF refuses the graph)
     d->H = 0;                                                 // hidden_size: accepted and ignored -- no GRU variable, workspace or launch
   }
   // (GCMC starts from RRN's two 1-hop sums, slice_model.py:184-187; GRU4Rec's user_seq rows are RRN's "sum" over a one-element set)
-  const bool rrn = d->mt == SCORE_MODEL_RRN || d->gcmc || d->g4r || d->caser;
+  const bool rrn = d->mt == SCORE_MODEL_RRN || d->gcmc || d->g4r || d->caser || d->delf;
   d->coattn = d->mt != SCORE_MODEL_RCA && !rrn;
   d->attn = d->mt != SCORE_MODEL_RIA && !rrn;
   d->NI = (d->mt == SCORE_MODEL_RCA || d->mt == SCORE_MODEL_RIA || rrn) ? 0 : 4 * d->K;
@@ -56,7 +62,7 @@ int make_dims(const score_config_t* c, Dims* d) {
   d->Ic = d->g4r && d->H > d->I ? d->H : d->I;
   if (d->gcmc && d->H > 256) return SCORE_E_SHAPE;            // (its head kernels, gcmc.hip)
   d->Dk = d->attn ? 2 * d->H + d->NI : 0;
-  d->nstate = d->caser ? 0 : (d->mt == SCORE_MODEL_SCORE_USER || d->mt == SCORE_MODEL_SCORE_ITEM || d->g4r) ? 1 : 2;
+  d->nstate = (d->caser || d->delf) ? 0 : (d->mt == SCORE_MODEL_SCORE_USER || d->mt == SCORE_MODEL_SCORE_ITEM || d->g4r) ? 1 : 2;
   d->Dhead = d->nstate * d->H + d->Di + d->Du;
   d->off_u = d->mt == SCORE_MODEL_SCORE_ITEM ? -1 : 0;       // (GRU4Rec: layer 2's final state sits where SCORE_USER's state does)
   d->off_i = d->mt == SCORE_MODEL_SCORE_USER ? -1 : (d->mt == SCORE_MODEL_SCORE_ITEM ? 0 : d->H);
@@ -94,6 +100,7 @@ struct Params {  // float offsets into the flat buffer
   int64_t bn_g, bn_b, fc_w[3], fc_b[3];
   int64_t gm_a[2], gm_c[2], gm_4, gm_5;  // GCMC: per side dense (Wa) and dense_2 / dense_3 (Wc); the head's dense_4, dense_5
   int64_t cs_wh, cs_bh, cs_wv, cs_bv, cs_wd, cs_bd;  // Caser: conv2d (horizontal), conv2d_1 (vertical), dense (the scalar one)
+  int64_t dl_w[11], dl_b[11];           // DELF: dense .. dense_10, kernels and biases
   int64_t n_floats, n_reg;
 };
 
@@ -130,7 +137,14 @@ int build_layout_raw(const Dims& d, score_param_entry_t* out, int max_entries, P
     add("conv2d_1/kernel", d.T, 1, 1, 3); add("conv2d_1/bias", 1, 0, 0, 0);
     dense(1, 1);
   }
-  for (int s = 0; s < 2 && !d.caser; ++s) {
+  // DELF (point_model.py:216-232, 235-249): the two attention denses, four fusion MLPs (10, 4), the output unit
+  if (d.delf) {
+    dense(d.Di, d.Di); dense(d.Du, d.Du);
+    const int in[4] = {d.Du + d.Di, d.Di + d.Du, 2 * d.Du, 2 * d.Di};      // [tu|ti], [ru|ri], [tu|ri], [ti|ru]
+    for (int k = 0; k < 4; ++k) { dense(in[k], 10); dense(10, 4); }
+    dense(4, 1);
+  }
+  for (int s = 0; s < 2 && !d.caser && !d.delf; ++s) {
     char b[64];
     snprintf(b, 64, "%s/gru_cell/gates/kernel", sides[s]); add(b, d.Is[s] + d.H, 2 * d.H, 1, 2);
     snprintf(b, 64, "%s/gru_cell/gates/bias", sides[s]); add(b, 2 * d.H, 0, 0, 1);
@@ -140,7 +154,7 @@ int build_layout_raw(const Dims& d, score_param_entry_t* out, int max_entries, P
   if (d.attn) { dense(d.Dq, d.Dk); dense(4 * d.Dk, AT1); dense(AT1, AT2); dense(AT2, 1); }
   if (d.gcmc) {
     add("dense_4/kernel", d.H, d.H, 1, 2); add("dense_5/kernel", d.H, d.H, 1, 2);
-  } else {
+  } else if (!d.delf) {
     add("bn1/gamma", d.Dhead, 0, 1, 1);
     add("bn1/beta", d.Dhead, 0, 1, 0);
     add("fc1/kernel", d.Dhead, FC1, 1, 2); add("fc1/bias", FC1, 0, 0, 0);
@@ -171,6 +185,13 @@ int build_layout_raw(const Dims& d, score_param_entry_t* out, int max_entries, P
     }
   }
   int i = 0;
+  if (d.delf) {       // (nothing else: no recurrence, no bn1 / fc head)
+    for (int k = 0; k < 11; ++k) { P->dl_w[k] = off[i++]; P->dl_b[k] = off[i++]; }
+    for (int s = 0; s < 2; ++s) P->gk[s] = P->gb[s] = P->ck[s] = P->cb[s] = 0;
+    P->bn_g = P->bn_b = 0;
+    for (int f = 0; f < 3; ++f) P->fc_w[f] = P->fc_b[f] = 0;
+    return n;
+  }
   if (d.coattn) { for (int c = 0; c < 2; ++c) { P->ca_w[c] = off[i++]; P->ca_b[c] = off[i++]; } }
   if (d.gcmc) { P->gm_a[0] = off[i++]; P->gm_a[1] = off[i++]; P->gm_c[0] = off[i++]; P->gm_c[1] = off[i++]; }
   if (d.caser) {
@@ -241,6 +262,9 @@ struct WS {
   // Caser only (-1 otherwise): the window sums [B, T - 49], the first position of their maximum [B] (int32), v before the scalar
   // dense [B, C]
   int64_t caser_hwin, caser_arg, caser_v;
+  // DELF only (-1 otherwise), per side: tanh keys [B*T, C], attention weights [B, T], attention outputs [B, C], the gradient at
+  // the scores [B, T] and at the keys' pre-activations [B*T, C]; the fusion layers' activations and their gradients [B, 64]
+  int64_t delf_key[2], delf_att[2], delf_rep[2], delf_ds[2], delf_dpre[2], delf_act, delf_dact;
   int64_t scratch_floats, total;
 };
 
@@ -375,6 +399,17 @@ void build_ws_raw(const Dims& d, int B, WS* w) {
     w->caser_hwin = take((int64_t)B * (d.T - CASER_L + 1)); w->caser_arg = take(B); w->caser_v = take((int64_t)B * d.Di);
   } else {
     w->caser_hwin = w->caser_arg = w->caser_v = -1;
+  }
+  if (d.delf) {
+    const int Cx[2] = {d.Di, d.Du};
+    for (int s = 0; s < 2; ++s) {
+      w->delf_key[s] = take(BT * Cx[s]); w->delf_att[s] = take(BT); w->delf_rep[s] = take((int64_t)B * Cx[s]);
+      w->delf_ds[s] = take(BT); w->delf_dpre[s] = take(BT * Cx[s]);
+    }
+    w->delf_act = take((int64_t)B * SCORE_DELF_ACT); w->delf_dact = take((int64_t)B * SCORE_DELF_ACT);
+  } else {
+    for (int s = 0; s < 2; ++s) w->delf_key[s] = w->delf_att[s] = w->delf_rep[s] = w->delf_ds[s] = w->delf_dpre[s] = -1;
+    w->delf_act = w->delf_dact = -1;
   }
   w->total = cur;
 }
@@ -680,6 +715,33 @@ static void caser_args(const Pass& c, float* gw, CaserArgs* a) {
   }
 }
 
+// ---------------------------------------------------------------- DELF (point_model.py:200-249, delf.hip)
+// Side 0: X = the gathered user_seq rows (columns [0, Di) of xside[0]) against target_item through dense; side 1: the item_seq
+// rows (columns [0, Du) of xside[1]) against target_user through dense_1, masked by score_batch_t.length2.  The backward kernel
+// writes every column of both dxside and the target rows' gradients into dhead ([d target_item | d target_user])
+static void delf_args(const Pass& c, DelfArgs* a) {
+  const Dims& d = c.d; const Params& P = c.P; const WS& w = c.w; float* ws = c.ws; const float* W = c.W;
+  memset(a, 0, sizeof(*a));
+  a->B = c.B; a->T = c.T; a->Cu = d.Du; a->Ci = d.Di; a->ldq = d.Dq; a->ldh = d.Dhead; a->off_ti = d.off_ti; a->off_tu = d.off_tu;
+  a->Bglobal = c.Bg;
+  const int Cx[2] = {d.Di, d.Du};
+  const int32_t* len[2] = {c.bt->length, c.bt->length2};
+  for (int s = 0; s < 2; ++s) {
+    DelfSide& S = a->s[s];
+    S.X = ws + w.xside[s]; S.ldx = d.I; S.C = Cx[s]; S.W = W + P.dl_w[s]; S.b = W + P.dl_b[s]; S.len = len[s];
+    S.key = ws + w.delf_key[s]; S.att = ws + w.delf_att[s]; S.rep = ws + w.delf_rep[s]; S.ds = ws + w.delf_ds[s];
+    S.dX = ws + w.dxside[s]; S.dpre = ws + w.delf_dpre[s];
+  }
+  a->tu = ws + w.query; a->ti = ws + w.query + d.Du;       // [target_user | target_item] (score_launch_target_fwd)
+  for (int k = 0; k < 4; ++k) {
+    a->A[k] = W + P.dl_w[2 + 2 * k]; a->a1[k] = W + P.dl_b[2 + 2 * k];
+    a->Bm[k] = W + P.dl_w[3 + 2 * k]; a->b2[k] = W + P.dl_b[3 + 2 * k];
+  }
+  a->w = W + P.dl_w[10]; a->c = W + P.dl_b[10];
+  a->label = c.bt->label;
+  a->act = ws + w.delf_act; a->dact = ws + w.delf_dact; a->logit = ws + w.logit; a->y = ws + w.y_pred; a->lossb = ws + w.lossb;
+  a->dlogit = ws + w.dlogit; a->dhead = ws + w.dhead;
+}
 // ---------------------------------------------------------------- the two co-attention calls
 // 1: (user_1hop, item_2hop, target_item) ; 2: (user_2hop, item_1hop, target_user)  (score.py:196-197)
 // user_side = [user_1hop_seq | user_2hop_seq], item_side = [item_1hop_seq | item_2hop_seq]   (:200-201)
@@ -843,6 +905,36 @@ static int queue_gru_side(const Pass& c, GradQueues* q, float* gw, int sd, int b
   return 0;
 }
 
+// the 22 variables' gradients as queued X^T dY products and column sums of what the backward kernel left: dense / dense_1
+// over the B * T rows of a side (masked rows: zero dpre), the fusion kernels over the B samples -- a kernel's rows in the two
+// blocks its input is concatenated from
+static int queue_delf(const Pass& c, GradQueues* q, float* gw) {
+  const Dims& d = c.d; const Params& P = c.P; const WS& w = c.w; float* ws = c.ws; const int B = c.B, BT = c.BT;
+  const int Cx[2] = {d.Di, d.Du};
+  for (int s = 0; s < 2; ++s) {
+    G(gemm_queue_add(&q->gq, Cx[s], Cx[s], BT, ws + w.xside[s], d.I, ws + w.delf_dpre[s], Cx[s], gw + P.dl_w[s], Cx[s]));
+    G(colsum_queue_add(&q->cq, ws + w.delf_dpre[s], BT, Cx[s], Cx[s], gw + P.dl_b[s], 0));
+  }
+  const float* tu = ws + w.query; const float* ti = ws + w.query + d.Du;
+  const float* ru = ws + w.delf_rep[0]; const float* ri = ws + w.delf_rep[1];
+  const float* act = ws + w.delf_act; const float* dact = ws + w.delf_dact;
+  const int LA = SCORE_DELF_ACT;
+  // fusion input k = [first | second]: 0 [tu|ti], 1 [ru|ri], 2 [tu|ri], 3 [ti|ru]
+  const float* first[4] = {tu, ru, tu, ti}; const int ld1[4] = {d.Dq, d.Di, d.Dq, d.Dq}; const int n1[4] = {d.Du, d.Di, d.Du, d.Di};
+  const float* second[4] = {ti, ri, ri, ru}; const int ld2[4] = {d.Dq, d.Du, d.Du, d.Di}; const int n2[4] = {d.Di, d.Du, d.Du, d.Di};
+  for (int k = 0; k < 4; ++k) {
+    float* gA = gw + P.dl_w[2 + 2 * k];
+    G(gemm_queue_add(&q->gq, n1[k], 10, B, first[k], ld1[k], dact + 10 * k, LA, gA, 10));
+    G(gemm_queue_add(&q->gq, n2[k], 10, B, second[k], ld2[k], dact + 10 * k, LA, gA + (int64_t)n1[k] * 10, 10));
+    G(colsum_queue_add(&q->cq, dact + 10 * k, B, 10, LA, gw + P.dl_b[2 + 2 * k], 0));
+    G(gemm_queue_add(&q->gq, 10, 4, B, act + 10 * k, LA, dact + 40 + 4 * k, LA, gw + P.dl_w[3 + 2 * k], 4));
+    G(colsum_queue_add(&q->cq, dact + 40 + 4 * k, B, 4, LA, gw + P.dl_b[3 + 2 * k], 0));
+  }
+  G(gemm_queue_add(&q->gq, 4, 1, B, act + 56, LA, ws + w.dlogit, 1, gw + P.dl_w[10], 1));
+  G(colsum_queue_add(&q->cq, ws + w.dlogit, B, 1, 1, gw + P.dl_b[10], 0));
+  return 0;
+}
+
 }  // namespace
 
 extern "C" int score_context_create(void** ctx) {
@@ -932,7 +1024,9 @@ extern "C" int score_workspace_field(const score_config_t* cfg, int32_t B, const
       {"gcmc_a", w.gcmc_a[0], w.gcmc_a[1]}, {"gcmc_z", w.gcmc_z[0], w.gcmc_z[1]}, {"gcmc_dz", w.gcmc_dz[0], w.gcmc_dz[1]},
       {"gcmc_da", w.gcmc_da[0], w.gcmc_da[1]}, {"gcmc_pn", w.gcmc_pn, w.gcmc_pn + (int64_t)B * d.H}, {"gcmc_g", w.gcmc_g, -1},
       {"gcmc_gu", w.gcmc_gu, w.gcmc_gu + (int64_t)B * d.H}, {"caser_hwin", w.caser_hwin, -1}, {"caser_arg", w.caser_arg, -1},
-      {"caser_v", w.caser_v, -1}};
+      {"caser_v", w.caser_v, -1}, {"delf_key", w.delf_key[0], w.delf_key[1]}, {"delf_att", w.delf_att[0], w.delf_att[1]},
+      {"delf_rep", w.delf_rep[0], w.delf_rep[1]}, {"delf_ds", w.delf_ds[0], w.delf_ds[1]},
+      {"delf_dpre", w.delf_dpre[0], w.delf_dpre[1]}, {"delf_act", w.delf_act, -1}, {"delf_dact", w.delf_dact, -1}};
   for (auto& e : tab)
     if (strcmp(e.n, name) == 0) {
       if (e.a < 0) return SCORE_E_BADARG;       // (a region of another model type)
@@ -1012,7 +1106,7 @@ extern "C" int score_index_plan(const score_config_t* cfg, const score_state_t* 
 // streams' work is small beside these products: 20.3 -> 19.8 ms/step with both.
 static bool panel_gemms(const Dims& d, const score_state_t* st, int BT, int which) {
   const Flags fl = flags_of(st);
-  if (st->gemm_mode != 1 || fl.no_panel || d.Is[0] != d.Is[1] || d.g4r || d.caser) return false;
+  if (st->gemm_mode != 1 || fl.no_panel || d.Is[0] != d.Is[1] || d.g4r || d.caser || d.delf) return false;
   if (which == 1 && d.gcmc) return false;      // (GCMC's input gradients take Z's relu mask in the epilogue: the tiled kernels)
   const int ns = panel_x_splits(d.H), nd = panel_d_splits(d.Is[0]);
   return which == 0 ? ns > 0 && score_gemm_panel_ok(2 * ns, BT, 3 * d.H / ns, d.Is[0], x_ld(d, 0), 3 * d.H, nullptr)
@@ -1249,6 +1343,7 @@ extern "C" int score_forward(const score_config_t* cfg, const score_state_t* st,
   if (!bt->user_1hop || !bt->user_2hop || !bt->item_1hop || !bt->item_2hop || !bt->target_user ||
       !bt->target_item || !bt->label || !bt->length)
     return SCORE_E_BADARG;
+  if (c.d.delf && !bt->length2) return SCORE_E_BADARG;        // (item_seq_length: the one model type that reads it)
   if (!(keep_prob > 0.f) || keep_prob > 1.f) return SCORE_E_BADARG;
   SCORE_TRY(pass_fill(&c, st, bt, stream));
   const Dims& d = c.d; const Params& P = c.P; const WS& w = c.w; const Flags& fl = c.fl;
@@ -1320,6 +1415,19 @@ extern "C" int score_forward(const score_config_t* cfg, const score_state_t* st,
                        nullptr, 0, scratch, w.scratch_floats, s));
       xin[sd] = ws + w.gcmc_z[sd];
     }
+  }
+  if (d.delf) {
+    // DELF: both attentions, the fusion MLPs, y and the loss terms in ONE launch behind the gather (the target rows come from
+    // the side stream); no dropout, keep_prob has no effect
+    HIPTRY(hipStreamWaitEvent(s, sd->join, 0));
+    DelfArgs a;
+    delf_args(c, &a);
+    G(score_delf_fwd(a, s));
+    EV(2);
+    EV(3);
+    G(loss_tail(c, sd, reg_lambda));
+    EV(4);
+    return 0;
   }
   // GRUs (:205-208): hoisted x-projection, then the persistent recurrence
   if (d.caser) {
@@ -1445,6 +1553,7 @@ extern "C" int score_backward(const score_config_t* cfg, const score_state_t* st
   SCORE_TRY(make_dims(cfg, &c.d));
   if (!st || !bt || !st->table || !st->w || !st->workspace || !gw || !grad_table || bt->B <= 0)
     return SCORE_E_BADARG;
+  if (c.d.delf && (!bt->length || !bt->length2)) return SCORE_E_BADARG;
   SCORE_TRY(pass_fill(&c, st, bt, stream));
   const Dims& d = c.d; const Params& P = c.P; const WS& w = c.w; const Flags& fl = c.fl;
   const int B = c.B, T = c.T, H = c.H, BT = c.BT, x3 = c.x3;
@@ -1474,7 +1583,15 @@ extern "C" int score_backward(const score_config_t* cfg, const score_state_t* st
   HIPTRY(hipMemsetAsync(gw, 0, P.n_floats * sizeof(float), side->st));
 
   EV(0);
-  if (d.gcmc) {
+  if (d.delf) {
+    // ---- DELF: the whole backward of the model between the scatter and the loss in ONE launch (delf.hip): dxside, dhead's
+    // target columns, and the rows the queued products and column sums below are taken from -- those run on the side stream,
+    // forked behind this launch, beside the target rows' and the embedding rows' scatter
+    DelfArgs a;
+    delf_args(c, &a);
+    G(score_delf_bwd(a, s));
+    G(queue_delf(c, &q, gw));
+  } else if (d.gcmc) {
     // ---- GCMC's head (slice_model.py:199-201): dh_u, dh_i into dfinal, and the rows +-g h_u whose products with h_i are
     // dW4 / dW5 (gcmc.hip)
     G(score_launch_gcmc_head_bwd(B, H, ws + w.gru_final[0], W + P.gm_4, W + P.gm_5, ws + w.gcmc_pn, ws + w.gcmc_pn + (int64_t)B * H,
@@ -1553,7 +1670,7 @@ extern "C" int score_backward(const score_config_t* cfg, const score_state_t* st
     }
   } else {
     // RIA: gradient enters through the final states only; atten_info is unused downstream (GCMC: the head kernel wrote dfinal)
-    for (int sd = 0; sd < 2 && !d.caser; ++sd) {       // (Caser: no state; dhead itself is what caser.hip reads)
+    for (int sd = 0; sd < 2 && !d.caser && !d.delf; ++sd) {       // (Caser, DELF: no state; dhead itself is what caser.hip reads / delf.hip writes)
       if (d.g4r) {      // GRU4Rec: the head reads layer 2's final state only; layer 1's dout comes from layer 2's backward
         if (sd == 0) continue;
         G(score_launch_copy2d(B, H, ws + w.dhead, d.Dhead, ws + w.dfinal[1], H, s));
@@ -1601,7 +1718,9 @@ extern "C" int score_backward(const score_config_t* cfg, const score_state_t* st
     if (q_on_side) G(colsum_queue_flush(&cq, ws + w.cs_part, w.cs_part_floats / 2, side->st));
     HIPTRY(hipEventRecord(side->join, side->st));
   }
-  if (d.caser) {
+  if (d.delf) {
+    // (DELF: no recurrence; delf.hip wrote both dxside above)
+  } else if (d.caser) {
     // Caser: d X into dxside[0] on the launch stream (dxside[1] carries nothing) and, beside it on the side stream -- behind the
     // head's backward since the fork above, and behind the fill of grad_w --, the six variables' gradients, each batch sum in a
     // fixed order; the join is recorded again behind them
@@ -1622,7 +1741,7 @@ extern "C" int score_backward(const score_config_t* cfg, const score_state_t* st
     G(score_gru_bwd_multi(ga, 2, s));
     gru_bias_rows = ga.bias_slab_rows;
   }
-  for (int sd = 0; sd < 2 && !d.caser; ++sd) {
+  for (int sd = 0; sd < 2 && !d.caser && !d.delf; ++sd) {
     float* dxp = ws + w.dxproj[sd];
     const float* cat = wxcat(c, sd);
     G(queue_gru_side(c, &q, gw, sd, gru_bias_rows));
@@ -1652,7 +1771,7 @@ extern "C" int score_backward(const score_config_t* cfg, const score_state_t* st
                        scratch, SF, s));
     }
   }
-  if (d.Is[0] == d.Is[1] && !d.gcmc && !d.g4r && !d.caser) {      // both sides' d x in ONE grouped launch: 2 x 576 tiles fill 512 slots better than twice 576
+  if (d.Is[0] == d.Is[1] && !d.gcmc && !d.g4r && !d.caser && !d.delf) {      // both sides' d x in ONE grouped launch: 2 x 576 tiles fill 512 slots better than twice 576
     const float* Ad[2] = {ws + w.dxproj[0], ws + w.dxproj[1]};
     float* Cd[2] = {ws + w.dxside[0], ws + w.dxside[1]};
     if (panel_gemms(d, st, BT, 1)) {      // (the images were written by the forward pass, like the concatenated copies)

@@ -307,3 +307,27 @@ struct CaserArgs {
 };
 int score_caser_fwd(const CaserArgs& a, hipStream_t s);
 int score_caser_bwd(const CaserArgs& a, hipStream_t s, hipStream_t sp);
+// delf.hip: the DELF point baseline (point_model.py:200-249) between the gather and the scatter.  Per side (0: user_seq rows
+// against target_item through dense; 1: item_seq rows against target_user through dense_1) X [B * T, C] with row stride ldx,
+// the saved keys [B * T, C] (live rows only), attention weights att [B, T], rep [B, C]; backward: ds [B, T] (gradient at the
+// scores), dX (every one of the ldx columns written) and dpre [B * T, C] (gradient at tanh's argument; zero rows past the
+// length).  act [B, SCORE_DELF_ACT] = [h1 of the four fusion MLPs (40) | h2 (16) | f (4) | pad], dact the same layout with the
+// gradients at the pre-activations (f's slots unused).  tu / ti: the gathered target rows (row stride ldq); dhead (stride ldh)
+// receives d target_item at off_ti and d target_user at off_tu.  One launch each way, a workgroup per sample.
+#define SCORE_DELF_CMAX 128       /* widest Fu * D / Fi * D the kernels cover */
+#define SCORE_DELF_ACT 64
+struct DelfSide {
+  const float* X; const float* W; const float* b; const int32_t* len;
+  float* key; float* att; float* rep; float* ds; float* dX; float* dpre;
+  int C, ldx;
+};
+struct DelfArgs {
+  DelfSide s[2];
+  const float* tu; const float* ti;
+  const float* A[4]; const float* a1[4]; const float* Bm[4]; const float* b2[4]; const float* w; const float* c;
+  const int32_t* label;
+  float* act; float* dact; float* logit; float* y; float* lossb; float* dlogit; float* dhead;
+  int B, T, Cu, Ci, ldq, ldh, off_ti, off_tu, Bglobal;
+};
+int score_delf_fwd(const DelfArgs& a, hipStream_t s);
+int score_delf_bwd(const DelfArgs& a, hipStream_t s);

@@ -62,13 +62,19 @@ def batch_shapes(cfg, B):
 class FeedSpec(object):
     """How a model's feed tuple fills the eight tensors of score_batch_t.  slots[i] = (position in the feed tuple or None,
     the field's name there, its shape there as a function of (cfg, B)) for tensor i of BATCH_FIELDS; a tensor without a
-    source is zero-filled (ids of the masked row 0: no arithmetic, no gradient).  `what` names the tuple in error messages."""
+    source is zero-filled (ids of the masked row 0: no arithmetic, no gradient).  `what` names the tuple in error messages.
+    A ninth slot, where a spec names one, is score_batch_t.length2 [B] (DUAL_FEED: item_seq_length); the device batch of such
+    a model carries it as a ninth tensor behind the eight, in the same flat allocation -- every other model's is unchanged."""
 
     def __init__(self, n, what, slots):
         self.n, self.what, self.slots = n, what, slots
 
+    def device_shapes(self, cfg, B):
+        """shapes of the device tensors of a batch: the library's eight, and [B] for a ninth slot"""
+        return tuple(batch_shapes(cfg, B)) + ((B,),) * (len(self.slots) - 8)
+
     def shapes(self, cfg, B):
-        lib = batch_shapes(cfg, B)
+        lib = self.device_shapes(cfg, B)
         return [tuple(sl[2](cfg, B)) if sl[0] is not None else lib[i] for i, sl in enumerate(self.slots)]
 
 
@@ -81,10 +87,19 @@ POINT_FEED = FeedSpec(5, "the 5-tuple of point_models/data_loader.py:87",
                        (None, None, None), (2, "target_user", lambda cfg, B: (B, cfg.user_fnum)),
                        (3, "target_item", lambda cfg, B: (B, cfg.item_fnum)), (4, "label", lambda cfg, B: (B,)),
                        (1, "user_seq_length", lambda cfg, B: (B,))])
+# point_model.py:251-264, data_loader.py:185: (user_seq [B,T,Fi], user_seq_length [B], item_seq [B,T,Fu], item_seq_length [B],
+# target_user [B,Fu], target_item [B,Fi], label [B]).  user_seq rides as user_1hop, item_seq as item_1hop [B,T,1,Fu], the two
+# 2-hop tensors are zeros, user_seq_length is `length` and item_seq_length the ninth tensor, `length2`
+DUAL_FEED = FeedSpec(7, "the 7-tuple of point_models/data_loader.py:185",
+                     [(0, "user_seq", lambda cfg, B: (B, cfg.max_time_len, cfg.item_fnum)), (None, None, None),
+                      (2, "item_seq", lambda cfg, B: (B, cfg.max_time_len, cfg.user_fnum)), (None, None, None),
+                      (4, "target_user", lambda cfg, B: (B, cfg.user_fnum)), (5, "target_item", lambda cfg, B: (B, cfg.item_fnum)),
+                      (6, "label", lambda cfg, B: (B,)), (1, "user_seq_length", lambda cfg, B: (B,)),
+                      (3, "item_seq_length", lambda cfg, B: (B,))])
 
 
 def carve_batch(flat, shapes):
-    """the eight int32 tensors of a batch as views of one flat buffer (every tensor 16-B aligned)"""
+    """the int32 tensors of a batch (eight; nine with a length2) as views of one flat buffer (every tensor 16-B aligned)"""
     out, off = [], 0
     for sh in shapes:
         n = int(np.prod(sh))
@@ -108,13 +123,14 @@ class DeviceBatch(object):
         spec = model.feed_spec
         if len(batch_data) != spec.n:
             raise ValueError("batch_data must be %s" % spec.what)
-        max_len = None
+        max_len = min_len = None
         on_device = all(torch.is_tensor(x) and x.device.type == "cuda" for x in batch_data)
         lab = batch_data[spec.slots[6][0]]
         B = int(lab.shape[0]) if hasattr(lab, "shape") else len(lab)
         if B == 0:
             raise ValueError("empty batch")
-        shapes = batch_shapes(model.cfg, B)            # of the eight device tensors
+        shapes = spec.device_shapes(model.cfg, B)      # of the eight device tensors (nine where the spec names a length2)
+        n_t = len(shapes)
         fshapes = spec.shapes(model.cfg, B)            # of their sources in the feed tuple (the same element order)
         src_of = [sl[0] for sl in spec.slots]
         self.B = B
@@ -133,7 +149,11 @@ class DeviceBatch(object):
                 if tuple(src.shape) != fshapes[i]:
                     raise bad(i, src.shape)
                 dst.view(fshapes[i]).copy_(src)             # (dtype / device conversion included)
-            max_len = int(self.tensors[7].max().item())     # one read-back per batch object
+            if n_t > 8:        # (two length tensors: one read-back of both extremes)
+                lens = torch.stack([self.tensors[7], self.tensors[8]])
+                max_len, min_len = [int(x) for x in torch.stack([lens.max(), lens.min()]).tolist()]
+            else:
+                max_len = int(self.tensors[7].max().item())     # one read-back per batch object
         else:
             # the whole feed tuple into ONE pinned int32 staging buffer, then one asynchronous copy to the device.  Nested
             # lists (what the reference's loader yields: ints, with float 0.0 in dummy slices, graph_loader.py:90-91) are
@@ -144,7 +164,7 @@ class DeviceBatch(object):
             lp = _lib.listpack()
             nthreads = int(getattr(model, "feed_threads", 1))
             try:
-                listed = [i for i in range(8) if src_of[i] is not None and lp is not None
+                listed = [i for i in range(n_t) if src_of[i] is not None and lp is not None
                           and isinstance(batch_data[src_of[i]], (list, tuple))]
                 if listed:      # every list-shaped tensor of the tuple in ONE threaded region (threads are created once)
                     try:
@@ -164,6 +184,9 @@ class DeviceBatch(object):
                         raise bad(i, a.shape)
                     dst.copy_(torch.from_numpy(np.ascontiguousarray(a.astype(np.int32, copy=False))))
                 max_len = int(views[7].max()) if B else 0
+                if n_t > 8:
+                    max_len = max(max_len, int(views[8].max()))
+                    min_len = min(int(views[7].min()), int(views[8].min()))
                 self.flat = torch.empty((n_flat,), dtype=torch.int32, device=model.device)
                 self.flat.copy_(pinned, non_blocking=True)
             finally:
@@ -171,28 +194,37 @@ class DeviceBatch(object):
                 slot[1] = torch.cuda.current_stream(model.device).record_event()
                 slot[2] = False
             self.tensors = carve_batch(self.flat, shapes)
-        self.active_slices = active_slices(model, max_len)
-        self.struct = _lib.Batch(*[_ptr(t) for t in self.tensors], B, self.active_slices)
+        self.active_slices = active_slices(model, max_len, min_len)
+        self.struct = _batch_struct(self.tensors, B, self.active_slices)
 
     @classmethod
     def empty(cls, model, B, active=0):
         """uninitialised batch of B samples (a loader / a captured step fills it)"""
         self = cls.__new__(cls)
-        shapes = batch_shapes(model.cfg, B)
+        shapes = model.feed_spec.device_shapes(model.cfg, B)
         self.flat = torch.empty((flat_batch_size(shapes),), dtype=torch.int32, device=model.device)
         self.tensors = carve_batch(self.flat, shapes)
         self.B = B
         self.active_slices = int(active)
-        self.struct = _lib.Batch(*[_ptr(t) for t in self.tensors], B, self.active_slices)
+        self.struct = _batch_struct(self.tensors, B, self.active_slices)
         return self
 
 
-def active_slices(model, max_len):
+def _batch_struct(tensors, B, active):
+    """score_batch_t over a batch's device tensors; the ninth, where there is one, is length2"""
+    return _lib.Batch(*[_ptr(t) for t in tensors[:8]], B, active, _ptr(tensors[8]) if len(tensors) > 8 else None)
+
+
+def active_slices(model, max_len, min_len=None):
     """score_batch_t.active_slices for a batch whose longest sample has `max_len` slices: the slices past every
     sample's length are masked out of the result by the model itself (dynamic_rnn's sequence_length,
     score.py:205-208; the attention mask, :182-185) and are not gathered or computed.  0 = all T."""
     T = int(model.cfg.max_time_len)
     if not getattr(model, "skip_masked_slices", True) or not getattr(model, "reads_length", True):
+        return 0
+    if min_len is not None and int(min_len) <= 0:
+        # (DELF: a sample whose every position is masked gets uniform weights over ALL T positions, point_model.py:246-247 --
+        #  the batch computes them all; max_len is the maximum over both length tensors)
         return 0
     a = min(max(int(max_len), 1), T)
     return 0 if a >= T else a
@@ -1882,5 +1914,20 @@ class Caser(GRU4Rec):
         return np.ascontiguousarray(a.reshape(shape))
 
 
+class DELF(GRU4Rec):
+    """point_models/point_model.py:200-279 on PointBaseModel (:9-63): the user's history user_seq [B, T, Fi] attended by the
+    target item and the item's history item_seq [B, T, Fu] attended by the target user -- key = tanh(X W + b), a masked softmax
+    over the T positions of <query, key>, the weighted sum of X itself -- then four fusion MLPs (10, 4) over [tu|ti], [ru|ri],
+    [tu|ri], [ti|ru], their sum through a sigmoid unit, log-loss with the L2 name filter (all eleven kernels), Adam.  GRU4Rec's
+    constructor and train / eval / save / restore; batch_data is the 7-tuple of point_models/data_loader.py:185, (user_seq,
+    user_seq_length, item_seq, item_seq_length, target_user, target_item, label), as nested lists, arrays or device tensors,
+    and the target item ids are batch_data[5].  hidden_size is accepted and ignored; there is no dropout, so keep_prob has no
+    effect.  A length >= max_time_len means all positions; a length <= 0 masks all of them, which TF turns into uniform weights
+    over all T positions -- a batch with such a sample computes every slice.  Variables: dense .. dense_10 with TF's names."""
+    model_type = "DELF"
+    feed_spec = DUAL_FEED
+    target_item_field = 5
+
+
 MODELS = {"SCORE": SCORE, "RIA": RIA, "RCA": RCA, "SCORE_USER": SCORE_USER, "SCORE_ITEM": SCORE_ITEM, "RRN": RRN, "GCMC": GCMC,
-          "GRU4Rec": GRU4Rec, "Caser": Caser}
+          "GRU4Rec": GRU4Rec, "Caser": Caser, "DELF": DELF}
