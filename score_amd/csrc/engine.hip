@@ -17,15 +17,25 @@ namespace {
 const int FC1 = 200, FC2 = 80, AT1 = 80, AT2 = 40;
 const int CASER_L = SCORE_CASER_L, CASER_HPAD = SCORE_CASER_HPAD;       // kernels.h
 
+// What decides a pass's launch sequence.  FAM_SLICE: SCORE, RIA, RCA, SCORE_USER, SCORE_ITEM and RRN, which differ by attn, coattn
+// and Is[] only; every other model type is a family of its own
+enum Family { FAM_SLICE, FAM_GCMC, FAM_G4R, FAM_CASER, FAM_DELF };
+
 struct Dims {
   int64_t N;
   int D, H, T, K, Fu, Fi, mt;
   int Du, Di, I, Dq, NI, Dk, Dhead, nstate;
   int Is[2];       // GRU input width per side (user, item): I, except RRN / GCMC (their 1-hop sums only)
-  bool coattn, attn, gcmc;
-  bool g4r;        // GRU4Rec: "side" 0 is layer 1 (input: the gathered user_seq rows, Di wide), "side" 1 layer 2 (input: layer 1's outputs, H wide)
-  bool caser;      // Caser: no recurrence at all (H = 0 here, whatever the config says); C = Di columns of xside[0] are its X
-  bool delf;       // DELF: no recurrence and no bn1 / fc head (H = 0 here); X of side 0 = Di columns of xside[0], of side 1 = Du columns of xside[1]
+  bool coattn, attn;
+  // the family and what follows from it (set in make_dims only).
+  // FAM_G4R: "side" 0 is layer 1 (input: the gathered user_seq rows, Di wide), "side" 1 layer 2 (input: layer 1's outputs, H wide)
+  // FAM_CASER: no recurrence at all (H = 0 here, whatever the config says); C = Di columns of xside[0] are its X
+  // FAM_DELF: no recurrence and no bn1 / fc head (H = 0 here); X of side 0 = Di columns of xside[0], of side 1 = Du columns of xside[1]
+  Family family;
+  int n_gru;             // recurrences with variables, workspace and launches: 2, or 0 (Caser, DELF)
+  bool fc_head;          // bn1 and fc1-3 behind head_inp (not GCMC, DELF)
+  bool sums_1hop;        // the gather leaves plain 1-hop sums: no co-attention, no attention, Is[] = {Di, Du} (RRN and every later type)
+  bool reads_targets;    // the model reads the target rows (not GCMC: their gradient is zero)
   int Ic;          // row capacity of a side's block of the concatenated [Wx_gates | Wx_cand] copy: I (GRU4Rec: max(I, H))
   int off_u, off_i, off_ti, off_tu;  // columns of head_inp
 };
@@ -38,36 +48,38 @@ int make_dims(const score_config_t* c, Dims* d) {
       d->Fu <= 0 || d->Fi <= 0 || d->mt < 0 || d->mt > SCORE_MODEL_DELF)
     return SCORE_E_SHAPE;
   d->Du = d->Fu * d->D; d->Di = d->Fi * d->D; d->I = d->Di + d->Du; d->Dq = d->Du + d->Di;
-  d->gcmc = d->mt == SCORE_MODEL_GCMC;
-  d->g4r = d->mt == SCORE_MODEL_GRU4REC;
-  d->caser = d->mt == SCORE_MODEL_CASER;
-  d->delf = d->mt == SCORE_MODEL_DELF;
-  if ((d->g4r || d->caser || d->delf) && d->K != 1) return SCORE_E_SHAPE;      // (user_seq rides as a [B, T, 1, Fi] set)
-  if (d->delf) {
+  const bool gcmc = d->mt == SCORE_MODEL_GCMC, g4r = d->mt == SCORE_MODEL_GRU4REC, caser = d->mt == SCORE_MODEL_CASER,
+             delf = d->mt == SCORE_MODEL_DELF;
+  d->family = gcmc ? FAM_GCMC : g4r ? FAM_G4R : caser ? FAM_CASER : delf ? FAM_DELF : FAM_SLICE;
+  d->n_gru = (caser || delf) ? 0 : 2;
+  d->fc_head = !gcmc && !delf;
+  d->reads_targets = !gcmc;
+  if ((g4r || caser || delf) && d->K != 1) return SCORE_E_SHAPE;      // (user_seq rides as a [B, T, 1, Fi] set)
+  if (delf) {
     if (d->Di > SCORE_DELF_CMAX || d->Du > SCORE_DELF_CMAX) return SCORE_E_SHAPE;      // (the widths delf.hip covers)
     d->H = 0;                                                 // hidden_size: accepted and ignored, as for Caser
   }
-  if (d->caser) {
+  if (caser) {
     if (d->T < CASER_L) return SCORE_E_SHAPE;                 // (conv2d's VALID window, point_model.py:147: TF refuses the graph)
     d->H = 0;                                                 // hidden_size: accepted and ignored -- no GRU variable, workspace or launch
   }
   // (GCMC starts from RRN's two 1-hop sums, slice_model.py:184-187; GRU4Rec's user_seq rows are RRN's "sum" over a one-element set)
-  const bool rrn = d->mt == SCORE_MODEL_RRN || d->gcmc || d->g4r || d->caser || d->delf;
-  d->coattn = d->mt != SCORE_MODEL_RCA && !rrn;
-  d->attn = d->mt != SCORE_MODEL_RIA && !rrn;
-  d->NI = (d->mt == SCORE_MODEL_RCA || d->mt == SCORE_MODEL_RIA || rrn) ? 0 : 4 * d->K;
+  d->sums_1hop = d->mt == SCORE_MODEL_RRN || d->family != FAM_SLICE;
+  d->coattn = d->mt != SCORE_MODEL_RCA && !d->sums_1hop;
+  d->attn = d->mt != SCORE_MODEL_RIA && !d->sums_1hop;
+  d->NI = (d->mt == SCORE_MODEL_RCA || d->mt == SCORE_MODEL_RIA || d->sums_1hop) ? 0 : 4 * d->K;
   // RRN (slice_model.py:159-160): user side = sum_k user_1hop (item features), item side = sum_k item_1hop
-  d->Is[0] = rrn ? d->Di : d->I;
-  d->Is[1] = d->g4r ? d->H : rrn ? d->Du : d->I;
-  d->Ic = d->g4r && d->H > d->I ? d->H : d->I;
-  if (d->gcmc && d->H > 256) return SCORE_E_SHAPE;            // (its head kernels, gcmc.hip)
+  d->Is[0] = d->sums_1hop ? d->Di : d->I;
+  d->Is[1] = g4r ? d->H : d->sums_1hop ? d->Du : d->I;
+  d->Ic = g4r && d->H > d->I ? d->H : d->I;
+  if (gcmc && d->H > 256) return SCORE_E_SHAPE;            // (its head kernels, gcmc.hip)
   d->Dk = d->attn ? 2 * d->H + d->NI : 0;
-  d->nstate = (d->caser || d->delf) ? 0 : (d->mt == SCORE_MODEL_SCORE_USER || d->mt == SCORE_MODEL_SCORE_ITEM || d->g4r) ? 1 : 2;
+  d->nstate = d->n_gru == 0 ? 0 : (d->mt == SCORE_MODEL_SCORE_USER || d->mt == SCORE_MODEL_SCORE_ITEM || g4r) ? 1 : 2;
   d->Dhead = d->nstate * d->H + d->Di + d->Du;
   d->off_u = d->mt == SCORE_MODEL_SCORE_ITEM ? -1 : 0;       // (GRU4Rec: layer 2's final state sits where SCORE_USER's state does)
   d->off_i = d->mt == SCORE_MODEL_SCORE_USER ? -1 : (d->mt == SCORE_MODEL_SCORE_ITEM ? 0 : d->H);
   d->off_ti = d->nstate * d->H;       // [..., target_item, target_user]  (score.py:217)
-  if (d->caser) {
+  if (caser) {
     // [h, 0, 0, 0 | v2 (Di) | target_item | target_user]: TF's 1 + 2 Di + Du columns with h padded to four floats, so that the
     // target kernels' 16-byte accesses at off_ti / off_tu and the head kernels' vector path (Dhead % 4 == 0) hold
     d->Dhead = CASER_HPAD + 2 * d->Di + d->Du;
@@ -80,13 +92,15 @@ int make_dims(const score_config_t* c, Dims* d) {
 
 // the GRUs' input rows of side sd and their stride: the [B*T, I] gather output, or GCMC's Z = relu(relu(S Wa) Wc) [B*T, Dx]
 // (GRU4Rec's layer 2 reads layer 1's outputs [B*T, H])
-static inline int x_ld(const Dims& d, int sd) { return d.gcmc ? d.Is[sd] : (d.g4r && sd == 1) ? d.H : d.I; }
+static inline int x_ld(const Dims& d, int sd) {
+  return d.family == FAM_GCMC ? d.Is[sd] : (d.family == FAM_G4R && sd == 1) ? d.H : d.I;
+}
 
 // time slices actually computed for a batch (score_batch_t.active_slices): every [B*T, .] activation of the
 // pass is laid out [B * TA, .]; the workspace regions keep their full-T sizes and offsets
 // (Caser reads no length: all T positions, whatever the batch says)
 static inline int active_T(const Dims& d, const score_batch_t* bt) {
-  const int a = d.caser ? 0 : bt->active_slices;
+  const int a = d.family == FAM_CASER ? 0 : bt->active_slices;
   return (a > 0 && a < d.T) ? a : d.T;
 }
 
@@ -109,6 +123,8 @@ int build_layout_raw(const Dims& d, score_param_entry_t* out, int max_entries, P
   char names[32][64];
   int rows[32], cols[32], reg[32], init[32];
   int n = 0, nd = 0;
+  memset(P, 0, sizeof(*P));      // (a variable the model type does not have: offset 0, never read)
+  const bool gcmc = d.family == FAM_GCMC, caser = d.family == FAM_CASER, delf = d.family == FAM_DELF;
   auto add = [&](const char* nm, int r, int c, int rg, int in) {
     snprintf(names[n], 64, "%s", nm);
     rows[n] = r; cols[n] = c; reg[n] = rg; init[n] = in; ++n;
@@ -124,27 +140,27 @@ int build_layout_raw(const Dims& d, score_param_entry_t* out, int max_entries, P
   if (d.coattn) { dense(3 * d.Di, 1); dense(3 * d.Du, 1); }
   // GCMC (slice_model.py:182-201): dense .. dense_3 (per-side relu denses, no bias), gru1 / gru2, dense_4 / dense_5 (the head)
   const int Dx[2] = {d.Di, d.Du};
-  if (d.gcmc) {
+  if (gcmc) {
     add("dense/kernel", Dx[0], Dx[0], 1, 2); add("dense_1/kernel", Dx[1], Dx[1], 1, 2);
     add("dense_2/kernel", Dx[0], Dx[0], 1, 2); add("dense_3/kernel", Dx[1], Dx[1], 1, 2);
   }
   const char* sides[2] = {"gru_user_side", "gru_item_side"};
-  if (d.gcmc || d.g4r) { sides[0] = "gru1"; sides[1] = "gru2"; }     // (GRU4Rec, point_model.py:129-132: the two stacked layers)
+  if (gcmc || d.family == FAM_G4R) { sides[0] = "gru1"; sides[1] = "gru2"; }     // (GRU4Rec, point_model.py:129-132: the two stacked layers)
   // Caser (point_model.py:147-157): conv2d [50, C, 1, 1], conv2d_1 [T, 1, 1, 1] (init 3: glorot with TF's convolution fans,
   // fan_in = fan_out = rows * cols), dense [1, 1]
-  if (d.caser) {
+  if (caser) {
     add("conv2d/kernel", CASER_L, d.Di, 1, 3); add("conv2d/bias", 1, 0, 0, 0);
     add("conv2d_1/kernel", d.T, 1, 1, 3); add("conv2d_1/bias", 1, 0, 0, 0);
     dense(1, 1);
   }
   // DELF (point_model.py:216-232, 235-249): the two attention denses, four fusion MLPs (10, 4), the output unit
-  if (d.delf) {
+  if (delf) {
     dense(d.Di, d.Di); dense(d.Du, d.Du);
     const int in[4] = {d.Du + d.Di, d.Di + d.Du, 2 * d.Du, 2 * d.Di};      // [tu|ti], [ru|ri], [tu|ri], [ti|ru]
     for (int k = 0; k < 4; ++k) { dense(in[k], 10); dense(10, 4); }
     dense(4, 1);
   }
-  for (int s = 0; s < 2 && !d.caser && !d.delf; ++s) {
+  for (int s = 0; s < d.n_gru; ++s) {
     char b[64];
     snprintf(b, 64, "%s/gru_cell/gates/kernel", sides[s]); add(b, d.Is[s] + d.H, 2 * d.H, 1, 2);
     snprintf(b, 64, "%s/gru_cell/gates/bias", sides[s]); add(b, 2 * d.H, 0, 0, 1);
@@ -152,9 +168,8 @@ int build_layout_raw(const Dims& d, score_param_entry_t* out, int max_entries, P
     snprintf(b, 64, "%s/gru_cell/candidate/bias", sides[s]); add(b, d.H, 0, 0, 0);
   }
   if (d.attn) { dense(d.Dq, d.Dk); dense(4 * d.Dk, AT1); dense(AT1, AT2); dense(AT2, 1); }
-  if (d.gcmc) {
-    add("dense_4/kernel", d.H, d.H, 1, 2); add("dense_5/kernel", d.H, d.H, 1, 2);
-  } else if (!d.delf) {
+  if (gcmc) { add("dense_4/kernel", d.H, d.H, 1, 2); add("dense_5/kernel", d.H, d.H, 1, 2); }
+  if (d.fc_head) {
     add("bn1/gamma", d.Dhead, 0, 1, 1);
     add("bn1/beta", d.Dhead, 0, 1, 0);
     add("fc1/kernel", d.Dhead, FC1, 1, 2); add("fc1/bias", FC1, 0, 0, 0);
@@ -184,30 +199,18 @@ int build_layout_raw(const Dims& d, score_param_entry_t* out, int max_entries, P
       out[i].regularised = reg[i]; out[i].init = init[i];
     }
   }
-  int i = 0;
-  if (d.delf) {       // (nothing else: no recurrence, no bn1 / fc head)
-    for (int k = 0; k < 11; ++k) { P->dl_w[k] = off[i++]; P->dl_b[k] = off[i++]; }
-    for (int s = 0; s < 2; ++s) P->gk[s] = P->gb[s] = P->ck[s] = P->cb[s] = 0;
-    P->bn_g = P->bn_b = 0;
-    for (int f = 0; f < 3; ++f) P->fc_w[f] = P->fc_b[f] = 0;
-    return n;
-  }
+  int i = 0;      // (in creation order, as above)
   if (d.coattn) { for (int c = 0; c < 2; ++c) { P->ca_w[c] = off[i++]; P->ca_b[c] = off[i++]; } }
-  if (d.gcmc) { P->gm_a[0] = off[i++]; P->gm_a[1] = off[i++]; P->gm_c[0] = off[i++]; P->gm_c[1] = off[i++]; }
-  if (d.caser) {
-    P->cs_wh = off[i++]; P->cs_bh = off[i++]; P->cs_wv = off[i++]; P->cs_bv = off[i++]; P->cs_wd = off[i++]; P->cs_bd = off[i++];
-    for (int s = 0; s < 2; ++s) P->gk[s] = P->gb[s] = P->ck[s] = P->cb[s] = 0;
-  } else
-  for (int s = 0; s < 2; ++s) { P->gk[s] = off[i++]; P->gb[s] = off[i++]; P->ck[s] = off[i++]; P->cb[s] = off[i++]; }
+  if (gcmc) { P->gm_a[0] = off[i++]; P->gm_a[1] = off[i++]; P->gm_c[0] = off[i++]; P->gm_c[1] = off[i++]; }
+  if (caser) { P->cs_wh = off[i++]; P->cs_bh = off[i++]; P->cs_wv = off[i++]; P->cs_bv = off[i++]; P->cs_wd = off[i++]; P->cs_bd = off[i++]; }
+  if (delf) { for (int k = 0; k < 11; ++k) { P->dl_w[k] = off[i++]; P->dl_b[k] = off[i++]; } }
+  for (int s = 0; s < d.n_gru; ++s) { P->gk[s] = off[i++]; P->gb[s] = off[i++]; P->ck[s] = off[i++]; P->cb[s] = off[i++]; }
   if (d.attn) { for (int a = 0; a < 4; ++a) { P->at_w[a] = off[i++]; P->at_b[a] = off[i++]; } }
-  if (d.gcmc) {
-    P->gm_4 = off[i++]; P->gm_5 = off[i++];
-    P->bn_g = P->bn_b = 0;
-    for (int f = 0; f < 3; ++f) P->fc_w[f] = P->fc_b[f] = 0;
-    return n;
+  if (gcmc) { P->gm_4 = off[i++]; P->gm_5 = off[i++]; }
+  if (d.fc_head) {
+    P->bn_g = off[i++]; P->bn_b = off[i++];
+    for (int f = 0; f < 3; ++f) { P->fc_w[f] = off[i++]; P->fc_b[f] = off[i++]; }
   }
-  P->bn_g = off[i++]; P->bn_b = off[i++];
-  for (int f = 0; f < 3; ++f) { P->fc_w[f] = off[i++]; P->fc_b[f] = off[i++]; }
   return n;
 }
 
@@ -287,9 +290,45 @@ static int64_t ps_image_region_floats(const Dims& d) {
 
 // distance between the replicas of the folded first attention layer's weight (head.hip)
 static inline int64_t weff_copy_stride(const Dims& d) { return align_up64(2 * (int64_t)d.Dk * AT1 + 48, 4); }
+// hands out the workspace's regions front to back, each 16-B aligned (an empty one still takes four floats)
+struct Taker {
+  int64_t cur;
+  int64_t operator()(int64_t n) { int64_t o = cur; cur = align_up64(cur + (n > 0 ? n : 4), 4); return o; }
+};
+// the regions only one family has: at the end, so that the other model types' layouts stay what they were
+void ws_family_regions(const Dims& d, int B, Taker& take, WS* w) {
+  const int64_t BT = (int64_t)B * d.T;
+  if (d.family == FAM_GCMC) {
+    const int Dx[2] = {d.Di, d.Du};
+    for (int s = 0; s < 2; ++s) {
+      w->gcmc_a[s] = take(BT * Dx[s]); w->gcmc_z[s] = take(BT * Dx[s]);
+      w->gcmc_dz[s] = take(BT * Dx[s]); w->gcmc_da[s] = take(BT * Dx[s]);
+    }
+    w->gcmc_pn = take(2 * (int64_t)B * d.H); w->gcmc_g = take(B); w->gcmc_gu = take(2 * (int64_t)B * d.H);
+  } else {
+    for (int s = 0; s < 2; ++s) w->gcmc_a[s] = w->gcmc_z[s] = w->gcmc_dz[s] = w->gcmc_da[s] = -1;
+    w->gcmc_pn = w->gcmc_g = w->gcmc_gu = -1;
+  }
+  if (d.family == FAM_CASER) {
+    w->caser_hwin = take((int64_t)B * (d.T - CASER_L + 1)); w->caser_arg = take(B); w->caser_v = take((int64_t)B * d.Di);
+  } else {
+    w->caser_hwin = w->caser_arg = w->caser_v = -1;
+  }
+  if (d.family == FAM_DELF) {
+    const int Cx[2] = {d.Di, d.Du};
+    for (int s = 0; s < 2; ++s) {
+      w->delf_key[s] = take(BT * Cx[s]); w->delf_att[s] = take(BT); w->delf_rep[s] = take((int64_t)B * Cx[s]);
+      w->delf_ds[s] = take(BT); w->delf_dpre[s] = take(BT * Cx[s]);
+    }
+    w->delf_act = take((int64_t)B * SCORE_DELF_ACT); w->delf_dact = take((int64_t)B * SCORE_DELF_ACT);
+  } else {
+    for (int s = 0; s < 2; ++s) w->delf_key[s] = w->delf_att[s] = w->delf_rep[s] = w->delf_ds[s] = w->delf_dpre[s] = -1;
+    w->delf_act = w->delf_dact = -1;
+  }
+}
+
 void build_ws_raw(const Dims& d, int B, WS* w) {
-  int64_t cur = 0;
-  auto take = [&](int64_t n) { int64_t o = cur; cur = align_up64(cur + (n > 0 ? n : 4), 4); return o; };
+  Taker take = {0};
   const int64_t BT = (int64_t)B * d.T;
   for (int s = 0; s < 2; ++s) w->xside[s] = take(BT * d.I);
   w->info = take(BT * 4 * d.K);
@@ -335,9 +374,9 @@ void build_ws_raw(const Dims& d, int B, WS* w) {
   w->cs_part = take(w->cs_part_floats);
   w->wxcat = take(2 * (int64_t)(d.Ic + 1) * 3 * d.H);
   for (int sd = 0; sd < 2; ++sd) {
-    const int ns = d.H > 0 ? panel_x_splits(d.H) : 0;      // (Caser: no recurrence, no projection)
+    const int ns = d.n_gru ? panel_x_splits(d.H) : 0;      // (Caser: no recurrence, no projection)
     w->pimg_x[sd] = take(ns ? ns * score_gemm_panel_image_floats(3 * d.H / ns, d.Is[sd]) : 0);
-    const int nd = d.H > 0 ? panel_d_splits(d.Is[sd]) : 0;
+    const int nd = d.n_gru ? panel_d_splits(d.Is[sd]) : 0;
     w->pimg_d[sd] = take(nd ? nd * score_gemm_panel_image_floats(d.Is[sd] / nd, 3 * d.H) : 0);
   }
   w->psimg = take(ps_image_region_floats(d));
@@ -383,35 +422,8 @@ void build_ws_raw(const Dims& d, int B, WS* w) {
     w->partial_floats = 2 * nw * d.D + 8 + 2 * nw;
   }
   w->partials = take(w->partial_floats);
-  // (at the end, and for GCMC only: the other model types' layouts stay what they were)
-  if (d.gcmc) {
-    const int Dx[2] = {d.Di, d.Du};
-    for (int s = 0; s < 2; ++s) {
-      w->gcmc_a[s] = take(BT * Dx[s]); w->gcmc_z[s] = take(BT * Dx[s]);
-      w->gcmc_dz[s] = take(BT * Dx[s]); w->gcmc_da[s] = take(BT * Dx[s]);
-    }
-    w->gcmc_pn = take(2 * (int64_t)B * d.H); w->gcmc_g = take(B); w->gcmc_gu = take(2 * (int64_t)B * d.H);
-  } else {
-    for (int s = 0; s < 2; ++s) w->gcmc_a[s] = w->gcmc_z[s] = w->gcmc_dz[s] = w->gcmc_da[s] = -1;
-    w->gcmc_pn = w->gcmc_g = w->gcmc_gu = -1;
-  }
-  if (d.caser) {
-    w->caser_hwin = take((int64_t)B * (d.T - CASER_L + 1)); w->caser_arg = take(B); w->caser_v = take((int64_t)B * d.Di);
-  } else {
-    w->caser_hwin = w->caser_arg = w->caser_v = -1;
-  }
-  if (d.delf) {
-    const int Cx[2] = {d.Di, d.Du};
-    for (int s = 0; s < 2; ++s) {
-      w->delf_key[s] = take(BT * Cx[s]); w->delf_att[s] = take(BT); w->delf_rep[s] = take((int64_t)B * Cx[s]);
-      w->delf_ds[s] = take(BT); w->delf_dpre[s] = take(BT * Cx[s]);
-    }
-    w->delf_act = take((int64_t)B * SCORE_DELF_ACT); w->delf_dact = take((int64_t)B * SCORE_DELF_ACT);
-  } else {
-    for (int s = 0; s < 2; ++s) w->delf_key[s] = w->delf_att[s] = w->delf_rep[s] = w->delf_ds[s] = w->delf_dpre[s] = -1;
-    w->delf_act = w->delf_dact = -1;
-  }
-  w->total = cur;
+  ws_family_regions(d, B, take, w);
+  w->total = take.cur;
 }
 
 void build_ws(const Dims& d, int B, WS* w) {
@@ -599,6 +611,12 @@ static int weight_prep(const Pass& c, hipStream_t on) {
                                   W + P.cb[1], d.Is[0], d.Is[1], d.Ic, d.H, c.ws + w.wxcat, d.Dk, AT1,
                                   d.attn ? W + P.at_w[1] : nullptr, c.ws + w.weff, c.ws + w.wq, SCORE_WEFF_COPIES, c.weff_stride, W,
                                   P.n_reg, c.ws + w.part, on);
+}
+
+// the GRUs' input rows of side sd, as the backward pass's queued weight gradients read them: the gather's output, GCMC's Z, or
+// (GRU4Rec's layer 2) layer 1's outputs; x_ld is their stride
+static inline const float* gru_x_rows(const Pass& c, int sd) {
+  return c.ws + (c.d.family == FAM_GCMC ? c.w.gcmc_z[sd] : (c.d.family == FAM_G4R && sd == 1) ? c.w.gru_out[0] : c.w.xside[sd]);
 }
 
 // ---------------------------------------------------------------- the recurrences' argument blocks
@@ -893,7 +911,7 @@ static int queue_gru_side(const Pass& c, GradQueues* q, float* gw, int sd, int b
   const Dims& d = c.d; const Params& P = c.P; const WS& w = c.w; float* ws = c.ws;
   const int H = c.H, BT = c.BT, Is = d.Is[sd], ld = x_ld(d, sd);
   float* dxp = ws + w.dxproj[sd];
-  const float* xin = d.gcmc ? ws + w.gcmc_z[sd] : (d.g4r && sd == 1) ? ws + w.gru_out[0] : ws + w.xside[sd];
+  const float* xin = gru_x_rows(c, sd);
   G(gemm_queue_add(&q->gq, Is, 2 * H, BT, xin, ld, dxp, 3 * H, gw + P.gk[sd], 2 * H));
   G(gemm_queue_add(&q->gq, Is, H, BT, xin, ld, dxp + 2 * H, 3 * H, gw + P.ck[sd], H));
   G(gemm_queue_add(&q->gq, H, 2 * H, BT, ws + w.hprev[sd], H, dxp, 3 * H, gw + P.gk[sd] + (int64_t)Is * 2 * H, 2 * H));
@@ -1106,8 +1124,9 @@ extern "C" int score_index_plan(const score_config_t* cfg, const score_state_t* 
 // streams' work is small beside these products: 20.3 -> 19.8 ms/step with both.
 static bool panel_gemms(const Dims& d, const score_state_t* st, int BT, int which) {
   const Flags fl = flags_of(st);
-  if (st->gemm_mode != 1 || fl.no_panel || d.Is[0] != d.Is[1] || d.g4r || d.caser || d.delf) return false;
-  if (which == 1 && d.gcmc) return false;      // (GCMC's input gradients take Z's relu mask in the epilogue: the tiled kernels)
+  const bool two_sided = d.family == FAM_SLICE || d.family == FAM_GCMC;      // (the families of fwd_grus_two_sided)
+  if (st->gemm_mode != 1 || fl.no_panel || d.Is[0] != d.Is[1] || !two_sided) return false;
+  if (which == 1 && d.family == FAM_GCMC) return false;      // (GCMC's input gradients take Z's relu mask in the epilogue: the tiled kernels)
   const int ns = panel_x_splits(d.H), nd = panel_d_splits(d.Is[0]);
   return which == 0 ? ns > 0 && score_gemm_panel_ok(2 * ns, BT, 3 * d.H / ns, d.Is[0], x_ld(d, 0), 3 * d.H, nullptr)
                     : (fl.panel_dx || (int64_t)BT >= 65536) && nd > 0 &&
@@ -1333,33 +1352,26 @@ extern "C" int score_persample_form(const score_config_t* cfg, const score_state
   return ps_path(d, st, &bt, active_T(d, &bt), &pp) ? 1 : 0;
 }
 
-extern "C" int score_forward(const score_config_t* cfg, const score_state_t* st, const score_batch_t* bt,
-                             float reg_lambda, float keep_prob, const uint8_t* drop_mask0,
-                             const uint8_t* drop_mask1, uint64_t drop_seed, void* const* stage_events,
-                             void* stream) {
-  Pass c;
-  SCORE_TRY(make_dims(cfg, &c.d));
-  if (!st || !bt || !st->table || !st->w || !st->workspace || bt->B <= 0) return SCORE_E_BADARG;
-  if (!bt->user_1hop || !bt->user_2hop || !bt->item_1hop || !bt->item_2hop || !bt->target_user ||
-      !bt->target_item || !bt->label || !bt->length)
-    return SCORE_E_BADARG;
-  if (c.d.delf && !bt->length2) return SCORE_E_BADARG;        // (item_seq_length: the one model type that reads it)
-  if (!(keep_prob > 0.f) || keep_prob > 1.f) return SCORE_E_BADARG;
-  SCORE_TRY(pass_fill(&c, st, bt, stream));
-  const Dims& d = c.d; const Params& P = c.P; const WS& w = c.w; const Flags& fl = c.fl;
-  const int B = c.B, T = c.T, H = c.H, BT = c.BT, x3 = c.x3, Bg = c.Bg;
-  hipStream_t s = c.s;
-  {
-    PsPlan pp;       // the reference's own shapes: the whole pass as one kernel per sample (persample.h)
-    if (!fl.ps_bwd_only && ps_path(d, st, bt, T, &pp))
-      return forward_ps(c, pp, reg_lambda, keep_prob, drop_mask0, drop_mask1, drop_seed, stage_events);
-  }
-  float* ws = c.ws; const float* W = c.W; float* scratch = c.scratch;
+// ---------------------------------------------------------------- the layer-by-layer forward pass
+// fwd_open, the same for every model type, then ONE function per family (fwd_slice .. fwd_delf): the family's launches
+// between EV(1) and EV(4), in order, with its waits for the side stream's `wx` and `join` where it needs them.
+namespace {
+// score_forward's arguments behind the batch, and what fwd_open leaves for the stages after it
+struct FwdState {
+  float reg_lambda, keep_prob; const uint8_t *mask0, *mask1; uint64_t seed; void* const* stage_events;
+  SideStream* sd;      // the side stream, forked behind the launch stream, `wx` and `join` recorded on it
+  bool panel_x;        // the projections take the panel form (panel_gemms)
+};
 
-  // side stream: the target rows, the L2 norm of the weights (needs no batch), then the attention's query branch (target rows and
-  // weights only) -- beside the gather and the GRUs
+// Side stream: the target rows, the L2 norm of the weights (needs no batch), then the attention's query branch (target rows and
+// weights only) -- beside the gather and the GRUs.  Launch stream: the gather.  Ends with EV(1).
+int fwd_open(const Pass& c, FwdState* f) {
+  const Dims& d = c.d; const Params& P = c.P; const WS& w = c.w; const score_state_t* st = c.st; const score_batch_t* bt = c.bt;
+  float* ws = c.ws; const float* W = c.W; const int B = c.B, x3 = c.x3; hipStream_t s = c.s;
+  void* const* stage_events = f->stage_events;
   SideStream* sd = nullptr;
   G(side_stream(st, s, &sd));
+  f->sd = sd;
   G(fork_side(sd, s));
   sd->fwd_on = s;       // (score_backward on this stream next finds the side stream already behind everything before this pass)
   // target rows -> query [tu | ti] and head_inp [.., ti, tu]      (score.py:62-66, 210, 217).  On the side stream since round 6:
@@ -1371,9 +1383,9 @@ extern "C" int score_forward(const score_config_t* cfg, const score_state_t* st,
   G(weight_prep(c, sd->st));       // (off the main stream)
   // the panel form of the projections and of their input gradients (gemm_panel.hip) takes the weights as fragment images:
   // written here, once per step, behind the concatenated copies (the backward pass reuses them as it reuses the copies)
-  const bool panel_x = panel_gemms(d, st, BT, 0);
-  if (panel_x) G(panel_prep(c, 0, sd->st));
-  if (panel_gemms(d, st, BT, 1)) G(panel_prep(c, 1, sd->st));
+  f->panel_x = panel_gemms(d, st, c.BT, 0);
+  if (f->panel_x) G(panel_prep(c, 0, sd->st));
+  if (panel_gemms(d, st, c.BT, 1)) G(panel_prep(c, 1, sd->st));
   HIPTRY(hipEventRecord(sd->wx, sd->st));
   if (d.attn) {
     float* scratch2 = ws + w.scratch2;
@@ -1403,386 +1415,481 @@ extern "C" int score_forward(const score_config_t* cfg, const score_state_t* st,
   }
   if (st->gather_done_event) HIPTRY(hipEventRecord((hipEvent_t)st->gather_done_event, s));
   EV(1);
-  // GCMC (slice_model.py:182-190): per side A = relu(S Wa), Z = relu(A Wc), S the 1-hop sum the gather left in xside.  TF applies
-  // Wa to every neighbour and sums; summing first is the same by linearity, with K times fewer flops
+  return 0;
+}
+
+// GRUs (:205-208) of the slice models and GCMC: hoisted x-projection of the rows xin[side], then the persistent recurrence
+int fwd_grus_two_sided(const Pass& c, const FwdState& f, const float* const* xin) {
+  const Dims& d = c.d; const WS& w = c.w; float* ws = c.ws; const int H = c.H, BT = c.BT, x3 = c.x3; hipStream_t s = c.s;
+  GruArgs ga;
+  gru_header(c, &ga);
+  float* xp[2] = {ws + w.xproj[0], ws + w.xproj[1]};
+  if (d.Is[0] == d.Is[1]) {    // both sides' projections in ONE grouped launch (each with its own bias row)
+    if (f.panel_x) {
+      G(panel_launch(c, 0, xin, xp));
+    } else {
+      const float* Bx[2] = {wxcat(c, 0), wxcat(c, 1)};
+      const float* bx[2] = {Bx[0] + (int64_t)d.Is[0] * 3 * H, Bx[1] + (int64_t)d.Is[1] * 3 * H};
+      G(score_gemm_same_shape(0, 2, BT, 3 * H, d.Is[0], xin, x_ld(d, 0), Bx, 3 * H, xp, 3 * H, GF_BIAS, x3 != 0, c.scratch,
+                              w.scratch_floats, s, bx));
+    }
+  }
+  for (int sd = 0; sd < 2; ++sd) {
+    // x . [Wx_gates | Wx_cand] + [b_gates | b_cand]: one GEMM per side on the concatenated copy
+    const float* cat = wxcat(c, sd);
+    if (d.Is[0] != d.Is[1])
+      G(gemm_mode_call(x3, 0, BT, 3 * H, d.Is[sd], xin[sd], x_ld(d, sd), cat, 3 * H, xp[sd], 3 * H, cat + (int64_t)d.Is[sd] * 3 * H,
+                       GF_BIAS, 1.f, nullptr, 0, c.scratch, w.scratch_floats, s));
+    gru_side(c, sd, &ga.s[sd]);
+    ga.s[sd].xproj = xp[sd]; ga.s[sd].final_state = ws + w.gru_final[sd];
+  }
+  return score_gru_fwd_multi(ga, 2, s);
+}
+
+// temporal attention (:169-186, 210-215); q, Weff/Wq and qz come from the side stream
+int fwd_attention(const Pass& c, const FwdState& f) {
+  const Dims& d = c.d; const Params& P = c.P; const WS& w = c.w; const score_batch_t* bt = c.bt;
+  float* ws = c.ws; const float* W = c.W; const int B = c.B, T = c.T, H = c.H, BT = c.BT, x3 = c.x3; hipStream_t s = c.s;
+  HIPTRY(hipStreamWaitEvent(s, f.sd->join, 0));
+  // all of it in one launch (head_fused.hip) where the shape allows ...
+  int frc = c.fl.attn_unfused ? SCORE_E_SHAPE
+                : score_launch_attn_fwd_fused(B, T, H, d.NI, AT1, AT2, ws + w.q, ws + w.gru_out[0], ws + w.gru_out[1],
+                                              ws + w.info, ws + w.weff, ws + w.qz, W + P.at_w[2], W + P.at_b[2],
+                                              W + P.at_w[3], W + P.at_b[3], bt->length, ws + w.ainp, ws + w.a1, ws + w.a2,
+                                              ws + w.att_score, ws + w.head_inp, d.Dhead, d.off_u, d.off_i, s,
+                                              SCORE_WEFF_COPIES, c.weff_stride);
+  if (frc != SCORE_E_SHAPE) return frc;
+  // (... else the separate launches)
+  G(score_launch_attn_build_inp(B, T, H, d.NI, ws + w.q, ws + w.gru_out[0], ws + w.gru_out[1], ws + w.info,
+                                ws + w.ainp, s));
+  G(gemm_mode_call(x3, 0, BT, AT1, 2 * d.Dk, ws + w.ainp, 2 * d.Dk, ws + w.weff, AT1, ws + w.a1, AT1, ws + w.qz,
+                   GF_BIAS | GF_RELU | (T << 16), 1.f, nullptr, 0, c.scratch, w.scratch_floats, s));
+  // dense_4, dense_5, mask, softmax over T and the pooling: one launch, a block per sample (head.hip)
+  int trc = c.fl.attn_unfused ? SCORE_E_SHAPE
+                : score_launch_attn_tail_fwd(B, T, H, AT1, AT2, ws + w.a1, W + P.at_w[2], W + P.at_b[2], W + P.at_w[3],
+                                             W + P.at_b[3], bt->length, ws + w.gru_out[0], ws + w.gru_out[1], ws + w.a2,
+                                             ws + w.att_score, ws + w.head_inp, d.Dhead, d.off_u, d.off_i, s);
+  if (trc != SCORE_E_SHAPE) return trc;
+  G(gemm_mode_call(x3, 0, BT, AT2, AT1, ws + w.a1, AT1, W + P.at_w[2], AT2, ws + w.a2, AT2, W + P.at_b[2],
+                   GF_BIAS | GF_RELU, 1.f, nullptr, 0, c.scratch, w.scratch_floats, s));
+  return score_launch_attn_pool_fwd(B, T, H, AT2, ws + w.a2, W + P.at_w[3], W + P.at_b[3], bt->length,
+                                    ws + w.gru_out[0], ws + w.gru_out[1], ws + w.att_score, ws + w.head_inp, d.Dhead,
+                                    d.off_u, d.off_i, s);
+}
+
+// build_fc_net (:68-76) on head_inp, the loss and its reduction
+int fwd_fc_head(const Pass& c, const FwdState& f) {
+  const Dims& d = c.d; const Params& P = c.P; const WS& w = c.w; const score_state_t* st = c.st; const score_batch_t* bt = c.bt;
+  float* ws = c.ws; const float* W = c.W; const int B = c.B, x3 = c.x3; hipStream_t s = c.s;
+  const float keep_prob = f.keep_prob;
+  const int dflag = keep_prob < 1.f ? GF_DROP : 0;
+  // the whole head in one launch (head_fused.hip); shapes it does not cover take the layer-by-layer path
+  int hrc = c.fl.head_unfused ? SCORE_E_SHAPE
+                : score_launch_head_fwd_fused(B, d.Dhead, FC1, FC2, ws + w.head_inp, W + P.bn_g, W + P.bn_b, c.rs, W + P.fc_w[0],
+                                              W + P.fc_b[0], W + P.fc_w[1], W + P.fc_b[1], W + P.fc_w[2], W + P.fc_b[2],
+                                              keep_prob, f.mask0, f.mask1, f.seed, f.seed ^ 0x5DEECE66Dull,
+                                              bt->label, ws + w.bn, ws + w.f1, ws + w.f2, ws + w.logit, ws + w.y_pred,
+                                              ws + w.lossb, ws + w.dlogit, c.Bg, s,
+                                              st->step_scalars ? &st->step_scalars->drop_seed : nullptr, ws + w.dz2,
+                                              c.fl.head_fused_any_b ? 1 : 0);
+  if (hrc == 0) return loss_tail(c, f.sd, f.reg_lambda);       // (dz2 came with the head)
+  if (hrc != SCORE_E_SHAPE) return hrc;
+  if (st->step_scalars && keep_prob < 1.f) return SCORE_E_SHAPE;   // the layer-by-layer path takes its seed by value
+  G(score_launch_bn_fwd(B, d.Dhead, ws + w.head_inp, W + P.bn_g, W + P.bn_b, c.rs, ws + w.bn, s));
+  G(gemm_mode_call(x3, 0, B, FC1, d.Dhead, ws + w.bn, d.Dhead, W + P.fc_w[0], FC1, ws + w.f1, FC1, W + P.fc_b[0],
+                   GF_BIAS | GF_RELU | dflag, keep_prob, f.mask0, f.seed, c.scratch, w.scratch_floats, s));
+  G(gemm_mode_call(x3, 0, B, FC2, FC1, ws + w.f1, FC1, W + P.fc_w[1], FC2, ws + w.f2, FC2, W + P.fc_b[1],
+                   GF_BIAS | GF_RELU | dflag, keep_prob, f.mask1, f.seed ^ 0x5DEECE66Dull, c.scratch, w.scratch_floats, s));
+  // fc3, sigmoid, log-loss, l2 (:74-94)
+  G(score_launch_head_out(B, FC2, ws + w.f2, W + P.fc_w[2], W + P.fc_b[2], bt->label, ws + w.logit, ws + w.y_pred,
+                          ws + w.lossb, ws + w.dlogit, ws + w.loss, f.reg_lambda, ws + w.part, c.Bg, s, st->id_status));
+  if (st->loss_done_event) HIPTRY(hipEventRecord((hipEvent_t)st->loss_done_event, s));
+  return 0;
+}
+
+// SCORE and its ablations, RRN: GRUs, then the attention (SCORE, RCA, SCORE_USER, SCORE_ITEM) or the final states, the fc head
+int fwd_slice(const Pass& c, const FwdState& f) {
+  const Dims& d = c.d; const WS& w = c.w; float* ws = c.ws; const int B = c.B, H = c.H; hipStream_t s = c.s;
+  void* const* stage_events = f.stage_events;
+  HIPTRY(hipStreamWaitEvent(s, f.sd->wx, 0));
   const float* xin[2] = {ws + w.xside[0], ws + w.xside[1]};
-  if (d.gcmc) {
-    for (int sd = 0; sd < 2; ++sd) {
-      const int Dx = d.Is[sd];
-      G(gemm_mode_call(x3, 0, BT, Dx, Dx, ws + w.xside[sd], d.I, W + P.gm_a[sd], Dx, ws + w.gcmc_a[sd], Dx, nullptr, GF_RELU, 1.f,
-                       nullptr, 0, scratch, w.scratch_floats, s));
-      G(gemm_mode_call(x3, 0, BT, Dx, Dx, ws + w.gcmc_a[sd], Dx, W + P.gm_c[sd], Dx, ws + w.gcmc_z[sd], Dx, nullptr, GF_RELU, 1.f,
-                       nullptr, 0, scratch, w.scratch_floats, s));
-      xin[sd] = ws + w.gcmc_z[sd];
-    }
-  }
-  if (d.delf) {
-    // DELF: both attentions, the fusion MLPs, y and the loss terms in ONE launch behind the gather (the target rows come from
-    // the side stream); no dropout, keep_prob has no effect
-    HIPTRY(hipStreamWaitEvent(s, sd->join, 0));
-    DelfArgs a;
-    delf_args(c, &a);
-    G(score_delf_fwd(a, s));
-    EV(2);
-    EV(3);
-    G(loss_tail(c, sd, reg_lambda));
-    EV(4);
-    return 0;
-  }
-  // GRUs (:205-208): hoisted x-projection, then the persistent recurrence
-  if (d.caser) {
-    // Caser has none: both convolutions, the max over the windows and the scalar dense in ONE launch, straight into head_inp
-    CaserArgs a;
-    caser_args(c, nullptr, &a);
-    G(score_caser_fwd(a, s));
-  } else if (d.g4r) {
-    HIPTRY(hipStreamWaitEvent(s, sd->wx, 0));
-    G(g4r_grus_fwd(c));
-  } else {
-    HIPTRY(hipStreamWaitEvent(s, sd->wx, 0));
-    GruArgs ga;
-    gru_header(c, &ga);
-    float* xp[2] = {ws + w.xproj[0], ws + w.xproj[1]};
-    if (d.Is[0] == d.Is[1]) {    // both sides' projections in ONE grouped launch (each with its own bias row)
-      if (panel_x) {
-        G(panel_launch(c, 0, xin, xp));
-      } else {
-        const float* Bx[2] = {wxcat(c, 0), wxcat(c, 1)};
-        const float* bx[2] = {Bx[0] + (int64_t)d.Is[0] * 3 * H, Bx[1] + (int64_t)d.Is[1] * 3 * H};
-        G(score_gemm_same_shape(0, 2, BT, 3 * H, d.Is[0], xin, x_ld(d, 0), Bx, 3 * H, xp, 3 * H, GF_BIAS, x3 != 0, scratch,
-                                w.scratch_floats, s, bx));
-      }
-    }
-    for (int sd = 0; sd < 2; ++sd) {
-      // x . [Wx_gates | Wx_cand] + [b_gates | b_cand]: one GEMM per side on the concatenated copy
-      const float* cat = wxcat(c, sd);
-      if (d.Is[0] != d.Is[1])
-        G(gemm_mode_call(x3, 0, BT, 3 * H, d.Is[sd], xin[sd], x_ld(d, sd), cat, 3 * H, xp[sd], 3 * H, cat + (int64_t)d.Is[sd] * 3 * H,
-                         GF_BIAS, 1.f, nullptr, 0, scratch, w.scratch_floats, s));
-      gru_side(c, sd, &ga.s[sd]);
-      ga.s[sd].xproj = xp[sd]; ga.s[sd].final_state = ws + w.gru_final[sd];
-    }
-    G(score_gru_fwd_multi(ga, 2, s));
-  }
+  G(fwd_grus_two_sided(c, f, xin));
   EV(2);
   if (d.attn) {
-    // temporal attention (:169-186, 210-215); q, Weff/Wq and qz come from the side stream
-    HIPTRY(hipStreamWaitEvent(s, sd->join, 0));
-    // all of it in one launch (head_fused.hip) where the shape allows ...
-    int frc = fl.attn_unfused ? SCORE_E_SHAPE
-                  : score_launch_attn_fwd_fused(B, T, H, d.NI, AT1, AT2, ws + w.q, ws + w.gru_out[0], ws + w.gru_out[1],
-                                                ws + w.info, ws + w.weff, ws + w.qz, W + P.at_w[2], W + P.at_b[2],
-                                                W + P.at_w[3], W + P.at_b[3], bt->length, ws + w.ainp, ws + w.a1, ws + w.a2,
-                                                ws + w.att_score, ws + w.head_inp, d.Dhead, d.off_u, d.off_i, s,
-                                                SCORE_WEFF_COPIES, c.weff_stride);
-    if (frc != 0 && frc != SCORE_E_SHAPE) return frc;
-    if (frc == SCORE_E_SHAPE) {
-    G(score_launch_attn_build_inp(B, T, H, d.NI, ws + w.q, ws + w.gru_out[0], ws + w.gru_out[1], ws + w.info,
-                                  ws + w.ainp, s));
-    G(gemm_mode_call(x3, 0, BT, AT1, 2 * d.Dk, ws + w.ainp, 2 * d.Dk, ws + w.weff, AT1, ws + w.a1, AT1, ws + w.qz,
-                     GF_BIAS | GF_RELU | (T << 16), 1.f, nullptr, 0, scratch, w.scratch_floats, s));
-    // dense_4, dense_5, mask, softmax over T and the pooling: one launch, a block per sample (head.hip)
-    int trc = fl.attn_unfused ? SCORE_E_SHAPE
-                  : score_launch_attn_tail_fwd(B, T, H, AT1, AT2, ws + w.a1, W + P.at_w[2], W + P.at_b[2], W + P.at_w[3],
-                                               W + P.at_b[3], bt->length, ws + w.gru_out[0], ws + w.gru_out[1], ws + w.a2,
-                                               ws + w.att_score, ws + w.head_inp, d.Dhead, d.off_u, d.off_i, s);
-    if (trc != 0 && trc != SCORE_E_SHAPE) return trc;
-    if (trc == SCORE_E_SHAPE) {
-      G(gemm_mode_call(x3, 0, BT, AT2, AT1, ws + w.a1, AT1, W + P.at_w[2], AT2, ws + w.a2, AT2, W + P.at_b[2],
-                   GF_BIAS | GF_RELU, 1.f, nullptr, 0, scratch, w.scratch_floats, s));
-      G(score_launch_attn_pool_fwd(B, T, H, AT2, ws + w.a2, W + P.at_w[3], W + P.at_b[3], bt->length,
-                                   ws + w.gru_out[0], ws + w.gru_out[1], ws + w.att_score, ws + w.head_inp, d.Dhead,
-                                   d.off_u, d.off_i, s));
-    }
-    }     // (... else the separate launches above)
-  } else if (d.g4r) {
-    // GRU4Rec (point_model.py:134): layer 2's final state feeds the head
-    G(score_launch_copy2d(B, H, ws + w.gru_final[1], H, ws + w.head_inp, d.Dhead, s));
-  } else if (!d.gcmc && !d.caser) {
+    G(fwd_attention(c, f));
+  } else {
     // RIA: final GRU states feed the head (:244-249)
     G(score_launch_copy2d(B, H, ws + w.gru_final[0], H, ws + w.head_inp, d.Dhead, s));
     G(score_launch_copy2d(B, H, ws + w.gru_final[1], H, ws + w.head_inp + H, d.Dhead, s));
   }
   EV(3);
-  // build_fc_net (:68-76)
-  const int dflag = keep_prob < 1.f ? GF_DROP : 0;
-  if (!d.attn) HIPTRY(hipStreamWaitEvent(s, sd->join, 0));     // (with attention the join was waited for there)
-  if (d.gcmc) {
-    // GCMC (:199-203): y = exp(a) / (exp(a) + exp(c)) of the final states, its log-loss term and dL/da (gcmc.hip); no dropout,
-    // keep_prob has no effect
-    G(score_launch_gcmc_head_fwd(B, H, ws + w.gru_final[0], ws + w.gru_final[1], W + P.gm_4, W + P.gm_5, bt->label, ws + w.y_pred,
-                                 ws + w.lossb, ws + w.gcmc_pn, ws + w.gcmc_pn + (int64_t)B * H, ws + w.gcmc_g, Bg, s));
-    G(loss_tail(c, sd, reg_lambda));
-    EV(4);
-    return 0;
-  }
-  // the whole head in one launch (head_fused.hip); shapes it does not cover take the layer-by-layer path
-  int hrc = fl.head_unfused ? SCORE_E_SHAPE
-                : score_launch_head_fwd_fused(B, d.Dhead, FC1, FC2, ws + w.head_inp, W + P.bn_g, W + P.bn_b, c.rs, W + P.fc_w[0],
-                                              W + P.fc_b[0], W + P.fc_w[1], W + P.fc_b[1], W + P.fc_w[2], W + P.fc_b[2],
-                                              keep_prob, drop_mask0, drop_mask1, drop_seed, drop_seed ^ 0x5DEECE66Dull,
-                                              bt->label, ws + w.bn, ws + w.f1, ws + w.f2, ws + w.logit, ws + w.y_pred,
-                                              ws + w.lossb, ws + w.dlogit, Bg, s,
-                                              st->step_scalars ? &st->step_scalars->drop_seed : nullptr, ws + w.dz2,
-                                              fl.head_fused_any_b ? 1 : 0);
-  if (hrc == 0) {
-    G(loss_tail(c, sd, reg_lambda));       // (dz2 came with the head)
-  } else if (hrc == SCORE_E_SHAPE) {
-    if (st->step_scalars && keep_prob < 1.f) return SCORE_E_SHAPE;   // the layer-by-layer path takes its seed by value
-    G(score_launch_bn_fwd(B, d.Dhead, ws + w.head_inp, W + P.bn_g, W + P.bn_b, c.rs, ws + w.bn, s));
-    G(gemm_mode_call(x3, 0, B, FC1, d.Dhead, ws + w.bn, d.Dhead, W + P.fc_w[0], FC1, ws + w.f1, FC1, W + P.fc_b[0],
-                 GF_BIAS | GF_RELU | dflag, keep_prob, drop_mask0, drop_seed, scratch, w.scratch_floats, s));
-    G(gemm_mode_call(x3, 0, B, FC2, FC1, ws + w.f1, FC1, W + P.fc_w[1], FC2, ws + w.f2, FC2, W + P.fc_b[1],
-                 GF_BIAS | GF_RELU | dflag, keep_prob, drop_mask1, drop_seed ^ 0x5DEECE66Dull, scratch,
-                 w.scratch_floats, s));
-    // fc3, sigmoid, log-loss, l2 (:74-94)
-    G(score_launch_head_out(B, FC2, ws + w.f2, W + P.fc_w[2], W + P.fc_b[2], bt->label, ws + w.logit, ws + w.y_pred,
-                            ws + w.lossb, ws + w.dlogit, ws + w.loss, reg_lambda, ws + w.part, Bg, s, st->id_status));
-    if (st->loss_done_event) HIPTRY(hipEventRecord((hipEvent_t)st->loss_done_event, s));
-  } else {
-    return hrc;
-  }
+  if (!d.attn) HIPTRY(hipStreamWaitEvent(s, f.sd->join, 0));     // (with attention the join was waited for there)
+  G(fwd_fc_head(c, f));
   EV(4);
   return 0;
 }
 
-extern "C" int score_backward(const score_config_t* cfg, const score_state_t* st, const score_batch_t* bt,
-                              float keep_prob, float* gw, float* grad_table, void* const* stage_events,
-                              void* stream) {
+int fwd_gcmc(const Pass& c, const FwdState& f) {
+  const Dims& d = c.d; const Params& P = c.P; const WS& w = c.w;
+  float* ws = c.ws; const float* W = c.W; const int B = c.B, H = c.H, BT = c.BT; hipStream_t s = c.s;
+  void* const* stage_events = f.stage_events;
+  // GCMC (slice_model.py:182-190): per side A = relu(S Wa), Z = relu(A Wc), S the 1-hop sum the gather left in xside.  TF applies
+  // Wa to every neighbour and sums; summing first is the same by linearity, with K times fewer flops
+  for (int sd = 0; sd < 2; ++sd) {
+    const int Dx = d.Is[sd];
+    G(gemm_mode_call(c.x3, 0, BT, Dx, Dx, ws + w.xside[sd], d.I, W + P.gm_a[sd], Dx, ws + w.gcmc_a[sd], Dx, nullptr, GF_RELU, 1.f,
+                     nullptr, 0, c.scratch, w.scratch_floats, s));
+    G(gemm_mode_call(c.x3, 0, BT, Dx, Dx, ws + w.gcmc_a[sd], Dx, W + P.gm_c[sd], Dx, ws + w.gcmc_z[sd], Dx, nullptr, GF_RELU, 1.f,
+                     nullptr, 0, c.scratch, w.scratch_floats, s));
+  }
+  HIPTRY(hipStreamWaitEvent(s, f.sd->wx, 0));
+  const float* xin[2] = {ws + w.gcmc_z[0], ws + w.gcmc_z[1]};
+  G(fwd_grus_two_sided(c, f, xin));
+  EV(2);
+  EV(3);
+  HIPTRY(hipStreamWaitEvent(s, f.sd->join, 0));
+  // GCMC (:199-203): y = exp(a) / (exp(a) + exp(c)) of the final states, its log-loss term and dL/da (gcmc.hip); no dropout,
+  // keep_prob has no effect
+  G(score_launch_gcmc_head_fwd(B, H, ws + w.gru_final[0], ws + w.gru_final[1], W + P.gm_4, W + P.gm_5, c.bt->label, ws + w.y_pred,
+                               ws + w.lossb, ws + w.gcmc_pn, ws + w.gcmc_pn + (int64_t)B * H, ws + w.gcmc_g, c.Bg, s));
+  G(loss_tail(c, f.sd, f.reg_lambda));
+  EV(4);
+  return 0;
+}
+
+int fwd_g4r(const Pass& c, const FwdState& f) {
+  hipStream_t s = c.s;
+  void* const* stage_events = f.stage_events;
+  HIPTRY(hipStreamWaitEvent(s, f.sd->wx, 0));
+  G(g4r_grus_fwd(c));
+  EV(2);
+  // GRU4Rec (point_model.py:134): layer 2's final state feeds the head
+  G(score_launch_copy2d(c.B, c.H, c.ws + c.w.gru_final[1], c.H, c.ws + c.w.head_inp, c.d.Dhead, s));
+  EV(3);
+  HIPTRY(hipStreamWaitEvent(s, f.sd->join, 0));
+  G(fwd_fc_head(c, f));
+  EV(4);
+  return 0;
+}
+
+int fwd_caser(const Pass& c, const FwdState& f) {
+  hipStream_t s = c.s;
+  void* const* stage_events = f.stage_events;
+  // Caser has no GRU: both convolutions, the max over the windows and the scalar dense in ONE launch, straight into head_inp
+  CaserArgs a;
+  caser_args(c, nullptr, &a);
+  G(score_caser_fwd(a, s));
+  EV(2);
+  EV(3);
+  HIPTRY(hipStreamWaitEvent(s, f.sd->join, 0));
+  G(fwd_fc_head(c, f));
+  EV(4);
+  return 0;
+}
+
+int fwd_delf(const Pass& c, const FwdState& f) {
+  hipStream_t s = c.s;
+  void* const* stage_events = f.stage_events;
+  // DELF: both attentions, the fusion MLPs, y and the loss terms in ONE launch behind the gather (the target rows come from
+  // the side stream); no dropout, keep_prob has no effect
+  HIPTRY(hipStreamWaitEvent(s, f.sd->join, 0));
+  DelfArgs a;
+  delf_args(c, &a);
+  G(score_delf_fwd(a, s));
+  EV(2);
+  EV(3);
+  G(loss_tail(c, f.sd, f.reg_lambda));
+  EV(4);
+  return 0;
+}
+}  // namespace
+
+extern "C" int score_forward(const score_config_t* cfg, const score_state_t* st, const score_batch_t* bt,
+                             float reg_lambda, float keep_prob, const uint8_t* drop_mask0,
+                             const uint8_t* drop_mask1, uint64_t drop_seed, void* const* stage_events,
+                             void* stream) {
   Pass c;
   SCORE_TRY(make_dims(cfg, &c.d));
-  if (!st || !bt || !st->table || !st->w || !st->workspace || !gw || !grad_table || bt->B <= 0)
+  if (!st || !bt || !st->table || !st->w || !st->workspace || bt->B <= 0) return SCORE_E_BADARG;
+  if (!bt->user_1hop || !bt->user_2hop || !bt->item_1hop || !bt->item_2hop || !bt->target_user ||
+      !bt->target_item || !bt->label || !bt->length)
     return SCORE_E_BADARG;
-  if (c.d.delf && (!bt->length || !bt->length2)) return SCORE_E_BADARG;
+  if (c.d.family == FAM_DELF && !bt->length2) return SCORE_E_BADARG;        // (item_seq_length: the one model type that reads it)
+  if (!(keep_prob > 0.f) || keep_prob > 1.f) return SCORE_E_BADARG;
   SCORE_TRY(pass_fill(&c, st, bt, stream));
-  const Dims& d = c.d; const Params& P = c.P; const WS& w = c.w; const Flags& fl = c.fl;
-  const int B = c.B, T = c.T, H = c.H, BT = c.BT, x3 = c.x3;
-  hipStream_t s = c.s;
   {
-    PsPlan pp;
-    if (!fl.ps_fwd_only && ps_path(d, st, bt, T, &pp))
-      return backward_ps(c, pp, keep_prob, gw, grad_table, stage_events);
+    PsPlan pp;       // the reference's own shapes: the whole pass as one kernel per sample (persample.h)
+    if (!c.fl.ps_bwd_only && ps_path(c.d, st, bt, c.T, &pp))
+      return forward_ps(c, pp, reg_lambda, keep_prob, drop_mask0, drop_mask1, drop_seed, stage_events);
   }
-  float* ws = c.ws; const float* W = c.W; float* scratch = c.scratch;
-  const int64_t SF = w.scratch_floats;
+  FwdState f = {reg_lambda, keep_prob, drop_mask0, drop_mask1, drop_seed, stage_events, nullptr, false};
+  SCORE_TRY(fwd_open(c, &f));
+  switch (c.d.family) {
+    case FAM_SLICE: return fwd_slice(c, f);
+    case FAM_GCMC: return fwd_gcmc(c, f);
+    case FAM_G4R: return fwd_g4r(c, f);
+    case FAM_CASER: return fwd_caser(c, f);
+    case FAM_DELF: return fwd_delf(c, f);
+  }
+  return SCORE_E_BADARG;
+}
+
+// ---------------------------------------------------------------- the layer-by-layer backward pass
+// ONE function per family (bwd_slice .. bwd_delf), each the list of its stages: bwd_open, the head's backward, the attention's
+// backward or the final states' gradients, bwd_side_products, the recurrences' backward, the input gradients, bwd_close.
+namespace {
+// score_backward's arguments behind the batch, and what the stages of a pass hand to each other
+struct BwdState {
+  float keep_prob; float* gw; float* grad_table; void* const* stage_events;
+  SideStream* side;
   GradQueues q;
-  queues_init(&q);
-  GemmQueue& gq = q.gq;
-  ColsumJobs& cq = q.cq;
-  // The dense gradient starts from zero (some of its pieces are accumulated, some variables of some model types get
-  // none).  Nothing on the main stream writes it before the side stream's join below -- every weight / bias
-  // gradient is queued -- so the fill runs on the side stream, off the chain of dependent launches.
+  const float* dfinal[2];     // dL/d final state of each recurrence (null: none enters there)
+  int gru_bias_rows;          // GruArgs.bias_slab_rows of the backward recurrence that ran
+};
+// region of the first flush of the queued products (bwd_side_products) in the split-K slabs; the second one's (bwd_close) follows
+inline int64_t slab_half(const WS& w) { return (w.dwslab_floats / 4) & ~(int64_t)3; }
+
+// The dense gradient starts from zero (some of its pieces are accumulated, some variables of some model types get
+// none).  Nothing on the main stream writes it before the side stream's join (bwd_side_products) -- every weight / bias
+// gradient is queued -- so the fill runs on the side stream, off the chain of dependent launches.  Ends with EV(0).
+int bwd_open(const Pass& c, BwdState* b) {
+  hipStream_t s = c.s;
+  void* const* stage_events = b->stage_events;
   SideStream* side = nullptr;
-  G(side_stream(st, s, &side));
+  G(side_stream(c.st, s, &side));
+  b->side = side;
   // (the fill needs the side stream behind the LAST readers of grad_w -- the previous step's optimizer --, not behind this pass's
   //  forward: score_forward of this step, on this stream and context, forked the side stream behind them already.  A record between
   //  the head's forward and backward costs the launch stream a ~6-us bubble; only a caller that skipped the forward pays it.)
   const bool forked = side->fwd_on == s;
   side->fwd_on = nullptr;
   if (!forked) G(fork_side(side, s));
-  HIPTRY(hipMemsetAsync(gw, 0, P.n_floats * sizeof(float), side->st));
-
+  HIPTRY(hipMemsetAsync(b->gw, 0, c.P.n_floats * sizeof(float), side->st));
   EV(0);
-  if (d.delf) {
-    // ---- DELF: the whole backward of the model between the scatter and the loss in ONE launch (delf.hip): dxside, dhead's
-    // target columns, and the rows the queued products and column sums below are taken from -- those run on the side stream,
-    // forked behind this launch, beside the target rows' and the embedding rows' scatter
-    DelfArgs a;
-    delf_args(c, &a);
-    G(score_delf_bwd(a, s));
-    G(queue_delf(c, &q, gw));
-  } else if (d.gcmc) {
-    // ---- GCMC's head (slice_model.py:199-201): dh_u, dh_i into dfinal, and the rows +-g h_u whose products with h_i are
-    // dW4 / dW5 (gcmc.hip)
-    G(score_launch_gcmc_head_bwd(B, H, ws + w.gru_final[0], W + P.gm_4, W + P.gm_5, ws + w.gcmc_pn, ws + w.gcmc_pn + (int64_t)B * H,
-                                 ws + w.gcmc_g, ws + w.dfinal[0], ws + w.dfinal[1], ws + w.gcmc_gu, ws + w.gcmc_gu + (int64_t)B * H, s));
-    G(gemm_queue_add(&gq, H, H, B, ws + w.gru_final[1], H, ws + w.gcmc_gu, H, gw + P.gm_4, H));
-    G(gemm_queue_add(&gq, H, H, B, ws + w.gru_final[1], H, ws + w.gcmc_gu + (int64_t)B * H, H, gw + P.gm_5, H));
-  } else {
-    // ---- head (score.py:68-81)
-    // fc3: dz2 = [f2>0] dlogit w3 / keep
-    if (fl.head_unfused || !score_head_fwd_fused_fits(B, d.Dhead, FC1, FC2))     // (else score_forward's fused head wrote dz2)
-      G(score_launch_outer_relu_bwd(B, FC2, ws + w.dlogit, W + P.fc_w[2], ws + w.f2, keep_prob, ws + w.dz2, s));
-    // dz1, d bn1, d head input and bn1's d gamma terms: one launch (head_fused.hip) ...
-    int hbrc = fl.head_unfused ? SCORE_E_SHAPE
-                   : score_launch_head_bwd_fused(B, d.Dhead, FC1, FC2, ws + w.dz2, W + P.fc_w[1], ws + w.f1, keep_prob,
-                                                 W + P.fc_w[0], ws + w.head_inp, W + P.bn_g, c.rs, ws + w.dz1, ws + w.dbn,
-                                                 ws + w.dhead, ws + w.dgstage, s);
-    if (hbrc != 0 && hbrc != SCORE_E_SHAPE) return hbrc;
-    // (bn1's d gamma / d beta behind the fused kernel: column sums of what it wrote)
-    G(queue_head(c, &q, gw, hbrc == 0));
-    if (hbrc == SCORE_E_SHAPE) {     // ... or layer by layer
-      G(gemm_mode_call(x3, 1, B, FC1, FC2, ws + w.dz2, FC2, W + P.fc_w[1], FC2, ws + w.dz1, FC1, nullptr, GF_RELUGRAD, keep_prob,
-                       reinterpret_cast<const uint8_t*>(ws + w.f1), 0, scratch, SF, s));   // relu/dropout mask of fc1 in the epilogue
-      G(gemm_mode_call(x3, 1, B, d.Dhead, FC1, ws + w.dz1, FC1, W + P.fc_w[0], FC1, ws + w.dbn, d.Dhead, nullptr, 0, 1.f,
-                   nullptr, 0, scratch, SF, s));
-      G(score_launch_bn_bwd(B, d.Dhead, ws + w.head_inp, W + P.bn_g, c.rs, ws + w.dbn, ws + w.dhead, gw + P.bn_g,
-                            gw + P.bn_b, ws + w.dgstage, scratch, SF, &cq, s));
-    }
-  }
+  return 0;
+}
 
-  EV(1);
-  const float* dfinal[2] = {nullptr, nullptr};
+// ---- head (score.py:68-81)
+int bwd_fc_head(const Pass& c, BwdState* b) {
+  const Dims& d = c.d; const Params& P = c.P; const WS& w = c.w;
+  float* ws = c.ws; const float* W = c.W; float* gw = b->gw; const int B = c.B, x3 = c.x3; hipStream_t s = c.s;
+  const float keep_prob = b->keep_prob; const int64_t SF = w.scratch_floats;
+  // fc3: dz2 = [f2>0] dlogit w3 / keep
+  if (c.fl.head_unfused || !score_head_fwd_fused_fits(B, d.Dhead, FC1, FC2))     // (else score_forward's fused head wrote dz2)
+    G(score_launch_outer_relu_bwd(B, FC2, ws + w.dlogit, W + P.fc_w[2], ws + w.f2, keep_prob, ws + w.dz2, s));
+  // dz1, d bn1, d head input and bn1's d gamma terms: one launch (head_fused.hip) ...
+  int hbrc = c.fl.head_unfused ? SCORE_E_SHAPE
+                 : score_launch_head_bwd_fused(B, d.Dhead, FC1, FC2, ws + w.dz2, W + P.fc_w[1], ws + w.f1, keep_prob,
+                                               W + P.fc_w[0], ws + w.head_inp, W + P.bn_g, c.rs, ws + w.dz1, ws + w.dbn,
+                                               ws + w.dhead, ws + w.dgstage, s);
+  if (hbrc != 0 && hbrc != SCORE_E_SHAPE) return hbrc;
+  // (bn1's d gamma / d beta behind the fused kernel: column sums of what it wrote)
+  G(queue_head(c, &b->q, gw, hbrc == 0));
+  if (hbrc == SCORE_E_SHAPE) {     // ... or layer by layer
+    G(gemm_mode_call(x3, 1, B, FC1, FC2, ws + w.dz2, FC2, W + P.fc_w[1], FC2, ws + w.dz1, FC1, nullptr, GF_RELUGRAD, keep_prob,
+                     reinterpret_cast<const uint8_t*>(ws + w.f1), 0, c.scratch, SF, s));   // relu/dropout mask of fc1 in the epilogue
+    G(gemm_mode_call(x3, 1, B, d.Dhead, FC1, ws + w.dz1, FC1, W + P.fc_w[0], FC1, ws + w.dbn, d.Dhead, nullptr, 0, 1.f,
+                     nullptr, 0, c.scratch, SF, s));
+    G(score_launch_bn_bwd(B, d.Dhead, ws + w.head_inp, W + P.bn_g, c.rs, ws + w.dbn, ws + w.dhead, gw + P.bn_g,
+                          gw + P.bn_b, ws + w.dgstage, c.scratch, SF, &b->q.cq, s));
+  }
+  return 0;
+}
+
+// ---- temporal attention (score.py:169-186, 214-215)
+int bwd_attention(const Pass& c, BwdState* b) {
+  const Dims& d = c.d; const Params& P = c.P; const WS& w = c.w; const score_batch_t* bt = c.bt;
+  float* ws = c.ws; const float* W = c.W; const int B = c.B, T = c.T, H = c.H, BT = c.BT, x3 = c.x3; hipStream_t s = c.s;
+  const int64_t SF = w.scratch_floats;
+  G(queue_attn(c, &b->q, b->gw));
+  // pooling / softmax / dense_5 backward and, in the same launch, dense_4's (da1 with dense_3's relu mask)
+  // (on small batches the fused attention backward below does this part too -- one launch less: 0.0218 -> 0.0183 ms for
+  //  the stage at the reference's own shape; at cfg-3, where a workgroup per four samples serialises what 1024 small
+  //  workgroups do side by side, the separate launch stays: 0.0613 vs 0.0629)
+  const bool pool_in_fused = !c.fl.attn_unfused && (int64_t)B * T < 8192 &&
+                             score_attn_inp_bwd_fused_fits(B, T, H, d.NI, AT1, AT2, d.Dhead, d.off_u, d.off_i, true);
+  int prc = pool_in_fused ? 0 : c.fl.attn_unfused ? SCORE_E_SHAPE
+                : score_launch_attn_pool_bwd(B, T, H, AT2, ws + w.a2, W + P.at_w[3], bt->length, ws + w.gru_out[0],
+                                             ws + w.gru_out[1], ws + w.att_score, ws + w.dhead, d.Dhead, d.off_u,
+                                             d.off_i, ws + w.ds, ws + w.da2, s, AT1, W + P.at_w[2], ws + w.a1, ws + w.da1);
+  if (prc != 0 && prc != SCORE_E_SHAPE) return prc;
+  const bool da1_done = prc == 0;
+  if (!da1_done) {
+    G(score_launch_attn_pool_bwd(B, T, H, AT2, ws + w.a2, W + P.at_w[3], bt->length, ws + w.gru_out[0],
+                                 ws + w.gru_out[1], ws + w.att_score, ws + w.dhead, d.Dhead, d.off_u, d.off_i,
+                                 ws + w.ds, ws + w.da2, s));
+    G(gemm_mode_call(x3, 1, BT, AT1, AT2, ws + w.da2, AT2, W + P.at_w[2], AT2, ws + w.da1, AT1, nullptr, GF_RELUGRAD, 1.f,
+                     reinterpret_cast<const uint8_t*>(ws + w.a1), 0, c.scratch, SF, s));    // relu mask of dense_3 in the epilogue
+  }
+  // (sum_t da1 -> adzsum feeds the query branch only: computed on the side stream, bwd_side_products)
+  // d inp = da1 . Weff^T and its way into d (states, atten_info, q): one launch where the shape allows (head_fused.hip).
+  // dq = sum_t d(q*k).k here; the per-sample q-term gradient dzsum . Wq^T is added, and the query projection's
+  // backward runs, on the side stream (bwd_side_products: beside the recurrence, only the target rows consume them)
+  int brc = c.fl.attn_unfused ? SCORE_E_SHAPE
+            : pool_in_fused
+                ? score_launch_attn_inp_bwd_fused(B, T, H, d.NI, AT1, nullptr, ws + w.weff, ws + w.q, ws + w.gru_out[0],
+                                                  ws + w.gru_out[1], ws + w.info, ws + w.att_score, ws + w.dhead, d.Dhead,
+                                                  d.off_u, d.off_i, ws + w.dgru[0], ws + w.dgru[1], ws + w.dinfo, ws + w.dq, s,
+                                                  AT2, ws + w.a2, ws + w.a1, W + P.at_w[3], W + P.at_w[2], bt->length,
+                                                  ws + w.ds, ws + w.da2, ws + w.da1)
+                : score_launch_attn_inp_bwd_fused(B, T, H, d.NI, AT1, ws + w.da1, ws + w.weff, ws + w.q, ws + w.gru_out[0],
+                                                  ws + w.gru_out[1], ws + w.info, ws + w.att_score, ws + w.dhead, d.Dhead,
+                                                  d.off_u, d.off_i, ws + w.dgru[0], ws + w.dgru[1], ws + w.dinfo, ws + w.dq, s);
+  if (pool_in_fused && brc != 0) return brc == SCORE_E_SHAPE ? SCORE_E_BADARG : brc;     // (the predicate said it fits)
+  if (brc != 0 && brc != SCORE_E_SHAPE) return brc;
+  if (brc == SCORE_E_SHAPE) {
+    G(gemm_mode_call(x3, 1, BT, 2 * d.Dk, AT1, ws + w.da1, AT1, ws + w.weff, AT1, ws + w.dainp, 2 * d.Dk, nullptr, 0,
+                     1.f, nullptr, 0, c.scratch, SF, s));
+    G(score_launch_attn_inp_bwd(B, T, H, d.NI, ws + w.dainp, ws + w.q, ws + w.gru_out[0], ws + w.gru_out[1],
+                                ws + w.info, ws + w.att_score, ws + w.dhead, d.Dhead, d.off_u, d.off_i,
+                                nullptr, ws + w.dgru[0], ws + w.dgru[1], ws + w.dinfo, ws + w.dq, s));
+  }
+  return 0;
+}
+
+// atten_info is unused downstream of a model without attention
+int bwd_zero_dinfo(const Pass& c) {
+  HIPTRY(hipMemsetAsync(c.ws + c.w.dinfo, 0, (int64_t)c.BT * 4 * c.d.K * sizeof(float), c.s));
+  return 0;
+}
+// Without attention the gradient enters a recurrence through its final state only: dL/d final state of recurrence sd from the
+// H columns of dhead at head_col (head_col < 0: a head kernel wrote dfinal already), zeros as its dL/d out (zero_dout)
+int bwd_final_state(const Pass& c, BwdState* b, int sd, int head_col, bool zero_dout) {
+  const WS& w = c.w; float* ws = c.ws; const int H = c.H;
+  if (head_col >= 0) G(score_launch_copy2d(c.B, H, ws + w.dhead + head_col, c.d.Dhead, ws + w.dfinal[sd], H, c.s));
+  b->dfinal[sd] = ws + w.dfinal[sd];
+  if (zero_dout) HIPTRY(hipMemsetAsync(ws + w.dgru[sd], 0, (int64_t)c.BT * H * sizeof(float), c.s));
+  return 0;
+}
+// ... of both sides' recurrences (from_head: the states lie side by side at the front of dhead), then dinfo
+int bwd_final_states(const Pass& c, BwdState* b, bool from_head) {
+  for (int sd = 0; sd < 2; ++sd) G(bwd_final_state(c, b, sd, from_head ? sd * c.H : -1, true));
+  return bwd_zero_dinfo(c);
+}
+
+// The weight gradients queued so far (head, attention) have everything they need: on the side stream, beside the recurrence,
+// behind the attention's query branch; the `join` record
+int bwd_side_products(const Pass& c, BwdState* b) {
+  const Dims& d = c.d; const Params& P = c.P; const WS& w = c.w; const score_state_t* st = c.st;
+  float* ws = c.ws; const float* W = c.W; float* gw = b->gw; const int B = c.B, x3 = c.x3; hipStream_t s = c.s;
+  const int64_t SF = w.scratch_floats;
+  SideStream* side = b->side;
+  G(fork_side(side, s));
+  // Sharded path (scatter_mode 2): the caller runs several streams of its own (plan prefetch, gradient exchange,
+  // two communicators) and the hardware queues are shared -- measured there, this side stream's kernels run 2-4x
+  // slower and the join below stalls the scatter (0.27 -> 0.40 ms): the query branch stays on the main stream
+  const bool q_on_side = st->scatter_mode != 2;
+  hipStream_t qs = q_on_side ? side->st : s;
   if (d.attn) {
-    // ---- temporal attention (score.py:169-186, 214-215)
-    G(queue_attn(c, &q, gw));
-    // pooling / softmax / dense_5 backward and, in the same launch, dense_4's (da1 with dense_3's relu mask)
-    // (on small batches the fused attention backward below does this part too -- one launch less: 0.0218 -> 0.0183 ms for
-    //  the stage at the reference's own shape; at cfg-3, where a workgroup per four samples serialises what 1024 small
-    //  workgroups do side by side, the separate launch stays: 0.0613 vs 0.0629)
-    const bool pool_in_fused = !fl.attn_unfused && (int64_t)B * T < 8192 &&
-                               score_attn_inp_bwd_fused_fits(B, T, H, d.NI, AT1, AT2, d.Dhead, d.off_u, d.off_i, true);
-    int prc = pool_in_fused ? 0 : fl.attn_unfused ? SCORE_E_SHAPE
-                  : score_launch_attn_pool_bwd(B, T, H, AT2, ws + w.a2, W + P.at_w[3], bt->length, ws + w.gru_out[0],
-                                               ws + w.gru_out[1], ws + w.att_score, ws + w.dhead, d.Dhead, d.off_u,
-                                               d.off_i, ws + w.ds, ws + w.da2, s, AT1, W + P.at_w[2], ws + w.a1, ws + w.da1);
-    if (prc != 0 && prc != SCORE_E_SHAPE) return prc;
-    const bool da1_done = prc == 0;
-    if (!da1_done) {
-      G(score_launch_attn_pool_bwd(B, T, H, AT2, ws + w.a2, W + P.at_w[3], bt->length, ws + w.gru_out[0],
-                                   ws + w.gru_out[1], ws + w.att_score, ws + w.dhead, d.Dhead, d.off_u, d.off_i,
-                                   ws + w.ds, ws + w.da2, s));
-      G(gemm_mode_call(x3, 1, BT, AT1, AT2, ws + w.da2, AT2, W + P.at_w[2], AT2, ws + w.da1, AT1, nullptr, GF_RELUGRAD, 1.f,
-                       reinterpret_cast<const uint8_t*>(ws + w.a1), 0, scratch, SF, s));    // relu mask of dense_3 in the epilogue
-    }
-    // (sum_t da1 -> adzsum feeds the query branch only: computed on the side stream below)
-    // d inp = da1 . Weff^T and its way into d (states, atten_info, q): one launch where the shape allows (head_fused.hip).
-    // dq = sum_t d(q*k).k here; the per-sample q-term gradient dzsum . Wq^T is added, and the query projection's
-    // backward runs, on the side stream below (beside the recurrence: only the target rows consume them)
-    int brc = fl.attn_unfused ? SCORE_E_SHAPE
-              : pool_in_fused
-                  ? score_launch_attn_inp_bwd_fused(B, T, H, d.NI, AT1, nullptr, ws + w.weff, ws + w.q, ws + w.gru_out[0],
-                                                    ws + w.gru_out[1], ws + w.info, ws + w.att_score, ws + w.dhead, d.Dhead,
-                                                    d.off_u, d.off_i, ws + w.dgru[0], ws + w.dgru[1], ws + w.dinfo, ws + w.dq, s,
-                                                    AT2, ws + w.a2, ws + w.a1, W + P.at_w[3], W + P.at_w[2], bt->length,
-                                                    ws + w.ds, ws + w.da2, ws + w.da1)
-                  : score_launch_attn_inp_bwd_fused(B, T, H, d.NI, AT1, ws + w.da1, ws + w.weff, ws + w.q, ws + w.gru_out[0],
-                                                    ws + w.gru_out[1], ws + w.info, ws + w.att_score, ws + w.dhead, d.Dhead,
-                                                    d.off_u, d.off_i, ws + w.dgru[0], ws + w.dgru[1], ws + w.dinfo, ws + w.dq, s);
-    if (pool_in_fused && brc != 0) return brc == SCORE_E_SHAPE ? SCORE_E_BADARG : brc;     // (the predicate said it fits)
-    if (brc != 0 && brc != SCORE_E_SHAPE) return brc;
-    if (brc == SCORE_E_SHAPE) {
-      G(gemm_mode_call(x3, 1, BT, 2 * d.Dk, AT1, ws + w.da1, AT1, ws + w.weff, AT1, ws + w.dainp, 2 * d.Dk, nullptr, 0,
-                   1.f, nullptr, 0, scratch, SF, s));
-      G(score_launch_attn_inp_bwd(B, T, H, d.NI, ws + w.dainp, ws + w.q, ws + w.gru_out[0], ws + w.gru_out[1],
-                                  ws + w.info, ws + w.att_score, ws + w.dhead, d.Dhead, d.off_u, d.off_i,
-                                  nullptr, ws + w.dgru[0], ws + w.dgru[1], ws + w.dinfo, ws + w.dq, s));
-    }
-  } else {
-    // RIA: gradient enters through the final states only; atten_info is unused downstream (GCMC: the head kernel wrote dfinal)
-    for (int sd = 0; sd < 2 && !d.caser && !d.delf; ++sd) {       // (Caser, DELF: no state; dhead itself is what caser.hip reads / delf.hip writes)
-      if (d.g4r) {      // GRU4Rec: the head reads layer 2's final state only; layer 1's dout comes from layer 2's backward
-        if (sd == 0) continue;
-        G(score_launch_copy2d(B, H, ws + w.dhead, d.Dhead, ws + w.dfinal[1], H, s));
-        dfinal[1] = ws + w.dfinal[1];
-        if (g4r_stacked(d, fl)) continue;       // (the stacked kernel reads no dout of layer 2; the composed form's kernel does)
-      }
-      else if (!d.gcmc) G(score_launch_copy2d(B, H, ws + w.dhead + sd * H, d.Dhead, ws + w.dfinal[sd], H, s));
-      dfinal[sd] = ws + w.dfinal[sd];
-      HIPTRY(hipMemsetAsync(ws + w.dgru[sd], 0, (int64_t)BT * H * sizeof(float), s));
-    }
-    HIPTRY(hipMemsetAsync(ws + w.dinfo, 0, (int64_t)BT * 4 * d.K * sizeof(float), s));
+    float* scratch2 = q_on_side ? ws + w.scratch2 : c.scratch;
+    G(score_launch_attn_dzsum(B, c.T, AT1, ws + w.da1, ws + w.adzsum, qs));
+    // dq += dzsum . Wq^T ; dense_2 (query projection): dW, db queued, d query = dq . W^T
+    G(gemm_mode_call(x3, 1, B, d.Dk, AT1, ws + w.adzsum, AT1, ws + w.wq, AT1, ws + w.dq, d.Dk, nullptr, GF_ACC, 1.f, nullptr,
+                     0, scratch2, SF, qs));
+    G(queue_query(c, &b->q, gw));
+    G(gemm_mode_call(x3, 1, B, d.Dq, d.Dk, ws + w.dq, d.Dk, W + P.at_w[0], d.Dk, ws + w.dquery, d.Dq, nullptr, 0, 1.f,
+                     nullptr, 0, scratch2, SF, qs));
+    // d query is what the main stream needs from here (target_bwd_kernel): its own event, so that the wait there does not
+    // also sit behind the weight-gradient products and column sums that follow on this stream (at the small shapes the
+    // side chain is as long as the main one: the scatter stage waited ~30 us for it)
+    if (q_on_side) HIPTRY(hipEventRecord(side->wx, side->st));
+    else G(fork_side(side, s));       // dq is final on the main stream: the side stream (its weight-gradient product) follows it
   }
+  G(gemm_queue_flush(&b->q.gq, x3 != 0, ws + w.dwslab, slab_half(w), side->st));
+  // the folded first attention layer's gradient from the two products just reduced (head.hip): here, off the launch stream
+  if (d.attn) G(score_launch_attn_w1_grad(d.Dk, AT1, ws + w.dweff, ws + w.dwq, gw + P.at_w[1], side->st));
+  // the bias / bn1 gradients known so far (column sums of matrices that are final by now), same place
+  if (q_on_side) G(colsum_queue_flush(&b->q.cq, ws + w.cs_part, w.cs_part_floats / 2, side->st));
+  HIPTRY(hipEventRecord(side->join, side->st));
+  return 0;
+}
 
-  EV(2);
-  int gru_bias_rows = 0;
-  // ---- GRUs (score.py:205-208)
-  // the weight gradients queued so far (head, attention) have everything they need: beside the recurrence
-  const int64_t slab_half = (w.dwslab_floats / 4) & ~(int64_t)3;        // region of the first one
-  {
-    G(fork_side(side, s));
-    // Sharded path (scatter_mode 2): the caller runs several streams of its own (plan prefetch, gradient exchange,
-    // two communicators) and the hardware queues are shared -- measured there, this side stream's kernels run 2-4x
-    // slower and the join below stalls the scatter (0.27 -> 0.40 ms): the query branch stays on the main stream
-    const bool q_on_side = st->scatter_mode != 2;
-    hipStream_t qs = q_on_side ? side->st : s;
-    if (d.attn) {
-      float* scratch2 = q_on_side ? ws + w.scratch2 : scratch;
-      G(score_launch_attn_dzsum(B, T, AT1, ws + w.da1, ws + w.adzsum, qs));
-      // dq += dzsum . Wq^T ; dense_2 (query projection): dW, db queued, d query = dq . W^T
-      G(gemm_mode_call(x3, 1, B, d.Dk, AT1, ws + w.adzsum, AT1, ws + w.wq, AT1, ws + w.dq, d.Dk, nullptr, GF_ACC, 1.f, nullptr,
-                       0, scratch2, SF, qs));
-      G(queue_query(c, &q, gw));
-      G(gemm_mode_call(x3, 1, B, d.Dq, d.Dk, ws + w.dq, d.Dk, W + P.at_w[0], d.Dk, ws + w.dquery, d.Dq, nullptr, 0, 1.f,
-                       nullptr, 0, scratch2, SF, qs));
-      // d query is what the main stream needs from here (target_bwd_kernel): its own event, so that the wait there does not
-      // also sit behind the weight-gradient products and column sums that follow on this stream (at the small shapes the
-      // side chain is as long as the main one: the scatter stage waited ~30 us for it)
-      if (q_on_side) HIPTRY(hipEventRecord(side->wx, side->st));
-      else G(fork_side(side, s));       // dq is final on the main stream: the side stream (its weight-gradient product) follows it
-    }
-    G(gemm_queue_flush(&gq, x3 != 0, ws + w.dwslab, slab_half, side->st));
-    // the folded first attention layer's gradient from the two products just reduced (head.hip): here, off the launch stream
-    if (d.attn) G(score_launch_attn_w1_grad(d.Dk, AT1, ws + w.dweff, ws + w.dwq, gw + P.at_w[1], side->st));
-    // the bias / bn1 gradients known so far (column sums of matrices that are final by now), same place
-    if (q_on_side) G(colsum_queue_flush(&cq, ws + w.cs_part, w.cs_part_floats / 2, side->st));
-    HIPTRY(hipEventRecord(side->join, side->st));
+// ---- GRUs (score.py:205-208) of the slice models and GCMC: both sides' backward recurrences in one launch
+int bwd_grus_two_sided(const Pass& c, BwdState* b) {
+  GruArgs ga;
+  gru_header(c, &ga);
+  for (int sd = 0; sd < 2; ++sd) {
+    gru_side(c, sd, &ga.s[sd]);
+    gru_side_bwd(c, sd, b->dfinal[sd], &ga.s[sd]);
   }
-  if (d.delf) {
-    // (DELF: no recurrence; delf.hip wrote both dxside above)
-  } else if (d.caser) {
-    // Caser: d X into dxside[0] on the launch stream (dxside[1] carries nothing) and, beside it on the side stream -- behind the
-    // head's backward since the fork above, and behind the fill of grad_w --, the six variables' gradients, each batch sum in a
-    // fixed order; the join is recorded again behind them
-    HIPTRY(hipMemsetAsync(ws + w.dxside[1], 0, (int64_t)BT * d.I * sizeof(float), s));
-    CaserArgs a;
-    caser_args(c, gw, &a);
-    G(score_caser_bwd(a, s, side->st));
-    HIPTRY(hipEventRecord(side->join, side->st));
-  } else if (d.g4r) {
-    G(g4r_grus_bwd(c, dfinal[1], &gru_bias_rows));
-  } else {
-    GruArgs ga;
-    gru_header(c, &ga);
-    for (int sd = 0; sd < 2; ++sd) {
-      gru_side(c, sd, &ga.s[sd]);
-      gru_side_bwd(c, sd, dfinal[sd], &ga.s[sd]);
-    }
-    G(score_gru_bwd_multi(ga, 2, s));
-    gru_bias_rows = ga.bias_slab_rows;
-  }
-  for (int sd = 0; sd < 2 && !d.caser && !d.delf; ++sd) {
-    float* dxp = ws + w.dxproj[sd];
-    const float* cat = wxcat(c, sd);
-    G(queue_gru_side(c, &q, gw, sd, gru_bias_rows));
-    // d x = [dgates | dcand] . [Wx_gates | Wx_cand]^T
-    if (d.Is[sd] != d.I || d.g4r)     // RRN: the 2-hop columns of this side carry no gradient (GRU4Rec: nor does any of "side" 1's)
+  G(score_gru_bwd_multi(ga, 2, c.s));
+  b->gru_bias_rows = ga.bias_slab_rows;
+  return 0;
+}
+
+// the recurrences' queued weight gradients and d x = [dgates | dcand] . [Wx_gates | Wx_cand]^T into dxside, slice models
+int bwd_dx_slice(const Pass& c, BwdState* b) {
+  const Dims& d = c.d; const WS& w = c.w; float* ws = c.ws; const int H = c.H, BT = c.BT, x3 = c.x3; hipStream_t s = c.s;
+  const int64_t SF = w.scratch_floats;
+  for (int sd = 0; sd < 2; ++sd) {
+    G(queue_gru_side(c, &b->q, b->gw, sd, b->gru_bias_rows));
+    if (d.Is[sd] != d.I)     // RRN: the 2-hop columns of this side carry no gradient
       HIPTRY(hipMemsetAsync(ws + w.dxside[sd], 0, (int64_t)BT * d.I * sizeof(float), s));
-    if (d.g4r) {      // (layer 1's input gradient, for the row scatter; layer 2's went to layer 1 above)
-      if (sd == 0)
-        G(gemm_mode_call(x3, 1, BT, d.Di, 3 * H, dxp, 3 * H, cat, 3 * H, ws + w.dxside[0], d.I, nullptr, 0, 1.f, nullptr, 0,
-                         scratch, SF, s));
-    } else if (d.gcmc) {
-      // GCMC's two denses (slice_model.py:186-190): dZ [Z>0] = (dxproj Wx^T) [Z>0] -> dWc = A^T (.) ; dA = (.) Wc^T [A>0] ->
-      // dWa = S^T dA ; dS = dA Wa^T, the gradient of the 1-hop sum (its 2-hop columns stay zero, as for RRN)
-      const int Dx = d.Is[sd];
-      float* dz = ws + w.gcmc_dz[sd];
-      float* da = ws + w.gcmc_da[sd];
-      G(gemm_mode_call(x3, 1, BT, Dx, 3 * H, dxp, 3 * H, cat, 3 * H, dz, Dx, nullptr, GF_RELUGRAD, 1.f,
-                       reinterpret_cast<const uint8_t*>(ws + w.gcmc_z[sd]), 0, scratch, SF, s));
-      G(gemm_queue_add(&gq, Dx, Dx, BT, ws + w.gcmc_a[sd], Dx, dz, Dx, gw + P.gm_c[sd], Dx));
-      G(gemm_mode_call(x3, 1, BT, Dx, Dx, dz, Dx, W + P.gm_c[sd], Dx, da, Dx, nullptr, GF_RELUGRAD, 1.f,
-                       reinterpret_cast<const uint8_t*>(ws + w.gcmc_a[sd]), 0, scratch, SF, s));
-      G(gemm_queue_add(&gq, Dx, Dx, BT, ws + w.xside[sd], d.I, da, Dx, gw + P.gm_a[sd], Dx));
-      G(gemm_mode_call(x3, 1, BT, Dx, Dx, da, Dx, W + P.gm_a[sd], Dx, ws + w.dxside[sd], d.I, nullptr, 0, 1.f, nullptr, 0,
-                       scratch, SF, s));
-    } else if (d.Is[0] != d.Is[1]) {
-      G(gemm_mode_call(x3, 1, BT, d.Is[sd], 3 * H, dxp, 3 * H, cat, 3 * H, ws + w.dxside[sd], d.I, nullptr, 0, 1.f, nullptr, 0,
-                       scratch, SF, s));
-    }
+    if (d.Is[0] != d.Is[1])
+      G(gemm_mode_call(x3, 1, BT, d.Is[sd], 3 * H, ws + w.dxproj[sd], 3 * H, wxcat(c, sd), 3 * H, ws + w.dxside[sd], d.I, nullptr, 0,
+                       1.f, nullptr, 0, c.scratch, SF, s));
   }
-  if (d.Is[0] == d.Is[1] && !d.gcmc && !d.g4r && !d.caser && !d.delf) {      // both sides' d x in ONE grouped launch: 2 x 576 tiles fill 512 slots better than twice 576
+  if (d.Is[0] == d.Is[1]) {      // both sides' d x in ONE grouped launch: 2 x 576 tiles fill 512 slots better than twice 576
     const float* Ad[2] = {ws + w.dxproj[0], ws + w.dxproj[1]};
     float* Cd[2] = {ws + w.dxside[0], ws + w.dxside[1]};
-    if (panel_gemms(d, st, BT, 1)) {      // (the images were written by the forward pass, like the concatenated copies)
+    if (panel_gemms(d, c.st, BT, 1)) {      // (the images were written by the forward pass, like the concatenated copies)
       G(panel_launch(c, 1, Ad, Cd));
     } else {
       const float* Bd[2] = {wxcat(c, 0), wxcat(c, 1)};
-      G(score_gemm_same_shape(1, 2, BT, d.Is[0], 3 * H, Ad, 3 * H, Bd, 3 * H, Cd, d.I, 0, x3 != 0, scratch, SF, s));
+      G(score_gemm_same_shape(1, 2, BT, d.Is[0], 3 * H, Ad, 3 * H, Bd, 3 * H, Cd, d.I, 0, x3 != 0, c.scratch, SF, s));
     }
   }
+  return 0;
+}
 
-  // ---- co-attention + embedding rows (score.py:147-167, 196-201, 51-66)
+// ... GCMC: through its two denses (slice_model.py:186-190): dZ [Z>0] = (dxproj Wx^T) [Z>0] -> dWc = A^T (.) ; dA = (.) Wc^T [A>0] ->
+// dWa = S^T dA ; dS = dA Wa^T, the gradient of the 1-hop sum (its 2-hop columns stay zero, as for RRN)
+int bwd_dx_gcmc(const Pass& c, BwdState* b) {
+  const Dims& d = c.d; const Params& P = c.P; const WS& w = c.w;
+  float* ws = c.ws; const float* W = c.W; float* gw = b->gw; const int H = c.H, BT = c.BT, x3 = c.x3; hipStream_t s = c.s;
+  const int64_t SF = w.scratch_floats;
+  GemmQueue& gq = b->q.gq;
+  for (int sd = 0; sd < 2; ++sd) {
+    G(queue_gru_side(c, &b->q, gw, sd, b->gru_bias_rows));
+    HIPTRY(hipMemsetAsync(ws + w.dxside[sd], 0, (int64_t)BT * d.I * sizeof(float), s));
+    const int Dx = d.Is[sd];
+    float* dz = ws + w.gcmc_dz[sd];
+    float* da = ws + w.gcmc_da[sd];
+    G(gemm_mode_call(x3, 1, BT, Dx, 3 * H, ws + w.dxproj[sd], 3 * H, wxcat(c, sd), 3 * H, dz, Dx, nullptr, GF_RELUGRAD, 1.f,
+                     reinterpret_cast<const uint8_t*>(ws + w.gcmc_z[sd]), 0, c.scratch, SF, s));
+    G(gemm_queue_add(&gq, Dx, Dx, BT, ws + w.gcmc_a[sd], Dx, dz, Dx, gw + P.gm_c[sd], Dx));
+    G(gemm_mode_call(x3, 1, BT, Dx, Dx, dz, Dx, W + P.gm_c[sd], Dx, da, Dx, nullptr, GF_RELUGRAD, 1.f,
+                     reinterpret_cast<const uint8_t*>(ws + w.gcmc_a[sd]), 0, c.scratch, SF, s));
+    G(gemm_queue_add(&gq, Dx, Dx, BT, ws + w.xside[sd], d.I, da, Dx, gw + P.gm_a[sd], Dx));
+    G(gemm_mode_call(x3, 1, BT, Dx, Dx, da, Dx, W + P.gm_a[sd], Dx, ws + w.dxside[sd], d.I, nullptr, 0, 1.f, nullptr, 0,
+                     c.scratch, SF, s));
+  }
+  return 0;
+}
+
+// ... GRU4Rec: layer 1's input gradient, for the row scatter (layer 2's went to layer 1 in g4r_grus_bwd); "side" 1 of dxside and
+// the columns past Di of side 0 carry no gradient
+int bwd_dx_g4r(const Pass& c, BwdState* b) {
+  const Dims& d = c.d; const WS& w = c.w; float* ws = c.ws; const int H = c.H, BT = c.BT; hipStream_t s = c.s;
+  G(queue_gru_side(c, &b->q, b->gw, 0, b->gru_bias_rows));
+  HIPTRY(hipMemsetAsync(ws + w.dxside[0], 0, (int64_t)BT * d.I * sizeof(float), s));
+  G(gemm_mode_call(c.x3, 1, BT, d.Di, 3 * H, ws + w.dxproj[0], 3 * H, wxcat(c, 0), 3 * H, ws + w.dxside[0], d.I, nullptr, 0, 1.f,
+                   nullptr, 0, c.scratch, w.scratch_floats, s));
+  G(queue_gru_side(c, &b->q, b->gw, 1, b->gru_bias_rows));
+  HIPTRY(hipMemsetAsync(ws + w.dxside[1], 0, (int64_t)BT * d.I * sizeof(float), s));
+  return 0;
+}
+
+// ---- co-attention + embedding rows (score.py:147-167, 196-201, 51-66), the remaining products and the finishers
+int bwd_close(const Pass& c, BwdState* b) {
+  const Dims& d = c.d; const Params& P = c.P; const WS& w = c.w; const score_state_t* st = c.st; const score_batch_t* bt = c.bt;
+  float* ws = c.ws; const float* W = c.W; float* gw = b->gw; float* grad_table = b->grad_table;
+  const int B = c.B, x3 = c.x3; hipStream_t s = c.s;
+  void* const* stage_events = b->stage_events;
+  SideStream* side = b->side;
+  GemmQueue& gq = b->q.gq;
+  ColsumJobs& cq = b->q.cq;
+  const int64_t half = slab_half(w);
   // The recurrences' weight-gradient products (X^T dY: eight products, K = B*T) need what the backward recurrence has written and
   // nothing else, and nothing inside the pass reads them.  Round 6: issued HERE on the side stream -- behind the head's / attention's
   // products, which end about where the input-gradient product below does -- so the matrix-bound launch runs beside the co-attention
@@ -1793,7 +1900,7 @@ extern "C" int score_backward(const score_config_t* cfg, const score_state_t* st
   // workspace.  Flags.products_late (debug_flags bit 14): the round-5 placement (A/B).  The sharded path keeps that placement too:
   // its caller runs the gradient exchange on streams of its own beside the scatter (score_amd/dist.py).
   ReduceGroup rg; rg.n = rg.blocks = 0;
-  const bool products_early = st->scatter_mode != 2 && !fl.products_late && gq.n > 0;
+  const bool products_early = st->scatter_mode != 2 && !c.fl.products_late && gq.n > 0;
   // ... and with them the finishers of the dense gradient (slab reduce, column sums), when the caller takes them on the side stream
   // (score_state_t.grads_done_event): forked behind target_bwd_kernel, the last launch that feeds them, instead of behind the row
   // scatter -- they ran beside the table's touched-row update, 58 + 28 us there against 20 + 12 alone, with the dense ApplyAdam and
@@ -1804,7 +1911,7 @@ extern "C" int score_backward(const score_config_t* cfg, const score_state_t* st
   //  where it would cost the launch stream no packet of its own: 872 k vs 884 k samples/s, profiles/r06_probes.md)
   if (products_early) {
     G(fork_side(side, s));
-    G(gemm_queue_flush(&gq, x3 != 0, ws + w.dwslab + slab_half, w.dwslab_floats - slab_half, side->st, &rg));
+    G(gemm_queue_flush(&gq, x3 != 0, ws + w.dwslab + half, w.dwslab_floats - half, side->st, &rg));
     HIPTRY(hipEventRecord(side->join, side->st));
   }
   EV(3);
@@ -1827,15 +1934,15 @@ extern "C" int score_backward(const score_config_t* cfg, const score_state_t* st
   // (the occurrence sort's event, which the row scatter below needs: waited for HERE, next to the wait above -- every wait or record
   //  between two launches costs the launch stream a bubble of ~6 us, two adjacent ones cost one)
   if (!atomic && st->plan_done_event) HIPTRY(hipStreamWaitEvent(s, (hipEvent_t)st->plan_done_event, 0));
-  if (d.gcmc) {     // (GCMC reads no target row: their gradient is zero)
+  if (!d.reads_targets) {     // (GCMC reads no target row: their gradient is zero)
     if (!atomic) HIPTRY(hipMemsetAsync(ws + w.dtgt, 0, (int64_t)B * d.Dq * sizeof(float), s));
   } else
-  G(score_launch_target_bwd(grad_table, d.D, d.Fu, d.Fi, B, T, bt->target_user, bt->target_item,
+  G(score_launch_target_bwd(grad_table, d.D, d.Fu, d.Fi, B, c.T, bt->target_user, bt->target_item,
                             d.attn ? ws + w.dquery : nullptr, d.Dq, ws + w.dhead, d.Dhead, d.off_ti, d.off_tu,
                             ws + w.query, d.coattn ? W + P.ca_w[0] : nullptr, d.coattn ? W + P.ca_w[1] : nullptr,
                             ws + w.dzsum[0], ws + w.dzsum[1], ws + w.S, d.coattn ? gw + P.ca_w[0] : nullptr,
                             d.coattn ? gw + P.ca_b[0] : nullptr, d.coattn ? gw + P.ca_w[1] : nullptr,
-                            d.coattn ? gw + P.ca_b[1] : nullptr, atomic ? nullptr : ws + w.dtgt, scratch, SF, &cq, &gq,
+                            d.coattn ? gw + P.ca_b[1] : nullptr, atomic ? nullptr : ws + w.dtgt, c.scratch, w.scratch_floats, &cq, &gq,
                             s, st->n_table_rows));
   float* cs_part2 = ws + w.cs_part + w.cs_part_floats / 2;      // the column sums' second half: the first was flushed beside the GRUs
   const int64_t cs_part2_floats = w.cs_part_floats - w.cs_part_floats / 2;
@@ -1852,11 +1959,11 @@ extern "C" int score_backward(const score_config_t* cfg, const score_state_t* st
   HIPTRY(hipStreamWaitEvent(s, side->join, 0));
   // The finishers of the dense gradient -- the split-K slab reduce and the column sums: TWO small launches behind the products
   // (score_launch_finish; four dependent ones before round 4, the folded attention layer's gradient among them -- that one now
-  // follows the side stream's products, above) -- have ONE consumer, the dense variables' ApplyAdam.  A caller that passes
+  // follows the side stream's products, bwd_side_products) -- have ONE consumer, the dense variables' ApplyAdam.  A caller that passes
   // score_state_t.grads_done_event gets them on the side stream (idle by now: the launch stream has just waited for its join)
   // behind the products, and the event recorded behind them: it may run the table's touched-row update, which needs the row
   // gradients only, on the launch stream meanwhile, and waits for the event before anything reads grad_w.
-  if (!products_early) G(gemm_queue_flush(&gq, x3 != 0, ws + w.dwslab + slab_half, w.dwslab_floats - slab_half, s, &rg));
+  if (!products_early) G(gemm_queue_flush(&gq, x3 != 0, ws + w.dwslab + half, w.dwslab_floats - half, s, &rg));
   EV(5);
   if (fin_early) return 0;
   if (fin_side) G(fork_side(side, s));
@@ -1864,4 +1971,122 @@ extern "C" int score_backward(const score_config_t* cfg, const score_state_t* st
   G(score_launch_finish(&rg, &cq, cs_part2, cs_part2_floats, fs, 0));
   if (fin_side) HIPTRY(hipEventRecord((hipEvent_t)st->grads_done_event, fs));
   return 0;
+}
+
+int bwd_slice(const Pass& c, BwdState* b) {
+  hipStream_t s = c.s;
+  void* const* stage_events = b->stage_events;
+  G(bwd_open(c, b));
+  G(bwd_fc_head(c, b));
+  EV(1);
+  if (c.d.attn) G(bwd_attention(c, b));
+  else G(bwd_final_states(c, b, true));       // RIA, RRN
+  EV(2);
+  G(bwd_side_products(c, b));
+  G(bwd_grus_two_sided(c, b));
+  G(bwd_dx_slice(c, b));
+  return bwd_close(c, b);
+}
+
+int bwd_gcmc(const Pass& c, BwdState* b) {
+  const Params& P = c.P; const WS& w = c.w; float* ws = c.ws; const float* W = c.W; const int B = c.B, H = c.H; hipStream_t s = c.s;
+  void* const* stage_events = b->stage_events;
+  G(bwd_open(c, b));
+  // ---- GCMC's head (slice_model.py:199-201): dh_u, dh_i into dfinal, and the rows +-g h_u whose products with h_i are
+  // dW4 / dW5 (gcmc.hip)
+  G(score_launch_gcmc_head_bwd(B, H, ws + w.gru_final[0], W + P.gm_4, W + P.gm_5, ws + w.gcmc_pn, ws + w.gcmc_pn + (int64_t)B * H,
+                               ws + w.gcmc_g, ws + w.dfinal[0], ws + w.dfinal[1], ws + w.gcmc_gu, ws + w.gcmc_gu + (int64_t)B * H, s));
+  G(gemm_queue_add(&b->q.gq, H, H, B, ws + w.gru_final[1], H, ws + w.gcmc_gu, H, b->gw + P.gm_4, H));
+  G(gemm_queue_add(&b->q.gq, H, H, B, ws + w.gru_final[1], H, ws + w.gcmc_gu + (int64_t)B * H, H, b->gw + P.gm_5, H));
+  EV(1);
+  G(bwd_final_states(c, b, false));       // (the head kernel wrote dfinal)
+  EV(2);
+  G(bwd_side_products(c, b));
+  G(bwd_grus_two_sided(c, b));
+  G(bwd_dx_gcmc(c, b));
+  return bwd_close(c, b);
+}
+
+int bwd_g4r(const Pass& c, BwdState* b) {
+  hipStream_t s = c.s;
+  void* const* stage_events = b->stage_events;
+  G(bwd_open(c, b));
+  G(bwd_fc_head(c, b));
+  EV(1);
+  // GRU4Rec: the head reads layer 2's final state only; layer 1's dout comes from layer 2's backward
+  // (the stacked kernel reads no dout of layer 2; the composed form's kernel does)
+  G(bwd_final_state(c, b, 1, 0, !g4r_stacked(c.d, c.fl)));
+  G(bwd_zero_dinfo(c));
+  EV(2);
+  G(bwd_side_products(c, b));
+  G(g4r_grus_bwd(c, b->dfinal[1], &b->gru_bias_rows));
+  G(bwd_dx_g4r(c, b));
+  return bwd_close(c, b);
+}
+
+int bwd_caser(const Pass& c, BwdState* b) {
+  hipStream_t s = c.s;
+  void* const* stage_events = b->stage_events;
+  G(bwd_open(c, b));
+  G(bwd_fc_head(c, b));
+  EV(1);
+  G(bwd_zero_dinfo(c));       // (no state: dhead itself is what caser.hip reads)
+  EV(2);
+  G(bwd_side_products(c, b));
+  // Caser: d X into dxside[0] on the launch stream (dxside[1] carries nothing) and, beside it on the side stream -- behind the
+  // head's backward since the fork in bwd_side_products, and behind the fill of grad_w --, the six variables' gradients, each
+  // batch sum in a fixed order; the join is recorded again behind them
+  HIPTRY(hipMemsetAsync(c.ws + c.w.dxside[1], 0, (int64_t)c.BT * c.d.I * sizeof(float), s));
+  CaserArgs a;
+  caser_args(c, b->gw, &a);
+  G(score_caser_bwd(a, s, b->side->st));
+  HIPTRY(hipEventRecord(b->side->join, b->side->st));
+  return bwd_close(c, b);
+}
+
+int bwd_delf(const Pass& c, BwdState* b) {
+  hipStream_t s = c.s;
+  void* const* stage_events = b->stage_events;
+  G(bwd_open(c, b));
+  // ---- DELF: the whole backward of the model between the scatter and the loss in ONE launch (delf.hip): dxside, dhead's
+  // target columns, and the rows the queued products and column sums are taken from -- those run on the side stream
+  // (bwd_side_products), forked behind this launch, beside the target rows' and the embedding rows' scatter
+  DelfArgs a;
+  delf_args(c, &a);
+  G(score_delf_bwd(a, s));
+  G(queue_delf(c, &b->q, b->gw));
+  EV(1);
+  G(bwd_zero_dinfo(c));       // (no state: dhead is what delf.hip wrote)
+  EV(2);
+  G(bwd_side_products(c, b));       // (no recurrence; delf.hip wrote both dxside above)
+  return bwd_close(c, b);
+}
+}  // namespace
+
+extern "C" int score_backward(const score_config_t* cfg, const score_state_t* st, const score_batch_t* bt,
+                              float keep_prob, float* gw, float* grad_table, void* const* stage_events,
+                              void* stream) {
+  Pass c;
+  SCORE_TRY(make_dims(cfg, &c.d));
+  if (!st || !bt || !st->table || !st->w || !st->workspace || !gw || !grad_table || bt->B <= 0)
+    return SCORE_E_BADARG;
+  if (c.d.family == FAM_DELF && (!bt->length || !bt->length2)) return SCORE_E_BADARG;
+  SCORE_TRY(pass_fill(&c, st, bt, stream));
+  {
+    PsPlan pp;
+    if (!c.fl.ps_fwd_only && ps_path(c.d, st, bt, c.T, &pp))
+      return backward_ps(c, pp, keep_prob, gw, grad_table, stage_events);
+  }
+  BwdState b;
+  b.keep_prob = keep_prob; b.gw = gw; b.grad_table = grad_table; b.stage_events = stage_events;
+  b.side = nullptr; b.dfinal[0] = b.dfinal[1] = nullptr; b.gru_bias_rows = 0;
+  queues_init(&b.q);
+  switch (c.d.family) {
+    case FAM_SLICE: return bwd_slice(c, &b);
+    case FAM_GCMC: return bwd_gcmc(c, &b);
+    case FAM_G4R: return bwd_g4r(c, &b);
+    case FAM_CASER: return bwd_caser(c, &b);
+    case FAM_DELF: return bwd_delf(c, &b);
+  }
+  return SCORE_E_BADARG;
 }
