@@ -114,7 +114,30 @@ enum { SCORE_MODEL_SCORE = 0, SCORE_MODEL_RIA = 1, SCORE_MODEL_RCA = 2,
         * delf_rep [B, C] ru / ri, delf_ds [B, T] and delf_dpre [B*T, C] the gradients at the scores and at tanh's argument;
         * delf_act / delf_dact [B, 64]: [h1 (4 x 10) | h2 (4 x 4) | f (4) | pad] and the pre-activation gradients.  Kernels:
         * csrc/delf.hip, one launch each way. */
-       SCORE_MODEL_DELF = 9 };
+       SCORE_MODEL_DELF = 9,
+       /* point_models/point_model.py:281-311 (DEEMS) on DELF (:200-249) on PointBaseModel (:9-63): h_u = the final state of gru1
+        * over user_seq under user_seq_length, h_i = that of gru2 over item_seq under item_seq_length (GRUCell(hidden_size),
+        * dynamic_rnn: the state frozen past the length, a length >= T all T positions, a length <= 0 a zero final state), then two
+        * build_fc_net towers (bn in inference form, fc 200 relu dropout, fc 80 relu dropout, fc 1, sigmoid) with variables and
+        * dropout masks of their own: y_u on [h_u | target_user], y_i on [h_i | target_item]; y_pred = (y_u + y_i) / 2.  The
+        * reference builds train_step from log_loss(label, y_pred) + reg_lambda * l2 and only then adds 0.05 * SUM_b (y_i - y_u)^2
+        * to self.loss (:299-300): loss[0] / loss[1] INCLUDE that term (a sum over the batch, not a mean), the gradients do NOT.
+        * DELF's constructor runs first, so its 22 variables exist: they are laid out, initialised, regularised (their kernels
+        * add to the L2 term and get reg_lambda * W through score_adam; their biases never change) and never read by a launch --
+        * the DELF kernels do not run.  score_param_layout: 46 entries in TF's creation order -- dense .. dense_10, gru1 / gru2,
+        * batch_normalization/{gamma, beta}, dense_11 .. dense_13 (user tower), batch_normalization_1/{gamma, beta}, dense_14 ..
+        * dense_16 (item tower).  obj_per_time_slice must be 1, hidden_size a multiple of 4.  The batch rides as for
+        * SCORE_MODEL_DELF (user_1hop = user_seq, item_1hop = item_seq, length, length2); active_slices = A promises both lengths
+        * <= A, and -- unlike DELF -- a length <= 0 does not ask for all T slices: that sample's recurrence never runs.
+        * score_forward's drop_mask0 / drop_mask1 cover both towers, the user tower first: [2, B, 200] and [2, B, 80]; from a seed
+        * the item tower draws from a stream of its own (the user tower's seeds ^ a constant).  The head input is ONE row
+        * [h_u | target_user | h_i | target_item] (score_workspace_t.head_inp, 2 H + Du + Di wide); workspace fields
+        * (score_workspace_field): gru_final = h_u | h_i, deems_y = y_u | y_i [B] each, deems_logit, deems_dlogit likewise,
+        * deems_f1 / deems_f2 / deems_dz1 / deems_dz2 the towers' layer outputs and their gradients.  At H in {16, 32, 64, 128}
+        * (128: with gemm_mode 0 or debug_flags bit 2) both recurrences run as ONE launch each way, each side under its own lengths;
+        * other H, and debug_flags bit 13, run one launch per side.  Both towers and the loss terms are ONE launch each way
+        * (csrc/deems.hip); debug_flags bit 6 runs them layer by layer. */
+       SCORE_MODEL_DEEMS = 10 };
 
 /* Constructor arguments of SCOREBASE.__init__ (score.py:12-13). */
 typedef struct {
@@ -122,7 +145,7 @@ typedef struct {
   int32_t eb_dim;              /* D: multiple of 4, <= 256                        */
   int32_t hidden_size;         /* H                                               */
   int32_t max_time_len;        /* T                                               */
-  int32_t obj_per_time_slice;  /* K <= 32 (SCORE_MODEL_GRU4REC / _CASER / _DELF: 1) */
+  int32_t obj_per_time_slice;  /* K <= 32 (SCORE_MODEL_GRU4REC / _CASER / _DELF / _DEEMS: 1) */
   int32_t user_fnum;           /* Fu                                              */
   int32_t item_fnum;           /* Fi                                              */
   int32_t model_type;          /* SCORE_MODEL_*                                   */
@@ -164,7 +187,7 @@ typedef struct {
                                   weight (:182-185), so loss, predictions and every gradient are
                                   unchanged; samples with length[b] > A are treated as length A.
                                   The index tensors keep their [B,T,K,F] strides.                   */
-  const int32_t* length2;      /* [B] SCORE_MODEL_DELF only: item_seq_length, the mask of item_1hop's T positions (length is
+  const int32_t* length2;      /* [B] SCORE_MODEL_DELF / _DEEMS only: item_seq_length, the mask of item_1hop's T positions (length is
                                   user_seq_length, the mask of user_1hop's).  NULL for every other model type: none reads it. */
 } score_batch_t;
 
@@ -455,7 +478,8 @@ typedef struct {
                            launch stream's chain, behind the row scatter (the round-5 placement), instead of on the side stream
                            beside the co-attention backward and the scatter (round 6; same bits); bit 13 (8192) =
                            (SCORE_MODEL_GRU4REC) the two stacked recurrences one layer per launch with the projection GEMM between
-                           them (the composed form: what H outside {16, 32, 64} runs anyway) instead of csrc/gru_stack.hip.
+                           them (the composed form: what H outside {16, 32, 64} runs anyway) instead of csrc/gru_stack.hip;
+                           (SCORE_MODEL_DEEMS) its two recurrences one launch per side instead of one grouped launch.
                            The ONLY switches of the launch sequence: the library reads no environment variable       */
   uint8_t* row_flags;   /* optional [n_table_rows] row state of the dense table optimizer (see
                            score_adam_rows): score_backward (scatter_mode 0) marks every row it
@@ -578,7 +602,7 @@ int score_rows_accumulate_multi(const int32_t* rows, const float* src, const int
 /* Forward of SCORE / RIA / RCA / SCORE_USER / SCORE_ITEM (score.py:188-369) +
  * build_fc_net / build_logloss / build_l2norm (:68-94).  keep_prob 1.0 = eval
  * (score.py:129), 0.8 = train (:113).  Results land in the workspace
- * (y_pred, loss, ...). drop_mask0/1: optional explicit [B,200]/[B,80] byte masks.
+ * (y_pred, loss, ...). drop_mask0/1: optional explicit [B,200]/[B,80] byte masks (SCORE_MODEL_DEEMS: [2,B,200]/[2,B,80]).
  * stage_events: null, or 5 hipEvent_t handles (each may be null) recorded on `stream`
  * at the stage boundaries: [0] before the fused gather+co-attention launch, [1] after
  * it, [2] after the GRUs, [3] after the temporal attention, [4] after head + loss. */

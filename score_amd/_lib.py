@@ -10,7 +10,10 @@ import os
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "lib", "libscore_hip.so")
 
-MODEL_TYPES = {"SCORE": 0, "RIA": 1, "RCA": 2, "SCORE_USER": 3, "SCORE_ITEM": 4, "RRN": 5, "GCMC": 6, "GRU4Rec": 7, "Caser": 8, "DELF": 9}
+MODEL_TYPES = {"SCORE": 0, "RIA": 1, "RCA": 2, "SCORE_USER": 3, "SCORE_ITEM": 4, "RRN": 5, "GCMC": 6, "GRU4Rec": 7, "Caser": 8, "DELF": 9,
+               "DEEMS": 10}
+
+MAX_PARAM_ENTRIES = 48   # dense variables of a model type at most (DEEMS: 46)
 
 c_f = C.c_void_p   # device float*
 c_i = C.c_void_p   # device int32*
@@ -30,7 +33,7 @@ class ParamEntry(C.Structure):
 class Batch(C.Structure):
     _fields_ = [("user_1hop", c_i), ("user_2hop", c_i), ("item_1hop", c_i), ("item_2hop", c_i),
                 ("target_user", c_i), ("target_item", c_i), ("label", c_i), ("length", c_i),
-                ("B", C.c_int32), ("active_slices", C.c_int32), ("length2", c_i)]     # (length2: DELF's item_seq_length; NULL otherwise)
+                ("B", C.c_int32), ("active_slices", C.c_int32), ("length2", c_i)]     # (length2: DELF's / DEEMS's item_seq_length; NULL otherwise)
 
 
 class Workspace(C.Structure):
@@ -256,9 +259,9 @@ def make_config(feature_size, eb_dim, hidden_size, max_time_len, obj_per_time_sl
 def param_layout(cfg):
     """-> (entries [(name, offset, rows, cols, regularised, init)], n_floats, n_reg)"""
     lib = load()
-    arr = (ParamEntry * 32)()
+    arr = (ParamEntry * MAX_PARAM_ENTRIES)()
     nf, nr = C.c_int64(0), C.c_int64(0)
-    n = lib.score_param_layout(C.byref(cfg), arr, 32, C.byref(nf), C.byref(nr))
+    n = lib.score_param_layout(C.byref(cfg), arr, MAX_PARAM_ENTRIES, C.byref(nf), C.byref(nr))
     if n < 0:
         check(n, "score_param_layout")
     out = [(arr[i].name.decode(), arr[i].offset, arr[i].rows, arr[i].cols, arr[i].regularised, arr[i].init)

@@ -1,7 +1,7 @@
 // Whole-path orchestration: parameter/workspace layout and the forward / backward
 // launch sequences of SCORE and its ablations (score.py:188-369) and of the slice baselines RRN and GCMC
-// (slice_model.py:155-203) and of the point baselines GRU4Rec, Caser and DELF (point_model.py:123-164, 200-249) on one stream.
-// Host code only; every kernel lives in embed/gemm/gru/gru_stack/head/gcmc/caser/delf.hip.
+// (slice_model.py:155-203) and of the point baselines GRU4Rec, Caser, DELF and DEEMS (point_model.py:123-164, 200-249, 281-311) on
+// one stream.  Host code only; every kernel lives in embed/gemm/gru/gru_stack/head/gcmc/caser/delf/deems.hip.
 #include <string.h>
 #include <stdlib.h>
 #include <stdio.h>
@@ -16,10 +16,11 @@ namespace {
 
 const int FC1 = 200, FC2 = 80, AT1 = 80, AT2 = 40;
 const int CASER_L = SCORE_CASER_L, CASER_HPAD = SCORE_CASER_HPAD;       // kernels.h
+const int MAX_ENTRIES = 48;       // dense variables of a model type at most (DEEMS: 46)
 
 // What decides a pass's launch sequence.  FAM_SLICE: SCORE, RIA, RCA, SCORE_USER, SCORE_ITEM and RRN, which differ by attn, coattn
 // and Is[] only; every other model type is a family of its own
-enum Family { FAM_SLICE, FAM_GCMC, FAM_G4R, FAM_CASER, FAM_DELF };
+enum Family { FAM_SLICE, FAM_GCMC, FAM_G4R, FAM_CASER, FAM_DELF, FAM_DEEMS };
 
 struct Dims {
   int64_t N;
@@ -31,9 +32,12 @@ struct Dims {
   // FAM_G4R: "side" 0 is layer 1 (input: the gathered user_seq rows, Di wide), "side" 1 layer 2 (input: layer 1's outputs, H wide)
   // FAM_CASER: no recurrence at all (H = 0 here, whatever the config says); C = Di columns of xside[0] are its X
   // FAM_DELF: no recurrence and no bn1 / fc head (H = 0 here); X of side 0 = Di columns of xside[0], of side 1 = Du columns of xside[1]
+  // FAM_DEEMS: side 0 = gru1 over the user_seq rows (Di columns of xside[0], lengths score_batch_t.length), side 1 = gru2 over the
+  //   item_seq rows (Du columns of xside[1], lengths length2); two fc heads of its own on the column ranges [h_u | target_user]
+  //   and [h_i | target_item] of ONE head_inp row; DELF's 22 variables laid out and regularised, never read by a launch
   Family family;
   int n_gru;             // recurrences with variables, workspace and launches: 2, or 0 (Caser, DELF)
-  bool fc_head;          // bn1 and fc1-3 behind head_inp (not GCMC, DELF)
+  bool fc_head;          // bn1 and fc1-3 behind head_inp (not GCMC, DELF; DEEMS has two heads of its own, deems_tower)
   bool sums_1hop;        // the gather leaves plain 1-hop sums: no co-attention, no attention, Is[] = {Di, Du} (RRN and every later type)
   bool reads_targets;    // the model reads the target rows (not GCMC: their gradient is zero)
   int Ic;          // row capacity of a side's block of the concatenated [Wx_gates | Wx_cand] copy: I (GRU4Rec: max(I, H))
@@ -45,16 +49,17 @@ int make_dims(const score_config_t* c, Dims* d) {
   d->N = c->feature_size; d->D = c->eb_dim; d->H = c->hidden_size; d->T = c->max_time_len;
   d->K = c->obj_per_time_slice; d->Fu = c->user_fnum; d->Fi = c->item_fnum; d->mt = c->model_type;
   if (d->N <= 0 || d->D <= 0 || (d->D & 3) || d->D > 256 || d->H <= 0 || d->T <= 0 || d->K <= 0 || d->K > 32 ||
-      d->Fu <= 0 || d->Fi <= 0 || d->mt < 0 || d->mt > SCORE_MODEL_DELF)
+      d->Fu <= 0 || d->Fi <= 0 || d->mt < 0 || d->mt > SCORE_MODEL_DEEMS)
     return SCORE_E_SHAPE;
   d->Du = d->Fu * d->D; d->Di = d->Fi * d->D; d->I = d->Di + d->Du; d->Dq = d->Du + d->Di;
   const bool gcmc = d->mt == SCORE_MODEL_GCMC, g4r = d->mt == SCORE_MODEL_GRU4REC, caser = d->mt == SCORE_MODEL_CASER,
-             delf = d->mt == SCORE_MODEL_DELF;
-  d->family = gcmc ? FAM_GCMC : g4r ? FAM_G4R : caser ? FAM_CASER : delf ? FAM_DELF : FAM_SLICE;
+             delf = d->mt == SCORE_MODEL_DELF, deems = d->mt == SCORE_MODEL_DEEMS;
+  d->family = gcmc ? FAM_GCMC : g4r ? FAM_G4R : caser ? FAM_CASER : delf ? FAM_DELF : deems ? FAM_DEEMS : FAM_SLICE;
   d->n_gru = (caser || delf) ? 0 : 2;
-  d->fc_head = !gcmc && !delf;
+  d->fc_head = !gcmc && !delf && !deems;
   d->reads_targets = !gcmc;
-  if ((g4r || caser || delf) && d->K != 1) return SCORE_E_SHAPE;      // (user_seq rides as a [B, T, 1, Fi] set)
+  if ((g4r || caser || delf || deems) && d->K != 1) return SCORE_E_SHAPE;      // (user_seq rides as a [B, T, 1, Fi] set)
+  if (deems && (d->H & 3)) return SCORE_E_SHAPE;                // (the towers' column ranges of head_inp start at 16-byte groups)
   if (delf) {
     if (d->Di > SCORE_DELF_CMAX || d->Du > SCORE_DELF_CMAX) return SCORE_E_SHAPE;      // (the widths delf.hip covers)
     d->H = 0;                                                 // hidden_size: accepted and ignored, as for Caser
@@ -87,6 +92,10 @@ int make_dims(const score_config_t* c, Dims* d) {
     d->off_ti = CASER_HPAD + d->Di;
   }
   d->off_tu = d->off_ti + d->Di;
+  if (deems) {
+    // [h_u | target_user | h_i | target_item]: each tower's input is a column range (deems_tower)
+    d->off_u = 0; d->off_tu = d->H; d->off_i = d->H + d->Du; d->off_ti = 2 * d->H + d->Du;
+  }
   return 0;
 }
 
@@ -114,17 +123,20 @@ struct Params {  // float offsets into the flat buffer
   int64_t bn_g, bn_b, fc_w[3], fc_b[3];
   int64_t gm_a[2], gm_c[2], gm_4, gm_5;  // GCMC: per side dense (Wa) and dense_2 / dense_3 (Wc); the head's dense_4, dense_5
   int64_t cs_wh, cs_bh, cs_wv, cs_bv, cs_wd, cs_bd;  // Caser: conv2d (horizontal), conv2d_1 (vertical), dense (the scalar one)
-  int64_t dl_w[11], dl_b[11];           // DELF: dense .. dense_10, kernels and biases
+  int64_t dl_w[11], dl_b[11];           // DELF: dense .. dense_10, kernels and biases (DEEMS: the same variables, dormant)
+  int64_t bn_g2, bn_b2, fc_w2[3], fc_b2[3];     // DEEMS: the item tower (batch_normalization_1, dense_14 .. dense_16); the user tower
+                                        // (batch_normalization, dense_11 .. dense_13) is bn_g / bn_b / fc_w / fc_b
   int64_t n_floats, n_reg;
 };
 
 int build_layout_raw(const Dims& d, score_param_entry_t* out, int max_entries, Params* P) {
   // TF creation order (score.py:188-224): co_attention denses, GRU cells, attention denses, bn1, fc1-3
-  char names[32][64];
-  int rows[32], cols[32], reg[32], init[32];
+  char names[MAX_ENTRIES][64];
+  int rows[MAX_ENTRIES], cols[MAX_ENTRIES], reg[MAX_ENTRIES], init[MAX_ENTRIES];
   int n = 0, nd = 0;
   memset(P, 0, sizeof(*P));      // (a variable the model type does not have: offset 0, never read)
-  const bool gcmc = d.family == FAM_GCMC, caser = d.family == FAM_CASER, delf = d.family == FAM_DELF;
+  const bool gcmc = d.family == FAM_GCMC, caser = d.family == FAM_CASER, deems = d.family == FAM_DEEMS;
+  const bool delf = d.family == FAM_DELF || deems;      // (DEEMS.__init__ runs DELF's first: its variables exist, point_model.py:283)
   auto add = [&](const char* nm, int r, int c, int rg, int in) {
     snprintf(names[n], 64, "%s", nm);
     rows[n] = r; cols[n] = c; reg[n] = rg; init[n] = in; ++n;
@@ -145,7 +157,7 @@ int build_layout_raw(const Dims& d, score_param_entry_t* out, int max_entries, P
     add("dense_2/kernel", Dx[0], Dx[0], 1, 2); add("dense_3/kernel", Dx[1], Dx[1], 1, 2);
   }
   const char* sides[2] = {"gru_user_side", "gru_item_side"};
-  if (gcmc || d.family == FAM_G4R) { sides[0] = "gru1"; sides[1] = "gru2"; }     // (GRU4Rec, point_model.py:129-132: the two stacked layers)
+  if (gcmc || d.family == FAM_G4R || deems) { sides[0] = "gru1"; sides[1] = "gru2"; }     // (GRU4Rec, point_model.py:129-132: the two stacked layers; DEEMS :287-290)
   // Caser (point_model.py:147-157): conv2d [50, C, 1, 1], conv2d_1 [T, 1, 1, 1] (init 3: glorot with TF's convolution fans,
   // fan_in = fan_out = rows * cols), dense [1, 1]
   if (caser) {
@@ -176,9 +188,19 @@ int build_layout_raw(const Dims& d, score_param_entry_t* out, int max_entries, P
     add("fc2/kernel", FC1, FC2, 1, 2); add("fc2/bias", FC2, 0, 0, 0);
     add("fc3/kernel", FC2, 1, 1, 2); add("fc3/bias", 1, 0, 0, 0);
   }
+  // DEEMS (point_model.py:295-296, 302-311): build_fc_net twice without names -- batch_normalization, dense_11 .. dense_13 on
+  // [h_u | target_user], batch_normalization_1, dense_14 .. dense_16 on [h_i | target_item]
+  if (deems) {
+    const int Dt[2] = {d.H + d.Du, d.H + d.Di};
+    for (int k = 0; k < 2; ++k) {
+      add(k ? "batch_normalization_1/gamma" : "batch_normalization/gamma", Dt[k], 0, 1, 1);
+      add(k ? "batch_normalization_1/beta" : "batch_normalization/beta", Dt[k], 0, 1, 0);
+      dense(Dt[k], FC1); dense(FC1, FC2); dense(FC2, 1);
+    }
+  }
   // offsets: regularised tensors first, then the rest; every tensor 16-B aligned.  The
   // regularised region is padded with zeros that stay zero (zero grad, zero l2 term).
-  int64_t off[32];
+  int64_t off[MAX_ENTRIES];
   int64_t cur = 0;
   for (int pass = 0; pass < 2; ++pass) {
     for (int i = 0; i < n; ++i) {
@@ -211,6 +233,12 @@ int build_layout_raw(const Dims& d, score_param_entry_t* out, int max_entries, P
     P->bn_g = off[i++]; P->bn_b = off[i++];
     for (int f = 0; f < 3; ++f) { P->fc_w[f] = off[i++]; P->fc_b[f] = off[i++]; }
   }
+  if (deems) {
+    P->bn_g = off[i++]; P->bn_b = off[i++];
+    for (int f = 0; f < 3; ++f) { P->fc_w[f] = off[i++]; P->fc_b[f] = off[i++]; }
+    P->bn_g2 = off[i++]; P->bn_b2 = off[i++];
+    for (int f = 0; f < 3; ++f) { P->fc_w2[f] = off[i++]; P->fc_b2[f] = off[i++]; }
+  }
   return n;
 }
 
@@ -226,12 +254,12 @@ static inline LayoutKey layout_key(const Dims& d, int B) {
 }
 static inline bool same_key(const LayoutKey& a, const LayoutKey& b) { return memcmp(&a, &b, sizeof(a)) == 0; }
 int build_layout(const Dims& d, score_param_entry_t* out, int max_entries, Params* P) {
-  struct Memo { bool ok; LayoutKey k; Params P; int n; score_param_entry_t ent[32]; };
+  struct Memo { bool ok; LayoutKey k; Params P; int n; score_param_entry_t ent[MAX_ENTRIES]; };
   static thread_local Memo memo = {};
   LayoutKey k = layout_key(d, 0);
   if (!memo.ok || !same_key(memo.k, k)) {
     memset(&memo.k, 0, sizeof(memo.k));
-    memo.n = build_layout_raw(d, memo.ent, 32, &memo.P);
+    memo.n = build_layout_raw(d, memo.ent, MAX_ENTRIES, &memo.P);
     memo.k = k; memo.ok = memo.n >= 0;
     if (memo.n < 0) return memo.n;
   }
@@ -268,6 +296,9 @@ struct WS {
   // DELF only (-1 otherwise), per side: tanh keys [B*T, C], attention weights [B, T], attention outputs [B, C], the gradient at
   // the scores [B, T] and at the keys' pre-activations [B*T, C]; the fusion layers' activations and their gradients [B, 64]
   int64_t delf_key[2], delf_att[2], delf_rep[2], delf_ds[2], delf_dpre[2], delf_act, delf_dact;
+  // DEEMS only (-1 otherwise): the item tower's f1 / f2 / dz1 / dz2 (the user tower's are the head's own regions; bn, dbn, dhead and
+  // dgstage hold both towers' column ranges), and per tower [2][B] the logits, y_u | y_i, dL/d logit
+  int64_t deems_f1, deems_f2, deems_dz1, deems_dz2, deems_logit, deems_y, deems_dlogit;
   int64_t scratch_floats, total;
 };
 
@@ -324,6 +355,13 @@ void ws_family_regions(const Dims& d, int B, Taker& take, WS* w) {
   } else {
     for (int s = 0; s < 2; ++s) w->delf_key[s] = w->delf_att[s] = w->delf_rep[s] = w->delf_ds[s] = w->delf_dpre[s] = -1;
     w->delf_act = w->delf_dact = -1;
+  }
+  if (d.family == FAM_DEEMS) {
+    w->deems_f1 = take((int64_t)B * FC1); w->deems_f2 = take((int64_t)B * FC2);
+    w->deems_dz1 = take((int64_t)B * FC1); w->deems_dz2 = take((int64_t)B * FC2);
+    w->deems_logit = take(2 * (int64_t)B); w->deems_y = take(2 * (int64_t)B); w->deems_dlogit = take(2 * (int64_t)B);
+  } else {
+    w->deems_f1 = w->deems_f2 = w->deems_dz1 = w->deems_dz2 = w->deems_logit = w->deems_y = w->deems_dlogit = -1;
   }
 }
 
@@ -523,6 +561,8 @@ enum {
   DF_HEAD_UNFUSED = 64, DF_ATTN_UNFUSED = 128, DF_SORT_OWN = 256, DF_NO_PS = 512, DF_PS_FWD_ONLY = 1024, DF_PS_BWD_ONLY = 2048,
   DF_ONE_STREAM = 4096, DF_G4R_COMPOSED = 8192, DF_PRODUCTS_LATE = 16384
 };
+// (DF_G4R_COMPOSED / Flags.g4r_composed, bit 13, reads "one recurrence per launch": GRU4Rec's composed form, and DEEMS's two
+//  recurrences as one launch per side instead of one grouped launch)
 struct Flags {
   bool gru_stepwise, head_fused_any_b, gru_f32_rec, no_panel, panel_dx, sort_lib, head_unfused, attn_unfused, sort_own, no_ps,
       ps_fwd_only, ps_bwd_only, one_stream, g4r_composed, products_late;
@@ -760,6 +800,94 @@ static void delf_args(const Pass& c, DelfArgs* a) {
   a->act = ws + w.delf_act; a->dact = ws + w.delf_dact; a->logit = ws + w.logit; a->y = ws + w.y_pred; a->lossb = ws + w.lossb;
   a->dlogit = ws + w.dlogit; a->dhead = ws + w.dhead;
 }
+// ---------------------------------------------------------------- DEEMS (point_model.py:281-311, deems.hip)
+// The two recurrences: side 0 = gru1 over the user_seq rows under score_batch_t.length, side 1 = gru2 over the item_seq rows under
+// length2.  On the register kernels of gru.hip both run as ONE grouped launch each way, each side reading its own lengths
+// (GruSide.length); every other route, and Flags.g4r_composed ("one recurrence per launch"), runs one call per side with that
+// side's lengths in GruArgs.length -- the same kernels on the same rows either way.
+static const int32_t* deems_length(const Pass& c, int sd) { return sd ? c.bt->length2 : c.bt->length; }
+// both sides' arguments as the grouped launch takes them (bwd: with what the backward recurrence reads and writes)
+static void deems_gru_args(const Pass& c, GruArgs* ga, const float* const* dfinal) {
+  gru_header(c, ga);
+  for (int sd = 0; sd < 2; ++sd) {
+    GruSide& g = ga->s[sd];
+    gru_side(c, sd, &g);
+    g.xproj = c.ws + c.w.xproj[sd]; g.final_state = c.ws + c.w.gru_final[sd]; g.length = deems_length(c, sd);
+    if (dfinal) gru_side_bwd(c, sd, dfinal[sd], &g);
+  }
+}
+static bool deems_grouped(const Pass& c, const GruArgs& ga) { return !c.fl.g4r_composed && score_gru_reg_route(ga, 2); }
+// side sd alone, its lengths the call's
+static void deems_one_side(const Pass& c, const GruArgs& both, int sd, GruArgs* one) {
+  gru_header(c, one);
+  one->s[0] = both.s[sd]; one->s[0].length = nullptr;
+  one->length = deems_length(c, sd);
+}
+static int deems_grus_fwd(const Pass& c) {
+  const Dims& d = c.d; const WS& w = c.w; float* ws = c.ws; const int H = c.H;
+  for (int sd = 0; sd < 2; ++sd) {     // x . [Wx_gates | Wx_cand] + [b_gates | b_cand]: one GEMM per side (Is[0] != Is[1])
+    const float* cat = wxcat(c, sd);
+    G(gemm_mode_call(c.x3, 0, c.BT, 3 * H, d.Is[sd], ws + w.xside[sd], d.I, cat, 3 * H, ws + w.xproj[sd], 3 * H,
+                     cat + (int64_t)d.Is[sd] * 3 * H, GF_BIAS, 1.f, nullptr, 0, c.scratch, w.scratch_floats, c.s));
+  }
+  GruArgs ga;
+  deems_gru_args(c, &ga, nullptr);
+  if (deems_grouped(c, ga)) return score_gru_fwd_multi(ga, 2, c.s);
+  for (int sd = 0; sd < 2; ++sd) {
+    GruArgs one;
+    deems_one_side(c, ga, sd, &one);
+    G(score_gru_fwd_multi(one, 1, c.s));
+  }
+  return 0;
+}
+static int deems_grus_bwd(const Pass& c, const float* const* dfinal, int* bias_rows) {
+  GruArgs ga;
+  deems_gru_args(c, &ga, dfinal);
+  if (deems_grouped(c, ga)) {
+    G(score_gru_bwd_multi(ga, 2, c.s));
+    *bias_rows = ga.bias_slab_rows;
+    return 0;
+  }
+  for (int sd = 0; sd < 2; ++sd) {
+    GruArgs one;
+    deems_one_side(c, ga, sd, &one);
+    G(score_gru_bwd_multi(one, 1, c.s));
+    *bias_rows = one.bias_slab_rows;
+  }
+  return 0;
+}
+// tower k's variables and buffers: 0 = the user tower on columns [0, H + Du) of a head_inp row, 1 = the item tower on the rest
+struct DeemsVars { int64_t bn_g, bn_b; const int64_t* fc_w; const int64_t* fc_b; };
+static DeemsVars deems_vars(const Params& P, int k) {
+  return k ? DeemsVars{P.bn_g2, P.bn_b2, P.fc_w2, P.fc_b2} : DeemsVars{P.bn_g, P.bn_b, P.fc_w, P.fc_b};
+}
+static void deems_args(const Pass& c, float keep_prob, const uint8_t* mask0, const uint8_t* mask1, uint64_t seed, DeemsArgs* a) {
+  const Dims& d = c.d; const WS& w = c.w; float* ws = c.ws; const float* W = c.W; const int B = c.B;
+  memset(a, 0, sizeof(*a));
+  a->B = B; a->H = c.H; a->ld = d.Dhead; a->Bglobal = c.Bg;
+  a->x = ws + w.head_inp; a->bn = ws + w.bn; a->dbn = ws + w.dbn; a->dhead = ws + w.dhead; a->tmp = ws + w.dgstage;
+  a->rs = c.rs; a->keep = keep_prob; a->seed0 = seed;
+  a->seed_dev = c.st->step_scalars ? &c.st->step_scalars->drop_seed : nullptr;
+  a->label = c.bt->label; a->y_pred = ws + w.y_pred; a->lossb = ws + w.lossb;
+  const int64_t f1[2] = {w.f1, w.deems_f1}, f2[2] = {w.f2, w.deems_f2}, dz1[2] = {w.dz1, w.deems_dz1}, dz2[2] = {w.dz2, w.deems_dz2};
+  for (int k = 0; k < 2; ++k) {
+    DeemsTower& t = a->t[k];
+    const DeemsVars v = deems_vars(c.P, k);
+    t.h = ws + w.gru_final[k];
+    t.gamma = W + v.bn_g; t.beta = W + v.bn_b;
+    t.W1 = W + v.fc_w[0]; t.b1 = W + v.fc_b[0]; t.W2 = W + v.fc_w[1]; t.b2 = W + v.fc_b[1]; t.W3 = W + v.fc_w[2]; t.b3 = W + v.fc_b[2];
+    // score_forward's masks cover both towers, the user tower first: [2, B, 200] and [2, B, 80]
+    t.mask0 = mask0 ? mask0 + (int64_t)k * B * FC1 : nullptr; t.mask1 = mask1 ? mask1 + (int64_t)k * B * FC2 : nullptr;
+    t.f1 = ws + f1[k]; t.f2 = ws + f2[k]; t.dz1 = ws + dz1[k]; t.dz2 = ws + dz2[k];
+    t.logit = ws + w.deems_logit + (int64_t)k * B; t.y = ws + w.deems_y + (int64_t)k * B; t.dlogit = ws + w.deems_dlogit + (int64_t)k * B;
+    t.Dh = c.H + (k ? d.Di : d.Du); t.col = k ? d.off_i : d.off_u;
+  }
+}
+// does score_forward's fused head run (and leave dz2)?
+static bool deems_head_fused(const Pass& c) {
+  return !c.fl.head_unfused && score_deems_head_fwd_fits(c.H + c.d.Du, c.H + c.d.Di);
+}
+
 // ---------------------------------------------------------------- the two co-attention calls
 // 1: (user_1hop, item_2hop, target_item) ; 2: (user_2hop, item_1hop, target_user)  (score.py:196-197)
 // user_side = [user_1hop_seq | user_2hop_seq], item_side = [item_1hop_seq | item_2hop_seq]   (:200-201)
@@ -877,6 +1005,20 @@ static int queue_head(const Pass& c, GradQueues* q, float* gw, bool bn1_sums) {
     G(colsum_queue_add(&q->cq, ws + w.dgstage, B, d.Dhead, d.Dhead, gw + P.bn_g, 0));
     G(colsum_queue_add(&q->cq, ws + w.dbn, B, d.Dhead, d.Dhead, gw + P.bn_b, 0));
   }
+  return 0;
+}
+// ... of one of DEEMS's towers: the same products and column sums on that tower's buffers and variables (bn's sums always from
+// what the head's backward wrote: dgstage and dbn hold both towers' column ranges)
+static int queue_head_tower(const Pass& c, GradQueues* q, float* gw, const DeemsArgs& a, int k) {
+  const DeemsTower& t = a.t[k]; const DeemsVars v = deems_vars(c.P, k); const int B = c.B, ld = a.ld;
+  G(gemm_queue_add(&q->gq, FC2, 1, B, t.f2, FC2, t.dlogit, 1, gw + v.fc_w[2], 1));
+  G(colsum_queue_add(&q->cq, t.dlogit, B, 1, 1, gw + v.fc_b[2], 0));
+  G(gemm_queue_add(&q->gq, FC1, FC2, B, t.f1, FC1, t.dz2, FC2, gw + v.fc_w[1], FC2));
+  G(colsum_queue_add(&q->cq, t.dz2, B, FC2, FC2, gw + v.fc_b[1], 0));
+  G(gemm_queue_add(&q->gq, t.Dh, FC1, B, a.bn + t.col, ld, t.dz1, FC1, gw + v.fc_w[0], FC1));
+  G(colsum_queue_add(&q->cq, t.dz1, B, FC1, FC1, gw + v.fc_b[0], 0));
+  G(colsum_queue_add(&q->cq, a.tmp + t.col, B, t.Dh, ld, gw + v.bn_g, 0));
+  G(colsum_queue_add(&q->cq, a.dbn + t.col, B, t.Dh, ld, gw + v.bn_b, 0));
   return 0;
 }
 // the temporal attention's denses (score.py:169-186)
@@ -1044,7 +1186,11 @@ extern "C" int score_workspace_field(const score_config_t* cfg, int32_t B, const
       {"gcmc_gu", w.gcmc_gu, w.gcmc_gu + (int64_t)B * d.H}, {"caser_hwin", w.caser_hwin, -1}, {"caser_arg", w.caser_arg, -1},
       {"caser_v", w.caser_v, -1}, {"delf_key", w.delf_key[0], w.delf_key[1]}, {"delf_att", w.delf_att[0], w.delf_att[1]},
       {"delf_rep", w.delf_rep[0], w.delf_rep[1]}, {"delf_ds", w.delf_ds[0], w.delf_ds[1]},
-      {"delf_dpre", w.delf_dpre[0], w.delf_dpre[1]}, {"delf_act", w.delf_act, -1}, {"delf_dact", w.delf_dact, -1}};
+      {"delf_dpre", w.delf_dpre[0], w.delf_dpre[1]}, {"delf_act", w.delf_act, -1}, {"delf_dact", w.delf_dact, -1},
+      {"deems_f1", w.deems_f1 < 0 ? -1 : w.f1, w.deems_f1}, {"deems_f2", w.deems_f2 < 0 ? -1 : w.f2, w.deems_f2},
+      {"deems_dz1", w.deems_dz1 < 0 ? -1 : w.dz1, w.deems_dz1}, {"deems_dz2", w.deems_dz2 < 0 ? -1 : w.dz2, w.deems_dz2},
+      {"deems_logit", w.deems_logit, w.deems_logit + B}, {"deems_y", w.deems_y, w.deems_y + B},
+      {"deems_dlogit", w.deems_dlogit, w.deems_dlogit + B}};
   for (auto& e : tab)
     if (strcmp(e.n, name) == 0) {
       if (e.a < 0) return SCORE_E_BADARG;       // (a region of another model type)
@@ -1271,9 +1417,9 @@ int backward_ps(const Pass& c, const PsPlan& pp, float keep_prob, float* gw, flo
   a.caslab[0] = ws + w.ca_slab; a.caslab[1] = ws + w.ca_slab + (int64_t)B * 2 * d.Di;
   a.keep = keep_prob; a.rs = c.rs;
   {
-    score_param_entry_t ent[32];
+    score_param_entry_t ent[MAX_ENTRIES];
     Params Pl;
-    const int ne = build_layout(d, ent, 32, &Pl);
+    const int ne = build_layout(d, ent, MAX_ENTRIES, &Pl);
     if (ne < 0) return ne;
     a.gw = gw; a.npad = 0;
     for (int i = 0; i < ne; ++i) {
@@ -1602,6 +1748,40 @@ int fwd_delf(const Pass& c, const FwdState& f) {
   EV(4);
   return 0;
 }
+
+int fwd_deems(const Pass& c, const FwdState& f) {
+  const WS& w = c.w; const int B = c.B; hipStream_t s = c.s;
+  void* const* stage_events = f.stage_events;
+  HIPTRY(hipStreamWaitEvent(s, f.sd->wx, 0));
+  G(deems_grus_fwd(c));
+  EV(2);
+  EV(3);
+  HIPTRY(hipStreamWaitEvent(s, f.sd->join, 0));       // (the target rows in head_inp come from the side stream)
+  DeemsArgs a;
+  deems_args(c, f.keep_prob, f.mask0, f.mask1, f.seed, &a);
+  // both towers, y and the loss terms in ONE launch (deems.hip); the final states go into head_inp on the way
+  int hrc = c.fl.head_unfused ? SCORE_E_SHAPE : score_deems_head_fwd(a, s);
+  if (hrc != 0 && hrc != SCORE_E_SHAPE) return hrc;
+  if (hrc == SCORE_E_SHAPE) {       // ... or layer by layer: bn of both towers, then each tower's three denses, then the combine
+    if (c.st->step_scalars && f.keep_prob < 1.f) return SCORE_E_SHAPE;   // (this form takes its seed by value)
+    const int dflag = f.keep_prob < 1.f ? GF_DROP : 0;
+    G(score_deems_bn_fwd(a, s));
+    for (int k = 0; k < 2; ++k) {
+      const DeemsTower& t = a.t[k];
+      const uint64_t seed = f.seed ^ (k ? SCORE_DEEMS_ITEM_SEED : 0ull);
+      G(gemm_mode_call(c.x3, 0, B, FC1, t.Dh, a.bn + t.col, a.ld, t.W1, FC1, t.f1, FC1, t.b1, GF_BIAS | GF_RELU | dflag, f.keep_prob,
+                       t.mask0, seed, c.scratch, w.scratch_floats, s));
+      G(gemm_mode_call(c.x3, 0, B, FC2, FC1, t.f1, FC1, t.W2, FC2, t.f2, FC2, t.b2, GF_BIAS | GF_RELU | dflag, f.keep_prob, t.mask1,
+                       seed ^ 0x5DEECE66Dull, c.scratch, w.scratch_floats, s));
+      G(gemm_mode_call(c.x3, 0, B, 1, FC2, t.f2, FC2, t.W3, 1, t.logit, 1, t.b3, GF_BIAS, 1.f, nullptr, 0, c.scratch,
+                       w.scratch_floats, s));
+    }
+    G(score_deems_out(a, s));
+  }
+  G(loss_tail(c, f.sd, f.reg_lambda));
+  EV(4);
+  return 0;
+}
 }  // namespace
 
 extern "C" int score_forward(const score_config_t* cfg, const score_state_t* st, const score_batch_t* bt,
@@ -1614,7 +1794,7 @@ extern "C" int score_forward(const score_config_t* cfg, const score_state_t* st,
   if (!bt->user_1hop || !bt->user_2hop || !bt->item_1hop || !bt->item_2hop || !bt->target_user ||
       !bt->target_item || !bt->label || !bt->length)
     return SCORE_E_BADARG;
-  if (c.d.family == FAM_DELF && !bt->length2) return SCORE_E_BADARG;        // (item_seq_length: the one model type that reads it)
+  if ((c.d.family == FAM_DELF || c.d.family == FAM_DEEMS) && !bt->length2) return SCORE_E_BADARG;        // (item_seq_length: the model types that read it)
   if (!(keep_prob > 0.f) || keep_prob > 1.f) return SCORE_E_BADARG;
   SCORE_TRY(pass_fill(&c, st, bt, stream));
   {
@@ -1630,6 +1810,7 @@ extern "C" int score_forward(const score_config_t* cfg, const score_state_t* st,
     case FAM_G4R: return fwd_g4r(c, f);
     case FAM_CASER: return fwd_caser(c, f);
     case FAM_DELF: return fwd_delf(c, f);
+    case FAM_DEEMS: return fwd_deems(c, f);
   }
   return SCORE_E_BADARG;
 }
@@ -2061,6 +2242,48 @@ int bwd_delf(const Pass& c, BwdState* b) {
   G(bwd_side_products(c, b));       // (no recurrence; delf.hip wrote both dxside above)
   return bwd_close(c, b);
 }
+
+int bwd_deems(const Pass& c, BwdState* b) {
+  const Dims& d = c.d; const WS& w = c.w; float* ws = c.ws; const int B = c.B, H = c.H, BT = c.BT; hipStream_t s = c.s;
+  void* const* stage_events = b->stage_events;
+  const int64_t SF = w.scratch_floats;
+  G(bwd_open(c, b));
+  // ---- both towers' heads: from dz2 (score_forward's fused head left it) to dz1, d bn, d head input in ONE launch (deems.hip)
+  DeemsArgs a;
+  deems_args(c, b->keep_prob, nullptr, nullptr, 0, &a);
+  if (!deems_head_fused(c))
+    for (int k = 0; k < 2; ++k)
+      G(score_launch_outer_relu_bwd(B, FC2, a.t[k].dlogit, a.t[k].W3, a.t[k].f2, b->keep_prob, a.t[k].dz2, s));
+  if (!c.fl.head_unfused) {
+    G(score_deems_head_bwd(a, s));
+  } else {      // ... or layer by layer, per tower
+    for (int k = 0; k < 2; ++k) {
+      const DeemsTower& t = a.t[k];
+      G(gemm_mode_call(c.x3, 1, B, FC1, FC2, t.dz2, FC2, t.W2, FC2, t.dz1, FC1, nullptr, GF_RELUGRAD, b->keep_prob,
+                       reinterpret_cast<const uint8_t*>(t.f1), 0, c.scratch, SF, s));
+      G(gemm_mode_call(c.x3, 1, B, t.Dh, FC1, t.dz1, FC1, t.W1, FC1, a.dbn + t.col, a.ld, nullptr, 0, 1.f, nullptr, 0, c.scratch, SF, s));
+    }
+    G(score_deems_bn_bwd(a, s));
+  }
+  for (int k = 0; k < 2; ++k) G(queue_head_tower(c, &b->q, b->gw, a, k));
+  EV(1);
+  // the gradient enters each recurrence through its final state only: the first H columns of its tower's range of dhead
+  G(bwd_final_state(c, b, 0, d.off_u, true));
+  G(bwd_final_state(c, b, 1, d.off_i, true));
+  G(bwd_zero_dinfo(c));
+  EV(2);
+  G(bwd_side_products(c, b));
+  G(deems_grus_bwd(c, b->dfinal, &b->gru_bias_rows));
+  // the recurrences' queued weight gradients and d x = [dgates | dcand] . [Wx_gates | Wx_cand]^T into the Is[sd] leading columns of
+  // dxside[sd] (the other columns carry no gradient), as RRN's and GRU4Rec's layer 1
+  for (int sd = 0; sd < 2; ++sd) {
+    G(queue_gru_side(c, &b->q, b->gw, sd, b->gru_bias_rows));
+    HIPTRY(hipMemsetAsync(ws + w.dxside[sd], 0, (int64_t)BT * d.I * sizeof(float), s));
+    G(gemm_mode_call(c.x3, 1, BT, d.Is[sd], 3 * H, ws + w.dxproj[sd], 3 * H, wxcat(c, sd), 3 * H, ws + w.dxside[sd], d.I, nullptr, 0, 1.f,
+                     nullptr, 0, c.scratch, SF, s));
+  }
+  return bwd_close(c, b);
+}
 }  // namespace
 
 extern "C" int score_backward(const score_config_t* cfg, const score_state_t* st, const score_batch_t* bt,
@@ -2070,7 +2293,7 @@ extern "C" int score_backward(const score_config_t* cfg, const score_state_t* st
   SCORE_TRY(make_dims(cfg, &c.d));
   if (!st || !bt || !st->table || !st->w || !st->workspace || !gw || !grad_table || bt->B <= 0)
     return SCORE_E_BADARG;
-  if (c.d.family == FAM_DELF && (!bt->length || !bt->length2)) return SCORE_E_BADARG;
+  if ((c.d.family == FAM_DELF || c.d.family == FAM_DEEMS) && (!bt->length || !bt->length2)) return SCORE_E_BADARG;
   SCORE_TRY(pass_fill(&c, st, bt, stream));
   {
     PsPlan pp;
@@ -2087,6 +2310,7 @@ extern "C" int score_backward(const score_config_t* cfg, const score_state_t* st
     case FAM_G4R: return bwd_g4r(c, &b);
     case FAM_CASER: return bwd_caser(c, &b);
     case FAM_DELF: return bwd_delf(c, &b);
+    case FAM_DEEMS: return bwd_deems(c, &b);
   }
   return SCORE_E_BADARG;
 }

@@ -349,12 +349,13 @@ __global__ __launch_bounds__(64 * NW) void gru_fwd_reg_kernel(const GruArgs a) {
   // Rows past the batch are DUPLICATES of the last sample: same inputs, same arithmetic, the same values stored to
   // the same addresses (a benign race) -- so a ragged batch needs no predicated memory operation either (with
   // stores under exec-mask branches the compiler's s_waitcnt placement falls back to vmcnt(0) in the time loop).
+  const int32_t* side_len = sd.length;      // (the side's own lengths -- DEEMS's two histories -- or GruArgs.length: gru_reg_args)
   int len[4];
   int64_t rowb[4];                // row of (sample, t = 0)
 #pragma unroll
   for (int r = 0; r < 4; ++r) {
     const int bc = min(b0 + lq * 4 + r, a.B - 1);
-    len[r] = a.length[bc];
+    len[r] = side_len[bc];
     rowb[r] = (int64_t)bc * T;
   }
   constexpr bool rok[4] = {true, true, true, true};
@@ -498,13 +499,14 @@ __global__ __launch_bounds__(64 * NW) void gru_bwd_reg_kernel(const GruArgs a) {
   // every thread owns the elements (row i = lq*4 + r, column j = (wave + NW*tt)*16 + lc) in all three
   // phases, so the saved activations of a step are read once, about one step ahead of their use.
   // Rows past the batch are duplicates of the last sample (see the forward): no predicated memory operation.
+  const int32_t* side_len = sd.length;
   int len[4], bcs[4];
   int64_t rowb[4];
   constexpr bool rok[4] = {true, true, true, true};
 #pragma unroll
   for (int r = 0; r < 4; ++r) {
     bcs[r] = min(b0 + lq * 4 + r, a.B - 1);
-    len[r] = a.length[bcs[r]];
+    len[r] = side_len[bcs[r]];
     rowb[r] = (int64_t)bcs[r] * T;
   }
 #pragma unroll
@@ -841,6 +843,16 @@ static GruRoute gru_route(const GruArgs& a, int nsides) {
   return {GRU_PER_SIDE, 0};
 }
 
+bool score_gru_reg_route(const GruArgs& a, int nsides) { return gru_route(a, nsides).family == GRU_REG; }
+// the register kernels' argument block: a side without lengths of its own (GruSide.length null) reads GruArgs.length.  Settled
+// here, on the host, so that the kernels' prologues load one pointer and test nothing
+static GruArgs gru_reg_args(const GruArgs& a, int nsides) {
+  GruArgs k = a;
+  for (int i = 0; i < nsides; ++i)
+    if (!k.s[i].length) k.s[i].length = a.length;
+  return k;
+}
+
 int score_gru_fwd_multi(GruArgs& a, int nsides, hipStream_t s) {
   const int H = a.H;
   const GruRoute rt = gru_route(a, nsides);
@@ -848,7 +860,8 @@ int score_gru_fwd_multi(GruArgs& a, int nsides, hipStream_t s) {
     case GRU_X3: return score_gru_fwd_x3(a, nsides, s);
     case GRU_REG: {
       dim3 grid(nsides * ((a.B + RRB - 1) / RRB));
-#define LF(Hv, NWv) hipLaunchKernelGGL((gru_fwd_reg_kernel<Hv, NWv>), grid, dim3(64 * NWv), 0, s, a)
+      const GruArgs k = gru_reg_args(a, nsides);
+#define LF(Hv, NWv) hipLaunchKernelGGL((gru_fwd_reg_kernel<Hv, NWv>), grid, dim3(64 * NWv), 0, s, k)
       if (H == 16) LF(16, 4);
       else if (H == 32) LF(32, 4);
       else if (H == 64) LF(64, 4);
@@ -877,7 +890,8 @@ int score_gru_bwd_multi(GruArgs& a, int nsides, hipStream_t s) {
     case GRU_X3: return score_gru_bwd_x3(a, nsides, s);
     case GRU_REG: {
       dim3 grid(nsides * ((a.B + RRB - 1) / RRB));
-#define LB(Hv, NWv) hipLaunchKernelGGL((gru_bwd_reg_kernel<Hv, NWv>), grid, dim3(64 * NWv), 0, s, a)
+      const GruArgs k = gru_reg_args(a, nsides);
+#define LB(Hv, NWv) hipLaunchKernelGGL((gru_bwd_reg_kernel<Hv, NWv>), grid, dim3(64 * NWv), 0, s, k)
       if (H == 16) LB(16, 4);
       else if (H == 32) {     // two waves from 20 slices on: a shorter step, a longer prologue (each wave holds twice the weights) -- the CCMR
         if (a.T >= 20) LB(32, 2);     // shape (T = 40) 0.5174 -> 0.5064 ms/step, cfg-2 (T = 10) 0.272 -> 0.278; the forward keeps four

@@ -232,6 +232,8 @@ struct GruSide {
   float* hprev;                  // [B*T, H] h_{t-1}  (+ 3*H*H scratch floats at its end for the fallback)
   float* bias_slab;              // optional [workgroups of this side][3H]: column sums of the dxproj rows a workgroup wrote
                                  // (the bias gradients' partial sums; only kernels that report GruArgs.bias_slab_rows fill it)
+  const int32_t* length;         // optional [B]: this side's own sequence lengths (null: GruArgs.length).  Honoured by the register
+                                 // kernels of gru.hip only (score_gru_reg_route); every other recurrence takes GruArgs.length
 };
 struct GruArgs {
   GruSide s[2];
@@ -268,6 +270,9 @@ int score_gru_fwd_x3(GruArgs& a, int nsides, hipStream_t s);
 int score_gru_bwd_x3(GruArgs& a, int nsides, hipStream_t s);
 int score_gru_fwd_multi(GruArgs& a, int nsides, hipStream_t s);
 int score_gru_bwd_multi(GruArgs& a, int nsides, hipStream_t s);
+// do score_gru_*_multi run these arguments on the register kernels of gru.hip (H in {16, 32, 64, 128} and not the bf16x3 route)?
+// Only then does a side's own GruSide.length count
+bool score_gru_reg_route(const GruArgs& a, int nsides);
 // gcmc.hip: the GCMC slice baseline's bilinear two-way softmax head (slice_model.py:199-201), H <= 256.  Forward: y, the
 // per-sample log-loss term, and p = h_i W4, n = h_i W5, g = dL/da saved for the backward; backward: dh_u, dh_i and the rows
 // gpos = g h_u, gneg = -g h_u of the dense gradients dW4 = h_i^T gpos, dW5 = h_i^T gneg
@@ -331,3 +336,32 @@ struct DelfArgs {
 };
 int score_delf_fwd(const DelfArgs& a, hipStream_t s);
 int score_delf_bwd(const DelfArgs& a, hipStream_t s);
+// deems.hip: the DEEMS point baseline's two build_fc_net towers (point_model.py:292-311).  x [B, ld] holds both head inputs as
+// column ranges of one row, [h_u | target_user | h_i | target_item]: tower k owns columns [col, col + Dh), the first H of them the
+// final state of its recurrence (h: where the recurrence left it, [B, H]; the forward kernels store it into x on the way; null: x
+// holds it already).  bn, dbn, dhead and tmp (bn's d gamma terms) are laid out as x; f1 / f2 / dz1 / dz2 / logit / y / dlogit are
+// per tower.  mask0 [B, 200] / mask1 [B, 80]: this tower's explicit dropout masks or null (then from seed0, or *seed_dev; the item
+// tower's stream is the user tower's seed ^ SCORE_DEEMS_ITEM_SEED).  lossb: log-loss term + 0.05 (y_i - y_u)^2 * Bglobal, so that
+// the mean the loss reduction takes gives mean(log-loss) + SUM(consistency); dlogit: of the log-loss alone.
+#define SCORE_DEEMS_ITEM_SEED 0xD1B54A32D192ED03ull
+struct DeemsTower {
+  const float* h;
+  const float* gamma; const float* beta;
+  const float* W1; const float* b1; const float* W2; const float* b2; const float* W3; const float* b3;
+  const uint8_t* mask0; const uint8_t* mask1;
+  float* f1; float* f2; float* dz2; float* dz1; float* logit; float* y; float* dlogit;
+  int Dh, col;
+};
+struct DeemsArgs {
+  DeemsTower t[2];       // 0: user tower, 1: item tower
+  int B, H, ld, Bglobal;
+  float* x; float* bn; float* dbn; float* dhead; float* tmp;
+  float rs, keep; uint64_t seed0; const uint64_t* seed_dev;
+  const int32_t* label; float* y_pred; float* lossb;
+};
+bool score_deems_head_fwd_fits(int Dh_user, int Dh_item);
+int score_deems_head_fwd(const DeemsArgs& a, hipStream_t s);      // everything in one launch; SCORE_E_SHAPE: does not fit
+int score_deems_bn_fwd(const DeemsArgs& a, hipStream_t s);        // the layer-by-layer form: both towers' bn ...
+int score_deems_out(const DeemsArgs& a, hipStream_t s);           // ... and, from the two logits, y / lossb / dlogit
+int score_deems_head_bwd(const DeemsArgs& a, hipStream_t s);      // both towers' head backward in one launch (from dz2)
+int score_deems_bn_bwd(const DeemsArgs& a, hipStream_t s);        // the layer-by-layer form's bn backward, both towers

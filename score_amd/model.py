@@ -222,7 +222,7 @@ def active_slices(model, max_len, min_len=None):
     T = int(model.cfg.max_time_len)
     if not getattr(model, "skip_masked_slices", True) or not getattr(model, "reads_length", True):
         return 0
-    if min_len is not None and int(min_len) <= 0:
+    if min_len is not None and int(min_len) <= 0 and getattr(model, "zero_length_reads_all", True):
         # (DELF: a sample whose every position is masked gets uniform weights over ALL T positions, point_model.py:246-247 --
         #  the batch computes them all; max_len is the maximum over both length tensors)
         return 0
@@ -234,6 +234,8 @@ class SCOREBASE(object):
     model_type = None
     feed_spec = SLICE_FEED
     reads_length = True          # False: the model's graph does not use the length tensor -- every slice is computed (Caser)
+    zero_length_reads_all = True  # (two length tensors) a length <= 0 makes the batch compute all T slices: DELF's rule, not DEEMS's
+    dropout_towers = 1           # build_fc_net heads with dropout masks of their own (DEEMS: 2, masks [2, B, 200] / [2, B, 80])
     head_pad_vars = ()           # variables whose rows 1..3 exist in the library's layout only (Caser's padded head input)
 
     def __init__(self, feature_size, eb_dim, hidden_size, max_time_len, obj_per_time_slice,
@@ -901,8 +903,9 @@ class SCOREBASE(object):
         if masks is not None:
             m0 = torch.as_tensor(np.asarray(masks[0]), dtype=torch.uint8).to(self.device).contiguous()
             m1 = torch.as_tensor(np.asarray(masks[1]), dtype=torch.uint8).to(self.device).contiguous()
-            if tuple(m0.shape) != (db.B, 200) or tuple(m1.shape) != (db.B, 80):
-                raise ValueError("dropout masks must be [B,200] and [B,80]")
+            lead = (self.dropout_towers,) if self.dropout_towers > 1 else ()
+            if tuple(m0.shape) != lead + (db.B, 200) or tuple(m1.shape) != lead + (db.B, 80):
+                raise ValueError("dropout masks must be %s and %s" % (list(lead + ("B", 200)), list(lead + ("B", 80))))
         seed = (self._drop_seed * 0x9E3779B1 + self.step * 0x85EBCA77) & 0xFFFFFFFFFFFFFFFF
         events = self.fwd_events
         if stage_event is not None:          # (k, event): score_forward records it at its stage boundary k
@@ -1929,5 +1932,23 @@ class DELF(GRU4Rec):
     target_item_field = 5
 
 
+class DEEMS(DELF):
+    """point_models/point_model.py:281-311 on DELF: h_u, the final state of gru1 over user_seq under user_seq_length, and h_i,
+    that of gru2 over item_seq under item_seq_length (GRUCell(hidden_size) -- used here --, dynamic_rnn semantics: a length >=
+    max_time_len means all positions, a length <= 0 a zero final state), through two build_fc_net towers with variables and
+    dropout masks of their own, y_u on [h_u | target_user] and y_i on [h_i | target_item]; y_pred = (y_u + y_i) / 2.  DELF's
+    constructor, 7-tuple and train / eval / save / restore.
+
+    As in the reference, train() and eval() RETURN log_loss + reg_lambda * l2 + 0.05 * sum_b (y_i - y_u)^2, while the gradient
+    Adam applies is that of log_loss + reg_lambda * l2 alone: train_step is built before the consistency term is added
+    (:299-300).  DELF's 22 variables (dense .. dense_10) exist, are regularised, exported and checkpointed, and never enter the
+    prediction: their kernels decay under reg_lambda, their biases never change.  Variables under TF's names: dense .. dense_10,
+    gru1 / gru2, batch_normalization, dense_11 .. dense_13 (user tower), batch_normalization_1, dense_14 .. dense_16 (item
+    tower).  dropout_masks, where given, is a pair shaped [2, B, 200], [2, B, 80], the user tower first."""
+    model_type = "DEEMS"
+    zero_length_reads_all = False
+    dropout_towers = 2
+
+
 MODELS = {"SCORE": SCORE, "RIA": RIA, "RCA": RCA, "SCORE_USER": SCORE_USER, "SCORE_ITEM": SCORE_ITEM, "RRN": RRN, "GCMC": GCMC,
-          "GRU4Rec": GRU4Rec, "Caser": Caser, "DELF": DELF}
+          "GRU4Rec": GRU4Rec, "Caser": Caser, "DELF": DELF, "DEEMS": DEEMS}

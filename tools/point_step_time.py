@@ -1,5 +1,5 @@
-"""ms per training step (and per evaluation call) of a point baseline (point_models/point_model.py:123-164, 200-249: GRU4Rec, Caser,
-DELF) through
+"""ms per training step (and per evaluation call) of a point baseline (point_models/point_model.py:123-164, 200-249, 281-311:
+GRU4Rec, Caser, DELF, DEEMS) through
 the reference's train() / eval signatures, at the reference's point-model shapes (train_time_point_models.py:15-35, 353-354):
 Tmall, N = 1,529,672, D = 16, H = 32, T = 50, Fu = 3, Fi = 4,
   train100: B = 100      train200: B = 200      eval1000: forward only (eval_async), B = 1000
@@ -7,6 +7,9 @@ each in both forms of the two stacked recurrences: "stacked" (csrc/gru_stack.hip
 (debug_flags bit 13: one layer per launch with the projection GEMM between them -- kernels the other model types run too).
 --model Caser times the Caser baseline (form "caser": csrc/caser.hip) against GRU4Rec's stacked form, alternating, same protocol;
 --model DELF the DELF baseline (form "delf": csrc/delf.hip; its batches carry a second history and length).
+--model DEEMS alternates DEEMS's own two forms on DELF's batches: "deems" (csrc/deems.hip: both towers in one launch each way, both
+recurrences in one grouped launch each way) and "deems_composed" (debug_flags bits 6 | 13: the towers layer by layer, one
+recurrence per launch).
 Every (case, form) runs in a fresh process: `warmup` untimed steps, then `steps` timed ones over a few pre-staged device
 batches (random ids; history lengths as the loader reports them, up to 300, so most samples run all T steps), wall clock
 between two device synchronisations.  With --pairs n the two forms alternate n times.
@@ -16,6 +19,7 @@ between two device synchronisations.  With --pairs n the two forms alternate n t
     python tools/point_step_time.py --case train200 --form composed --steps 200 --warmup 20
     python tools/point_step_time.py --model Caser --pairs 3  # three cases, (GRU4Rec stacked, Caser) alternating three times
     python tools/point_step_time.py --model DELF --pairs 3   # ... (GRU4Rec stacked, DELF)
+    python tools/point_step_time.py --model DEEMS --pairs 3  # ... (DEEMS fused, DEEMS composed)
     python tools/point_step_time.py --case train200 --form stacked --profile-steps 30     # no timing: a short run for a profiler
 """
 import argparse
@@ -28,9 +32,10 @@ import time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 TMALL = dict(N=1529672, D=16, H=32, T=50, Fu=3, Fi=4)
 CASES = {"train100": dict(B=100, train=True), "train200": dict(B=200, train=True), "eval1000": dict(B=1000, train=False)}
-FORMS = {"stacked": 0, "composed": 8192, "caser": 0, "delf": 0}                    # debug_flags of a form
-FORM_MODEL = {"stacked": "GRU4Rec", "composed": "GRU4Rec", "caser": "Caser", "delf": "DELF"}
-PAIRS = {"GRU4Rec": ("stacked", "composed"), "Caser": ("stacked", "caser"), "DELF": ("stacked", "delf")}     # what --model alternates
+FORMS = {"stacked": 0, "composed": 8192, "caser": 0, "delf": 0, "deems": 0, "deems_composed": 64 | 8192}      # debug_flags of a form
+FORM_MODEL = {"stacked": "GRU4Rec", "composed": "GRU4Rec", "caser": "Caser", "delf": "DELF", "deems": "DEEMS", "deems_composed": "DEEMS"}
+PAIRS = {"GRU4Rec": ("stacked", "composed"), "Caser": ("stacked", "caser"), "DELF": ("stacked", "delf"),
+         "DEEMS": ("deems", "deems_composed")}     # what --model alternates
 
 
 def run_one(case, form, steps, warmup, n_batches=4, H=None):
@@ -48,7 +53,7 @@ def run_one(case, form, steps, warmup, n_batches=4, H=None):
     B, T, Fu, Fi = s["B"], s["T"], s["Fu"], s["Fi"]
     ids = lambda *sh: torch.randint(1, s["N"], sh, **dev)
     lens = lambda: torch.randint(1, 301, (B,), **dev)
-    if form == "delf":      # (the 7-tuple: a second history, of users, with lengths of its own)
+    if FORM_MODEL[form] in ("DELF", "DEEMS"):      # (the 7-tuple: a second history, of users, with lengths of its own)
         batches = [m.device_batch((ids(B, T, Fi), lens(), ids(B, T, Fu), lens(), ids(B, Fu), ids(B, Fi),
                                    torch.randint(0, 2, (B,), **dev))) for _ in range(n_batches)]
     else:
