@@ -137,7 +137,27 @@ enum { SCORE_MODEL_SCORE = 0, SCORE_MODEL_RIA = 1, SCORE_MODEL_RCA = 2,
         * (128: with gemm_mode 0 or debug_flags bit 2) both recurrences run as ONE launch each way, each side under its own lengths;
         * other H, and debug_flags bit 13, run one launch per side.  Both towers and the loss terms are ONE launch each way
         * (csrc/deems.hip); debug_flags bit 6 runs them layer by layer. */
-       SCORE_MODEL_DEEMS = 10 };
+       SCORE_MODEL_DEEMS = 10,
+       /* point_models/point_model.py:167-198 (SVDpp) on PointBaseModel (:9-63): the matrix-factorisation baseline.  One scalar
+        * weight per feature field; per sample p_u = sum_i wu_i E(target_user[i]), p_i = sum_j wi_j E(target_item[j]),
+        * s_t = [t < length] sum_j wi_j E(user_seq[t][j]) (tf.sequence_mask: a length >= T means all T positions), nb = sum_t s_t,
+        * n = tf.norm(s, 1, (1, 2)) -- the MATRIX 1-norm: max over the D columns of sum_t |s_t,d| --, q = nb / sqrt(n),
+        * y_pred = sigmoid(<p_i, p_u + q>), tf.losses.log_loss + reg_lambda * sum w^2 / 2 over the scalars (emb_mtx is not
+        * regularised).  No bn, no fc head, no dropout (keep_prob has no effect); hidden_size is accepted and ignored.  The
+        * gradient of the maximum is shared equally among the columns that attain it (reduce_max), sign(0) = 0.  A sample whose
+        * length is <= 0 or whose live history rows are all id 0 has n = 0 and nb = 0: q = 0 / 0, so its y_pred and the batch
+        * loss are NaN, as in TF (the reference's loader yields no such sample); nothing special-cases it.
+        * score_param_layout: Fu + Fi entries in TF's creation order, user_feat_w_0 .. user_feat_w_{Fu-1}, item_feat_w_0 ..
+        * item_feat_w_{Fi-1}, each rows = 1, cols = 0, regularised, init 4.  Offsets stay multiples of 4: every scalar owns a
+        * 4-float cell of the regularised region whose three pad floats are zero from initialisation on and a fixed point of
+        * training (zero gradient, zero L2 term, zero Adam update).  obj_per_time_slice must be 1, eb_dim <= 128 (a pass
+        * also needs user_fnum, item_fnum <= 8, the index plan's limit for every type).  The batch rides as for SCORE_MODEL_GRU4REC (user_1hop = user_seq as [B, T, 1, Fi], length =
+        * user_seq_length, read; the other index tensors zeros; length2 NULL); active_slices = A promises every length <= A, and a
+        * length <= 0 does not ask for all T slices.  Workspace field (score_workspace_field): svdpp_act [B, 4 D + 4] =
+        * [p_u | p_i | nb | share | n, ties, 0, 0], share_d = [c_d == n] / ties with c_d = sum_t |s_t,d| and ties the number of
+        * maximal columns.  Kernels: csrc/svdpp.hip, one launch each way; the batch sums of the weight gradients through the
+        * queued column sums, every sum in a fixed order. */
+       SCORE_MODEL_SVDPP = 11 };
 
 /* Constructor arguments of SCOREBASE.__init__ (score.py:12-13). */
 typedef struct {
@@ -145,7 +165,7 @@ typedef struct {
   int32_t eb_dim;              /* D: multiple of 4, <= 256                        */
   int32_t hidden_size;         /* H                                               */
   int32_t max_time_len;        /* T                                               */
-  int32_t obj_per_time_slice;  /* K <= 32 (SCORE_MODEL_GRU4REC / _CASER / _DELF / _DEEMS: 1) */
+  int32_t obj_per_time_slice;  /* K <= 32 (SCORE_MODEL_GRU4REC / _CASER / _DELF / _DEEMS / _SVDPP: 1) */
   int32_t user_fnum;           /* Fu                                              */
   int32_t item_fnum;           /* Fi                                              */
   int32_t model_type;          /* SCORE_MODEL_*                                   */
@@ -158,7 +178,8 @@ typedef struct {
   int64_t offset;              /* in floats, into the flat buffer                 */
   int32_t rows, cols;          /* cols == 0 for vectors                           */
   int32_t regularised;         /* build_l2norm name filter, score.py:91-94        */
-  int32_t init;                /* 0 zeros, 1 ones, 2 glorot-uniform, 3 glorot-uniform with TF's convolution fans: fan_in = fan_out = rows * cols */
+  int32_t init;                /* 0 zeros, 1 ones, 2 glorot-uniform, 3 glorot-uniform with TF's convolution fans: fan_in = fan_out = rows * cols,
+                                  4 truncated normal(0, 1): values beyond +-2 redrawn (tf.truncated_normal_initializer) */
 } score_param_entry_t;
 
 /* Layout of the flat dense-parameter buffer: regularised tensors first

@@ -11,7 +11,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "lib", "libscore_hip.so")
 
 MODEL_TYPES = {"SCORE": 0, "RIA": 1, "RCA": 2, "SCORE_USER": 3, "SCORE_ITEM": 4, "RRN": 5, "GCMC": 6, "GRU4Rec": 7, "Caser": 8, "DELF": 9,
-               "DEEMS": 10}
+               "DEEMS": 10, "SVDpp": 11}
 
 MAX_PARAM_ENTRIES = 48   # dense variables of a model type at most (DEEMS: 46)
 

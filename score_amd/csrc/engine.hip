@@ -1,7 +1,7 @@
 // Whole-path orchestration: parameter/workspace layout and the forward / backward
 // launch sequences of SCORE and its ablations (score.py:188-369) and of the slice baselines RRN and GCMC
-// (slice_model.py:155-203) and of the point baselines GRU4Rec, Caser, DELF and DEEMS (point_model.py:123-164, 200-249, 281-311) on
-// one stream.  Host code only; every kernel lives in embed/gemm/gru/gru_stack/head/gcmc/caser/delf/deems.hip.
+// (slice_model.py:155-203) and of the point baselines GRU4Rec, Caser, SVD++, DELF and DEEMS (point_model.py:123-311) on
+// one stream.  Host code only; every kernel lives in embed/gemm/gru/gru_stack/head/gcmc/caser/delf/deems/svdpp.hip.
 #include <string.h>
 #include <stdlib.h>
 #include <stdio.h>
@@ -20,7 +20,7 @@ const int MAX_ENTRIES = 48;       // dense variables of a model type at most (DE
 
 // What decides a pass's launch sequence.  FAM_SLICE: SCORE, RIA, RCA, SCORE_USER, SCORE_ITEM and RRN, which differ by attn, coattn
 // and Is[] only; every other model type is a family of its own
-enum Family { FAM_SLICE, FAM_GCMC, FAM_G4R, FAM_CASER, FAM_DELF, FAM_DEEMS };
+enum Family { FAM_SLICE, FAM_GCMC, FAM_G4R, FAM_CASER, FAM_DELF, FAM_DEEMS, FAM_SVDPP };
 
 struct Dims {
   int64_t N;
@@ -35,9 +35,10 @@ struct Dims {
   // FAM_DEEMS: side 0 = gru1 over the user_seq rows (Di columns of xside[0], lengths score_batch_t.length), side 1 = gru2 over the
   //   item_seq rows (Du columns of xside[1], lengths length2); two fc heads of its own on the column ranges [h_u | target_user]
   //   and [h_i | target_item] of ONE head_inp row; DELF's 22 variables laid out and regularised, never read by a launch
+  // FAM_SVDPP: no recurrence, no head (H = 0 here); X = Di columns of xside[0]; Fu + Fi scalar variables (svdpp.hip)
   Family family;
-  int n_gru;             // recurrences with variables, workspace and launches: 2, or 0 (Caser, DELF)
-  bool fc_head;          // bn1 and fc1-3 behind head_inp (not GCMC, DELF; DEEMS has two heads of its own, deems_tower)
+  int n_gru;             // recurrences with variables, workspace and launches: 2, or 0 (Caser, DELF, SVD++)
+  bool fc_head;          // bn1 and fc1-3 behind head_inp (not GCMC, DELF, SVD++; DEEMS has two heads of its own, deems_tower)
   bool sums_1hop;        // the gather leaves plain 1-hop sums: no co-attention, no attention, Is[] = {Di, Du} (RRN and every later type)
   bool reads_targets;    // the model reads the target rows (not GCMC: their gradient is zero)
   int Ic;          // row capacity of a side's block of the concatenated [Wx_gates | Wx_cand] copy: I (GRU4Rec: max(I, H))
@@ -49,16 +50,20 @@ int make_dims(const score_config_t* c, Dims* d) {
   d->N = c->feature_size; d->D = c->eb_dim; d->H = c->hidden_size; d->T = c->max_time_len;
   d->K = c->obj_per_time_slice; d->Fu = c->user_fnum; d->Fi = c->item_fnum; d->mt = c->model_type;
   if (d->N <= 0 || d->D <= 0 || (d->D & 3) || d->D > 256 || d->H <= 0 || d->T <= 0 || d->K <= 0 || d->K > 32 ||
-      d->Fu <= 0 || d->Fi <= 0 || d->mt < 0 || d->mt > SCORE_MODEL_DEEMS)
+      d->Fu <= 0 || d->Fi <= 0 || d->mt < 0 || d->mt > SCORE_MODEL_SVDPP)
     return SCORE_E_SHAPE;
   d->Du = d->Fu * d->D; d->Di = d->Fi * d->D; d->I = d->Di + d->Du; d->Dq = d->Du + d->Di;
   const bool gcmc = d->mt == SCORE_MODEL_GCMC, g4r = d->mt == SCORE_MODEL_GRU4REC, caser = d->mt == SCORE_MODEL_CASER,
-             delf = d->mt == SCORE_MODEL_DELF, deems = d->mt == SCORE_MODEL_DEEMS;
-  d->family = gcmc ? FAM_GCMC : g4r ? FAM_G4R : caser ? FAM_CASER : delf ? FAM_DELF : deems ? FAM_DEEMS : FAM_SLICE;
-  d->n_gru = (caser || delf) ? 0 : 2;
-  d->fc_head = !gcmc && !delf && !deems;
+             delf = d->mt == SCORE_MODEL_DELF, deems = d->mt == SCORE_MODEL_DEEMS, svdpp = d->mt == SCORE_MODEL_SVDPP;
+  d->family = gcmc ? FAM_GCMC : g4r ? FAM_G4R : caser ? FAM_CASER : delf ? FAM_DELF : deems ? FAM_DEEMS : svdpp ? FAM_SVDPP : FAM_SLICE;
+  d->n_gru = (caser || delf || svdpp) ? 0 : 2;
+  d->fc_head = !gcmc && !delf && !deems && !svdpp;
   d->reads_targets = !gcmc;
-  if ((g4r || caser || delf || deems) && d->K != 1) return SCORE_E_SHAPE;      // (user_seq rides as a [B, T, 1, Fi] set)
+  if ((g4r || caser || delf || deems || svdpp) && d->K != 1) return SCORE_E_SHAPE;      // (user_seq rides as a [B, T, 1, Fi] set)
+  if (svdpp) {
+    if (d->D > SCORE_SVDPP_DMAX || d->Fu + d->Fi > MAX_ENTRIES) return SCORE_E_SHAPE;      // (the widths svdpp.hip covers; a variable per field)
+    d->H = 0;                                                 // hidden_size: accepted and ignored, as for Caser and DELF
+  }
   if (deems && (d->H & 3)) return SCORE_E_SHAPE;                // (the towers' column ranges of head_inp start at 16-byte groups)
   if (delf) {
     if (d->Di > SCORE_DELF_CMAX || d->Du > SCORE_DELF_CMAX) return SCORE_E_SHAPE;      // (the widths delf.hip covers)
@@ -124,6 +129,7 @@ struct Params {  // float offsets into the flat buffer
   int64_t gm_a[2], gm_c[2], gm_4, gm_5;  // GCMC: per side dense (Wa) and dense_2 / dense_3 (Wc); the head's dense_4, dense_5
   int64_t cs_wh, cs_bh, cs_wv, cs_bv, cs_wd, cs_bd;  // Caser: conv2d (horizontal), conv2d_1 (vertical), dense (the scalar one)
   int64_t dl_w[11], dl_b[11];           // DELF: dense .. dense_10, kernels and biases (DEEMS: the same variables, dormant)
+  int64_t sv_w;                         // SVD++: user_feat_w_0's 4-float cell; user_feat_w_i at + 4 i, item_feat_w_j at + 4 (Fu + j)
   int64_t bn_g2, bn_b2, fc_w2[3], fc_b2[3];     // DEEMS: the item tower (batch_normalization_1, dense_14 .. dense_16); the user tower
                                         // (batch_normalization, dense_11 .. dense_13) is bn_g / bn_b / fc_w / fc_b
   int64_t n_floats, n_reg;
@@ -164,6 +170,13 @@ int build_layout_raw(const Dims& d, score_param_entry_t* out, int max_entries, P
     add("conv2d/kernel", CASER_L, d.Di, 1, 3); add("conv2d/bias", 1, 0, 0, 0);
     add("conv2d_1/kernel", d.T, 1, 1, 3); add("conv2d_1/bias", 1, 0, 0, 0);
     dense(1, 1);
+  }
+  // SVD++ (point_model.py:171-187): one scalar per feature field, shape [], truncated normal (init 4), all regularised -- each
+  // in a 4-float cell of the regularised region (the 16-byte alignment below), consecutive: the pad floats stay zero
+  if (d.family == FAM_SVDPP) {
+    char b[64];
+    for (int i = 0; i < d.Fu; ++i) { snprintf(b, 64, "user_feat_w_%d", i); add(b, 1, 0, 1, 4); }
+    for (int j = 0; j < d.Fi; ++j) { snprintf(b, 64, "item_feat_w_%d", j); add(b, 1, 0, 1, 4); }
   }
   // DELF (point_model.py:216-232, 235-249): the two attention denses, four fusion MLPs (10, 4), the output unit
   if (delf) {
@@ -225,6 +238,7 @@ int build_layout_raw(const Dims& d, score_param_entry_t* out, int max_entries, P
   if (d.coattn) { for (int c = 0; c < 2; ++c) { P->ca_w[c] = off[i++]; P->ca_b[c] = off[i++]; } }
   if (gcmc) { P->gm_a[0] = off[i++]; P->gm_a[1] = off[i++]; P->gm_c[0] = off[i++]; P->gm_c[1] = off[i++]; }
   if (caser) { P->cs_wh = off[i++]; P->cs_bh = off[i++]; P->cs_wv = off[i++]; P->cs_bv = off[i++]; P->cs_wd = off[i++]; P->cs_bd = off[i++]; }
+  if (d.family == FAM_SVDPP) { P->sv_w = off[i]; i += d.Fu + d.Fi; }
   if (delf) { for (int k = 0; k < 11; ++k) { P->dl_w[k] = off[i++]; P->dl_b[k] = off[i++]; } }
   for (int s = 0; s < d.n_gru; ++s) { P->gk[s] = off[i++]; P->gb[s] = off[i++]; P->ck[s] = off[i++]; P->cb[s] = off[i++]; }
   if (d.attn) { for (int a = 0; a < 4; ++a) { P->at_w[a] = off[i++]; P->at_b[a] = off[i++]; } }
@@ -299,6 +313,9 @@ struct WS {
   // DEEMS only (-1 otherwise): the item tower's f1 / f2 / dz1 / dz2 (the user tower's are the head's own regions; bn, dbn, dhead and
   // dgstage hold both towers' column ranges), and per tower [2][B] the logits, y_u | y_i, dL/d logit
   int64_t deems_f1, deems_f2, deems_dz1, deems_dz2, deems_logit, deems_y, deems_dlogit;
+  // SVD++ only (-1 otherwise): what the forward kernel saves [B, 4 D + 4] (kernels.h: SvdppArgs.act) and the per-sample partials of
+  // the weight gradients [B, Fu + Fi]
+  int64_t svdpp_act, svdpp_dw;
   int64_t scratch_floats, total;
 };
 
@@ -362,6 +379,11 @@ void ws_family_regions(const Dims& d, int B, Taker& take, WS* w) {
     w->deems_logit = take(2 * (int64_t)B); w->deems_y = take(2 * (int64_t)B); w->deems_dlogit = take(2 * (int64_t)B);
   } else {
     w->deems_f1 = w->deems_f2 = w->deems_dz1 = w->deems_dz2 = w->deems_logit = w->deems_y = w->deems_dlogit = -1;
+  }
+  if (d.family == FAM_SVDPP) {
+    w->svdpp_act = take((int64_t)B * score_svdpp_act_floats(d.D)); w->svdpp_dw = take((int64_t)B * (d.Fu + d.Fi));
+  } else {
+    w->svdpp_act = w->svdpp_dw = -1;
   }
 }
 
@@ -800,6 +822,20 @@ static void delf_args(const Pass& c, DelfArgs* a) {
   a->act = ws + w.delf_act; a->dact = ws + w.delf_dact; a->logit = ws + w.logit; a->y = ws + w.y_pred; a->lossb = ws + w.lossb;
   a->dlogit = ws + w.dlogit; a->dhead = ws + w.dhead;
 }
+// ---------------------------------------------------------------- SVD++ (point_model.py:167-198, svdpp.hip)
+// X = the gathered user_seq rows (columns [0, Di) of xside[0]) under score_batch_t.length; the backward kernel writes every column
+// of dxside[0], the target rows' gradients into dhead ([d target_item | d target_user]) and the weight gradients' per-sample partials
+static void svdpp_args(const Pass& c, SvdppArgs* a) {
+  const Dims& d = c.d; const WS& w = c.w; float* ws = c.ws;
+  memset(a, 0, sizeof(*a));
+  a->B = c.B; a->T = c.T; a->D = d.D; a->Fu = d.Fu; a->Fi = d.Fi; a->ldx = d.I; a->ldq = d.Dq; a->ldh = d.Dhead;
+  a->off_ti = d.off_ti; a->off_tu = d.off_tu; a->Bglobal = c.Bg;
+  a->X = ws + w.xside[0]; a->tu = ws + w.query; a->ti = ws + w.query + d.Du;       // [target_user | target_item] (score_launch_target_fwd)
+  a->wu = c.W + c.P.sv_w; a->wi = c.W + c.P.sv_w + 4 * (int64_t)d.Fu;
+  a->length = c.bt->length; a->label = c.bt->label;
+  a->act = ws + w.svdpp_act; a->logit = ws + w.logit; a->y = ws + w.y_pred; a->lossb = ws + w.lossb; a->dlogit = ws + w.dlogit;
+  a->dX = ws + w.dxside[0]; a->dhead = ws + w.dhead; a->dwpart = ws + w.svdpp_dw;
+}
 // ---------------------------------------------------------------- DEEMS (point_model.py:281-311, deems.hip)
 // The two recurrences: side 0 = gru1 over the user_seq rows under score_batch_t.length, side 1 = gru2 over the item_seq rows under
 // length2.  On the register kernels of gru.hip both run as ONE grouped launch each way, each side reading its own lengths
@@ -1095,6 +1131,14 @@ static int queue_delf(const Pass& c, GradQueues* q, float* gw) {
   return 0;
 }
 
+// SVD++'s Fu + Fi scalars: each the batch sum of its column of the per-sample partials, into its own 4-float cell
+static int queue_svdpp(const Pass& c, GradQueues* q, float* gw) {
+  const int nv = c.d.Fu + c.d.Fi;
+  for (int k = 0; k < nv; ++k)
+    G(colsum_queue_add(&q->cq, c.ws + c.w.svdpp_dw + k, c.B, 1, nv, gw + c.P.sv_w + 4 * (int64_t)k, 0));
+  return 0;
+}
+
 }  // namespace
 
 extern "C" int score_context_create(void** ctx) {
@@ -1190,7 +1234,7 @@ extern "C" int score_workspace_field(const score_config_t* cfg, int32_t B, const
       {"deems_f1", w.deems_f1 < 0 ? -1 : w.f1, w.deems_f1}, {"deems_f2", w.deems_f2 < 0 ? -1 : w.f2, w.deems_f2},
       {"deems_dz1", w.deems_dz1 < 0 ? -1 : w.dz1, w.deems_dz1}, {"deems_dz2", w.deems_dz2 < 0 ? -1 : w.dz2, w.deems_dz2},
       {"deems_logit", w.deems_logit, w.deems_logit + B}, {"deems_y", w.deems_y, w.deems_y + B},
-      {"deems_dlogit", w.deems_dlogit, w.deems_dlogit + B}};
+      {"deems_dlogit", w.deems_dlogit, w.deems_dlogit + B}, {"svdpp_act", w.svdpp_act, -1}, {"svdpp_dw", w.svdpp_dw, -1}};
   for (auto& e : tab)
     if (strcmp(e.n, name) == 0) {
       if (e.a < 0) return SCORE_E_BADARG;       // (a region of another model type)
@@ -1749,6 +1793,22 @@ int fwd_delf(const Pass& c, const FwdState& f) {
   return 0;
 }
 
+int fwd_svdpp(const Pass& c, const FwdState& f) {
+  hipStream_t s = c.s;
+  void* const* stage_events = f.stage_events;
+  // SVD++: the factor sums, the norm, y and the loss terms in ONE launch behind the gather (the target rows come from the side
+  // stream); no dropout, keep_prob has no effect
+  HIPTRY(hipStreamWaitEvent(s, f.sd->join, 0));
+  SvdppArgs a;
+  svdpp_args(c, &a);
+  G(score_svdpp_fwd(a, s));
+  EV(2);
+  EV(3);
+  G(loss_tail(c, f.sd, f.reg_lambda));
+  EV(4);
+  return 0;
+}
+
 int fwd_deems(const Pass& c, const FwdState& f) {
   const WS& w = c.w; const int B = c.B; hipStream_t s = c.s;
   void* const* stage_events = f.stage_events;
@@ -1811,6 +1871,7 @@ extern "C" int score_forward(const score_config_t* cfg, const score_state_t* st,
     case FAM_CASER: return fwd_caser(c, f);
     case FAM_DELF: return fwd_delf(c, f);
     case FAM_DEEMS: return fwd_deems(c, f);
+    case FAM_SVDPP: return fwd_svdpp(c, f);
   }
   return SCORE_E_BADARG;
 }
@@ -2243,6 +2304,25 @@ int bwd_delf(const Pass& c, BwdState* b) {
   return bwd_close(c, b);
 }
 
+int bwd_svdpp(const Pass& c, BwdState* b) {
+  hipStream_t s = c.s;
+  void* const* stage_events = b->stage_events;
+  G(bwd_open(c, b));
+  // ---- SVD++: the whole backward between the scatter and the loss in ONE launch (svdpp.hip): dxside[0], dhead's target columns
+  // and the weight gradients' per-sample partials, whose batch sums run on the side stream (bwd_side_products); dxside[1] carries
+  // nothing
+  SvdppArgs a;
+  svdpp_args(c, &a);
+  G(score_svdpp_bwd(a, s));
+  G(queue_svdpp(c, &b->q, b->gw));
+  HIPTRY(hipMemsetAsync(c.ws + c.w.dxside[1], 0, (int64_t)c.BT * c.d.I * sizeof(float), s));
+  EV(1);
+  G(bwd_zero_dinfo(c));       // (no state: dhead is what svdpp.hip wrote)
+  EV(2);
+  G(bwd_side_products(c, b));
+  return bwd_close(c, b);
+}
+
 int bwd_deems(const Pass& c, BwdState* b) {
   const Dims& d = c.d; const WS& w = c.w; float* ws = c.ws; const int B = c.B, H = c.H, BT = c.BT; hipStream_t s = c.s;
   void* const* stage_events = b->stage_events;
@@ -2311,6 +2391,7 @@ extern "C" int score_backward(const score_config_t* cfg, const score_state_t* st
     case FAM_CASER: return bwd_caser(c, &b);
     case FAM_DELF: return bwd_delf(c, &b);
     case FAM_DEEMS: return bwd_deems(c, &b);
+    case FAM_SVDPP: return bwd_svdpp(c, &b);
   }
   return SCORE_E_BADARG;
 }

@@ -365,3 +365,21 @@ int score_deems_bn_fwd(const DeemsArgs& a, hipStream_t s);        // the layer-b
 int score_deems_out(const DeemsArgs& a, hipStream_t s);           // ... and, from the two logits, y / lossb / dlogit
 int score_deems_head_bwd(const DeemsArgs& a, hipStream_t s);      // both towers' head backward in one launch (from dz2)
 int score_deems_bn_bwd(const DeemsArgs& a, hipStream_t s);        // the layer-by-layer form's bn backward, both towers
+// svdpp.hip: the SVD++ point baseline (point_models/point_model.py:167-198) between the gather and the scatter.  X [B * T, ldx]:
+// the gathered user_seq rows, Fi * D columns read; tu / ti: the gathered target rows (row stride ldq); wu / wi: the scalar
+// weights, one per 4-float cell (wu[4 i], wi[4 j]).  act [B, 4 D + 4] = [p_u | p_i | nb | share | n, ties, 0, 0] is what the
+// forward kernel saves (share_d = [c_d == n] / ties); s_t is recomputed from X in the backward kernel, which writes dX (every one
+// of the ldx columns; an exact 0 past the length), d target_item / d target_user into dhead (row stride ldh) and the per-sample
+// weight-gradient partials dwpart [B, Fu + Fi] (user weights first).  One launch each way, a workgroup per sample.
+#define SCORE_SVDPP_DMAX 128      /* widest eb_dim the kernels cover */
+#define SCORE_SVDPP_FMAX 8        /* most feature fields per side (the index plan's limit too) */
+struct SvdppArgs {
+  const float* X; const float* tu; const float* ti; const float* wu; const float* wi;
+  const int32_t* length; const int32_t* label;
+  float* act; float* logit; float* y; float* lossb; float* dlogit;
+  float* dX; float* dhead; float* dwpart;
+  int B, T, D, Fu, Fi, ldx, ldq, ldh, off_ti, off_tu, Bglobal;
+};
+__host__ __device__ static inline int64_t score_svdpp_act_floats(int D) { return 4 * (int64_t)D + 4; }
+int score_svdpp_fwd(const SvdppArgs& a, hipStream_t s);
+int score_svdpp_bwd(const SvdppArgs& a, hipStream_t s);

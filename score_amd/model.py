@@ -615,6 +615,12 @@ class SCOREBASE(object):
             elif e[5] == 3:       # glorot-uniform with TF's convolution fans: fan_in = fan_out = the receptive field, rows * cols
                 lim = math.sqrt(6.0 / (2 * e[2] * max(e[3], 1)))
                 v.uniform_(-lim, lim, generator=gen)
+            elif e[5] == 4:       # tf.truncated_normal_initializer: N(0, 1), values beyond +-2 redrawn
+                v.normal_(0.0, 1.0, generator=gen)
+                bad = v.abs() > 2.0
+                while bool(bad.any()):
+                    v[bad] = torch.empty((int(bad.sum()),), dtype=v.dtype, device=v.device).normal_(0.0, 1.0, generator=gen)
+                    bad = v.abs() > 2.0
             elif e[5] == 1:
                 v.fill_(1.0)
             else:
@@ -1950,5 +1956,24 @@ class DEEMS(DELF):
     dropout_towers = 2
 
 
+class SVDpp(GRU4Rec):
+    """point_models/point_model.py:167-198 on PointBaseModel (:9-63), the matrix-factorisation baseline: one scalar weight per
+    feature field (user_feat_w_i, item_feat_w_j, truncated normal, all L2-regularised), p_u / p_i the weighted sums of the target
+    rows' fields, the history summed the same way under user_seq_length into nb and scaled by the square root of
+    tf.norm(., 1, (1, 2)) -- the MATRIX 1-norm of the masked [T, D] history, max over the columns of the absolute column sums --,
+    y_pred = sigmoid(<p_i, p_u + nb / sqrt(n)>), log-loss, Adam.  GRU4Rec's constructor, 5-tuple, loader and train / eval / save
+    / restore.  hidden_size is accepted and ignored; there is no dropout, so keep_prob has no effect.  A length >= max_time_len
+    means all positions.  A sample with length <= 0, or whose live history rows are all id 0, has n = 0: its y_pred and the
+    batch loss are NaN, as in TF (the reference's loader yields no such sample).
+
+    The library holds every scalar in a 4-float cell (its three pad floats are zero and stay zero); at this boundary every
+    variable, gradient and Adam slot has TF's name and TF's shape () (_export)."""
+    model_type = "SVDpp"
+    zero_length_reads_all = False
+
+    def _export(self, name, a):
+        return np.asarray(a, dtype=np.float32).reshape(())      # (_import: the base class's reshape to the library's (1,))
+
+
 MODELS = {"SCORE": SCORE, "RIA": RIA, "RCA": RCA, "SCORE_USER": SCORE_USER, "SCORE_ITEM": SCORE_ITEM, "RRN": RRN, "GCMC": GCMC,
-          "GRU4Rec": GRU4Rec, "Caser": Caser, "DELF": DELF, "DEEMS": DEEMS}
+          "GRU4Rec": GRU4Rec, "Caser": Caser, "DELF": DELF, "DEEMS": DEEMS, "SVDpp": SVDpp, "SVD++": SVDpp}      # ("SVD++": the driver's name, train_time_point_models.py:157-170)

@@ -1,5 +1,5 @@
-"""ms per training step (and per evaluation call) of a point baseline (point_models/point_model.py:123-164, 200-249, 281-311:
-GRU4Rec, Caser, DELF, DEEMS) through
+"""ms per training step (and per evaluation call) of a point baseline (point_models/point_model.py:123-311:
+GRU4Rec, Caser, SVD++, DELF, DEEMS) through
 the reference's train() / eval signatures, at the reference's point-model shapes (train_time_point_models.py:15-35, 353-354):
 Tmall, N = 1,529,672, D = 16, H = 32, T = 50, Fu = 3, Fi = 4,
   train100: B = 100      train200: B = 200      eval1000: forward only (eval_async), B = 1000
@@ -10,6 +10,8 @@ each in both forms of the two stacked recurrences: "stacked" (csrc/gru_stack.hip
 --model DEEMS alternates DEEMS's own two forms on DELF's batches: "deems" (csrc/deems.hip: both towers in one launch each way, both
 recurrences in one grouped launch each way) and "deems_composed" (debug_flags bits 6 | 13: the towers layer by layer, one
 recurrence per launch).
+--model SVDpp times the SVD++ baseline (form "svdpp": csrc/svdpp.hip, one launch each way) against GRU4Rec's stacked form at
+train200 and eval1000.
 Every (case, form) runs in a fresh process: `warmup` untimed steps, then `steps` timed ones over a few pre-staged device
 batches (random ids; history lengths as the loader reports them, up to 300, so most samples run all T steps), wall clock
 between two device synchronisations.  With --pairs n the two forms alternate n times.
@@ -20,6 +22,7 @@ between two device synchronisations.  With --pairs n the two forms alternate n t
     python tools/point_step_time.py --model Caser --pairs 3  # three cases, (GRU4Rec stacked, Caser) alternating three times
     python tools/point_step_time.py --model DELF --pairs 3   # ... (GRU4Rec stacked, DELF)
     python tools/point_step_time.py --model DEEMS --pairs 3  # ... (DEEMS fused, DEEMS composed)
+    python tools/point_step_time.py --model SVDpp --pairs 3  # train200 and eval1000, (GRU4Rec stacked, SVD++) alternating three times
     python tools/point_step_time.py --case train200 --form stacked --profile-steps 30     # no timing: a short run for a profiler
 """
 import argparse
@@ -32,10 +35,13 @@ import time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 TMALL = dict(N=1529672, D=16, H=32, T=50, Fu=3, Fi=4)
 CASES = {"train100": dict(B=100, train=True), "train200": dict(B=200, train=True), "eval1000": dict(B=1000, train=False)}
-FORMS = {"stacked": 0, "composed": 8192, "caser": 0, "delf": 0, "deems": 0, "deems_composed": 64 | 8192}      # debug_flags of a form
-FORM_MODEL = {"stacked": "GRU4Rec", "composed": "GRU4Rec", "caser": "Caser", "delf": "DELF", "deems": "DEEMS", "deems_composed": "DEEMS"}
+FORMS = {"stacked": 0, "composed": 8192, "caser": 0, "delf": 0, "deems": 0, "deems_composed": 64 | 8192,
+         "svdpp": 0}      # debug_flags of a form
+FORM_MODEL = {"stacked": "GRU4Rec", "composed": "GRU4Rec", "caser": "Caser", "delf": "DELF", "deems": "DEEMS", "deems_composed": "DEEMS",
+              "svdpp": "SVDpp"}
 PAIRS = {"GRU4Rec": ("stacked", "composed"), "Caser": ("stacked", "caser"), "DELF": ("stacked", "delf"),
-         "DEEMS": ("deems", "deems_composed")}     # what --model alternates
+         "DEEMS": ("deems", "deems_composed"), "SVDpp": ("stacked", "svdpp")}     # what --model alternates
+MODEL_CASES = {"SVDpp": ("train200", "eval1000")}      # the cases --model runs without --case (default: all three)
 
 
 def run_one(case, form, steps, warmup, n_batches=4, H=None):
@@ -82,7 +88,7 @@ def main():
     ap.add_argument("--form", choices=tuple(FORMS))
     ap.add_argument("--steps", type=int, default=200)
     ap.add_argument("--warmup", type=int, default=20)
-    ap.add_argument("--model", choices=tuple(PAIRS), default="GRU4Rec", help="the model whose two forms (Caser / DELF: GRU4Rec stacked and the model) alternate")
+    ap.add_argument("--model", choices=tuple(PAIRS), default="GRU4Rec", help="the model whose two forms (Caser / DELF / SVDpp: GRU4Rec stacked and the model) alternate")
     ap.add_argument("--pairs", type=int, default=1, help="alternating pairs per case")
     ap.add_argument("--hidden", type=int, default=0, help="another hidden size than the reference's 32")
     ap.add_argument("--profile-steps", type=int, default=0, help="run this many steps after the warm-up and print nothing timed")
@@ -94,7 +100,7 @@ def main():
             r.pop("ms_per_step")
         print(json.dumps(r), flush=True)
         return
-    for case in (a.case,) if a.case else tuple(CASES):
+    for case in (a.case,) if a.case else MODEL_CASES.get(a.model, tuple(CASES)):
         first, second = PAIRS[a.model]
         res = {f: [] for f in FORMS}
         for _ in range(a.pairs):
