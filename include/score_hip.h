@@ -157,7 +157,37 @@ enum { SCORE_MODEL_SCORE = 0, SCORE_MODEL_RIA = 1, SCORE_MODEL_RCA = 2,
         * [p_u | p_i | nb | share | n, ties, 0, 0], share_d = [c_d == n] / ties with c_d = sum_t |s_t,d| and ties the number of
         * maximal columns.  Kernels: csrc/svdpp.hip, one launch each way; the batch sums of the weight gradients through the
         * queued column sums, every sum in a fixed order. */
-       SCORE_MODEL_SVDPP = 11 };
+       SCORE_MODEL_SVDPP = 11,
+       /* point_models/point_model.py:313-469 (SASRec) on PointBaseModel (:9-63): one block of two-head self-attention over the flat
+        * history.  C = Fi * D, X [B, T, C] the gathered user_seq.  Per row N = (X - mean) / sqrt(var + 1e-8) (population variance
+        * over C), Qin = gamma N + beta; Q = Qin Wq + bq, K = X Wk + bk, V = X Wv + bv (K and V from the RAW X); per head (width
+        * C / 2) S = Q_h K_h^T / sqrt(C / 2), a key u with sum_c X[u, c] == 0 gets the score -2^32 + 1, softmax over ALL T keys (no
+        * causal mask, lengths not used: every key masked gives uniform weights 1 / T), the weights times the query mask
+        * [sum_c Qin[t, c] != 0], tf.nn.dropout on them ([2 B, T, T], head h of sample b at row h B + b), Y = concat_h(A_h V_h) + Qin.
+        * rep_t = Y_t [t < length] (a length >= T: all positions), final = sum_t rep_t.  The shared head prediction_layer/fc1..fc3
+        * (200 relu, dropout, 80 relu, dropout, 1 sigmoid; NO batch norm; input width 2 C + Cu) is applied three times with
+        * independent dropout: to the positive rows [rep_t | Y_t | target_user], t = 1 .. T - 1, to the "negative" rows, the same
+        * expression for t = 2 .. T - 1, and to [final | target_item | target_user], which gives y_pred [B].  loss = mean over
+        * B (T - 1) of -log(p_pos + 1e-7) + mean over B (T - 2) of -log(1 - p_neg + 1e-7) + log_loss(label, y_pred) + reg_lambda *
+        * sum l2_loss over the eight variables whose names hold neither "bias" nor "emb" -- BOTH layer-norm variables among them
+        * (gamma's ones contribute reg_lambda * C / 2 from the start); padded positions count in both means.  The masks carry no
+        * gradient.  At keep_prob = 1 the negative predictions equal the positive ones for t >= 2 and are computed once.
+        * max_time_len >= 3, Fi * D <= 128 and 4 T (C + 1) + 2 T^2 + 4 T floats within 160 KiB (SCORE_E_SHAPE beyond);
+        * obj_per_time_slice must be 1; hidden_size is accepted and ignored.  All T positions are always computed: active_slices
+        * has no effect, length is read for rep / final only; length2 NULL.  The batch rides as for SCORE_MODEL_GRU4REC.
+        * THE QUERY MASK AT TF'S INITIAL VALUES: with gamma = 1 and beta = 0, sum_c Qin of a live row is the rounding residue of
+        * a sum that is exactly 0 in real arithmetic; TF's own mask there is an accident of its fp32 summation order.  The
+        * kernels compute the formula as written, in fp32, in rising c; this one case is not pinned to any restatement.
+        * score_param_layout: 14 entries in TF's creation order -- ln/Variable (beta, zeros), ln/Variable_1 (gamma, ones), both
+        * regularised; multihead_attention/dense, dense_1, dense_2 (kernel [C, C] + bias); prediction_layer/fc1, fc2, fc3.
+        * Dropout: score_forward's drop_mask0 [R, 200] / drop_mask1 [R, 80] with R = B (T - 1) + B (T - 2) + B rows ordered positive
+        * (b-major, t = 1 .. T - 1), negative (t = 2 .. T - 1), final; score_state_t.drop_mask2 [2, B, T, T] for the attention
+        * weights; without masks from the counter hash of drop_seed (or of score_step_scalars_t.drop_seed), one stream per use.
+        * Workspace fields (score_workspace_field): sasrec_y [B, T, C], sasrec_final [B, C], sasrec_p / sasrec_att [B, 2, T, T]
+        * (softmax / final weights), sasrec_qin [B, T, C], sasrec_hin (the head-input rows), sasrec_logit [R].
+        * Kernels: csrc/sasrec.hip -- the attention in one launch each way, a workgroup per sample; the head's products are the
+        * library's GEMMs; every sum in a fixed order, no atomics. */
+       SCORE_MODEL_SASREC = 12 };
 
 /* Constructor arguments of SCOREBASE.__init__ (score.py:12-13). */
 typedef struct {
@@ -165,7 +195,7 @@ typedef struct {
   int32_t eb_dim;              /* D: multiple of 4, <= 256                        */
   int32_t hidden_size;         /* H                                               */
   int32_t max_time_len;        /* T                                               */
-  int32_t obj_per_time_slice;  /* K <= 32 (SCORE_MODEL_GRU4REC / _CASER / _DELF / _DEEMS / _SVDPP: 1) */
+  int32_t obj_per_time_slice;  /* K <= 32 (SCORE_MODEL_GRU4REC / _CASER / _DELF / _DEEMS / _SVDPP / _SASREC: 1) */
   int32_t user_fnum;           /* Fu                                              */
   int32_t item_fnum;           /* Fi                                              */
   int32_t model_type;          /* SCORE_MODEL_*                                   */
@@ -555,8 +585,9 @@ typedef struct {
                            workspace of the same layout, where score_index_plan wrote it -- instead of in `workspace`: a caller
                            that alternates two buffers for the plans can sort the next batch's plan while this step's scatter
                            still reads its own (everything else of the step stays in `workspace`).  NULL: in `workspace`.       */
-  int32_t reserved4;
-  int32_t reserved3;
+  const uint8_t* drop_mask2; /* optional (score_forward, SCORE_MODEL_SASREC with keep_prob < 1): explicit dropout mask of the
+                           attention weights, device [2, B, T, T] of 0 / 1 (head h of sample b at row h B + b); NULL: from the seed.
+                           (The slot of two reserved 32-bit words: 8 bytes, 8-byte aligned -- size and every offset as before.) */
 } score_state_t;
 
 /* Synchronous query of a score_state_t.id_status word: copies it to *bits (optional), waits for `stream`, clears the

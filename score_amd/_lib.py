@@ -11,7 +11,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "lib", "libscore_hip.so")
 
 MODEL_TYPES = {"SCORE": 0, "RIA": 1, "RCA": 2, "SCORE_USER": 3, "SCORE_ITEM": 4, "RRN": 5, "GCMC": 6, "GRU4Rec": 7, "Caser": 8, "DELF": 9,
-               "DEEMS": 10, "SVDpp": 11}
+               "DEEMS": 10, "SVDpp": 11, "SASRec": 12}
 
 MAX_PARAM_ENTRIES = 48   # dense variables of a model type at most (DEEMS: 46)
 
@@ -50,7 +50,7 @@ class State(C.Structure):
                 ("gather_done_event", C.c_void_p), ("plan_done_event", C.c_void_p), ("step_scalars", C.c_void_p),
                 ("context", C.c_void_p), ("id_status", C.c_void_p), ("grads_done_event", C.c_void_p),
                 ("loss_done_event", C.c_void_p), ("loss_host", C.c_void_p), ("plan_workspace", C.c_void_p),
-                ("reserved4", C.c_int32), ("reserved3", C.c_int32)]
+                ("drop_mask2", C.c_void_p)]      # (drop_mask2: SASRec's attention dropout mask; the slot of two reserved words)
 
 
 class Graph(C.Structure):

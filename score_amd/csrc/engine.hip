@@ -1,7 +1,7 @@
 // Whole-path orchestration: parameter/workspace layout and the forward / backward
 // launch sequences of SCORE and its ablations (score.py:188-369) and of the slice baselines RRN and GCMC
-// (slice_model.py:155-203) and of the point baselines GRU4Rec, Caser, SVD++, DELF and DEEMS (point_model.py:123-311) on
-// one stream.  Host code only; every kernel lives in embed/gemm/gru/gru_stack/head/gcmc/caser/delf/deems/svdpp.hip.
+// (slice_model.py:155-203) and of the point baselines GRU4Rec, Caser, SVD++, DELF, DEEMS and SASRec (point_model.py:123-469) on
+// one stream.  Host code only; every kernel lives in embed/gemm/gru/gru_stack/head/gcmc/caser/delf/deems/svdpp/sasrec.hip.
 #include <string.h>
 #include <stdlib.h>
 #include <stdio.h>
@@ -20,7 +20,7 @@ const int MAX_ENTRIES = 48;       // dense variables of a model type at most (DE
 
 // What decides a pass's launch sequence.  FAM_SLICE: SCORE, RIA, RCA, SCORE_USER, SCORE_ITEM and RRN, which differ by attn, coattn
 // and Is[] only; every other model type is a family of its own
-enum Family { FAM_SLICE, FAM_GCMC, FAM_G4R, FAM_CASER, FAM_DELF, FAM_DEEMS, FAM_SVDPP };
+enum Family { FAM_SLICE, FAM_GCMC, FAM_G4R, FAM_CASER, FAM_DELF, FAM_DEEMS, FAM_SVDPP, FAM_SASREC };
 
 struct Dims {
   int64_t N;
@@ -36,9 +36,11 @@ struct Dims {
   //   item_seq rows (Du columns of xside[1], lengths length2); two fc heads of its own on the column ranges [h_u | target_user]
   //   and [h_i | target_item] of ONE head_inp row; DELF's 22 variables laid out and regularised, never read by a launch
   // FAM_SVDPP: no recurrence, no head (H = 0 here); X = Di columns of xside[0]; Fu + Fi scalar variables (svdpp.hip)
+  // FAM_SASREC: no recurrence, no bn1 (H = 0 here); X = Di columns of xside[0]; a head of its own applied to 2 T - 2 rows per sample,
+  //   in workspace regions of its own (sasrec.hip); Dhead = Di + Du holds the target rows only
   Family family;
-  int n_gru;             // recurrences with variables, workspace and launches: 2, or 0 (Caser, DELF, SVD++)
-  bool fc_head;          // bn1 and fc1-3 behind head_inp (not GCMC, DELF, SVD++; DEEMS has two heads of its own, deems_tower)
+  int n_gru;             // recurrences with variables, workspace and launches: 2, or 0 (Caser, DELF, SVD++, SASRec)
+  bool fc_head;          // bn1 and fc1-3 behind head_inp (not GCMC, DELF, SVD++; DEEMS has two heads of its own, deems_tower; SASRec: prediction_layer, no bn1)
   bool sums_1hop;        // the gather leaves plain 1-hop sums: no co-attention, no attention, Is[] = {Di, Du} (RRN and every later type)
   bool reads_targets;    // the model reads the target rows (not GCMC: their gradient is zero)
   int Ic;          // row capacity of a side's block of the concatenated [Wx_gates | Wx_cand] copy: I (GRU4Rec: max(I, H))
@@ -50,16 +52,23 @@ int make_dims(const score_config_t* c, Dims* d) {
   d->N = c->feature_size; d->D = c->eb_dim; d->H = c->hidden_size; d->T = c->max_time_len;
   d->K = c->obj_per_time_slice; d->Fu = c->user_fnum; d->Fi = c->item_fnum; d->mt = c->model_type;
   if (d->N <= 0 || d->D <= 0 || (d->D & 3) || d->D > 256 || d->H <= 0 || d->T <= 0 || d->K <= 0 || d->K > 32 ||
-      d->Fu <= 0 || d->Fi <= 0 || d->mt < 0 || d->mt > SCORE_MODEL_SVDPP)
+      d->Fu <= 0 || d->Fi <= 0 || d->mt < 0 || d->mt > SCORE_MODEL_SASREC)
     return SCORE_E_SHAPE;
   d->Du = d->Fu * d->D; d->Di = d->Fi * d->D; d->I = d->Di + d->Du; d->Dq = d->Du + d->Di;
   const bool gcmc = d->mt == SCORE_MODEL_GCMC, g4r = d->mt == SCORE_MODEL_GRU4REC, caser = d->mt == SCORE_MODEL_CASER,
-             delf = d->mt == SCORE_MODEL_DELF, deems = d->mt == SCORE_MODEL_DEEMS, svdpp = d->mt == SCORE_MODEL_SVDPP;
-  d->family = gcmc ? FAM_GCMC : g4r ? FAM_G4R : caser ? FAM_CASER : delf ? FAM_DELF : deems ? FAM_DEEMS : svdpp ? FAM_SVDPP : FAM_SLICE;
-  d->n_gru = (caser || delf || svdpp) ? 0 : 2;
-  d->fc_head = !gcmc && !delf && !deems && !svdpp;
+             delf = d->mt == SCORE_MODEL_DELF, deems = d->mt == SCORE_MODEL_DEEMS, svdpp = d->mt == SCORE_MODEL_SVDPP,
+             sasrec = d->mt == SCORE_MODEL_SASREC;
+  d->family = gcmc ? FAM_GCMC : g4r ? FAM_G4R : caser ? FAM_CASER : delf ? FAM_DELF : deems ? FAM_DEEMS : svdpp ? FAM_SVDPP :
+              sasrec ? FAM_SASREC : FAM_SLICE;
+  d->n_gru = (caser || delf || svdpp || sasrec) ? 0 : 2;
+  d->fc_head = !gcmc && !delf && !deems && !svdpp && !sasrec;
   d->reads_targets = !gcmc;
-  if ((g4r || caser || delf || deems || svdpp) && d->K != 1) return SCORE_E_SHAPE;      // (user_seq rides as a [B, T, 1, Fi] set)
+  if ((g4r || caser || delf || deems || svdpp || sasrec) && d->K != 1) return SCORE_E_SHAPE;      // (user_seq rides as a [B, T, 1, Fi] set)
+  if (sasrec) {
+    // (max_time_len >= 3: the negative rows t = 2 .. T - 1; Fi * D <= 128 and a sample's buffers inside one workgroup's LDS)
+    if (!score_sasrec_fits(d->T, d->Di)) return SCORE_E_SHAPE;
+    d->H = 0;                                                 // hidden_size: accepted and ignored, as for Caser and DELF
+  }
   if (svdpp) {
     if (d->D > SCORE_SVDPP_DMAX || d->Fu + d->Fi > MAX_ENTRIES) return SCORE_E_SHAPE;      // (the widths svdpp.hip covers; a variable per field)
     d->H = 0;                                                 // hidden_size: accepted and ignored, as for Caser and DELF
@@ -112,9 +121,9 @@ static inline int x_ld(const Dims& d, int sd) {
 
 // time slices actually computed for a batch (score_batch_t.active_slices): every [B*T, .] activation of the
 // pass is laid out [B * TA, .]; the workspace regions keep their full-T sizes and offsets
-// (Caser reads no length: all T positions, whatever the batch says)
+// (Caser reads no length, SASRec attends over all T positions: all of them, whatever the batch says)
 static inline int active_T(const Dims& d, const score_batch_t* bt) {
-  const int a = d.family == FAM_CASER ? 0 : bt->active_slices;
+  const int a = (d.family == FAM_CASER || d.family == FAM_SASREC) ? 0 : bt->active_slices;
   return (a > 0 && a < d.T) ? a : d.T;
 }
 
@@ -130,6 +139,8 @@ struct Params {  // float offsets into the flat buffer
   int64_t cs_wh, cs_bh, cs_wv, cs_bv, cs_wd, cs_bd;  // Caser: conv2d (horizontal), conv2d_1 (vertical), dense (the scalar one)
   int64_t dl_w[11], dl_b[11];           // DELF: dense .. dense_10, kernels and biases (DEEMS: the same variables, dormant)
   int64_t sv_w;                         // SVD++: user_feat_w_0's 4-float cell; user_feat_w_i at + 4 i, item_feat_w_j at + 4 (Fu + j)
+  int64_t sa_beta, sa_gamma, sa_w[3], sa_b[3];      // SASRec: ln/Variable, ln/Variable_1, multihead_attention/dense .. dense_2 (Q, K, V);
+                                        // prediction_layer/fc1 .. fc3 are fc_w / fc_b
   int64_t bn_g2, bn_b2, fc_w2[3], fc_b2[3];     // DEEMS: the item tower (batch_normalization_1, dense_14 .. dense_16); the user tower
                                         // (batch_normalization, dense_11 .. dense_13) is bn_g / bn_b / fc_w / fc_b
   int64_t n_floats, n_reg;
@@ -177,6 +188,21 @@ int build_layout_raw(const Dims& d, score_param_entry_t* out, int max_entries, P
     char b[64];
     for (int i = 0; i < d.Fu; ++i) { snprintf(b, 64, "user_feat_w_%d", i); add(b, 1, 0, 1, 4); }
     for (int j = 0; j < d.Fi; ++j) { snprintf(b, 64, "item_feat_w_%d", j); add(b, 1, 0, 1, 4); }
+  }
+  // SASRec (point_model.py:441-469, 362-439, 353-360): the layer norm's beta and gamma -- plain tf.Variable's whose names hold
+  // neither "bias" nor "emb": BOTH regularised --, the three projections, the shared head without a batch norm
+  if (d.family == FAM_SASREC) {
+    add("ln/Variable", d.Di, 0, 1, 0); add("ln/Variable_1", d.Di, 0, 1, 1);
+    const char* pr[3] = {"multihead_attention/dense", "multihead_attention/dense_1", "multihead_attention/dense_2"};
+    for (int k = 0; k < 3; ++k) {
+      char b[64];
+      snprintf(b, 64, "%s/kernel", pr[k]); add(b, d.Di, d.Di, 1, 2);
+      snprintf(b, 64, "%s/bias", pr[k]); add(b, d.Di, 0, 0, 0);
+    }
+    const int Dh = 2 * d.Di + d.Du;
+    add("prediction_layer/fc1/kernel", Dh, FC1, 1, 2); add("prediction_layer/fc1/bias", FC1, 0, 0, 0);
+    add("prediction_layer/fc2/kernel", FC1, FC2, 1, 2); add("prediction_layer/fc2/bias", FC2, 0, 0, 0);
+    add("prediction_layer/fc3/kernel", FC2, 1, 1, 2); add("prediction_layer/fc3/bias", 1, 0, 0, 0);
   }
   // DELF (point_model.py:216-232, 235-249): the two attention denses, four fusion MLPs (10, 4), the output unit
   if (delf) {
@@ -239,6 +265,11 @@ int build_layout_raw(const Dims& d, score_param_entry_t* out, int max_entries, P
   if (gcmc) { P->gm_a[0] = off[i++]; P->gm_a[1] = off[i++]; P->gm_c[0] = off[i++]; P->gm_c[1] = off[i++]; }
   if (caser) { P->cs_wh = off[i++]; P->cs_bh = off[i++]; P->cs_wv = off[i++]; P->cs_bv = off[i++]; P->cs_wd = off[i++]; P->cs_bd = off[i++]; }
   if (d.family == FAM_SVDPP) { P->sv_w = off[i]; i += d.Fu + d.Fi; }
+  if (d.family == FAM_SASREC) {
+    P->sa_beta = off[i++]; P->sa_gamma = off[i++];
+    for (int k = 0; k < 3; ++k) { P->sa_w[k] = off[i++]; P->sa_b[k] = off[i++]; }
+    for (int f = 0; f < 3; ++f) { P->fc_w[f] = off[i++]; P->fc_b[f] = off[i++]; }
+  }
   if (delf) { for (int k = 0; k < 11; ++k) { P->dl_w[k] = off[i++]; P->dl_b[k] = off[i++]; } }
   for (int s = 0; s < d.n_gru; ++s) { P->gk[s] = off[i++]; P->gb[s] = off[i++]; P->ck[s] = off[i++]; P->cb[s] = off[i++]; }
   if (d.attn) { for (int a = 0; a < 4; ++a) { P->at_w[a] = off[i++]; P->at_b[a] = off[i++]; } }
@@ -316,6 +347,12 @@ struct WS {
   // SVD++ only (-1 otherwise): what the forward kernel saves [B, 4 D + 4] (kernels.h: SvdppArgs.act) and the per-sample partials of
   // the weight gradients [B, Fu + Fi]
   int64_t svdpp_act, svdpp_dw;
+  // SASRec only (-1 otherwise; kernels.h: SasrecArgs).  Per (b, t) row: N, Qin, Q, K, V, Y and dQ, dK, dV [B*T, C], 1 / sqrt(var +
+  // eps) and the key mask [B*T]; per sample the softmax and the final attention weights [B, 2, T, T], final [B, C] and the
+  // gamma / beta partials [B, C]; the head: its input rows and their gradient [B (T-1) + B, 2 C + Cu], z1 / dz1 [.., 200], and over
+  // the R = B (T-1) + B (T-2) + B rows of the three applications f1 / dz1e [R, 200], z2 / f2 / dz2 [R, 80], logit / dlogit [R]
+  int64_t sas_nrm, sas_qin, sas_q, sas_k, sas_v, sas_y, sas_dq, sas_dk, sas_dv, sas_rstd, sas_km, sas_p, sas_att, sas_fin,
+      sas_dgamma, sas_dbeta, sas_hin, sas_dhin, sas_z1, sas_dz1, sas_f1, sas_dz1e, sas_z2, sas_f2, sas_dz2, sas_logit, sas_dlogit;
   int64_t scratch_floats, total;
 };
 
@@ -384,6 +421,20 @@ void ws_family_regions(const Dims& d, int B, Taker& take, WS* w) {
     w->svdpp_act = take((int64_t)B * score_svdpp_act_floats(d.D)); w->svdpp_dw = take((int64_t)B * (d.Fu + d.Fi));
   } else {
     w->svdpp_act = w->svdpp_dw = -1;
+  }
+  if (d.family == FAM_SASREC) {
+    const int64_t C = d.Di, rows1 = BT, R = BT + (int64_t)B * (d.T - 2), TT2 = 2 * (int64_t)B * d.T * d.T;      // (rows1 = B (T-1) + B)
+    w->sas_nrm = take(BT * C); w->sas_qin = take(BT * C); w->sas_q = take(BT * C); w->sas_k = take(BT * C); w->sas_v = take(BT * C);
+    w->sas_y = take(BT * C); w->sas_dq = take(BT * C); w->sas_dk = take(BT * C); w->sas_dv = take(BT * C);
+    w->sas_rstd = take(BT); w->sas_km = take(BT); w->sas_p = take(TT2); w->sas_att = take(TT2);
+    w->sas_fin = take((int64_t)B * C); w->sas_dgamma = take((int64_t)B * C); w->sas_dbeta = take((int64_t)B * C);
+    w->sas_hin = take(rows1 * (2 * C + d.Du)); w->sas_dhin = take(rows1 * (2 * C + d.Du));
+    w->sas_z1 = take(rows1 * FC1); w->sas_dz1 = take(rows1 * FC1); w->sas_f1 = take(R * FC1); w->sas_dz1e = take(R * FC1);
+    w->sas_z2 = take(R * FC2); w->sas_f2 = take(R * FC2); w->sas_dz2 = take(R * FC2); w->sas_logit = take(R); w->sas_dlogit = take(R);
+  } else {
+    w->sas_nrm = w->sas_qin = w->sas_q = w->sas_k = w->sas_v = w->sas_y = w->sas_dq = w->sas_dk = w->sas_dv = w->sas_rstd = w->sas_km =
+        w->sas_p = w->sas_att = w->sas_fin = w->sas_dgamma = w->sas_dbeta = w->sas_hin = w->sas_dhin = w->sas_z1 = w->sas_dz1 = w->sas_f1 =
+            w->sas_dz1e = w->sas_z2 = w->sas_f2 = w->sas_dz2 = w->sas_logit = w->sas_dlogit = -1;
   }
 }
 
@@ -836,6 +887,33 @@ static void svdpp_args(const Pass& c, SvdppArgs* a) {
   a->act = ws + w.svdpp_act; a->logit = ws + w.logit; a->y = ws + w.y_pred; a->lossb = ws + w.lossb; a->dlogit = ws + w.dlogit;
   a->dX = ws + w.dxside[0]; a->dhead = ws + w.dhead; a->dwpart = ws + w.svdpp_dw;
 }
+// ---------------------------------------------------------------- SASRec (point_model.py:313-469, sasrec.hip)
+// X = the gathered user_seq rows (columns [0, Di) of xside[0]), all T positions; score_batch_t.length masks rep / final only.  The
+// head's rows live in regions of their own (R per batch, not B); the backward kernel writes every column of dxside[0] and the target
+// rows' gradients into dhead ([d target_item | d target_user]).  share: keep_prob = 1, the negative rows ride on the positive ones
+static void sasrec_args(const Pass& c, float keep_prob, const uint8_t* mask0, const uint8_t* mask1, uint64_t seed, SasrecArgs* a) {
+  const Dims& d = c.d; const Params& P = c.P; const WS& w = c.w; float* ws = c.ws; const float* W = c.W;
+  memset(a, 0, sizeof(*a));
+  a->B = c.B; a->T = d.T; a->C = d.Di; a->Cu = d.Du; a->Dh = 2 * d.Di + d.Du; a->ldx = d.I; a->ldq = d.Dq; a->ldh = d.Dhead;
+  a->off_ti = d.off_ti; a->off_tu = d.off_tu; a->Bglobal = c.Bg; a->share = keep_prob >= 1.f ? 1 : 0;
+  a->X = ws + w.xside[0]; a->tu = ws + w.query; a->ti = ws + w.query + d.Du;       // [target_user | target_item] (score_launch_target_fwd)
+  a->beta = W + P.sa_beta; a->gamma = W + P.sa_gamma;
+  a->Wq = W + P.sa_w[0]; a->bq = W + P.sa_b[0]; a->Wk = W + P.sa_w[1]; a->bk = W + P.sa_b[1]; a->Wv = W + P.sa_w[2]; a->bv = W + P.sa_b[2];
+  a->W3 = W + P.fc_w[2]; a->b3 = W + P.fc_b[2];
+  a->length = c.bt->length; a->label = c.bt->label;
+  a->mask0 = mask0; a->mask1 = mask1; a->mask_a = c.st->drop_mask2;
+  a->keep = keep_prob; a->seed = seed; a->seed_dev = c.st->step_scalars ? &c.st->step_scalars->drop_seed : nullptr;
+  a->nrm = ws + w.sas_nrm; a->rstd = ws + w.sas_rstd; a->km = ws + w.sas_km; a->qin = ws + w.sas_qin; a->q = ws + w.sas_q;
+  a->k = ws + w.sas_k; a->v = ws + w.sas_v; a->yseq = ws + w.sas_y; a->p = ws + w.sas_p; a->att = ws + w.sas_att; a->fin = ws + w.sas_fin;
+  a->hin = ws + w.sas_hin; a->z1 = ws + w.sas_z1; a->f1 = ws + w.sas_f1; a->z2 = ws + w.sas_z2; a->f2 = ws + w.sas_f2;
+  a->rlogit = ws + w.sas_logit; a->dlogit = ws + w.sas_dlogit; a->dz2 = ws + w.sas_dz2; a->dz1e = ws + w.sas_dz1e; a->dz1 = ws + w.sas_dz1;
+  a->dhin = ws + w.sas_dhin; a->logit = ws + w.logit; a->ypred = ws + w.y_pred; a->lossb = ws + w.lossb;
+  a->dq = ws + w.sas_dq; a->dk = ws + w.sas_dk; a->dv = ws + w.sas_dv; a->dX = ws + w.dxside[0]; a->dhead = ws + w.dhead;
+  a->dgamma = ws + w.sas_dgamma; a->dbeta = ws + w.sas_dbeta;
+}
+// rows of fc1's GEMM (positive + final) and of everything behind it (+ the negative rows, unless shared)
+static inline int sasrec_rows1(const Pass& c) { return c.B * c.d.T; }
+static inline int sasrec_rows(const Pass& c, const SasrecArgs& a) { return c.B * c.d.T + (a.share ? 0 : c.B * (c.d.T - 2)); }
 // ---------------------------------------------------------------- DEEMS (point_model.py:281-311, deems.hip)
 // The two recurrences: side 0 = gru1 over the user_seq rows under score_batch_t.length, side 1 = gru2 over the item_seq rows under
 // length2.  On the register kernels of gru.hip both run as ONE grouped launch each way, each side reading its own lengths
@@ -1139,6 +1217,29 @@ static int queue_svdpp(const Pass& c, GradQueues* q, float* gw) {
   return 0;
 }
 
+// SASRec's 14 variables: the head's kernels over the rows of its three applications (fc1: over the rows of z1, its folded
+// gradient), the three projections over the B * T rows (Q from Qin, K and V from the raw X), gamma and beta from the per-sample
+// partials
+static int queue_sasrec(const Pass& c, GradQueues* q, float* gw, const SasrecArgs& a) {
+  const Dims& d = c.d; const Params& P = c.P; const int B = c.B, BT = B * d.T, C = d.Di;
+  const int R1 = sasrec_rows1(c), R = sasrec_rows(c, a);
+  G(gemm_queue_add(&q->gq, FC2, 1, R, a.f2, FC2, a.dlogit, 1, gw + P.fc_w[2], 1));
+  G(colsum_queue_add(&q->cq, a.dlogit, R, 1, 1, gw + P.fc_b[2], 0));
+  G(gemm_queue_add(&q->gq, FC1, FC2, R, a.f1, FC1, a.dz2, FC2, gw + P.fc_w[1], FC2));
+  G(colsum_queue_add(&q->cq, a.dz2, R, FC2, FC2, gw + P.fc_b[1], 0));
+  G(gemm_queue_add(&q->gq, a.Dh, FC1, R1, a.hin, a.Dh, a.dz1, FC1, gw + P.fc_w[0], FC1));
+  G(colsum_queue_add(&q->cq, a.dz1, R1, FC1, FC1, gw + P.fc_b[0], 0));
+  const float* in[3] = {a.qin, a.X, a.X}; const int ldi[3] = {C, d.I, d.I};
+  const float* dy[3] = {a.dq, a.dk, a.dv};
+  for (int k = 0; k < 3; ++k) {
+    G(gemm_queue_add(&q->gq, C, C, BT, in[k], ldi[k], dy[k], C, gw + P.sa_w[k], C));
+    G(colsum_queue_add(&q->cq, dy[k], BT, C, C, gw + P.sa_b[k], 0));
+  }
+  G(colsum_queue_add(&q->cq, a.dgamma, B, C, C, gw + P.sa_gamma, 0));
+  G(colsum_queue_add(&q->cq, a.dbeta, B, C, C, gw + P.sa_beta, 0));
+  return 0;
+}
+
 }  // namespace
 
 extern "C" int score_context_create(void** ctx) {
@@ -1234,7 +1335,9 @@ extern "C" int score_workspace_field(const score_config_t* cfg, int32_t B, const
       {"deems_f1", w.deems_f1 < 0 ? -1 : w.f1, w.deems_f1}, {"deems_f2", w.deems_f2 < 0 ? -1 : w.f2, w.deems_f2},
       {"deems_dz1", w.deems_dz1 < 0 ? -1 : w.dz1, w.deems_dz1}, {"deems_dz2", w.deems_dz2 < 0 ? -1 : w.dz2, w.deems_dz2},
       {"deems_logit", w.deems_logit, w.deems_logit + B}, {"deems_y", w.deems_y, w.deems_y + B},
-      {"deems_dlogit", w.deems_dlogit, w.deems_dlogit + B}, {"svdpp_act", w.svdpp_act, -1}, {"svdpp_dw", w.svdpp_dw, -1}};
+      {"deems_dlogit", w.deems_dlogit, w.deems_dlogit + B}, {"svdpp_act", w.svdpp_act, -1}, {"svdpp_dw", w.svdpp_dw, -1},
+      {"sasrec_y", w.sas_y, -1}, {"sasrec_final", w.sas_fin, -1}, {"sasrec_att", w.sas_att, -1}, {"sasrec_p", w.sas_p, -1},
+      {"sasrec_qin", w.sas_qin, -1}, {"sasrec_hin", w.sas_hin, -1}, {"sasrec_logit", w.sas_logit, -1}};
   for (auto& e : tab)
     if (strcmp(e.n, name) == 0) {
       if (e.a < 0) return SCORE_E_BADARG;       // (a region of another model type)
@@ -1809,6 +1912,31 @@ int fwd_svdpp(const Pass& c, const FwdState& f) {
   return 0;
 }
 
+int fwd_sasrec(const Pass& c, const FwdState& f) {
+  const WS& w = c.w; hipStream_t s = c.s;
+  void* const* stage_events = f.stage_events;
+  // SASRec: layer norm, attention, rep / final and the head-input rows in ONE launch behind the gather (the target rows come from
+  // the side stream)
+  HIPTRY(hipStreamWaitEvent(s, f.sd->join, 0));
+  SasrecArgs a;
+  sasrec_args(c, f.keep_prob, f.mask0, f.mask1, f.seed, &a);
+  G(score_sasrec_attn_fwd(a, s));
+  EV(2);
+  // the shared head: fc1's pre-activations ONCE over the positive and the final rows, fanned out into the three applications'
+  // dropout groups; fc2 over all rows; fc3, the sigmoid, the three loss means and the gradients at the logits in one launch
+  const int R1 = sasrec_rows1(c), R = sasrec_rows(c, a);
+  G(gemm_mode_call(c.x3, 0, R1, FC1, a.Dh, a.hin, a.Dh, c.W + c.P.fc_w[0], FC1, a.z1, FC1, c.W + c.P.fc_b[0], GF_BIAS, 1.f, nullptr, 0,
+                   c.scratch, w.scratch_floats, s));
+  G(score_sasrec_fan(a, s));
+  G(gemm_mode_call(c.x3, 0, R, FC2, FC1, a.f1, FC1, c.W + c.P.fc_w[1], FC2, a.z2, FC2, c.W + c.P.fc_b[1], GF_BIAS, 1.f, nullptr, 0,
+                   c.scratch, w.scratch_floats, s));
+  EV(3);
+  G(score_sasrec_out(a, s));
+  G(loss_tail(c, f.sd, f.reg_lambda));
+  EV(4);
+  return 0;
+}
+
 int fwd_deems(const Pass& c, const FwdState& f) {
   const WS& w = c.w; const int B = c.B; hipStream_t s = c.s;
   void* const* stage_events = f.stage_events;
@@ -1872,6 +2000,7 @@ extern "C" int score_forward(const score_config_t* cfg, const score_state_t* st,
     case FAM_DELF: return fwd_delf(c, f);
     case FAM_DEEMS: return fwd_deems(c, f);
     case FAM_SVDPP: return fwd_svdpp(c, f);
+    case FAM_SASREC: return fwd_sasrec(c, f);
   }
   return SCORE_E_BADARG;
 }
@@ -2323,6 +2452,33 @@ int bwd_svdpp(const Pass& c, BwdState* b) {
   return bwd_close(c, b);
 }
 
+int bwd_sasrec(const Pass& c, BwdState* b) {
+  const WS& w = c.w; hipStream_t s = c.s;
+  void* const* stage_events = b->stage_events;
+  G(bwd_open(c, b));
+  SasrecArgs a;
+  sasrec_args(c, b->keep_prob, nullptr, nullptr, 0, &a);
+  // ---- the shared head from dz2 (the forward pass's last launch left it): through fc2 with fc1's relu / dropout mask per
+  // application, folded back onto the rows of z1, through fc1 to the head-input rows
+  const int R1 = sasrec_rows1(c), R = sasrec_rows(c, a);
+  G(gemm_mode_call(c.x3, 1, R, FC1, FC2, a.dz2, FC2, c.W + c.P.fc_w[1], FC2, a.dz1e, FC1, nullptr, GF_RELUGRAD, b->keep_prob,
+                   reinterpret_cast<const uint8_t*>(a.f1), 0, c.scratch, w.scratch_floats, s));
+  G(score_sasrec_fold(a, s));
+  G(gemm_mode_call(c.x3, 1, R1, a.Dh, FC1, a.dz1, FC1, c.W + c.P.fc_w[0], FC1, a.dhin, a.Dh, nullptr, 0, 1.f, nullptr, 0, c.scratch,
+                   w.scratch_floats, s));
+  EV(1);
+  // ---- residual, A V, softmax, the scaled Q K^T, the three projections and the layer norm in ONE launch (sasrec.hip): dxside[0],
+  // dhead's target columns and the rows the queued products and column sums are taken from -- those run on the side stream
+  // (bwd_side_products); dxside[1] carries nothing
+  G(score_sasrec_attn_bwd(a, s));
+  G(queue_sasrec(c, &b->q, b->gw, a));
+  HIPTRY(hipMemsetAsync(c.ws + w.dxside[1], 0, (int64_t)c.BT * c.d.I * sizeof(float), s));
+  G(bwd_zero_dinfo(c));       // (no state: dhead is what sasrec.hip wrote)
+  EV(2);
+  G(bwd_side_products(c, b));
+  return bwd_close(c, b);
+}
+
 int bwd_deems(const Pass& c, BwdState* b) {
   const Dims& d = c.d; const WS& w = c.w; float* ws = c.ws; const int B = c.B, H = c.H, BT = c.BT; hipStream_t s = c.s;
   void* const* stage_events = b->stage_events;
@@ -2392,6 +2548,7 @@ extern "C" int score_backward(const score_config_t* cfg, const score_state_t* st
     case FAM_DELF: return bwd_delf(c, &b);
     case FAM_DEEMS: return bwd_deems(c, &b);
     case FAM_SVDPP: return bwd_svdpp(c, &b);
+    case FAM_SASREC: return bwd_sasrec(c, &b);
   }
   return SCORE_E_BADARG;
 }

@@ -383,3 +383,35 @@ struct SvdppArgs {
 __host__ __device__ static inline int64_t score_svdpp_act_floats(int D) { return 4 * (int64_t)D + 4; }
 int score_svdpp_fwd(const SvdppArgs& a, hipStream_t s);
 int score_svdpp_bwd(const SvdppArgs& a, hipStream_t s);
+// sasrec.hip: the SASRec point baseline (point_models/point_model.py:313-469) between the gather and the scatter.  X [B * T, ldx]:
+// the gathered user_seq rows, C = Fi * D columns read; tu / ti: the gathered target rows (row stride ldq).  The attention's
+// forward kernel saves, per (b, t) row, N (nrm), 1 / sqrt(var + eps) (rstd), the key mask (km), Qin, Q, K, V and Y (yseq)
+// [B * T, C], per sample the softmax P and the final weights att = dropout(P * query mask) [B, 2, T, T] and final [B, C], and
+// writes the head-input rows hin [B (T - 1) + B, Dh = 2 C + Cu]: [rep_t | Y_t | tu] for t = 1 .. T - 1 (b-major), then
+// [final | ti | tu].  The shared head runs fc1 ONCE over those rows (z1, the engine's GEMM); from there on the rows are
+// positive (b-major, t = 1 .. T - 1), negative (t = 2 .. T - 1), final -- R of them: f1 = dropout(relu(z1)) fanned out
+// (score_sasrec_fan), z2 (GEMM), then f2, the logits, y, the loss terms, dlogit and dz2 (score_sasrec_out).  share != 0
+// (keep_prob = 1): no negative rows, their terms ride on the positive rows t >= 2.  Backward: dz1e [R, 200] (GEMM) folded back
+// onto the rows of z1 (score_sasrec_fold), dhin (GEMM), then score_sasrec_attn_bwd: dQ / dK / dV [B * T, C], dX (every one of the
+// ldx columns), per-sample dgamma / dbeta [B, C], d target_item / d target_user into dhead (row stride ldh).
+// mask0 [R, 200] / mask1 [R, 80] / mask_a [2, B, T, T]: explicit dropout masks or null (then from seed, or *seed_dev).
+#define SCORE_SASREC_CMAX 128     /* widest Fi * D the kernels cover */
+struct SasrecArgs {
+  const float* X; const float* tu; const float* ti;
+  const float* beta; const float* gamma; const float* Wq; const float* bq; const float* Wk; const float* bk; const float* Wv; const float* bv;
+  const float* W3; const float* b3;
+  const int32_t* length; const int32_t* label;
+  const uint8_t* mask0; const uint8_t* mask1; const uint8_t* mask_a;
+  float keep; uint64_t seed; const uint64_t* seed_dev;
+  float* nrm; float* rstd; float* km; float* qin; float* q; float* k; float* v; float* yseq; float* p; float* att; float* fin; float* hin;
+  float* z1; float* f1; float* z2; float* f2; float* rlogit; float* dlogit; float* dz2; float* dz1e; float* dz1; float* dhin;
+  float* logit; float* ypred; float* lossb;
+  float* dq; float* dk; float* dv; float* dX; float* dhead; float* dgamma; float* dbeta;
+  int B, T, C, Cu, Dh, ldx, ldq, ldh, off_ti, off_tu, Bglobal, share;
+};
+bool score_sasrec_fits(int T, int C);                             // T >= 3, C <= SCORE_SASREC_CMAX, a sample's buffers inside 160 KiB of LDS
+int score_sasrec_attn_fwd(const SasrecArgs& a, hipStream_t s);
+int score_sasrec_fan(const SasrecArgs& a, hipStream_t s);
+int score_sasrec_out(const SasrecArgs& a, hipStream_t s);
+int score_sasrec_fold(const SasrecArgs& a, hipStream_t s);
+int score_sasrec_attn_bwd(const SasrecArgs& a, hipStream_t s);

@@ -601,7 +601,7 @@ class ShardedSCORE(object):
 
     def __init__(self, feature_size, eb_dim, hidden_size, max_time_len, obj_per_time_slice, user_fnum, item_fnum,
                  seed=1111, comm=None, backend=None, model_type=None, device=None):
-        if model_type in ("GRU4Rec", "Caser", "DELF", "DEEMS", "SVDpp", "SVD++"):      # (a point model: another feed tuple, another constructor; its row-sharded form does not exist)
+        if model_type in ("GRU4Rec", "Caser", "DELF", "DEEMS", "SVDpp", "SVD++", "SASRec"):      # (a point model: another feed tuple, another constructor; its row-sharded form does not exist)
             raise ValueError("ShardedSCORE does not run model_type='%s': row-sharded training covers the slice models only "
                              "(use score_amd.model.%s on one device)" % (model_type, model_type))
         self.comm = comm if comm is not None else TorchDistComm()

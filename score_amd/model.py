@@ -760,6 +760,7 @@ class SCOREBASE(object):
         st.id_status = self._id_status.data_ptr()      # (a caller may have pointed the struct at a status word of its own: dist.py)
         st.gather_done_event = st.plan_done_event = st.grads_done_event = st.loss_done_event = st.loss_host = None
         st.plan_workspace = None
+        st.drop_mask2 = None
         return st
 
     def _event_array(self, events):
@@ -905,13 +906,23 @@ class SCOREBASE(object):
             self._flush_adam()
         if gather_event is not None:
             st.gather_done_event = C.c_void_p(gather_event.cuda_event)
-        m0 = m1 = None
+        m0 = m1 = m2 = None
         if masks is not None:
             m0 = torch.as_tensor(np.asarray(masks[0]), dtype=torch.uint8).to(self.device).contiguous()
             m1 = torch.as_tensor(np.asarray(masks[1]), dtype=torch.uint8).to(self.device).contiguous()
-            lead = (self.dropout_towers,) if self.dropout_towers > 1 else ()
-            if tuple(m0.shape) != lead + (db.B, 200) or tuple(m1.shape) != lead + (db.B, 80):
-                raise ValueError("dropout masks must be %s and %s" % (list(lead + ("B", 200)), list(lead + ("B", 80))))
+            want = self._mask_shapes(db.B)
+            if len(want) == 2:
+                lead = (self.dropout_towers,) if self.dropout_towers > 1 else ()
+                if tuple(m0.shape) != want[0] or tuple(m1.shape) != want[1]:
+                    raise ValueError("dropout masks must be %s and %s" % (list(lead + ("B", 200)), list(lead + ("B", 80))))
+            else:                   # (a third mask rides in score_state_t.drop_mask2: SASRec's attention weights)
+                bad = len(masks) != 3 or tuple(m0.shape) != want[0] or tuple(m1.shape) != want[1]
+                if not bad:
+                    m2 = torch.as_tensor(np.asarray(masks[2]), dtype=torch.uint8).to(self.device).contiguous()
+                    bad = tuple(m2.shape) != want[2]
+                if bad:
+                    raise ValueError("dropout masks must be shaped %s" % ", ".join(str(list(w)) for w in want))
+                st.drop_mask2 = m2.data_ptr()
         seed = (self._drop_seed * 0x9E3779B1 + self.step * 0x85EBCA77) & 0xFFFFFFFFFFFFFFFF
         events = self.fwd_events
         if stage_event is not None:          # (k, event): score_forward records it at its stage boundary k
@@ -923,8 +934,13 @@ class SCOREBASE(object):
                                     float(keep_prob), _ptr(m0), _ptr(m1), C.c_uint64(seed),
                                     self._event_array(events), self._stream())
         _lib.check(rc, "score_forward")
-        self._keep = (m0, m1)
+        self._keep = (m0, m1, m2)
         return lay, ws, st
+
+    def _mask_shapes(self, B):
+        """shapes of the explicit dropout masks a batch of B samples takes (forward_backward / train: dropout_masks)"""
+        lead = (self.dropout_towers,) if self.dropout_towers > 1 else ()
+        return (lead + (B, 200), lead + (B, 80))
 
     def forward_backward(self, batch_data, reg_lambda, keep_prob=1.0, dropout_masks=None):
         """Forward + backward; gradients land in self.w_g (without the L2 term) and
@@ -1975,5 +1991,43 @@ class SVDpp(GRU4Rec):
         return np.asarray(a, dtype=np.float32).reshape(())      # (_import: the base class's reshape to the library's (1,))
 
 
+class SASRec(GRU4Rec):
+    """point_models/point_model.py:313-469 on PointBaseModel (:9-63): the flat user history X = user_seq [B, T, C = Fi * D] through
+    a layer norm (ln/Variable = beta, ln/Variable_1 = gamma: plain variables, BOTH L2-regularised) and one block of two-head
+    self-attention -- Q from the normalised rows, K and V from the raw X, keys whose row sums to 0 masked, softmax over all T keys
+    (no causal mask, lengths not used), query mask, dropout on the weights, residual --, then the shared head prediction_layer/
+    fc1..fc3 (no batch norm) three times with independent dropout: on [rep_t | Y_t | target_user] for t = 1 .. T - 1 (label 1), on
+    the same rows for t = 2 .. T - 1 (label 0) and on [final | target_item | target_user], which gives y_pred; the loss is the sum
+    of the three log-loss means and the L2 term.  rep_t = Y_t [t < user_seq_length], final = sum_t rep_t.  GRU4Rec's constructor,
+    5-tuple, loader and train / eval / save / restore; hidden_size is accepted and ignored.  max_time_len >= 3 and
+    item_fnum * eb_dim <= 128 (ValueError beyond).  Every batch computes all T positions (skip_masked_slices has no effect);
+    the positions the loader padded take part in the attention and in both sequence means, as in the reference.
+
+    dropout_masks, where given, is (m0 [R, 200], m1 [R, 80], ma [2, B, T, T]) with R = B (T - 1) + B (T - 2) + B rows ordered
+    positive (b-major, t = 1 .. T - 1), negative (t = 2 .. T - 1), final.  Without masks every use of tf.nn.dropout draws from
+    a hash stream of its own, seeded per step -- from device memory under a captured step, so every step form trains at
+    keep_prob < 1.
+
+    The query mask at TF's initial values (gamma = 1, beta = 0): sum_c Qin of a live row is then the rounding residue of a sum
+    that is exactly 0, and TF's own mask an accident of its fp32 summation.  The kernels compute the formula as written, in
+    fp32, in a fixed order; that one case is not pinned to the float64 restatement (tests/sasrec_ref.py)."""
+    model_type = "SASRec"
+    reads_length = False
+    CMAX = 128
+
+    def __init__(self, feature_size, eb_dim, hidden_size, max_time_len, user_fnum, item_fnum, seed=1111, device=None):
+        if int(max_time_len) < 3:
+            raise ValueError("SASRec: max_time_len = %d is below 3 (the negative rows are the positions 2 .. T - 1)" % int(max_time_len))
+        if int(item_fnum) * int(eb_dim) > self.CMAX:
+            raise ValueError("SASRec: item_fnum * eb_dim = %d is above %d, the widest row the attention kernels cover"
+                             % (int(item_fnum) * int(eb_dim), self.CMAX))
+        GRU4Rec.__init__(self, feature_size, eb_dim, hidden_size, max_time_len, user_fnum, item_fnum, seed=seed, device=device)
+
+    def _mask_shapes(self, B):
+        T = int(self.cfg.max_time_len)
+        R = B * (T - 1) + B * (T - 2) + B
+        return ((R, 200), (R, 80), (2, B, T, T))
+
+
 MODELS = {"SCORE": SCORE, "RIA": RIA, "RCA": RCA, "SCORE_USER": SCORE_USER, "SCORE_ITEM": SCORE_ITEM, "RRN": RRN, "GCMC": GCMC,
-          "GRU4Rec": GRU4Rec, "Caser": Caser, "DELF": DELF, "DEEMS": DEEMS, "SVDpp": SVDpp, "SVD++": SVDpp}      # ("SVD++": the driver's name, train_time_point_models.py:157-170)
+          "GRU4Rec": GRU4Rec, "Caser": Caser, "DELF": DELF, "DEEMS": DEEMS, "SVDpp": SVDpp, "SVD++": SVDpp, "SASRec": SASRec}      # ("SVD++": the driver's name, train_time_point_models.py:157-170)

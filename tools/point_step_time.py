@@ -1,5 +1,5 @@
-"""ms per training step (and per evaluation call) of a point baseline (point_models/point_model.py:123-311:
-GRU4Rec, Caser, SVD++, DELF, DEEMS) through
+"""ms per training step (and per evaluation call) of a point baseline (point_models/point_model.py:123-469:
+GRU4Rec, Caser, SVD++, DELF, DEEMS, SASRec) through
 the reference's train() / eval signatures, at the reference's point-model shapes (train_time_point_models.py:15-35, 353-354):
 Tmall, N = 1,529,672, D = 16, H = 32, T = 50, Fu = 3, Fi = 4,
   train100: B = 100      train200: B = 200      eval1000: forward only (eval_async), B = 1000
@@ -12,6 +12,8 @@ recurrences in one grouped launch each way) and "deems_composed" (debug_flags bi
 recurrence per launch).
 --model SVDpp times the SVD++ baseline (form "svdpp": csrc/svdpp.hip, one launch each way) against GRU4Rec's stacked form at
 train200 and eval1000.
+--model SASRec times the SASRec baseline (form "sasrec": csrc/sasrec.hip, the attention in one launch each way, the shared head over
+2 T - 2 rows per sample; train() at its default keep_prob 0.8) against GRU4Rec's stacked form at train200 and eval1000.
 Every (case, form) runs in a fresh process: `warmup` untimed steps, then `steps` timed ones over a few pre-staged device
 batches (random ids; history lengths as the loader reports them, up to 300, so most samples run all T steps), wall clock
 between two device synchronisations.  With --pairs n the two forms alternate n times.
@@ -23,6 +25,7 @@ between two device synchronisations.  With --pairs n the two forms alternate n t
     python tools/point_step_time.py --model DELF --pairs 3   # ... (GRU4Rec stacked, DELF)
     python tools/point_step_time.py --model DEEMS --pairs 3  # ... (DEEMS fused, DEEMS composed)
     python tools/point_step_time.py --model SVDpp --pairs 3  # train200 and eval1000, (GRU4Rec stacked, SVD++) alternating three times
+    python tools/point_step_time.py --model SASRec --pairs 3 # ... (GRU4Rec stacked, SASRec)
     python tools/point_step_time.py --case train200 --form stacked --profile-steps 30     # no timing: a short run for a profiler
 """
 import argparse
@@ -36,12 +39,13 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 TMALL = dict(N=1529672, D=16, H=32, T=50, Fu=3, Fi=4)
 CASES = {"train100": dict(B=100, train=True), "train200": dict(B=200, train=True), "eval1000": dict(B=1000, train=False)}
 FORMS = {"stacked": 0, "composed": 8192, "caser": 0, "delf": 0, "deems": 0, "deems_composed": 64 | 8192,
-         "svdpp": 0}      # debug_flags of a form
+         "svdpp": 0, "sasrec": 0}      # debug_flags of a form
 FORM_MODEL = {"stacked": "GRU4Rec", "composed": "GRU4Rec", "caser": "Caser", "delf": "DELF", "deems": "DEEMS", "deems_composed": "DEEMS",
-              "svdpp": "SVDpp"}
+              "svdpp": "SVDpp", "sasrec": "SASRec"}
 PAIRS = {"GRU4Rec": ("stacked", "composed"), "Caser": ("stacked", "caser"), "DELF": ("stacked", "delf"),
-         "DEEMS": ("deems", "deems_composed"), "SVDpp": ("stacked", "svdpp")}     # what --model alternates
-MODEL_CASES = {"SVDpp": ("train200", "eval1000")}      # the cases --model runs without --case (default: all three)
+         "DEEMS": ("deems", "deems_composed"), "SVDpp": ("stacked", "svdpp"),
+         "SASRec": ("stacked", "sasrec")}     # what --model alternates
+MODEL_CASES = {"SVDpp": ("train200", "eval1000"), "SASRec": ("train200", "eval1000")}      # the cases --model runs without --case (default: all three)
 
 
 def run_one(case, form, steps, warmup, n_batches=4, H=None):
@@ -88,7 +92,7 @@ def main():
     ap.add_argument("--form", choices=tuple(FORMS))
     ap.add_argument("--steps", type=int, default=200)
     ap.add_argument("--warmup", type=int, default=20)
-    ap.add_argument("--model", choices=tuple(PAIRS), default="GRU4Rec", help="the model whose two forms (Caser / DELF / SVDpp: GRU4Rec stacked and the model) alternate")
+    ap.add_argument("--model", choices=tuple(PAIRS), default="GRU4Rec", help="the model whose two forms (Caser / DELF / SVDpp / SASRec: GRU4Rec stacked and the model) alternate")
     ap.add_argument("--pairs", type=int, default=1, help="alternating pairs per case")
     ap.add_argument("--hidden", type=int, default=0, help="another hidden size than the reference's 32")
     ap.add_argument("--profile-steps", type=int, default=0, help="run this many steps after the warm-up and print nothing timed")
