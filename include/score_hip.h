@@ -765,6 +765,37 @@ int score_batch_assemble(const score_graph_t* g, const int32_t* uids, const int3
                          int32_t start_time, int32_t pred_time, uint64_t seed,
                          const score_batch_out_t* out, void* stream);
 
+/* ---- point baselines: batch assembly from a device-resident sequence store ------------------- */
+
+/* The files of point_models/data_loader.py parsed once (score_amd/pointdata.py, PointSeqStore), device int32 / int64.
+ * Line l of the target file: its user history is user_seq[user_off[l] .. user_off[l + 1]) -- the LAST max_len ids of the line,
+ * at least one, each the ROW of that item in item_rows -- and user_len[l] its untruncated length.  The dual form (DataLoaderDualSeq)
+ * adds one history per sample: item_seq[item_off[l * per_line + c] ..) rows of user_rows, item_len[l * per_line + c]; NULL in
+ * the single form.  target_user [n_lines] / target_item [n_lines * per_line] are rows of user_rows [n_user_rows, Fu] /
+ * item_rows [n_item_rows, Fi], which hold [id, side features...].  struct_bytes = sizeof(score_point_store_t): the call
+ * refuses any other value (this struct's own size check; score_abi_struct_sizes does not list it). */
+typedef struct {
+  int64_t struct_bytes;
+  const int64_t* user_off; const int32_t* user_seq; const int32_t* user_len;
+  const int64_t* item_off; const int32_t* item_seq; const int32_t* item_len;
+  const int32_t* target_user; const int32_t* target_item;
+  const int32_t* user_rows; const int32_t* item_rows;
+  int64_t n_lines, n_user_rows, n_item_rows;
+  int32_t per_line, max_len;
+} score_point_store_t;
+
+/* One batch of DataLoaderUserSeq / DataLoaderDualSeq (data_loader.py:15-87, 89-185) in ONE launch: target lines
+ * [first_line, first_line + n_lines) of the store, B = n_lines * per_line samples, into the flat batch layout.
+ * user_1hop = user_seq as [B, T, 1, Fi] (a history shorter than T is padded by repeating its last id), length = the untruncated
+ * user length, target_user / target_item, label = 1 for a line's first sample and 0 for the others.  length2 != NULL: the dual
+ * form -- item_1hop = item_seq as [B, T, 1, Fu] and length2 = item_seq_length (the store must hold the item side).  Every
+ * tensor the point model does not use (user_2hop, item_2hop, and item_1hop in the single form) is written as zeros by the
+ * same launch.  T * Fi and T * Fu may not exceed 8192 words (SCORE_E_SHAPE); T must equal the store's max_len, per_line
+ * its per_line. */
+int score_point_batch_assemble(const score_point_store_t* store, int64_t first_line, int32_t n_lines, int32_t per_line,
+                               int32_t T, int32_t Fu, int32_t Fi, const score_batch_out_t* out, int32_t* length2,
+                               void* stream);
+
 /* ---- "next" row f4: ranking metrics of an evaluation pass on the device ----------------------- */
 
 /* get_ranking_quality (train_score.py:104-142) without the host round trip of the predictions:

@@ -65,6 +65,15 @@ class BatchOut(C.Structure):
                                            "target_item", "label", "length")]
 
 
+class PointStore(C.Structure):
+    """score_point_store_t (struct_bytes is its own size check: score_point_batch_assemble refuses another value)"""
+    _fields_ = [("struct_bytes", C.c_int64)] + \
+               [(n, C.c_void_p) for n in ("user_off", "user_seq", "user_len", "item_off", "item_seq", "item_len", "target_user",
+                                           "target_item", "user_rows", "item_rows")] + \
+               [("n_lines", C.c_int64), ("n_user_rows", C.c_int64), ("n_item_rows", C.c_int64),
+                ("per_line", C.c_int32), ("max_len", C.c_int32)]
+
+
 class AdamTable(C.Structure):
     """score_adam_table_t"""
     _fields_ = [("p", C.c_void_p), ("m", C.c_void_p), ("v", C.c_void_p), ("g", C.c_void_p), ("n_rows", C.c_int64),
@@ -101,6 +110,8 @@ _SIGS = {
     "score_table_init": [c_f, C.c_int64, C.c_int32, C.c_int64, C.c_int64, C.c_int64, C.c_uint64, C.c_void_p],
     "score_batch_assemble": [C.POINTER(Graph), c_i, c_i, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
                              C.c_int32, C.c_uint64, C.POINTER(BatchOut), C.c_void_p],
+    "score_point_batch_assemble": [C.POINTER(PointStore), C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
+                                   C.POINTER(BatchOut), c_i, C.c_void_p],
     "score_param_layout": [C.POINTER(Config), C.POINTER(ParamEntry), C.c_int32, C.POINTER(C.c_int64),
                            C.POINTER(C.c_int64)],
     "score_workspace_layout": [C.POINTER(Config), C.c_int32, C.POINTER(Workspace)],

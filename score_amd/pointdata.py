@@ -23,7 +23,11 @@ target line i -- the positive's first, then each negative's --, sequences separa
 truncated like the user history and reported with its untruncated length.  It yields the 7-tuple score_amd.model.DELF trains on,
 
     (user_seq [B, max_len, Fi], user_seq_length [B], item_seq [B, max_len, Fu], item_seq_length [B], target_user [B, Fu],
-     target_item [B, Fi], label [B])."""
+     target_item [B, Fi], label [B]).
+
+PointSeqStore parses the same files once into flat arrays that live on the device, and DeviceDataLoaderUserSeq /
+DeviceDataLoaderDualSeq -- the same constructors -- assemble every batch from them in one kernel launch (csrc/pointloader.hip):
+the same batches, as device tensors."""
 import pickle
 
 import numpy as np
@@ -152,3 +156,285 @@ class DataLoaderDualSeq(DataLoaderUserSeq):
                 np.asarray(labels, dtype=i32))
 
     next = __next__
+
+
+# ---- the same batches from a device-resident store ------------------------------------------------------------------------
+class PointSeqStore(object):
+    """The files of DataLoaderUserSeq / DataLoaderDualSeq parsed ONCE on the host into flat integer arrays that
+    `.to_device()` uploads; csrc/pointloader.hip then assembles a batch from them in one launch (DeviceDataLoaderUserSeq /
+    DeviceDataLoaderDualSeq below).  item_seq_file=None is the single form, a path the dual form.
+
+    Row tables, COMPACTED over the ids that occur in the parsed lines (memory follows the files, not the id range: CCMR has
+    about 5 M ids): user_rows [n_user_rows, Fu] and item_rows [n_item_rows, Fi] hold [id, features...] per entity, one row
+    per distinct dictionary KEY, in order of first use.  A history id's key is str(int(id)), a target id's key the text as
+    written -- what the host loaders look up -- so '7' and '07' are two rows where a target line writes the latter.  Everything
+    else names a row of these tables, never an id (column 0 of the row is the id):
+      user_off int64 [n_lines + 1], user_seq int32: line l's history is user_seq[user_off[l]:user_off[l + 1]], the rows (in
+          item_rows) of the LAST max_len ids of the line; user_len int32 [n_lines] its untruncated length;
+      item_off / item_seq / item_len: the same per sample l * per_line + c (rows in user_rows), dual form only, else None;
+      target_user int32 [n_lines] (DualSeq's rebinding kept: the row of the last id of the line's last item sequence as
+          written), target_item int32 [n_lines * per_line].
+    Only the lines of whole batches are parsed (n_lines = lines in the target file // lines_per_batch * lines_per_batch); the
+    tail of the history files is never read.  Per batch, from parse time: batch_max_user_len, and in the dual form
+    batch_max_len / batch_min_len over both length arrays (in the single form they are the user side's), so no batch needs a
+    read-back to know its active slices.
+
+    Malformed input raises here what the host loader raises at that batch: ValueError for an empty history or a history file
+    shorter than the target file (int('')), IndexError for fewer item sequences than 1 + neg_sample_num, KeyError for an id
+    missing from a dictionary; ValueError for batch_size % (1 + neg_sample_num) != 0.  A target line with fewer than
+    1 + neg_sample_num items, which the host loader turns into a short batch, is a ValueError: a batch here has one size."""
+
+    def __init__(self, target_file, user_seq_file, item_seq_file, max_len, neg_sample_num, batch_size,
+                 user_feat_dict_file=None, item_feat_dict_file=None):
+        self.batch_size, self.max_len, self.neg_sample_num = int(batch_size), int(max_len), int(neg_sample_num)
+        self.per_line = per_line = 1 + self.neg_sample_num
+        if self.batch_size % per_line != 0:
+            raise ValueError("batch size should be a multiple of %d (1 + neg_sample_num)" % per_line)
+        if self.max_len <= 0:
+            raise ValueError("max_len must be positive")
+        self.lines_per_batch = self.batch_size // per_line
+        self.dual = item_seq_file is not None
+        self.files = (target_file, user_seq_file, item_seq_file, user_feat_dict_file, item_feat_dict_file)
+        user_dict = DataLoaderUserSeq._load(user_feat_dict_file)
+        item_dict = DataLoaderUserSeq._load(item_feat_dict_file)
+        L = self.max_len
+        u_rows, i_rows, u_map, i_map = [], [], {}, {}
+
+        def row_of(key, table, rows, dct):
+            r = table.get(key)
+            if r is None:
+                row = [int(key)] + (list(dct[key]) if dct is not None else [])
+                r = table[key] = len(rows)
+                rows.append(row)
+            return r
+
+        def kept(hist):        # (the pad repeats the last id: converting it again could not raise anything new)
+            return [str(int(i)) for i in hist[-L:]]
+        with open(target_file) as f:
+            n_total = sum(1 for _ in f)
+        self.n_batches = n_total // self.lines_per_batch
+        self.n_lines = n_lines = self.n_batches * self.lines_per_batch
+        user_seq, user_len, item_seq, item_len, t_user, t_item = [], [], [], [], [], []
+        user_off, item_off = [0], [0]
+        tf, uf = open(target_file), open(user_seq_file)
+        itf = open(item_seq_file) if self.dual else None
+        try:
+            for _ in range(n_lines):
+                fields = tf.readline()[:-1].split(",")
+                uid, iids = fields[0], fields[1:1 + per_line]
+                hist = uf.readline()[:-1].split(",")
+                if self.dual:
+                    item_hists = [h.split(",") for h in itf.readline()[:-1].split("\t")]
+                user_seq += [row_of(k, i_map, i_rows, item_dict) for k in kept(hist)]
+                user_off.append(len(user_seq))
+                user_len.append(len(hist))
+                if self.dual:
+                    resolved = [[row_of(k, u_map, u_rows, user_dict) for k in kept(h)] for h in item_hists]
+                    uid = item_hists[-1][-1]          # (the reference's rebinding of `uid`)
+                t_user.append(row_of(uid, u_map, u_rows, user_dict))
+                if len(iids) < per_line:
+                    raise ValueError("a target line holds %d items, fewer than 1 + neg_sample_num = %d" % (len(iids), per_line))
+                for j, iid in enumerate(iids):
+                    t_item.append(row_of(iid, i_map, i_rows, item_dict))
+                    if self.dual:
+                        item_len.append(len(item_hists[j]))
+                        item_seq += resolved[j]
+                        item_off.append(len(item_seq))
+        finally:
+            tf.close()
+            uf.close()
+            if itf is not None:
+                itf.close()
+        i32 = np.int32
+        self.user_off, self.user_seq = np.asarray(user_off, dtype=np.int64), np.asarray(user_seq, dtype=i32)
+        self.user_len = np.asarray(user_len, dtype=i32)
+        self.target_user, self.target_item = np.asarray(t_user, dtype=i32), np.asarray(t_item, dtype=i32)
+        if self.dual:
+            self.item_off, self.item_seq = np.asarray(item_off, dtype=np.int64), np.asarray(item_seq, dtype=i32)
+            self.item_len = np.asarray(item_len, dtype=i32)
+        else:
+            self.item_off = self.item_seq = self.item_len = None
+        # (rows of unequal width: the ValueError np.stack raises in the host loader)
+        self.user_rows = np.asarray(u_rows, dtype=i32).reshape(len(u_rows), -1) if u_rows else np.zeros((0, 1), dtype=i32)
+        self.item_rows = np.asarray(i_rows, dtype=i32).reshape(len(i_rows), -1) if i_rows else np.zeros((0, 1), dtype=i32)
+        self.Fu, self.Fi = int(self.user_rows.shape[1]), int(self.item_rows.shape[1])
+        per_batch = self.user_len.reshape(self.n_batches, self.lines_per_batch)
+        self.batch_max_user_len = per_batch.max(axis=1) if self.n_batches else np.zeros((0,), dtype=i32)
+        self.batch_max_len, self.batch_min_len = self.batch_max_user_len, (per_batch.min(axis=1) if self.n_batches else self.batch_max_user_len)
+        if self.dual and self.n_batches:
+            other = self.item_len.reshape(self.n_batches, self.batch_size)
+            self.batch_max_len = np.maximum(self.batch_max_len, other.max(axis=1))
+            self.batch_min_len = np.minimum(self.batch_min_len, other.min(axis=1))
+        self._dev = self.device = self.struct = None
+
+    def check(self, batch_size, max_len, neg_sample_num, dual):
+        """ValueError unless a loader with these arguments would cut this store's lines into this store's batches"""
+        got = (int(batch_size), int(max_len), int(neg_sample_num), bool(dual))
+        have = (self.batch_size, self.max_len, self.neg_sample_num, self.dual)
+        if got != have:
+            raise ValueError("the store was built for (batch_size, max_len, neg_sample_num, dual) = %r, the loader asks for %r"
+                             % (have, got))
+
+    def to_device(self, device=None):
+        import ctypes as C
+        import torch
+        from . import _lib
+        if not torch.cuda.is_available():
+            raise RuntimeError("PointSeqStore.to_device needs an AMD GPU (HIP); batch assembly has no CPU path")
+        dev = torch.device(device if device is not None else "cuda:%d" % torch.cuda.current_device())
+        names = ("user_off", "user_seq", "user_len", "item_off", "item_seq", "item_len", "target_user", "target_item",
+                 "user_rows", "item_rows")
+        d = {}
+        for k in names:
+            a = getattr(self, k)
+            if a is not None:       # (an empty array still needs a valid pointer)
+                d[k] = torch.from_numpy(np.ascontiguousarray(a)).to(dev) if a.size else torch.zeros((1,), dtype=torch.int32, device=dev)
+        ptr = lambda k: C.c_void_p(d[k].data_ptr()) if k in d else C.c_void_p(0)
+        self._dev, self.device = d, dev
+        self.struct = _lib.PointStore(C.sizeof(_lib.PointStore), *[ptr(k) for k in names], self.n_lines,
+                                      len(self.user_rows), len(self.item_rows), self.per_line, self.max_len)
+        return self
+
+
+class _Shape(object):
+    """the fields of a model's cfg that say how large a batch's tensors are (a loader without a model has no cfg)"""
+
+    def __init__(self, T, Fu, Fi):
+        self.max_time_len, self.obj_per_time_slice, self.user_fnum, self.item_fnum = T, 1, Fu, Fi
+
+
+class DeviceDataLoaderUserSeq(object):
+    """DataLoaderUserSeq's constructor (point_models/data_loader.py:16), its batches assembled on the device: every batch is one
+    torch.empty and one launch (score_point_batch_assemble) on the current stream, and what comes out is a DeviceBatch that
+    train / eval / harness.evaluate take as it is and that still indexes like the reference's 5-tuple (batch_data[3]: the target
+    items).  The files are parsed once, by a PointSeqStore: the reference builds a fresh loader per epoch and per validation
+    pass, and `store=previous.store` skips the parse and the upload (ValueError if batch_size, max_len or neg_sample_num are
+    not the store's).  model=: the batches carry the active_slices DeviceBatch(model, host_tuple) would compute, from the
+    store's per-batch length extremes -- no device value is read; max_len and the two feature counts are checked against
+    model.cfg.  Without a model active_slices is 0 (all T).  Needs a GPU (RuntimeError); a PointSeqStore alone does not."""
+    dual = False
+
+    def __init__(self, batch_size, max_len, target_file, user_seq_file, neg_sample_num, user_feat_dict_file,
+                 item_feat_dict_file, model=None, store=None, device=None):
+        self._setup(batch_size, max_len, target_file, user_seq_file, None, neg_sample_num, user_feat_dict_file,
+                    item_feat_dict_file, model, store, device)
+
+    def _setup(self, batch_size, max_len, target_file, user_seq_file, item_seq_file, neg_sample_num, user_feat_dict_file,
+               item_feat_dict_file, model, store, device):
+        import torch
+        from . import _lib
+        from . import model as M
+        self.batch_size, self.max_len, self.neg_sample_num = int(batch_size), int(max_len), int(neg_sample_num)
+        per_line = 1 + self.neg_sample_num
+        if self.batch_size % per_line != 0:
+            raise ValueError("batch size should be a multiple of %d (1 + neg_sample_num)" % per_line)
+        if store is not None:
+            store.check(batch_size, max_len, neg_sample_num, self.dual)
+        if not torch.cuda.is_available():
+            raise RuntimeError("%s needs an AMD GPU (HIP); batch assembly has no CPU path" % type(self).__name__)
+        if store is None:
+            store = PointSeqStore(target_file, user_seq_file, item_seq_file, max_len, neg_sample_num, batch_size,
+                                  user_feat_dict_file, item_feat_dict_file)
+        self.store = store
+        self.spec = M.DUAL_FEED if self.dual else M.POINT_FEED
+        if model is not None:
+            cfg = model.cfg
+            if model.feed_spec.n != self.spec.n:
+                raise ValueError("the model is fed %s, this loader yields %s" % (model.feed_spec.what, self.spec.what))
+            if store.n_batches and (int(cfg.max_time_len), int(cfg.user_fnum), int(cfg.item_fnum)) != (store.max_len, store.Fu, store.Fi):
+                raise ValueError("the model has (max_time_len, user_fnum, item_fnum) = %r, the files give %r"
+                                 % ((cfg.max_time_len, cfg.user_fnum, cfg.item_fnum), (store.max_len, store.Fu, store.Fi)))
+            if device is None:
+                device = model.device
+            if self.dual:
+                self._active = [M.active_slices(model, a, b) for a, b in zip(store.batch_max_len, store.batch_min_len)]
+            else:
+                self._active = [M.active_slices(model, a) for a in store.batch_max_user_len]
+        else:
+            self._active = [0] * store.n_batches
+        if store._dev is None or (device is not None and torch.device(device) != store.device):
+            store.to_device(device)
+        self.device, self.lib = store.device, _lib.load()
+        self.lines_per_batch = store.lines_per_batch
+        self._shape = _Shape(store.max_len, store.Fu, store.Fi)
+        self._shapes = self.spec.device_shapes(self._shape, self.batch_size)
+        self._n_flat = M.flat_batch_size(self._shapes)
+        self._feed_shapes = self.spec.shapes(self._shape, self.batch_size)
+        self._batch_no = 0
+
+    def close(self):
+        """the host loaders close their files here; the store read them to their end and holds none open"""
+        return None
+
+    def __iter__(self):
+        return self
+
+    def __len__(self):
+        return self.store.n_batches
+
+    def __next__(self):
+        import ctypes as C
+        import torch
+        from . import _lib
+        from . import model as M
+        i, st = self._batch_no, self.store
+        if i >= st.n_batches:
+            raise StopIteration
+        flat = torch.empty((self._n_flat,), dtype=torch.int32, device=self.device)
+        tens = M.carve_batch(flat, self._shapes)
+        out = _lib.BatchOut(*[M._ptr(t) for t in tens[:8]])
+        rc = self.lib.score_point_batch_assemble(C.byref(st.struct), i * self.lines_per_batch, self.lines_per_batch, st.per_line,
+                                                 st.max_len, st.Fu, st.Fi, C.byref(out), M._ptr(tens[8]) if self.dual else None,
+                                                 C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream))
+        _lib.check(rc, "score_point_batch_assemble")
+        self._batch_no = i + 1
+        return _point_batch_class()(tens, flat, self.batch_size, self._active[i], self.spec, self._feed_shapes)
+
+    next = __next__
+
+
+class DeviceDataLoaderDualSeq(DeviceDataLoaderUserSeq):
+    """DataLoaderDualSeq's constructor (data_loader.py:90) over the same store and kernel: the 7-tuple's item_seq rides as
+    item_1hop and item_seq_length as the ninth tensor, length2; batch_data[5] are the target items.  With model=, active_slices
+    follows both length arrays (DELF: a length <= 0 anywhere in the batch computes all T; DEEMS: it does not)."""
+    dual = True
+
+    def __init__(self, batch_size, max_len, target_file, user_seq_file, item_seq_file, neg_sample_num, user_feat_dict_file,
+                 item_feat_dict_file, model=None, store=None, device=None):
+        if item_seq_file is None and store is None:
+            raise ValueError("DeviceDataLoaderDualSeq needs an item_seq_file")
+        self._setup(batch_size, max_len, target_file, user_seq_file, item_seq_file, neg_sample_num, user_feat_dict_file,
+                    item_feat_dict_file, model, store, device)
+
+
+_POINT_BATCH = None
+
+
+def _point_batch_class():
+    """the DeviceBatch subclass the device loaders yield (made on first use: score_amd.model imports torch, this module's host
+    loaders do not need it)"""
+    global _POINT_BATCH
+    if _POINT_BATCH is None:
+        from .model import DeviceBatch, _batch_struct
+
+        class PointDeviceBatch(DeviceBatch):
+            """a point batch assembled on the device (views of one flat buffer, like every DeviceBatch); indexable like the
+            reference's 5- / 7-tuple, field i in the tuple's own shape"""
+
+            def __init__(self, tensors, flat, B, active, spec, feed_shapes):
+                self.tensors, self.flat, self.B, self.active_slices = tensors, flat, B, int(active)
+                self._spec, self._feed_shapes = spec, feed_shapes
+                self.struct = _batch_struct(tensors, B, self.active_slices)
+
+            def __len__(self):
+                return self._spec.n
+
+            def __getitem__(self, i):
+                if not -self._spec.n <= i < self._spec.n:
+                    raise IndexError(i)
+                i %= self._spec.n
+                for k, sl in enumerate(self._spec.slots):
+                    if sl[0] == i:
+                        return self.tensors[k].view(self._feed_shapes[k])
+        _POINT_BATCH = PointDeviceBatch
+    return _POINT_BATCH
