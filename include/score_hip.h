@@ -796,6 +796,51 @@ int score_point_batch_assemble(const score_point_store_t* store, int64_t first_l
                                int32_t T, int32_t Fu, int32_t Fi, const score_batch_out_t* out, int32_t* length2,
                                void* stream);
 
+/* ---- point baselines: per-entity histories from the interaction log, and batches from them ---- */
+
+/* One side's histories straight from the remapped log (gen_target.py:223-275 gen_user_item_hist_dict_*, then
+ * gen_history_point.py:22-65's cut to the last MAX_LEN ids), device arrays.  ent / other / time_key / t_idx [n_events]: the
+ * entity whose history an event joins (users: uid), the id it contributes (iid), a non-negative key below 2^time_bits that
+ * orders events as the reference's time_int does, and the slice index; events with start_time <= t_idx < pred_time and
+ * id_lo <= ent < id_lo + n_ent count.  Entity e = ent - id_lo: its history, ordered by (time_key, position in the log) as
+ * Python's stable sorted orders it, is seq[off[e] .. off[e + 1]); len[e] = min(its count, hist_max_len), and the KEPT
+ * history is the last len[e] ids of it.  off int64 [n_ent + 1], seq int32 [n_events] (off[n_ent] words are used, the rest
+ * is zero), len int32 [n_ent].  A stable sort (score_sort_pairs: once where bits(n_ent) + time_bits <= 32, else by time and
+ * then by entity) and one kernel of binary searches; no atomics, so the output is a pure function of the input.
+ * n_events < 2^31 (SCORE_E_SHAPE); temp: score_point_hist_temp_bytes(n_events) (SCORE_E_WORKSPACE). */
+int score_point_hist_build(const int32_t* ent, const int32_t* other, const int32_t* time_key, const int32_t* t_idx,
+                           int64_t n_events, int32_t start_time, int32_t pred_time, int32_t id_lo, int32_t n_ent,
+                           int32_t time_bits, int32_t hist_max_len, int64_t* off, int32_t* seq, int32_t* len,
+                           void* temp, int64_t temp_bytes, void* stream);
+int64_t score_point_hist_temp_bytes(int64_t n_events);
+
+/* Both sides' histories and the target lines (score_amd/pointdata.py, PointLogStore), device int32 / int64.  Users are the
+ * ids 1 .. n_users (row id - 1 of user_rows [n_users, Fu]), items n_users + 1 .. n_users + n_items (row id - 1 - n_users of
+ * item_rows [n_items, Fi]).  line_user [n_lines], line_items [n_lines * per_line] (a line's positive, then its negatives),
+ * line_last_item [n_lines] (the line's last item AS WRITTEN, which may lie behind the first per_line).  The item side and
+ * line_last_item may be NULL in the single form.  struct_bytes = sizeof(score_point_log_store_t): the call refuses any other
+ * value (this struct's own size check; score_abi_struct_sizes does not list it). */
+typedef struct {
+  int64_t struct_bytes;
+  const int64_t* user_hist_off; const int32_t* user_hist_seq; const int32_t* user_hist_len;
+  const int64_t* item_hist_off; const int32_t* item_hist_seq; const int32_t* item_hist_len;
+  const int32_t* line_user; const int32_t* line_items; const int32_t* line_last_item;
+  const int32_t* user_rows; const int32_t* item_rows;
+  int64_t n_lines, n_users, n_items;
+  int32_t per_line, hist_max_len;
+} score_point_log_store_t;
+
+/* score_point_batch_assemble from a score_point_log_store_t: the same launch shape, the same output, the same error codes and
+ * shape limits.  A sample's history is found through its entity's id and is the last min(len, T) ids of the kept history,
+ * padded by repeating the last; length = len of the line's user; the dual form's length2 = len of the sample's item, 1 for an
+ * item without history, whose sequence is zeros (the reference's one-element history [0]); id 0 anywhere is a row of zeros
+ * (the reference needs a key '0' in its feature dictionary for that).  target_user is the line's user in the single form; in
+ * the dual form it is the last id of the kept history of line_last_item (DataLoaderDualSeq's rebinding), zeros where that
+ * item has none.  T is free: one store serves every T with T * Fi, T * Fu <= 8192. */
+int score_point_batch_assemble_log(const score_point_log_store_t* store, int64_t first_line, int32_t n_lines, int32_t per_line,
+                                   int32_t T, int32_t Fu, int32_t Fi, const score_batch_out_t* out, int32_t* length2,
+                                   void* stream);
+
 /* ---- "next" row f4: ranking metrics of an evaluation pass on the device ----------------------- */
 
 /* get_ranking_quality (train_score.py:104-142) without the host round trip of the predictions:

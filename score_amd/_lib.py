@@ -74,6 +74,15 @@ class PointStore(C.Structure):
                 ("per_line", C.c_int32), ("max_len", C.c_int32)]
 
 
+class PointLogStore(C.Structure):
+    """score_point_log_store_t (struct_bytes is its own size check, like PointStore's)"""
+    _fields_ = [("struct_bytes", C.c_int64)] + \
+               [(n, C.c_void_p) for n in ("user_hist_off", "user_hist_seq", "user_hist_len", "item_hist_off", "item_hist_seq",
+                                           "item_hist_len", "line_user", "line_items", "line_last_item", "user_rows", "item_rows")] + \
+               [("n_lines", C.c_int64), ("n_users", C.c_int64), ("n_items", C.c_int64),
+                ("per_line", C.c_int32), ("hist_max_len", C.c_int32)]
+
+
 class AdamTable(C.Structure):
     """score_adam_table_t"""
     _fields_ = [("p", C.c_void_p), ("m", C.c_void_p), ("v", C.c_void_p), ("g", C.c_void_p), ("n_rows", C.c_int64),
@@ -112,6 +121,11 @@ _SIGS = {
                              C.c_int32, C.c_uint64, C.POINTER(BatchOut), C.c_void_p],
     "score_point_batch_assemble": [C.POINTER(PointStore), C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
                                    C.POINTER(BatchOut), c_i, C.c_void_p],
+    "score_point_batch_assemble_log": [C.POINTER(PointLogStore), C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
+                                       C.POINTER(BatchOut), c_i, C.c_void_p],
+    "score_point_hist_build": [c_i, c_i, c_i, c_i, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
+                               C.c_void_p, c_i, c_i, C.c_void_p, C.c_int64, C.c_void_p],
+    "score_point_hist_temp_bytes": [C.c_int64],
     "score_param_layout": [C.POINTER(Config), C.POINTER(ParamEntry), C.c_int32, C.POINTER(C.c_int64),
                            C.POINTER(C.c_int64)],
     "score_workspace_layout": [C.POINTER(Config), C.c_int32, C.POINTER(Workspace)],

@@ -119,3 +119,89 @@ def tmall_pipeline(log, seed=11):
         targets[name] = gen_target_lines(r["uid"], r["iid"], r["t_idx"], r["n_users"], r["n_items"], pt, neg,
                                          c["start_time"], seed + pt)
     return g, r, targets
+
+
+# ---- the point baselines' history files (gen_target.py:223-275, gen_history_point.py:22-65) ------------------------------------
+POINT_HIST_MAX_LEN = 300                    # gen_history_point.py:12-20 (MAX_LEN_CCMR / _Taobao / _Tmall)
+
+
+def point_history_lines(uid, iid, time_key, t_idx, target_lines, start_time, pred_time, hist_max_len=POINT_HIST_MAX_LEN):
+    """The two history files of the point baselines as text lines (without the newline), from an in-memory log:
+    TargetGen.gen_user_item_hist_dict_* (gen_target.py:223-275) followed by gen_history_point.py's gen_user_hist_seq_file /
+    gen_item_hist_seq_file (:22-65), restated in plain Python -- the yardstick of PointLogStore.
+
+    An event counts if start_time <= t_idx < pred_time (:241-244).  A user's history is the items of its events ordered by
+    time_key with Python's stable sorted (:257), so events of one time stay in log order; an item's the same with the roles
+    exchanged.  time_key: any non-negative integer that orders events as the reference's time_int does (Tmall: the MMDD
+    column).  Line l of the user file is the last hist_max_len ids of the user of target line l (:31-32); a user without
+    history makes the reference exit(1) (:36) -- here a ValueError naming the line.  Line l of the item file holds one history
+    per item of target line l AS WRITTEN (all of them, not only the first 1 + neg_sample_num, :48), tab separated; an item
+    without history has the history '0' (:59).
+
+    -> (user_hist_lines, item_hist_lines)"""
+    H = int(hist_max_len)
+    if H <= 0:
+        raise ValueError("hist_max_len must be positive")
+    user_hist, item_hist = {}, {}
+    for u, i, k, t in zip(np.asarray(uid).tolist(), np.asarray(iid).tolist(), np.asarray(time_key).tolist(),
+                          np.asarray(t_idx).tolist()):
+        if t < start_time or t >= pred_time:
+            continue
+        user_hist.setdefault(u, []).append((i, k))
+        item_hist.setdefault(i, []).append((u, k))
+    for d in (user_hist, item_hist):
+        for key in d:
+            d[key] = [str(x[0]) for x in sorted(d[key], key=lambda tup: tup[1])]
+    user_lines, item_lines = [], []
+    for l, (u, items) in enumerate(target_lines):
+        if int(u) not in user_hist:
+            raise ValueError("target line %d: user %d has no history in slices [%d, %d)" % (l, int(u), start_time, pred_time))
+        user_lines.append(",".join(user_hist[int(u)][-H:]))
+        item_lines.append("\t".join(",".join(item_hist[int(i)][-H:]) if int(i) in item_hist else "0" for i in items))
+    return user_lines, item_lines
+
+
+def write_point_files(directory, target_lines, user_hist_lines, item_hist_lines, user_rows, item_rows):
+    """The files DataLoaderUserSeq / DataLoaderDualSeq / PointSeqStore read, written into `directory`: target.txt
+    ('uid,iid,iid,...' per line), user_hist.txt, item_hist.txt and the two pickled feature dictionaries, keyed by the id as a
+    string with the features that follow the id as values (feateng_tmall.py:125-133) -- plus a key '0' with zeros, the row the
+    reference's loader looks up for the stand-in history of an item without one.  user_rows [U, Fu] / item_rows [I, Fi] are
+    remap_tmall_log's tables (column 0 the id).  -> (target, user_hist, item_hist, user_feat_dict, item_feat_dict) paths"""
+    import os
+    import pickle
+    os.makedirs(directory, exist_ok=True)
+    paths = [os.path.join(directory, n) for n in ("target.txt", "user_hist.txt", "item_hist.txt", "user_feat_dict.pkl",
+                                                  "item_feat_dict.pkl")]
+    texts = (["%d,%s" % (int(u), ",".join(str(int(i)) for i in items)) for u, items in target_lines], user_hist_lines,
+             item_hist_lines)
+    for p, lines in zip(paths[:3], texts):
+        with open(p, "w") as f:
+            f.write("".join(l + "\n" for l in lines))
+    for p, rows in zip(paths[3:], (user_rows, item_rows)):
+        rows = np.asarray(rows)
+        dct = {str(int(r[0])): [int(x) for x in r[1:]] for r in rows}
+        dct["0"] = [0] * (rows.shape[1] - 1)
+        with open(p, "wb") as f:
+            pickle.dump(dct, f)
+    return tuple(paths)
+
+
+def tmall_point_stores(log, seed=11, dual=True, batch_size=None, build="device", device=None):
+    """Raw Tmall log -> ({'train' | 'validation' | 'test': PointLogStore}, remap dict): the point baselines' data path on the
+    log SCoRe trains from (tmall_pipeline's target lines: the same seed gives the same lines).  Train lines carry 1 negative,
+    validation / test lines 99; histories are cut at the reference's 300.  batch_size: a dict per split or one number;
+    default 200 for train (a multiple of 2) and TMALL's eval_batch_size for the others."""
+    from .pointdata import PointLogStore
+    r = remap_tmall_log(log)
+    c = TMALL
+    stores = {}
+    for name, pt, neg in (("train", c["pred_time_train"], c["train_neg"]),
+                          ("validation", c["pred_time_validation"], c["test_neg"]),
+                          ("test", c["pred_time_test"], c["test_neg"])):
+        lines = gen_target_lines(r["uid"], r["iid"], r["t_idx"], r["n_users"], r["n_items"], pt, neg, c["start_time"], seed + pt)
+        B = batch_size.get(name) if isinstance(batch_size, dict) else batch_size
+        if B is None:
+            B = 200 if name == "train" else c["eval_batch_size"]
+        stores[name] = PointLogStore(r["uid"], r["iid"], np.asarray(log)[:, 5], r["t_idx"], lines, c["start_time"], pt,
+                                     POINT_HIST_MAX_LEN, neg, B, r["user_rows"], r["item_rows"], dual, build=build, device=device)
+    return stores, r

@@ -27,7 +27,11 @@ truncated like the user history and reported with its untruncated length.  It yi
 
 PointSeqStore parses the same files once into flat arrays that live on the device, and DeviceDataLoaderUserSeq /
 DeviceDataLoaderDualSeq -- the same constructors -- assemble every batch from them in one kernel launch (csrc/pointloader.hip):
-the same batches, as device tensors."""
+the same batches, as device tensors.
+
+PointLogStore holds what those files are made from instead -- one history per user and per item, built from the remapped
+interaction log on the device (csrc/pointhist.hip) or in numpy -- and the same two device loaders take it as `store=`: the
+batches of the reference's whole chain (history dictionaries -> history files -> loader) without writing a file."""
 import pickle
 
 import numpy as np
@@ -296,6 +300,250 @@ class PointSeqStore(object):
         return self
 
 
+def host_hist_csr(ent, other, time_key, t_idx, start_time, pred_time, id_lo, n_ent, hist_max_len):
+    """score_point_hist_build (csrc/pointhist.hip) in numpy: one side's histories from the log.  -> (off int64 [n_ent + 1],
+    seq int32, len int32 [n_ent]): entity e = id - id_lo has the history seq[off[e]:off[e + 1]], its events of slices
+    [start_time, pred_time) ordered by (time_key, position in the log); len[e] = min(its count, hist_max_len), and the kept
+    history is the last len[e] ids of it."""
+    ent, other, time_key, t_idx = (np.asarray(a) for a in (ent, other, time_key, t_idx))
+    e = ent.astype(np.int64) - id_lo
+    keep = np.flatnonzero((t_idx >= start_time) & (t_idx < pred_time) & (e >= 0) & (e < n_ent))
+    order = keep[np.lexsort((keep, time_key[keep], e[keep]))]
+    off = np.zeros(n_ent + 1, dtype=np.int64)
+    np.cumsum(np.bincount(e[keep], minlength=n_ent), out=off[1:])
+    return off, other[order].astype(np.int32), np.minimum(np.diff(off), hist_max_len).astype(np.int32)
+
+
+class PointLogStore(object):
+    """The point baselines' histories straight from the remapped interaction log -- ONE history per user and one per item,
+    bounded by the log, instead of the file form's one sequence per sample -- and the target lines; the device loaders below
+    take it as `store=` and yield, integer for integer, the batches the reference's chain yields from the same log and lines:
+    gen_target.py:223-275 (hist dicts) -> gen_history_point.py:22-65 (files; dataprep.point_history_lines restates both) ->
+    DataLoaderUserSeq / DataLoaderDualSeq.
+
+    uid / iid / time_key / t_idx [n]: the log as dataprep.remap_tmall_log returns it (users 1 .. U, items U + 1 .. U + I,
+    U and I the row counts of user_rows [U, Fu] / item_rows [I, Fi], whose column 0 is the id) and a non-negative key that
+    orders events as the reference's time_int does (Tmall: the MMDD column).  target_lines: (uid, [items...]) as
+    dataprep.gen_target_lines yields them.
+
+    Arrays (numpy with build="host", device tensors with build="device"; .arrays() gives numpy either way):
+      user_hist_off int64 [U + 1], user_hist_seq int32, user_hist_len int32 [U]: user u's events of slices
+          [start_time, pred_time) ordered by (time_key, position in the log) are the ITEM IDS
+          user_hist_seq[off[u - 1]:off[u]]; len = min(count, hist_max_len), the length the loaders report, and the kept
+          history the last len ids of the segment; a batch at max_len T reads the last min(len, T) of those;
+      item_hist_off / _seq / _len: the same over the items (user ids), dual form only, else None;
+      line_user int32 [n_lines], line_items int32 [n_lines * per_line], line_last_item int32 [n_lines] (the line's last item
+          AS WRITTEN: in the dual form target_user is the last id of ITS kept history, DataLoaderDualSeq's rebinding, 0 if none).
+    Only the lines of whole batches are kept.  batch_max_user_len / batch_max_len / batch_min_len as PointSeqStore's.  The
+    store does not depend on max_len: one store serves models of different max_time_len.
+
+    build="host" is numpy and needs no GPU; build="device" sorts the log on the device (csrc/pointhist.hip) and reads back
+    once, the per-batch length extremes and the shortest user history of a target line; no batch reads anything back.
+
+    An item without history has the reference's stand-in history [0]: a sequence of zero rows, length 1.  Id 0 is a row of
+    ZEROS here; the reference's loader raises KeyError for it unless its feature dictionary has a key '0' -- that failure is
+    deliberately not reproduced (dataprep.write_point_files writes the key).
+    ValueError: batch_size % (1 + neg_sample_num) != 0; a log or target id outside its range; a target line with fewer than
+    1 + neg_sample_num items; a target line whose user has no history (the reference: exit(1)), naming the line."""
+
+    def __init__(self, uid, iid, time_key, t_idx, target_lines, start_time, pred_time, hist_max_len, neg_sample_num, batch_size,
+                 user_rows, item_rows, dual, build="device", device=None):
+        i32 = np.int32
+        self.batch_size, self.neg_sample_num, self.hist_max_len = int(batch_size), int(neg_sample_num), int(hist_max_len)
+        self.per_line = per_line = 1 + self.neg_sample_num
+        if self.batch_size % per_line != 0:
+            raise ValueError("batch size should be a multiple of %d (1 + neg_sample_num)" % per_line)
+        if self.hist_max_len <= 0:
+            raise ValueError("hist_max_len must be positive")
+        if build not in ("device", "host"):
+            raise ValueError("build must be 'device' or 'host'")
+        self.lines_per_batch = self.batch_size // per_line
+        self.dual, self.build = bool(dual), build
+        self.start_time, self.pred_time = int(start_time), int(pred_time)
+        self.user_rows = np.ascontiguousarray(user_rows, dtype=i32)
+        self.item_rows = np.ascontiguousarray(item_rows, dtype=i32)
+        if self.user_rows.ndim != 2 or self.item_rows.ndim != 2 or not len(self.user_rows) or not len(self.item_rows):
+            raise ValueError("user_rows / item_rows must be non-empty [n, F] tables")
+        self.n_users, self.n_items = U, I = len(self.user_rows), len(self.item_rows)
+        self.Fu, self.Fi = int(self.user_rows.shape[1]), int(self.item_rows.shape[1])
+        if not (np.array_equal(self.user_rows[:, 0], np.arange(1, U + 1)) and
+                np.array_equal(self.item_rows[:, 0], np.arange(U + 1, U + I + 1))):
+            raise ValueError("column 0 of user_rows / item_rows must be the ids 1 .. U / U + 1 .. U + I")
+        cols = [np.ascontiguousarray(np.asarray(a).reshape(-1)) for a in (uid, iid, time_key, t_idx)]
+        n = len(cols[0])
+        if n == 0 or any(len(c) != n for c in cols) or n >= 2 ** 31:
+            raise ValueError("uid, iid, time_key and t_idx must be equally long, with 1 .. 2^31 - 1 events")
+        if cols[0].min() < 1 or cols[0].max() > U or cols[1].min() < U + 1 or cols[1].max() > U + I:
+            raise ValueError("the log's uid must lie in 1 .. %d and its iid in %d .. %d" % (U, U + 1, U + I))
+        if cols[2].min() < 0 or cols[2].max() >= 2 ** 31:
+            raise ValueError("time_key must be a non-negative 31-bit integer")
+        self._log = uid, iid, time_key, t_idx = [c.astype(i32) for c in cols]
+        self.time_bits = max(1, int(time_key.max()).bit_length())
+        self.n_batches = len(target_lines) // self.lines_per_batch
+        self.n_lines = n_lines = self.n_batches * self.lines_per_batch
+        line_user, line_items, line_last = [], [], []
+        for l, (u, items) in enumerate(target_lines[:n_lines]):
+            if len(items) < per_line:
+                raise ValueError("target line %d holds %d items, fewer than 1 + neg_sample_num = %d" % (l, len(items), per_line))
+            line_user.append(int(u))
+            line_items += [int(i) for i in items[:per_line]]
+            line_last.append(int(items[-1]))
+            if not 1 <= line_user[-1] <= U or min(int(i) for i in items) < U + 1 or max(int(i) for i in items) > U + I:
+                raise ValueError("target line %d: an id outside users 1 .. %d / items %d .. %d" % (l, U, U + 1, U + I))
+        self.line_user, self.line_items = np.asarray(line_user, dtype=i32), np.asarray(line_items, dtype=i32)
+        self.line_last_item = np.asarray(line_last, dtype=i32)
+        self._dev = self.device = self.struct = None
+        if build == "host":
+            self._build_host()
+        else:
+            self._build_device(device)
+        self._log = None
+        if n_lines and self._line_min_user_len[0] <= 0:
+            l = int(self._line_min_user_len[1])
+            raise ValueError("target line %d: user %d has no history in slices [%d, %d)"
+                             % (l, line_user[l], self.start_time, self.pred_time))
+
+    HIST = ("user_hist_off", "user_hist_seq", "user_hist_len", "item_hist_off", "item_hist_seq", "item_hist_len")
+
+    def _extremes(self, user_len, item_len, take, maximum, minimum, amax, amin):
+        """per batch: the longest user history, the longest and the shortest history of both sides; and the shortest user
+        history of any line with its line -- in numpy or torch, whichever the five functions belong to"""
+        nb, lpb = self.n_batches, self.lines_per_batch
+        lu = take(user_len, self.line_user.astype(np.int64) - 1)
+        per = lu.reshape(nb, lpb)
+        mx_u, mn = amax(per), amin(per)
+        mx = mx_u
+        if self.dual:
+            li = take(item_len, self.line_items.astype(np.int64) - 1 - self.n_users).reshape(nb, self.batch_size)
+            li = maximum(li, li * 0 + 1)                                       # (no history: the stand-in [0], length 1)
+            mx, mn = maximum(mx, amax(li)), minimum(mn, amin(li))
+        return mx_u, mx, mn, lu.min().reshape(1), lu.argmin().reshape(1)
+
+    def _set_extremes(self, parts):
+        nb = self.n_batches
+        parts = [np.asarray(p).astype(np.int64) for p in parts]
+        self.batch_max_user_len, self.batch_max_len, self.batch_min_len = (p.astype(np.int32) for p in parts[:3])
+        self._line_min_user_len = (int(parts[3][0]), int(parts[4][0])) if nb else (1, 0)     # (length, line)
+
+    def _build_host(self):
+        uid, iid, time_key, t_idx = self._log
+        U, I, H = self.n_users, self.n_items, self.hist_max_len
+        self.user_hist_off, self.user_hist_seq, self.user_hist_len = host_hist_csr(uid, iid, time_key, t_idx, self.start_time,
+                                                                                   self.pred_time, 1, U, H)
+        if self.dual:
+            self.item_hist_off, self.item_hist_seq, self.item_hist_len = host_hist_csr(iid, uid, time_key, t_idx, self.start_time,
+                                                                                       self.pred_time, U + 1, I, H)
+        else:
+            self.item_hist_off = self.item_hist_seq = self.item_hist_len = None
+        if self.n_batches:
+            self._set_extremes(self._extremes(self.user_hist_len, self.item_hist_len, lambda a, i: a[i], np.maximum, np.minimum,
+                                              lambda a: a.max(axis=1), lambda a: a.min(axis=1)))
+        else:
+            self._set_extremes([np.zeros((0,))] * 5)
+
+    def _build_device(self, device):
+        import ctypes as C
+        import torch
+        from . import _lib
+        if not torch.cuda.is_available():
+            raise RuntimeError("PointLogStore(build='device') needs an AMD GPU (HIP); build='host' does not")
+        dev = torch.device(device if device is not None else "cuda:%d" % torch.cuda.current_device())
+        lib = _lib.load()
+        uid, iid, time_key, t_idx = [torch.from_numpy(c).to(dev) for c in self._log]
+        n, U, I = len(self._log[0]), self.n_users, self.n_items
+        temp_bytes = int(lib.score_point_hist_temp_bytes(n))
+        temp = torch.empty((temp_bytes,), dtype=torch.uint8, device=dev)
+        stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+        ptr = lambda t: C.c_void_p(t.data_ptr())
+        out = {}
+        for side, ent, other, id_lo, n_ent in (("user", uid, iid, 1, U), ("item", iid, uid, U + 1, I)):
+            if side == "item" and not self.dual:
+                out.update(item_hist_off=None, item_hist_seq=None, item_hist_len=None)
+                continue
+            off = torch.empty((n_ent + 1,), dtype=torch.int64, device=dev)
+            seq = torch.empty((n,), dtype=torch.int32, device=dev)
+            ln = torch.empty((n_ent,), dtype=torch.int32, device=dev)
+            rc = lib.score_point_hist_build(ptr(ent), ptr(other), ptr(time_key), ptr(t_idx), n, self.start_time, self.pred_time,
+                                            id_lo, n_ent, self.time_bits, self.hist_max_len, ptr(off), ptr(seq), ptr(ln),
+                                            ptr(temp), temp_bytes, stream)
+            _lib.check(rc, "score_point_hist_build")
+            out.update({side + "_hist_off": off, side + "_hist_seq": seq, side + "_hist_len": ln})
+        for k, v in out.items():
+            setattr(self, k, v)
+        if self.n_batches:       # the one read-back of the build
+            parts = self._extremes(self.user_hist_len, self.item_hist_len, lambda a, i: a[torch.from_numpy(i).to(dev)],
+                                   torch.maximum, torch.minimum, lambda a: a.amax(dim=1), lambda a: a.amin(dim=1))
+            sizes = [len(p) for p in parts]
+            host = torch.cat([p.to(torch.int64) for p in parts]).cpu().numpy()
+            self._set_extremes(np.split(host, np.cumsum(sizes)[:-1]))
+        else:
+            torch.cuda.current_stream(dev).synchronize()
+            self._set_extremes([np.zeros((0,))] * 5)
+        del temp
+        self._upload(dev, out)
+
+    def arrays(self):
+        """the six history arrays as numpy (None for a missing item side), the seq arrays cut to the words in use"""
+        out = {}
+        for k in self.HIST:
+            a = getattr(self, k)
+            out[k] = a if a is None or isinstance(a, np.ndarray) else a.cpu().numpy()
+        for side in ("user", "item"):
+            if out[side + "_hist_seq"] is not None:
+                out[side + "_hist_seq"] = out[side + "_hist_seq"][:int(out[side + "_hist_off"][-1])]
+        return out
+
+    def check(self, batch_size, max_len, neg_sample_num, dual):
+        """ValueError unless a loader with these arguments cuts this store's lines into this store's batches and its max_len
+        fits the assembly kernel (T * F <= 8192 words on both sides)"""
+        got = (int(batch_size), int(neg_sample_num), bool(dual))
+        have = (self.batch_size, self.neg_sample_num, self.dual)
+        if got != have:
+            raise ValueError("the store was built for (batch_size, neg_sample_num, dual) = %r, the loader asks for %r" % (have, got))
+        if int(max_len) <= 0 or int(max_len) * max(self.Fu, self.Fi) > 8192:
+            raise ValueError("max_len %d: max_len * max(Fu, Fi) must lie in 1 .. 8192" % int(max_len))
+
+    def _upload(self, dev, have):
+        import ctypes as C
+        import torch
+        from . import _lib
+        names = self.HIST + ("line_user", "line_items", "line_last_item", "user_rows", "item_rows")
+        d = {}
+        for k in names:
+            a = have.get(k, getattr(self, k))
+            if a is None:
+                continue
+            if isinstance(a, np.ndarray):        # (an empty array still needs a valid pointer)
+                a = torch.from_numpy(np.ascontiguousarray(a)).to(dev) if a.size else torch.zeros((1,), dtype=torch.int32, device=dev)
+            d[k] = a
+        ptr = lambda k: C.c_void_p(d[k].data_ptr()) if k in d else C.c_void_p(0)
+        self._dev, self.device = d, dev
+        self.struct = _lib.PointLogStore(C.sizeof(_lib.PointLogStore), *[ptr(k) for k in names], self.n_lines, self.n_users,
+                                         self.n_items, self.per_line, self.hist_max_len)
+
+    def to_device(self, device=None):
+        import torch
+        if not torch.cuda.is_available():
+            raise RuntimeError("PointLogStore.to_device needs an AMD GPU (HIP); batch assembly has no CPU path")
+        dev = torch.device(device if device is not None else "cuda:%d" % torch.cuda.current_device())
+        have = {}
+        if self._dev is not None:                # (a device build on another device: its tensors move)
+            have = {k: v.to(dev) for k, v in self._dev.items() if k in self.HIST}
+            for k, v in have.items():
+                setattr(self, k, v)
+        self._upload(dev, have)
+        return self
+
+    def store_bytes(self):
+        """bytes of the arrays a batch reads (the row tables excluded: both forms hold them)"""
+        total = 0
+        for k in self.HIST + ("line_user", "line_items", "line_last_item"):
+            a = getattr(self, k)
+            if a is not None:
+                total += int(a.numel() * a.element_size()) if not isinstance(a, np.ndarray) else int(a.nbytes)
+        return total
+
+
 class _Shape(object):
     """the fields of a model's cfg that say how large a batch's tensors are (a loader without a model has no cfg)"""
 
@@ -309,7 +557,9 @@ class DeviceDataLoaderUserSeq(object):
     train / eval / harness.evaluate take as it is and that still indexes like the reference's 5-tuple (batch_data[3]: the target
     items).  The files are parsed once, by a PointSeqStore: the reference builds a fresh loader per epoch and per validation
     pass, and `store=previous.store` skips the parse and the upload (ValueError if batch_size, max_len or neg_sample_num are
-    not the store's).  model=: the batches carry the active_slices DeviceBatch(model, host_tuple) would compute, from the
+    not the store's).  store= a PointLogStore: the same batches from per-entity histories built from the log
+    (score_point_batch_assemble_log); the file arguments may then be None, max_len is free (one store serves every T with
+    T * F <= 8192) and batch_size, neg_sample_num and the form are checked.  model=: the batches carry the active_slices DeviceBatch(model, host_tuple) would compute, from the
     store's per-batch length extremes -- no device value is read; max_len and the two feature counts are checked against
     model.cfg.  Without a model active_slices is 0 (all T).  Needs a GPU (RuntimeError); a PointSeqStore alone does not."""
     dual = False
@@ -336,14 +586,16 @@ class DeviceDataLoaderUserSeq(object):
             store = PointSeqStore(target_file, user_seq_file, item_seq_file, max_len, neg_sample_num, batch_size,
                                   user_feat_dict_file, item_feat_dict_file)
         self.store = store
+        self.from_log = isinstance(store, PointLogStore)      # (its histories are not cut to one max_len: T is the loader's)
+        T = self.max_len if self.from_log else store.max_len
         self.spec = M.DUAL_FEED if self.dual else M.POINT_FEED
         if model is not None:
             cfg = model.cfg
             if model.feed_spec.n != self.spec.n:
                 raise ValueError("the model is fed %s, this loader yields %s" % (model.feed_spec.what, self.spec.what))
-            if store.n_batches and (int(cfg.max_time_len), int(cfg.user_fnum), int(cfg.item_fnum)) != (store.max_len, store.Fu, store.Fi):
+            if store.n_batches and (int(cfg.max_time_len), int(cfg.user_fnum), int(cfg.item_fnum)) != (T, store.Fu, store.Fi):
                 raise ValueError("the model has (max_time_len, user_fnum, item_fnum) = %r, the files give %r"
-                                 % ((cfg.max_time_len, cfg.user_fnum, cfg.item_fnum), (store.max_len, store.Fu, store.Fi)))
+                                 % ((cfg.max_time_len, cfg.user_fnum, cfg.item_fnum), (T, store.Fu, store.Fi)))
             if device is None:
                 device = model.device
             if self.dual:
@@ -356,7 +608,8 @@ class DeviceDataLoaderUserSeq(object):
             store.to_device(device)
         self.device, self.lib = store.device, _lib.load()
         self.lines_per_batch = store.lines_per_batch
-        self._shape = _Shape(store.max_len, store.Fu, store.Fi)
+        self._T = T
+        self._shape = _Shape(T, store.Fu, store.Fi)
         self._shapes = self.spec.device_shapes(self._shape, self.batch_size)
         self._n_flat = M.flat_batch_size(self._shapes)
         self._feed_shapes = self.spec.shapes(self._shape, self.batch_size)
@@ -383,10 +636,11 @@ class DeviceDataLoaderUserSeq(object):
         flat = torch.empty((self._n_flat,), dtype=torch.int32, device=self.device)
         tens = M.carve_batch(flat, self._shapes)
         out = _lib.BatchOut(*[M._ptr(t) for t in tens[:8]])
-        rc = self.lib.score_point_batch_assemble(C.byref(st.struct), i * self.lines_per_batch, self.lines_per_batch, st.per_line,
-                                                 st.max_len, st.Fu, st.Fi, C.byref(out), M._ptr(tens[8]) if self.dual else None,
-                                                 C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream))
-        _lib.check(rc, "score_point_batch_assemble")
+        call = self.lib.score_point_batch_assemble_log if self.from_log else self.lib.score_point_batch_assemble
+        rc = call(C.byref(st.struct), i * self.lines_per_batch, self.lines_per_batch, st.per_line, self._T, st.Fu, st.Fi,
+                  C.byref(out), M._ptr(tens[8]) if self.dual else None,
+                  C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream))
+        _lib.check(rc, "score_point_batch_assemble_log" if self.from_log else "score_point_batch_assemble")
         self._batch_no = i + 1
         return _point_batch_class()(tens, flat, self.batch_size, self._active[i], self.spec, self._feed_shapes)
 

@@ -12,8 +12,17 @@ measurement runs in a fresh process and is one JSON line (stdout and --out, defa
                      --pairs (3) times.  A device-loader pass builds its loader on the store of the warm-up's, as a training
                      script does per epoch.
 
+  what = "from_log": (--from-log) the same two shapes -- DEEMS eval1000 (dual, 99 negatives, B = 1000) and GRU4Rec train200
+                     (single, B = 200) -- fed from a synthetic LOG of 20,000 users whose histories run 1 - 299 events over
+                     40,000 items: bytes of the log store (score_amd.pointdata.PointLogStore) against the file store's
+                     (PointSeqStore over the files dataprep.point_history_lines / write_point_files write), the device build
+                     against the numpy build, and ms per batch of score_point_batch_assemble_log against
+                     score_point_batch_assemble on the same lines: whole passes between two synchronisations, the two forms
+                     alternating --pairs times after a warm-up pass each; medians and the spread (max - min) of each.
+
     python tools/point_loader_time.py                               # GRU4Rec and DEEMS, both cases
     python tools/point_loader_time.py --model DEEMS --case eval1000
+    python tools/point_loader_time.py --from-log
 """
 import argparse
 import json
@@ -131,8 +140,91 @@ def run_pass(d, model_name, case, loader, warmup):
     return dict(what="pass", model=model_name, case=case, loader=loader, steps=n, warmup=warmup, ms_per_step=round(ms, 4))
 
 
+def synth_log(case, seed=7, n_users=20000, n_items=40000):
+    """a remapped log (users 1 .. U, items U + 1 .. U + I) whose user histories run 1 - 299 events, days of May - August 2015
+    (all inside the window [0, 8)), its tables and the case's target lines (one line more than whole batches)"""
+    import numpy as np
+    from score_amd import dataprep as dp
+    c = CASES[case]
+    rng = np.random.default_rng(seed)
+    U, I = n_users, n_items
+    counts = rng.integers(1, 300, U)
+    uid = np.repeat(np.arange(1, U + 1), counts)
+    uid = uid[rng.permutation(len(uid))]
+    iid = rng.integers(U + 1, U + I + 1, len(uid))
+    days = np.asarray([m * 100 + d for m in (5, 6, 7, 8) for d in range(1, 29)])
+    mmdd = rng.choice(days, len(uid))
+    per = 1 + c["neg"]
+    lines = [(int(rng.integers(1, U + 1)), [int(x) for x in rng.integers(U + 1, U + I + 1, per)])
+             for _ in range(c["batches"] * (c["B"] // per) + 1)]
+    user_rows = np.concatenate([np.arange(1, U + 1)[:, None], rng.integers(U + I + 1, TMALL["N"], (U, TMALL["Fu"] - 1))], axis=1)
+    item_rows = np.concatenate([np.arange(U + 1, U + I + 1)[:, None], rng.integers(U + I + 1, TMALL["N"], (I, TMALL["Fi"] - 1))], axis=1)
+    return dict(uid=uid, iid=iid, time_key=mmdd, t_idx=dp.tmall_slice_index(mmdd), lines=lines, user_rows=user_rows,
+                item_rows=item_rows, start=0, pred=8)
+
+
+def run_from_log(d, model_name, case, pairs):
+    import statistics
+    import numpy as np
+    import torch
+    from score_amd import dataprep as dp
+    from score_amd import pointdata as pd
+    torch.cuda.set_device(0)
+    c, dual, T = CASES[case], DUAL[model_name], TMALL["T"]
+    g = synth_log(case)
+    args = (g["uid"], g["iid"], g["time_key"], g["t_idx"], g["lines"], g["start"], g["pred"], dp.POINT_HIST_MAX_LEN, c["neg"],
+            c["B"], g["user_rows"], g["item_rows"], dual)
+    build_s = {}
+    for build in ("device", "device", "host"):          # (the first device build loads the code objects: the second is reported)
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        st = pd.PointLogStore(*args, build=build)
+        torch.cuda.synchronize()
+        build_s[build] = time.perf_counter() - t0
+        if build == "device":
+            log_store = st
+    t0 = time.perf_counter()
+    users, items = dp.point_history_lines(g["uid"], g["iid"], g["time_key"], g["t_idx"], g["lines"], g["start"], g["pred"])
+    tf, uf, itf, ud, idd = dp.write_point_files(d, g["lines"], users, items, g["user_rows"], g["item_rows"])
+    write_s = time.perf_counter() - t0
+    t0 = time.perf_counter()
+    file_store = pd.PointSeqStore(tf, uf, itf if dual else None, T, c["neg"], c["B"], ud, idd).to_device()
+    torch.cuda.synchronize()
+    parse_s = time.perf_counter() - t0
+    names = ("user_off", "user_seq", "user_len", "item_off", "item_seq", "item_len", "target_user", "target_item")
+    file_bytes = sum(int(getattr(file_store, k).nbytes) for k in names if getattr(file_store, k) is not None)
+    Dv = pd.DeviceDataLoaderDualSeq if dual else pd.DeviceDataLoaderUserSeq
+    files = (None, None, None) if dual else (None, None)
+
+    def one_pass(store):
+        loader = Dv(c["B"], T, *files, c["neg"], None, None, store=store)
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        n = sum(1 for _ in loader)
+        torch.cuda.synchronize()
+        return (time.perf_counter() - t0) * 1e3 / n
+    # the two forms yield the same batches (checked on the first one), then the timed passes
+    a, b = next(Dv(c["B"], T, *files, c["neg"], None, None, store=log_store)), next(Dv(c["B"], T, *files, c["neg"], None, None, store=file_store))
+    same = all(bool(torch.equal(a[k], b[k])) for k in range(len(a)))
+    for st in (log_store, file_store):
+        one_pass(st)
+    ms = {"log": [], "file": []}
+    for _ in range(pairs):
+        ms["log"].append(one_pass(log_store))
+        ms["file"].append(one_pass(file_store))
+    r4 = lambda x: round(x, 4)
+    return dict(what="from_log", model=model_name, case=case, events=int(len(g["uid"])), lines=log_store.n_lines,
+                batches=log_store.n_batches, same_first_batch=same, log_store_bytes=log_store.store_bytes(), file_store_bytes=file_bytes,
+                build_device_s=round(build_s["device"], 4), build_host_s=round(build_s["host"], 4),
+                files_write_s=round(write_s, 3), files_parse_upload_s=round(parse_s, 3),
+                log_ms_per_batch=[r4(x) for x in ms["log"]], file_ms_per_batch=[r4(x) for x in ms["file"]],
+                log_ms_median=r4(statistics.median(ms["log"])), file_ms_median=r4(statistics.median(ms["file"])),
+                log_ms_spread=r4(max(ms["log"]) - min(ms["log"])), file_ms_spread=r4(max(ms["file"]) - min(ms["file"])))
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--from-log", action="store_true", help="log store against file store: bytes, build time, ms per batch")
     ap.add_argument("--model", choices=tuple(DUAL))
     ap.add_argument("--case", choices=tuple(CASES))
     ap.add_argument("--pairs", type=int, default=3, help="alternating (host, device) passes per model and case")
@@ -140,9 +232,12 @@ def main():
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "point_loader_time.jsonl"))
     ap.add_argument("--timeout", type=int, default=300, help="seconds per fresh process")
     ap.add_argument("--dir", help=argparse.SUPPRESS)          # (a child: the files are here)
-    ap.add_argument("--what", choices=("loaders", "pass"), help=argparse.SUPPRESS)
+    ap.add_argument("--what", choices=("loaders", "pass", "from_log"), help=argparse.SUPPRESS)
     ap.add_argument("--loader", choices=("host", "device"), help=argparse.SUPPRESS)
     a = ap.parse_args()
+    if a.what == "from_log":
+        print(json.dumps(dict(run_from_log(a.dir, a.model, a.case, a.pairs), **TMALL)), flush=True)
+        return
     if a.what:
         r = run_loaders(a.dir, a.model, a.case) if a.what == "loaders" else run_pass(a.dir, a.model, a.case, a.loader, a.warmup)
         print(json.dumps(dict(r, **TMALL)), flush=True)
@@ -159,6 +254,15 @@ def main():
         with open(a.out, "a") as f:
             f.write(line + "\n")
         return json.loads(line)
+    if a.from_log:
+        with tempfile.TemporaryDirectory() as root:
+            for model_name, case in (("DEEMS", "eval1000"), ("GRU4Rec", "train200")):
+                if (a.model and a.model != model_name) or (a.case and a.case != case):
+                    continue
+                d = os.path.join(root, case)
+                os.makedirs(d)
+                child("--what", "from_log", "--dir", d, "--model", model_name, "--case", case, "--pairs", a.pairs)
+        return
     with tempfile.TemporaryDirectory() as root:
         for case in (a.case,) if a.case else tuple(CASES):
             d = os.path.join(root, case)
