@@ -548,6 +548,12 @@ def test_adam_matches_tf_form():
     (300_000, 12, "uniform"),        # one pass of 12 bits
     (70_000, 21, "equal"),           # every key equal: the order of the values must be the input order
     (50_000, 1, "uniform"),
+    (16_384, 13, "hot"),             # the first width of two passes (7 + 6 bits), n an exact multiple of the tile
+    (40_000, 24, "hot"),             # two passes of 4,096 bins: the widest LDS layout, eight digits per thread
+    (40_000, 25, "uniform"),         # the first width of three passes
+    (524_288, 24, "hot"),            # 64 tiles: the last size at which the scatter scans its own histogram columns
+    (524_289, 13, "uniform"),        # 65 tiles: the first size with the column-scan launch, and a last tile of one pair
+    (524_289, 32, "hot"),
 ])
 def test_sort_pairs_is_a_stable_sort(n, key_bits, dist):
     """csrc/sort.hip (score_sort_pairs): the occurrence sort of the index plan for small batches against torch's stable sort --

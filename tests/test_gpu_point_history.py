@@ -10,6 +10,7 @@ import numpy as np
 import pytest
 import torch
 
+import point_hist_cases as phc
 from helpers import GOLDEN
 from score_amd import dataprep as dp
 from score_amd.pointdata import (DataLoaderDualSeq, DataLoaderUserSeq, DeviceDataLoaderDualSeq, DeviceDataLoaderUserSeq,
@@ -217,3 +218,84 @@ def test_training_on_the_tmall_sample_from_the_log_equals_training_from_the_file
     assert sorted(pa) == sorted(pb)
     for k in pa:
         assert np.array_equal(pa[k], pb[k]), k
+
+
+# ---- score_point_hist_build itself at the sort's pass, tile and id-range edges (tests/point_hist_cases.py) -------------------
+POISON = -7
+
+
+def _build_call(lib, ent, other, d, c, temp, temp_bytes):
+    """one score_point_hist_build of the arguments c over the device columns (ent, other, d["time_key"], d["t_idx"]), on the
+    current stream, into poisoned outputs"""
+    import ctypes as C
+    ptr = lambda t: C.c_void_p(t.data_ptr())
+    off = torch.full((c["n_ent"] + 1,), POISON, dtype=torch.int64, device="cuda")
+    seq = torch.full((c["n"],), POISON, dtype=torch.int32, device="cuda")
+    ln = torch.full((c["n_ent"],), POISON, dtype=torch.int32, device="cuda")
+    rc = lib.score_point_hist_build(ptr(ent), ptr(other), ptr(d["time_key"]), ptr(d["t_idx"]),
+                                    c["n"], c["start"], c["pred"], c["id_lo"], c["n_ent"], c["time_bits"], c["H"], ptr(off), ptr(seq),
+                                    ptr(ln), ptr(temp), temp_bytes, C.c_void_p(torch.cuda.current_stream().cuda_stream))
+    return rc, off, seq, ln
+
+
+@pytest.mark.parametrize("name", phc.NAMES)
+def test_hist_build_equals_the_restatement_at_the_sorts_edges(name):
+    """the build called directly, twice back to back into ONE workspace -- the case, then the two id columns exchanged, as
+    PointLogStore._build_device does for the two sides --, against the plain-Python restatement: off, len, the window's words of
+    seq, zeros behind them (the header's promise), nothing left unwritten; and a workspace one byte short is refused untouched"""
+    from score_amd import _lib
+    lib = _lib.load()
+    first = phc.case(name)
+    second = phc.swapped(first)
+    d = {k: torch.from_numpy(first[k].copy()).cuda() for k in ("ent", "other", "time_key", "t_idx")}   # (read-only arrays)
+    temp_bytes = int(lib.score_point_hist_temp_bytes(first["n"]))
+    assert temp_bytes > 0
+    temp = torch.empty((temp_bytes,), dtype=torch.uint8, device="cuda")
+    rc, off, seq, ln = _build_call(lib, d["ent"], d["other"], d, first, temp, temp_bytes - 1)
+    torch.cuda.synchronize()
+    assert rc == -3                                                  # SCORE_E_WORKSPACE
+    assert bool((off == POISON).all()) and bool((seq == POISON).all()) and bool((ln == POISON).all())
+    runs = [_build_call(lib, d["ent"], d["other"], d, first, temp, temp_bytes),
+            _build_call(lib, d["other"], d["ent"], d, second, temp, temp_bytes)]
+    torch.cuda.synchronize()
+    for which, (c, (rc, off, seq, ln)) in enumerate(zip((first, second), runs)):
+        want_off, want_seq, want_len = phc.expected(name, swap=bool(which))
+        assert rc == 0, which
+        off, seq, ln = off.cpu().numpy(), seq.cpu().numpy(), ln.cpu().numpy()
+        used = int(want_off[-1])
+        print(name, "build", which, "structure", phc.structure(c["n_ent"], c["time_bits"]), "words in the window", used)
+        assert np.array_equal(off, want_off), which
+        assert np.array_equal(ln, want_len), which
+        assert np.array_equal(seq[:used], want_seq), which
+        assert not seq[used:].any(), which
+
+
+# ---- the loaders at the assembly kernel's edges: T = 1; T > H; T * Fu > 4,096 (one sample per chunk); T * Fi = 8,192 (all LDS) --
+EDGE_TS = (1, 65, 1400, 2048)
+
+
+@pytest.fixture(scope="module")
+def edge(cases, tmp_path_factory):
+    """the synthetic case's files and the host loaders' batches at every edge T (computed once, never modified), and ONE
+    device-built store per form, read at every T"""
+    c = cases["synth"]["c"]
+    _, host = _files_and_host(c, str(tmp_path_factory.mktemp("point_history_edges")), EDGE_TS)
+    stores = {dual: log_store(c, dual, build="device") for dual in (False, True)}
+    return c, host, stores
+
+
+@pytest.mark.parametrize("T", EDGE_TS)
+@pytest.mark.parametrize("dual", [False, True])
+def test_loaders_at_the_assembly_kernels_edges(edge, dual, T):
+    c, host, stores = edge
+    store = stores[dual]
+    assert (store.Fu, store.Fi, store.hist_max_len, c["B"]) == (3, 4, 64, 10)
+    assert 1400 * store.Fu > 4096 and 2048 * store.Fi == 8192 and 65 > store.hist_max_len
+    _check_batches(dual, _device(dual, c, T, store), host[(dual, T)])
+
+
+@pytest.mark.parametrize("dual", [False, True])
+def test_a_max_len_past_the_assembly_kernels_lds_is_refused(edge, dual):
+    c, _, stores = edge
+    with pytest.raises(ValueError, match="max_len 2049"):   # T * Fi = 8,196 words: the store's check, in front of any launch
+        _device(dual, c, 2049, stores[dual])

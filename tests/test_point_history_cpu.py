@@ -8,9 +8,10 @@ import os
 import numpy as np
 import pytest
 
+import point_hist_cases as phc
 from helpers import GOLDEN
 from score_amd import dataprep as dp
-from score_amd.pointdata import DataLoaderDualSeq, DataLoaderUserSeq, PointLogStore
+from score_amd.pointdata import DataLoaderDualSeq, DataLoaderUserSeq, PointLogStore, host_hist_csr
 
 SINGLE = ("user_seq", "user_seq_length", "target_user", "target_item", "label")
 DUAL = ("user_seq", "user_seq_length", "item_seq", "item_seq_length", "target_user", "target_item", "label")
@@ -226,3 +227,60 @@ def test_abi_entries_and_struct():
     for n in (1, 8192, 54925330):                                       # (the full Tmall log)
         assert lib.score_point_hist_temp_bytes(n) == 16 * ((n + 63) // 64 * 64) + lib.score_sort_pairs_temp_bytes(n)
     assert lib.score_point_hist_build(None, None, None, None, 10, 0, 1, 1, 5, 11, 6, None, None, None, None, 0, None) == -1
+
+
+# ---- the build's edge cases (tests/point_hist_cases.py): the numpy build against the plain-Python restatement ----------------
+@pytest.mark.parametrize("swap", [False, True])
+@pytest.mark.parametrize("name", phc.NAMES)
+def test_host_hist_csr_equals_the_restatement(name, swap):
+    c = phc.swapped(phc.case(name)) if swap else phc.case(name)
+    off, seq, ln = phc.expected(name, swap)
+    got = host_hist_csr(*[c[k] for k in phc.ARGS])
+    assert off.shape == (c["n_ent"] + 1,) and ln.shape == (c["n_ent"],) and seq.shape == (int(off[-1]),)
+    for g, w in zip(got, (off, seq, ln)):
+        assert g.dtype == w.dtype and g.shape == w.shape and np.array_equal(g, w)
+
+
+@pytest.mark.parametrize("name", phc.NAMES)
+def test_hist_cases_are_worth_running(name):
+    """what each case is in the table for, on the restatement alone"""
+    n, n_ent, id_lo, time_bits, H, _, key_bits, sorts, npass = phc.CASES[name]
+    c = phc.case(name)
+    off, seq, ln = phc.expected(name)
+    count = np.diff(off)
+    # the pass structure of the table, and the side of 32 bits it stands for
+    assert phc.structure(n_ent, time_bits) == (key_bits, sorts, npass) and (key_bits <= 32) == (sorts == 1)
+    # ... and another one for the second build into the same workspace
+    assert phc.structure(phc.swap_n_ent(name), time_bits)[1:] != (sorts, npass)
+    tiles = -(-n // phc.TILE)
+    assert (tiles > phc.FUSED_MAX_TILES) == (name == "past_fused") and (name != "fused_limit" or n == phc.FUSED_MAX_TILES * phc.TILE)
+    assert len(c["ent"]) == n and int(c["time_key"].max()) == 2 ** time_bits - 1 and int(c["time_key"].min()) == 0
+    assert len(np.unique(c["time_key"])) <= 12 and set(np.unique(c["t_idx"]).tolist()) == set(range(7))
+    # ids outside the range on both sides, inside the window too
+    inwin = (c["t_idx"] >= c["start"]) & (c["t_idx"] < c["pred"])
+    below, above = c["ent"] < id_lo, c["ent"].astype(np.int64) >= id_lo + n_ent
+    assert below.any() and above.any() and (name == "empty_window" or ((below & inwin).any() and (above & inwin).any()))
+    assert (id_lo != 1 or (c["ent"] < 0).any()) and int(off[-1]) == int((inwin & ~below & ~above).sum())
+    if name == "empty_window":
+        assert not inwin.any() and not off.any() and not ln.any() and len(seq) == 0
+        return
+    assert off[-1] > 0
+    if n_ent > 1:
+        assert (count > H).any() and (count == 0).any() and (ln == H).any()
+        assert count[n_ent - 2] == 0 and count[n_ent - 1] > 0 and (n_ent < 4 or count[n_ent - 3] > 0)
+    else:
+        assert count[0] > H
+    if name == "pack32_top_bit":                    # keys of real entities with the top bit set, not the sink's alone
+        assert count[2 ** 20:].sum() > 0 and n_ent > n
+    # equal (entity, time) with different payloads: what shows a sort that is not stable; over the tile seam where there is one
+    hist = phc.histories(*[c[k] for k in phc.ARGS[:-1]])
+    tied = seam = False
+    for l in hist.values():
+        runs = {}
+        for o, tk, pos in l:
+            runs.setdefault(tk, []).append((o, pos))
+        for r in runs.values():
+            if len(set(o for o, _ in r)) >= 2:
+                tied = True
+                seam = seam or (min(p for _, p in r) < phc.TILE <= max(p for _, p in r))
+    assert tied and (seam or n <= phc.TILE)
