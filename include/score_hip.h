@@ -841,6 +841,46 @@ int score_point_batch_assemble_log(const score_point_log_store_t* store, int64_t
                                    int32_t T, int32_t Fu, int32_t Fi, const score_batch_out_t* out, int32_t* length2,
                                    void* stream);
 
+/* ---- the temporal graph store from the behaviour log, on the device (csrc/graphbuild.hip) ---- */
+
+/* What TemporalGraph.from_log(draws="cell") builds (graph_storage.py:93-246 with per-cell counter-based draws), as device
+ * arrays.  uid / iid / t_idx int32 [n_events]: the remapped log (users 1 .. n_users, items n_users + 1 .. n_users + n_items,
+ * slices 0 .. time_slice_num - 1); an event with ANY of the three outside its range joins no cell on either side.  Cell
+ * c = e * time_slice_num + t of 0-based entity e.  user_off1 int64 [n_users * S + 1], item_off1 int64 [n_items * S + 1],
+ * user_nbr1 / item_nbr1 int32 [n_events] (off1[last] words are used, the rest is zero).
+ * The draw rule: G = 0x9E3779B97F4A7C15, mix = the finaliser of splitmix64,
+ *   key(seed, tag, c, j) = mix(mix(seed + G * ((tag << 40) + c + 1)) + G * (j + 1)) >> 32,
+ * tag 0 item shuffle, 1 item down-sample, 2 user shuffle, 3 user down-sample; the random order of n positions is the
+ * positions sorted by (key, position).  struct_bytes = sizeof(score_graph_build_t): the calls refuse any other value.
+ * Limits: n_events, n_users * S, n_items * S, n_users + n_items < 2^31 and max_1hop^2 <= 4096 (SCORE_E_SHAPE beyond); temp:
+ * score_graph_build_temp_bytes (SCORE_E_WORKSPACE, before any launch).  One workspace serves all calls of a build, and has to:
+ * the sorted cell keys of score_graph_build_1hop stay in it for the 2-hop calls. */
+typedef struct {
+  int64_t struct_bytes;
+  const int32_t* uid; const int32_t* iid; const int32_t* t_idx;
+  int64_t n_events;
+  int32_t n_users, n_items, time_slice_num, max_1hop, max_2hop, reserved;
+  uint64_t seed;
+  int64_t* user_off1; int32_t* user_nbr1; int64_t* item_off1; int32_t* item_nbr1;
+} score_graph_build_t;
+
+int64_t score_graph_build_temp_bytes(int64_t n_events, int32_t n_users, int32_t n_items, int32_t time_slice_num);
+
+/* Both sides' 1-hop CSRs in log order: a stable score_sort_pairs by cell and a binary search per cell.  No host wait. */
+int score_graph_build_1hop(const score_graph_build_t* g, void* temp, int64_t temp_bytes, void* stream);
+
+/* One side's 2-hop and degree lists (item_side: 1 items, 0 users), in two calls.
+ *   nbr2 == NULL: the side's cells with more than max_1hop entries are put in their random order in place (two
+ *     score_sort_pairs over their entries only), every cell's capped 2-hop length is counted and scanned into off2
+ *     int64 [n_ent * S + 1], and *total (host) receives off2's last word.  Waits for the stream twice.
+ *   nbr2 != NULL: nbr2 / deg2 int32 [cap2 >= total] are filled from off2; nothing is written past cap2.  No host wait.
+ * A cell walks the first min(len, max_1hop) entries x of its stored list; x's cell of the same slice, of full length d > 1,
+ * contributes its first min(d, max_1hop) stored entries and d once per entry; more than max_2hop candidates keep the first
+ * max_2hop of their random order.  The reference's pass order is the caller's: items (both calls), then users -- the item
+ * fill reads user lists still in log order, the user fill reads item lists as the item pass left them. */
+int score_graph_build_2hop(const score_graph_build_t* g, int32_t item_side, int64_t* off2, int32_t* nbr2, int32_t* deg2,
+                           int64_t cap2, int64_t* total, void* temp, int64_t temp_bytes, void* stream);
+
 /* ---- "next" row f4: ranking metrics of an evaluation pass on the device ----------------------- */
 
 /* get_ranking_quality (train_score.py:104-142) without the host round trip of the predictions:

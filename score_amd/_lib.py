@@ -83,6 +83,15 @@ class PointLogStore(C.Structure):
                 ("per_line", C.c_int32), ("hist_max_len", C.c_int32)]
 
 
+class GraphBuild(C.Structure):
+    """score_graph_build_t (struct_bytes is its own size check, like PointStore's)"""
+    _fields_ = [("struct_bytes", C.c_int64), ("uid", C.c_void_p), ("iid", C.c_void_p), ("t_idx", C.c_void_p),
+                ("n_events", C.c_int64)] + \
+               [(n, C.c_int32) for n in ("n_users", "n_items", "time_slice_num", "max_1hop", "max_2hop", "reserved")] + \
+               [("seed", C.c_uint64)] + \
+               [(n, C.c_void_p) for n in ("user_off1", "user_nbr1", "item_off1", "item_nbr1")]
+
+
 class AdamTable(C.Structure):
     """score_adam_table_t"""
     _fields_ = [("p", C.c_void_p), ("m", C.c_void_p), ("v", C.c_void_p), ("g", C.c_void_p), ("n_rows", C.c_int64),
@@ -126,6 +135,10 @@ _SIGS = {
     "score_point_hist_build": [c_i, c_i, c_i, c_i, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
                                C.c_void_p, c_i, c_i, C.c_void_p, C.c_int64, C.c_void_p],
     "score_point_hist_temp_bytes": [C.c_int64],
+    "score_graph_build_temp_bytes": [C.c_int64, C.c_int32, C.c_int32, C.c_int32],
+    "score_graph_build_1hop": [C.POINTER(GraphBuild), C.c_void_p, C.c_int64, C.c_void_p],
+    "score_graph_build_2hop": [C.POINTER(GraphBuild), C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64,
+                               C.POINTER(C.c_int64), C.c_void_p, C.c_int64, C.c_void_p],
     "score_param_layout": [C.POINTER(Config), C.POINTER(ParamEntry), C.c_int32, C.POINTER(C.c_int64),
                            C.POINTER(C.c_int64)],
     "score_workspace_layout": [C.POINTER(Config), C.c_int32, C.POINTER(Workspace)],

@@ -104,14 +104,15 @@ TMALL = dict(obj_per_time_slice=10, time_slice_num=12, graph_time_slice_num=14, 
              eval_batch_size=100, train_neg=1, test_neg=99, max_1hop=10, max_2hop=100)
 
 
-def tmall_pipeline(log, seed=11):
+def tmall_pipeline(log, seed=11, build="host", draws="stream"):
     """Raw Tmall log -> (TemporalGraph, remap dict, {'train' | 'validation' | 'test': target lines}).  Train
-    lines carry 1 negative (train_score.py:18), validation / test lines 99 (:19)."""
+    lines carry 1 negative (train_score.py:18), validation / test lines 99 (:19).  build / draws: TemporalGraph.from_log's."""
     from .graph import TemporalGraph
     r = remap_tmall_log(log)
     c = TMALL
     g = TemporalGraph.from_log(r["uid"], r["iid"], r["t_idx"], r["n_users"], r["n_items"], c["graph_time_slice_num"],
-                               r["user_rows"], r["item_rows"], max_1hop=c["max_1hop"], max_2hop=c["max_2hop"], seed=seed)
+                               r["user_rows"], r["item_rows"], max_1hop=c["max_1hop"], max_2hop=c["max_2hop"], seed=seed,
+                               build=build, draws=draws)
     targets = {}
     for name, pt, neg in (("train", c["pred_time_train"], c["train_neg"]),
                           ("validation", c["pred_time_validation"], c["test_neg"]),

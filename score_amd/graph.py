@@ -3,7 +3,8 @@
 Replaces, for the training loop, the reference's MongoDB documents (code/graph_storage.py:78-246:
 per entity and time slice a 1-hop list, a sampled 2-hop list) and its loader processes
 (code/score/graph_loader.py:279-402).  The graph is built once on the host (it is preprocessing in the
-reference too), lives in HBM as CSR, and every batch is assembled by one HIP launch
+reference too) or, with from_log(build="device"), on the device from the uploaded log (csrc/graphbuild.hip), lives in HBM as
+CSR, and every batch is assembled by one HIP launch
 (score_batch_assemble, include/score_hip.h) into the int32 tensors score.py:21-30 feeds on.
 """
 import ctypes as C
@@ -23,12 +24,40 @@ def _csr(lists_per_cell):
     return off, nbr
 
 
+# ---- the per-cell draw rule (from_log(draws="cell"); csrc/graphbuild.hip evaluates the same) -----------------------------
+_G = np.uint64(0x9E3779B97F4A7C15)
+TAG_ITEM_SHUFFLE, TAG_ITEM_SAMPLE, TAG_USER_SHUFFLE, TAG_USER_SAMPLE = 0, 1, 2, 3
+
+
+def _mix(z):
+    """splitmix64's finaliser on a uint64 array (wrapping), what hash_uniform in csrc/common.h uses"""
+    z = (z ^ (z >> np.uint64(30))) * np.uint64(0xBF58476D1CE4E5B9)
+    z = (z ^ (z >> np.uint64(27))) * np.uint64(0x94D049BB133111EB)
+    return z ^ (z >> np.uint64(31))
+
+
+def _cell_keys(seed, tag, c, j):
+    """key(seed, tag, c, j) = mix(mix(seed + G * ((tag << 40) + c + 1)) + G * (j + 1)) >> 32 for arrays c (cell = e * S + t)
+    and j (position) -> uint32.  A draw depends on nothing but its own cell and position."""
+    c, j = np.asarray(c).astype(np.uint64), np.asarray(j).astype(np.uint64)
+    with np.errstate(over="ignore"):
+        h = _mix(np.uint64(int(seed) & 0xFFFFFFFFFFFFFFFF) + _G * (np.uint64(int(tag) << 40) + c + np.uint64(1)))
+        return (_mix(h + _G * (j + np.uint64(1))) >> np.uint64(32)).astype(np.uint32)
+
+
+def _random_order(seed, tag, cell, pos):
+    """Entries (cell, pos), sorted by cell then pos, in every cell's random order: the permutation that sorts them by
+    (cell, key, pos) -- a stable argsort of the keys inside each cell."""
+    return np.lexsort((pos, _cell_keys(seed, tag, cell, pos), cell))
+
+
 class TemporalGraph(object):
     """CSR over (entity, slice) for both sides + feature rows.  Ids: users 1..U, items U+1..U+I
     (feateng_tmall.py:72-101)."""
 
     def __init__(self, n_users, n_items, time_slice_num, user_csr, item_csr, user_rows, item_rows):
         self.U, self.I, self.S = int(n_users), int(n_items), int(time_slice_num)
+        self._built = None                                         # from_log(build="device"): the arrays as device tensors
         self.user_csr, self.item_csr = user_csr, item_csr          # dicts: off1, nbr1, off2, nbr2
         self.user_rows = np.ascontiguousarray(user_rows, dtype=np.int32)
         self.item_rows = np.ascontiguousarray(item_rows, dtype=np.int32)
@@ -36,6 +65,27 @@ class TemporalGraph(object):
         self.Fu, self.Fi = self.user_rows.shape[1], self.item_rows.shape[1]
         self._dev = None
         self.user_degrees = self.item_degrees = None      # mode 'is': degree behind every 2-hop entry (aligned with nbr2)
+
+    # ---- host arrays: a device-built graph downloads them on first access ---------------
+    def _download(self):
+        b, self._downloaded = self._built, True
+        for p in ("u", "i"):
+            n1, n2 = int(b[p + "_off1"][-1]), int(b[p + "_off2"][-1])
+            self._host[p] = dict(off1=b[p + "_off1"].cpu().numpy(), nbr1=b[p + "_nbr1"][:n1].cpu().numpy(),
+                                 off2=b[p + "_off2"].cpu().numpy(), nbr2=b[p + "_nbr2"][:n2].cpu().numpy())
+            self._host[p + "deg"] = b[p + "_deg2"][:n2].cpu().numpy()
+
+    def _host_get(self, key):
+        if self._host.get(key) is None and self._built is not None and not self.__dict__.get("_downloaded"):
+            self._download()
+        return self._host.get(key)
+
+    user_csr = property(lambda self: self._host_get("u"), lambda self, v: self.__dict__.setdefault("_host", {}).__setitem__("u", v))
+    item_csr = property(lambda self: self._host_get("i"), lambda self, v: self.__dict__.setdefault("_host", {}).__setitem__("i", v))
+    user_degrees = property(lambda self: self._host_get("udeg"),
+                            lambda self, v: self.__dict__.setdefault("_host", {}).__setitem__("udeg", v))
+    item_degrees = property(lambda self: self._host_get("ideg"),
+                            lambda self, v: self.__dict__.setdefault("_host", {}).__setitem__("ideg", v))
 
     # ---- construction -----------------------------------------------------------------
     @classmethod
@@ -57,7 +107,7 @@ class TemporalGraph(object):
 
     @classmethod
     def from_log(cls, uid, iid, t_idx, n_users, n_items, time_slice_num, user_rows, item_rows,
-                 max_1hop=10, max_2hop=100, seed=11):
+                 max_1hop=10, max_2hop=100, seed=11, build="host", draws="stream", device=None):
         """From a remapped behaviour log, as GraphStore does (graph_storage.py:93-128 construct_coll_1hop,
         :130-246 construct_coll_2hop; pinned by tests/golden/g5_graph_store.npz, documents written by the
         reference itself):
@@ -70,7 +120,24 @@ class TemporalGraph(object):
             it, the degree of the neighbour each entry came through (what mode 'is' weights by);
           items first, then users (:147-189, :193-237): the user pass cuts item lists the item pass has
             already permuted.
-        The random choices come from `seed`, not from the reference's `random` / `np.random` streams."""
+        The random choices come from `seed`, not from the reference's `random` / `np.random` streams.
+        draws: "stream" (the default) takes them from ONE sequential PCG64 stream in cell order; "cell" from the per-cell,
+          counter-based rule of _cell_keys: a shuffle / a down-sample is "the random order" of its positions -- the positions
+          sorted by (key, position) --, so no draw depends on another, and events with an id or slice outside its range
+          are dropped.  The two give different (equally valid) graphs wherever a cap is hit, the same one where none is.
+        build: "host" numpy; "device" (needs draws="cell" and a GPU) csrc/graphbuild.hip: the same arrays, word for word,
+          built in HBM from the uploaded log -- the graph is born resident (to_device uploads nothing) and downloads its
+          arrays the first time cell(), save() or the degree lists are asked for."""
+        if build not in ("host", "device") or draws not in ("stream", "cell"):
+            raise ValueError("build is 'host' or 'device', draws 'stream' or 'cell': got %r, %r" % (build, draws))
+        if build == "device":
+            if draws != "cell":
+                raise ValueError("build='device' needs draws='cell': the sequential stream of draws='stream' has no device form")
+            return cls._from_log_device(uid, iid, t_idx, n_users, n_items, time_slice_num, user_rows, item_rows,
+                                        max_1hop, max_2hop, seed, device)
+        if draws == "cell":
+            return cls._from_log_cell(uid, iid, t_idx, n_users, n_items, time_slice_num, user_rows, item_rows,
+                                      max_1hop, max_2hop, seed)
         rng = np.random.Generator(np.random.PCG64(seed))
         S, U, I = int(time_slice_num), int(n_users), int(n_items)
         uid, iid, t_idx = (np.asarray(a).astype(np.int64) for a in (uid, iid, t_idx))
@@ -149,6 +216,136 @@ class TemporalGraph(object):
                 dict(off1=io1, nbr1=in1, off2=io2, nbr2=in2), user_rows, item_rows)
         g.user_degrees, g.item_degrees = udeg, ideg                      # aligned with nbr2 (same offsets)
         return g
+
+    @classmethod
+    def _from_log_cell(cls, uid, iid, t_idx, n_users, n_items, time_slice_num, user_rows, item_rows, max_1hop, max_2hop, seed):
+        """from_log(draws="cell") on the host, vectorised: no draw depends on another, so there is no loop over cells."""
+        S, U, I = int(time_slice_num), int(n_users), int(n_items)
+        max_1hop, max_2hop = int(max_1hop), int(max_2hop)
+        uid, iid, t_idx = (np.asarray(a).astype(np.int64).ravel() for a in (uid, iid, t_idx))
+        ok = (uid >= 1) & (uid <= U) & (iid >= U + 1) & (iid <= U + I) & (t_idx >= 0) & (t_idx < S)
+        uid, iid, t_idx = uid[ok], iid[ok], t_idx[ok]
+
+        def one_hop(ent0, nbr, n_ent):
+            key = ent0 * S + t_idx
+            order = np.argsort(key, kind="stable")
+            off = np.zeros(n_ent * S + 1, dtype=np.int64)
+            np.cumsum(np.bincount(key, minlength=n_ent * S), out=off[1:])
+            return off, nbr[order].astype(np.int32)
+
+        def shuffle(off, nbr, tag):
+            """every cell with more than max_1hop entries: replaced, whole, by itself in the random order"""
+            len1 = off[1:] - off[:-1]
+            over = np.nonzero(len1 > max_1hop)[0]
+            if len(over) == 0:
+                return
+            lens = len1[over]
+            cell = np.repeat(over, lens)
+            pos = np.arange(int(lens.sum()), dtype=np.int64) - np.repeat(np.cumsum(lens) - lens, lens)
+            idx = off[cell] + pos
+            nbr[idx] = nbr[idx[_random_order(seed, tag, cell, pos)]]
+
+        def two_hop(own_off, own_nbr, other_off, other_nbr, other_base, n_ent, tag):
+            ncell = n_ent * S
+            len1 = np.minimum(own_off[1:] - own_off[:-1], max_1hop)                  # the first max_1hop neighbours
+            cell1 = np.repeat(np.arange(ncell, dtype=np.int64), len1)
+            pos1 = np.arange(int(len1.sum()), dtype=np.int64) - np.repeat(np.cumsum(len1) - len1, len1)
+            x = own_nbr[own_off[cell1] + pos1].astype(np.int64)
+            oc = (x - other_base) * S + (cell1 % S)
+            d = other_off[oc + 1] - other_off[oc]
+            L = np.where(d > 1, np.minimum(d, max_1hop), 0)
+            tot = int(L.sum())
+            within = np.arange(tot, dtype=np.int64) - np.repeat(np.cumsum(L) - L, L)
+            vals = other_nbr[np.repeat(other_off[oc], L) + within]
+            degs = np.repeat(d, L).astype(np.int32)
+            lens = np.bincount(np.repeat(cell1, L), minlength=ncell).astype(np.int64)
+            over = np.nonzero(lens > max_2hop)[0]
+            if len(over):
+                coff = np.cumsum(lens) - lens
+                ol = lens[over]
+                cell = np.repeat(over, ol)
+                pos = np.arange(int(ol.sum()), dtype=np.int64) - np.repeat(np.cumsum(ol) - ol, ol)
+                idx = coff[cell] + pos
+                src = np.arange(tot, dtype=np.int64)
+                src[idx] = idx[_random_order(seed, tag, cell, pos)]                  # the candidates in random order ..
+                keep = np.ones(tot, dtype=bool)
+                keep[idx] = pos < max_2hop                                           # .. of which the first max_2hop stay
+                vals, degs = vals[src[keep]], degs[src[keep]]
+                lens = np.minimum(lens, max_2hop)
+            off = np.zeros(ncell + 1, dtype=np.int64)
+            np.cumsum(lens, out=off[1:])
+            return off, vals.astype(np.int32), degs.astype(np.int32)
+        uo1, un1 = one_hop(uid - 1, iid, U)
+        io1, in1 = one_hop(iid - U - 1, uid, I)
+        shuffle(io1, in1, TAG_ITEM_SHUFFLE)
+        io2, in2, ideg = two_hop(io1, in1, uo1, un1, 1, I, TAG_ITEM_SAMPLE)           # reads user lists still in log order
+        shuffle(uo1, un1, TAG_USER_SHUFFLE)
+        uo2, un2, udeg = two_hop(uo1, un1, io1, in1, U + 1, U, TAG_USER_SAMPLE)       # reads item lists as the item pass left them
+        g = cls(U, I, S, dict(off1=uo1, nbr1=un1, off2=uo2, nbr2=un2),
+                dict(off1=io1, nbr1=in1, off2=io2, nbr2=in2), user_rows, item_rows)
+        g.user_degrees, g.item_degrees = udeg, ideg
+        return g
+
+    @classmethod
+    def _from_log_device(cls, uid, iid, t_idx, n_users, n_items, time_slice_num, user_rows, item_rows, max_1hop, max_2hop,
+                         seed, device=None, timings=None):
+        """from_log(build="device"): score_graph_build_1hop, then per side score_graph_build_2hop twice (count, fill), items
+        first.  timings: a dict that receives the seconds of the three stages (synchronised; tools/graph_build_time.py)."""
+        if not torch.cuda.is_available():
+            raise RuntimeError("TemporalGraph.from_log(build='device') needs an AMD GPU (HIP); build='host' does not")
+        import time
+        dev = torch.device(device if device is not None else "cuda:%d" % torch.cuda.current_device())
+        lib = _lib.load()
+        S, U, I = int(time_slice_num), int(n_users), int(n_items)
+        up = lambda a: torch.from_numpy(np.ascontiguousarray(np.asarray(a).ravel(), dtype=np.int32)).to(dev)
+        with torch.cuda.device(dev):
+            d_uid, d_iid, d_t = up(uid), up(iid), up(t_idx)
+            n = int(d_uid.numel())
+            if n == 0 or d_iid.numel() != n or d_t.numel() != n:
+                raise ValueError("from_log(build='device'): uid, iid and t_idx must be non-empty and of one length")
+            temp_bytes = int(lib.score_graph_build_temp_bytes(n, U, I, S))
+            if temp_bytes < 0:
+                _lib.check(-2, "score_graph_build_temp_bytes")
+            temp = torch.empty((temp_bytes,), dtype=torch.uint8, device=dev)
+            b = {"u_off1": torch.empty((U * S + 1,), dtype=torch.int64, device=dev),
+                 "i_off1": torch.empty((I * S + 1,), dtype=torch.int64, device=dev),
+                 "u_nbr1": torch.empty((n,), dtype=torch.int32, device=dev),
+                 "i_nbr1": torch.empty((n,), dtype=torch.int32, device=dev)}
+            a = _lib.GraphBuild(C.sizeof(_lib.GraphBuild), _ptr(d_uid), _ptr(d_iid), _ptr(d_t), n, U, I, S, int(max_1hop),
+                                int(max_2hop), 0, int(seed) & 0xFFFFFFFFFFFFFFFF, _ptr(b["u_off1"]), _ptr(b["u_nbr1"]),
+                                _ptr(b["i_off1"]), _ptr(b["i_nbr1"]))
+            stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+            clock = [time.perf_counter()]
+
+            def lap(name):
+                if timings is not None:
+                    torch.cuda.synchronize(dev)
+                    clock.append(time.perf_counter())
+                    timings[name] = timings.get(name, 0.0) + clock[-1] - clock[-2]
+            if timings is not None:
+                torch.cuda.synchronize(dev)
+                clock[0] = time.perf_counter()
+            _lib.check(lib.score_graph_build_1hop(C.byref(a), _ptr(temp), temp_bytes, stream), "score_graph_build_1hop")
+            lap("sort")
+            for p, item_side in (("i", 1), ("u", 0)):             # the reference's pass order: items, then users
+                ncell = (I if item_side else U) * S
+                b[p + "_off2"] = torch.empty((ncell + 1,), dtype=torch.int64, device=dev)
+                total = C.c_int64(0)
+                _lib.check(lib.score_graph_build_2hop(C.byref(a), item_side, _ptr(b[p + "_off2"]), None, None, 0, C.byref(total),
+                                                      _ptr(temp), temp_bytes, stream), "score_graph_build_2hop (count)")
+                lap("shuffle_count")
+                cap = max(int(total.value), 1)                     # (an empty list still needs a valid pointer)
+                b[p + "_nbr2"] = torch.zeros((cap,), dtype=torch.int32, device=dev)
+                b[p + "_deg2"] = torch.zeros((cap,), dtype=torch.int32, device=dev)
+                _lib.check(lib.score_graph_build_2hop(C.byref(a), item_side, _ptr(b[p + "_off2"]), _ptr(b[p + "_nbr2"]),
+                                                      _ptr(b[p + "_deg2"]), cap, None, _ptr(temp), temp_bytes, stream),
+                           "score_graph_build_2hop (fill)")
+                lap("fill")
+            g = cls(U, I, S, None, None, user_rows, item_rows)
+            b["user_rows"], b["item_rows"] = torch.from_numpy(g.user_rows).to(dev), torch.from_numpy(g.item_rows).to(dev)
+            torch.cuda.current_stream(dev).synchronize()           # (temp and the uploaded log are released behind this)
+        g._built, g._built_device = b, dev
+        return g.to_device(dev)
 
     @classmethod
     def _from_log_lists(cls, uid, iid, t_idx, n_users, n_items, time_slice_num, user_rows, item_rows,
@@ -231,22 +428,26 @@ class TemporalGraph(object):
         'is' degree-weighted (graph_loader.py:94-167; needs the degree lists from_log / from_padded keep)."""
         if mode not in ("rs", "is"):
             raise ValueError("WRONG GRAPH_HANDLER MODE: {}".format(mode))          # graph_loader.py:248
-        if mode == "is" and (self.user_degrees is None or self.item_degrees is None):
+        if mode == "is" and self._built is None and (self.user_degrees is None or self.item_degrees is None):
             raise ValueError("mode 'is' needs the 2-hop degree lists")
         if not torch.cuda.is_available():
             raise RuntimeError("TemporalGraph.to_device needs an AMD GPU (HIP); batch assembly has no CPU path")
         dev = torch.device(device if device is not None else "cuda:%d" % torch.cuda.current_device())
         t = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)
-        d = {"u_" + k: t(v) for k, v in self.user_csr.items()}
-        d.update({"i_" + k: t(v) for k, v in self.item_csr.items()})
-        # an empty neighbour array still needs a valid pointer
-        for k in list(d):
-            if d[k].numel() == 0:
-                d[k] = torch.zeros((1,), dtype=d[k].dtype, device=dev)
-        d["user_rows"], d["item_rows"] = t(self.user_rows), t(self.item_rows)
-        if mode == "is":
-            for k, a in (("u_deg2", self.user_degrees), ("i_deg2", self.item_degrees)):
-                d[k] = t(np.asarray(a, dtype=np.int32)) if len(a) else torch.zeros((1,), dtype=torch.int32, device=dev)
+        if self._built is not None and dev == self._built_device:
+            # built on this device (from_log(build="device")): the arrays are there already, the degree lists included
+            d = {k: v for k, v in self._built.items() if mode == "is" or not k.endswith("_deg2")}
+        else:
+            d = {"u_" + k: t(v) for k, v in self.user_csr.items()}
+            d.update({"i_" + k: t(v) for k, v in self.item_csr.items()})
+            # an empty neighbour array still needs a valid pointer
+            for k in list(d):
+                if d[k].numel() == 0:
+                    d[k] = torch.zeros((1,), dtype=d[k].dtype, device=dev)
+            d["user_rows"], d["item_rows"] = t(self.user_rows), t(self.item_rows)
+            if mode == "is":
+                for k, a in (("u_deg2", self.user_degrees), ("i_deg2", self.item_degrees)):
+                    d[k] = t(np.asarray(a, dtype=np.int32)) if len(a) else torch.zeros((1,), dtype=torch.int32, device=dev)
         self._dev = d
         self.device = dev
         self.mode = mode
