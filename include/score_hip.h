@@ -881,6 +881,62 @@ int score_graph_build_1hop(const score_graph_build_t* g, void* temp, int64_t tem
 int score_graph_build_2hop(const score_graph_build_t* g, int32_t item_side, int64_t* off2, int32_t* nbr2, int32_t* deg2,
                            int64_t cap2, int64_t* total, void* temp, int64_t temp_bytes, void* stream);
 
+/* ---- the target lines from the behaviour log, on the device (csrc/targetgen.hip) ---- */
+
+/* What dataprep.gen_target_lines(draws="cell") yields (gen_target.py:79-121, with sampling.py:31-37's down-sampling folded
+ * in), as device arrays.  uid / iid / t_idx int32 [n_events]: the remapped log; an event whose uid lies outside 1 .. n_users,
+ * whose iid outside n_users + 1 .. n_users + n_items or whose slice is negative is dropped.  User u gets a line iff it has an
+ * event in slice pred_time and one in [start_time, pred_time) and, where sample_factor > 1,
+ * (key(seed, 6, u, 0) * sample_factor) >> 32 == 0 (sample_factor 0 or 1: no down-sampling).  Lines come in ascending user id:
+ * line_user int32 [n_lines], line_items int32 [n_lines, 1 + neg_sample_num] = the user's first item of slice pred_time in log
+ * order, then negative j = n_users + 1 + ((key(seed, 4, u, j) * n_items) >> 32), or, with a pop list (pop_items != NULL,
+ * device int32 [n_pop], n_pop > 0 wherever a line is filled), pop_items[(key(seed, 5, u, j) * n_pop) >> 32]; key is the
+ * graph build's, its cell the user id, the products 64-bit.  struct_bytes = sizeof(score_target_build_t): the calls refuse any
+ * other value.  Limits: n_events, n_users + n_items < 2^31 and 1 + neg_sample_num <= 4096 (SCORE_E_SHAPE beyond); temp:
+ * score_target_build_temp_bytes (SCORE_E_WORKSPACE); both before any launch.  One workspace serves both calls of a build.
+ * Tile sizes (a test puts event counts at their edges): the prefix sum works on SCORE_TARGET_SCAN_TILE words per workgroup,
+ * score_sort_pairs on SCORE_TARGET_SORT_TILE pairs. */
+#define SCORE_TARGET_SCAN_TILE 4096
+#define SCORE_TARGET_SORT_TILE 8192
+typedef struct {
+  int64_t struct_bytes;
+  const int32_t* uid; const int32_t* iid; const int32_t* t_idx;
+  int64_t n_events;
+  int32_t n_users, n_items, start_time, pred_time, neg_sample_num, sample_factor;
+  uint64_t seed;
+  const int32_t* pop_items; int64_t n_pop;
+} score_target_build_t;
+
+int64_t score_target_build_temp_bytes(int64_t n_events, int32_t n_users);
+
+/* In two calls.
+ *   line_user == NULL: the events of slice pred_time are sorted by user (a stable score_sort_pairs on (uid, log position), every
+ *     other event behind a sink key, so a run's head is the user's first event of the slice), users with history are marked
+ *     by plain stores of one constant, the heads that get a line are flagged and scanned to their line index, and *n_lines
+ *     (host) receives the count.  Waits for the stream once.
+ *   line_user != NULL: one kernel evaluates the keys and fills line_user / line_items of lines 0 .. min(n_lines, cap_lines) - 1
+ *     from what the first call left in temp, 16 bytes per store where a line's words allow it; nothing is written at or past
+ *     line cap_lines.  No host wait.
+ * No atomics, no workgroup waits on another: the output is a pure function of the input. */
+int score_target_build(const score_target_build_t* a, int32_t* line_user, int32_t* line_items, int64_t cap_lines,
+                       int64_t* n_lines, void* temp, int64_t temp_bytes, void* stream);
+
+/* The popular-item list (gen_target.py:277-290, dataprep.gen_pop_items): the ids n_users + 1 + i, ascending, of the items i
+ * with at least pop_standard non-empty slices in item_off1 int64 [n_items * time_slice_num + 1] (a graph's item side) and
+ * id <= max_iid.  struct_bytes = sizeof(score_pop_items_t).  Two calls like score_target_build: pop_items == NULL counts
+ * (flags, a scan, *n_pop on the host: one stream wait), pop_items != NULL compacts in id order into int32 [cap_pop], writing
+ * nothing at or past cap_pop.  n_items * time_slice_num, n_users + n_items < 2^31 (SCORE_E_SHAPE); temp:
+ * score_pop_items_temp_bytes (SCORE_E_WORKSPACE). */
+typedef struct {
+  int64_t struct_bytes;
+  const int64_t* item_off1;
+  int32_t n_users, n_items, time_slice_num, pop_standard, max_iid, reserved;
+} score_pop_items_t;
+
+int64_t score_pop_items_temp_bytes(int32_t n_items);
+int score_pop_items(const score_pop_items_t* a, int32_t* pop_items, int64_t cap_pop, int64_t* n_pop, void* temp,
+                    int64_t temp_bytes, void* stream);
+
 /* ---- "next" row f4: ranking metrics of an evaluation pass on the device ----------------------- */
 
 /* get_ranking_quality (train_score.py:104-142) without the host round trip of the predictions:

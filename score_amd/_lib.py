@@ -92,6 +92,23 @@ class GraphBuild(C.Structure):
                [(n, C.c_void_p) for n in ("user_off1", "user_nbr1", "item_off1", "item_nbr1")]
 
 
+class TargetBuild(C.Structure):
+    """score_target_build_t (struct_bytes is its own size check, like GraphBuild's)"""
+    _fields_ = [("struct_bytes", C.c_int64), ("uid", C.c_void_p), ("iid", C.c_void_p), ("t_idx", C.c_void_p),
+                ("n_events", C.c_int64)] + \
+               [(n, C.c_int32) for n in ("n_users", "n_items", "start_time", "pred_time", "neg_sample_num", "sample_factor")] + \
+               [("seed", C.c_uint64), ("pop_items", C.c_void_p), ("n_pop", C.c_int64)]
+
+
+class PopItems(C.Structure):
+    """score_pop_items_t (struct_bytes is its own size check)"""
+    _fields_ = [("struct_bytes", C.c_int64), ("item_off1", C.c_void_p)] + \
+               [(n, C.c_int32) for n in ("n_users", "n_items", "time_slice_num", "pop_standard", "max_iid", "reserved")]
+
+
+TARGET_SCAN_TILE, TARGET_SORT_TILE = 4096, 8192      # SCORE_TARGET_SCAN_TILE / SCORE_TARGET_SORT_TILE
+
+
 class AdamTable(C.Structure):
     """score_adam_table_t"""
     _fields_ = [("p", C.c_void_p), ("m", C.c_void_p), ("v", C.c_void_p), ("g", C.c_void_p), ("n_rows", C.c_int64),
@@ -139,6 +156,11 @@ _SIGS = {
     "score_graph_build_1hop": [C.POINTER(GraphBuild), C.c_void_p, C.c_int64, C.c_void_p],
     "score_graph_build_2hop": [C.POINTER(GraphBuild), C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64,
                                C.POINTER(C.c_int64), C.c_void_p, C.c_int64, C.c_void_p],
+    "score_target_build_temp_bytes": [C.c_int64, C.c_int32],
+    "score_target_build": [C.POINTER(TargetBuild), C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(C.c_int64), C.c_void_p,
+                           C.c_int64, C.c_void_p],
+    "score_pop_items_temp_bytes": [C.c_int32],
+    "score_pop_items": [C.POINTER(PopItems), C.c_void_p, C.c_int64, C.POINTER(C.c_int64), C.c_void_p, C.c_int64, C.c_void_p],
     "score_param_layout": [C.POINTER(Config), C.POINTER(ParamEntry), C.c_int32, C.POINTER(C.c_int64),
                            C.POINTER(C.c_int64)],
     "score_workspace_layout": [C.POINTER(Config), C.c_int32, C.POINTER(Workspace)],

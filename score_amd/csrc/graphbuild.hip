@@ -27,27 +27,15 @@
 // The scan is reduce-then-scan (block sums, one workgroup over the block sums, a second pass): no workgroup waits on
 // another.  Nothing here is atomic: every array is a pure function of (log, caps, seed).
 #include "common.h"
+#include "cellkey.h"
+#include "scan.h"
 
 #define GB_THREADS 256
 
 namespace {
 
-constexpr uint64_t GB_G = 0x9E3779B97F4A7C15ull;
 constexpr int GB_MAX_CAND = 4096;                        // max_1hop^2 at most
-constexpr int SCAN_T = 256, SCAN_E = 16, SCAN_CHUNK = SCAN_T * SCAN_E, SCAN_TOP_T = 1024;
 constexpr int FILL_WAVES = 2;
-
-__device__ __forceinline__ uint64_t gb_mix(uint64_t z) {
-  z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-  z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-  return z ^ (z >> 31);
-}
-__device__ __forceinline__ uint64_t gb_cell_hash(uint64_t seed, uint64_t tag, uint64_t c) {
-  return gb_mix(seed + GB_G * ((tag << 40) + c + 1ull));
-}
-__device__ __forceinline__ uint32_t gb_key(uint64_t cell_hash, uint64_t j) {
-  return (uint32_t)(gb_mix(cell_hash + GB_G * (j + 1ull)) >> 32);
-}
 
 struct Side {                       // one side's view of the build: its own lists and the other side's
   int64_t* off1; int32_t* nbr1;
@@ -94,85 +82,6 @@ __global__ __launch_bounds__(GB_THREADS) void gb_segments_kernel(const uint32_t*
     }
     if (i <= ncell) off1[i] = gb_lower_bound(keys, n, (uint32_t)i);
   }
-}
-
-// ------------------------------------------------------------------------------------------------------------------ scan
-// out[i] = x[0] + .. + x[i - 1] for i = 0 .. n (n + 1 words), x >= 0: block sums, one workgroup over them, second pass
-template <int T>
-__device__ __forceinline__ int64_t gb_block_incl_scan(int64_t v, int64_t* s, int tid) {
-  s[tid] = v;
-  __syncthreads();
-  for (int off = 1; off < T; off <<= 1) {
-    const int64_t y = tid >= off ? s[tid - off] : 0;
-    __syncthreads();
-    s[tid] += y;
-    __syncthreads();
-  }
-  const int64_t r = s[tid];
-  __syncthreads();                        // (s may be written again by the next call)
-  return r;
-}
-
-__global__ __launch_bounds__(SCAN_T) void gb_scan_reduce_kernel(const int32_t* __restrict__ x, int64_t n,
-                                                               int64_t* __restrict__ bsum) {
-  __shared__ int64_t s[SCAN_T];
-  const int tid = threadIdx.x;
-  const int64_t base = (int64_t)blockIdx.x * SCAN_CHUNK;
-  int64_t v = 0;
-#pragma unroll
-  for (int j = 0; j < SCAN_E; ++j) {
-    const int64_t i = base + j * SCAN_T + tid;
-    v += i < n ? (int64_t)x[i] : 0;
-  }
-  const int64_t incl = gb_block_incl_scan<SCAN_T>(v, s, tid);
-  if (tid == SCAN_T - 1) bsum[blockIdx.x] = incl;
-}
-
-// bsum[b] <- sum of the blocks before b; *total <- the sum of all
-__global__ __launch_bounds__(SCAN_TOP_T) void gb_scan_top_kernel(int64_t* __restrict__ bsum, int64_t nb,
-                                                                int64_t* __restrict__ total) {
-  __shared__ int64_t s[SCAN_TOP_T];
-  const int tid = threadIdx.x;
-  const int64_t per = (nb + SCAN_TOP_T - 1) / SCAN_TOP_T;
-  const int64_t b0 = tid * per, b1 = b0 + per < nb ? b0 + per : nb;
-  int64_t v = 0;
-  for (int64_t b = b0; b < b1; ++b) v += bsum[b];
-  const int64_t incl = gb_block_incl_scan<SCAN_TOP_T>(v, s, tid);
-  int64_t run = incl - v;
-  for (int64_t b = b0; b < b1; ++b) { const int64_t c = bsum[b]; bsum[b] = run; run += c; }
-  if (tid == SCAN_TOP_T - 1) *total = incl;
-}
-
-__global__ __launch_bounds__(SCAN_T) void gb_scan_write_kernel(const int32_t* __restrict__ x, int64_t n,
-                                                              const int64_t* __restrict__ bsum, int64_t* __restrict__ out) {
-  __shared__ int64_t s[SCAN_T];
-  const int tid = threadIdx.x;
-  const int64_t base = (int64_t)blockIdx.x * SCAN_CHUNK + (int64_t)tid * SCAN_E;      // SCAN_E consecutive words per thread
-  int32_t c[SCAN_E];
-  int64_t v = 0;
-#pragma unroll
-  for (int j = 0; j < SCAN_E; ++j) {
-    c[j] = base + j < n ? x[base + j] : 0;
-    v += c[j];
-  }
-  int64_t run = gb_block_incl_scan<SCAN_T>(v, s, tid) - v + bsum[blockIdx.x];
-#pragma unroll
-  for (int j = 0; j < SCAN_E; ++j) {
-    if (base + j < n) out[base + j] = run;
-    run += c[j];
-  }
-}
-
-// out[0 .. n] <- exclusive prefix of x[0 .. n - 1] and the total (out[n]); bsum: cdiv(n, SCAN_CHUNK) words
-int gb_scan(const int32_t* x, int64_t n, int64_t* bsum, int64_t* out, hipStream_t s) {
-  const int64_t nb = cdiv64(n, SCAN_CHUNK);
-  hipLaunchKernelGGL(gb_scan_reduce_kernel, dim3((unsigned)nb), dim3(SCAN_T), 0, s, x, n, bsum);
-  SCORE_CHECK_LAUNCH();
-  hipLaunchKernelGGL(gb_scan_top_kernel, dim3(1), dim3(SCAN_TOP_T), 0, s, bsum, nb, out + n);
-  SCORE_CHECK_LAUNCH();
-  hipLaunchKernelGGL(gb_scan_write_kernel, dim3((unsigned)nb), dim3(SCAN_T), 0, s, x, n, bsum, out);
-  SCORE_CHECK_LAUNCH();
-  return 0;
 }
 
 // --------------------------------------------------------------------------------------------------------------- shuffle

@@ -33,6 +33,7 @@
 namespace {
 
 constexpr int TILE = 8192, THREADS = 512, WAVES = 8, EPT = 16, PER_WAVE = TILE / WAVES;   // EPT rounds of 64 keys per wave
+static_assert(TILE == SCORE_TARGET_SORT_TILE, "include/score_hip.h documents the sort's tile: tests put event counts at its edges");
 
 // exclusive prefix of x over the 512 threads of the block (all of them call); sc: 16 words of LDS
 __device__ __forceinline__ uint32_t block_excl_scan(uint32_t x, uint32_t* sc, int tid) {

@@ -1,0 +1,270 @@
+// The target lines every loader iterates over (gen_target.py:79-121; dataprep.gen_target_lines(draws="cell")), the popular-item
+// list (gen_target.py:277-290) and sampling.py:31-37's 1-in-N down-sampling, on the device from the uploaded log.
+//
+// Draws: key(seed, tag, c, j) of cellkey.h with cell c = the line's user id.  tag 4: negative j without a pop list,
+//   n_users + 1 + ((key * n_items) >> 32); tag 5: negative j from the pop list, pop[(key * n_pop) >> 32]; tag 6, j = 0: the
+//   line stays iff (key * sample_factor) >> 32 == 0.  The products are 64-bit.
+//
+// score_target_build, count call:
+//   keys     key = 0-based user of an event of slice pred_time, the sink n_users for every other event (and for an event whose
+//            uid, iid or slice lies outside its range); value = its position in the log.  The same kernel marks the users with
+//            an event in [start_time, pred_time): plain stores of the constant 1 into a zeroed array, so it does not matter
+//            which store lands last.
+//   sort     score_sort_pairs (sort.hip): stable, so the head of a user's run is its first event of the slice in log order.
+//   flags    a head whose user is marked and passes the sample rule gets a line; the scan of the flags is its line index, and
+//            the total goes back to the host (the call's one wait).
+// fill call: a wave takes 64 sorted positions (a lane reads one flag), then the flagged ones in turn, the whole wave on one
+//   line: word 0 the positive, word 1 + j negative j.  The words up to the first 16-byte boundary and behind the last go out
+//   one per lane, those between four per lane.  A line of 1 + neg = 100 words is 400 bytes = 25 * 16, so every such line
+//   starts on a boundary and takes the 16-byte stores alone; a width that is no multiple of 4 words (5, 7, 11, 101 in the
+//   tests) puts line starts 0, 4, 8 and 12 bytes past one.
+// score_pop_items: per item the count of non-empty slices, a flag, the scan, a compaction in id order.
+// No atomics, no workgroup waits on another: every array is a pure function of the input.
+#include "common.h"
+#include "cellkey.h"
+#include "scan.h"
+
+#define TG_THREADS 256
+
+namespace {
+
+static_assert(SCAN_CHUNK == SCORE_TARGET_SCAN_TILE, "the header documents the scan's tile");
+constexpr uint64_t TAG_NEG = 4, TAG_POP = 5, TAG_SAMPLE = 6;
+constexpr int TG_MAX_PER_LINE = 4096;
+
+__global__ __launch_bounds__(TG_THREADS) void tg_zero_kernel(int32_t* __restrict__ x, int64_t n) {
+  for (int64_t i = (int64_t)blockIdx.x * TG_THREADS + threadIdx.x; i < n; i += (int64_t)gridDim.x * TG_THREADS) x[i] = 0;
+}
+
+__global__ __launch_bounds__(TG_THREADS) void tg_keys_kernel(const int32_t* __restrict__ uid, const int32_t* __restrict__ iid,
+                                                            const int32_t* __restrict__ t_idx, int64_t n, int32_t U, int32_t I,
+                                                            int32_t start_time, int32_t pred_time, uint32_t* __restrict__ keys,
+                                                            uint32_t* __restrict__ vals, int32_t* __restrict__ hist) {
+  for (int64_t i = (int64_t)blockIdx.x * TG_THREADS + threadIdx.x; i < n; i += (int64_t)gridDim.x * TG_THREADS) {
+    const int64_t u = (int64_t)uid[i] - 1, it = (int64_t)iid[i] - U - 1;
+    const int32_t t = t_idx[i];
+    const bool ok = u >= 0 && u < U && it >= 0 && it < I && t >= 0;
+    keys[i] = (uint32_t)(ok && t == pred_time ? u : U);
+    vals[i] = (uint32_t)i;
+    if (ok && t >= start_time && t < pred_time) hist[u] = 1;
+  }
+}
+
+// flag[p] = 1 where sorted position p is a head that gets a line, ev[p] = the log position of that event (else -1)
+__global__ __launch_bounds__(TG_THREADS) void tg_flag_kernel(const uint32_t* __restrict__ keys, const uint32_t* __restrict__ vals,
+                                                            const int32_t* __restrict__ hist, int64_t n, int32_t U,
+                                                            int32_t sample_factor, uint64_t seed, int32_t* __restrict__ flag,
+                                                            int32_t* __restrict__ ev) {
+  for (int64_t p = (int64_t)blockIdx.x * TG_THREADS + threadIdx.x; p < n; p += (int64_t)gridDim.x * TG_THREADS) {
+    const uint32_t k = keys[p], v = vals[p];
+    bool keep = k < (uint32_t)U && (p == 0 || keys[p - 1] != k) && (int64_t)v < n && hist[k] != 0;
+    if (keep && sample_factor > 1)
+      keep = (((uint64_t)gb_key(gb_cell_hash(seed, TAG_SAMPLE, (uint64_t)k + 1ull), 0) * (uint64_t)sample_factor) >> 32) == 0;
+    flag[p] = keep ? 1 : 0;
+    ev[p] = keep ? (int32_t)v : -1;
+  }
+}
+
+struct Fill {
+  const int32_t* uid; const int32_t* iid; const int32_t* ev; const int64_t* lidx; const int32_t* pop;
+  int32_t* line_user; int32_t* line_items;
+  int64_t n, cap_lines, n_pop;
+  int32_t U, I, per;
+  uint64_t seed;
+};
+
+__device__ __forceinline__ int32_t tg_word(const Fill& a, uint64_t h, int32_t pos, int32_t w) {
+  if (w == 0) return pos;
+  const uint64_t k = gb_key(h, (uint64_t)(w - 1));
+  return a.pop ? a.pop[(k * (uint64_t)a.n_pop) >> 32] : (int32_t)((int64_t)a.U + 1 + (int64_t)((k * (uint64_t)a.I) >> 32));
+}
+
+__global__ __launch_bounds__(TG_THREADS) void tg_fill_kernel(Fill a) {
+  const int lane = threadIdx.x & 63;
+  const int64_t wave = ((int64_t)blockIdx.x * TG_THREADS + threadIdx.x) >> 6, nwaves = (int64_t)gridDim.x * (TG_THREADS / 64);
+  for (int64_t base = wave * 64; base < a.n; base += nwaves * 64) {
+    const int64_t p = base + lane;
+    uint64_t live = __ballot(p < a.n && a.ev[p] >= 0);
+    while (live) {                                                  // (wave-uniform)
+      const int src = __ffsll((unsigned long long)live) - 1;
+      live &= live - 1;
+      const int64_t v = a.ev[base + src], l = a.lidx[base + src];
+      if (v < 0 || v >= a.n || l < 0 || l >= a.cap_lines) continue;
+      const int32_t u = a.uid[v], pos = a.iid[v];
+      if (u < 1 || u > a.U) continue;                               // (never with the count call's own ev)
+      const uint64_t h = gb_cell_hash(a.seed, a.pop ? TAG_POP : TAG_NEG, (uint64_t)u);
+      int32_t* row = a.line_items + l * a.per;
+      if (lane == 0) a.line_user[l] = u;
+      int32_t head = (int32_t)(((16u - (uint32_t)(reinterpret_cast<uintptr_t>(row) & 15u)) & 15u) >> 2);
+      head = head < a.per ? head : a.per;
+      const int32_t nvec = (a.per - head) >> 2, tail = head + 4 * nvec;
+      if (lane < head) row[lane] = tg_word(a, h, pos, lane);
+      for (int32_t c = lane; c < nvec; c += 64) {
+        const int32_t w = head + 4 * c;
+        int4 x;
+        x.x = tg_word(a, h, pos, w); x.y = tg_word(a, h, pos, w + 1); x.z = tg_word(a, h, pos, w + 2); x.w = tg_word(a, h, pos, w + 3);
+        *reinterpret_cast<int4*>(row + w) = x;
+      }
+      if (tail + lane < a.per) row[tail + lane] = tg_word(a, h, pos, tail + lane);      // (fewer than 4 words)
+    }
+  }
+}
+
+// ------------------------------------------------------------------------------------------------------------- pop items
+__global__ __launch_bounds__(TG_THREADS) void tg_pop_flag_kernel(const int64_t* __restrict__ off1, int32_t U, int32_t I, int32_t S,
+                                                                int32_t pop_standard, int32_t max_iid, int32_t* __restrict__ flag) {
+  for (int64_t i = (int64_t)blockIdx.x * TG_THREADS + threadIdx.x; i < I; i += (int64_t)gridDim.x * TG_THREADS) {
+    const int64_t* o = off1 + i * S;
+    int32_t cnt = 0;
+    int64_t prev = o[0];
+    for (int32_t t = 1; t <= S; ++t) {
+      const int64_t next = o[t];
+      cnt += next > prev ? 1 : 0;
+      prev = next;
+    }
+    flag[i] = (cnt >= pop_standard && (int64_t)U + 1 + i <= (int64_t)max_iid) ? 1 : 0;
+  }
+}
+
+__global__ __launch_bounds__(TG_THREADS) void tg_pop_fill_kernel(const int32_t* __restrict__ flag, const int64_t* __restrict__ idx,
+                                                                int32_t U, int32_t I, int32_t* __restrict__ pop, int64_t cap) {
+  for (int64_t i = (int64_t)blockIdx.x * TG_THREADS + threadIdx.x; i < I; i += (int64_t)gridDim.x * TG_THREADS) {
+    if (!flag[i]) continue;
+    const int64_t q = idx[i];
+    if (q >= 0 && q < cap) pop[q] = (int32_t)((int64_t)U + 1 + i);
+  }
+}
+
+// ------------------------------------------------------------------------------------------------------------------ host
+int tg_bits_of(uint32_t x) {       // bits that hold the values 0 .. x
+  int b = 1;
+  while (b < 32 && (x >> b)) ++b;
+  return b;
+}
+
+unsigned tg_grid(int64_t n) {
+  const int64_t g = cdiv64(n > 0 ? n : 1, TG_THREADS);
+  return (unsigned)(g < 65536 ? g : 65536);
+}
+
+struct Temp {
+  uint32_t* k0; uint32_t* v0; uint32_t* k1; uint32_t* v1;
+  int32_t* flag; int32_t* ev; int32_t* hist; int64_t* lidx; int64_t* bsum; void* sort_temp; int64_t sort_bytes, total_bytes;
+};
+
+Temp carve(void* temp, int64_t n, int64_t U) {
+  Temp t;
+  const int64_t w = align_up64(n, 64) * 4;
+  char* p = reinterpret_cast<char*>(temp);
+  t.k0 = reinterpret_cast<uint32_t*>(p); p += w;
+  t.v0 = reinterpret_cast<uint32_t*>(p); p += w;
+  t.k1 = reinterpret_cast<uint32_t*>(p); p += w;
+  t.v1 = reinterpret_cast<uint32_t*>(p); p += w;
+  t.flag = reinterpret_cast<int32_t*>(p); p += w;
+  t.ev = reinterpret_cast<int32_t*>(p); p += w;
+  t.hist = reinterpret_cast<int32_t*>(p); p += align_up64(U, 64) * 4;
+  t.lidx = reinterpret_cast<int64_t*>(p); p += align_up64(n + 1, 32) * 8;
+  t.bsum = reinterpret_cast<int64_t*>(p); p += align_up64(cdiv64(n, SCAN_CHUNK) + 1, 32) * 8;
+  t.sort_temp = p;
+  t.sort_bytes = score_sort_pairs_temp_bytes(n);
+  t.total_bytes = (p - reinterpret_cast<char*>(temp)) + t.sort_bytes;
+  return t;
+}
+
+struct PopTemp { int32_t* flag; int64_t* idx; int64_t* bsum; int64_t total_bytes; };
+
+PopTemp pop_carve(void* temp, int64_t I) {
+  PopTemp t;
+  char* p = reinterpret_cast<char*>(temp);
+  t.flag = reinterpret_cast<int32_t*>(p); p += align_up64(I, 64) * 4;
+  t.idx = reinterpret_cast<int64_t*>(p); p += align_up64(I + 1, 32) * 8;
+  t.bsum = reinterpret_cast<int64_t*>(p); p += align_up64(cdiv64(I, SCAN_CHUNK) + 1, 32) * 8;
+  t.total_bytes = p - reinterpret_cast<char*>(temp);
+  return t;
+}
+
+int read_total(const int64_t* dev, int64_t* host, hipStream_t s) {
+  hipError_t e = hipMemcpyAsync(host, dev, sizeof(int64_t), hipMemcpyDeviceToHost, s);
+  if (e == hipSuccess) e = hipStreamSynchronize(s);
+  return e == hipSuccess ? 0 : (int)e;
+}
+
+}  // namespace
+
+extern "C" int64_t score_target_build_temp_bytes(int64_t n_events, int32_t n_users) {
+  if (n_events <= 0 || n_events >= (1ll << 31) || n_users <= 0) return -1;
+  return carve(nullptr, n_events, n_users).total_bytes;
+}
+
+extern "C" int score_target_build(const score_target_build_t* a, int32_t* line_user, int32_t* line_items, int64_t cap_lines,
+                                  int64_t* n_lines, void* temp, int64_t temp_bytes, void* stream) {
+  if (!a || a->struct_bytes != (int64_t)sizeof(score_target_build_t)) return SCORE_E_BADARG;
+  if (!a->uid || !a->iid || !a->t_idx || !temp) return SCORE_E_BADARG;
+  if (a->n_events <= 0 || a->n_users <= 0 || a->n_items <= 0 || a->neg_sample_num < 0 || a->sample_factor < 0 || a->n_pop < 0)
+    return SCORE_E_BADARG;
+  if (line_user ? (!line_items || cap_lines <= 0 || (a->pop_items && a->n_pop <= 0)) : !n_lines) return SCORE_E_BADARG;
+  const int64_t lim = 1ll << 31;
+  if (a->n_events >= lim || (int64_t)a->n_users + a->n_items >= lim || a->n_pop >= lim ||
+      (int64_t)a->neg_sample_num + 1 > TG_MAX_PER_LINE)
+    return SCORE_E_SHAPE;
+  if (score_target_build_temp_bytes(a->n_events, a->n_users) > temp_bytes) return SCORE_E_WORKSPACE;
+  hipStream_t s = (hipStream_t)stream;
+  const int64_t n = a->n_events;
+  const int32_t U = a->n_users;
+  const Temp t = carve(temp, n, U);
+  if (line_user) {
+    Fill f;
+    f.uid = a->uid; f.iid = a->iid; f.ev = t.ev; f.lidx = t.lidx; f.pop = a->pop_items;
+    f.line_user = line_user; f.line_items = line_items;
+    f.n = n; f.cap_lines = cap_lines; f.n_pop = a->n_pop;
+    f.U = U; f.I = a->n_items; f.per = 1 + a->neg_sample_num;
+    f.seed = a->seed;
+    const int64_t groups = cdiv64(cdiv64(n, 64), TG_THREADS / 64);
+    hipLaunchKernelGGL(tg_fill_kernel, dim3((unsigned)(groups < 8192 ? groups : 8192)), dim3(TG_THREADS), 0, s, f);
+    SCORE_CHECK_LAUNCH();
+    return 0;
+  }
+  uint32_t* k = t.k0; uint32_t* v = t.v0;
+  int32_t in_alt = 0;
+  hipLaunchKernelGGL(tg_zero_kernel, dim3(tg_grid(U)), dim3(TG_THREADS), 0, s, t.hist, (int64_t)U);
+  SCORE_CHECK_LAUNCH();
+  hipLaunchKernelGGL(tg_keys_kernel, dim3(tg_grid(n)), dim3(TG_THREADS), 0, s, a->uid, a->iid, a->t_idx, n, U, a->n_items,
+                     a->start_time, a->pred_time, k, v, t.hist);
+  SCORE_CHECK_LAUNCH();
+  SCORE_TRY(score_sort_pairs(k, v, t.k1, t.v1, n, tg_bits_of((uint32_t)U), t.sort_temp, t.sort_bytes, &in_alt, s));
+  if (in_alt) { k = t.k1; v = t.v1; }
+  hipLaunchKernelGGL(tg_flag_kernel, dim3(tg_grid(n)), dim3(TG_THREADS), 0, s, k, v, t.hist, n, U, a->sample_factor, a->seed,
+                     t.flag, t.ev);
+  SCORE_CHECK_LAUNCH();
+  SCORE_TRY(gb_scan(t.flag, n, t.bsum, t.lidx, s));
+  return read_total(t.lidx + n, n_lines, s);
+}
+
+extern "C" int64_t score_pop_items_temp_bytes(int32_t n_items) {
+  if (n_items <= 0) return -1;
+  return pop_carve(nullptr, n_items).total_bytes;
+}
+
+extern "C" int score_pop_items(const score_pop_items_t* a, int32_t* pop_items, int64_t cap_pop, int64_t* n_pop, void* temp,
+                               int64_t temp_bytes, void* stream) {
+  if (!a || a->struct_bytes != (int64_t)sizeof(score_pop_items_t)) return SCORE_E_BADARG;
+  if (!a->item_off1 || !temp || a->n_users <= 0 || a->n_items <= 0 || a->time_slice_num <= 0) return SCORE_E_BADARG;
+  if (pop_items ? cap_pop <= 0 : !n_pop) return SCORE_E_BADARG;
+  const int64_t lim = 1ll << 31;
+  if ((int64_t)a->n_items * a->time_slice_num >= lim || (int64_t)a->n_users + a->n_items >= lim) return SCORE_E_SHAPE;
+  if (score_pop_items_temp_bytes(a->n_items) > temp_bytes) return SCORE_E_WORKSPACE;
+  hipStream_t s = (hipStream_t)stream;
+  const int64_t I = a->n_items;
+  const PopTemp t = pop_carve(temp, I);
+  if (pop_items) {
+    hipLaunchKernelGGL(tg_pop_fill_kernel, dim3(tg_grid(I)), dim3(TG_THREADS), 0, s, t.flag, t.idx, a->n_users, a->n_items,
+                       pop_items, cap_pop);
+    SCORE_CHECK_LAUNCH();
+    return 0;
+  }
+  hipLaunchKernelGGL(tg_pop_flag_kernel, dim3(tg_grid(I)), dim3(TG_THREADS), 0, s, a->item_off1, a->n_users, a->n_items,
+                     a->time_slice_num, a->pop_standard, a->max_iid, t.flag);
+  SCORE_CHECK_LAUNCH();
+  SCORE_TRY(gb_scan(t.flag, I, t.bsum, t.idx, s));
+  return read_total(t.idx + I, n_pop, s);
+}

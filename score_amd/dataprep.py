@@ -7,6 +7,9 @@ step path.
                                                        cats, sellers, brands, ages, genders; feature rows
   tmall_slice_index    code/feateng_tmall.py:10-11,53-56   15-day time slices counted from 2015-05-01
   gen_target_lines     code/gen_target.py:99-121       'uid,pos_iid,neg...' lines of one prediction slice
+  gen_pop_items        code/gen_target.py:277-290      the popular-item list negatives may be drawn from
+  sample_target_lines  code/sampling.py:31-37          1-in-N down-sampling of validation / test lines
+(targets.TargetStore.from_log(build="device") evaluates the three on the device, csrc/targetgen.hip.)
 
 The reference enumerates each id vocabulary through ``list(set(...))`` (feateng_tmall.py:58-64), i.e. in
 Python's per-process string-hash order: its remap is not reproducible from run to run.  Here every
@@ -76,12 +79,58 @@ def remap_tmall_log(log, age=None, gender=None):
                 user_rows=user_rows, item_rows=item_rows, vocab_sizes=tuple(sizes))
 
 
-def gen_target_lines(uid, iid, t_idx, n_users, n_items, pred_time, neg_sample_num, start_time=0, seed=11):
+TAG_TARGET_NEG, TAG_TARGET_POP, TAG_TARGET_SAMPLE = 4, 5, 6      # next to graph.TAG_*: the cell of a draw is the line's user id
+
+
+def _target_heads(uid, iid, t_idx, n_users, n_items, pred_time, start_time):
+    """draws="cell": (users that get a line, ascending; their positives).  Events with a uid or iid outside its range or a
+    negative slice are dropped, as TemporalGraph.from_log(draws="cell") drops them."""
+    uid, iid, t_idx = (np.asarray(a).astype(np.int64).ravel() for a in (uid, iid, t_idx))
+    ok = (uid >= 1) & (uid <= n_users) & (iid >= n_users + 1) & (iid <= n_users + n_items) & (t_idx >= 0)
+    uid, iid, t_idx = uid[ok], iid[ok], t_idx[ok]
+    has_hist = np.zeros(n_users + 1, dtype=bool)
+    has_hist[uid[(t_idx >= start_time) & (t_idx < pred_time)]] = True
+    at = np.flatnonzero(t_idx == pred_time)
+    users, first = np.unique(uid[at], return_index=True)         # (the first occurrence: the first event in log order)
+    keep = has_hist[users]
+    return users[keep], iid[at[first[keep]]]
+
+
+def gen_target_lines(uid, iid, t_idx, n_users, n_items, pred_time, neg_sample_num, start_time=0, seed=11, draws="stream",
+                     pop_items=None):
     """TargetGen.gen_target_file (gen_target.py:99-121) on an in-memory log: one line per user that has at
     least one interaction in slice `pred_time` AND a history in [start_time, pred_time) (user_hist_dict,
     :225-236): (uid, [pos_iid, neg...]) with pos_iid the user's FIRST item of the slice in log order and the
     negatives uniform over the item id range (gen_user_neg_items with no pop list, :88-90).  Users are
-    visited in id order, as the collection scan does."""
+    visited in id order, as the collection scan does.
+
+    pop_items: the popular-item list (gen_pop_items; the Taobao run's mode, gen_target.py:92-96): every negative is an entry
+      of it, uniform over its positions.  An empty list with at least one eligible user raises ValueError (the reference's
+      random.randint(0, -1) raises there too).  (targets.TargetStore.from_log, which folds the down-sampling in, raises only
+      if a line is left after it.)
+    draws: "stream" (the default) takes the negatives from ONE sequential PCG64 stream, rng.integers per eligible user -- with
+      a pop list rng.integers(0, len(pop)) --; "cell" takes negative j of user u from the counter rule of graph._cell_keys,
+      lo + ((key(seed, tag, u, j) * n) >> 32) in 64-bit arithmetic: lo = n_users + 1, n = n_items, tag TAG_TARGET_NEG without a
+      pop list, pop_items[(key * len(pop)) >> 32], tag TAG_TARGET_POP with one.  No line depends on another, which is what
+      csrc/targetgen.hip evaluates on the device; events with an id outside its range or a negative slice are dropped.
+      Eligibility, the positive and the line order are the same under both rules.
+    Not restated: CCMR's user_neg_dict (gen_target.py:80-86), negatives read from the rating file, which is not available."""
+    if draws not in ("stream", "cell"):
+        raise ValueError("draws is 'stream' or 'cell': got %r" % (draws,))
+    pop = None if pop_items is None else np.asarray(pop_items).astype(np.int64).ravel()
+    if draws == "cell":
+        from .graph import _cell_keys
+        users, pos = _target_heads(uid, iid, t_idx, int(n_users), int(n_items), pred_time, start_time)
+        if pop is not None and len(pop) == 0 and len(users):
+            raise ValueError("pop_items is empty and %d users are eligible" % len(users))
+        neg = int(neg_sample_num)
+        key = _cell_keys(seed, TAG_TARGET_NEG if pop is None else TAG_TARGET_POP, np.repeat(users, neg),
+                         np.tile(np.arange(neg, dtype=np.int64), len(users))).astype(np.uint64).reshape(len(users), neg)
+        if pop is None:
+            negs = n_users + 1 + ((key * np.uint64(n_items)) >> np.uint64(32)).astype(np.int64)
+        else:
+            negs = pop[((key * np.uint64(len(pop))) >> np.uint64(32)).astype(np.int64)] if len(users) else key.astype(np.int64)
+        return [(int(u), [int(p)] + row) for u, p, row in zip(users.tolist(), pos.tolist(), negs.tolist())]
     rng = np.random.Generator(np.random.PCG64(seed))
     uid, iid, t_idx = np.asarray(uid), np.asarray(iid), np.asarray(t_idx)
     has_hist = np.zeros(n_users + 1, dtype=bool)
@@ -93,9 +142,55 @@ def gen_target_lines(uid, iid, t_idx, n_users, n_items, pred_time, neg_sample_nu
     lines = []
     for u in sorted(first_pos):
         if has_hist[u]:
-            negs = rng.integers(n_users + 1, n_users + n_items + 1, neg_sample_num).tolist()
+            if pop is None:
+                negs = rng.integers(n_users + 1, n_users + n_items + 1, neg_sample_num).tolist()
+            elif len(pop) == 0:
+                raise ValueError("pop_items is empty and user %d is eligible" % u)
+            else:
+                negs = pop[rng.integers(0, len(pop), neg_sample_num)].tolist()
             lines.append((u, [first_pos[u]] + negs))
     return lines
+
+
+def gen_pop_items(graph, pop_standard, max_iid=None):
+    """TargetGen.gen_pop_items (gen_target.py:277-290): the item ids, ascending, with at least `pop_standard` non-empty
+    slices among the graph's S and iid <= max_iid (default: all).  Reads the item side's off1.  -> int32 array"""
+    off1 = np.asarray(graph.item_csr["off1"]).astype(np.int64)
+    nonempty = (np.diff(off1) > 0).reshape(graph.I, graph.S).sum(axis=1)
+    ids = np.arange(graph.U + 1, graph.U + graph.I + 1, dtype=np.int64)
+    keep = nonempty >= int(pop_standard)
+    if max_iid is not None:
+        keep &= ids <= int(max_iid)
+    return ids[keep].astype(np.int32)
+
+
+def sample_target_lines(lines, sample_factor, seed=11, draws="stream"):
+    """sampling.py:31-37, the 1-in-N down-sampling of validation / test lines.  "stream": line l stays iff
+    rng.integers(1, sample_factor + 1) == 1, drawn in line order from one PCG64 stream; "cell": iff
+    (key(seed, TAG_TARGET_SAMPLE, uid, 0) * sample_factor) >> 32 == 0 -- a line's fate depends on its user alone.
+    Factor 1 keeps every line; a factor below 1 raises ValueError."""
+    f = int(sample_factor)
+    if f < 1:
+        raise ValueError("sample_factor must be at least 1: got %r" % (sample_factor,))
+    if draws not in ("stream", "cell"):
+        raise ValueError("draws is 'stream' or 'cell': got %r" % (draws,))
+    lines = list(lines)
+    if f == 1 or not lines:
+        return lines
+    if draws == "cell":
+        keep = target_sample_keep([int(l[0]) for l in lines], f, seed)
+    else:
+        rng = np.random.Generator(np.random.PCG64(seed))
+        keep = [int(rng.integers(1, f + 1)) == 1 for _ in lines]
+    return [l for l, k in zip(lines, keep) if k]
+
+
+def target_sample_keep(users, sample_factor, seed):
+    """the "cell" sample rule on an array of user ids -> bool array"""
+    from .graph import _cell_keys
+    users = np.asarray(users, dtype=np.int64)
+    key = _cell_keys(seed, TAG_TARGET_SAMPLE, users, np.zeros(len(users), dtype=np.int64)).astype(np.uint64)
+    return ((key * np.uint64(int(sample_factor))) >> np.uint64(32)) == 0
 
 
 # constants of the Tmall run, code/score/train_score.py:45-54,339-364 and code/graph_storage.py:39-47
@@ -104,22 +199,64 @@ TMALL = dict(obj_per_time_slice=10, time_slice_num=12, graph_time_slice_num=14, 
              eval_batch_size=100, train_neg=1, test_neg=99, max_1hop=10, max_2hop=100)
 
 
-def tmall_pipeline(log, seed=11, build="host", draws="stream"):
+TMALL_SPLITS = (("train", "pred_time_train", "train_neg"), ("validation", "pred_time_validation", "test_neg"),
+                ("test", "pred_time_test", "test_neg"))
+
+
+def _split_factor(sample_factor, name):
+    """sample_factor= of the pipelines: one number for validation and test, or a dict per split; never the train split"""
+    if isinstance(sample_factor, dict):
+        return sample_factor.get(name)
+    return None if name == "train" else sample_factor
+
+
+def _check_targets(targets, draws, sample_factor):
+    if targets not in ("host", "device"):
+        raise ValueError("targets is 'host' or 'device': got %r" % (targets,))
+    if targets == "device" and draws != "cell":
+        raise ValueError("targets='device' needs draws='cell': the sequential stream of draws='stream' has no device form")
+    if targets == "host" and sample_factor is not None:
+        raise ValueError("sample_factor= needs targets='device' (sample_target_lines down-samples host lines)")
+
+
+def _device_log(r, device=None):
+    """the remapped log's three columns uploaded once -> int32 tensors"""
+    import torch
+    if not torch.cuda.is_available():
+        raise RuntimeError("targets='device' needs an AMD GPU (HIP); targets='host' does not")
+    dev = torch.device(device if device is not None else "cuda:%d" % torch.cuda.current_device())
+    from .targets import device_i32
+    return tuple(device_i32(r[k], dev) for k in ("uid", "iid", "t_idx"))
+
+
+def tmall_pipeline(log, seed=11, build="host", draws="stream", targets="host", sample_factor=None):
     """Raw Tmall log -> (TemporalGraph, remap dict, {'train' | 'validation' | 'test': target lines}).  Train
-    lines carry 1 negative (train_score.py:18), validation / test lines 99 (:19).  build / draws: TemporalGraph.from_log's."""
+    lines carry 1 negative (train_score.py:18), validation / test lines 99 (:19).  build / draws: TemporalGraph.from_log's.
+    targets: "host" (the default) gen_target_lines with the same draws; "device" (needs a GPU and draws="cell") the log is
+    uploaded once and the dict holds targets.TargetStore objects built from it (csrc/targetgen.hip), which the loaders take in
+    place of lines; sample_factor (one number, or a dict per split) then down-samples the validation / test lines as
+    sampling.py does."""
     from .graph import TemporalGraph
+    _check_targets(targets, draws, sample_factor)
     r = remap_tmall_log(log)
     c = TMALL
-    g = TemporalGraph.from_log(r["uid"], r["iid"], r["t_idx"], r["n_users"], r["n_items"], c["graph_time_slice_num"],
+    cols = _device_log(r) if targets == "device" and build == "device" else (r["uid"], r["iid"], r["t_idx"])
+    g = TemporalGraph.from_log(cols[0], cols[1], cols[2], r["n_users"], r["n_items"], c["graph_time_slice_num"],
                                r["user_rows"], r["item_rows"], max_1hop=c["max_1hop"], max_2hop=c["max_2hop"], seed=seed,
                                build=build, draws=draws)
-    targets = {}
-    for name, pt, neg in (("train", c["pred_time_train"], c["train_neg"]),
-                          ("validation", c["pred_time_validation"], c["test_neg"]),
-                          ("test", c["pred_time_test"], c["test_neg"])):
-        targets[name] = gen_target_lines(r["uid"], r["iid"], r["t_idx"], r["n_users"], r["n_items"], pt, neg,
-                                         c["start_time"], seed + pt)
-    return g, r, targets
+    if targets == "device" and build != "device":
+        cols = _device_log(r)
+    out = {}
+    for name, pt, neg in TMALL_SPLITS:
+        pt, neg = c[pt], c[neg]
+        if targets == "device":
+            from .targets import TargetStore
+            out[name] = TargetStore.from_log(cols[0], cols[1], cols[2], r["n_users"], r["n_items"], pt, neg, c["start_time"],
+                                             seed + pt, build="device", sample_factor=_split_factor(sample_factor, name))
+        else:
+            out[name] = gen_target_lines(r["uid"], r["iid"], r["t_idx"], r["n_users"], r["n_items"], pt, neg,
+                                         c["start_time"], seed + pt, draws=draws)
+    return g, r, out
 
 
 # ---- the point baselines' history files (gen_target.py:223-275, gen_history_point.py:22-65) ------------------------------------
@@ -187,22 +324,35 @@ def write_point_files(directory, target_lines, user_hist_lines, item_hist_lines,
     return tuple(paths)
 
 
-def tmall_point_stores(log, seed=11, dual=True, batch_size=None, build="device", device=None):
+def tmall_point_stores(log, seed=11, dual=True, batch_size=None, build="device", device=None, targets="host", draws="stream",
+                       sample_factor=None):
     """Raw Tmall log -> ({'train' | 'validation' | 'test': PointLogStore}, remap dict): the point baselines' data path on the
-    log SCoRe trains from (tmall_pipeline's target lines: the same seed gives the same lines).  Train lines carry 1 negative,
-    validation / test lines 99; histories are cut at the reference's 300.  batch_size: a dict per split or one number;
-    default 200 for train (a multiple of 2) and TMALL's eval_batch_size for the others."""
+    log SCoRe trains from (tmall_pipeline's target lines: the same seed, draws and targets give the same lines).  Train lines
+    carry 1 negative, validation / test lines 99; histories are cut at the reference's 300.  batch_size: a dict per split or
+    one number; default 200 for train (a multiple of 2) and TMALL's eval_batch_size for the others.  targets / draws /
+    sample_factor: tmall_pipeline's -- with targets="device" the lines are built on the device and handed over as tensors."""
     from .pointdata import PointLogStore
+    _check_targets(targets, draws, sample_factor)
     r = remap_tmall_log(log)
     c = TMALL
+    cols = _device_log(r, device) if targets == "device" else None
+    log4 = (r["uid"], r["iid"], np.asarray(log)[:, 5], r["t_idx"])
+    if targets == "device" and build == "device":                  # the uploaded log serves the histories too
+        from .targets import device_i32
+        log4 = (cols[0], cols[1], device_i32(log4[2], cols[0].device), cols[2])
     stores = {}
-    for name, pt, neg in (("train", c["pred_time_train"], c["train_neg"]),
-                          ("validation", c["pred_time_validation"], c["test_neg"]),
-                          ("test", c["pred_time_test"], c["test_neg"])):
-        lines = gen_target_lines(r["uid"], r["iid"], r["t_idx"], r["n_users"], r["n_items"], pt, neg, c["start_time"], seed + pt)
+    for name, pt, neg in TMALL_SPLITS:
+        pt, neg = c[pt], c[neg]
+        if targets == "device":
+            from .targets import TargetStore
+            lines = TargetStore.from_log(cols[0], cols[1], cols[2], r["n_users"], r["n_items"], pt, neg, c["start_time"],
+                                         seed + pt, build="device", sample_factor=_split_factor(sample_factor, name))
+        else:
+            lines = gen_target_lines(r["uid"], r["iid"], r["t_idx"], r["n_users"], r["n_items"], pt, neg, c["start_time"],
+                                     seed + pt, draws=draws)
         B = batch_size.get(name) if isinstance(batch_size, dict) else batch_size
         if B is None:
             B = 200 if name == "train" else c["eval_batch_size"]
-        stores[name] = PointLogStore(r["uid"], r["iid"], np.asarray(log)[:, 5], r["t_idx"], lines, c["start_time"], pt,
+        stores[name] = PointLogStore(log4[0], log4[1], log4[2], log4[3], lines, c["start_time"], pt,
                                      POINT_HIST_MAX_LEN, neg, B, r["user_rows"], r["item_rows"], dual, build=build, device=device)
     return stores, r

@@ -297,7 +297,9 @@ class TemporalGraph(object):
         dev = torch.device(device if device is not None else "cuda:%d" % torch.cuda.current_device())
         lib = _lib.load()
         S, U, I = int(time_slice_num), int(n_users), int(n_items)
-        up = lambda a: torch.from_numpy(np.ascontiguousarray(np.asarray(a).ravel(), dtype=np.int32)).to(dev)
+        # (a log already uploaded -- int32 tensors -- is used where it is: one upload serves the graph and the target lines)
+        from .targets import device_i32
+        up = lambda a: device_i32(a, dev)
         with torch.cuda.device(dev):
             d_uid, d_iid, d_t = up(uid), up(iid), up(t_idx)
             n = int(d_uid.numel())
@@ -479,19 +481,34 @@ class _AssembledBatch(DeviceBatch):
 class DeviceGraphLoader(object):
     """Iterator over device batches accepted by SCORE.train / SCORE.eval, from a TemporalGraph object and target lines in
     memory (`target_lines`: iterable of 'uid,pos_iid,neg...' strings or of (uid, [iids]) pairs -- gen_target.py's
-    target_<t>.txt format).  NOT the reference's constructor: `GraphLoader` below has that one (graph_loader.py:279-281)
-    and resolves its arguments to this class."""
+    target_<t>.txt format -- or a targets.TargetStore, whose tensors are used as they are: a smaller neg_sample_num than the
+    store's takes the first 1 + neg_sample_num columns with one device copy, a larger one is a ValueError).  NOT the reference's constructor:
+    `GraphLoader` below has that one (graph_loader.py:279-281) and resolves its arguments to this class."""
 
     def __init__(self, graph, batch_size, target_lines, start_time, pred_time, neg_sample_num,
                  max_time_len, obj_per_time_slice, seed=1111):
         if batch_size % (1 + neg_sample_num) != 0:
             raise ValueError("batch size should be time of {}".format(1 + neg_sample_num))    # :289-291
+        from .targets import TargetStore
+        store = target_lines if isinstance(target_lines, TargetStore) else None
+        if store is not None and neg_sample_num > store.neg_sample_num:
+            raise ValueError("the target store holds %d negatives per line, the loader asks for %d"
+                             % (store.neg_sample_num, neg_sample_num))
         if graph._dev is None:
             graph.to_device()
         self.g, self.lib = graph, _lib.load()
         self.lines_per_batch = batch_size // (1 + neg_sample_num)
         self.neg, self.start_time, self.pred_time = neg_sample_num, start_time, pred_time
         self.T, self.K, self.seed = max_time_len, obj_per_time_slice, seed
+        self._pos = 0
+        self._batch_no = 0
+        if store is not None:
+            self.uids, items = store.device_tensors(graph.device)
+            if neg_sample_num < store.neg_sample_num:
+                items = items[:, :1 + neg_sample_num].contiguous()
+            self.iids = items.reshape(-1)
+            self.n_lines = store.n_lines
+            return
         uids, iids = [], []
         for line in target_lines:
             if isinstance(line, str):
@@ -504,8 +521,6 @@ class DeviceGraphLoader(object):
         self.uids = torch.tensor(uids, dtype=torch.int32, device=graph.device)
         self.iids = torch.tensor(iids, dtype=torch.int32, device=graph.device)
         self.n_lines = len(uids)
-        self._pos = 0
-        self._batch_no = 0
 
     def __iter__(self):
         return self

@@ -321,10 +321,12 @@ class PointLogStore(object):
     gen_target.py:223-275 (hist dicts) -> gen_history_point.py:22-65 (files; dataprep.point_history_lines restates both) ->
     DataLoaderUserSeq / DataLoaderDualSeq.
 
-    uid / iid / time_key / t_idx [n]: the log as dataprep.remap_tmall_log returns it (users 1 .. U, items U + 1 .. U + I,
+    uid / iid / time_key / t_idx [n]: the log as dataprep.remap_tmall_log returns it, or (build="device") the same four columns as
+    int32 tensors already on the device (users 1 .. U, items U + 1 .. U + I,
     U and I the row counts of user_rows [U, Fu] / item_rows [I, Fi], whose column 0 is the id) and a non-negative key that
     orders events as the reference's time_int does (Tmall: the MMDD column).  target_lines: (uid, [items...]) as
-    dataprep.gen_target_lines yields them.
+    dataprep.gen_target_lines yields them, or a targets.TargetStore: its arrays are taken as they are, and under build="device" a
+    store on the device is never downloaded.
 
     Arrays (numpy with build="host", device tensors with build="device"; .arrays() gives numpy either way):
       user_hist_off int64 [U + 1], user_hist_seq int32, user_hist_len int32 [U]: user u's events of slices
@@ -369,29 +371,48 @@ class PointLogStore(object):
         if not (np.array_equal(self.user_rows[:, 0], np.arange(1, U + 1)) and
                 np.array_equal(self.item_rows[:, 0], np.arange(U + 1, U + I + 1))):
             raise ValueError("column 0 of user_rows / item_rows must be the ids 1 .. U / U + 1 .. U + I")
-        cols = [np.ascontiguousarray(np.asarray(a).reshape(-1)) for a in (uid, iid, time_key, t_idx)]
-        n = len(cols[0])
-        if n == 0 or any(len(c) != n for c in cols) or n >= 2 ** 31:
+        from .targets import _host, _is_tensor, device_i32
+        if all(_is_tensor(a) and a.is_cuda for a in (uid, iid, time_key, t_idx)):
+            # the log as int32 tensors already on the device (one upload serves the graph, the targets and the histories):
+            # the range checks read six extremes back
+            import torch
+            if build != "device":
+                raise ValueError("a log on the device needs build='device'")
+            if device is None:
+                device = uid.device
+            cols = [device_i32(a, device) for a in (uid, iid, time_key, t_idx)]
+            sizes = [int(c.numel()) for c in cols]
+            ext = torch.stack([f(c) for c in cols[:3] for f in (torch.amin, torch.amax)]).cpu().tolist() if min(sizes) else None
+        else:
+            cols = [np.ascontiguousarray(np.asarray(_host(a)).reshape(-1)) for a in (uid, iid, time_key, t_idx)]
+            sizes = [len(c) for c in cols]
+            ext = [int(f()) for c in cols[:3] for f in (c.min, c.max)] if min(sizes) else None
+        if ext is None or any(n != sizes[0] for n in sizes) or sizes[0] >= 2 ** 31:
             raise ValueError("uid, iid, time_key and t_idx must be equally long, with 1 .. 2^31 - 1 events")
-        if cols[0].min() < 1 or cols[0].max() > U or cols[1].min() < U + 1 or cols[1].max() > U + I:
+        if ext[0] < 1 or ext[1] > U or ext[2] < U + 1 or ext[3] > U + I:
             raise ValueError("the log's uid must lie in 1 .. %d and its iid in %d .. %d" % (U, U + 1, U + I))
-        if cols[2].min() < 0 or cols[2].max() >= 2 ** 31:
+        if ext[4] < 0 or ext[5] >= 2 ** 31:
             raise ValueError("time_key must be a non-negative 31-bit integer")
-        self._log = uid, iid, time_key, t_idx = [c.astype(i32) for c in cols]
-        self.time_bits = max(1, int(time_key.max()).bit_length())
-        self.n_batches = len(target_lines) // self.lines_per_batch
+        self._log = cols if not isinstance(cols[0], np.ndarray) else [c.astype(i32) for c in cols]
+        self.time_bits = max(1, int(ext[5]).bit_length())
+        from .targets import TargetStore
+        self.n_batches = (target_lines.n_lines if isinstance(target_lines, TargetStore) else len(target_lines)) // self.lines_per_batch
         self.n_lines = n_lines = self.n_batches * self.lines_per_batch
-        line_user, line_items, line_last = [], [], []
-        for l, (u, items) in enumerate(target_lines[:n_lines]):
-            if len(items) < per_line:
-                raise ValueError("target line %d holds %d items, fewer than 1 + neg_sample_num = %d" % (l, len(items), per_line))
-            line_user.append(int(u))
-            line_items += [int(i) for i in items[:per_line]]
-            line_last.append(int(items[-1]))
-            if not 1 <= line_user[-1] <= U or min(int(i) for i in items) < U + 1 or max(int(i) for i in items) > U + I:
-                raise ValueError("target line %d: an id outside users 1 .. %d / items %d .. %d" % (l, U, U + 1, U + I))
-        self.line_user, self.line_items = np.asarray(line_user, dtype=i32), np.asarray(line_items, dtype=i32)
-        self.line_last_item = np.asarray(line_last, dtype=i32)
+        self._first_bad_line = None
+        if isinstance(target_lines, TargetStore):
+            self._lines_from_store(target_lines, build, device)
+        else:
+            line_user, line_items, line_last = [], [], []
+            for l, (u, items) in enumerate(target_lines[:n_lines]):
+                if len(items) < per_line:
+                    raise ValueError("target line %d holds %d items, fewer than 1 + neg_sample_num = %d" % (l, len(items), per_line))
+                line_user.append(int(u))
+                line_items += [int(i) for i in items[:per_line]]
+                line_last.append(int(items[-1]))
+                if not 1 <= line_user[-1] <= U or min(int(i) for i in items) < U + 1 or max(int(i) for i in items) > U + I:
+                    raise ValueError("target line %d: an id outside users 1 .. %d / items %d .. %d" % (l, U, U + 1, U + I))
+            self.line_user, self.line_items = np.asarray(line_user, dtype=i32), np.asarray(line_items, dtype=i32)
+            self.line_last_item = np.asarray(line_last, dtype=i32)
         self._dev = self.device = self.struct = None
         if build == "host":
             self._build_host()
@@ -401,7 +422,40 @@ class PointLogStore(object):
         if n_lines and self._line_min_user_len[0] <= 0:
             l = int(self._line_min_user_len[1])
             raise ValueError("target line %d: user %d has no history in slices [%d, %d)"
-                             % (l, line_user[l], self.start_time, self.pred_time))
+                             % (l, int(self.line_user[l]), self.start_time, self.pred_time))
+
+    def _lines_from_store(self, store, build, device):
+        """line_user / line_items / line_last_item from a targets.TargetStore's arrays, whole batches only.  A store on the
+        device stays there under build="device": its id-range check rides in the build's one read-back (_first_bad_line)."""
+        U, I, per_line, n_lines = self.n_users, self.n_items, self.per_line, self.n_lines
+        if store.per_line < per_line:
+            raise ValueError("target line 0 holds %d items, fewer than 1 + neg_sample_num = %d" % (store.per_line, per_line))
+        if build == "device" and store.on_device:
+            import torch
+            dev = torch.device(device if device is not None else store.line_user.device)
+            lu, li = (a[:n_lines] for a in store.device_tensors(dev))
+            self.line_user, self.line_items = lu.contiguous(), li[:, :per_line].contiguous().view(-1)
+            self.line_last_item = li[:, -1].contiguous()
+            if n_lines:
+                bad = (lu < 1) | (lu > U) | (li.amin(dim=1) < U + 1) | (li.amax(dim=1) > U + I)
+                lines = torch.arange(n_lines, device=dev)
+                self._first_bad_line = torch.where(bad, lines, torch.full_like(lines, n_lines)).amin().reshape(1)
+            return
+        lu, li = (a[:n_lines] for a in store.arrays())
+        bad = np.flatnonzero((lu < 1) | (lu > U) | (li.min(axis=1, initial=U + 1) < U + 1) | (li.max(axis=1, initial=U + 1) > U + I))
+        if len(bad):
+            raise ValueError("target line %d: an id outside users 1 .. %d / items %d .. %d" % (int(bad[0]), U, U + 1, U + I))
+        self.line_user = np.ascontiguousarray(lu, dtype=np.int32)
+        self.line_items = np.ascontiguousarray(li[:, :per_line], dtype=np.int32).reshape(-1)
+        self.line_last_item = np.ascontiguousarray(li[:, -1], dtype=np.int32)
+
+    def _line_rows(self):
+        """the 0-based rows of the lines' users and items in the length arrays: numpy, or (a store on the device) long tensors
+        clamped into range -- an id outside it is reported from the read-back, not looked up"""
+        if isinstance(self.line_user, np.ndarray):
+            return self.line_user.astype(np.int64) - 1, self.line_items.astype(np.int64) - 1 - self.n_users
+        return ((self.line_user.long() - 1).clamp(0, self.n_users - 1),
+                (self.line_items.long() - 1 - self.n_users).clamp(0, self.n_items - 1))
 
     HIST = ("user_hist_off", "user_hist_seq", "user_hist_len", "item_hist_off", "item_hist_seq", "item_hist_len")
 
@@ -409,12 +463,13 @@ class PointLogStore(object):
         """per batch: the longest user history, the longest and the shortest history of both sides; and the shortest user
         history of any line with its line -- in numpy or torch, whichever the five functions belong to"""
         nb, lpb = self.n_batches, self.lines_per_batch
-        lu = take(user_len, self.line_user.astype(np.int64) - 1)
+        rows_u, rows_i = self._line_rows()
+        lu = take(user_len, rows_u)
         per = lu.reshape(nb, lpb)
         mx_u, mn = amax(per), amin(per)
         mx = mx_u
         if self.dual:
-            li = take(item_len, self.line_items.astype(np.int64) - 1 - self.n_users).reshape(nb, self.batch_size)
+            li = take(item_len, rows_i).reshape(nb, self.batch_size)
             li = maximum(li, li * 0 + 1)                                       # (no history: the stand-in [0], length 1)
             mx, mn = maximum(mx, amax(li)), minimum(mn, amin(li))
         return mx_u, mx, mn, lu.min().reshape(1), lu.argmin().reshape(1)
@@ -449,8 +504,8 @@ class PointLogStore(object):
             raise RuntimeError("PointLogStore(build='device') needs an AMD GPU (HIP); build='host' does not")
         dev = torch.device(device if device is not None else "cuda:%d" % torch.cuda.current_device())
         lib = _lib.load()
-        uid, iid, time_key, t_idx = [torch.from_numpy(c).to(dev) for c in self._log]
-        n, U, I = len(self._log[0]), self.n_users, self.n_items
+        uid, iid, time_key, t_idx = [c.to(dev) if torch.is_tensor(c) else torch.from_numpy(c).to(dev) for c in self._log]
+        n, U, I = int(uid.numel()), self.n_users, self.n_items
         temp_bytes = int(lib.score_point_hist_temp_bytes(n))
         temp = torch.empty((temp_bytes,), dtype=torch.uint8, device=dev)
         stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
@@ -471,11 +526,17 @@ class PointLogStore(object):
         for k, v in out.items():
             setattr(self, k, v)
         if self.n_batches:       # the one read-back of the build
-            parts = self._extremes(self.user_hist_len, self.item_hist_len, lambda a, i: a[torch.from_numpy(i).to(dev)],
+            parts = self._extremes(self.user_hist_len, self.item_hist_len,
+                                   lambda a, i: a[i.to(dev) if torch.is_tensor(i) else torch.from_numpy(i).to(dev)],
                                    torch.maximum, torch.minimum, lambda a: a.amax(dim=1), lambda a: a.amin(dim=1))
+            if self._first_bad_line is not None:                   # (a target store on the device: its id-range check)
+                parts = tuple(parts) + (self._first_bad_line.to(dev),)
             sizes = [len(p) for p in parts]
-            host = torch.cat([p.to(torch.int64) for p in parts]).cpu().numpy()
-            self._set_extremes(np.split(host, np.cumsum(sizes)[:-1]))
+            host = np.split(torch.cat([p.to(torch.int64) for p in parts]).cpu().numpy(), np.cumsum(sizes)[:-1])
+            if self._first_bad_line is not None and int(host[5][0]) < self.n_lines:
+                raise ValueError("target line %d: an id outside users 1 .. %d / items %d .. %d"
+                                 % (int(host[5][0]), U, U + 1, U + I))
+            self._set_extremes(host[:5])
         else:
             torch.cuda.current_stream(dev).synchronize()
             self._set_extremes([np.zeros((0,))] * 5)
@@ -515,6 +576,10 @@ class PointLogStore(object):
                 continue
             if isinstance(a, np.ndarray):        # (an empty array still needs a valid pointer)
                 a = torch.from_numpy(np.ascontiguousarray(a)).to(dev) if a.size else torch.zeros((1,), dtype=torch.int32, device=dev)
+            elif a.numel() == 0:
+                a = torch.zeros((1,), dtype=torch.int32, device=dev)
+            else:
+                a = a.to(dev)
             d[k] = a
         ptr = lambda k: C.c_void_p(d[k].data_ptr()) if k in d else C.c_void_p(0)
         self._dev, self.device = d, dev

@@ -1,0 +1,191 @@
+"""The target lines of one prediction slice as two integer arrays -- built from the remapped log on the device
+(csrc/targetgen.hip) or on the host (dataprep.gen_target_lines(draws="cell")), the same words either way -- which the loaders
+take as they are: DeviceGraphLoader and PointLogStore accept a TargetStore where they accept target lines, without a Python
+list in between.  Replaces gen_target.py:79-121 (target_<t>.txt), :277-290 (the pop list) and sampling.py:31-37 (the _sample
+files) for the training loop.
+"""
+import ctypes as C
+
+import numpy as np
+
+from . import dataprep
+
+
+def _is_tensor(a):
+    return type(a).__module__.startswith("torch") and hasattr(a, "data_ptr")
+
+
+def _host(a):
+    return a.cpu().numpy() if _is_tensor(a) else np.asarray(a)
+
+
+def device_i32(a, dev):
+    """a column of the log as a flat int32 tensor on `dev`: a tensor is used where it is (converted or moved only if it has
+    to be), anything else goes through numpy and is uploaded"""
+    import torch
+    if _is_tensor(a):
+        return a.to(device=dev, dtype=torch.int32).contiguous().view(-1)
+    return torch.from_numpy(np.ascontiguousarray(np.asarray(a).ravel(), dtype=np.int32)).to(dev)
+
+
+def pop_items_device(graph, pop_standard, max_iid=None):
+    """dataprep.gen_pop_items on a graph built on the device (TemporalGraph.from_log(build="device")): score_pop_items over
+    its resident item-side off1 -> device int32 tensor [n_pop]; the list never leaves the device."""
+    import torch
+    from . import _lib
+    b, dev = graph._built, graph._built_device
+    lib = _lib.load()
+    with torch.cuda.device(dev):
+        temp_bytes = int(lib.score_pop_items_temp_bytes(graph.I))
+        temp = torch.empty((temp_bytes,), dtype=torch.uint8, device=dev)
+        a = _lib.PopItems(C.sizeof(_lib.PopItems), b["i_off1"].data_ptr(), graph.U, graph.I, graph.S, int(pop_standard),
+                          int(max_iid) if max_iid is not None else 2 ** 31 - 1, 0)
+        stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+        n_pop = C.c_int64(-1)
+        _lib.check(lib.score_pop_items(C.byref(a), None, 0, C.byref(n_pop), temp.data_ptr(), temp_bytes, stream),
+                   "score_pop_items (count)")
+        pop = torch.empty((int(n_pop.value),), dtype=torch.int32, device=dev)
+        if n_pop.value:
+            _lib.check(lib.score_pop_items(C.byref(a), pop.data_ptr(), int(n_pop.value), None, temp.data_ptr(), temp_bytes, stream),
+                       "score_pop_items (fill)")
+            torch.cuda.current_stream(dev).synchronize()          # (temp is released behind this)
+    return pop
+
+
+class TargetStore(object):
+    """line_user int32 [n_lines] and line_items int32 [n_lines, per_line] (the positive, then per_line - 1 negatives), numpy
+    arrays or device tensors; n_lines, per_line."""
+
+    def __init__(self, line_user, line_items, per_line=None):
+        self.line_user, self.line_items = line_user, line_items
+        self.n_lines = int(line_user.shape[0])
+        self.per_line = int(per_line if per_line is not None else line_items.shape[1])
+        if tuple(line_items.shape) != (self.n_lines, self.per_line):
+            raise ValueError("line_items must be [n_lines, per_line] = %r, got %r"
+                             % ((self.n_lines, self.per_line), tuple(line_items.shape)))
+        self._lines = None
+
+    neg_sample_num = property(lambda self: self.per_line - 1)
+    on_device = property(lambda self: _is_tensor(self.line_user))
+
+    @classmethod
+    def from_log(cls, uid, iid, t_idx, n_users, n_items, pred_time, neg_sample_num, start_time=0, seed=11, build="device",
+                 pop_items=None, sample_factor=None, device=None):
+        """The lines dataprep.gen_target_lines(draws="cell") yields, after dataprep.sample_target_lines(draws="cell") where
+        sample_factor is given (same seed).  build="host": numpy, those two functions; build="device" (needs a GPU):
+        score_target_build, the same words.  uid / iid / t_idx: numpy arrays or int32 tensors already on the device -- one
+        upload serves the graph and the targets.  pop_items: None, an array, a device tensor or (graph, pop_standard) --
+        dataprep.gen_pop_items, evaluated on the device where the graph was built there.  ValueError: a sample_factor below
+        1; an empty pop list with at least one line to fill.  On both builds that means a line LEFT by the down-sampling (the
+        device learns the count of those alone); gen_target_lines itself, which knows nothing of a sample_factor, raises as
+        soon as any user is eligible."""
+        if build not in ("host", "device"):
+            raise ValueError("build is 'host' or 'device': got %r" % (build,))
+        if sample_factor is not None and int(sample_factor) < 1:
+            raise ValueError("sample_factor must be at least 1: got %r" % (sample_factor,))
+        U, I, neg = int(n_users), int(n_items), int(neg_sample_num)
+        if neg < 0:
+            raise ValueError("neg_sample_num must not be negative")
+        if build == "host":
+            pop = pop_items
+            if isinstance(pop, tuple):
+                pop = dataprep.gen_pop_items(pop[0], pop[1])
+            elif pop is not None:
+                pop = _host(pop)
+            empty_pop = pop is not None and len(pop) == 0        # (an error only if a line is left after the down-sampling)
+            lines = dataprep.gen_target_lines(_host(uid), _host(iid), _host(t_idx), U, I, pred_time, neg, start_time, seed,
+                                              draws="cell", pop_items=None if empty_pop else pop)
+            if sample_factor is not None:
+                lines = dataprep.sample_target_lines(lines, sample_factor, seed, draws="cell")
+            if empty_pop and lines:
+                raise ValueError("pop_items is empty and %d users are eligible" % len(lines))
+            return cls._from_lines(lines, 1 + neg)
+        import torch
+        from . import _lib
+        if not torch.cuda.is_available():
+            raise RuntimeError("TargetStore.from_log(build='device') needs an AMD GPU (HIP); build='host' does not")
+        dev = torch.device(device if device is not None else
+                           uid.device if _is_tensor(uid) else "cuda:%d" % torch.cuda.current_device())
+        lib = _lib.load()
+
+        up = lambda a: device_i32(a, dev)
+        with torch.cuda.device(dev):
+            d_uid, d_iid, d_t = up(uid), up(iid), up(t_idx)
+            n = int(d_uid.numel())
+            if n == 0 or d_iid.numel() != n or d_t.numel() != n:
+                raise ValueError("from_log(build='device'): uid, iid and t_idx must be non-empty and of one length")
+            if isinstance(pop_items, tuple):
+                g, standard = pop_items
+                if g._built is not None and g._built_device == dev:
+                    d_pop = pop_items_device(g, standard)
+                else:
+                    d_pop = up(dataprep.gen_pop_items(g, standard))
+            else:
+                d_pop = None if pop_items is None else up(pop_items)
+            n_pop = 0 if d_pop is None else int(d_pop.numel())
+            pop_arg = None if d_pop is None else d_pop if n_pop else torch.zeros((1,), dtype=torch.int32, device=dev)
+            temp_bytes = int(lib.score_target_build_temp_bytes(n, U))
+            if temp_bytes < 0:
+                _lib.check(-2, "score_target_build_temp_bytes")
+            temp = torch.empty((temp_bytes,), dtype=torch.uint8, device=dev)
+            a = _lib.TargetBuild(C.sizeof(_lib.TargetBuild), d_uid.data_ptr(), d_iid.data_ptr(), d_t.data_ptr(), n, U, I,
+                                 int(start_time), int(pred_time), neg, int(sample_factor or 0), int(seed) & 0xFFFFFFFFFFFFFFFF,
+                                 None if pop_arg is None else pop_arg.data_ptr(), n_pop)
+            stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+            n_lines = C.c_int64(-1)
+            _lib.check(lib.score_target_build(C.byref(a), None, None, 0, C.byref(n_lines), temp.data_ptr(), temp_bytes, stream),
+                       "score_target_build (count)")
+            L = int(n_lines.value)
+            if L and d_pop is not None and n_pop == 0:
+                raise ValueError("pop_items is empty and %d users are eligible" % L)
+            line_user = torch.empty((L,), dtype=torch.int32, device=dev)
+            line_items = torch.empty((L, 1 + neg), dtype=torch.int32, device=dev)
+            if L:
+                _lib.check(lib.score_target_build(C.byref(a), line_user.data_ptr(), line_items.data_ptr(), L, None,
+                                                  temp.data_ptr(), temp_bytes, stream), "score_target_build (fill)")
+                torch.cuda.current_stream(dev).synchronize()      # (temp and an uploaded log are released behind this)
+        return cls(line_user, line_items, 1 + neg)
+
+    @classmethod
+    def _from_lines(cls, lines, per_line=None):
+        if per_line is None:
+            if not lines:
+                raise ValueError("no lines: per_line is unknown")
+            per_line = len(lines[0][1])
+        lu = np.asarray([int(u) for u, _ in lines], dtype=np.int32)
+        li = np.asarray([its for _, its in lines], dtype=np.int32).reshape(len(lines), per_line)
+        return cls(lu, li, per_line)
+
+    def arrays(self):
+        """(line_user, line_items) as numpy"""
+        return _host(self.line_user), _host(self.line_items)
+
+    def device_tensors(self, device):
+        """(line_user, line_items) as int32 tensors on `device`: the store's own where it lives there"""
+        import torch
+        dev = torch.device(device)
+        if self.on_device:
+            return self.line_user.to(dev), self.line_items.to(dev)
+        to = lambda a: torch.from_numpy(np.ascontiguousarray(a, dtype=np.int32)).to(dev)
+        return to(self.line_user), to(self.line_items)
+
+    def lines(self):
+        """[(uid, [pos, neg...])], what dataprep.gen_target_lines yields; a device store downloads on first use"""
+        if self._lines is None:
+            lu, li = self.arrays()
+            self._lines = list(zip(lu.tolist(), li.tolist()))
+        return self._lines
+
+    def save(self, path):
+        """target_<t>.txt's format (gen_target.py:118): 'uid,pos,neg...' and a newline per line"""
+        with open(path, "w") as f:
+            f.write("".join("%d,%s\n" % (u, ",".join(map(str, its))) for u, its in self.lines()))
+        return path
+
+    @classmethod
+    def load(cls, path):
+        with open(path, "r") as f:
+            rows = [[int(x) for x in l.strip().split(",")] for l in f if l.strip()]
+        if not rows or any(len(r) != len(rows[0]) or len(r) < 2 for r in rows):
+            raise ValueError("%s: every line must be 'uid,pos,neg...' with one number of items" % path)
+        return cls._from_lines([(r[0], r[1:]) for r in rows])
