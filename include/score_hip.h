@@ -530,7 +530,10 @@ typedef struct {
                            beside the co-attention backward and the scatter (round 6; same bits); bit 13 (8192) =
                            (SCORE_MODEL_GRU4REC) the two stacked recurrences one layer per launch with the projection GEMM between
                            them (the composed form: what H outside {16, 32, 64} runs anyway) instead of csrc/gru_stack.hip;
-                           (SCORE_MODEL_DEEMS) its two recurrences one launch per side instead of one grouped launch.
+                           (SCORE_MODEL_DEEMS) its two recurrences one launch per side instead of one grouped launch;
+                           bit 15 (32768) = the co-attention backward loads the seq1 / seq2 rows of EVERY neighbour for the
+                           w1 / w2 gradients, instead of only those whose relu'd score is > 0 (an inactive one contributes
+                           dz = 0 times its row: the same bits on a finite table; csrc/embed.hip).
                            The ONLY switches of the launch sequence: the library reads no environment variable       */
   uint8_t* row_flags;   /* optional [n_table_rows] row state of the dense table optimizer (see
                            score_adam_rows): score_backward (scatter_mode 0) marks every row it

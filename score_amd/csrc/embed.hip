@@ -242,6 +242,13 @@ __device__ __forceinline__ void atomic_add4(float* d, float4 v) {
   atomicAdd(d, v.x); atomicAdd(d + 1, v.y); atomicAdd(d + 2, v.z); atomicAdd(d + 3, v.w);
 }
 
+// Nothing that uses `row` is placed in front of the load of `last`, the last row of its batch (an empty statement the
+// compiler cannot move a use across: a scheduling barrier alone left the uses where instruction selection had put
+// them, in front of it).  Loads return in order, so one wait for `last` is the wait for the whole batch.
+__device__ __forceinline__ void rows_in_flight(float4& row, const float4& last) {
+  asm volatile("" : "+v"(row.x), "+v"(row.y), "+v"(row.z), "+v"(row.w) : "v"(last.w));
+}
+
 template <int KMAX, int SPL, bool ATOMIC>
 __global__ __launch_bounds__(256, (KMAX <= 10 && SPL == 1) ? 4 : 1) void coattn_bwd_kernel_t(const CoattnArgs a) {
   extern __shared__ float lds[];  // [4 waves][upw][2*Dx]
@@ -249,6 +256,7 @@ __global__ __launch_bounds__(256, (KMAX <= 10 && SPL == 1) ? 4 : 1) void coattn_
   const CoattnCall& cc = a.c[ci];
   const int GS = cc.GS, nslots = cc.nslots, F = cc.F, K = a.K, D4 = a.D4, n_units = a.n_units;
   const int mode = a.mode;
+  const bool all_rows = a.all_rows != 0;
   const int lane = threadIdx.x & 63;
   const int wib = threadIdx.x >> 6;
   const int upw = 64 / GS;
@@ -318,11 +326,15 @@ __global__ __launch_bounds__(256, (KMAX <= 10 && SPL == 1) ? 4 : 1) void coattn_
       continue;
     }
 
-    // pass 1: seq1 rows -> dp_k = g1 . seq1_k (seq1 stays in registers for dw1).  All 2K row ids, then the K
-    // seq1 rows, are loaded unconditionally up front (clamped addresses, zeroed by selects afterwards): under
-    // `if (k < K && ok)` every k was a region of its own that waited for its id and then for its row
+    // pass 1: seq1 rows -> dp_k = g1 . seq1_k.  All 2K row ids, then the K seq1 rows, are loaded unconditionally up
+    // front (clamped addresses, zeroed by selects afterwards): under `if (k < K && ok)` every k was a region of its
+    // own that waited for its id and then for its row.  The scheduling barrier behind the ids and rows_in_flight
+    // behind the rows keep it that way in the code the compiler emits: held to 128 VGPRs, it put every load next to
+    // its use -- the ids one after the other through ONE register (a wait per k) and the rows two at a time with
+    // vmcnt(0) between the pairs, five dependent round trips to the table where passes 2 and 3 make one each
+    // (profiles/coattn_bwd_active_rows.md).  The rows need no more registers in flight together than pass 2 holds
+    // anyway.  Same arithmetic in the same order.
     int32_t r1[SPL][KMAX], rb2[SPL][KMAX];
-    float4 v1[SPL][KMAX];
     float dp[KMAX];
 #pragma unroll
     for (int k = 0; k < KMAX; ++k) {
@@ -331,30 +343,35 @@ __global__ __launch_bounds__(256, (KMAX <= 10 && SPL == 1) ? 4 : 1) void coattn_
       for (int j = 0; j < SPL; ++j) {
         r1[j][k] = i1[kc * F + f[j]];
         rb2[j][k] = i2[kc * F + f[j]];
-        r1[j][k] = (uint32_t)r1[j][k] < a.n_rows ? r1[j][k] : 0;      // (the forward reported it: score_state_t.id_status)
-        rb2[j][k] = (uint32_t)rb2[j][k] < a.n_rows ? rb2[j][k] : 0;
       }
     }
-#pragma unroll
-    for (int k = 0; k < KMAX; ++k)
-#pragma unroll
-      for (int j = 0; j < SPL; ++j) v1[j][k] = ld4(table + (int64_t)r1[j][k] * D + coff[j]);
+    __builtin_amdgcn_sched_barrier(0);      // every id is requested before the first one is used
 #pragma unroll
     for (int k = 0; k < KMAX; ++k) {
       dp[k] = 0.f;
 #pragma unroll
       for (int j = 0; j < SPL; ++j) {
-        const bool live = ok[j] && k < K;
-        v1[j][k].x = live ? v1[j][k].x : 0.f; v1[j][k].y = live ? v1[j][k].y : 0.f;
-        v1[j][k].z = live ? v1[j][k].z : 0.f; v1[j][k].w = live ? v1[j][k].w : 0.f;
-        r1[j][k] = live ? r1[j][k] : 0;
-        rb2[j][k] = live ? rb2[j][k] : 0;
+        r1[j][k] = (uint32_t)r1[j][k] < a.n_rows ? r1[j][k] : 0;      // (the forward reported it: score_state_t.id_status)
+        rb2[j][k] = (uint32_t)rb2[j][k] < a.n_rows ? rb2[j][k] : 0;
       }
     }
 #pragma unroll
-    for (int k = 0; k < KMAX; ++k)
+    for (int j = 0; j < SPL; ++j) {
+      float4 v1[KMAX];
 #pragma unroll
-      for (int j = 0; j < SPL; ++j) dp[k] += dot4(v1[j][k], g1[j]);
+      for (int k = 0; k < KMAX; ++k) v1[k] = ld4(table + (int64_t)r1[j][k] * D + coff[j]);
+#pragma unroll
+      for (int k = 0; k < KMAX; ++k) rows_in_flight(v1[k], v1[KMAX - 1]);
+#pragma unroll
+      for (int k = 0; k < KMAX; ++k) {
+        const bool live = ok[j] && k < K;
+        v1[k].x = live ? v1[k].x : 0.f; v1[k].y = live ? v1[k].y : 0.f;
+        v1[k].z = live ? v1[k].z : 0.f; v1[k].w = live ? v1[k].w : 0.f;
+        r1[j][k] = live ? r1[j][k] : 0;
+        rb2[j][k] = live ? rb2[j][k] : 0;
+        dp[k] += dot4(v1[k], g1[j]);
+      }
+    }
     // softmax from the saved relu'd scores
     float r[KMAX], p[KMAX], gik[KMAX];
     float rmax = 0.f, gsum = 0.f;
@@ -406,14 +423,30 @@ __global__ __launch_bounds__(256, (KMAX <= 10 && SPL == 1) ? 4 : 1) void coattn_
       }
     }
     const float invK = 1.0f / (float)K;
-    // dw1 += dz_k seq1_k, then the seq2 rows: dw2 += dz_k seq2_k.  The seq1 rows are READ AGAIN here (cache hits:
-    // this wave fetched them a moment ago; masked uses carry row id 0, the all-zero row) instead of being held in
+    // Passes 2 and 3: dw1 += dz_k seq1_k over the seq1 rows, then dw2 += dz_k seq2_k over the seq2 rows, K rows in
+    // flight together each.  Every term carries dz_k = [r_k > 0] dr_k, so only the rows of the k whose relu was
+    // ACTIVE (r_k > 0 in rsave) are requested: an inactive k adds fma(0, row, acc) = acc whatever its row holds, and
+    // its load goes to row 0, the all-zero row, like every masked use (a select on the row id per lane, no branch:
+    // see the forward kernel's loads) -- one hot line instead of a gathered row.  A third of all (unit, k) are
+    // inactive on the cfg-3 batches: the kernel fetches 12 % less, in the same time (it is bound by its dependent
+    // round trips, not by bytes: profiles/coattn_bwd_active_rows.md).
+    // Pass 1 keeps all K rows: dp_k enters sum_k p_k dp_k for every k.  The atomic scatter's target row
+    // and its != 0 test keep the real id (an inactive k still adds p_k g1 / g2/K to its row): only the load moves.
+    // The only value that can differ: a table that already holds Inf/NaN in a row of an inactive k no longer poisons dw1/dw2.
+    // (CoattnArgs.all_rows, debug_flags bit 15: every row as before, the A/B.)
+    // The seq1 rows are READ AGAIN (cache hits: this wave fetched them a moment ago) instead of being held in
     // 40 VGPRs across the reductions and the softmax: 24 -> 10 spilled registers at 4 waves/SIMD, 0.262 -> 0.241 ms
+    bool act[KMAX];
+#pragma unroll
+    for (int k = 0; k < KMAX; ++k) act[k] = all_rows || (k < K && r[k] > 0.f);
 #pragma unroll
     for (int j = 0; j < SPL; ++j) {
       float4 xr[KMAX];
 #pragma unroll
-      for (int k = 0; k < KMAX; ++k) xr[k] = ld4(table + (int64_t)r1[j][k] * D + coff[j]);
+      for (int k = 0; k < KMAX; ++k) {
+        const int32_t lr = act[k] ? r1[j][k] : 0;      // the row LOADED; r1 stays the row the gradient goes to
+        xr[k] = ld4(table + (int64_t)lr * D + coff[j]);
+      }
 #pragma unroll
       for (int k = 0; k < KMAX; ++k) {
         dw1[j] = fma4(dz[k], xr[k], dw1[j]);
@@ -424,13 +457,15 @@ __global__ __launch_bounds__(256, (KMAX <= 10 && SPL == 1) ? 4 : 1) void coattn_
         }
       }
     }
-    // pass 2: the K seq2 rows, all in flight together (masked uses carry row id 0: the all-zero dummy row)
 #pragma unroll
     for (int j = 0; j < SPL; ++j) {
       const float4 g2k = make_float4(g2[j].x * invK, g2[j].y * invK, g2[j].z * invK, g2[j].w * invK);
       float4 y[KMAX];
 #pragma unroll
-      for (int k = 0; k < KMAX; ++k) y[k] = ld4(table + (int64_t)rb2[j][k] * D + coff[j]);
+      for (int k = 0; k < KMAX; ++k) {
+        const int32_t lr = act[k] ? rb2[j][k] : 0;
+        y[k] = ld4(table + (int64_t)lr * D + coff[j]);
+      }
 #pragma unroll
       for (int k = 0; k < KMAX; ++k) {
         dw2[j] = fma4(dz[k], y[k], dw2[j]);

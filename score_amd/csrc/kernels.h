@@ -100,6 +100,7 @@ struct CoattnArgs {
   // ids outside [0, n_rows) (tf.nn.embedding_lookup raises there, score.py:51-66) are read as the dummy row 0 and
   // reported: bit1 / bit2 of the call OR-ed into *id_status (optional device word, score_state_t.id_status)
   uint32_t n_rows; int32_t* id_status;
+  int all_rows;                               // backward, A/B (debug_flags bit 15): the rows of relu-inactive k are loaded too
 };
 int score_coattn_fwd_multi(CoattnArgs& a, int ncalls, int D, int B, hipStream_t s);
 int score_coattn_bwd_multi(CoattnArgs& a, int ncalls, int D, int B, float* const dW[2], float* scratch,
