@@ -940,6 +940,73 @@ int64_t score_pop_items_temp_bytes(int32_t n_items);
 int score_pop_items(const score_pop_items_t* a, int32_t* pop_items, int64_t cap_pop, int64_t* n_pop, void* temp,
                     int64_t temp_bytes, void* stream);
 
+/* ---- the raw log's remap on the device (csrc/logremap.hip) --------------------------------------- */
+/* feateng_tmall.py:30-133 / feateng_taobao.py:16-88 (dataprep.remap_tmall_log / remap_taobao_log): n_cols <= 8 raw int32 columns
+ * of n_events events, each one vocabulary.  The vocabularies are numbered one behind the other from 1 in column order, the
+ * values of a column in order of FIRST APPEARANCE in the log: ids[c][pos] = base_c + rank of the value's first log position
+ * among the column's distinct values, base_0 = 1, base_{c+1} = base_c + counts[c].  Per column a stable score_sort_pairs on
+ * (the value's 32-bit pattern, log position), two prefix sums and plain stores; the bases ride in a device word, so the whole
+ * remap waits for the stream ONCE, for the counts.  key_bits (1 .. 32): every column's patterns must fit it (a negative value
+ * needs 32); one that does not is found on the device and the count call returns SCORE_E_BADARG after its wait.
+ * Up to two feature-row tables: a table names an entity column and up to seven feature columns, and row id_e - base_e is
+ * [id_e, id_f1[last], id_f2[last], ...] with `last` the entity's LAST log position ("later rows overwrite earlier ones": the
+ * dict assignments of feateng_tmall.py:130-131 and feateng_taobao.py:81).
+ * struct_bytes = sizeof(score_log_remap_t): the calls refuse any other value.  Limits: n_events < 2^31, 1 + the sum of the
+ * counts < 2^31 (SCORE_E_SHAPE; the latter after the count call's wait); temp: score_log_remap_temp_bytes (SCORE_E_WORKSPACE,
+ * before any launch).  One workspace serves both calls. */
+#define SCORE_LOG_REMAP_MAX_COLS 8
+#define SCORE_LOG_REMAP_MAX_TABLES 2
+#define SCORE_LOG_REMAP_MAX_FEATS 7
+typedef struct {
+  int32_t entity, n_feat;                      /* column indices; the row is 1 + n_feat words wide */
+  int32_t feat[SCORE_LOG_REMAP_MAX_FEATS];
+  int32_t reserved;
+} score_log_table_t;
+
+typedef struct {
+  int64_t struct_bytes;
+  const int32_t* cols[SCORE_LOG_REMAP_MAX_COLS];   /* DEVICE int32 [n_events] each: the raw columns          */
+  int32_t* ids[SCORE_LOG_REMAP_MAX_COLS];          /* DEVICE int32 [n_events] each: the remapped columns     */
+  int64_t n_events;
+  int32_t n_cols, key_bits, n_tables, reserved;
+  score_log_table_t tables[SCORE_LOG_REMAP_MAX_TABLES];
+} score_log_remap_t;
+
+int64_t score_log_remap_temp_bytes(int64_t n_events, int32_t n_cols);
+
+/* In two calls.
+ *   rows == NULL: writes ids[c] for every column and counts[0 .. n_cols) (HOST int64), and leaves every table entity's last
+ *     log position per row in temp.  Waits for the stream once.
+ *   rows != NULL: HOST array of n_tables DEVICE pointers, rows[t] int32 [cap_rows[t], 1 + n_feat]; fills them from what the
+ *     first call left in temp and the ids it wrote (which must still be there), 16 bytes per store where a row is a multiple
+ *     of four words; nothing is written at or past row cap_rows[t].  No host wait.
+ * No atomics, no workgroup waits on another: the output is a pure function of the input. */
+int score_log_remap(const score_log_remap_t* a, int32_t* const* rows, const int64_t* cap_rows, int64_t* counts, void* temp,
+                    int64_t temp_bytes, void* stream);
+
+/* The time slices of a raw log, element-wise; no host wait.
+ *   SCORE_LOG_SLICES_TMALL (feateng_tmall.py:10-11,53-56): time = MMDD as an integer; t_idx = floor((day of 2015 - day of
+ *     05-01) / 15), negative before May 1 (floor, as Python's //).  A month outside 1 .. 12 or a day outside the month (2015 has
+ *     no February 29) sets *status (DEVICE int32, zeroed by the caller, sticky) to 1.  flag / keep / start_ts .. delta unused.
+ *   SCORE_LOG_SLICES_EPOCH (feateng_taobao.py:27-32): keep[i] = start_ts <= time[i] <= end_ts (both inclusive) and, where flag
+ *     is given, flag[i] != 0; t_idx = (time - start_ts) / delta for kept events, -1 for the others.  delta > 0. */
+#define SCORE_LOG_SLICES_TMALL 0
+#define SCORE_LOG_SLICES_EPOCH 1
+int score_log_slices(int32_t mode, const int32_t* time, const int32_t* flag, int64_t n_events, int32_t start_ts, int32_t end_ts,
+                     int32_t delta, int32_t* t_idx, int32_t* keep, int32_t* status, void* stream);
+
+/* Stable compaction of n_cols <= 8 columns by keep flags (any non-zero word keeps): cols_in / cols_out are HOST arrays of DEVICE
+ * pointers, cols_out[c] int32 [cap]; kept_pos (optional) int32 [cap] receives the kept events' log positions.  A prefix sum,
+ * *n_kept (HOST) after one stream wait, then one scatter -- not launched when nothing is kept; nothing is written at or past cap.
+ * temp: score_log_compact_temp_bytes(n_events). */
+int64_t score_log_compact_temp_bytes(int64_t n_events);
+/* How often score_log_remap and score_log_compact have waited for a stream in this process so far (host only): a test takes
+ * the difference around a call -- one per count call and per compaction, none per fill. */
+int score_log_host_waits(void);
+int score_log_compact(const int32_t* const* cols_in, int32_t* const* cols_out, int32_t n_cols, const int32_t* keep,
+                      int64_t n_events, int32_t* kept_pos, int64_t cap, int64_t* n_kept, void* temp, int64_t temp_bytes,
+                      void* stream);
+
 /* ---- "next" row f4: ranking metrics of an evaluation pass on the device ----------------------- */
 
 /* get_ranking_quality (train_score.py:104-142) without the host round trip of the predictions:

@@ -106,6 +106,18 @@ class PopItems(C.Structure):
                [(n, C.c_int32) for n in ("n_users", "n_items", "time_slice_num", "pop_standard", "max_iid", "reserved")]
 
 
+class LogTable(C.Structure):
+    """score_log_table_t"""
+    _fields_ = [("entity", C.c_int32), ("n_feat", C.c_int32), ("feat", C.c_int32 * 7), ("reserved", C.c_int32)]
+
+
+class LogRemap(C.Structure):
+    """score_log_remap_t (struct_bytes is its own size check, like TargetBuild's)"""
+    _fields_ = [("struct_bytes", C.c_int64), ("cols", C.c_void_p * 8), ("ids", C.c_void_p * 8), ("n_events", C.c_int64)] + \
+               [(n, C.c_int32) for n in ("n_cols", "key_bits", "n_tables", "reserved")] + [("tables", LogTable * 2)]
+
+
+LOG_SLICES_TMALL, LOG_SLICES_EPOCH = 0, 1            # SCORE_LOG_SLICES_*
 TARGET_SCAN_TILE, TARGET_SORT_TILE = 4096, 8192      # SCORE_TARGET_SCAN_TILE / SCORE_TARGET_SORT_TILE
 
 
@@ -161,6 +173,14 @@ _SIGS = {
                            C.c_int64, C.c_void_p],
     "score_pop_items_temp_bytes": [C.c_int32],
     "score_pop_items": [C.POINTER(PopItems), C.c_void_p, C.c_int64, C.POINTER(C.c_int64), C.c_void_p, C.c_int64, C.c_void_p],
+    "score_log_remap_temp_bytes": [C.c_int64, C.c_int32],
+    "score_log_remap": [C.POINTER(LogRemap), C.POINTER(C.c_void_p), C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.c_void_p,
+                        C.c_int64, C.c_void_p],
+    "score_log_slices": [C.c_int32, c_i, c_i, C.c_int64, C.c_int32, C.c_int32, C.c_int32, c_i, c_i, c_i, C.c_void_p],
+    "score_log_compact_temp_bytes": [C.c_int64],
+    "score_log_host_waits": [],
+    "score_log_compact": [C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.c_int32, c_i, C.c_int64, c_i, C.c_int64,
+                          C.POINTER(C.c_int64), C.c_void_p, C.c_int64, C.c_void_p],
     "score_param_layout": [C.POINTER(Config), C.POINTER(ParamEntry), C.c_int32, C.POINTER(C.c_int64),
                            C.POINTER(C.c_int64)],
     "score_workspace_layout": [C.POINTER(Config), C.c_int32, C.POINTER(Workspace)],

@@ -9,7 +9,9 @@ step path.
   gen_target_lines     code/gen_target.py:99-121       'uid,pos_iid,neg...' lines of one prediction slice
   gen_pop_items        code/gen_target.py:277-290      the popular-item list negatives may be drawn from
   sample_target_lines  code/sampling.py:31-37          1-in-N down-sampling of validation / test lines
-(targets.TargetStore.from_log(build="device") evaluates the three on the device, csrc/targetgen.hip.)
+  remap_taobao_log     code/feateng_taobao.py:16-88   the pv events of a time window; users, items, categories
+(targets.TargetStore.from_log(build="device") evaluates the three on the device, csrc/targetgen.hip; remap_tmall_log and
+remap_taobao_log(build="device") number the ids, fill the feature rows and cut the slices there, csrc/logremap.hip.)
 
 The reference enumerates each id vocabulary through ``list(set(...))`` (feateng_tmall.py:58-64), i.e. in
 Python's per-process string-hash order: its remap is not reproducible from run to run.  Here every
@@ -46,14 +48,28 @@ def _first_appearance(col):
     return rank[inv.reshape(-1)], len(uniq)
 
 
-def remap_tmall_log(log, age=None, gender=None):
+def _check_build(build):
+    if build not in ("host", "device"):
+        raise ValueError("build is 'host' or 'device': got %r" % (build,))
+
+
+def remap_tmall_log(log, age=None, gender=None, build="host", device=None):
     """log: int array [n, >=6] with columns user_id, item_id, cat_id, seller_id, brand_id, time_stamp(MMDD)
     (tests/golden/tmall_sample_log.npz).  age / gender: per-row arrays (the joined user profile,
     feateng_tmall.py:13-28); default = the synthesised profile uid % 9 / uid % 3.
 
     Returns a dict: uid, iid (remapped ids per row), t_idx, n_users, n_items, feature_size (the reference
     prints it as 'feat size', :104), user_rows [U, 3] = [uid, age_id, gender_id] and item_rows [I, 4] =
-    [iid, cat_id, seller_id, brand_id] (user_feat_dict / item_feat_dict, :125-133, keyed by row order)."""
+    [iid, cat_id, seller_id, brand_id] (user_feat_dict / item_feat_dict, :125-133, keyed by row order).
+
+    build="device" (needs a GPU): the six raw columns are uploaded once and everything is computed there
+    (csrc/logremap.hip), the same integers: uid, iid and t_idx are int32 tensors on the device, a further key time_key is the
+    raw MMDD column there (what PointLogStore orders histories by), and user_rows / item_rows are numpy arrays, downloaded
+    once (TemporalGraph keeps its row tables on the host).  The default profile is computed from the uploaded user column.
+    An invalid MMDD raises ValueError, as datetime.date does on the host."""
+    _check_build(build)
+    if build == "device":
+        return _remap_tmall_device(log, age, gender, device)
     log = np.asarray(log)
     raw_u, raw_i, raw_c, raw_s, raw_b = (log[:, j].astype(np.int64) for j in range(5))
     if age is None:
@@ -77,6 +93,106 @@ def remap_tmall_log(log, age=None, gender=None):
     item_rows[iid - 1 - U] = np.stack([iid, cid, sid, bid], axis=1)
     return dict(uid=uid, iid=iid, t_idx=tmall_slice_index(log[:, 5]), n_users=U, n_items=I, feature_size=int(base),
                 user_rows=user_rows, item_rows=item_rows, vocab_sizes=tuple(sizes))
+
+
+def _remap_tmall_device(log, age, gender, device):
+    import torch
+    from . import logremap as lr
+    from .targets import device_i32
+    dev = lr.device_of(device, "remap_tmall_log(build='device')")
+    with torch.cuda.device(dev):
+        raw, wide = lr.upload_columns(log, 6, dev)                 # [6, n]: the one upload
+        n = int(raw.shape[1])
+        if n == 0:
+            raise ValueError("remap_tmall_log(build='device'): the log is empty")
+        prof = [torch.remainder(raw[0], m).to(torch.int32) if a is None else device_i32(np.asarray(a).astype(np.int64), dev)
+                for a, m in ((age, 9), (gender, 3))]
+        if any(int(p.numel()) != n for p in prof):
+            raise ValueError("age / gender must hold one value per log row")
+        cols = [raw[j] for j in range(5)] + prof
+        status = torch.zeros((1,), dtype=torch.int32, device=dev)
+        t_idx = lr.log_slices_tmall(raw[5], status)
+        ext = torch.stack([torch.stack([c.amin() for c in cols]).amin().long(), torch.stack([c.amax() for c in cols]).amax().long(),
+                           status[0].long(), wide]).cpu().tolist()  # one read-back: the key width (and the two status words)
+        if ext[3]:
+            raise ValueError(lr.WIDE_MESSAGE)
+        if ext[2]:
+            raise ValueError("time_stamp must be a date MMDD of 2015: month must be in 1..12, day in the month's range")
+        ids, sizes, rows = lr.log_remap(cols, lr.key_bits_of(ext[0], ext[1]), tables=((0, (5, 6)), (1, (2, 3, 4))))
+    return dict(uid=ids[0], iid=ids[1], t_idx=t_idx, time_key=raw[5], n_users=sizes[0], n_items=sizes[1],
+                feature_size=1 + int(sum(sizes)), user_rows=rows[0], item_rows=rows[1], vocab_sizes=tuple(sizes))
+
+
+TAOBAO_START_DATE, TAOBAO_END_DATE = "2017-11-25", "2017-12-04"    # feateng_taobao.py:11-12 (midnights, local time there)
+TAOBAO_SLICE_SECONDS = 24 * 3600                                   # feateng_taobao.py:13
+
+
+def remap_taobao_log(log, start_ts, end_ts, delta=TAOBAO_SLICE_SECONDS, build="host", device=None):
+    """feateng_taobao.py:16-88 on an in-memory log: int array [n, 5] with columns user, item, category, is_pv (1 where the
+    behaviour type is 'pv', else 0) and unix time.  An event is kept iff start_ts <= time <= end_ts (both inclusive: :27 drops
+    `< START or > END`) and is_pv != 0 (:29); its slice is (time - start_ts) // delta (:32).  Users, items and categories of the
+    KEPT events are numbered one behind the other from 1, each in order of first appearance among the kept events (the
+    reference: set order, see the module header).
+
+    start_ts / end_ts: the reference takes time.mktime of TAOBAO_START_DATE and TAOBAO_END_DATE (2017-11-25 and 2017-12-04,
+    00:00), which follows the machine's time zone -- so both are parameters here (UTC: 1511568000 and 1512345600).
+
+    Returns a dict: uid, iid, t_idx (per kept event), n_users, n_items, feature_size, item_rows [I, 2] = [iid, cid] with the
+    category of the item's LAST kept event (item_feat_dict, :81), user_rows [U, 1] = [uid], vocab_sizes (users, items,
+    categories) and kept, the log positions of the kept events.  build="device" (needs a GPU): one upload, then slices,
+    compaction and remap on the device (csrc/logremap.hip); uid, iid, t_idx and kept are int32 tensors there, the row tables
+    numpy."""
+    _check_build(build)
+    start_ts, end_ts, delta = int(start_ts), int(end_ts), int(delta)
+    if delta <= 0 or end_ts < start_ts:
+        raise ValueError("remap_taobao_log: delta must be positive and end_ts >= start_ts")
+    if build == "device":
+        return _remap_taobao_device(log, start_ts, end_ts, delta, device)
+    log = np.asarray(log)
+    t = log[:, 4].astype(np.int64)
+    kept = np.flatnonzero((t >= start_ts) & (t <= end_ts) & (log[:, 3] != 0))
+    base = 1
+    ids, sizes = [], []
+    for j in range(3):                                   # users, items, categories (:48-61)
+        r, n = _first_appearance(log[kept, j].astype(np.int64))
+        ids.append((r + base).astype(np.int32))
+        sizes.append(n)
+        base += n
+    uid, iid, cid = ids
+    U, I = sizes[0], sizes[1]
+    item_rows = np.zeros((I, 2), dtype=np.int32)
+    item_rows[iid - 1 - U] = np.stack([iid, cid], axis=1)          # later events overwrite earlier ones (:81)
+    return dict(uid=uid, iid=iid, t_idx=((t[kept] - start_ts) // delta).astype(np.int32), n_users=U, n_items=I,
+                feature_size=int(base), item_rows=item_rows, user_rows=np.arange(1, U + 1, dtype=np.int32).reshape(U, 1),
+                vocab_sizes=tuple(sizes), kept=kept)
+
+
+def _remap_taobao_device(log, start_ts, end_ts, delta, device):
+    import torch
+    from . import logremap as lr
+    dev = lr.device_of(device, "remap_taobao_log(build='device')")
+    if not -2 ** 31 <= start_ts <= end_ts < 2 ** 31:
+        raise ValueError("the device remap takes int32 times: start_ts / end_ts lie outside")
+    with torch.cuda.device(dev):
+        raw, wide = lr.upload_columns(log, 5, dev)                 # [5, n]: the one upload
+        empty = torch.empty((0,), dtype=torch.int32, device=dev)
+        cols, kept = [empty] * 4, empty
+        if int(raw.shape[1]):
+            t_idx, keep = lr.log_slices_epoch(raw[4], raw[3], start_ts, end_ts, delta)
+            cols, kept = lr.log_compact([raw[0], raw[1], raw[2], t_idx], keep)
+        if int(kept.numel()) == 0:
+            if int(wide):
+                raise ValueError(lr.WIDE_MESSAGE)
+            z = lambda w: np.zeros((0, w), dtype=np.int32)
+            return dict(uid=empty, iid=empty, t_idx=empty, n_users=0, n_items=0, feature_size=1, item_rows=z(2), user_rows=z(1),
+                        vocab_sizes=(0, 0, 0), kept=empty)
+        ext = torch.stack([torch.stack([c.amin() for c in cols[:3]]).amin().long(),
+                           torch.stack([c.amax() for c in cols[:3]]).amax().long(), wide]).cpu().tolist()   # the key width's read-back
+        if ext[2]:
+            raise ValueError(lr.WIDE_MESSAGE)
+        ids, sizes, rows = lr.log_remap(cols[:3], lr.key_bits_of(ext[0], ext[1]), tables=((0, ()), (1, (2,))))
+    return dict(uid=ids[0], iid=ids[1], t_idx=cols[3], n_users=sizes[0], n_items=sizes[1], feature_size=1 + int(sum(sizes)),
+                item_rows=rows[1], user_rows=rows[0], vocab_sizes=tuple(sizes), kept=kept)
 
 
 TAG_TARGET_NEG, TAG_TARGET_POP, TAG_TARGET_SAMPLE = 4, 5, 6      # next to graph.TAG_*: the cell of a draw is the line's user id
@@ -219,6 +335,19 @@ def _check_targets(targets, draws, sample_factor):
         raise ValueError("sample_factor= needs targets='device' (sample_target_lines down-samples host lines)")
 
 
+def _check_remap(remap, build):
+    if remap not in ("host", "device"):
+        raise ValueError("remap is 'host' or 'device': got %r" % (remap,))
+    if remap == "device" and build != "device":
+        raise ValueError("remap='device' needs build='device': its columns are born on the device and stay there")
+
+
+def _host_cols(cols):
+    """the remap's three columns as numpy, for the host target rule (a download where the remap ran on the device)"""
+    from .targets import _host
+    return tuple(_host(c) for c in cols)
+
+
 def _device_log(r, device=None):
     """the remapped log's three columns uploaded once -> int32 tensors"""
     import torch
@@ -229,23 +358,30 @@ def _device_log(r, device=None):
     return tuple(device_i32(r[k], dev) for k in ("uid", "iid", "t_idx"))
 
 
-def tmall_pipeline(log, seed=11, build="host", draws="stream", targets="host", sample_factor=None):
+def tmall_pipeline(log, seed=11, build="host", draws="stream", targets="host", sample_factor=None, remap="host"):
     """Raw Tmall log -> (TemporalGraph, remap dict, {'train' | 'validation' | 'test': target lines}).  Train
     lines carry 1 negative (train_score.py:18), validation / test lines 99 (:19).  build / draws: TemporalGraph.from_log's.
     targets: "host" (the default) gen_target_lines with the same draws; "device" (needs a GPU and draws="cell") the log is
     uploaded once and the dict holds targets.TargetStore objects built from it (csrc/targetgen.hip), which the loaders take in
     place of lines; sample_factor (one number, or a dict per split) then down-samples the validation / test lines as
-    sampling.py does."""
+    sampling.py does.  remap: "host" (the default) remap_tmall_log in numpy; "device" (needs build="device") the RAW log is
+    uploaded once, remapped there (csrc/logremap.hip), and the graph and the targets are built from those columns -- the dict
+    then holds device tensors under uid / iid / t_idx / time_key."""
     from .graph import TemporalGraph
     _check_targets(targets, draws, sample_factor)
-    r = remap_tmall_log(log)
+    _check_remap(remap, build)
+    r = remap_tmall_log(log, build=remap)
     c = TMALL
-    cols = _device_log(r) if targets == "device" and build == "device" else (r["uid"], r["iid"], r["t_idx"])
+    if remap == "device":
+        cols = (r["uid"], r["iid"], r["t_idx"])
+    else:
+        cols = _device_log(r) if targets == "device" and build == "device" else (r["uid"], r["iid"], r["t_idx"])
     g = TemporalGraph.from_log(cols[0], cols[1], cols[2], r["n_users"], r["n_items"], c["graph_time_slice_num"],
                                r["user_rows"], r["item_rows"], max_1hop=c["max_1hop"], max_2hop=c["max_2hop"], seed=seed,
                                build=build, draws=draws)
     if targets == "device" and build != "device":
         cols = _device_log(r)
+    host_cols = _host_cols(cols) if remap == "device" and targets != "device" else (r["uid"], r["iid"], r["t_idx"])
     out = {}
     for name, pt, neg in TMALL_SPLITS:
         pt, neg = c[pt], c[neg]
@@ -254,7 +390,7 @@ def tmall_pipeline(log, seed=11, build="host", draws="stream", targets="host", s
             out[name] = TargetStore.from_log(cols[0], cols[1], cols[2], r["n_users"], r["n_items"], pt, neg, c["start_time"],
                                              seed + pt, build="device", sample_factor=_split_factor(sample_factor, name))
         else:
-            out[name] = gen_target_lines(r["uid"], r["iid"], r["t_idx"], r["n_users"], r["n_items"], pt, neg,
+            out[name] = gen_target_lines(host_cols[0], host_cols[1], host_cols[2], r["n_users"], r["n_items"], pt, neg,
                                          c["start_time"], seed + pt, draws=draws)
     return g, r, out
 
@@ -325,21 +461,30 @@ def write_point_files(directory, target_lines, user_hist_lines, item_hist_lines,
 
 
 def tmall_point_stores(log, seed=11, dual=True, batch_size=None, build="device", device=None, targets="host", draws="stream",
-                       sample_factor=None):
+                       sample_factor=None, remap="host"):
     """Raw Tmall log -> ({'train' | 'validation' | 'test': PointLogStore}, remap dict): the point baselines' data path on the
     log SCoRe trains from (tmall_pipeline's target lines: the same seed, draws and targets give the same lines).  Train lines
     carry 1 negative, validation / test lines 99; histories are cut at the reference's 300.  batch_size: a dict per split or
     one number; default 200 for train (a multiple of 2) and TMALL's eval_batch_size for the others.  targets / draws /
-    sample_factor: tmall_pipeline's -- with targets="device" the lines are built on the device and handed over as tensors."""
+    sample_factor: tmall_pipeline's -- with targets="device" the lines are built on the device and handed over as tensors.
+    remap: tmall_pipeline's -- with remap="device" (needs build="device") the raw log is uploaded once and the remap's device
+    columns, time_key among them, serve the lines and the histories."""
     from .pointdata import PointLogStore
     _check_targets(targets, draws, sample_factor)
-    r = remap_tmall_log(log)
+    _check_remap(remap, build)
+    r = remap_tmall_log(log, build=remap, device=device)
     c = TMALL
-    cols = _device_log(r, device) if targets == "device" else None
-    log4 = (r["uid"], r["iid"], np.asarray(log)[:, 5], r["t_idx"])
-    if targets == "device" and build == "device":                  # the uploaded log serves the histories too
-        from .targets import device_i32
-        log4 = (cols[0], cols[1], device_i32(log4[2], cols[0].device), cols[2])
+    if remap == "device":
+        cols = (r["uid"], r["iid"], r["t_idx"])
+        log4 = (cols[0], cols[1], r["time_key"], cols[2])
+        host_cols = _host_cols(cols) if targets != "device" else None
+    else:
+        cols = _device_log(r, device) if targets == "device" else None
+        log4 = (r["uid"], r["iid"], np.asarray(log)[:, 5], r["t_idx"])
+        host_cols = log4[0], log4[1], log4[3]
+        if targets == "device" and build == "device":              # the uploaded log serves the histories too
+            from .targets import device_i32
+            log4 = (cols[0], cols[1], device_i32(log4[2], cols[0].device), cols[2])
     stores = {}
     for name, pt, neg in TMALL_SPLITS:
         pt, neg = c[pt], c[neg]
@@ -348,8 +493,8 @@ def tmall_point_stores(log, seed=11, dual=True, batch_size=None, build="device",
             lines = TargetStore.from_log(cols[0], cols[1], cols[2], r["n_users"], r["n_items"], pt, neg, c["start_time"],
                                          seed + pt, build="device", sample_factor=_split_factor(sample_factor, name))
         else:
-            lines = gen_target_lines(r["uid"], r["iid"], r["t_idx"], r["n_users"], r["n_items"], pt, neg, c["start_time"],
-                                     seed + pt, draws=draws)
+            lines = gen_target_lines(host_cols[0], host_cols[1], host_cols[2], r["n_users"], r["n_items"], pt, neg,
+                                     c["start_time"], seed + pt, draws=draws)
         B = batch_size.get(name) if isinstance(batch_size, dict) else batch_size
         if B is None:
             B = 200 if name == "train" else c["eval_batch_size"]
