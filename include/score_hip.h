@@ -924,6 +924,38 @@ int64_t score_target_build_temp_bytes(int64_t n_events, int32_t n_users);
 int score_target_build(const score_target_build_t* a, int32_t* line_user, int32_t* line_items, int64_t cap_lines,
                        int64_t* n_lines, void* temp, int64_t temp_bytes, void* stream);
 
+/* How often score_target_build and score_target_build_lists have waited for a stream in this process so far (host only): one
+ * per count call, none per fill. */
+int score_target_host_waits(void);
+
+/* CCMR's target rule (gen_target.py:79-96; dataprep.gen_target_lines(draws="cell", neg_lists=...)): score_target_build with the
+ * users' own negatively rated items in front of the draws.  neg_off int64 [n_users + 1] and neg_items int32 [n_neg] are a CSR
+ * over uid = 1 .. n_users (score_neg_lists_build): negative j of user u is neg_items[neg_off[u - 1] + j] where
+ * j < neg_off[u] - neg_off[u - 1], otherwise the draw score_target_build makes at position j (the same key, tag and j, so with
+ * empty lists the output is score_target_build's word for word, and under one seed a user's padding is the same for every
+ * pred_time).  Eligibility, the positive and the line order come from `build` alone.  struct_bytes =
+ * sizeof(score_target_lists_t) and build.struct_bytes = sizeof(score_target_build_t): the calls refuse any other value.  The
+ * same two calls (count: one stream wait; fill: none, 16-byte stores where a line's words allow, nothing at or past
+ * cap_lines), limits and workspace (score_target_build_temp_bytes) as score_target_build; n_neg < 2^31 (SCORE_E_SHAPE).  A list
+ * whose bounds do not lie in 0 .. n_neg in ascending order is taken as empty. */
+typedef struct {
+  int64_t struct_bytes;
+  score_target_build_t build;
+  const int64_t* neg_off; const int32_t* neg_items; int64_t n_neg;
+} score_target_lists_t;
+
+int score_target_build_lists(const score_target_lists_t* a, int32_t* line_user, int32_t* line_items, int64_t cap_lines,
+                             int64_t* n_lines, void* temp, int64_t temp_bytes, void* stream);
+
+/* user_neg_dict (feateng_ccmr.py:173-183; targets.UserNegLists) from the negative events neg_uid / neg_iid int32 [n_neg] in log
+ * order: off int64 [n_users + 1], items int32 [n_neg]; the items of uid u are items[off[u - 1] .. off[u]) in log order,
+ * duplicates kept.  An event whose uid lies outside 1 .. n_users joins no list: off[n_users] words of items are used, the rest
+ * is zero.  A stable score_sort_pairs on (uid, log position), a gather and a binary search per user; no host wait; n_neg = 0
+ * is allowed (off is all zero).  temp: score_neg_lists_temp_bytes(n_neg) (SCORE_E_WORKSPACE, before any launch). */
+int64_t score_neg_lists_temp_bytes(int64_t n_neg);
+int score_neg_lists_build(const int32_t* neg_uid, const int32_t* neg_iid, int64_t n_neg, int32_t n_users, int64_t* off,
+                          int32_t* items, void* temp, int64_t temp_bytes, void* stream);
+
 /* The popular-item list (gen_target.py:277-290, dataprep.gen_pop_items): the ids n_users + 1 + i, ascending, of the items i
  * with at least pop_standard non-empty slices in item_off1 int64 [n_items * time_slice_num + 1] (a graph's item side) and
  * id <= max_iid.  struct_bytes = sizeof(score_pop_items_t).  Two calls like score_target_build: pop_items == NULL counts
@@ -1006,6 +1038,42 @@ int score_log_host_waits(void);
 int score_log_compact(const int32_t* const* cols_in, int32_t* const* cols_out, int32_t n_cols, const int32_t* keep,
                       int64_t n_events, int32_t* kept_pos, int64_t cap, int64_t* n_kept, void* temp, int64_t temp_bytes,
                       void* stream);
+
+/* ---- CCMR's rating log on the device (csrc/ccmr.hip) ------------------------------------------------ */
+/* feateng_ccmr.py:24-44,119-171 (dataprep.remap_ccmr_log) in one call without a host wait.  user / item / rating / date int32
+ * [n_events]: the raw log, date = YYYYMMDD as an integer.  Per event: uid = user + 1, iid = item + 1 + n_users, day =
+ * the date's day number (datetime.date.toordinal(): 0001-01-01 is 1; integer civil-date arithmetic, no table), t_idx =
+ * (day - start_day) / delta_days truncated TOWARDS ZERO (a date 1 .. delta_days - 1 days before the start lies in slice 0),
+ * keep_pos = 1 iff rating is 4 or 5, keep_neg = 1 for every other rating.  A date datetime.date refuses (year outside 1 .. 9999,
+ * month, day of the month, February 29 outside a leap year), a user outside [0, n_users) or an item outside [0, n_items) sets
+ * its status word to 1; that event gets zeros, slice -1 and neither flag.
+ * movie[0 .. 4] int32 [n_movies]: raw item, first director, actor, genre, nation of a movie_info line, -1 = empty.  item_rows
+ * int32 [n_items, 5] = [iid, did, aid, gid, nid] from the item's FIRST line (feateng_ccmr.py:167): a present feature f of
+ * field k is 1 + f + n_users + n_items + vocab[0] + .. + vocab[k - 1], an empty one the field's last id n_users + n_items +
+ * vocab[0] + .. + vocab[k]; vocab counts that "none" entry, so f must lie in [0, vocab[k] - 1).  An item without a line gets the
+ * four "none" ids.  status int32 [SCORE_CCMR_STATUS_WORDS] (DEVICE, zeroed by the call): SCORE_CCMR_ST_MISSING receives the
+ * number of items that occur among the positive events and have no line, the other words 0 or 1.
+ * struct_bytes = sizeof(score_ccmr_prep_t).  Limits: n_events, n_movies, 1 + n_users + n_items + the vocabularies < 2^31
+ * (SCORE_E_SHAPE); temp: score_ccmr_prep_temp_bytes (SCORE_E_WORKSPACE); both before any launch.  n_movies = 0 is allowed. */
+#define SCORE_CCMR_STATUS_WORDS 8
+#define SCORE_CCMR_ST_DATE 0
+#define SCORE_CCMR_ST_USER 1
+#define SCORE_CCMR_ST_ITEM 2
+#define SCORE_CCMR_ST_MOVIE_ITEM 3
+#define SCORE_CCMR_ST_FEATURE 4
+#define SCORE_CCMR_ST_MISSING 5
+typedef struct {
+  int64_t struct_bytes;
+  const int32_t* user; const int32_t* item; const int32_t* rating; const int32_t* date;
+  const int32_t* movie[5];
+  int64_t n_events, n_movies;
+  int32_t n_users, n_items, vocab[4], start_day, delta_days;
+  int32_t* uid; int32_t* iid; int32_t* t_idx; int32_t* day; int32_t* keep_pos; int32_t* keep_neg;
+  int32_t* item_rows; int32_t* status;
+} score_ccmr_prep_t;
+
+int64_t score_ccmr_prep_temp_bytes(int64_t n_movies, int32_t n_items);
+int score_ccmr_prep(const score_ccmr_prep_t* a, void* temp, int64_t temp_bytes, void* stream);
 
 /* ---- "next" row f4: ranking metrics of an evaluation pass on the device ----------------------- */
 

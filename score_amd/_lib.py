@@ -100,6 +100,20 @@ class TargetBuild(C.Structure):
                [("seed", C.c_uint64), ("pop_items", C.c_void_p), ("n_pop", C.c_int64)]
 
 
+class TargetLists(C.Structure):
+    """score_target_lists_t (struct_bytes is its own size check; so is build.struct_bytes)"""
+    _fields_ = [("struct_bytes", C.c_int64), ("build", TargetBuild), ("neg_off", C.c_void_p), ("neg_items", C.c_void_p),
+                ("n_neg", C.c_int64)]
+
+
+class CcmrPrep(C.Structure):
+    """score_ccmr_prep_t (struct_bytes is its own size check)"""
+    _fields_ = [("struct_bytes", C.c_int64)] + [(n, C.c_void_p) for n in ("user", "item", "rating", "date")] + \
+               [("movie", C.c_void_p * 5), ("n_events", C.c_int64), ("n_movies", C.c_int64), ("n_users", C.c_int32),
+                ("n_items", C.c_int32), ("vocab", C.c_int32 * 4), ("start_day", C.c_int32), ("delta_days", C.c_int32)] + \
+               [(n, C.c_void_p) for n in ("uid", "iid", "t_idx", "day", "keep_pos", "keep_neg", "item_rows", "status")]
+
+
 class PopItems(C.Structure):
     """score_pop_items_t (struct_bytes is its own size check)"""
     _fields_ = [("struct_bytes", C.c_int64), ("item_off1", C.c_void_p)] + \
@@ -119,6 +133,8 @@ class LogRemap(C.Structure):
 
 LOG_SLICES_TMALL, LOG_SLICES_EPOCH = 0, 1            # SCORE_LOG_SLICES_*
 TARGET_SCAN_TILE, TARGET_SORT_TILE = 4096, 8192      # SCORE_TARGET_SCAN_TILE / SCORE_TARGET_SORT_TILE
+CCMR_STATUS_WORDS = 8                                # SCORE_CCMR_STATUS_WORDS
+CCMR_ST_DATE, CCMR_ST_USER, CCMR_ST_ITEM, CCMR_ST_MOVIE_ITEM, CCMR_ST_FEATURE, CCMR_ST_MISSING = range(6)     # SCORE_CCMR_ST_*
 
 
 class AdamTable(C.Structure):
@@ -171,6 +187,13 @@ _SIGS = {
     "score_target_build_temp_bytes": [C.c_int64, C.c_int32],
     "score_target_build": [C.POINTER(TargetBuild), C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(C.c_int64), C.c_void_p,
                            C.c_int64, C.c_void_p],
+    "score_target_host_waits": [],
+    "score_target_build_lists": [C.POINTER(TargetLists), C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(C.c_int64), C.c_void_p,
+                                 C.c_int64, C.c_void_p],
+    "score_neg_lists_temp_bytes": [C.c_int64],
+    "score_neg_lists_build": [c_i, c_i, C.c_int64, C.c_int32, C.c_void_p, c_i, C.c_void_p, C.c_int64, C.c_void_p],
+    "score_ccmr_prep_temp_bytes": [C.c_int64, C.c_int32],
+    "score_ccmr_prep": [C.POINTER(CcmrPrep), C.c_void_p, C.c_int64, C.c_void_p],
     "score_pop_items_temp_bytes": [C.c_int32],
     "score_pop_items": [C.POINTER(PopItems), C.c_void_p, C.c_int64, C.POINTER(C.c_int64), C.c_void_p, C.c_int64, C.c_void_p],
     "score_log_remap_temp_bytes": [C.c_int64, C.c_int32],

@@ -18,8 +18,13 @@
 //   one per lane, those between four per lane.  A line of 1 + neg = 100 words is 400 bytes = 25 * 16, so every such line
 //   starts on a boundary and takes the 16-byte stores alone; a width that is no multiple of 4 words (5, 7, 11, 101 in the
 //   tests) puts line starts 0, 4, 8 and 12 bytes past one.
+// score_target_build_lists (CCMR's user_neg_dict, gen_target.py:79-96): the same two calls with one more source per negative
+//   word: negative j of user u is neg_items[neg_off[u - 1] + j] where j is below the user's list length, else the draw above at
+//   the same j.  The fill kernel is the one above, compiled a second time with the list lookup in tg_word.
+// Host waits: one per count call (the line count's read-back), none per fill; score_target_host_waits counts them.
 // score_pop_items: per item the count of non-empty slices, a flag, the scan, a compaction in id order.
 // No atomics, no workgroup waits on another: every array is a pure function of the input.
+#include <atomic>
 #include "common.h"
 #include "cellkey.h"
 #include "scan.h"
@@ -67,18 +72,23 @@ __global__ __launch_bounds__(TG_THREADS) void tg_flag_kernel(const uint32_t* __r
 
 struct Fill {
   const int32_t* uid; const int32_t* iid; const int32_t* ev; const int64_t* lidx; const int32_t* pop;
+  const int64_t* noff; const int32_t* nitems;                      // the users' negative lists (score_target_build_lists)
   int32_t* line_user; int32_t* line_items;
-  int64_t n, cap_lines, n_pop;
+  int64_t n, cap_lines, n_pop, n_neg;
   int32_t U, I, per;
   uint64_t seed;
 };
 
-__device__ __forceinline__ int32_t tg_word(const Fill& a, uint64_t h, int32_t pos, int32_t w) {
+// lbase / llen: where the user's list starts in nitems and how many of its entries the line takes (LISTS only)
+template <bool LISTS>
+__device__ __forceinline__ int32_t tg_word(const Fill& a, uint64_t h, int32_t pos, int32_t w, int64_t lbase, int32_t llen) {
   if (w == 0) return pos;
+  if (LISTS && w - 1 < llen) return a.nitems[lbase + (w - 1)];
   const uint64_t k = gb_key(h, (uint64_t)(w - 1));
   return a.pop ? a.pop[(k * (uint64_t)a.n_pop) >> 32] : (int32_t)((int64_t)a.U + 1 + (int64_t)((k * (uint64_t)a.I) >> 32));
 }
 
+template <bool LISTS>
 __global__ __launch_bounds__(TG_THREADS) void tg_fill_kernel(Fill a) {
   const int lane = threadIdx.x & 63;
   const int64_t wave = ((int64_t)blockIdx.x * TG_THREADS + threadIdx.x) >> 6, nwaves = (int64_t)gridDim.x * (TG_THREADS / 64);
@@ -93,19 +103,26 @@ __global__ __launch_bounds__(TG_THREADS) void tg_fill_kernel(Fill a) {
       const int32_t u = a.uid[v], pos = a.iid[v];
       if (u < 1 || u > a.U) continue;                               // (never with the count call's own ev)
       const uint64_t h = gb_cell_hash(a.seed, a.pop ? TAG_POP : TAG_NEG, (uint64_t)u);
+      int64_t lbase = 0;
+      int32_t llen = 0;
+      if (LISTS) {
+        const int64_t b = a.noff[u - 1], e = a.noff[u];
+        if (b >= 0 && e >= b && e <= a.n_neg) { lbase = b; llen = (int32_t)(e - b < (int64_t)a.per ? e - b : (int64_t)a.per); }
+      }
       int32_t* row = a.line_items + l * a.per;
       if (lane == 0) a.line_user[l] = u;
       int32_t head = (int32_t)(((16u - (uint32_t)(reinterpret_cast<uintptr_t>(row) & 15u)) & 15u) >> 2);
       head = head < a.per ? head : a.per;
       const int32_t nvec = (a.per - head) >> 2, tail = head + 4 * nvec;
-      if (lane < head) row[lane] = tg_word(a, h, pos, lane);
+      const auto word = [&](int32_t w) { return tg_word<LISTS>(a, h, pos, w, lbase, llen); };
+      if (lane < head) row[lane] = word(lane);
       for (int32_t c = lane; c < nvec; c += 64) {
         const int32_t w = head + 4 * c;
         int4 x;
-        x.x = tg_word(a, h, pos, w); x.y = tg_word(a, h, pos, w + 1); x.z = tg_word(a, h, pos, w + 2); x.w = tg_word(a, h, pos, w + 3);
+        x.x = word(w); x.y = word(w + 1); x.z = word(w + 2); x.w = word(w + 3);
         *reinterpret_cast<int4*>(row + w) = x;
       }
-      if (tail + lane < a.per) row[tail + lane] = tg_word(a, h, pos, tail + lane);      // (fewer than 4 words)
+      if (tail + lane < a.per) row[tail + lane] = word(tail + lane);                    // (fewer than 4 words)
     }
   }
 }
@@ -183,7 +200,10 @@ PopTemp pop_carve(void* temp, int64_t I) {
   return t;
 }
 
+std::atomic<int> g_host_waits{0};      // every wait for a stream in this file goes through read_total
+
 int read_total(const int64_t* dev, int64_t* host, hipStream_t s) {
+  g_host_waits.fetch_add(1, std::memory_order_relaxed);
   hipError_t e = hipMemcpyAsync(host, dev, sizeof(int64_t), hipMemcpyDeviceToHost, s);
   if (e == hipSuccess) e = hipStreamSynchronize(s);
   return e == hipSuccess ? 0 : (int)e;
@@ -196,8 +216,11 @@ extern "C" int64_t score_target_build_temp_bytes(int64_t n_events, int32_t n_use
   return carve(nullptr, n_events, n_users).total_bytes;
 }
 
-extern "C" int score_target_build(const score_target_build_t* a, int32_t* line_user, int32_t* line_items, int64_t cap_lines,
-                                  int64_t* n_lines, void* temp, int64_t temp_bytes, void* stream) {
+namespace {
+
+// both entry points: noff == nullptr is score_target_build
+int tg_build(const score_target_build_t* a, const int64_t* noff, const int32_t* nitems, int64_t n_neg, int32_t* line_user,
+             int32_t* line_items, int64_t cap_lines, int64_t* n_lines, void* temp, int64_t temp_bytes, void* stream) {
   if (!a || a->struct_bytes != (int64_t)sizeof(score_target_build_t)) return SCORE_E_BADARG;
   if (!a->uid || !a->iid || !a->t_idx || !temp) return SCORE_E_BADARG;
   if (a->n_events <= 0 || a->n_users <= 0 || a->n_items <= 0 || a->neg_sample_num < 0 || a->sample_factor < 0 || a->n_pop < 0)
@@ -215,12 +238,15 @@ extern "C" int score_target_build(const score_target_build_t* a, int32_t* line_u
   if (line_user) {
     Fill f;
     f.uid = a->uid; f.iid = a->iid; f.ev = t.ev; f.lidx = t.lidx; f.pop = a->pop_items;
+    f.noff = noff; f.nitems = nitems; f.n_neg = n_neg;
     f.line_user = line_user; f.line_items = line_items;
     f.n = n; f.cap_lines = cap_lines; f.n_pop = a->n_pop;
     f.U = U; f.I = a->n_items; f.per = 1 + a->neg_sample_num;
     f.seed = a->seed;
     const int64_t groups = cdiv64(cdiv64(n, 64), TG_THREADS / 64);
-    hipLaunchKernelGGL(tg_fill_kernel, dim3((unsigned)(groups < 8192 ? groups : 8192)), dim3(TG_THREADS), 0, s, f);
+    const dim3 grid((unsigned)(groups < 8192 ? groups : 8192));
+    if (noff) hipLaunchKernelGGL(tg_fill_kernel<true>, grid, dim3(TG_THREADS), 0, s, f);
+    else hipLaunchKernelGGL(tg_fill_kernel<false>, grid, dim3(TG_THREADS), 0, s, f);
     SCORE_CHECK_LAUNCH();
     return 0;
   }
@@ -238,6 +264,24 @@ extern "C" int score_target_build(const score_target_build_t* a, int32_t* line_u
   SCORE_CHECK_LAUNCH();
   SCORE_TRY(gb_scan(t.flag, n, t.bsum, t.lidx, s));
   return read_total(t.lidx + n, n_lines, s);
+}
+
+}  // namespace
+
+extern "C" int score_target_host_waits(void) { return g_host_waits.load(std::memory_order_relaxed); }
+
+extern "C" int score_target_build(const score_target_build_t* a, int32_t* line_user, int32_t* line_items, int64_t cap_lines,
+                                  int64_t* n_lines, void* temp, int64_t temp_bytes, void* stream) {
+  return tg_build(a, nullptr, nullptr, 0, line_user, line_items, cap_lines, n_lines, temp, temp_bytes, stream);
+}
+
+extern "C" int score_target_build_lists(const score_target_lists_t* a, int32_t* line_user, int32_t* line_items,
+                                        int64_t cap_lines, int64_t* n_lines, void* temp, int64_t temp_bytes, void* stream) {
+  if (!a || a->struct_bytes != (int64_t)sizeof(score_target_lists_t)) return SCORE_E_BADARG;
+  if (!a->neg_off || a->n_neg < 0 || (a->n_neg > 0 && !a->neg_items)) return SCORE_E_BADARG;
+  if (a->n_neg >= (1ll << 31)) return SCORE_E_SHAPE;
+  return tg_build(&a->build, a->neg_off, a->neg_items, a->n_neg, line_user, line_items, cap_lines, n_lines, temp, temp_bytes,
+                  stream);
 }
 
 extern "C" int64_t score_pop_items_temp_bytes(int32_t n_items) {

@@ -10,8 +10,10 @@ step path.
   gen_pop_items        code/gen_target.py:277-290      the popular-item list negatives may be drawn from
   sample_target_lines  code/sampling.py:31-37          1-in-N down-sampling of validation / test lines
   remap_taobao_log     code/feateng_taobao.py:16-88   the pv events of a time window; users, items, categories
+  remap_ccmr_log       code/feateng_ccmr.py:24-171    positive / negative split by rating, 90-day slices, offset ids, movie rows
 (targets.TargetStore.from_log(build="device") evaluates the three on the device, csrc/targetgen.hip; remap_tmall_log and
-remap_taobao_log(build="device") number the ids, fill the feature rows and cut the slices there, csrc/logremap.hip.)
+remap_taobao_log(build="device") number the ids, fill the feature rows and cut the slices there, csrc/logremap.hip;
+remap_ccmr_log(build="device") in csrc/ccmr.hip.  CCMR's user_neg_dict, feateng_ccmr.py:173-183, is targets.UserNegLists.)
 
 The reference enumerates each id vocabulary through ``list(set(...))`` (feateng_tmall.py:58-64), i.e. in
 Python's per-process string-hash order: its remap is not reproducible from run to run.  Here every
@@ -195,6 +197,144 @@ def _remap_taobao_device(log, start_ts, end_ts, delta, device):
                 item_rows=rows[1], user_rows=rows[0], vocab_sizes=tuple(sizes), kept=kept)
 
 
+CCMR_START_DATE = 20050519        # feateng_ccmr.py:22: 1116432000 is 2005-05-19 00:00 at UTC+8
+CCMR_DELTA_DAYS = 90              # feateng_ccmr.py:19
+CCMR_VOCAB = (80171 + 1, 213481 + 1, 62 + 1, 1043 + 1)      # feateng_ccmr.py:13-16: directors, actors, genres, nations, each + "none"
+
+
+def _ordinal(yyyymmdd):
+    v = int(yyyymmdd)
+    if v <= 0:
+        raise ValueError("date must be a calendar date YYYYMMDD: got %d" % v)
+    try:
+        return datetime.date(v // 10000, v // 100 % 100, v % 100).toordinal()
+    except ValueError:
+        raise ValueError("date must be a calendar date YYYYMMDD: got %d" % v)
+
+
+def ccmr_slice_index(day, start_day, delta_days=CCMR_DELTA_DAYS):
+    """day numbers -> slice index, int((day - start_day) / delta_days): truncated TOWARDS ZERO (feateng_ccmr.py:125)"""
+    d = np.asarray(day).astype(np.int64) - int(start_day)
+    return (np.sign(d) * (np.abs(d) // int(delta_days))).astype(np.int32)
+
+
+def _ccmr_field_ids(feat, n_users, n_items, vocab):
+    """[m, 4] raw first features (-1 = empty) -> their ids (feateng_ccmr.py:150-165)"""
+    out = np.empty(feat.shape, dtype=np.int64)
+    base = n_users + n_items
+    for k in range(4):
+        out[:, k] = np.where(feat[:, k] >= 0, base + 1 + feat[:, k], base + vocab[k])
+        base += vocab[k]
+    return out
+
+
+CCMR_ERRORS = ("date must be a calendar date YYYYMMDD", "a raw user id lies outside [0, n_users)",
+               "a raw item id lies outside [0, n_items)", "movie_info: a raw item id lies outside [0, n_items)",
+               "movie_info: a feature lies outside its vocabulary (-1 = empty, else 0 .. vocab - 2)",
+               "%d items occur among the positive events and have no movie_info line")
+
+
+def remap_ccmr_log(log, movie_info, n_users, n_items, vocab=CCMR_VOCAB, start_date=CCMR_START_DATE, delta_days=CCMR_DELTA_DAYS,
+                   build="host", device=None):
+    """feateng_ccmr.py's pos_neg_split, time2idx, remap_ids on an in-memory rating log.  log: int array [n, 4] with columns raw
+    user, raw item, rating, date as the integer YYYYMMDD.  movie_info: int array [m, 5] with columns raw item, first director,
+    first actor, first genre, first nation, -1 for an empty field (the reference keeps only the first value of a field).
+
+    An event is positive iff its rating is 4 or 5 (:34), negative otherwise.  uid = raw + 1, iid = raw + 1 + n_users (:137).  A
+    present feature f of field k gets 1 + f + n_users + n_items + sum(vocab[:k]), an empty field the LAST id of its vocabulary,
+    n_users + n_items + sum(vocab[:k + 1]) (:150-165): vocab counts that "none" entry, as DIRECTOR_NUM = 80171 + 1 does.
+    item_rows [n_items, 5] = [iid, did, aid, gid, nid] from the item's FIRST movie_info line (:167 -- the opposite of Tmall's
+    "last event wins"); an item without a line that does not occur among the positive events gets the four "none" ids, one
+    that does occur raises ValueError with the count (the reference's loader would raise KeyError).  user_rows [n_users, 1].
+
+    t_idx = trunc((days(date) - days(start_date)) / delta_days), truncated TOWARDS ZERO as int() does at :125: a date 1 .. 89 days
+    before the start lies in slice 0, one 90 or more days before it in a negative slice (the graph and target builds drop
+    those).  This is time2idx, which the reference's __main__ runs; time_filter is not called there.
+    start_date: the reference takes time.mktime of the date, which follows the machine's time zone, and compares it with the
+    constant 1116432000 = 2005-05-19 00:00 at UTC+8; in that zone, without DST, the difference is whole days -- so the rule is
+    stated in days here and the start is a parameter (YYYYMMDD).
+
+    ValueError: an invalid calendar date; a raw id outside [0, n_users) / [0, n_items); a feature outside its vocabulary.
+
+    Returns a dict: uid, iid, t_idx, time_key (the day number, datetime.date.toordinal()) of the positive events in log order;
+    neg_uid, neg_iid of the negative events in log order (targets.UserNegLists.from_events); pos, neg: the log positions of the
+    two halves; n_users, n_items, feature_size = 1 + n_users + n_items + sum(vocab), user_rows, item_rows, vocab_sizes.
+    build="device" (needs a GPU): log and movie_info are uploaded once and everything is computed there (csrc/ccmr.hip, then
+    score_log_compact for the two halves), the same integers; the per-event arrays are int32 tensors on the device, the row
+    tables numpy, downloaded once together with the status words."""
+    _check_build(build)
+    U, I, vocab = int(n_users), int(n_items), tuple(int(v) for v in vocab)
+    delta = int(delta_days)
+    if U <= 0 or I <= 0 or len(vocab) != 4 or min(vocab) < 1 or delta <= 0:
+        raise ValueError("remap_ccmr_log: n_users, n_items, delta_days must be positive and vocab four sizes of at least 1")
+    start_day = _ordinal(start_date)
+    size = 1 + U + I + sum(vocab)
+    if build == "device":
+        return _remap_ccmr_device(log, movie_info, U, I, vocab, start_day, delta, size, device)
+    log, mi = np.asarray(log), np.asarray(movie_info)
+    if log.ndim != 2 or log.shape[1] < 4 or mi.ndim != 2 or mi.shape[1] < 5:
+        raise ValueError("the log must be [n, >= 4] and movie_info [m, >= 5]: got %r and %r" % (log.shape, mi.shape))
+    raw_u, raw_i, rating, date = (log[:, j].astype(np.int64) for j in range(4))
+    dates, inv = np.unique(date, return_inverse=True)
+    day = np.asarray([_ordinal(v) for v in dates.tolist()], dtype=np.int64)[inv.reshape(-1)]
+    if ((raw_u < 0) | (raw_u >= U)).any():
+        raise ValueError(CCMR_ERRORS[1])
+    if ((raw_i < 0) | (raw_i >= I)).any():
+        raise ValueError(CCMR_ERRORS[2])
+    m_item, feat = mi[:, 0].astype(np.int64), mi[:, 1:5].astype(np.int64)
+    if ((m_item < 0) | (m_item >= I)).any():
+        raise ValueError(CCMR_ERRORS[3])
+    if ((feat < -1) | (feat >= np.asarray(vocab) - 1)).any():
+        raise ValueError(CCMR_ERRORS[4])
+    is_pos = (rating == 4) | (rating == 5)
+    pos, neg = np.flatnonzero(is_pos), np.flatnonzero(~is_pos)
+    item_rows = np.empty((I, 5), dtype=np.int64)
+    item_rows[:, 0] = np.arange(U + 1, U + I + 1)
+    item_rows[:, 1:] = _ccmr_field_ids(np.full((1, 4), -1, dtype=np.int64), U, I, vocab)
+    has_line = np.zeros(I, dtype=bool)
+    lined, first = np.unique(m_item, return_index=True)            # (the first line of an item: :167)
+    item_rows[lined, 1:] = _ccmr_field_ids(feat[first], U, I, vocab)
+    has_line[lined] = True
+    missing = int((~has_line[np.unique(raw_i[pos])]).sum())
+    if missing:
+        raise ValueError(CCMR_ERRORS[5] % missing)
+    uid, iid = (raw_u + 1).astype(np.int32), (raw_i + 1 + U).astype(np.int32)
+    return dict(uid=uid[pos], iid=iid[pos], t_idx=ccmr_slice_index(day[pos], start_day, delta), time_key=day[pos].astype(np.int32),
+                neg_uid=uid[neg], neg_iid=iid[neg], pos=pos, neg=neg, n_users=U, n_items=I, feature_size=size,
+                user_rows=np.arange(1, U + 1, dtype=np.int32).reshape(U, 1), item_rows=item_rows.astype(np.int32),
+                vocab_sizes=(U, I) + vocab)
+
+
+def _remap_ccmr_device(log, movie_info, U, I, vocab, start_day, delta, size, device):
+    import torch
+    from . import _lib
+    from . import logremap as lr
+    dev = lr.device_of(device, "remap_ccmr_log(build='device')")
+    if size >= 2 ** 31:
+        raise ValueError("the device remap takes int32 ids: feature_size %d lies outside" % size)
+    with torch.cuda.device(dev):
+        raw, wide = lr.upload_columns(log, 4, dev)                 # [4, n] and [5, m]: the two uploads
+        movie, wide_m = lr.upload_columns(movie_info, 5, dev)
+        if int(raw.shape[1]) == 0:
+            raise ValueError("remap_ccmr_log(build='device'): the log is empty")
+        cols, flat = lr.ccmr_prep(raw, movie, U, I, vocab, start_day, delta)
+        host = torch.cat([torch.stack([wide, wide_m]).to(torch.int32), flat]).cpu().numpy()     # the one download
+        if host[0] or host[1]:
+            raise ValueError(lr.WIDE_MESSAGE)
+        status = host[2:2 + _lib.CCMR_STATUS_WORDS]
+        for k in range(5):
+            if status[k]:
+                raise ValueError(CCMR_ERRORS[k])
+        if status[_lib.CCMR_ST_MISSING]:
+            raise ValueError(CCMR_ERRORS[5] % int(status[_lib.CCMR_ST_MISSING]))
+        item_rows = host[2 + _lib.CCMR_STATUS_WORDS:].reshape(I, 5).copy()
+        (uid, iid, t_idx, day), pos = lr.log_compact(cols[:4], cols[4])
+        (neg_uid, neg_iid), neg = lr.log_compact(cols[:2], cols[5])
+    return dict(uid=uid, iid=iid, t_idx=t_idx, time_key=day, neg_uid=neg_uid, neg_iid=neg_iid, pos=pos, neg=neg, n_users=U,
+                n_items=I, feature_size=size, user_rows=np.arange(1, U + 1, dtype=np.int32).reshape(U, 1), item_rows=item_rows,
+                vocab_sizes=(U, I) + vocab)
+
+
 TAG_TARGET_NEG, TAG_TARGET_POP, TAG_TARGET_SAMPLE = 4, 5, 6      # next to graph.TAG_*: the cell of a draw is the line's user id
 
 
@@ -213,7 +353,7 @@ def _target_heads(uid, iid, t_idx, n_users, n_items, pred_time, start_time):
 
 
 def gen_target_lines(uid, iid, t_idx, n_users, n_items, pred_time, neg_sample_num, start_time=0, seed=11, draws="stream",
-                     pop_items=None):
+                     pop_items=None, neg_lists=None):
     """TargetGen.gen_target_file (gen_target.py:99-121) on an in-memory log: one line per user that has at
     least one interaction in slice `pred_time` AND a history in [start_time, pred_time) (user_hist_dict,
     :225-236): (uid, [pos_iid, neg...]) with pos_iid the user's FIRST item of the slice in log order and the
@@ -230,10 +370,21 @@ def gen_target_lines(uid, iid, t_idx, n_users, n_items, pred_time, neg_sample_nu
       pop list, pop_items[(key * len(pop)) >> 32], tag TAG_TARGET_POP with one.  No line depends on another, which is what
       csrc/targetgen.hip evaluates on the device; events with an id outside its range or a negative slice are dropped.
       Eligibility, the positive and the line order are the same under both rules.
-    Not restated: CCMR's user_neg_dict (gen_target.py:80-86), negatives read from the rating file, which is not available."""
+    neg_lists: a targets.UserNegLists, CCMR's user_neg_dict (gen_target.py:79-96): negative j of user u (j = 0-based position
+      among the line's negatives) is the user's own j-th negatively rated item, in file order, where the list is that long;
+      only the rest is drawn.  "cell": the draw the rule above makes at position j, same tag and j -- so empty lists give the
+      lines of neg_lists=None word for word, and under one seed a user's padding is the same for every pred_time (what the
+      reference does by accident: gen_user_neg_items appends its pads to the list INSIDE the dict, :89-95, and one TargetGen
+      writes target_40, _39, _38, :309-311).  "stream" (host only): the neg_sample_num - len missing values of each eligible
+      user come from the one PCG64 stream, in line order, and are APPENDED to the user's list in neg_lists -- the object is
+      mutated, as the reference's dict is, so a second split sees them.  As there, this holds for a user that HAS an entry: for
+      a user without one the reference pads a fresh [] that it never stores (:82-83), so such a user is drawn anew in every
+      split.  Eligibility, the positive and the line order do not change."""
     if draws not in ("stream", "cell"):
         raise ValueError("draws is 'stream' or 'cell': got %r" % (draws,))
     pop = None if pop_items is None else np.asarray(pop_items).astype(np.int64).ravel()
+    if neg_lists is not None and neg_lists.n_users != int(n_users):
+        raise ValueError("neg_lists is over %d users, the log over %d" % (neg_lists.n_users, int(n_users)))
     if draws == "cell":
         from .graph import _cell_keys
         users, pos = _target_heads(uid, iid, t_idx, int(n_users), int(n_items), pred_time, start_time)
@@ -246,7 +397,16 @@ def gen_target_lines(uid, iid, t_idx, n_users, n_items, pred_time, neg_sample_nu
             negs = n_users + 1 + ((key * np.uint64(n_items)) >> np.uint64(32)).astype(np.int64)
         else:
             negs = pop[((key * np.uint64(len(pop))) >> np.uint64(32)).astype(np.int64)] if len(users) else key.astype(np.int64)
+        if neg_lists is not None and len(users) and neg:
+            off, items = neg_lists.arrays()
+            if len(items):
+                j = np.arange(neg, dtype=np.int64)[None, :]
+                own = j < (off[users] - off[users - 1])[:, None]
+                negs = np.where(own, items[np.minimum(off[users - 1][:, None] + j, len(items) - 1)], negs)
         return [(int(u), [int(p)] + row) for u, p, row in zip(users.tolist(), pos.tolist(), negs.tolist())]
+    if neg_lists is not None and neg_lists.on_device:
+        raise ValueError("draws='stream' exists on the host only: neg_lists lives on the device")
+    own_lists, pads = {} if neg_lists is None else neg_lists.lists(), {}
     rng = np.random.Generator(np.random.PCG64(seed))
     uid, iid, t_idx = np.asarray(uid), np.asarray(iid), np.asarray(t_idx)
     has_hist = np.zeros(n_users + 1, dtype=bool)
@@ -258,13 +418,21 @@ def gen_target_lines(uid, iid, t_idx, n_users, n_items, pred_time, neg_sample_nu
     lines = []
     for u in sorted(first_pos):
         if has_hist[u]:
-            if pop is None:
-                negs = rng.integers(n_users + 1, n_users + n_items + 1, neg_sample_num).tolist()
-            elif len(pop) == 0:
+            own = own_lists.get(u, [])
+            need = neg_sample_num - len(own) if own else neg_sample_num
+            if pop is not None and len(pop) == 0:
                 raise ValueError("pop_items is empty and user %d is eligible" % u)
+            if need <= 0 and own:
+                negs = own[:neg_sample_num]
+            elif pop is None:
+                negs = own + rng.integers(n_users + 1, n_users + n_items + 1, need).tolist()
             else:
-                negs = pop[rng.integers(0, len(pop), neg_sample_num)].tolist()
+                negs = own + pop[rng.integers(0, len(pop), need)].tolist()
+            if own and len(negs) > len(own):                    # (a user without an entry: the reference's fresh [] is not kept)
+                pads[u] = negs[len(own):]
             lines.append((u, [first_pos[u]] + negs))
+    if pads:
+        neg_lists._append(pads)
     return lines
 
 
@@ -393,6 +561,96 @@ def tmall_pipeline(log, seed=11, build="host", draws="stream", targets="host", s
             out[name] = gen_target_lines(host_cols[0], host_cols[1], host_cols[2], r["n_users"], r["n_items"], pt, neg,
                                          c["start_time"], seed + pt, draws=draws)
     return g, r, out
+
+
+# constants of the CCMR run: graph_storage.py:16-25 (41 graph slices, caps 10 / 100), gen_target.py:14-23,309-311 (start index 0,
+# splits at prediction times 38 / 39 / 40, all three files with NEG_SAMPLE_NUM = 99 negatives), train_score.py:23-32,285-310
+CCMR = dict(obj_per_time_slice=10, time_slice_num=41, graph_time_slice_num=41, start_time=0, user_fnum=1, item_fnum=5,
+            pred_time_train=38, pred_time_validation=39, pred_time_test=40, eb_dim=16, hidden_size=32, eval_batch_size=100,
+            train_neg=99, test_neg=99, max_1hop=10, max_2hop=100, start_date=CCMR_START_DATE, delta_days=CCMR_DELTA_DAYS)
+
+
+def _ccmr_front(log, movie_info, n_users, n_items, vocab, build, draws, targets, remap, sample_factor, device=None):
+    """the remap, its columns where the builds want them, and the negative lists -> (r, cols, host_cols, neg_lists)"""
+    from .targets import UserNegLists
+    _check_targets(targets, draws, sample_factor)
+    _check_remap(remap, build)
+    c = CCMR
+    r = remap_ccmr_log(log, movie_info, n_users, n_items, vocab, c["start_date"], c["delta_days"], build=remap, device=device)
+    if remap == "device":
+        cols = (r["uid"], r["iid"], r["t_idx"])
+    else:
+        cols = _device_log(r, device) if targets == "device" else (r["uid"], r["iid"], r["t_idx"])
+    host_cols = None if targets == "device" else _host_cols(cols)
+    neg_lists = UserNegLists.from_events(r["neg_uid"], r["neg_iid"], r["n_users"], build=targets, device=device)
+    return r, cols, host_cols, neg_lists
+
+
+def _ccmr_lines(r, cols, host_cols, neg_lists, name, pt, neg, seed, draws, targets, sample_factor):
+    c = CCMR
+    if targets == "device":
+        from .targets import TargetStore
+        return TargetStore.from_log(cols[0], cols[1], cols[2], r["n_users"], r["n_items"], pt, neg, c["start_time"], seed,
+                                    build="device", sample_factor=_split_factor(sample_factor, name), neg_lists=neg_lists)
+    return gen_target_lines(host_cols[0], host_cols[1], host_cols[2], r["n_users"], r["n_items"], pt, neg, c["start_time"], seed,
+                            draws=draws, neg_lists=neg_lists)
+
+
+# the reference's order: target_40, _39, _38 on ONE TargetGen (gen_target.py:309-311) -- it matters under draws="stream"
+CCMR_SPLITS = (("test", "pred_time_test", "test_neg"), ("validation", "pred_time_validation", "test_neg"),
+               ("train", "pred_time_train", "train_neg"))
+
+
+def ccmr_pipeline(log, movie_info, n_users, n_items, vocab=CCMR_VOCAB, seed=11, build="host", draws="stream", targets="host",
+                  sample_factor=None, remap="host"):
+    """Raw CCMR rating log (remap_ccmr_log's log and movie_info) -> (TemporalGraph, remap dict, {'train' | 'validation' |
+    'test': target lines or TargetStore}), the shape of tmall_pipeline.  The graph is built from the POSITIVE events; a line's
+    negatives are the user's own negatively rated items first (the remap dict's neg_uid / neg_iid as a targets.UserNegLists),
+    draws only behind them (gen_target_lines' neg_lists).  All three splits carry 99 negatives and use ONE seed -- not
+    tmall_pipeline's seed + pt --, so that under draws="cell" a user's padding is the same in every split, which is what the
+    reference's one TargetGen does; under draws="stream" the splits are generated in the reference's order, test first, from
+    one stream per call with the pads carried along in the lists.  build / draws / targets / sample_factor / remap:
+    tmall_pipeline's."""
+    from .graph import TemporalGraph
+    c = CCMR
+    r, cols, host_cols, neg_lists = _ccmr_front(log, movie_info, n_users, n_items, vocab, build, draws, targets, remap,
+                                                sample_factor)
+    gcols = cols if build == "device" or remap == "device" else (r["uid"], r["iid"], r["t_idx"])
+    g = TemporalGraph.from_log(gcols[0], gcols[1], gcols[2], r["n_users"], r["n_items"], c["graph_time_slice_num"],
+                               r["user_rows"], r["item_rows"], max_1hop=c["max_1hop"], max_2hop=c["max_2hop"], seed=seed,
+                               build=build, draws=draws)
+    out = {}
+    for name, pt, neg in CCMR_SPLITS:
+        out[name] = _ccmr_lines(r, cols, host_cols, neg_lists, name, c[pt], c[neg], seed, draws, targets, sample_factor)
+    return g, r, out
+
+
+def ccmr_point_stores(log, movie_info, n_users, n_items, vocab=CCMR_VOCAB, seed=11, dual=True, batch_size=None, build="device",
+                      device=None, targets="host", draws="stream", sample_factor=None, remap="host"):
+    """Raw CCMR rating log -> ({'train' | 'validation' | 'test': PointLogStore}, remap dict), like tmall_point_stores, on
+    ccmr_pipeline's lines (the same seed, draws and targets give the same lines).  Histories are ordered by (entity, day),
+    stable in log order -- gen_user_item_hist_dict_ccmr's stable sorted on time_int (gen_target.py:149-152) --, which is what
+    PointLogStore does with the remap's time_key, and cut at the reference's 300.  batch_size: a dict per split or one number;
+    default 200 for train and CCMR's eval_batch_size for the others (multiples of 1 + 99)."""
+    from .pointdata import PointLogStore
+    c = CCMR
+    r, cols, host_cols, neg_lists = _ccmr_front(log, movie_info, n_users, n_items, vocab, build, draws, targets, remap,
+                                                sample_factor, device)
+    if remap == "device" or (targets == "device" and build == "device"):
+        from .targets import device_i32
+        log4 = (cols[0], cols[1], device_i32(r["time_key"], cols[0].device), cols[2])
+    else:
+        log4 = (r["uid"], r["iid"], r["time_key"], r["t_idx"])
+    stores = {}
+    for name, pt, neg in CCMR_SPLITS:
+        pt, neg = c[pt], c[neg]
+        lines = _ccmr_lines(r, cols, host_cols, neg_lists, name, pt, neg, seed, draws, targets, sample_factor)
+        B = batch_size.get(name) if isinstance(batch_size, dict) else batch_size
+        if B is None:
+            B = 200 if name == "train" else c["eval_batch_size"]
+        stores[name] = PointLogStore(log4[0], log4[1], log4[2], log4[3], lines, c["start_time"], pt, POINT_HIST_MAX_LEN, neg, B,
+                                     r["user_rows"], r["item_rows"], dual, build=build, device=device)
+    return stores, r
 
 
 # ---- the point baselines' history files (gen_target.py:223-275, gen_history_point.py:22-65) ------------------------------------

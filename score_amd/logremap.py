@@ -1,7 +1,7 @@
-"""The raw log's remap on the device (csrc/logremap.hip): thin wrappers of score_log_remap, score_log_slices and
-score_log_compact over int32 tensors, which dataprep.remap_tmall_log / remap_taobao_log(build="device") put together.
-Replaces the id numbering, the feature dictionaries and the time slices of feateng_tmall.py:30-133 and
-feateng_taobao.py:16-88 for a log that is uploaded once.
+"""The raw log's remap on the device (csrc/logremap.hip, csrc/ccmr.hip): thin wrappers of score_log_remap, score_log_slices,
+score_log_compact and score_ccmr_prep over int32 tensors, which dataprep.remap_tmall_log / remap_taobao_log / remap_ccmr_log
+(build="device") put together.  Replaces the id numbering, the feature dictionaries and the time slices of
+feateng_tmall.py:30-133, feateng_taobao.py:16-88 and feateng_ccmr.py:24-171 for a log that is uploaded once.
 """
 import ctypes as C
 
@@ -152,3 +152,33 @@ def log_remap(cols, key_bits, tables=(), download=True):
                 torch.cuda.current_stream(dev).synchronize()      # (temp is released behind this)
                 rows = [flat[o:o + s].view(-1, w) for o, s, w in zip(offs, sizes, widths)]
     return [ids[c, :n] for c in range(k)], counts, rows
+
+
+def ccmr_prep(raw, movie, n_users, n_items, vocab, start_day, delta_days):
+    """score_ccmr_prep on the uploaded columns: raw int32 [4, n] (user, item, rating, YYYYMMDD), movie int32 [5, m] ->
+    ([uid, iid, t_idx, day, keep_pos, keep_neg] int32 tensors [n], flat int32 tensor [8 + n_items * 5]: the status words with
+    the item rows behind them, so one download brings both).  No wait here."""
+    import torch
+    from . import _lib
+    lib, dev = _lib.load(), raw.device
+    n, m, I = int(raw.shape[1]), int(movie.shape[1]), int(n_items)
+    with torch.cuda.device(dev):
+        out = torch.empty((6, _pitch(n)), dtype=torch.int32, device=dev)
+        flat = torch.empty((_lib.CCMR_STATUS_WORDS + I * 5,), dtype=torch.int32, device=dev)
+        temp_bytes = int(lib.score_ccmr_prep_temp_bytes(m, I))
+        if temp_bytes < 0:
+            _lib.check(-2, "score_ccmr_prep_temp_bytes")
+        temp = torch.empty((temp_bytes,), dtype=torch.uint8, device=dev)
+        a = _lib.CcmrPrep()
+        a.struct_bytes, a.n_events, a.n_movies, a.n_users, a.n_items = C.sizeof(_lib.CcmrPrep), n, m, int(n_users), I
+        a.user, a.item, a.rating, a.date = (raw[j].data_ptr() for j in range(4))
+        for k in range(5):
+            a.movie[k] = movie[k].data_ptr() if m else None
+        for k in range(4):
+            a.vocab[k] = int(vocab[k])
+        a.start_day, a.delta_days = int(start_day), int(delta_days)
+        a.uid, a.iid, a.t_idx, a.day, a.keep_pos, a.keep_neg = (out[j].data_ptr() for j in range(6))
+        a.status, a.item_rows = flat.data_ptr(), flat.data_ptr() + 4 * _lib.CCMR_STATUS_WORDS
+        _lib.check(lib.score_ccmr_prep(C.byref(a), temp.data_ptr(), temp_bytes, _stream(dev)), "score_ccmr_prep")
+    # (temp goes back to the allocator of the stream the launches are on: whatever reuses it is ordered behind them)
+    return [out[j, :n] for j in range(6)], flat
