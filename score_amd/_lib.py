@@ -353,6 +353,22 @@ def check(rc, what):
         raise ScoreHipError("%s failed: %s" % (what, kinds.get(rc, "hipError_t %d" % rc)))
 
 
+def current_stream(dev):
+    """the hipStream_t of torch's current stream on `dev`, as the library's calls take it"""
+    import torch
+    return C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+
+
+def workspace(name, dev, *size_args):
+    """-> (uint8 tensor on `dev`, its size) for the call `name`, sized by <name>_temp_bytes(*size_args); a size the library refuses
+    (negative) raises its error before anything is allocated"""
+    nbytes = int(getattr(load(), name + "_temp_bytes")(*size_args))
+    if nbytes < 0:
+        check(-2, name + "_temp_bytes")
+    import torch
+    return torch.empty((nbytes,), dtype=torch.uint8, device=dev), nbytes
+
+
 def make_config(feature_size, eb_dim, hidden_size, max_time_len, obj_per_time_slice, user_fnum, item_fnum,
                 model_type="SCORE"):
     return Config(int(feature_size), int(eb_dim), int(hidden_size), int(max_time_len),

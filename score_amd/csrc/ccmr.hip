@@ -22,16 +22,9 @@
 // status words in front of it) and the two compactions of score_log_compact (score_log_host_waits counts those).
 // No atomics, no workgroup waits on another: every array is a pure function of the input.
 #include "common.h"
-#include "scan.h"
-
-#define CC_THREADS 256
-#define CC_LOOP(i, n) for (int64_t i = (int64_t)blockIdx.x * CC_THREADS + threadIdx.x; i < (n); i += (int64_t)gridDim.x * CC_THREADS)
+#include "devprep.h"
 
 namespace {
-
-__global__ __launch_bounds__(CC_THREADS) void cc_zero_kernel(int32_t* __restrict__ x, int64_t n) {
-  CC_LOOP(i, n) x[i] = 0;
-}
 
 // YYYYMMDD -> date.toordinal() (0001-01-01 is day 1), or -1 for what datetime.date refuses
 __device__ __forceinline__ int32_t cc_ordinal(int32_t v) {
@@ -57,8 +50,8 @@ struct Prep {
   int32_t U, I, start_day, delta_days;
 };
 
-__global__ __launch_bounds__(CC_THREADS) void cc_events_kernel(Prep a) {
-  CC_LOOP(i, a.n) {
+__global__ __launch_bounds__(DP_THREADS) void cc_events_kernel(Prep a) {
+  DP_LOOP(i, a.n) {
     const int32_t u = a.user[i], it = a.item[i], r = a.rating[i];
     const int32_t day = cc_ordinal(a.date[i]);
     const bool ok_u = u >= 0 && u < a.U, ok_i = it >= 0 && it < a.I, ok = ok_u && ok_i && day >= 0;
@@ -82,9 +75,9 @@ struct Movies {
   int32_t U, I, vocab[4];
 };
 
-__global__ __launch_bounds__(CC_THREADS) void cc_movie_keys_kernel(Movies a, uint32_t* __restrict__ keys, uint32_t* __restrict__ vals,
+__global__ __launch_bounds__(DP_THREADS) void cc_movie_keys_kernel(Movies a, uint32_t* __restrict__ keys, uint32_t* __restrict__ vals,
                                                                   int32_t* __restrict__ status) {
-  CC_LOOP(j, a.m) {
+  DP_LOOP(j, a.m) {
     const int32_t it = a.col[0][j];
     const bool ok = it >= 0 && it < a.I;
     if (!ok) status[SCORE_CCMR_ST_MOVIE_ITEM] = 1;
@@ -98,20 +91,11 @@ __global__ __launch_bounds__(CC_THREADS) void cc_movie_keys_kernel(Movies a, uin
   }
 }
 
-__device__ __forceinline__ int64_t cc_lower_bound(const uint32_t* __restrict__ keys, int64_t n, uint32_t c) {
-  int64_t lo = 0, hi = n;
-  while (lo < hi) {
-    const int64_t mid = lo + ((hi - lo) >> 1);
-    if (keys[mid] < c) lo = mid + 1; else hi = mid;
-  }
-  return lo;
-}
-
-__global__ __launch_bounds__(CC_THREADS) void cc_rows_kernel(Movies a, const uint32_t* __restrict__ keys,
+__global__ __launch_bounds__(DP_THREADS) void cc_rows_kernel(Movies a, const uint32_t* __restrict__ keys,
                                                             const uint32_t* __restrict__ vals, const int32_t* __restrict__ occurs,
                                                             int32_t* __restrict__ rows, int32_t* __restrict__ miss) {
-  CC_LOOP(i, a.I) {
-    const int64_t p = cc_lower_bound(keys, a.m, (uint32_t)i);
+  DP_LOOP(i, a.I) {
+    const int64_t p = dp_lower_bound(keys, a.m, (uint32_t)i);
     int64_t line = -1;
     if (p < a.m && keys[p] == (uint32_t)i && (int64_t)vals[p] < a.m) line = vals[p];
     int64_t base = (int64_t)a.U + a.I;                              // the ids of field k are base + 1 .. base + vocab[k]
@@ -132,76 +116,50 @@ __global__ void cc_total_kernel(const int64_t* __restrict__ total, int32_t* __re
 }
 
 // ------------------------------------------------------------------------------------------------------------- neg lists
-__global__ __launch_bounds__(CC_THREADS) void cc_neg_keys_kernel(const int32_t* __restrict__ uid, int64_t n, int32_t U,
+__global__ __launch_bounds__(DP_THREADS) void cc_neg_keys_kernel(const int32_t* __restrict__ uid, int64_t n, int32_t U,
                                                                 uint32_t* __restrict__ keys, uint32_t* __restrict__ vals) {
-  CC_LOOP(i, n) {
+  DP_LOOP(i, n) {
     const int64_t u = (int64_t)uid[i] - 1;
     keys[i] = (uint32_t)(u >= 0 && u < U ? u : U);
     vals[i] = (uint32_t)i;
   }
 }
 
-__global__ __launch_bounds__(CC_THREADS) void cc_neg_lists_kernel(const uint32_t* __restrict__ keys, const uint32_t* __restrict__ vals,
+__global__ __launch_bounds__(DP_THREADS) void cc_neg_lists_kernel(const uint32_t* __restrict__ keys, const uint32_t* __restrict__ vals,
                                                                  const int32_t* __restrict__ iid, int64_t n, int32_t U,
                                                                  int64_t* __restrict__ off, int32_t* __restrict__ items) {
   const int64_t total = n > (int64_t)U + 1 ? n : (int64_t)U + 1;
-  CC_LOOP(i, total) {
+  DP_LOOP(i, total) {
     if (i < n) {
       const uint32_t k = keys[i], v = vals[i];
       items[i] = (k < (uint32_t)U && (int64_t)v < n) ? iid[v] : 0;
     }
-    if (i <= U) off[i] = cc_lower_bound(keys, n, (uint32_t)i);
+    if (i <= U) off[i] = dp_lower_bound(keys, n, (uint32_t)i);
   }
 }
 
 // ------------------------------------------------------------------------------------------------------------------ host
-int cc_bits_of(uint32_t x) {       // bits that hold the values 0 .. x
-  int b = 1;
-  while (b < 32 && (x >> b)) ++b;
-  return b;
-}
-
-unsigned cc_grid(int64_t n) {
-  const int64_t g = cdiv64(n > 0 ? n : 1, CC_THREADS);
-  return (unsigned)(g < 65536 ? g : 65536);
-}
-
-struct PrepTemp {
-  uint32_t* k0; uint32_t* v0; uint32_t* k1; uint32_t* v1;
-  int32_t* occurs; int32_t* miss; int64_t* midx; int64_t* bsum; void* sort_temp; int64_t sort_bytes, total_bytes;
-};
+struct PrepTemp { SortBufs sort; int32_t* occurs; int32_t* miss; int64_t* midx; int64_t* bsum; int64_t total_bytes; };
 
 PrepTemp prep_carve(void* temp, int64_t m, int64_t I) {
   PrepTemp t;
-  const int64_t w = align_up64(m > 0 ? m : 1, 64) * 4, wi = align_up64(I, 64) * 4;
-  char* p = reinterpret_cast<char*>(temp);
-  t.k0 = reinterpret_cast<uint32_t*>(p); p += w;
-  t.v0 = reinterpret_cast<uint32_t*>(p); p += w;
-  t.k1 = reinterpret_cast<uint32_t*>(p); p += w;
-  t.v1 = reinterpret_cast<uint32_t*>(p); p += w;
-  t.occurs = reinterpret_cast<int32_t*>(p); p += wi;
-  t.miss = reinterpret_cast<int32_t*>(p); p += wi;
-  t.midx = reinterpret_cast<int64_t*>(p); p += align_up64(I + 1, 32) * 8;
-  t.bsum = reinterpret_cast<int64_t*>(p); p += align_up64(cdiv64(I, SCAN_CHUNK) + 1, 32) * 8;
-  t.sort_temp = p;
-  t.sort_bytes = m > 0 ? score_sort_pairs_temp_bytes(m) : 0;
-  t.total_bytes = (p - reinterpret_cast<char*>(temp)) + t.sort_bytes;
+  Carver c(temp);
+  c.sort_pairs(t.sort, m > 0 ? m : 1);
+  t.occurs = c.words<int32_t>(I);
+  c.scan(t.miss, t.midx, t.bsum, I);
+  c.sort_temp(t.sort, m);
+  t.total_bytes = c.off;
   return t;
 }
 
-struct NegTemp { uint32_t* k0; uint32_t* v0; uint32_t* k1; uint32_t* v1; void* sort_temp; int64_t sort_bytes, total_bytes; };
+struct NegTemp { SortBufs sort; int64_t total_bytes; };
 
 NegTemp neg_carve(void* temp, int64_t n) {
   NegTemp t;
-  const int64_t w = align_up64(n > 0 ? n : 1, 64) * 4;
-  char* p = reinterpret_cast<char*>(temp);
-  t.k0 = reinterpret_cast<uint32_t*>(p); p += w;
-  t.v0 = reinterpret_cast<uint32_t*>(p); p += w;
-  t.k1 = reinterpret_cast<uint32_t*>(p); p += w;
-  t.v1 = reinterpret_cast<uint32_t*>(p); p += w;
-  t.sort_temp = p;
-  t.sort_bytes = n > 0 ? score_sort_pairs_temp_bytes(n) : 0;
-  t.total_bytes = (p - reinterpret_cast<char*>(temp)) + t.sort_bytes;
+  Carver c(temp);
+  c.sort_pairs(t.sort, n > 0 ? n : 1);
+  c.sort_temp(t.sort, n);
+  t.total_bytes = c.off;
   return t;
 }
 
@@ -232,9 +190,9 @@ extern "C" int score_ccmr_prep(const score_ccmr_prep_t* a, void* temp, int64_t t
   hipStream_t s = (hipStream_t)stream;
   const int64_t n = a->n_events, m = a->n_movies, I = a->n_items;
   const PrepTemp t = prep_carve(temp, m, I);
-  hipLaunchKernelGGL(cc_zero_kernel, dim3(1), dim3(CC_THREADS), 0, s, a->status, (int64_t)SCORE_CCMR_STATUS_WORDS);
+  hipLaunchKernelGGL(dp_zero_kernel<int32_t>, dim3(1), dim3(DP_THREADS), 0, s, a->status, (int64_t)SCORE_CCMR_STATUS_WORDS);
   SCORE_CHECK_LAUNCH();
-  hipLaunchKernelGGL(cc_zero_kernel, dim3(cc_grid(I)), dim3(CC_THREADS), 0, s, t.occurs, I);
+  hipLaunchKernelGGL(dp_zero_kernel<int32_t>, dim3(dp_grid(I)), dim3(DP_THREADS), 0, s, t.occurs, I);
   SCORE_CHECK_LAUNCH();
   Prep e;
   e.user = a->user; e.item = a->item; e.rating = a->rating; e.date = a->date;
@@ -242,22 +200,20 @@ extern "C" int score_ccmr_prep(const score_ccmr_prep_t* a, void* temp, int64_t t
   e.occurs = t.occurs; e.status = a->status;
   e.n = n;
   e.U = a->n_users; e.I = a->n_items; e.start_day = a->start_day; e.delta_days = a->delta_days;
-  hipLaunchKernelGGL(cc_events_kernel, dim3(cc_grid(n)), dim3(CC_THREADS), 0, s, e);
+  hipLaunchKernelGGL(cc_events_kernel, dim3(dp_grid(n)), dim3(DP_THREADS), 0, s, e);
   SCORE_CHECK_LAUNCH();
   Movies mv;
   for (int k = 0; k < 5; ++k) mv.col[k] = a->movie[k];
   mv.m = m;
   mv.U = a->n_users; mv.I = a->n_items;
   for (int k = 0; k < 4; ++k) mv.vocab[k] = a->vocab[k];
-  uint32_t* k = t.k0; uint32_t* v = t.v0;
+  SortBufs b = t.sort;
   if (m > 0) {
-    int32_t in_alt = 0;
-    hipLaunchKernelGGL(cc_movie_keys_kernel, dim3(cc_grid(m)), dim3(CC_THREADS), 0, s, mv, k, v, a->status);
+    hipLaunchKernelGGL(cc_movie_keys_kernel, dim3(dp_grid(m)), dim3(DP_THREADS), 0, s, mv, b.k0, b.v0, a->status);
     SCORE_CHECK_LAUNCH();
-    SCORE_TRY(score_sort_pairs(k, v, t.k1, t.v1, m, cc_bits_of((uint32_t)I), t.sort_temp, t.sort_bytes, &in_alt, s));
-    if (in_alt) { k = t.k1; v = t.v1; }
+    SCORE_TRY(dp_sort(b, m, dp_bits_of((uint32_t)I), s));
   }
-  hipLaunchKernelGGL(cc_rows_kernel, dim3(cc_grid(I)), dim3(CC_THREADS), 0, s, mv, k, v, t.occurs, a->item_rows, t.miss);
+  hipLaunchKernelGGL(cc_rows_kernel, dim3(dp_grid(I)), dim3(DP_THREADS), 0, s, mv, b.k0, b.v0, t.occurs, a->item_rows, t.miss);
   SCORE_CHECK_LAUNCH();
   SCORE_TRY(gb_scan(t.miss, I, t.bsum, t.midx, s));
   hipLaunchKernelGGL(cc_total_kernel, dim3(1), dim3(64), 0, s, t.midx + I, a->status);
@@ -277,16 +233,15 @@ extern "C" int score_neg_lists_build(const int32_t* neg_uid, const int32_t* neg_
   if (score_neg_lists_temp_bytes(n_neg) > temp_bytes) return SCORE_E_WORKSPACE;
   hipStream_t s = (hipStream_t)stream;
   const NegTemp t = neg_carve(temp, n_neg);
-  uint32_t* k = t.k0; uint32_t* v = t.v0;
+  SortBufs b = t.sort;
   if (n_neg > 0) {
-    int32_t in_alt = 0;
-    hipLaunchKernelGGL(cc_neg_keys_kernel, dim3(cc_grid(n_neg)), dim3(CC_THREADS), 0, s, neg_uid, n_neg, n_users, k, v);
+    hipLaunchKernelGGL(cc_neg_keys_kernel, dim3(dp_grid(n_neg)), dim3(DP_THREADS), 0, s, neg_uid, n_neg, n_users, b.k0, b.v0);
     SCORE_CHECK_LAUNCH();
-    SCORE_TRY(score_sort_pairs(k, v, t.k1, t.v1, n_neg, cc_bits_of((uint32_t)n_users), t.sort_temp, t.sort_bytes, &in_alt, s));
-    if (in_alt) { k = t.k1; v = t.v1; }
+    SCORE_TRY(dp_sort(b, n_neg, dp_bits_of((uint32_t)n_users), s));
   }
   const int64_t total = n_neg > (int64_t)n_users + 1 ? n_neg : (int64_t)n_users + 1;
-  hipLaunchKernelGGL(cc_neg_lists_kernel, dim3(cc_grid(total)), dim3(CC_THREADS), 0, s, k, v, neg_iid, n_neg, n_users, off, items);
+  hipLaunchKernelGGL(cc_neg_lists_kernel, dim3(dp_grid(total)), dim3(DP_THREADS), 0, s, b.k0, b.v0, neg_iid, n_neg, n_users, off,
+                     items);
   SCORE_CHECK_LAUNCH();
   return 0;
 }

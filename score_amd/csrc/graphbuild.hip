@@ -28,9 +28,7 @@
 // another.  Nothing here is atomic: every array is a pure function of (log, caps, seed).
 #include "common.h"
 #include "cellkey.h"
-#include "scan.h"
-
-#define GB_THREADS 256
+#include "devprep.h"
 
 namespace {
 
@@ -46,12 +44,12 @@ struct Side {                       // one side's view of the build: its own lis
 };
 
 // ---------------------------------------------------------------------------------------------------------------- 1-hop
-__global__ __launch_bounds__(GB_THREADS) void gb_keys_kernel(const int32_t* __restrict__ uid, const int32_t* __restrict__ iid,
+__global__ __launch_bounds__(DP_THREADS) void gb_keys_kernel(const int32_t* __restrict__ uid, const int32_t* __restrict__ iid,
                                                             const int32_t* __restrict__ t_idx, int64_t n, int32_t U, int32_t I,
                                                             int32_t S, int item_side, uint32_t* __restrict__ keys,
                                                             uint32_t* __restrict__ vals) {
   const int64_t ncell = (int64_t)(item_side ? I : U) * S;
-  for (int64_t i = (int64_t)blockIdx.x * GB_THREADS + threadIdx.x; i < n; i += (int64_t)gridDim.x * GB_THREADS) {
+  DP_LOOP(i, n) {
     const int64_t u = (int64_t)uid[i] - 1, it = (int64_t)iid[i] - U - 1, t = t_idx[i];
     const bool ok = u >= 0 && u < U && it >= 0 && it < I && t >= 0 && t < S;
     keys[i] = (uint32_t)(ok ? (item_side ? it : u) * S + t : ncell);
@@ -59,36 +57,27 @@ __global__ __launch_bounds__(GB_THREADS) void gb_keys_kernel(const int32_t* __re
   }
 }
 
-__device__ __forceinline__ int64_t gb_lower_bound(const uint32_t* __restrict__ keys, int64_t n, uint32_t c) {
-  int64_t lo = 0, hi = n;
-  while (lo < hi) {
-    const int64_t mid = lo + ((hi - lo) >> 1);
-    if (keys[mid] < c) lo = mid + 1; else hi = mid;
-  }
-  return lo;
-}
-
-__global__ __launch_bounds__(GB_THREADS) void gb_segments_kernel(const uint32_t* __restrict__ keys,
+__global__ __launch_bounds__(DP_THREADS) void gb_segments_kernel(const uint32_t* __restrict__ keys,
                                                                 const uint32_t* __restrict__ vals,
                                                                 const int32_t* __restrict__ other, int64_t n, int64_t ncell,
                                                                 int64_t* __restrict__ off1, int32_t* __restrict__ nbr1,
                                                                 uint32_t* __restrict__ cellkey) {
   const int64_t total = n > ncell + 1 ? n : ncell + 1;
-  for (int64_t i = (int64_t)blockIdx.x * GB_THREADS + threadIdx.x; i < total; i += (int64_t)gridDim.x * GB_THREADS) {
+  DP_LOOP(i, total) {
     if (i < n) {
       const uint32_t k = keys[i], v = vals[i];
       nbr1[i] = ((int64_t)k < ncell && (int64_t)v < n) ? other[v] : 0;
       cellkey[i] = k;
     }
-    if (i <= ncell) off1[i] = gb_lower_bound(keys, n, (uint32_t)i);
+    if (i <= ncell) off1[i] = dp_lower_bound(keys, n, (uint32_t)i);
   }
 }
 
 // --------------------------------------------------------------------------------------------------------------- shuffle
 // len[c] = the cell's length if it is over-long, else 0
-__global__ __launch_bounds__(GB_THREADS) void gb_over_len_kernel(const int64_t* __restrict__ off1, int64_t ncell,
+__global__ __launch_bounds__(DP_THREADS) void gb_over_len_kernel(const int64_t* __restrict__ off1, int64_t ncell,
                                                                 int32_t max_1hop, int32_t* __restrict__ len) {
-  for (int64_t c = (int64_t)blockIdx.x * GB_THREADS + threadIdx.x; c < ncell; c += (int64_t)gridDim.x * GB_THREADS) {
+  DP_LOOP(c, ncell) {
     const int64_t l = off1[c + 1] - off1[c];
     len[c] = l > max_1hop ? (int32_t)l : 0;
   }
@@ -96,12 +85,12 @@ __global__ __launch_bounds__(GB_THREADS) void gb_over_len_kernel(const int64_t* 
 
 // the entries of the over-long cells, compacted in (cell, log) order: key = the draw of (cell, position), value = the entry's
 // place in nbr1.  ooff: the scan of gb_over_len_kernel's lengths.
-__global__ __launch_bounds__(GB_THREADS) void gb_compact_kernel(const uint32_t* __restrict__ cellkey,
+__global__ __launch_bounds__(DP_THREADS) void gb_compact_kernel(const uint32_t* __restrict__ cellkey,
                                                                const int64_t* __restrict__ off1,
                                                                const int64_t* __restrict__ ooff, int64_t n, int64_t ncell,
                                                                int32_t max_1hop, uint64_t seed, uint64_t tag,
                                                                uint32_t* __restrict__ keys, uint32_t* __restrict__ vals) {
-  for (int64_t p = (int64_t)blockIdx.x * GB_THREADS + threadIdx.x; p < n; p += (int64_t)gridDim.x * GB_THREADS) {
+  DP_LOOP(p, n) {
     const int64_t c = cellkey[p];
     if (c >= ncell) continue;
     const int64_t b = off1[c];
@@ -112,32 +101,32 @@ __global__ __launch_bounds__(GB_THREADS) void gb_compact_kernel(const uint32_t* 
   }
 }
 
-__global__ __launch_bounds__(GB_THREADS) void gb_rekey_kernel(const uint32_t* __restrict__ cellkey,
+__global__ __launch_bounds__(DP_THREADS) void gb_rekey_kernel(const uint32_t* __restrict__ cellkey,
                                                              const uint32_t* __restrict__ vals, int64_t m, int64_t n,
                                                              int64_t ncell, uint32_t* __restrict__ keys) {
-  for (int64_t i = (int64_t)blockIdx.x * GB_THREADS + threadIdx.x; i < m; i += (int64_t)gridDim.x * GB_THREADS) {
+  DP_LOOP(i, m) {
     const int64_t v = vals[i];
     const uint32_t c = v < n ? cellkey[v] : (uint32_t)ncell;
     keys[i] = (int64_t)c < ncell ? c : (uint32_t)(ncell - 1);                     // (inside bits(ncell - 1), whatever temp held)
   }
 }
 
-__global__ __launch_bounds__(GB_THREADS) void gb_gather_kernel(const int32_t* __restrict__ nbr1,
+__global__ __launch_bounds__(DP_THREADS) void gb_gather_kernel(const int32_t* __restrict__ nbr1,
                                                               const uint32_t* __restrict__ vals, int64_t m, int64_t n,
                                                               uint32_t* __restrict__ picked) {
-  for (int64_t i = (int64_t)blockIdx.x * GB_THREADS + threadIdx.x; i < m; i += (int64_t)gridDim.x * GB_THREADS) {
+  DP_LOOP(i, m) {
     const int64_t v = vals[i];
     picked[i] = v < n ? (uint32_t)nbr1[v] : 0u;
   }
 }
 
 // compacted slot i (now sorted by (cell, key, position)) goes back to entry i - ooff[cell] of its cell
-__global__ __launch_bounds__(GB_THREADS) void gb_writeback_kernel(const uint32_t* __restrict__ cells,
+__global__ __launch_bounds__(DP_THREADS) void gb_writeback_kernel(const uint32_t* __restrict__ cells,
                                                                  const uint32_t* __restrict__ picked,
                                                                  const int64_t* __restrict__ off1,
                                                                  const int64_t* __restrict__ ooff, int64_t m, int64_t ncell,
                                                                  int32_t* __restrict__ nbr1) {
-  for (int64_t i = (int64_t)blockIdx.x * GB_THREADS + threadIdx.x; i < m; i += (int64_t)gridDim.x * GB_THREADS) {
+  DP_LOOP(i, m) {
     const int64_t c = cells[i];
     if (c >= ncell) continue;
     const int64_t j = i - ooff[c];
@@ -159,8 +148,8 @@ __device__ __forceinline__ int32_t gb_contrib(const Side& a, int32_t x, int32_t 
   return d > 1 ? (d < a.max_1hop ? d : a.max_1hop) : 0;
 }
 
-__global__ __launch_bounds__(GB_THREADS) void gb_count_kernel(Side a, int32_t* __restrict__ len2) {
-  for (int64_t c = (int64_t)blockIdx.x * GB_THREADS + threadIdx.x; c < a.ncell; c += (int64_t)gridDim.x * GB_THREADS) {
+__global__ __launch_bounds__(DP_THREADS) void gb_count_kernel(Side a, int32_t* __restrict__ len2) {
+  DP_LOOP(c, a.ncell) {
     const int64_t b = a.off1[c], l = a.off1[c + 1] - b;
     const int32_t m = (int32_t)(l < a.max_1hop ? l : a.max_1hop), t = (int32_t)(c % a.S);
     int32_t cand = 0, d, st;
@@ -251,38 +240,18 @@ __global__ __launch_bounds__(FILL_WAVES * 64) void gb_fill_kernel(Side a, const 
 }
 
 // ------------------------------------------------------------------------------------------------------------------ host
-int bits_of(uint32_t x) {          // bits that hold the values 0 .. x
-  int b = 1;
-  while (b < 32 && (x >> b)) ++b;
-  return b;
-}
-
-unsigned grid_for(int64_t n) {
-  const int64_t g = cdiv64(n > 0 ? n : 1, GB_THREADS);
-  return (unsigned)(g < 65536 ? g : 65536);
-}
-
-struct Temp {
-  uint32_t* cellkey[2]; uint32_t* k0; uint32_t* v0; uint32_t* k1; uint32_t* v1;
-  int32_t* len; int64_t* bsum; void* sort_temp; int64_t sort_bytes; int64_t total_bytes;
-};
+struct Temp { uint32_t* cellkey[2]; SortBufs sort; int32_t* len; int64_t* bsum; int64_t total_bytes; };
 
 Temp carve(void* temp, int64_t n, int64_t ncell_max) {
   Temp t;
-  const int64_t w = align_up64(n, 64) * 4, lw = align_up64(ncell_max, 64) * 4;
-  const int64_t bw = align_up64(cdiv64(ncell_max, SCAN_CHUNK) + 1, 32) * 8;
-  char* p = reinterpret_cast<char*>(temp);
-  t.cellkey[0] = reinterpret_cast<uint32_t*>(p); p += w;
-  t.cellkey[1] = reinterpret_cast<uint32_t*>(p); p += w;
-  t.k0 = reinterpret_cast<uint32_t*>(p); p += w;
-  t.v0 = reinterpret_cast<uint32_t*>(p); p += w;
-  t.k1 = reinterpret_cast<uint32_t*>(p); p += w;
-  t.v1 = reinterpret_cast<uint32_t*>(p); p += w;
-  t.len = reinterpret_cast<int32_t*>(p); p += lw;
-  t.bsum = reinterpret_cast<int64_t*>(p); p += bw;
-  t.sort_temp = p;
-  t.sort_bytes = score_sort_pairs_temp_bytes(n);
-  t.total_bytes = (p - reinterpret_cast<char*>(temp)) + t.sort_bytes;
+  Carver c(temp);
+  t.cellkey[0] = c.words<uint32_t>(n);
+  t.cellkey[1] = c.words<uint32_t>(n);
+  c.sort_pairs(t.sort, n);
+  t.len = c.words<int32_t>(ncell_max);
+  t.bsum = c.block_sums(ncell_max);
+  c.sort_temp(t.sort, n);
+  t.total_bytes = c.off;
   return t;
 }
 
@@ -320,14 +289,12 @@ extern "C" int score_graph_build_1hop(const score_graph_build_t* g, void* temp, 
   const Temp t = carve(temp, n, ncell_max_of(g));
   for (int side = 0; side < 2; ++side) {
     const int64_t ncell = (int64_t)(side ? g->n_items : g->n_users) * g->time_slice_num;
-    uint32_t* k0 = t.k0; uint32_t* v0 = t.v0; uint32_t* k1 = t.k1; uint32_t* v1 = t.v1;
-    int32_t in_alt = 0;
-    hipLaunchKernelGGL(gb_keys_kernel, dim3(grid_for(n)), dim3(GB_THREADS), 0, s, g->uid, g->iid, g->t_idx, n, g->n_users,
-                       g->n_items, g->time_slice_num, side, k0, v0);
+    SortBufs b = t.sort;
+    hipLaunchKernelGGL(gb_keys_kernel, dim3(dp_grid(n)), dim3(DP_THREADS), 0, s, g->uid, g->iid, g->t_idx, n, g->n_users,
+                       g->n_items, g->time_slice_num, side, b.k0, b.v0);
     SCORE_CHECK_LAUNCH();
-    SCORE_TRY(score_sort_pairs(k0, v0, k1, v1, n, bits_of((uint32_t)ncell), t.sort_temp, t.sort_bytes, &in_alt, s));
-    if (in_alt) { k0 = k1; v0 = v1; }
-    hipLaunchKernelGGL(gb_segments_kernel, dim3(grid_for(n > ncell + 1 ? n : ncell + 1)), dim3(GB_THREADS), 0, s, k0, v0,
+    SCORE_TRY(dp_sort(b, n, dp_bits_of((uint32_t)ncell), s));
+    hipLaunchKernelGGL(gb_segments_kernel, dim3(dp_grid(n > ncell + 1 ? n : ncell + 1)), dim3(DP_THREADS), 0, s, b.k0, b.v0,
                        side ? g->uid : g->iid, n, ncell, side ? g->item_off1 : g->user_off1,
                        side ? g->item_nbr1 : g->user_nbr1, t.cellkey[side]);
     SCORE_CHECK_LAUNCH();
@@ -365,37 +332,30 @@ extern "C" int score_graph_build_2hop(const score_graph_build_t* g, int32_t item
   const Temp t = carve(temp, n, ncell_max_of(g));
   const uint32_t* cellkey = t.cellkey[item_side];
   // the over-long cells' entries, in their random order
-  hipLaunchKernelGGL(gb_over_len_kernel, dim3(grid_for(a.ncell)), dim3(GB_THREADS), 0, s, a.off1, a.ncell, a.max_1hop, t.len);
+  hipLaunchKernelGGL(gb_over_len_kernel, dim3(dp_grid(a.ncell)), dim3(DP_THREADS), 0, s, a.off1, a.ncell, a.max_1hop, t.len);
   SCORE_CHECK_LAUNCH();
   SCORE_TRY(gb_scan(t.len, a.ncell, t.bsum, off2, s));
   int64_t n_over = 0;
-  hipError_t e = hipMemcpyAsync(&n_over, off2 + a.ncell, sizeof(int64_t), hipMemcpyDeviceToHost, s);
-  if (e == hipSuccess) e = hipStreamSynchronize(s);
-  if (e != hipSuccess) return (int)e;
+  SCORE_TRY(dp_read_words(off2 + a.ncell, &n_over, 1, s, nullptr));
   if (n_over < 0 || n_over > n) return SCORE_E_BADARG;
   if (n_over > 0) {
-    uint32_t* k0 = t.k0; uint32_t* v0 = t.v0; uint32_t* k1 = t.k1; uint32_t* v1 = t.v1;
-    int32_t in_alt = 0;
-    hipLaunchKernelGGL(gb_compact_kernel, dim3(grid_for(n)), dim3(GB_THREADS), 0, s, cellkey, a.off1, off2, n, a.ncell,
-                       a.max_1hop, a.seed, a.tag_shuffle, k0, v0);
+    SortBufs b = t.sort;
+    hipLaunchKernelGGL(gb_compact_kernel, dim3(dp_grid(n)), dim3(DP_THREADS), 0, s, cellkey, a.off1, off2, n, a.ncell,
+                       a.max_1hop, a.seed, a.tag_shuffle, b.k0, b.v0);
     SCORE_CHECK_LAUNCH();
-    SCORE_TRY(score_sort_pairs(k0, v0, k1, v1, n_over, 32, t.sort_temp, t.sort_bytes, &in_alt, s));
-    if (in_alt) { uint32_t* x = k0; k0 = k1; k1 = x; x = v0; v0 = v1; v1 = x; }
-    hipLaunchKernelGGL(gb_rekey_kernel, dim3(grid_for(n_over)), dim3(GB_THREADS), 0, s, cellkey, v0, n_over, n, a.ncell, k0);
+    SCORE_TRY(dp_sort(b, n_over, 32, s));
+    hipLaunchKernelGGL(gb_rekey_kernel, dim3(dp_grid(n_over)), dim3(DP_THREADS), 0, s, cellkey, b.v0, n_over, n, a.ncell, b.k0);
     SCORE_CHECK_LAUNCH();
-    SCORE_TRY(score_sort_pairs(k0, v0, k1, v1, n_over, bits_of((uint32_t)(a.ncell - 1)), t.sort_temp, t.sort_bytes, &in_alt, s));
-    if (in_alt) { uint32_t* x = k0; k0 = k1; k1 = x; x = v0; v0 = v1; v1 = x; }
-    hipLaunchKernelGGL(gb_gather_kernel, dim3(grid_for(n_over)), dim3(GB_THREADS), 0, s, a.nbr1, v0, n_over, n, k1);
+    SCORE_TRY(dp_sort(b, n_over, dp_bits_of((uint32_t)(a.ncell - 1)), s));
+    hipLaunchKernelGGL(gb_gather_kernel, dim3(dp_grid(n_over)), dim3(DP_THREADS), 0, s, a.nbr1, b.v0, n_over, n, b.k1);
     SCORE_CHECK_LAUNCH();
-    hipLaunchKernelGGL(gb_writeback_kernel, dim3(grid_for(n_over)), dim3(GB_THREADS), 0, s, k0, k1, a.off1, off2, n_over,
+    hipLaunchKernelGGL(gb_writeback_kernel, dim3(dp_grid(n_over)), dim3(DP_THREADS), 0, s, b.k0, b.k1, a.off1, off2, n_over,
                        a.ncell, a.nbr1);
     SCORE_CHECK_LAUNCH();
   }
   // the capped 2-hop lengths and their scan
-  hipLaunchKernelGGL(gb_count_kernel, dim3(grid_for(a.ncell)), dim3(GB_THREADS), 0, s, a, t.len);
+  hipLaunchKernelGGL(gb_count_kernel, dim3(dp_grid(a.ncell)), dim3(DP_THREADS), 0, s, a, t.len);
   SCORE_CHECK_LAUNCH();
   SCORE_TRY(gb_scan(t.len, a.ncell, t.bsum, off2, s));
-  e = hipMemcpyAsync(total, off2 + a.ncell, sizeof(int64_t), hipMemcpyDeviceToHost, s);
-  if (e == hipSuccess) e = hipStreamSynchronize(s);
-  return e == hipSuccess ? 0 : (int)e;
+  return dp_read_words(off2 + a.ncell, total, 1, s, nullptr);
 }

@@ -20,28 +20,23 @@
 // score_log_slices: element-wise, the Tmall 15-day slices from MMDD (floor division) or the epoch filter and slices.
 // score_log_compact: keep flags -> gb_scan -> stable scatter of up to 8 columns and the kept positions.
 // No atomics, no workgroup waits on another: every array is a pure function of the input.
-#include <atomic>
 #include "common.h"
-#include "scan.h"
-
-#define LR_THREADS 256
+#include "devprep.h"
 
 namespace {
 
 constexpr int LR_MAX_COLS = SCORE_LOG_REMAP_MAX_COLS, LR_MAX_TABLES = SCORE_LOG_REMAP_MAX_TABLES;
 constexpr int LR_RES_WORDS = 32;              // int64: base[0 .. 8], counts at 9 .. 16, status at 17
 
-#define LR_LOOP(i, n) for (int64_t i = (int64_t)blockIdx.x * LR_THREADS + threadIdx.x; i < (n); i += (int64_t)gridDim.x * LR_THREADS)
-
 __global__ void lr_init_kernel(int64_t* __restrict__ res) {
   if (threadIdx.x < LR_RES_WORDS) res[threadIdx.x] = threadIdx.x == 0 ? 1 : 0;      // base[0] = 1: 0 is the dummy node
 }
 
-__global__ __launch_bounds__(LR_THREADS) void lr_keys_kernel(const int32_t* __restrict__ col, int64_t n, int32_t key_bits,
+__global__ __launch_bounds__(DP_THREADS) void lr_keys_kernel(const int32_t* __restrict__ col, int64_t n, int32_t key_bits,
                                                             uint32_t* __restrict__ keys, uint32_t* __restrict__ vals,
                                                             int64_t* __restrict__ status) {
   const uint32_t mask = key_bits >= 32 ? 0xFFFFFFFFu : ((1u << key_bits) - 1u);
-  LR_LOOP(i, n) {
+  DP_LOOP(i, n) {
     const uint32_t k = (uint32_t)col[i];
     if (k & ~mask) *status = 1;
     keys[i] = k & mask;
@@ -49,9 +44,9 @@ __global__ __launch_bounds__(LR_THREADS) void lr_keys_kernel(const int32_t* __re
   }
 }
 
-__global__ __launch_bounds__(LR_THREADS) void lr_mark_kernel(const uint32_t* __restrict__ keys, const uint32_t* __restrict__ vals,
+__global__ __launch_bounds__(DP_THREADS) void lr_mark_kernel(const uint32_t* __restrict__ keys, const uint32_t* __restrict__ vals,
                                                             int64_t n, int32_t* __restrict__ head, int32_t* __restrict__ is_first) {
-  LR_LOOP(p, n) {
+  DP_LOOP(p, n) {
     const int32_t h = (p == 0 || keys[p - 1] != keys[p]) ? 1 : 0;
     const uint32_t v = vals[p];
     head[p] = h;
@@ -66,11 +61,11 @@ __global__ void lr_base_kernel(int64_t* __restrict__ res, const int64_t* __restr
   }
 }
 
-__global__ __launch_bounds__(LR_THREADS) void lr_runs_kernel(const uint32_t* __restrict__ keys, const uint32_t* __restrict__ vals,
+__global__ __launch_bounds__(DP_THREADS) void lr_runs_kernel(const uint32_t* __restrict__ keys, const uint32_t* __restrict__ vals,
                                                             const int32_t* __restrict__ head, const int64_t* __restrict__ run,
                                                             int64_t n, int32_t* __restrict__ run_first,
                                                             int32_t* __restrict__ run_last) {
-  LR_LOOP(p, n) {
+  DP_LOOP(p, n) {
     const int64_t r = run[p] + head[p] - 1;
     if (r < 0 || r >= n) continue;                                  // (never with this call's own scan)
     if (head[p]) run_first[r] = (int32_t)vals[p];
@@ -78,14 +73,14 @@ __global__ __launch_bounds__(LR_THREADS) void lr_runs_kernel(const uint32_t* __r
   }
 }
 
-__global__ __launch_bounds__(LR_THREADS) void lr_write_kernel(const uint32_t* __restrict__ vals, const int32_t* __restrict__ head,
+__global__ __launch_bounds__(DP_THREADS) void lr_write_kernel(const uint32_t* __restrict__ vals, const int32_t* __restrict__ head,
                                                              const int64_t* __restrict__ run, const int64_t* __restrict__ rank,
                                                              const int32_t* __restrict__ run_first,
                                                              const int32_t* __restrict__ run_last, const int64_t* __restrict__ base,
                                                              int64_t n, int32_t* __restrict__ ids, int32_t* __restrict__ ent_last0,
                                                              int32_t* __restrict__ ent_last1) {
   const int64_t b = *base;
-  LR_LOOP(p, n) {
+  DP_LOOP(p, n) {
     const int64_t r = run[p] + head[p] - 1;
     const uint32_t v = vals[p];
     if (r < 0 || r >= n || (int64_t)v >= n) continue;
@@ -108,11 +103,11 @@ struct RowFill {
   int32_t width;
 };
 
-__global__ __launch_bounds__(LR_THREADS) void lr_rows_kernel(RowFill a) {
+__global__ __launch_bounds__(DP_THREADS) void lr_rows_kernel(RowFill a) {
   int64_t m = *a.count;
   m = m < a.cap ? m : a.cap;
   const bool vec = (a.width & 3) == 0 && (reinterpret_cast<uintptr_t>(a.rows) & 15u) == 0;
-  LR_LOOP(e, m) {
+  DP_LOOP(e, m) {
     const int64_t last = a.ent_last[e];
     if (last < 0 || last >= a.n) continue;
     int32_t w[1 + SCORE_LOG_REMAP_MAX_FEATS];
@@ -131,9 +126,9 @@ __global__ __launch_bounds__(LR_THREADS) void lr_rows_kernel(RowFill a) {
 }
 
 // ---------------------------------------------------------------------------------------------------------------- slices
-__global__ __launch_bounds__(LR_THREADS) void lr_slices_tmall_kernel(const int32_t* __restrict__ mmdd, int64_t n,
+__global__ __launch_bounds__(DP_THREADS) void lr_slices_tmall_kernel(const int32_t* __restrict__ mmdd, int64_t n,
                                                                     int32_t* __restrict__ t_idx, int32_t* __restrict__ status) {
-  LR_LOOP(i, n) {
+  DP_LOOP(i, n) {
     const int32_t v = mmdd[i];
     const int32_t m = v / 100, d = v - m * 100;
     // days before the month's first in 2015 (no leap day), and the month's length
@@ -152,10 +147,10 @@ __global__ __launch_bounds__(LR_THREADS) void lr_slices_tmall_kernel(const int32
   }
 }
 
-__global__ __launch_bounds__(LR_THREADS) void lr_slices_epoch_kernel(const int32_t* __restrict__ ts, const int32_t* __restrict__ flag,
+__global__ __launch_bounds__(DP_THREADS) void lr_slices_epoch_kernel(const int32_t* __restrict__ ts, const int32_t* __restrict__ flag,
                                                                     int64_t n, int32_t start_ts, int32_t end_ts, int32_t delta,
                                                                     int32_t* __restrict__ t_idx, int32_t* __restrict__ keep) {
-  LR_LOOP(i, n) {
+  DP_LOOP(i, n) {
     const int32_t t = ts[i];
     const bool k = t >= start_ts && t <= end_ts && (!flag || flag[i] != 0);
     keep[i] = k ? 1 : 0;
@@ -171,12 +166,12 @@ struct Compact {
   int32_t n_cols;
 };
 
-__global__ __launch_bounds__(LR_THREADS) void lr_flag_kernel(const int32_t* __restrict__ keep, int64_t n, int32_t* __restrict__ flag) {
-  LR_LOOP(i, n) flag[i] = keep[i] != 0 ? 1 : 0;
+__global__ __launch_bounds__(DP_THREADS) void lr_flag_kernel(const int32_t* __restrict__ keep, int64_t n, int32_t* __restrict__ flag) {
+  DP_LOOP(i, n) flag[i] = keep[i] != 0 ? 1 : 0;
 }
 
-__global__ __launch_bounds__(LR_THREADS) void lr_compact_kernel(Compact a) {
-  LR_LOOP(i, a.n) {
+__global__ __launch_bounds__(DP_THREADS) void lr_compact_kernel(Compact a) {
+  DP_LOOP(i, a.n) {
     if (!a.flag[i]) continue;
     const int64_t q = a.idx[i];
     if (q < 0 || q >= a.cap) continue;
@@ -188,38 +183,27 @@ __global__ __launch_bounds__(LR_THREADS) void lr_compact_kernel(Compact a) {
 }
 
 // ------------------------------------------------------------------------------------------------------------------ host
-unsigned lr_grid(int64_t n) {
-  const int64_t g = cdiv64(n > 0 ? n : 1, LR_THREADS);
-  return (unsigned)(g < 65536 ? g : 65536);
-}
-
 struct Temp {
-  int64_t* res;
-  uint32_t* k0; uint32_t* v0; uint32_t* k1; uint32_t* v1;
+  int64_t* res; SortBufs sort;
   int32_t* head; int32_t* is_first; int32_t* run_first; int32_t* run_last; int32_t* ent_last[LR_MAX_TABLES];
-  int64_t* rank; int64_t* run; int64_t* bsum; void* sort_temp; int64_t sort_bytes, total_bytes;
+  int64_t* rank; int64_t* run; int64_t* bsum; int64_t total_bytes;
 };
 
 Temp carve(void* temp, int64_t n) {
   Temp t;
-  const int64_t w = align_up64(n, 64) * 4, w8 = align_up64(n + 1, 32) * 8;
-  char* p = reinterpret_cast<char*>(temp);
-  t.res = reinterpret_cast<int64_t*>(p); p += LR_RES_WORDS * 8;
-  t.k0 = reinterpret_cast<uint32_t*>(p); p += w;
-  t.v0 = reinterpret_cast<uint32_t*>(p); p += w;
-  t.k1 = reinterpret_cast<uint32_t*>(p); p += w;
-  t.v1 = reinterpret_cast<uint32_t*>(p); p += w;
-  t.head = reinterpret_cast<int32_t*>(p); p += w;
-  t.is_first = reinterpret_cast<int32_t*>(p); p += w;
-  t.run_first = reinterpret_cast<int32_t*>(p); p += w;
-  t.run_last = reinterpret_cast<int32_t*>(p); p += w;
-  for (int i = 0; i < LR_MAX_TABLES; ++i) { t.ent_last[i] = reinterpret_cast<int32_t*>(p); p += w; }
-  t.rank = reinterpret_cast<int64_t*>(p); p += w8;
-  t.run = reinterpret_cast<int64_t*>(p); p += w8;
-  t.bsum = reinterpret_cast<int64_t*>(p); p += align_up64(cdiv64(n, SCAN_CHUNK) + 1, 32) * 8;
-  t.sort_temp = p;
-  t.sort_bytes = score_sort_pairs_temp_bytes(n);
-  t.total_bytes = (p - reinterpret_cast<char*>(temp)) + t.sort_bytes;
+  Carver c(temp);
+  t.res = c.take<int64_t>(LR_RES_WORDS, 1);
+  c.sort_pairs(t.sort, n);
+  t.head = c.words<int32_t>(n);
+  t.is_first = c.words<int32_t>(n);
+  t.run_first = c.words<int32_t>(n);
+  t.run_last = c.words<int32_t>(n);
+  for (int i = 0; i < LR_MAX_TABLES; ++i) t.ent_last[i] = c.words<int32_t>(n);
+  t.rank = c.prefix(n);
+  t.run = c.prefix(n);
+  t.bsum = c.block_sums(n);
+  c.sort_temp(t.sort, n);
+  t.total_bytes = c.off;
   return t;
 }
 
@@ -227,22 +211,13 @@ struct CompactTemp { int32_t* flag; int64_t* idx; int64_t* bsum; int64_t total_b
 
 CompactTemp compact_carve(void* temp, int64_t n) {
   CompactTemp t;
-  char* p = reinterpret_cast<char*>(temp);
-  t.flag = reinterpret_cast<int32_t*>(p); p += align_up64(n, 64) * 4;
-  t.idx = reinterpret_cast<int64_t*>(p); p += align_up64(n + 1, 32) * 8;
-  t.bsum = reinterpret_cast<int64_t*>(p); p += align_up64(cdiv64(n, SCAN_CHUNK) + 1, 32) * 8;
-  t.total_bytes = p - reinterpret_cast<char*>(temp);
+  Carver c(temp);
+  c.scan(t.flag, t.idx, t.bsum, n);
+  t.total_bytes = c.off;
   return t;
 }
 
-std::atomic<int> g_host_waits{0};      // every wait for a stream in this file goes through read_words
-
-int read_words(const int64_t* dev, int64_t* host, int n, hipStream_t s) {
-  g_host_waits.fetch_add(1, std::memory_order_relaxed);
-  hipError_t e = hipMemcpyAsync(host, dev, sizeof(int64_t) * n, hipMemcpyDeviceToHost, s);
-  if (e == hipSuccess) e = hipStreamSynchronize(s);
-  return e == hipSuccess ? 0 : (int)e;
-}
+std::atomic<int> g_host_waits{0};      // every wait for a stream in this file is a dp_read_words that counts here
 
 }  // namespace
 
@@ -289,7 +264,7 @@ extern "C" int score_log_remap(const score_log_remap_t* a, int32_t* const* rows,
       f.rows = rows[k];
       f.n = n; f.cap = cap_rows[k];
       f.width = 1 + tb.n_feat;
-      hipLaunchKernelGGL(lr_rows_kernel, dim3(lr_grid(f.cap < n ? f.cap : n)), dim3(LR_THREADS), 0, s, f);
+      hipLaunchKernelGGL(lr_rows_kernel, dim3(dp_grid(f.cap < n ? f.cap : n)), dim3(DP_THREADS), 0, s, f);
       SCORE_CHECK_LAUNCH();
     }
     return 0;
@@ -298,29 +273,28 @@ extern "C" int score_log_remap(const score_log_remap_t* a, int32_t* const* rows,
   SCORE_CHECK_LAUNCH();
   int64_t* status = t.res + 1 + 2 * LR_MAX_COLS;
   for (int c = 0; c < a->n_cols; ++c) {
-    uint32_t* k = t.k0; uint32_t* v = t.v0;
-    int32_t in_alt = 0;
+    SortBufs b = t.sort;
     int32_t* el[LR_MAX_TABLES] = {nullptr, nullptr};
     for (int j = 0; j < a->n_tables; ++j)
       if (a->tables[j].entity == c) el[j] = t.ent_last[j];
-    hipLaunchKernelGGL(lr_keys_kernel, dim3(lr_grid(n)), dim3(LR_THREADS), 0, s, a->cols[c], n, a->key_bits, k, v, status);
+    hipLaunchKernelGGL(lr_keys_kernel, dim3(dp_grid(n)), dim3(DP_THREADS), 0, s, a->cols[c], n, a->key_bits, b.k0, b.v0, status);
     SCORE_CHECK_LAUNCH();
-    SCORE_TRY(score_sort_pairs(k, v, t.k1, t.v1, n, a->key_bits, t.sort_temp, t.sort_bytes, &in_alt, s));
-    if (in_alt) { k = t.k1; v = t.v1; }
-    hipLaunchKernelGGL(lr_mark_kernel, dim3(lr_grid(n)), dim3(LR_THREADS), 0, s, k, v, n, t.head, t.is_first);
+    SCORE_TRY(dp_sort(b, n, a->key_bits, s));
+    hipLaunchKernelGGL(lr_mark_kernel, dim3(dp_grid(n)), dim3(DP_THREADS), 0, s, b.k0, b.v0, n, t.head, t.is_first);
     SCORE_CHECK_LAUNCH();
     SCORE_TRY(gb_scan(t.is_first, n, t.bsum, t.rank, s));
     hipLaunchKernelGGL(lr_base_kernel, dim3(1), dim3(64), 0, s, t.res, t.rank + n, c);
     SCORE_CHECK_LAUNCH();
     SCORE_TRY(gb_scan(t.head, n, t.bsum, t.run, s));
-    hipLaunchKernelGGL(lr_runs_kernel, dim3(lr_grid(n)), dim3(LR_THREADS), 0, s, k, v, t.head, t.run, n, t.run_first, t.run_last);
+    hipLaunchKernelGGL(lr_runs_kernel, dim3(dp_grid(n)), dim3(DP_THREADS), 0, s, b.k0, b.v0, t.head, t.run, n, t.run_first,
+                       t.run_last);
     SCORE_CHECK_LAUNCH();
-    hipLaunchKernelGGL(lr_write_kernel, dim3(lr_grid(n)), dim3(LR_THREADS), 0, s, v, t.head, t.run, t.rank, t.run_first,
+    hipLaunchKernelGGL(lr_write_kernel, dim3(dp_grid(n)), dim3(DP_THREADS), 0, s, b.v0, t.head, t.run, t.rank, t.run_first,
                        t.run_last, t.res + c, n, a->ids[c], el[0], el[1]);
     SCORE_CHECK_LAUNCH();
   }
   int64_t host[1 + LR_MAX_COLS];                                     // the counts and the status word behind them: one wait
-  SCORE_TRY(read_words(t.res + 1 + LR_MAX_COLS, host, 1 + LR_MAX_COLS, s));
+  SCORE_TRY(dp_read_words(t.res + 1 + LR_MAX_COLS, host, 1 + LR_MAX_COLS, s, &g_host_waits));
   if (host[LR_MAX_COLS] != 0) return SCORE_E_BADARG;                 // a value wider than key_bits
   int64_t sum = 0;
   for (int c = 0; c < a->n_cols; ++c) sum += host[c];
@@ -336,10 +310,10 @@ extern "C" int score_log_slices(int32_t mode, const int32_t* time, const int32_t
   hipStream_t s = (hipStream_t)stream;
   if (mode == SCORE_LOG_SLICES_TMALL) {
     if (!status) return SCORE_E_BADARG;
-    hipLaunchKernelGGL(lr_slices_tmall_kernel, dim3(lr_grid(n_events)), dim3(LR_THREADS), 0, s, time, n_events, t_idx, status);
+    hipLaunchKernelGGL(lr_slices_tmall_kernel, dim3(dp_grid(n_events)), dim3(DP_THREADS), 0, s, time, n_events, t_idx, status);
   } else if (mode == SCORE_LOG_SLICES_EPOCH) {
     if (!keep || delta <= 0 || end_ts < start_ts) return SCORE_E_BADARG;
-    hipLaunchKernelGGL(lr_slices_epoch_kernel, dim3(lr_grid(n_events)), dim3(LR_THREADS), 0, s, time, flag, n_events, start_ts,
+    hipLaunchKernelGGL(lr_slices_epoch_kernel, dim3(dp_grid(n_events)), dim3(DP_THREADS), 0, s, time, flag, n_events, start_ts,
                        end_ts, delta, t_idx, keep);
   } else {
     return SCORE_E_BADARG;
@@ -365,18 +339,18 @@ extern "C" int score_log_compact(const int32_t* const* cols_in, int32_t* const* 
   hipStream_t s = (hipStream_t)stream;
   const int64_t n = n_events;
   const CompactTemp t = compact_carve(temp, n);
-  hipLaunchKernelGGL(lr_flag_kernel, dim3(lr_grid(n)), dim3(LR_THREADS), 0, s, keep, n, t.flag);
+  hipLaunchKernelGGL(lr_flag_kernel, dim3(dp_grid(n)), dim3(DP_THREADS), 0, s, keep, n, t.flag);
   SCORE_CHECK_LAUNCH();
   SCORE_TRY(gb_scan(t.flag, n, t.bsum, t.idx, s));
   int64_t total = 0;
-  SCORE_TRY(read_words(t.idx + n, &total, 1, s));
+  SCORE_TRY(dp_read_words(t.idx + n, &total, 1, s, &g_host_waits));
   *n_kept = total;
   if (total == 0) return 0;
   Compact k;
   for (int c = 0; c < LR_MAX_COLS; ++c) { k.in[c] = cols_in[c < n_cols ? c : 0]; k.out[c] = cols_out[c < n_cols ? c : 0]; }
   k.flag = t.flag; k.idx = t.idx; k.kept_pos = kept_pos;
   k.n = n; k.cap = cap; k.n_cols = n_cols;
-  hipLaunchKernelGGL(lr_compact_kernel, dim3(lr_grid(n)), dim3(LR_THREADS), 0, s, k);
+  hipLaunchKernelGGL(lr_compact_kernel, dim3(dp_grid(n)), dim3(DP_THREADS), 0, s, k);
   SCORE_CHECK_LAUNCH();
   return 0;
 }

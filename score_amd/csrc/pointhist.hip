@@ -19,8 +19,7 @@
 // most whatever n).  The 54 M rows of the full Tmall log are 6,592 tiles: 864 MB of keys and values in two copies and 108 MB
 // of histogram matrix in `temp`.
 #include "common.h"
-
-#define PH_THREADS 256
+#include "devprep.h"
 
 namespace {
 
@@ -40,10 +39,10 @@ __device__ __forceinline__ uint32_t ph_entity(const HistFill& a, int64_t i) {
 // mode 0: keys[i] = (entity << time_bits) | time_key, vals[i] = i      (the one-sort form)
 // mode 1: keys[i] = time_key, vals[i] = i                               (first of two sorts)
 // mode 2: keys[p] = entity of event vals[p]                             (second of two sorts: vals is sorted by time)
-__global__ __launch_bounds__(PH_THREADS) void point_hist_fill_kernel(HistFill a, int mode, uint32_t* __restrict__ keys,
+__global__ __launch_bounds__(DP_THREADS) void point_hist_fill_kernel(HistFill a, int mode, uint32_t* __restrict__ keys,
                                                                      uint32_t* __restrict__ vals) {
   const uint32_t tmask = a.time_bits >= 32 ? 0xFFFFFFFFu : ((1u << a.time_bits) - 1u);
-  for (int64_t i = (int64_t)blockIdx.x * PH_THREADS + threadIdx.x; i < a.n; i += (int64_t)gridDim.x * PH_THREADS) {
+  DP_LOOP(i, a.n) {
     if (mode == 2) {
       const uint32_t v = vals[i];
       keys[i] = (int64_t)v < a.n ? ph_entity(a, v) : (uint32_t)a.n_ent;
@@ -56,52 +55,45 @@ __global__ __launch_bounds__(PH_THREADS) void point_hist_fill_kernel(HistFill a,
   }
 }
 
-// first sorted position whose entity (key >> shift) is >= e
-__device__ __forceinline__ int64_t ph_lower_bound(const uint32_t* __restrict__ keys, int64_t n, int shift, uint32_t e) {
-  int64_t lo = 0, hi = n;
-  while (lo < hi) {
-    const int64_t mid = lo + ((hi - lo) >> 1);
-    if ((keys[mid] >> shift) < e) lo = mid + 1; else hi = mid;
-  }
-  return lo;
-}
-
-__global__ __launch_bounds__(PH_THREADS) void point_hist_segments_kernel(const uint32_t* __restrict__ keys,
+__global__ __launch_bounds__(DP_THREADS) void point_hist_segments_kernel(const uint32_t* __restrict__ keys,
                                                                          const uint32_t* __restrict__ vals,
                                                                          const int32_t* __restrict__ other, int64_t n, int shift,
                                                                          int32_t n_ent, int32_t hist_max_len,
                                                                          int64_t* __restrict__ off, int32_t* __restrict__ seq,
                                                                          int32_t* __restrict__ len) {
   const int64_t total = n > (int64_t)n_ent + 1 ? n : (int64_t)n_ent + 1;
-  for (int64_t i = (int64_t)blockIdx.x * PH_THREADS + threadIdx.x; i < total; i += (int64_t)gridDim.x * PH_THREADS) {
+  DP_LOOP(i, total) {
     if (i < n) {
       const uint32_t v = vals[i];
       seq[i] = ((keys[i] >> shift) < (uint32_t)n_ent && (int64_t)v < n) ? other[v] : 0;
     }
     if (i <= n_ent) {
-      const int64_t b = ph_lower_bound(keys, n, shift, (uint32_t)i);
+      const int64_t b = dp_lower_bound(keys, n, shift, (uint32_t)i);
       off[i] = b;
       if (i < n_ent) {
-        const int64_t c = ph_lower_bound(keys, n, shift, (uint32_t)i + 1u) - b;
+        const int64_t c = dp_lower_bound(keys, n, shift, (uint32_t)i + 1u) - b;
         len[i] = (int32_t)(c < hist_max_len ? c : hist_max_len);
       }
     }
   }
 }
 
-int bits_of(uint32_t x) {          // bits that hold the values 0 .. x
-  int b = 1;
-  while (b < 32 && (x >> b)) ++b;
-  return b;
-}
+struct Temp { SortBufs sort; int64_t total_bytes; };
 
-int64_t pair_words(int64_t n) { return align_up64(n, 64); }       // (each of the four arrays starts on a 256-byte boundary)
+Temp carve(void* temp, int64_t n) {
+  Temp t;
+  Carver c(temp);
+  c.sort_pairs(t.sort, n);
+  c.sort_temp(t.sort, n);
+  t.total_bytes = c.off;
+  return t;
+}
 
 }  // namespace
 
 extern "C" int64_t score_point_hist_temp_bytes(int64_t n_events) {
   if (n_events <= 0 || n_events >= (1ll << 31)) return -1;
-  return 4 * pair_words(n_events) * 4 + score_sort_pairs_temp_bytes(n_events);
+  return carve(nullptr, n_events).total_bytes;
 }
 
 extern "C" int score_point_hist_build(const int32_t* ent, const int32_t* other, const int32_t* time_key, const int32_t* t_idx,
@@ -113,33 +105,23 @@ extern "C" int score_point_hist_build(const int32_t* ent, const int32_t* other, 
   if (n_events >= (1ll << 31) || n_ent == 0x7FFFFFFF) return SCORE_E_SHAPE;
   if (score_point_hist_temp_bytes(n_events) > temp_bytes) return SCORE_E_WORKSPACE;
   hipStream_t s = (hipStream_t)stream;
-  const int64_t w = pair_words(n_events);
-  uint32_t* k0 = reinterpret_cast<uint32_t*>(temp);
-  uint32_t* v0 = k0 + w;
-  uint32_t* k1 = v0 + w;
-  uint32_t* v1 = k1 + w;
-  void* sort_temp = v1 + w;
-  const int64_t sort_bytes = temp_bytes - 4 * w * 4;
+  SortBufs b = carve(temp, n_events).sort;
   HistFill a;
   a.ent = ent; a.time_key = time_key; a.t_idx = t_idx; a.n = n_events;
   a.start_time = start_time; a.pred_time = pred_time; a.id_lo = id_lo; a.n_ent = n_ent; a.time_bits = time_bits;
-  const int ebits = bits_of((uint32_t)n_ent);                  // (the sink is entity n_ent)
+  const int ebits = dp_bits_of((uint32_t)n_ent);                  // (the sink is entity n_ent)
   const bool one_sort = ebits + time_bits <= 32;
-  const unsigned grid = (unsigned)(cdiv64(n_events, PH_THREADS) < 65536 ? cdiv64(n_events, PH_THREADS) : 65536);
-  int32_t in_alt = 0;
-  hipLaunchKernelGGL(point_hist_fill_kernel, dim3(grid), dim3(PH_THREADS), 0, s, a, one_sort ? 0 : 1, k0, v0);
+  const unsigned grid = dp_grid(n_events);
+  hipLaunchKernelGGL(point_hist_fill_kernel, dim3(grid), dim3(DP_THREADS), 0, s, a, one_sort ? 0 : 1, b.k0, b.v0);
   SCORE_CHECK_LAUNCH();
-  SCORE_TRY(score_sort_pairs(k0, v0, k1, v1, n_events, one_sort ? ebits + time_bits : time_bits, sort_temp, sort_bytes, &in_alt, s));
-  if (in_alt) { uint32_t* t = k0; k0 = k1; k1 = t; t = v0; v0 = v1; v1 = t; }
+  SCORE_TRY(dp_sort(b, n_events, one_sort ? ebits + time_bits : time_bits, s));
   if (!one_sort) {
-    hipLaunchKernelGGL(point_hist_fill_kernel, dim3(grid), dim3(PH_THREADS), 0, s, a, 2, k0, v0);
+    hipLaunchKernelGGL(point_hist_fill_kernel, dim3(grid), dim3(DP_THREADS), 0, s, a, 2, b.k0, b.v0);
     SCORE_CHECK_LAUNCH();
-    SCORE_TRY(score_sort_pairs(k0, v0, k1, v1, n_events, ebits, sort_temp, sort_bytes, &in_alt, s));
-    if (in_alt) { uint32_t* t = k0; k0 = k1; k1 = t; t = v0; v0 = v1; v1 = t; }
+    SCORE_TRY(dp_sort(b, n_events, ebits, s));
   }
   const int64_t total = n_events > (int64_t)n_ent + 1 ? n_events : (int64_t)n_ent + 1;
-  const unsigned sgrid = (unsigned)(cdiv64(total, PH_THREADS) < 65536 ? cdiv64(total, PH_THREADS) : 65536);
-  hipLaunchKernelGGL(point_hist_segments_kernel, dim3(sgrid), dim3(PH_THREADS), 0, s, k0, v0, other, n_events,
+  hipLaunchKernelGGL(point_hist_segments_kernel, dim3(dp_grid(total)), dim3(DP_THREADS), 0, s, b.k0, b.v0, other, n_events,
                      one_sort ? time_bits : 0, n_ent, hist_max_len, off, seq, len);
   SCORE_CHECK_LAUNCH();
   return 0;

@@ -1,5 +1,5 @@
-// The device builds' prefix sum (graphbuild.hip, targetgen.hip): reduce-then-scan -- block sums, one workgroup over the block
-// sums, a second pass --, so no workgroup waits on another and nothing is atomic.
+// The device builds' prefix sum (graphbuild.hip, targetgen.hip, logremap.hip, ccmr.hip, through devprep.h): reduce-then-scan --
+// block sums, one workgroup over the block sums, a second pass --, so no workgroup waits on another and nothing is atomic.
 #pragma once
 #include "common.h"
 

@@ -24,12 +24,9 @@
 // Host waits: one per count call (the line count's read-back), none per fill; score_target_host_waits counts them.
 // score_pop_items: per item the count of non-empty slices, a flag, the scan, a compaction in id order.
 // No atomics, no workgroup waits on another: every array is a pure function of the input.
-#include <atomic>
 #include "common.h"
 #include "cellkey.h"
-#include "scan.h"
-
-#define TG_THREADS 256
+#include "devprep.h"
 
 namespace {
 
@@ -37,15 +34,11 @@ static_assert(SCAN_CHUNK == SCORE_TARGET_SCAN_TILE, "the header documents the sc
 constexpr uint64_t TAG_NEG = 4, TAG_POP = 5, TAG_SAMPLE = 6;
 constexpr int TG_MAX_PER_LINE = 4096;
 
-__global__ __launch_bounds__(TG_THREADS) void tg_zero_kernel(int32_t* __restrict__ x, int64_t n) {
-  for (int64_t i = (int64_t)blockIdx.x * TG_THREADS + threadIdx.x; i < n; i += (int64_t)gridDim.x * TG_THREADS) x[i] = 0;
-}
-
-__global__ __launch_bounds__(TG_THREADS) void tg_keys_kernel(const int32_t* __restrict__ uid, const int32_t* __restrict__ iid,
+__global__ __launch_bounds__(DP_THREADS) void tg_keys_kernel(const int32_t* __restrict__ uid, const int32_t* __restrict__ iid,
                                                             const int32_t* __restrict__ t_idx, int64_t n, int32_t U, int32_t I,
                                                             int32_t start_time, int32_t pred_time, uint32_t* __restrict__ keys,
                                                             uint32_t* __restrict__ vals, int32_t* __restrict__ hist) {
-  for (int64_t i = (int64_t)blockIdx.x * TG_THREADS + threadIdx.x; i < n; i += (int64_t)gridDim.x * TG_THREADS) {
+  DP_LOOP(i, n) {
     const int64_t u = (int64_t)uid[i] - 1, it = (int64_t)iid[i] - U - 1;
     const int32_t t = t_idx[i];
     const bool ok = u >= 0 && u < U && it >= 0 && it < I && t >= 0;
@@ -56,11 +49,11 @@ __global__ __launch_bounds__(TG_THREADS) void tg_keys_kernel(const int32_t* __re
 }
 
 // flag[p] = 1 where sorted position p is a head that gets a line, ev[p] = the log position of that event (else -1)
-__global__ __launch_bounds__(TG_THREADS) void tg_flag_kernel(const uint32_t* __restrict__ keys, const uint32_t* __restrict__ vals,
+__global__ __launch_bounds__(DP_THREADS) void tg_flag_kernel(const uint32_t* __restrict__ keys, const uint32_t* __restrict__ vals,
                                                             const int32_t* __restrict__ hist, int64_t n, int32_t U,
                                                             int32_t sample_factor, uint64_t seed, int32_t* __restrict__ flag,
                                                             int32_t* __restrict__ ev) {
-  for (int64_t p = (int64_t)blockIdx.x * TG_THREADS + threadIdx.x; p < n; p += (int64_t)gridDim.x * TG_THREADS) {
+  DP_LOOP(p, n) {
     const uint32_t k = keys[p], v = vals[p];
     bool keep = k < (uint32_t)U && (p == 0 || keys[p - 1] != k) && (int64_t)v < n && hist[k] != 0;
     if (keep && sample_factor > 1)
@@ -89,9 +82,9 @@ __device__ __forceinline__ int32_t tg_word(const Fill& a, uint64_t h, int32_t po
 }
 
 template <bool LISTS>
-__global__ __launch_bounds__(TG_THREADS) void tg_fill_kernel(Fill a) {
+__global__ __launch_bounds__(DP_THREADS) void tg_fill_kernel(Fill a) {
   const int lane = threadIdx.x & 63;
-  const int64_t wave = ((int64_t)blockIdx.x * TG_THREADS + threadIdx.x) >> 6, nwaves = (int64_t)gridDim.x * (TG_THREADS / 64);
+  const int64_t wave = ((int64_t)blockIdx.x * DP_THREADS + threadIdx.x) >> 6, nwaves = (int64_t)gridDim.x * (DP_THREADS / 64);
   for (int64_t base = wave * 64; base < a.n; base += nwaves * 64) {
     const int64_t p = base + lane;
     uint64_t live = __ballot(p < a.n && a.ev[p] >= 0);
@@ -128,9 +121,9 @@ __global__ __launch_bounds__(TG_THREADS) void tg_fill_kernel(Fill a) {
 }
 
 // ------------------------------------------------------------------------------------------------------------- pop items
-__global__ __launch_bounds__(TG_THREADS) void tg_pop_flag_kernel(const int64_t* __restrict__ off1, int32_t U, int32_t I, int32_t S,
+__global__ __launch_bounds__(DP_THREADS) void tg_pop_flag_kernel(const int64_t* __restrict__ off1, int32_t U, int32_t I, int32_t S,
                                                                 int32_t pop_standard, int32_t max_iid, int32_t* __restrict__ flag) {
-  for (int64_t i = (int64_t)blockIdx.x * TG_THREADS + threadIdx.x; i < I; i += (int64_t)gridDim.x * TG_THREADS) {
+  DP_LOOP(i, I) {
     const int64_t* o = off1 + i * S;
     int32_t cnt = 0;
     int64_t prev = o[0];
@@ -143,9 +136,9 @@ __global__ __launch_bounds__(TG_THREADS) void tg_pop_flag_kernel(const int64_t* 
   }
 }
 
-__global__ __launch_bounds__(TG_THREADS) void tg_pop_fill_kernel(const int32_t* __restrict__ flag, const int64_t* __restrict__ idx,
+__global__ __launch_bounds__(DP_THREADS) void tg_pop_fill_kernel(const int32_t* __restrict__ flag, const int64_t* __restrict__ idx,
                                                                 int32_t U, int32_t I, int32_t* __restrict__ pop, int64_t cap) {
-  for (int64_t i = (int64_t)blockIdx.x * TG_THREADS + threadIdx.x; i < I; i += (int64_t)gridDim.x * TG_THREADS) {
+  DP_LOOP(i, I) {
     if (!flag[i]) continue;
     const int64_t q = idx[i];
     if (q >= 0 && q < cap) pop[q] = (int32_t)((int64_t)U + 1 + i);
@@ -153,38 +146,19 @@ __global__ __launch_bounds__(TG_THREADS) void tg_pop_fill_kernel(const int32_t* 
 }
 
 // ------------------------------------------------------------------------------------------------------------------ host
-int tg_bits_of(uint32_t x) {       // bits that hold the values 0 .. x
-  int b = 1;
-  while (b < 32 && (x >> b)) ++b;
-  return b;
-}
-
-unsigned tg_grid(int64_t n) {
-  const int64_t g = cdiv64(n > 0 ? n : 1, TG_THREADS);
-  return (unsigned)(g < 65536 ? g : 65536);
-}
-
-struct Temp {
-  uint32_t* k0; uint32_t* v0; uint32_t* k1; uint32_t* v1;
-  int32_t* flag; int32_t* ev; int32_t* hist; int64_t* lidx; int64_t* bsum; void* sort_temp; int64_t sort_bytes, total_bytes;
-};
+struct Temp { SortBufs sort; int32_t* flag; int32_t* ev; int32_t* hist; int64_t* lidx; int64_t* bsum; int64_t total_bytes; };
 
 Temp carve(void* temp, int64_t n, int64_t U) {
   Temp t;
-  const int64_t w = align_up64(n, 64) * 4;
-  char* p = reinterpret_cast<char*>(temp);
-  t.k0 = reinterpret_cast<uint32_t*>(p); p += w;
-  t.v0 = reinterpret_cast<uint32_t*>(p); p += w;
-  t.k1 = reinterpret_cast<uint32_t*>(p); p += w;
-  t.v1 = reinterpret_cast<uint32_t*>(p); p += w;
-  t.flag = reinterpret_cast<int32_t*>(p); p += w;
-  t.ev = reinterpret_cast<int32_t*>(p); p += w;
-  t.hist = reinterpret_cast<int32_t*>(p); p += align_up64(U, 64) * 4;
-  t.lidx = reinterpret_cast<int64_t*>(p); p += align_up64(n + 1, 32) * 8;
-  t.bsum = reinterpret_cast<int64_t*>(p); p += align_up64(cdiv64(n, SCAN_CHUNK) + 1, 32) * 8;
-  t.sort_temp = p;
-  t.sort_bytes = score_sort_pairs_temp_bytes(n);
-  t.total_bytes = (p - reinterpret_cast<char*>(temp)) + t.sort_bytes;
+  Carver c(temp);
+  c.sort_pairs(t.sort, n);
+  t.flag = c.words<int32_t>(n);
+  t.ev = c.words<int32_t>(n);
+  t.hist = c.words<int32_t>(U);
+  t.lidx = c.prefix(n);
+  t.bsum = c.block_sums(n);
+  c.sort_temp(t.sort, n);
+  t.total_bytes = c.off;
   return t;
 }
 
@@ -192,22 +166,13 @@ struct PopTemp { int32_t* flag; int64_t* idx; int64_t* bsum; int64_t total_bytes
 
 PopTemp pop_carve(void* temp, int64_t I) {
   PopTemp t;
-  char* p = reinterpret_cast<char*>(temp);
-  t.flag = reinterpret_cast<int32_t*>(p); p += align_up64(I, 64) * 4;
-  t.idx = reinterpret_cast<int64_t*>(p); p += align_up64(I + 1, 32) * 8;
-  t.bsum = reinterpret_cast<int64_t*>(p); p += align_up64(cdiv64(I, SCAN_CHUNK) + 1, 32) * 8;
-  t.total_bytes = p - reinterpret_cast<char*>(temp);
+  Carver c(temp);
+  c.scan(t.flag, t.idx, t.bsum, I);
+  t.total_bytes = c.off;
   return t;
 }
 
-std::atomic<int> g_host_waits{0};      // every wait for a stream in this file goes through read_total
-
-int read_total(const int64_t* dev, int64_t* host, hipStream_t s) {
-  g_host_waits.fetch_add(1, std::memory_order_relaxed);
-  hipError_t e = hipMemcpyAsync(host, dev, sizeof(int64_t), hipMemcpyDeviceToHost, s);
-  if (e == hipSuccess) e = hipStreamSynchronize(s);
-  return e == hipSuccess ? 0 : (int)e;
-}
+std::atomic<int> g_host_waits{0};      // every wait for a stream in this file is a dp_read_words that counts here
 
 }  // namespace
 
@@ -243,27 +208,25 @@ int tg_build(const score_target_build_t* a, const int64_t* noff, const int32_t* 
     f.n = n; f.cap_lines = cap_lines; f.n_pop = a->n_pop;
     f.U = U; f.I = a->n_items; f.per = 1 + a->neg_sample_num;
     f.seed = a->seed;
-    const int64_t groups = cdiv64(cdiv64(n, 64), TG_THREADS / 64);
+    const int64_t groups = cdiv64(cdiv64(n, 64), DP_THREADS / 64);
     const dim3 grid((unsigned)(groups < 8192 ? groups : 8192));
-    if (noff) hipLaunchKernelGGL(tg_fill_kernel<true>, grid, dim3(TG_THREADS), 0, s, f);
-    else hipLaunchKernelGGL(tg_fill_kernel<false>, grid, dim3(TG_THREADS), 0, s, f);
+    if (noff) hipLaunchKernelGGL(tg_fill_kernel<true>, grid, dim3(DP_THREADS), 0, s, f);
+    else hipLaunchKernelGGL(tg_fill_kernel<false>, grid, dim3(DP_THREADS), 0, s, f);
     SCORE_CHECK_LAUNCH();
     return 0;
   }
-  uint32_t* k = t.k0; uint32_t* v = t.v0;
-  int32_t in_alt = 0;
-  hipLaunchKernelGGL(tg_zero_kernel, dim3(tg_grid(U)), dim3(TG_THREADS), 0, s, t.hist, (int64_t)U);
+  SortBufs b = t.sort;
+  hipLaunchKernelGGL(dp_zero_kernel<int32_t>, dim3(dp_grid(U)), dim3(DP_THREADS), 0, s, t.hist, (int64_t)U);
   SCORE_CHECK_LAUNCH();
-  hipLaunchKernelGGL(tg_keys_kernel, dim3(tg_grid(n)), dim3(TG_THREADS), 0, s, a->uid, a->iid, a->t_idx, n, U, a->n_items,
-                     a->start_time, a->pred_time, k, v, t.hist);
+  hipLaunchKernelGGL(tg_keys_kernel, dim3(dp_grid(n)), dim3(DP_THREADS), 0, s, a->uid, a->iid, a->t_idx, n, U, a->n_items,
+                     a->start_time, a->pred_time, b.k0, b.v0, t.hist);
   SCORE_CHECK_LAUNCH();
-  SCORE_TRY(score_sort_pairs(k, v, t.k1, t.v1, n, tg_bits_of((uint32_t)U), t.sort_temp, t.sort_bytes, &in_alt, s));
-  if (in_alt) { k = t.k1; v = t.v1; }
-  hipLaunchKernelGGL(tg_flag_kernel, dim3(tg_grid(n)), dim3(TG_THREADS), 0, s, k, v, t.hist, n, U, a->sample_factor, a->seed,
+  SCORE_TRY(dp_sort(b, n, dp_bits_of((uint32_t)U), s));
+  hipLaunchKernelGGL(tg_flag_kernel, dim3(dp_grid(n)), dim3(DP_THREADS), 0, s, b.k0, b.v0, t.hist, n, U, a->sample_factor, a->seed,
                      t.flag, t.ev);
   SCORE_CHECK_LAUNCH();
   SCORE_TRY(gb_scan(t.flag, n, t.bsum, t.lidx, s));
-  return read_total(t.lidx + n, n_lines, s);
+  return dp_read_words(t.lidx + n, n_lines, 1, s, &g_host_waits);
 }
 
 }  // namespace
@@ -301,14 +264,14 @@ extern "C" int score_pop_items(const score_pop_items_t* a, int32_t* pop_items, i
   const int64_t I = a->n_items;
   const PopTemp t = pop_carve(temp, I);
   if (pop_items) {
-    hipLaunchKernelGGL(tg_pop_fill_kernel, dim3(tg_grid(I)), dim3(TG_THREADS), 0, s, t.flag, t.idx, a->n_users, a->n_items,
+    hipLaunchKernelGGL(tg_pop_fill_kernel, dim3(dp_grid(I)), dim3(DP_THREADS), 0, s, t.flag, t.idx, a->n_users, a->n_items,
                        pop_items, cap_pop);
     SCORE_CHECK_LAUNCH();
     return 0;
   }
-  hipLaunchKernelGGL(tg_pop_flag_kernel, dim3(tg_grid(I)), dim3(TG_THREADS), 0, s, a->item_off1, a->n_users, a->n_items,
+  hipLaunchKernelGGL(tg_pop_flag_kernel, dim3(dp_grid(I)), dim3(DP_THREADS), 0, s, a->item_off1, a->n_users, a->n_items,
                      a->time_slice_num, a->pop_standard, a->max_iid, t.flag);
   SCORE_CHECK_LAUNCH();
   SCORE_TRY(gb_scan(t.flag, I, t.bsum, t.idx, s));
-  return read_total(t.idx + I, n_pop, s);
+  return dp_read_words(t.idx + I, n_pop, 1, s, &g_host_waits);
 }

@@ -305,10 +305,7 @@ class TemporalGraph(object):
             n = int(d_uid.numel())
             if n == 0 or d_iid.numel() != n or d_t.numel() != n:
                 raise ValueError("from_log(build='device'): uid, iid and t_idx must be non-empty and of one length")
-            temp_bytes = int(lib.score_graph_build_temp_bytes(n, U, I, S))
-            if temp_bytes < 0:
-                _lib.check(-2, "score_graph_build_temp_bytes")
-            temp = torch.empty((temp_bytes,), dtype=torch.uint8, device=dev)
+            temp, temp_bytes = _lib.workspace("score_graph_build", dev, n, U, I, S)
             b = {"u_off1": torch.empty((U * S + 1,), dtype=torch.int64, device=dev),
                  "i_off1": torch.empty((I * S + 1,), dtype=torch.int64, device=dev),
                  "u_nbr1": torch.empty((n,), dtype=torch.int32, device=dev),
@@ -316,7 +313,7 @@ class TemporalGraph(object):
             a = _lib.GraphBuild(C.sizeof(_lib.GraphBuild), _ptr(d_uid), _ptr(d_iid), _ptr(d_t), n, U, I, S, int(max_1hop),
                                 int(max_2hop), 0, int(seed) & 0xFFFFFFFFFFFFFFFF, _ptr(b["u_off1"]), _ptr(b["u_nbr1"]),
                                 _ptr(b["i_off1"]), _ptr(b["i_nbr1"]))
-            stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+            stream = _lib.current_stream(dev)
             clock = [time.perf_counter()]
 
             def lap(name):
@@ -542,7 +539,7 @@ class DeviceGraphLoader(object):
         it = self.iids[self._pos * c:(self._pos + n) * c]
         rc = self.lib.score_batch_assemble(C.byref(g.struct), _ptr(u), _ptr(it), n, self.neg, T, K, self.start_time,
                                            self.pred_time, C.c_uint64(self.seed + 7919 * self._batch_no),
-                                           C.byref(out), C.c_void_p(torch.cuda.current_stream(g.device).cuda_stream))
+                                           C.byref(out), _lib.current_stream(g.device))
         _lib.check(rc, "score_batch_assemble")
         self._pos += n
         self._batch_no += 1

@@ -50,11 +50,6 @@ def key_bits_of(lo, hi):
     return 32 if lo < 0 else max(1, int(hi).bit_length())
 
 
-def _stream(dev):
-    import torch
-    return C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-
-
 def log_slices_tmall(mmdd, status):
     """MMDD int32 tensor -> t_idx int32 tensor; status: zeroed int32 tensor [1], set to 1 by an invalid date (no wait here)"""
     import torch
@@ -63,7 +58,8 @@ def log_slices_tmall(mmdd, status):
     t_idx = torch.empty_like(mmdd)
     with torch.cuda.device(dev):
         _lib.check(lib.score_log_slices(_lib.LOG_SLICES_TMALL, mmdd.data_ptr(), None, int(mmdd.numel()), 0, 0, 0,
-                                        t_idx.data_ptr(), None, status.data_ptr(), _stream(dev)), "score_log_slices (tmall)")
+                                        t_idx.data_ptr(), None, status.data_ptr(), _lib.current_stream(dev)),
+                   "score_log_slices (tmall)")
     return t_idx
 
 
@@ -76,7 +72,7 @@ def log_slices_epoch(ts, flag, start_ts, end_ts, delta):
     with torch.cuda.device(dev):
         _lib.check(lib.score_log_slices(_lib.LOG_SLICES_EPOCH, ts.data_ptr(), None if flag is None else flag.data_ptr(),
                                         int(ts.numel()), int(start_ts), int(end_ts), int(delta), t_idx.data_ptr(), keep.data_ptr(),
-                                        None, _stream(dev)), "score_log_slices (epoch)")
+                                        None, _lib.current_stream(dev)), "score_log_slices (epoch)")
     return t_idx, keep
 
 
@@ -88,15 +84,12 @@ def log_compact(cols, keep):
     n, k = int(keep.numel()), len(cols)
     with torch.cuda.device(dev):
         out = torch.empty((k + 1, _pitch(n)), dtype=torch.int32, device=dev)
-        temp_bytes = int(lib.score_log_compact_temp_bytes(n))
-        if temp_bytes < 0:
-            _lib.check(-2, "score_log_compact_temp_bytes")
-        temp = torch.empty((temp_bytes,), dtype=torch.uint8, device=dev)
+        temp, temp_bytes = _lib.workspace("score_log_compact", dev, n)
         cin = (C.c_void_p * k)(*[c.data_ptr() for c in cols])
         cout = (C.c_void_p * k)(*[out[j].data_ptr() for j in range(k)])
         n_kept = C.c_int64(-1)
         _lib.check(lib.score_log_compact(cin, cout, k, keep.data_ptr(), n, out[k].data_ptr(), n, C.byref(n_kept),
-                                         temp.data_ptr(), temp_bytes, _stream(dev)), "score_log_compact")
+                                         temp.data_ptr(), temp_bytes, _lib.current_stream(dev)), "score_log_compact")
         m = int(n_kept.value)
         if m:
             torch.cuda.current_stream(dev).synchronize()          # (temp is released behind this)
@@ -115,10 +108,7 @@ def log_remap(cols, key_bits, tables=(), download=True):
         raise ValueError("log_remap: the columns must be non-empty and of one length")
     with torch.cuda.device(dev):
         ids = torch.empty((k, _pitch(n)), dtype=torch.int32, device=dev)
-        temp_bytes = int(lib.score_log_remap_temp_bytes(n, k))
-        if temp_bytes < 0:
-            _lib.check(-2, "score_log_remap_temp_bytes")
-        temp = torch.empty((temp_bytes,), dtype=torch.uint8, device=dev)
+        temp, temp_bytes = _lib.workspace("score_log_remap", dev, n, k)
         a = _lib.LogRemap()
         a.struct_bytes, a.n_events, a.n_cols, a.key_bits, a.n_tables = C.sizeof(_lib.LogRemap), n, k, int(key_bits), len(tables)
         for c in range(k):
@@ -128,7 +118,7 @@ def log_remap(cols, key_bits, tables=(), download=True):
             for j, f in enumerate(feats):
                 a.tables[t].feat[j] = int(f)
         counts = (C.c_int64 * k)()
-        stream = _stream(dev)
+        stream = _lib.current_stream(dev)
         _lib.check(lib.score_log_remap(C.byref(a), None, None, counts, temp.data_ptr(), temp_bytes, stream),
                    "score_log_remap (count)")
         counts = tuple(int(x) for x in counts)
@@ -165,10 +155,7 @@ def ccmr_prep(raw, movie, n_users, n_items, vocab, start_day, delta_days):
     with torch.cuda.device(dev):
         out = torch.empty((6, _pitch(n)), dtype=torch.int32, device=dev)
         flat = torch.empty((_lib.CCMR_STATUS_WORDS + I * 5,), dtype=torch.int32, device=dev)
-        temp_bytes = int(lib.score_ccmr_prep_temp_bytes(m, I))
-        if temp_bytes < 0:
-            _lib.check(-2, "score_ccmr_prep_temp_bytes")
-        temp = torch.empty((temp_bytes,), dtype=torch.uint8, device=dev)
+        temp, temp_bytes = _lib.workspace("score_ccmr_prep", dev, m, I)
         a = _lib.CcmrPrep()
         a.struct_bytes, a.n_events, a.n_movies, a.n_users, a.n_items = C.sizeof(_lib.CcmrPrep), n, m, int(n_users), I
         a.user, a.item, a.rating, a.date = (raw[j].data_ptr() for j in range(4))
@@ -179,6 +166,6 @@ def ccmr_prep(raw, movie, n_users, n_items, vocab, start_day, delta_days):
         a.start_day, a.delta_days = int(start_day), int(delta_days)
         a.uid, a.iid, a.t_idx, a.day, a.keep_pos, a.keep_neg = (out[j].data_ptr() for j in range(6))
         a.status, a.item_rows = flat.data_ptr(), flat.data_ptr() + 4 * _lib.CCMR_STATUS_WORDS
-        _lib.check(lib.score_ccmr_prep(C.byref(a), temp.data_ptr(), temp_bytes, _stream(dev)), "score_ccmr_prep")
+        _lib.check(lib.score_ccmr_prep(C.byref(a), temp.data_ptr(), temp_bytes, _lib.current_stream(dev)), "score_ccmr_prep")
     # (temp goes back to the allocator of the stream the launches are on: whatever reuses it is ordered behind them)
     return [out[j, :n] for j in range(6)], flat

@@ -506,9 +506,8 @@ class PointLogStore(object):
         lib = _lib.load()
         uid, iid, time_key, t_idx = [c.to(dev) if torch.is_tensor(c) else torch.from_numpy(c).to(dev) for c in self._log]
         n, U, I = int(uid.numel()), self.n_users, self.n_items
-        temp_bytes = int(lib.score_point_hist_temp_bytes(n))
-        temp = torch.empty((temp_bytes,), dtype=torch.uint8, device=dev)
-        stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+        temp, temp_bytes = _lib.workspace("score_point_hist", dev, n)
+        stream = _lib.current_stream(dev)
         ptr = lambda t: C.c_void_p(t.data_ptr())
         out = {}
         for side, ent, other, id_lo, n_ent in (("user", uid, iid, 1, U), ("item", iid, uid, U + 1, I)):
@@ -704,7 +703,7 @@ class DeviceDataLoaderUserSeq(object):
         call = self.lib.score_point_batch_assemble_log if self.from_log else self.lib.score_point_batch_assemble
         rc = call(C.byref(st.struct), i * self.lines_per_batch, self.lines_per_batch, st.per_line, self._T, st.Fu, st.Fi,
                   C.byref(out), M._ptr(tens[8]) if self.dual else None,
-                  C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream))
+                  _lib.current_stream(self.device))
         _lib.check(rc, "score_point_batch_assemble_log" if self.from_log else "score_point_batch_assemble")
         self._batch_no = i + 1
         return _point_batch_class()(tens, flat, self.batch_size, self._active[i], self.spec, self._feed_shapes)

@@ -37,11 +37,10 @@ def pop_items_device(graph, pop_standard, max_iid=None):
     b, dev = graph._built, graph._built_device
     lib = _lib.load()
     with torch.cuda.device(dev):
-        temp_bytes = int(lib.score_pop_items_temp_bytes(graph.I))
-        temp = torch.empty((temp_bytes,), dtype=torch.uint8, device=dev)
+        temp, temp_bytes = _lib.workspace("score_pop_items", dev, graph.I)
         a = _lib.PopItems(C.sizeof(_lib.PopItems), b["i_off1"].data_ptr(), graph.U, graph.I, graph.S, int(pop_standard),
                           int(max_iid) if max_iid is not None else 2 ** 31 - 1, 0)
-        stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+        stream = _lib.current_stream(dev)
         n_pop = C.c_int64(-1)
         _lib.check(lib.score_pop_items(C.byref(a), None, 0, C.byref(n_pop), temp.data_ptr(), temp_bytes, stream),
                    "score_pop_items (count)")
@@ -104,15 +103,12 @@ class UserNegLists(object):
             n = int(d_u.numel())
             if int(d_i.numel()) != n:
                 raise ValueError("neg_uid and neg_iid must be of one length")
-            temp_bytes = int(lib.score_neg_lists_temp_bytes(n))
-            if temp_bytes < 0:
-                _lib.check(-2, "score_neg_lists_temp_bytes")
-            temp = torch.empty((temp_bytes,), dtype=torch.uint8, device=dev)
+            temp, temp_bytes = _lib.workspace("score_neg_lists", dev, n)
             off = torch.empty((U + 1,), dtype=torch.int64, device=dev)
             items = torch.empty((n,), dtype=torch.int32, device=dev)
             ptr = lambda t: t.data_ptr() if n else None
             _lib.check(lib.score_neg_lists_build(ptr(d_u), ptr(d_i), n, U, off.data_ptr(), ptr(items), temp.data_ptr(), temp_bytes,
-                                                 C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)), "score_neg_lists_build")
+                                                 _lib.current_stream(dev)), "score_neg_lists_build")
             torch.cuda.current_stream(dev).synchronize()          # (temp and uploaded columns are released behind this)
         return cls(off, items, U)
 
@@ -224,14 +220,11 @@ class TargetStore(object):
                 d_pop = None if pop_items is None else up(pop_items)
             n_pop = 0 if d_pop is None else int(d_pop.numel())
             pop_arg = None if d_pop is None else d_pop if n_pop else torch.zeros((1,), dtype=torch.int32, device=dev)
-            temp_bytes = int(lib.score_target_build_temp_bytes(n, U))
-            if temp_bytes < 0:
-                _lib.check(-2, "score_target_build_temp_bytes")
-            temp = torch.empty((temp_bytes,), dtype=torch.uint8, device=dev)
+            temp, temp_bytes = _lib.workspace("score_target_build", dev, n, U)
             a = _lib.TargetBuild(C.sizeof(_lib.TargetBuild), d_uid.data_ptr(), d_iid.data_ptr(), d_t.data_ptr(), n, U, I,
                                  int(start_time), int(pred_time), neg, int(sample_factor or 0), int(seed) & 0xFFFFFFFFFFFFFFFF,
                                  None if pop_arg is None else pop_arg.data_ptr(), n_pop)
-            stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+            stream = _lib.current_stream(dev)
             n_lines = C.c_int64(-1)
             call, what = lib.score_target_build, "score_target_build"
             if neg_lists is not None:

@@ -47,6 +47,11 @@ def case(name):
     elif name == "factor_lists":                    # a down-sampling factor together with lists
         c = dict(tc.case("factor4"))
         u, i = _events_of_lengths(rng, rng.integers(0, 6, c["U"]), c["U"], c["I"])
+    elif name.startswith("users_"):                 # users_<U>: target_cases' case of that name and 500 negative events, half of
+        c = dict(tc.case(name))                     # them of users of its log; a uid outside the range on each side
+        u = np.concatenate([rng.choice(c["uid"], 250), rng.integers(1, c["U"] + 1, 250)])
+        u[[7, 491]] = [c["U"] + 1, 0]
+        i = rng.integers(c["U"] + 1, c["U"] + c["I"] + 1, 500)
     else:
         raise KeyError(name)
     c["neg_uid"], c["neg_iid"] = np.ascontiguousarray(u, dtype=np.int64), np.ascontiguousarray(i, dtype=np.int64)
@@ -56,7 +61,8 @@ def case(name):
 
 
 LIST_CASES = (["nneg_%d" % n for n in NEG_COUNTS] + ["one_owner", "all_long_neg5", "lens_neg5", "pop_lists", "factor_lists"] +
-              ["width_neg%d" % k for k in WIDTHS])
+              ["width_neg%d" % k for k in WIDTHS] + ["users_4095", "users_4096"])
+PASS_LOGS = ("items_4095", "items_4096")          # raw logs whose movie lines sort in one and in two passes (keys 0 .. I)
 
 START = datetime.date(2005, 5, 19)
 # calendar edges, and both sides of the start: the 89th day before it is still slice 0, the 90th is slice -1
@@ -74,7 +80,8 @@ def yyyymmdd(day_from_start):
 @functools.lru_cache(maxsize=None)
 def raw_log(name):
     """-> (log [n, 4], movie_info [m, 5], U, I): 'edges' = one event per EDGE_DATES entry and rating; 'tenk' = about 10 k events
-    over 41 slices and some days before the start, about a fifth of them negative"""
+    over 41 slices and some days before the start, about a fifth of them negative; 'items_<I>' = 400 events over the 250 items
+    that have a movie line (300 lines: 50 items have two), most of the I items without one"""
     rng = np.random.Generator(np.random.PCG64(tc.hash_name(name)))
     if name == "edges":
         U, I = 7, 5
@@ -88,9 +95,16 @@ def raw_log(name):
         rating = np.where(rng.random(n) < 0.2, rng.integers(1, 4, n), rng.integers(4, 6, n))
         log = np.stack([rng.integers(0, U, n), rng.integers(0, I, n), rating, [yyyymmdd(d) for d in days]], axis=1)
         log = log[rng.permutation(n)]
+    elif name.startswith("items_"):
+        U, I, n = 40, int(name.split("_")[1]), 400
+        lined = np.concatenate([[0, I - 1], rng.choice(np.arange(1, I - 1), 248, replace=False)])
+        rating = np.where(rng.random(n) < 0.2, rng.integers(1, 4, n), rng.integers(4, 6, n))
+        log = np.stack([rng.integers(0, U, n), rng.choice(lined, n), rating, [yyyymmdd(d) for d in rng.integers(0, 41 * 90, n)]], axis=1)
+        items = np.concatenate([lined, rng.choice(lined, 50, replace=False)])[rng.permutation(300)]
     else:
         raise KeyError(name)
-    items = np.concatenate([rng.permutation(I), rng.integers(0, I, I // 3)])      # a third of the items has a second line
+    if not name.startswith("items_"):
+        items = np.concatenate([rng.permutation(I), rng.integers(0, I, I // 3)])  # a third of the items has a second line
     feat = np.stack([np.where(rng.random(len(items)) < 0.2, -1, rng.integers(0, v - 1, len(items))) for v in VOCAB], axis=1)
     movie = np.concatenate([items[:, None], feat], axis=1)
     log, movie = np.ascontiguousarray(log, dtype=np.int64), np.ascontiguousarray(movie, dtype=np.int64)

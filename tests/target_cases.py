@@ -91,6 +91,17 @@ def case(name):
             c.update(factor=4, neg=99)
         elif "_neg" in name:
             c["neg"] = int(name.split("_neg")[1])
+    elif name.startswith("users_"):                    # users_<U>, users_<U>_pop: 600 events, most users absent, 40 or so eligible
+        U = int(name.split("_")[1])                    # (both ends of the id range among them); the sort's keys are 0 .. U
+        some = np.unique(np.concatenate([[1, U], rng.integers(1, U + 1, 38)]))
+        u, i, t = _random_log(rng, 600 - 2 * len(some), U, 50, 6)
+        order = rng.permutation(600)
+        c.update(U=U, I=50)
+        c["uid"] = np.concatenate([some, some, u])[order]
+        c["iid"] = np.concatenate([rng.integers(U + 1, U + 51, 2 * len(some)), i])[order]
+        c["t_idx"] = np.concatenate([np.full(len(some), 2), np.full(len(some), 4), t])[order]
+        if name.endswith("_pop"):
+            c["pop"] = np.sort(rng.choice(np.arange(U + 1, U + 51), 9, replace=False)).astype(np.int32)
     else:
         raise KeyError(name)
     for k in ("uid", "iid", "t_idx"):
@@ -103,13 +114,21 @@ def hash_name(name):
     return sum((k + 1) * ord(ch) for k, ch in enumerate(name)) * 2654435761 % (2 ** 31)
 
 
+def sort_passes(max_key):
+    """radix passes of score_sort_pairs over keys 0 .. max_key: 12 bits a pass.  An odd count leaves the result in the
+    alternate pair of arrays, an even one in the first"""
+    return -(-max(1, int(max_key).bit_length()) // 12)
+
+
 # line widths 1 + neg above 4 that are no multiple of 4 words: most lines start off a 16-byte boundary, so the fill kernel's
 # one-word stores in front of and behind its 16-byte stores all run
 ODD_WIDTH_CASES = ["all_eligible_neg4", "all_eligible_neg6", "all_eligible_neg100", "pop_list_neg6", "pop_list_neg10"]
+# user counts on both sides of the sort's second pass (keys 0 .. U: 12 bits hold 4,095, 13 are two passes)
+PASS_CASES = ["users_4095", "users_4096", "users_4096_pop"]
 CASES = (["tile_%d" % n for n in TILE_COUNTS] +
          ["edges", "edges_neg0", "edges_neg1", "edges_neg99", "edges_neg4095", "edges_factor1", "edges_factor4_seed3", "edges_pop",
           "pop_list_factor4_neg99", "no_pred_slice", "all_eligible", "one_item", "highest_user_only", "factor0", "factor1",
-          "factor4", "pop_list"] + ODD_WIDTH_CASES)
+          "factor4", "pop_list"] + ODD_WIDTH_CASES + PASS_CASES)
 
 
 def host_lines(c):

@@ -168,6 +168,23 @@ def test_cases_hold_what_they_are_for():
         if name != "all_long_neg5":
             assert (own < li.shape[1] - 1).any(), name
     assert {host_arrays("width_neg%d" % k)[1].shape[1] for k in cc.WIDTHS} == {2, 6, 7, 100, 101}
+    # both sorts of the list path (the lines' and the lists', keys 0 .. U) in one pass and in two: every other case takes one
+    assert {tc.sort_passes(cc.case(n)["U"]) for n in cc.LIST_CASES if not n.startswith("users_")} == {1}
+    assert (tc.sort_passes(cc.case("users_4095")["U"]), tc.sort_passes(cc.case("users_4096")["U"])) == (1, 2)
+    for name in ("users_4095", "users_4096"):
+        c = cc.case(name)
+        assert len(c["neg_uid"]) == 500 and c["neg_uid"].min() == 0 and c["neg_uid"].max() == c["U"] + 1, name
+        assert lens(name).sum() == 498 and 24 <= len(host_arrays(name)[0]) <= 60, name
+    # score_ccmr_prep sorts its movie lines by item (keys 0 .. I): the other raw logs take one pass
+    assert {tc.sort_passes(cc.raw_log(n)[3]) for n in ("edges", "tenk")} == {1}
+    assert [tc.sort_passes(cc.raw_log(n)[3]) for n in cc.PASS_LOGS] == [1, 2]
+    for name in cc.PASS_LOGS:
+        log, movie, U, I = cc.raw_log(name)
+        items, lines = np.unique(movie[:, 0], return_counts=True)
+        assert len(log) == 400 and len(movie) == 300 and len(items) == 250 < I // 4 and items[0] == 0 and items[-1] == I - 1, name
+        two = items[lines == 2]                                       # the first line counts: the second one differs
+        assert len(two) == 50 and all((np.diff(movie[movie[:, 0] == x][:, 1:], axis=0) != 0).any() for x in two), name
+        assert set(log[:, 1].tolist()) & set(two.tolist()) and set(log[:, 1].tolist()) <= set(items.tolist()), name
     assert cc.case("pop_lists")["pop"] is not None and cc.case("factor_lists")["factor"] == 4
     plain = tc.host_lines(tc.case("factor4"))
     assert [u for u, _ in plain] == host_arrays("factor_lists")[0].tolist()      # the lists change no line's fate
@@ -294,6 +311,13 @@ def test_dates_at_the_calendar_edges_and_on_both_sides_of_the_start():
     for build in ("host", "device"):
         with pytest.raises(ValueError, match="%d items occur" % len(set(log[h["pos"], 1].tolist()))):
             dp.remap_ccmr_log(log, movie[:0], U, I, cc.VOCAB, build=build)
+
+
+@pytest.mark.parametrize("name", cc.PASS_LOGS)
+def test_movie_lines_sorted_in_one_and_in_two_passes(name):
+    """item counts on both sides of the sort's second pass; most items have no line, 50 have two"""
+    log, movie, U, I = cc.raw_log(name)
+    assert_same_remap(dp.remap_ccmr_log(log, movie, U, I, cc.VOCAB, build="device"), dp.remap_ccmr_log(log, movie, U, I, cc.VOCAB))
 
 
 def test_bad_dates_ids_and_features_raise_the_hosts_value_error():

@@ -111,6 +111,15 @@ def test_cases_hold_what_they_are_for():
         assert per > 4 and per % 4 != 0 and len(lu) >= 8, name
         assert {(l * per * 4) % 16 for l in range(len(lu))} == {0, 4, 8, 12}, name
     assert {host_arrays(n)[1].shape[1] for n in tc.ODD_WIDTH_CASES} == {5, 7, 11, 101}
+    # the sort's result lands in either pair of arrays: every other case sorts in one pass (keys 0 .. U below 4,096)
+    assert tc.sort_passes(4095) == 1 and tc.sort_passes(4096) == 2 and tc.sort_passes(2 ** 24) == 3
+    assert {tc.sort_passes(tc.case(n)["U"]) for n in tc.CASES if n not in tc.PASS_CASES} == {1}
+    assert [tc.sort_passes(tc.case(n)["U"]) for n in tc.PASS_CASES] == [1, 2, 2]
+    for name in tc.PASS_CASES:
+        c, (lu, _) = tc.case(name), host_arrays(name)
+        assert c["I"] == 50 and len(c["uid"]) == 600 and len(set(c["uid"].tolist())) < c["U"] // 4, name      # most users absent
+        assert 24 <= len(lu) <= 60 and lu[0] == 1 and lu[-1] == c["U"], name
+    assert tc.case("users_4096_pop")["pop"] is not None and tc.case("users_4096")["pop"] is None
 
 
 @pytest.mark.parametrize("name", tc.ODD_WIDTH_CASES)
