@@ -533,7 +533,10 @@ typedef struct {
                            (SCORE_MODEL_DEEMS) its two recurrences one launch per side instead of one grouped launch;
                            bit 15 (32768) = the co-attention backward loads the seq1 / seq2 rows of EVERY neighbour for the
                            w1 / w2 gradients, instead of only those whose relu'd score is > 0 (an inactive one contributes
-                           dz = 0 times its row: the same bits on a finite table; csrc/embed.hip).
+                           dz = 0 times its row: the same bits on a finite table; csrc/embed.hip);
+                           bit 16 (65536) = the co-attention backward requests a unit's ids and saved scalars one unit ahead,
+                           behind the pass-1 rows of the unit before, instead of at the top of the unit's own iteration
+                           (same registers, same arithmetic, same bits; K <= 10 only; measured inside the noise at cfg-3).
                            The ONLY switches of the launch sequence: the library reads no environment variable       */
   uint8_t* row_flags;   /* optional [n_table_rows] row state of the dense table optimizer (see
                            score_adam_rows): score_backward (scatter_mode 0) marks every row it

@@ -249,19 +249,130 @@ __device__ __forceinline__ void rows_in_flight(float4& row, const float4& last) 
   asm volatile("" : "+v"(row.x), "+v"(row.y), "+v"(row.z), "+v"(row.w) : "v"(last.w));
 }
 
-template <int KMAX, int SPL, bool ATOMIC>
+// Per-unit metadata of the backward, ONE ELEMENT PER LANE (the instances with NM > 0).  A unit's K*F ids of each index
+// tensor and its 3K saved scalars (K relu'd scores from rsave, then the 2K score gradients of ginfo) are lists whose
+// addresses depend on nothing but the unit's number, and every lane of a feature needs the same few of them.  Instead of
+// 2K id registers and 3K scalar registers in every lane, the GS lanes of the unit's group load each list contiguously:
+//  * ids: register i of lane gl holds element i * kpr * F + gl, i.e. the ids of the kpr = 2^ksh neighbours
+//    [i * kpr, (i + 1) * kpr) (kpr * F <= GS; lanes past kpr * F and elements past K * F repeat the last element).  The
+//    register a neighbour k lives in, k >> ksh, is the same in every lane: a select between registers and ONE
+//    ds_bpermute inside the group give lane gl the id of (k, its feature) when it uses it;
+//  * scalars: register i of lane gl holds element i * GS + gl; element e is broadcast from lane e % GS.
+// Ids outside the table become row 0 once, on the lane that loaded them.  NM registers per list: coattn_meta_regs()
+// says what a geometry needs, and score_coattn_bwd_multi takes the NM = 0 instance (every lane reads its own ids and
+// scalars, nothing a unit ahead) where that is more than the instance holds.
+
+static inline int coattn_ksh(int GS, int F) {      // log2 of the neighbours per id register; -1: a feature set does not fit a group
+  if (F > GS) return -1;
+  int sh = 0;
+  while ((2 << sh) * F <= GS) ++sh;
+  return sh;
+}
+static inline int coattn_meta_regs(int GS, int F, int K) {      // registers per list (0: not in this form)
+  const int ksh = coattn_ksh(GS, F);
+  if (ksh < 0) return 0;
+  const int ids = (K + (1 << ksh) - 1) >> ksh, sc = (3 * K + GS - 1) / GS;
+  return ids > sc ? ids : sc;
+}
+
+// One list: up to four registers, NAMED (r0 .. r3; an instance touches the first NM).  As an array read through selects
+// on the register number the compiler kept the list in scratch memory and indexed it there.
+template <typename T> struct MetaList { T r0, r1, r2, r3; };
+struct UnitMeta { MetaList<int32_t> a, b; MetaList<float> s; };      // ids of idx1, ids of idx2, saved scalars
+template <int I, typename T> __device__ __forceinline__ T& meta_at(MetaList<T>& l) {
+  if constexpr (I == 0) return l.r0;
+  else if constexpr (I == 1) return l.r1;
+  else if constexpr (I == 2) return l.r2;
+  else return l.r3;
+}
+// register `reg` (the same in every lane, < NM) of a list
+template <int NM, typename T>
+__device__ __forceinline__ T meta_reg(const MetaList<T>& l, int reg) {
+  static_assert(NM >= 1 && NM <= 4, "a list is at most four registers");
+  T v = l.r0;
+  if constexpr (NM > 1) { const T x = l.r1; v = reg == 1 ? x : v; }
+  if constexpr (NM > 2) { const T x = l.r2; v = reg == 2 ? x : v; }
+  if constexpr (NM > 3) { const T x = l.r3; v = reg == 3 ? x : v; }
+  return v;
+}
+
+// every load unconditional, to a clamped, valid position
+template <int I>
+__device__ __forceinline__ void unit_meta_load1(UnitMeta& m, const int32_t* __restrict__ i1, const int32_t* __restrict__ i2,
+                                                const float* __restrict__ rs, const float* __restrict__ gi, int K, int KF,
+                                                int GS, int per, int gc, int gl) {
+  const int e = I * per + gc, es = I * GS + gl;
+  const int ei = e < KF ? e : KF - 1;
+  const int esc = es < 3 * K ? es : 3 * K - 1;
+  meta_at<I>(m.a) = i1[ei];
+  meta_at<I>(m.b) = i2[ei];
+  meta_at<I>(m.s) = *(esc < K ? rs + esc : gi + (esc - K));
+}
+template <int I>
+__device__ __forceinline__ void unit_meta_clamp1(UnitMeta& m, uint32_t n_rows) {      // (the forward reported them: score_state_t.id_status)
+  const int32_t x = meta_at<I>(m.a), y = meta_at<I>(m.b);
+  meta_at<I>(m.a) = (uint32_t)x < n_rows ? x : 0;
+  meta_at<I>(m.b) = (uint32_t)y < n_rows ? y : 0;
+}
+template <int NM>
+__device__ __forceinline__ void unit_meta_load(UnitMeta& m, const CoattnArgs& a, const CoattnCall& cc, int u, int gl) {
+  const int K = a.K, KF = a.K * cc.F, GS = cc.GS, per = cc.F << cc.ksh;
+  const int ub = u / a.T;
+  const int64_t ui = (int64_t)ub * a.Tidx + (u - ub * a.T);   // [B, Tidx, K, F] strides of the index tensors
+  const int32_t* __restrict__ i1 = cc.idx1 + ui * KF;
+  const int32_t* __restrict__ i2 = cc.idx2 + ui * KF;
+  const float* __restrict__ rs = cc.rsave + (int64_t)u * K;
+  const float* __restrict__ gi = cc.ginfo + (int64_t)u * cc.ldi;
+  const int gc = gl < per ? gl : per - 1;
+  unit_meta_load1<0>(m, i1, i2, rs, gi, K, KF, GS, per, gc, gl);
+  if constexpr (NM > 1) unit_meta_load1<1>(m, i1, i2, rs, gi, K, KF, GS, per, gc, gl);
+  if constexpr (NM > 2) unit_meta_load1<2>(m, i1, i2, rs, gi, K, KF, GS, per, gc, gl);
+  if constexpr (NM > 3) unit_meta_load1<3>(m, i1, i2, rs, gi, K, KF, GS, per, gc, gl);
+  unit_meta_clamp1<0>(m, a.n_rows);
+  if constexpr (NM > 1) unit_meta_clamp1<1>(m, a.n_rows);
+  if constexpr (NM > 2) unit_meta_clamp1<2>(m, a.n_rows);
+  if constexpr (NM > 3) unit_meta_clamp1<3>(m, a.n_rows);
+}
+
+// The source lanes and register numbers of a unit's elements are the same for every unit.  Hoisted out of the unit loop
+// they are 10 to 30 registers that live through all of it -- the compiler spilled them and read them back one at a
+// time -- so each use site works from copies of its inputs that the compiler cannot look through (an empty volatile
+// statement: nothing is emitted), and the two or three integer operations per element stay where the element is used.
+#define META_RECOMPUTE(vgpr, sgpr0, sgpr1) asm volatile("" : "+v"(vgpr), "+s"(sgpr0), "+s"(sgpr1))
+
+// the ids of (k, feature fj) of one index tensor for k < KMAX (k >= K repeats K - 1)
+template <int KMAX, int NM>
+__device__ __forceinline__ void unit_ids(int32_t (&out)[KMAX], const MetaList<int32_t>& l, int K, int F, int ksh, int fj, int gbase) {
+  META_RECOMPUTE(gbase, K, F);
+#pragma unroll
+  for (int k = 0; k < KMAX; ++k) {
+    const int kc = k < K ? k : K - 1;
+    const int reg = kc >> ksh;
+    out[k] = __builtin_amdgcn_ds_bpermute((gbase + (kc - (reg << ksh)) * F + fj) << 2, meta_reg<NM>(l, reg));
+  }
+}
+
+// element e (the same in every lane) of the unit's list of saved scalars
+template <int NM>
+__device__ __forceinline__ float unit_scalar(const MetaList<float>& l, int e, int gbase, int GS, int gsh) {
+  return __int_as_float(__builtin_amdgcn_ds_bpermute((gbase + (e & (GS - 1))) << 2, __float_as_int(meta_reg<NM>(l, e >> gsh))));
+}
+
+template <int KMAX, int SPL, bool ATOMIC, int NM>
 __global__ __launch_bounds__(256, (KMAX <= 10 && SPL == 1) ? 4 : 1) void coattn_bwd_kernel_t(const CoattnArgs a) {
   extern __shared__ float lds[];  // [4 waves][upw][2*Dx]
   const int ci = (int)blockIdx.x >= a.c[1].first_block ? 1 : 0;
   const CoattnCall& cc = a.c[ci];
   const int GS = cc.GS, nslots = cc.nslots, F = cc.F, K = a.K, D4 = a.D4, n_units = a.n_units;
   const int mode = a.mode;
-  const bool all_rows = a.all_rows != 0;
+  const bool all_rows = a.all_rows != 0, ahead = a.meta_ahead != 0;
   const int lane = threadIdx.x & 63;
   const int wib = threadIdx.x >> 6;
   const int upw = 64 / GS;
   const int gl = lane & (GS - 1);
   const int grp = lane / GS;
+  const int gbase = lane - gl;      // first lane of this lane's group
+  const int gsh = __builtin_ctz(GS), ksh = cc.ksh;
   const int Dx = nslots * 4;
   const int D = D4 * 4;
   const int my_blocks = (ci == 0 ? min(a.c[1].first_block, (int)gridDim.x) : (int)gridDim.x) - cc.first_block;
@@ -290,6 +401,13 @@ __global__ __launch_bounds__(256, (KMAX <= 10 && SPL == 1) ? 4 : 1) void coattn_
   }
 
   const int n_iter = (n_units + waves_total * upw - 1) / (waves_total * upw);
+  UnitMeta cur;      // the current unit's id lists and saved scalars, one element per lane
+  if constexpr (NM > 0) {
+    if (ahead) {      // the first unit's metadata (a group past the last unit reads unit 0's, like everything else)
+      const int unit = wave0 * upw + grp;
+      unit_meta_load<NM>(cur, a, cc, unit < n_units ? unit : 0, gl);
+    }
+  }
   for (int it = 0; it < n_iter; ++it) {
     const int unit = (it * waves_total + wave0) * upw + grp;
     const bool unit_ok = unit < n_units;
@@ -301,12 +419,15 @@ __global__ __launch_bounds__(256, (KMAX <= 10 && SPL == 1) ? 4 : 1) void coattn_
     float4 g1[SPL], g2[SPL];
     bool ok[SPL];
 #pragma unroll
-    for (int j = 0; j < SPL; ++j) {
-      ok[j] = unit_ok && sok[j];
-      g1[j] = g2[j] = make_float4(0.f, 0.f, 0.f, 0.f);
-      if (ok[j]) {
-        g1[j] = ld4(cc.g1 + (int64_t)u * cc.ld1 + (gl + j * GS) * 4);
-        g2[j] = ld4(cc.g2 + (int64_t)u * cc.ld2 + (gl + j * GS) * 4);
+    for (int j = 0; j < SPL; ++j) ok[j] = unit_ok && sok[j];
+    if (NM == 0 || mode == 1) {
+#pragma unroll
+      for (int j = 0; j < SPL; ++j) {
+        g1[j] = g2[j] = make_float4(0.f, 0.f, 0.f, 0.f);
+        if (ok[j]) {
+          g1[j] = ld4(cc.g1 + (int64_t)u * cc.ld1 + (gl + j * GS) * 4);
+          g2[j] = ld4(cc.g2 + (int64_t)u * cc.ld2 + (gl + j * GS) * 4);
+        }
       }
     }
     if (mode == 1) {  // RCA: d(sum_k row_k) = g for every k
@@ -326,61 +447,113 @@ __global__ __launch_bounds__(256, (KMAX <= 10 && SPL == 1) ? 4 : 1) void coattn_
       continue;
     }
 
-    // pass 1: seq1 rows -> dp_k = g1 . seq1_k.  All 2K row ids, then the K seq1 rows, are loaded unconditionally up
-    // front (clamped addresses, zeroed by selects afterwards): under `if (k < K && ok)` every k was a region of its
-    // own that waited for its id and then for its row.  The scheduling barrier behind the ids and rows_in_flight
-    // behind the rows keep it that way in the code the compiler emits: held to 128 VGPRs, it put every load next to
-    // its use -- the ids one after the other through ONE register (a wait per k) and the rows two at a time with
-    // vmcnt(0) between the pairs, five dependent round trips to the table where passes 2 and 3 make one each
-    // (profiles/coattn_bwd_active_rows.md).  The rows need no more registers in flight together than pass 2 holds
-    // anyway.  Same arithmetic in the same order.
+    // pass 1: seq1 rows -> dp_k = g1 . seq1_k.
+    // Every load is unconditional (clamped addresses, zeroed by selects afterwards): under `if (k < K && ok)` every k
+    // was a region of its own that waited for its id and then for its row.  The scheduling barriers and rows_in_flight
+    // behind the rows keep the requests together in the code the compiler emits: held to 128 VGPRs, it put every load
+    // next to its use (profiles/coattn_bwd_active_rows.md), and it would sink the next unit's requests to the bottom of
+    // the loop, where nothing hides them.
+    // NM > 0: the unit's ids and saved scalars (`cur`, one element per lane: UnitMeta) are requested at the top of its
+    // iteration, a round trip of their own; g1 / g2 go out in front of pass 1's rows and ride on their wait; then one
+    // round trip per pass: four per unit, where the NM = 0 form makes seven in the emitted code (two for the ids, the
+    // saved scalars' own, g1 / g2 in front of everything) and spills (profiles/coattn_bwd_prefetch.md).
+    // CoattnArgs.meta_ahead (debug_flags bit 16): the metadata is requested ONE UNIT AHEAD instead, right behind the
+    // pass-1 rows of the unit before -- a wave knows its next unit's number an iteration early, and its loads return
+    // in issue order, so they arrive with the wait for that unit's pass 2: three round trips per unit.  The first
+    // unit's come from a prologue in front of the loop; the request behind a wave's last unit goes to a clamped, valid
+    // unit (unit 0) and is dropped.  Not the default: 12 us of the kernel's 93 at cfg-3 are the one-element-per-lane
+    // form's, the unit ahead added 0.7 us more and 0.3 % of step rate, inside the run-to-run spread.
+    // NM = 0: all 2K row ids of every lane, then the K seq1 rows; the saved scalars between pass 1 and pass 2.
+    // Same arithmetic in the same order in both.
     int32_t r1[SPL][KMAX], rb2[SPL][KMAX];
     float dp[KMAX];
-#pragma unroll
-    for (int k = 0; k < KMAX; ++k) {
-      const int kc = k < K ? k : K - 1;
-#pragma unroll
-      for (int j = 0; j < SPL; ++j) {
-        r1[j][k] = i1[kc * F + f[j]];
-        rb2[j][k] = i2[kc * F + f[j]];
-      }
-    }
-    __builtin_amdgcn_sched_barrier(0);      // every id is requested before the first one is used
-#pragma unroll
-    for (int k = 0; k < KMAX; ++k) {
-      dp[k] = 0.f;
+    UnitMeta nxt;
+    if constexpr (NM > 0) {
+      if (!ahead) unit_meta_load<NM>(cur, a, cc, u, gl);
 #pragma unroll
       for (int j = 0; j < SPL; ++j) {
-        r1[j][k] = (uint32_t)r1[j][k] < a.n_rows ? r1[j][k] : 0;      // (the forward reported it: score_state_t.id_status)
-        rb2[j][k] = (uint32_t)rb2[j][k] < a.n_rows ? rb2[j][k] : 0;
+        const int sc = sok[j] ? gl + j * GS : 0;
+        g1[j] = ld4(cc.g1 + (int64_t)u * cc.ld1 + sc * 4);
+        g2[j] = ld4(cc.g2 + (int64_t)u * cc.ld2 + sc * 4);
+      }
+    } else {
+#pragma unroll
+      for (int k = 0; k < KMAX; ++k) {
+        const int kc = k < K ? k : K - 1;
+#pragma unroll
+        for (int j = 0; j < SPL; ++j) {
+          r1[j][k] = i1[kc * F + f[j]];
+          rb2[j][k] = i2[kc * F + f[j]];
+        }
+      }
+      __builtin_amdgcn_sched_barrier(0);      // every id is requested before the first one is used
+#pragma unroll
+      for (int k = 0; k < KMAX; ++k) {
+#pragma unroll
+        for (int j = 0; j < SPL; ++j) {
+          r1[j][k] = (uint32_t)r1[j][k] < a.n_rows ? r1[j][k] : 0;      // (the forward reported it: score_state_t.id_status)
+          rb2[j][k] = (uint32_t)rb2[j][k] < a.n_rows ? rb2[j][k] : 0;
+        }
       }
     }
+#pragma unroll
+    for (int k = 0; k < KMAX; ++k) dp[k] = 0.f;
 #pragma unroll
     for (int j = 0; j < SPL; ++j) {
+      if constexpr (NM > 0) unit_ids<KMAX, NM>(r1[j], cur.a, K, F, ksh, f[j], gbase);
       float4 v1[KMAX];
 #pragma unroll
       for (int k = 0; k < KMAX; ++k) v1[k] = ld4(table + (int64_t)r1[j][k] * D + coff[j]);
+      if constexpr (NM > 0) {
+        if (j == 0) {
+          if (ahead) {
+            const int64_t unit_n = ((int64_t)(it + 1) * waves_total + wave0) * upw + grp;
+            unit_meta_load<NM>(nxt, a, cc, unit_n < n_units ? (int)unit_n : 0, gl);
+          }
+          __builtin_amdgcn_sched_barrier(0);      // all of it is requested before the first row is used
+        }
+      }
 #pragma unroll
       for (int k = 0; k < KMAX; ++k) rows_in_flight(v1[k], v1[KMAX - 1]);
+      if constexpr (NM > 0) {
+        g1[j].x = ok[j] ? g1[j].x : 0.f; g1[j].y = ok[j] ? g1[j].y : 0.f;
+        g1[j].z = ok[j] ? g1[j].z : 0.f; g1[j].w = ok[j] ? g1[j].w : 0.f;
+        g2[j].x = ok[j] ? g2[j].x : 0.f; g2[j].y = ok[j] ? g2[j].y : 0.f;
+        g2[j].z = ok[j] ? g2[j].z : 0.f; g2[j].w = ok[j] ? g2[j].w : 0.f;
+        // (g2 is not used before pass 3: without this its load was moved down there, a round trip of its own)
+        asm volatile("" : "+v"(g2[j].x), "+v"(g2[j].y), "+v"(g2[j].z), "+v"(g2[j].w));
+      }
 #pragma unroll
       for (int k = 0; k < KMAX; ++k) {
         const bool live = ok[j] && k < K;
         v1[k].x = live ? v1[k].x : 0.f; v1[k].y = live ? v1[k].y : 0.f;
         v1[k].z = live ? v1[k].z : 0.f; v1[k].w = live ? v1[k].w : 0.f;
-        r1[j][k] = live ? r1[j][k] : 0;
-        rb2[j][k] = live ? rb2[j][k] : 0;
+        if constexpr (NM == 0) {
+          r1[j][k] = live ? r1[j][k] : 0;
+          rb2[j][k] = live ? rb2[j][k] : 0;
+        }
         dp[k] += dot4(v1[k], g1[j]);
       }
     }
     // softmax from the saved relu'd scores
     float r[KMAX], p[KMAX], gik[KMAX];
     float rmax = 0.f, gsum = 0.f;
+    int gb_s = gbase, K_s = K, GS_s = GS;
+    if constexpr (NM > 0) META_RECOMPUTE(gb_s, K_s, GS_s);
 #pragma unroll
-    for (int k = 0; k < KMAX; ++k) {      // (clamped, unconditional loads: see above)
+    for (int k = 0; k < KMAX; ++k) {      // (k >= K repeats K - 1; NM = 0: clamped, unconditional loads, see above)
       const int kc = k < K ? k : K - 1;
-      const float rv = cc.rsave[(int64_t)u * K + kc];
-      const float g2v = cc.ginfo[(int64_t)u * cc.ldi + K + kc];
-      gik[k] = cc.ginfo[(int64_t)u * cc.ldi + kc];
+      float rv, g2v;
+      if constexpr (NM > 0) {
+        const int kcs = k < K_s ? k : K_s - 1;
+        rv = unit_scalar<NM>(cur.s, kcs, gb_s, GS_s, gsh);
+        gik[k] = unit_scalar<NM>(cur.s, K_s + kcs, gb_s, GS_s, gsh);
+        g2v = unit_scalar<NM>(cur.s, 2 * K_s + kcs, gb_s, GS_s, gsh);
+      } else {
+        rv = cc.rsave[(int64_t)u * K + kc];
+        g2v = cc.ginfo[(int64_t)u * cc.ldi + K + kc];
+        gik[k] = cc.ginfo[(int64_t)u * cc.ldi + kc];
+      }
       r[k] = (k < K) ? rv : 0.f;
       rmax = fmaxf(rmax, r[k]);
       gsum += (k < K) ? g2v : 0.f;
@@ -442,10 +615,19 @@ __global__ __launch_bounds__(256, (KMAX <= 10 && SPL == 1) ? 4 : 1) void coattn_
 #pragma unroll
     for (int j = 0; j < SPL; ++j) {
       float4 xr[KMAX];
+      if constexpr (NM > 0) {      // (from the unit's list again: a shuffle, not K registers held since pass 1)
+        unit_ids<KMAX, NM>(r1[j], cur.a, K, F, ksh, f[j], gbase);
+#pragma unroll
+        for (int k = 0; k < KMAX; ++k) r1[j][k] = (ok[j] && k < K) ? r1[j][k] : 0;
+      }
 #pragma unroll
       for (int k = 0; k < KMAX; ++k) {
         const int32_t lr = act[k] ? r1[j][k] : 0;      // the row LOADED; r1 stays the row the gradient goes to
         xr[k] = ld4(table + (int64_t)lr * D + coff[j]);
+      }
+      if constexpr (NM > 0) {      // (one round trip: the first row was requested, waited for and used in front of the other K - 1)
+#pragma unroll
+        for (int k = 0; k < KMAX; ++k) rows_in_flight(xr[k], xr[KMAX - 1]);
       }
 #pragma unroll
       for (int k = 0; k < KMAX; ++k) {
@@ -461,16 +643,28 @@ __global__ __launch_bounds__(256, (KMAX <= 10 && SPL == 1) ? 4 : 1) void coattn_
     for (int j = 0; j < SPL; ++j) {
       const float4 g2k = make_float4(g2[j].x * invK, g2[j].y * invK, g2[j].z * invK, g2[j].w * invK);
       float4 y[KMAX];
+      if constexpr (NM > 0) {
+        unit_ids<KMAX, NM>(rb2[j], cur.b, K, F, ksh, f[j], gbase);
+#pragma unroll
+        for (int k = 0; k < KMAX; ++k) rb2[j][k] = (ok[j] && k < K) ? rb2[j][k] : 0;
+      }
 #pragma unroll
       for (int k = 0; k < KMAX; ++k) {
         const int32_t lr = act[k] ? rb2[j][k] : 0;
         y[k] = ld4(table + (int64_t)lr * D + coff[j]);
+      }
+      if constexpr (NM > 0) {
+#pragma unroll
+        for (int k = 0; k < KMAX; ++k) rows_in_flight(y[k], y[KMAX - 1]);
       }
 #pragma unroll
       for (int k = 0; k < KMAX; ++k) {
         dw2[j] = fma4(dz[k], y[k], dw2[j]);
         if (ATOMIC && rb2[j][k] != 0) atomic_add4(gtable + (int64_t)rb2[j][k] * D + coff[j], fma4(dz[k], w2[j], g2k));
       }
+    }
+    if constexpr (NM > 0) {
+      if (ahead) cur = nxt;
     }
   }
   if (mode == 1) return;
@@ -508,8 +702,34 @@ __global__ __launch_bounds__(256, (KMAX <= 10 && SPL == 1) ? 4 : 1) void coattn_
       else { hipLaunchKernelGGL((KERNEL<20, 4 EXTRA>), __VA_ARGS__); }                    \
     }                                                                                     \
   } while (0)
-#define COMMA_TRUE , true
-#define COMMA_FALSE , false
+#define COMMA_TRUE0 , true, 0
+#define COMMA_FALSE0 , false, 0
+// The backward's instances that hold a unit's metadata one element per lane (SPL <= 2), by the registers per list:
+// one where a whole list fits the group (cfg-3: 40 ids and 30 scalars in 64 lanes), two or four otherwise; K <= 10 only.
+// Returns false where no instance holds `need` registers: the caller takes the NM = 0 instance.
+template <int KMAX, int SPL, bool ATOMIC, int NM>
+static void coattn_bwd_launch(int total, size_t lds_bytes, hipStream_t s, const CoattnArgs& a) {
+  hipLaunchKernelGGL((coattn_bwd_kernel_t<KMAX, SPL, ATOMIC, NM>), dim3(total), dim3(256), lds_bytes, s, a);
+}
+template <int SPL, bool ATOMIC>
+static bool coattn_bwd_ahead(int need, int total, size_t lds_bytes, hipStream_t s, const CoattnArgs& a) {
+  const int K = a.K;
+  if (need < 1 || need > 4) return false;
+  if (K <= 4) {
+    if (need > 2) return false;
+    if (need == 1) coattn_bwd_launch<4, SPL, ATOMIC, 1>(total, lds_bytes, s, a);
+    else coattn_bwd_launch<4, SPL, ATOMIC, 2>(total, lds_bytes, s, a);
+  } else if (K <= 10) {
+    if (need == 1) coattn_bwd_launch<10, SPL, ATOMIC, 1>(total, lds_bytes, s, a);
+    else if (need == 2) coattn_bwd_launch<10, SPL, ATOMIC, 2>(total, lds_bytes, s, a);
+    else coattn_bwd_launch<10, SPL, ATOMIC, 4>(total, lds_bytes, s, a);
+  } else {
+    // K > 10: the 256-register instances neither spill nor wait on scratch in the NM = 0 form, and at cfg-5 (K = 20,
+    // 3.2 ms of row requests per launch) the shuffles cost more than the waits they save: 3.17 -> 3.50 ms measured
+    return false;
+  }
+  return true;
+}
 
 static int coattn_check(const void* table, int64_t n_rows, int D, int F, int K, int B, int T) {
   if (!table || n_rows <= 0 || B <= 0 || T <= 0) return SCORE_E_BADARG;
@@ -568,8 +788,21 @@ int score_coattn_bwd_multi(CoattnArgs& a, int ncalls, int D, int B, float* const
   }
   if (a.mode == 0 && used > scratch_floats) return SCORE_E_WORKSPACE;
   if (spl == 3) spl = 4;
-  if (atomic_scatter) COATTN_DISPATCH(coattn_bwd_kernel_t, COMMA_TRUE, spl, a.K, dim3(total), dim3(256), lds_bytes, s, a);
-  else COATTN_DISPATCH(coattn_bwd_kernel_t, COMMA_FALSE, spl, a.K, dim3(total), dim3(256), lds_bytes, s, a);
+  // one element per lane and a unit ahead where the lists of both calls fit an instance's registers
+  int need = (a.mode == 0 && spl <= 2) ? 1 : 0;
+  for (int c = 0; c < ncalls && need > 0; ++c) {
+    const int n = coattn_meta_regs(a.c[c].GS, a.c[c].F, a.K);
+    need = n == 0 ? 0 : n > need ? n : need;
+  }
+  for (int c = 0; c < 2; ++c) a.c[c].ksh = need > 0 ? coattn_ksh(a.c[c].GS, a.c[c].F) : 0;
+  bool ahead;
+  if (spl == 1) ahead = atomic_scatter ? coattn_bwd_ahead<1, true>(need, total, lds_bytes, s, a) : coattn_bwd_ahead<1, false>(need, total, lds_bytes, s, a);
+  else if (spl == 2) ahead = atomic_scatter ? coattn_bwd_ahead<2, true>(need, total, lds_bytes, s, a) : coattn_bwd_ahead<2, false>(need, total, lds_bytes, s, a);
+  else ahead = false;
+  if (!ahead) {
+    if (atomic_scatter) COATTN_DISPATCH(coattn_bwd_kernel_t, COMMA_TRUE0, spl, a.K, dim3(total), dim3(256), lds_bytes, s, a);
+    else COATTN_DISPATCH(coattn_bwd_kernel_t, COMMA_FALSE0, spl, a.K, dim3(total), dim3(256), lds_bytes, s, a);
+  }
   SCORE_CHECK_LAUNCH();
   if (a.mode == 0) {
     for (int c = 0; c < ncalls; ++c) {

@@ -632,13 +632,14 @@ static int side_stream(const score_state_t* st, SideStream** out) {
 enum {
   DF_GRU_STEPWISE = 1, DF_HEAD_FUSED_ANY_B = 2, DF_GRU_F32_REC = 4, DF_NO_PANEL = 8, DF_PANEL_DX = 16, DF_SORT_LIB = 32,
   DF_HEAD_UNFUSED = 64, DF_ATTN_UNFUSED = 128, DF_SORT_OWN = 256, DF_NO_PS = 512, DF_PS_FWD_ONLY = 1024, DF_PS_BWD_ONLY = 2048,
-  DF_ONE_STREAM = 4096, DF_G4R_COMPOSED = 8192, DF_PRODUCTS_LATE = 16384, DF_COATTN_ALL_ROWS = 32768
+  DF_ONE_STREAM = 4096, DF_G4R_COMPOSED = 8192, DF_PRODUCTS_LATE = 16384, DF_COATTN_ALL_ROWS = 32768,
+  DF_COATTN_META_AHEAD = 65536
 };
 // (DF_G4R_COMPOSED / Flags.g4r_composed, bit 13, reads "one recurrence per launch": GRU4Rec's composed form, and DEEMS's two
 //  recurrences as one launch per side instead of one grouped launch)
 struct Flags {
   bool gru_stepwise, head_fused_any_b, gru_f32_rec, no_panel, panel_dx, sort_lib, head_unfused, attn_unfused, sort_own, no_ps,
-      ps_fwd_only, ps_bwd_only, one_stream, g4r_composed, products_late, coattn_all_rows;
+      ps_fwd_only, ps_bwd_only, one_stream, g4r_composed, products_late, coattn_all_rows, coattn_meta_ahead;
 };
 static inline Flags flags_of(const score_state_t* st) {
   auto on = [st](int bit) { return (st->debug_flags & bit) != 0; };
@@ -648,6 +649,7 @@ static inline Flags flags_of(const score_state_t* st) {
   o.head_unfused = on(DF_HEAD_UNFUSED); o.attn_unfused = on(DF_ATTN_UNFUSED); o.no_ps = on(DF_NO_PS);
   o.ps_fwd_only = on(DF_PS_FWD_ONLY); o.ps_bwd_only = on(DF_PS_BWD_ONLY); o.one_stream = on(DF_ONE_STREAM);
   o.g4r_composed = on(DF_G4R_COMPOSED); o.products_late = on(DF_PRODUCTS_LATE); o.coattn_all_rows = on(DF_COATTN_ALL_ROWS);
+  o.coattn_meta_ahead = on(DF_COATTN_META_AHEAD);
   return o;
 }
 // Flags.one_stream (debug_flags bit 12): no second stream at all -- everything the passes would fork runs on the caller's
@@ -2293,6 +2295,7 @@ int bwd_close(const Pass& c, BwdState* b) {
     coattn_args(c, &ca, &k);
     ca.gtable = grad_table;
     ca.all_rows = c.fl.coattn_all_rows ? 1 : 0;      // (debug_flags bit 15: the rows of relu-inactive k are loaded too, A/B)
+    ca.meta_ahead = c.fl.coattn_meta_ahead ? 1 : 0;    // (debug_flags bit 16: a unit's ids and scalars requested a unit ahead, A/B)
     for (int i = 0; i < 2; ++i) {
       CoattnCall& cc = ca.c[i];
       cc.g1 = ws + w.dxside[0] + k.col1[i]; cc.g2 = ws + w.dxside[1] + k.col2[i]; cc.ginfo = ws + w.dinfo + k.info_col[i];

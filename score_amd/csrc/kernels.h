@@ -90,6 +90,7 @@ struct CoattnCall {
   float* dzsum; float* slab;
   float* pcoef; float* dzcoef;                // backward, pull mode: softmax p_i and dz_i per (unit, i)
   int F, GS, nslots, first_block;
+  int ksh;                                    // backward (set by the launcher): log2 of the neighbours per id register (embed.hip)
   int bit1, bit2;                             // bits of *CoattnArgs.id_status that name idx1 / idx2 (position in the feed tuple)
 };
 struct CoattnArgs {
@@ -101,6 +102,8 @@ struct CoattnArgs {
   // reported: bit1 / bit2 of the call OR-ed into *id_status (optional device word, score_state_t.id_status)
   uint32_t n_rows; int32_t* id_status;
   int all_rows;                               // backward, A/B (debug_flags bit 15): the rows of relu-inactive k are loaded too
+  int meta_ahead;                             // backward, A/B (debug_flags bit 16): a unit's ids and saved scalars are requested one
+                                              // unit ahead, not at the top of its own iteration
 };
 int score_coattn_fwd_multi(CoattnArgs& a, int ncalls, int D, int B, hipStream_t s);
 int score_coattn_bwd_multi(CoattnArgs& a, int ncalls, int D, int B, float* const dW[2], float* scratch,
