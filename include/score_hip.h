@@ -686,6 +686,46 @@ int score_backward(const score_config_t* cfg, const score_state_t* st, const sco
                    float keep_prob, float* grad_w, float* grad_table, void* const* stage_events,
                    void* stream);
 
+/* ---- line-form ranking pass of the point baselines (csrc/rank.hip) ---------------------------------------------------------
+ * A target line is one user and C = 1 + neg_sample_num candidate items.  The reference's loader writes the SAME user_seq,
+ * user_seq_length and target_user for all C samples of a line (point_models/data_loader.py:48-85: only target_item differs) and
+ * its evaluation loop (train_time_point_models.py:127-154) runs PointBaseModel.eval (point_model.py:101-112) on the expanded
+ * batch of B = L * C samples: C identical recurrences (or convolutions) per line.  Here the history encoder runs ONCE per line,
+ * at batch size L, and one head launch scores the L * C candidates.
+ *
+ * SCORE_MODEL_GRU4REC and SCORE_MODEL_CASER only (SCORE_E_SHAPE for every other model type): the two point baselines whose
+ * sequence part depends on the user alone and that share the bn1 / fc1 / fc2 / fc3 head (point_model.py:44-52).  bn1 is a
+ * per-column affine and fc1 is linear, so fc1's pre-activation splits by the columns of the head input:
+ *     z1[l, c] = (fc1/bias + bn1(x_line[l]) . W1[line rows])  +  bn1(target_item[l, c]) . W1[item rows]
+ * with x_line = [h | target_user] (Caser: [h, 0, 0, 0 | v2 | target_user]).  The first term is computed once per line, the second
+ * per candidate, straight from the table rows.  The results are those of score_forward at keep_prob = 1 on the expanded batch,
+ * up to the order of fc1's sum: y_pred [L * C] in the loader's order (sample l * C + c), and loss[0..3] as the workspace's
+ * loss region -- loss = log_loss + reg_lambda * l2, log_loss (the mean over the L * C samples, or over
+ * score_state_t.global_batch where that is set), l2, and the id status bits.
+ *
+ * Ids outside [0, feature_size) follow the library's rule: read as row 0, their feed-tuple bit OR-ed into
+ * score_state_t.id_status -- 0 for user_seq, 4 for target_user, 5 for cand_items -- and the loss turns NaN.
+ * Needs D % 4 == 0 as everywhere, hidden_size % 4 == 0 (GRU4Rec: the item columns of bn1 are read 16 bytes at a time) and
+ * L * ceil(C / 16) < 2^31 (SCORE_E_SHAPE beyond).  score_state_t.workspace must hold score_rank_workspace_bytes(cfg, L, C) bytes
+ * (SCORE_E_WORKSPACE): the workspace of score_workspace_layout at B = L, and behind it the lines' z1 part [L, 200], the
+ * per-sample loss terms [L * C] and a block of zero ids (the index tensors a point model does not have).  Nothing in
+ * score_state_t but table, w, workspace, context, id_status, global_batch, gemm_mode, debug_flags and loss_done_event is read. */
+typedef struct {
+  const int32_t* user_seq;     /* [L, T, Fi]                                                                              */
+  const int32_t* length;       /* [L]   user_seq_length (SCORE_MODEL_CASER: required, not read, as in score_forward)       */
+  const int32_t* target_user;  /* [L, Fu]                                                                                 */
+  const int32_t* cand_items;   /* [L, C, Fi]  a line's candidates, as target_item of the expanded batch lies in memory     */
+  const int32_t* label;        /* [L * C]                                                                                 */
+  int32_t L, C;
+  int32_t active_slices;       /* as score_batch_t.active_slices, for the L histories                                     */
+} score_rank_batch_t;
+
+/* *bytes = size of the workspace score_rank_forward needs for L lines of C candidates.  Host only.  SCORE_E_SHAPE for a model
+ * type other than GRU4Rec / Caser, SCORE_E_BADARG for L <= 0, C <= 0 or a null pointer. */
+int score_rank_workspace_bytes(const score_config_t* cfg, int32_t L, int32_t C, int64_t* bytes);
+int score_rank_forward(const score_config_t* cfg, const score_state_t* st, const score_rank_batch_t* rb,
+                       float reg_lambda, float* y_pred /* [L*C] */, float* loss /* [4] as workspace.loss */, void* stream);
+
 /* ---- one training step in one call (csrc/step.hip) -----------------------------------------------------------------------
  * The steady-state step of model.train (score.py:101-116) for a caller that runs the time-tiled table optimizer with the
  * look-ahead (score_adam_catchup_ids_through) and sorts the next batch's index plan a step ahead: exactly

@@ -36,6 +36,12 @@ class Batch(C.Structure):
                 ("B", C.c_int32), ("active_slices", C.c_int32), ("length2", c_i)]     # (length2: DELF's / DEEMS's item_seq_length; NULL otherwise)
 
 
+class RankBatch(C.Structure):
+    """score_rank_batch_t: L target lines of C candidates each (score_rank_forward)"""
+    _fields_ = [("user_seq", c_i), ("length", c_i), ("target_user", c_i), ("cand_items", c_i), ("label", c_i),
+                ("L", C.c_int32), ("C", C.c_int32), ("active_slices", C.c_int32)]
+
+
 class Workspace(C.Structure):
     _fields_ = [(n, C.c_int64) for n in
                 ("total_bytes", "xside", "atten_info", "rsave", "query", "head_inp", "att_score",
@@ -273,7 +279,11 @@ _SIGS = {
                       C.c_void_p, C.c_uint64, C.POINTER(C.c_void_p), C.c_void_p],
     "score_backward": [C.POINTER(Config), C.POINTER(State), C.POINTER(Batch), C.c_float, c_f, c_f,
                        C.POINTER(C.c_void_p), C.c_void_p],
+    "score_rank_workspace_bytes": [C.POINTER(Config), C.c_int32, C.c_int32, C.POINTER(C.c_int64)],
+    "score_rank_forward": [C.POINTER(Config), C.POINTER(State), C.POINTER(RankBatch), C.c_float, c_f, c_f, C.c_void_p],
 }
+# (score_rank_workspace_bytes returns a status; the size comes back through its last argument)
+_STATUS_RETURN = ("score_rank_workspace_bytes",)
 
 EXPORTS = tuple(_SIGS)
 _lib = None
@@ -344,7 +354,8 @@ def load():
     for name, args in _SIGS.items():
         fn = getattr(lib, name)      # AttributeError if a declared symbol is missing
         fn.argtypes = args
-        fn.restype = C.c_int64 if name.endswith("_bytes") or name.endswith("_floats") else C.c_int
+        sized = (name.endswith("_bytes") or name.endswith("_floats")) and name not in _STATUS_RETURN
+        fn.restype = C.c_int64 if sized else C.c_int
     _lib = lib
     return lib
 
@@ -396,6 +407,13 @@ def workspace_layout(cfg, B):
     ws = Workspace()
     check(lib.score_workspace_layout(C.byref(cfg), int(B), C.byref(ws)), "score_workspace_layout")
     return ws
+
+
+def rank_workspace_bytes(cfg, L, n_cand):
+    """bytes of the workspace score_rank_forward needs for L lines of n_cand candidates"""
+    n = C.c_int64(0)
+    check(load().score_rank_workspace_bytes(C.byref(cfg), int(L), int(n_cand), C.byref(n)), "score_rank_workspace_bytes")
+    return n.value
 
 
 def workspace_field(cfg, B, name):

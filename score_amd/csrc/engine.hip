@@ -1,7 +1,7 @@
 // Whole-path orchestration: parameter/workspace layout and the forward / backward
 // launch sequences of SCORE and its ablations (score.py:188-369) and of the slice baselines RRN and GCMC
 // (slice_model.py:155-203) and of the point baselines GRU4Rec, Caser, SVD++, DELF, DEEMS and SASRec (point_model.py:123-469) on
-// one stream.  Host code only; every kernel lives in embed/gemm/gru/gru_stack/head/gcmc/caser/delf/deems/svdpp/sasrec.hip.
+// one stream.  Host code only; every kernel lives in embed/gemm/gru/gru_stack/head/gcmc/caser/delf/deems/svdpp/sasrec/rank.hip.
 #include <string.h>
 #include <stdlib.h>
 #include <stdio.h>
@@ -1060,13 +1060,16 @@ static int panel_launch(const Pass& c, int which, const float* const* A, float* 
 // ---------------------------------------------------------------- the loss reduction behind a head
 // One workgroup, no reader inside the step: with score_state_t.loss_done_event it runs on the side stream, so the backward
 // pass's first launch follows the head directly
-static int loss_tail(const Pass& c, SideStream* sd, float reg_lambda) {
-  const WS& w = c.w;
+// n per-sample terms at lossb, averaged over Bg samples, into loss[0..3] (the ranking pass: its own terms and the caller's loss)
+static int loss_tail_at(const Pass& c, SideStream* sd, float reg_lambda, int n, const float* lossb, float* loss, int Bg) {
   hipStream_t ls = c.s;
   if (c.st->loss_done_event) { G(fork_side(sd, c.s)); ls = sd->st; }
-  G(score_launch_loss_final(c.B, c.ws + w.lossb, c.ws + w.loss, reg_lambda, c.ws + w.part, c.Bg, ls, c.st->id_status));
+  G(score_launch_loss_final(n, lossb, loss, reg_lambda, c.ws + c.w.part, Bg, ls, c.st->id_status));
   if (c.st->loss_done_event) HIPTRY(hipEventRecord((hipEvent_t)c.st->loss_done_event, ls));
   return 0;
+}
+static int loss_tail(const Pass& c, SideStream* sd, float reg_lambda) {
+  return loss_tail_at(c, sd, reg_lambda, c.B, c.ws + c.w.lossb, c.ws + c.w.loss, c.Bg);
 }
 
 // ---------------------------------------------------------------- embedding rows (score.py:51-66): the sorted pull-form scatter
@@ -2005,6 +2008,92 @@ extern "C" int score_forward(const score_config_t* cfg, const score_state_t* st,
     case FAM_SASREC: return fwd_sasrec(c, f);
   }
   return SCORE_E_BADARG;
+}
+
+// ---------------------------------------------------------------- the line-form ranking pass (GRU4Rec, Caser; rank.hip)
+// L target lines of C candidates (include/score_hip.h: score_rank_forward): fwd_open and the history encoder at B = L -- the
+// launches score_forward makes for a batch of L samples, up to the head --, then the line-form head and the loss reduction over
+// the L * C terms.
+namespace {
+// Behind the workspace of a batch of L samples (build_ws at B = L, untouched): the lines' part of fc1's pre-activation [L, FC1], the
+// per-sample loss terms [L * C], and zero ids for the three index tensors a point model's batch does not have and for the target
+// item of the B = L pass (int32 [L * T * max(Fu, Fi)]; the head input's item columns get row 0 there and are not read)
+struct RankWS { int64_t zline, lossb, zero_ids, n_zero_ids, total; };
+void build_rank_ws(const Dims& d, int L, int C, RankWS* r) {
+  WS w;
+  build_ws(d, L, &w);
+  Taker take = {w.total};
+  r->zline = take((int64_t)L * FC1);
+  r->lossb = take((int64_t)L * C);
+  r->n_zero_ids = (int64_t)L * d.T * (d.Fu > d.Fi ? d.Fu : d.Fi);
+  r->zero_ids = take(r->n_zero_ids);
+  r->total = take.cur;
+}
+// the model types and shapes the pass covers, and its argument checks that need no device
+int rank_dims(const score_config_t* cfg, int L, int C, Dims* d) {
+  SCORE_TRY(make_dims(cfg, d));
+  if (d->family != FAM_G4R && d->family != FAM_CASER) return SCORE_E_SHAPE;
+  if (L <= 0 || C <= 0) return SCORE_E_BADARG;
+  if (!score_rank_head_fits(L, C, d->Dhead, d->off_ti, d->Di, d->D, FC1, FC2)) return SCORE_E_SHAPE;
+  return 0;
+}
+}  // namespace
+
+extern "C" int score_rank_workspace_bytes(const score_config_t* cfg, int32_t L, int32_t C, int64_t* bytes) {
+  if (!cfg || !bytes) return SCORE_E_BADARG;
+  Dims d;
+  SCORE_TRY(rank_dims(cfg, L, C, &d));
+  RankWS r;
+  build_rank_ws(d, L, C, &r);
+  *bytes = r.total * 4;
+  return 0;
+}
+
+extern "C" int score_rank_forward(const score_config_t* cfg, const score_state_t* st, const score_rank_batch_t* rb,
+                                  float reg_lambda, float* y_pred, float* loss, void* stream) {
+  if (!cfg || !st || !rb || !y_pred || !loss) return SCORE_E_BADARG;
+  Pass c;
+  SCORE_TRY(rank_dims(cfg, rb->L, rb->C, &c.d));
+  if (!st->table || !st->w || !st->workspace) return SCORE_E_BADARG;
+  if (!rb->user_seq || !rb->length || !rb->target_user || !rb->cand_items || !rb->label) return SCORE_E_BADARG;
+  const Dims& d = c.d;
+  const int L = rb->L, C = rb->C;
+  RankWS r;
+  build_rank_ws(d, L, C, &r);
+  if (r.total * 4 > st->workspace_bytes) return SCORE_E_WORKSPACE;
+  hipStream_t s = (hipStream_t)stream;
+  int32_t* zero_ids = reinterpret_cast<int32_t*>(st->workspace + r.zero_ids);
+  HIPTRY(hipMemsetAsync(zero_ids, 0, (size_t)r.n_zero_ids * sizeof(int32_t), s));
+  // the lines as a batch of L samples: user_seq rides as user_1hop [L, T, 1, Fi], as in a point model's score_batch_t
+  score_batch_t lb;
+  memset(&lb, 0, sizeof(lb));
+  lb.user_1hop = rb->user_seq; lb.user_2hop = lb.item_1hop = lb.item_2hop = zero_ids;
+  lb.target_user = rb->target_user; lb.target_item = zero_ids; lb.label = rb->label; lb.length = rb->length;
+  lb.B = L; lb.active_slices = rb->active_slices;
+  SCORE_TRY(pass_fill(&c, st, &lb, stream));
+  FwdState f = {reg_lambda, 1.f, nullptr, nullptr, 0, nullptr, nullptr, false};
+  SCORE_TRY(fwd_open(c, &f));
+  float* ws = c.ws; const float* W = c.W; const Params& P = c.P;
+  if (d.family == FAM_G4R) {       // (fwd_g4r's launches in front of the head)
+    HIPTRY(hipStreamWaitEvent(s, f.sd->wx, 0));
+    G(g4r_grus_fwd(c));
+    G(score_launch_copy2d(L, c.H, ws + c.w.gru_final[1], c.H, ws + c.w.head_inp, d.Dhead, s));
+  } else {                         // (fwd_caser's)
+    CaserArgs a;
+    caser_args(c, nullptr, &a);
+    G(score_caser_fwd(a, s));
+  }
+  HIPTRY(hipStreamWaitEvent(s, f.sd->join, 0));       // (the target-user rows and the L2 partial sums come from the side stream)
+  RankArgs a;
+  memset(&a, 0, sizeof(a));
+  a.L = L; a.C = C; a.Dh = d.Dhead; a.off_ti = d.off_ti; a.Di = d.Di; a.D = d.D; a.N1 = FC1; a.N2 = FC2;
+  a.head = ws + c.w.head_inp; a.table = st->table; a.cand = rb->cand_items; a.label = rb->label;
+  a.gamma = W + P.bn_g; a.beta = W + P.bn_b; a.rs = c.rs;
+  a.W1 = W + P.fc_w[0]; a.b1 = W + P.fc_b[0]; a.W2 = W + P.fc_w[1]; a.b2 = W + P.fc_b[1]; a.W3 = W + P.fc_w[2]; a.b3 = W + P.fc_b[2];
+  a.zline = ws + r.zline; a.y = y_pred; a.lossb = ws + r.lossb;
+  a.n_rows = c.n_rows; a.id_status = st->id_status;
+  G(score_rank_head(a, s));
+  return loss_tail_at(c, f.sd, reg_lambda, L * C, ws + r.lossb, loss, global_batch(st, L * C));
 }
 
 // ---------------------------------------------------------------- the layer-by-layer backward pass

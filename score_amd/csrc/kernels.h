@@ -316,6 +316,21 @@ struct CaserArgs {
 };
 int score_caser_fwd(const CaserArgs& a, hipStream_t s);
 int score_caser_bwd(const CaserArgs& a, hipStream_t s, hipStream_t sp);
+// rank.hip: the bn1 / fc1 / fc2 / fc3 head of the point baselines over L target lines of C candidates (score_rank_forward).
+// head: the lines' head input rows [L, Dh] -- every column but the item's [off_ti, off_ti + Di) is the line's own.  Two launches:
+// zline[l, :N1] = b1 + bn1(head[l]) . W1 over the line's columns (a workgroup per line), then a workgroup per (line, 16
+// candidates): the candidates' table rows -> bn1 -> LDS, relu(zline[l] + x . W1[item rows]), fc2, fc3, sigmoid;
+// y / lossb [L * C] at l * C + c.  Ids >= n_rows are read as row 0 and reported as bit 5 of *id_status.
+struct RankArgs {
+  int L, C, Dh, off_ti, Di, D, N1, N2;
+  const float* head; const float* table; const int32_t* cand; const int32_t* label;
+  const float* gamma; const float* beta; float rs;
+  const float* W1; const float* b1; const float* W2; const float* b2; const float* W3; const float* b3;
+  float* zline; float* y; float* lossb;
+  uint32_t n_rows; int32_t* id_status;
+};
+bool score_rank_head_fits(int L, int C, int Dh, int off_ti, int Di, int D, int N1, int N2);
+int score_rank_head(const RankArgs& a, hipStream_t s);
 // delf.hip: the DELF point baseline (point_model.py:200-249) between the gather and the scatter.  Per side (0: user_seq rows
 // against target_item through dense; 1: item_seq rows against target_user through dense_1) X [B * T, C] with row stride ldx,
 // the saved keys [B * T, C] (live rows only), attention weights att [B, T], rep [B, C]; backward: ds [B, T] (gradient at the

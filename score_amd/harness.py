@@ -314,15 +314,22 @@ def auc_logloss_device(preds, labels):
     return auc, ll
 
 
-def evaluate_device(model, batches, reg_lambda, neg_sample_num=TEST_NEG_SAMPLE_NUM):
+def evaluate_device(model, batches, reg_lambda, neg_sample_num=TEST_NEG_SAMPLE_NUM, shared_history=False):
     """evaluate() with predictions, ids and labels kept on the device: one forward per batch
     (model.eval_async), ranking metrics by score_ranking_quality, AUC / log-loss by score_auc_logloss; two
-    small read-backs at the end.  Returns the same 9-tuple as evaluate()."""
+    small read-backs at the end.  Returns the same 9-tuple as evaluate().
+
+    shared_history=True (GRU4Rec, Caser): every batch goes through model.rank_async instead -- the history of a target line's
+    1 + neg_sample_num samples is encoded once, not once per candidate (the loaders write the same history for all of them).
+    Predictions differ from eval_async's by the order of fc1's sum only; everything else here is unchanged."""
     import torch
     preds, labels, iids, losses = [], [], [], []
     for batch_data in batches:
         db = model.device_batch(batch_data)
-        pred, label, loss = model.eval_async(db, reg_lambda)
+        if shared_history:
+            pred, label, loss = model.rank_async(db, reg_lambda, neg_sample_num=neg_sample_num)
+        else:
+            pred, label, loss = model.eval_async(db, reg_lambda)
         preds.append(pred.clone()); labels.append(label); losses.append(loss.clone())
         iids.append(db.tensors[5][:, 0])
     preds, labels, iids = torch.cat(preds), torch.cat(labels), torch.cat(iids)

@@ -22,6 +22,7 @@ import numpy as np
 import torch
 
 from . import _lib
+from .harness import TEST_NEG_SAMPLE_NUM
 
 ADAM_B1, ADAM_B2, ADAM_EPS = 0.9, 0.999, 1e-8      # tf.train.AdamOptimizer defaults
 BATCH_FIELDS = ("user_1hop", "user_2hop", "item_1hop", "item_2hop",
@@ -230,6 +231,14 @@ def active_slices(model, max_len, min_len=None):
     return 0 if a >= T else a
 
 
+def rank_lines(B, neg_sample_num):
+    """(L, C) of a batch of B samples made of target lines of C = 1 + neg_sample_num candidates each"""
+    n_cand = 1 + int(neg_sample_num)
+    if n_cand < 1 or int(B) <= 0 or int(B) % n_cand:
+        raise ValueError("a batch of %d samples is not made of lines of 1 + neg_sample_num = %d candidates" % (int(B), n_cand))
+    return int(B) // n_cand, n_cand
+
+
 class SCOREBASE(object):
     model_type = None
     feed_spec = SLICE_FEED
@@ -319,6 +328,7 @@ class SCOREBASE(object):
         self.w = torch.zeros((self.n_w,), **f32)
         self._alloc_optimizer()
         self._ws = {}              # (B, slot) -> (layout, buffer), least recently used first
+        self._rank_ws = {}         # (L, C) -> (workspace, y_pred, loss) of the line-form ranking pass, likewise
         self.max_workspaces = 8
         ctx = C.c_void_p(0)
         _lib.check(self.lib.score_context_create(C.byref(ctx)), "score_context_create")
@@ -1815,6 +1825,78 @@ class SCOREBASE(object):
             self.check_ids()
         return pred.reshape([-1, ]).tolist(), label.reshape([-1, ]).tolist(), loss
 
+    # ------------------------------------------------------------------ ranking a target line's candidates (score_rank_forward)
+    # why a model type has no line-form pass (None: it has one -- GRU4Rec and Caser)
+    rank_unsupported = ("its recurrences and attention read per-sample neighbour sets of the target user AND the target item, so "
+                        "nothing of a sample is shared along a target line")
+
+    def _rank_buffers(self, L, n_cand):
+        """(workspace, y_pred [L * n_cand], loss [4]) of the line-form pass, one set per (L, n_cand); the last few are kept"""
+        key = (L, n_cand)
+        ent = self._rank_ws.pop(key, None)
+        if ent is None:
+            nbytes = _lib.rank_workspace_bytes(self.cfg, L, n_cand)
+            while len(self._rank_ws) >= self.max_workspaces:       # (as _workspace: kernels on other streams may still use it)
+                torch.cuda.synchronize(self.device)
+                self._rank_ws.pop(next(iter(self._rank_ws)))
+            f32 = dict(dtype=torch.float32, device=self.device)
+            ent = (torch.empty(((nbytes + 3) // 4,), **f32), torch.empty((L * n_cand,), **f32), torch.empty((4,), **f32))
+        self._rank_ws[key] = ent
+        return ent
+
+    def rank_async(self, batch_data, reg_lambda, neg_sample_num=TEST_NEG_SAMPLE_NUM, verify=False):
+        """eval_async for batches made of target LINES: every run of C = 1 + neg_sample_num samples shares its user_seq,
+        user_seq_length and target_user and differs in target_item only -- what DataLoaderUserSeq writes
+        (point_models/data_loader.py:48-85).  The history encoder runs once per line (batch size L = B / C) and one head launch
+        scores the B candidates (include/score_hip.h: score_rank_forward).  batch_data is what eval takes; the line form is taken
+        from it on the device: every C-th history, length and target-user row by one strided copy each, target_item and label
+        as they lie.  Returns what eval_async returns -- (y_pred [B] device tensor: copy it before the next rank call, labels
+        [B], loss 0-d) -- equal to eval_async's up to the order of fc1's sum.
+
+        verify=True checks on the device (one read-back) that the three per-line tensors are constant within every line and
+        raises ValueError naming the first that is not; the default trusts the loaders, which guarantee it: a batch that breaks
+        the rule is scored with each line's FIRST history."""
+        if self.rank_unsupported is not None:
+            raise NotImplementedError("%s has no line-form ranking pass: %s" % (type(self).__name__, self.rank_unsupported))
+        db = self.device_batch(batch_data)
+        L, n_cand = rank_lines(db.B, neg_sample_num)
+        t = db.tensors
+        per_line = []
+        for i in (0, 7, 4):                      # user_seq (as user_1hop), user_seq_length, target_user
+            rows = t[i].view(L, n_cand, -1)
+            first = rows[:, 0].contiguous()
+            per_line.append(first)
+            if verify:
+                per_line.append((rows != first[:, None]).any())
+        if verify:
+            bad = torch.stack(per_line[1::2]).tolist()
+            per_line = per_line[0::2]
+            sl = self.feed_spec.slots
+            for i, b in zip((0, 7, 4), bad):
+                if b:
+                    raise ValueError("batch_data[%d] (%s) is not constant within every line of %d samples" % (sl[i][0], sl[i][1], n_cand))
+        useq, length, tuser = per_line
+        ws, y, loss = self._rank_buffers(L, n_cand)
+        rb = _lib.RankBatch(_ptr(useq), _ptr(length), _ptr(tuser), _ptr(t[5]), _ptr(t[6]), L, n_cand, db.active_slices)
+        with self._Pin(self):
+            st = self._state(ws)
+            if self._tiled_on():
+                self._catchup(db, False)
+            else:
+                self._flush_adam()
+            rc = self.lib.score_rank_forward(C.byref(self.cfg), C.byref(st), C.byref(rb), float(reg_lambda), _ptr(y), _ptr(loss),
+                                             self._stream())
+        _lib.check(rc, "score_rank_forward")
+        return y, t[6], loss[0]
+
+    def rank(self, sess, batch_data, reg_lambda, neg_sample_num=TEST_NEG_SAMPLE_NUM, verify=False):
+        """eval for batches made of target lines (rank_async): (y_pred list, label list, loss)"""
+        pred, label, loss = self.rank_async(batch_data, reg_lambda, neg_sample_num=neg_sample_num, verify=verify)
+        pred, label, loss = pred.cpu().numpy(), label.cpu().numpy(), float(loss.item())
+        if loss != loss:
+            self.check_ids()
+        return pred.reshape([-1, ]).tolist(), label.reshape([-1, ]).tolist(), loss
+
     def save(self, sess, path):
         """All global variables incl. the Adam slots, under the TF variable names."""
         if self._guard_on:
@@ -1896,6 +1978,7 @@ class GRU4Rec(SCOREBASE):
     model_type = "GRU4Rec"
     feed_spec = POINT_FEED
     target_item_field = 3
+    rank_unsupported = None         # rank / rank_async: the stacked recurrences read the user's history alone (Caser: its convolutions)
 
     def __init__(self, feature_size, eb_dim, hidden_size, max_time_len, user_fnum, item_fnum, seed=1111, device=None):
         SCOREBASE.__init__(self, feature_size, eb_dim, hidden_size, max_time_len, 1, user_fnum, item_fnum, seed=seed,
@@ -1952,6 +2035,7 @@ class DELF(GRU4Rec):
     model_type = "DELF"
     feed_spec = DUAL_FEED
     target_item_field = 5
+    rank_unsupported = "its attention over the user's history is conditioned on the target item, so no part of it is shared along a line"
 
 
 class DEEMS(DELF):
@@ -1970,6 +2054,7 @@ class DEEMS(DELF):
     model_type = "DEEMS"
     zero_length_reads_all = False
     dropout_towers = 2
+    rank_unsupported = "its cost is the recurrence over each candidate's own item history, which no line shares"
 
 
 class SVDpp(GRU4Rec):
@@ -1986,6 +2071,7 @@ class SVDpp(GRU4Rec):
     variable, gradient and Adam slot has TF's name and TF's shape () (_export)."""
     model_type = "SVDpp"
     zero_length_reads_all = False
+    rank_unsupported = "its line form (the history sum once per line) is left for a follow-up"
 
     def _export(self, name, a):
         return np.asarray(a, dtype=np.float32).reshape(())      # (_import: the base class's reshape to the library's (1,))
@@ -2014,6 +2100,7 @@ class SASRec(GRU4Rec):
     model_type = "SASRec"
     reads_length = False
     CMAX = 128
+    rank_unsupported = "its line form (the attention block once per line) is left for a follow-up"
 
     def __init__(self, feature_size, eb_dim, hidden_size, max_time_len, user_fnum, item_fnum, seed=1111, device=None):
         if int(max_time_len) < 3:
