@@ -1,7 +1,9 @@
 """The per-sample whole-model kernels (csrc/persample.h: one workgroup per sample runs the whole forward / backward pass
 of score.py:188-224, the form SCORE / SCORE_USER / SCORE_ITEM take at the reference's own shapes, train_score.py:15-16,
 285-372) against the oracle and against the layer-by-layer pass they replace (score_state_t.debug_flags bit 9 forces
-that one; bits 10 / 11 mix the forms: fused forward + layered backward and the reverse)."""
+that one; bits 10 / 11 mix the forms: fused forward + layered backward and the reverse).  The shapes here are the workloads';
+tests/test_gpu_persample_edges.py (cases: tests/persample_cases.py) runs the same comparisons at the edges of what ps_plan_shape
+admits."""
 import numpy as np
 import pytest
 import torch
