@@ -25,6 +25,8 @@ import datetime
 
 import numpy as np
 
+from .placement import check_build, device_i32, device_of, is_tensor, to_host
+
 TMALL_START = datetime.date(2015, 5, 1)     # feateng_tmall.py:10
 TMALL_SLICE_DAYS = 15                       # feateng_tmall.py:11
 
@@ -50,11 +52,6 @@ def _first_appearance(col):
     return rank[inv.reshape(-1)], len(uniq)
 
 
-def _check_build(build):
-    if build not in ("host", "device"):
-        raise ValueError("build is 'host' or 'device': got %r" % (build,))
-
-
 def remap_tmall_log(log, age=None, gender=None, build="host", device=None):
     """log: int array [n, >=6] with columns user_id, item_id, cat_id, seller_id, brand_id, time_stamp(MMDD)
     (tests/golden/tmall_sample_log.npz).  age / gender: per-row arrays (the joined user profile,
@@ -69,7 +66,7 @@ def remap_tmall_log(log, age=None, gender=None, build="host", device=None):
     raw MMDD column there (what PointLogStore orders histories by), and user_rows / item_rows are numpy arrays, downloaded
     once (TemporalGraph keeps its row tables on the host).  The default profile is computed from the uploaded user column.
     An invalid MMDD raises ValueError, as datetime.date does on the host."""
-    _check_build(build)
+    check_build(build)
     if build == "device":
         return _remap_tmall_device(log, age, gender, device)
     log = np.asarray(log)
@@ -100,8 +97,7 @@ def remap_tmall_log(log, age=None, gender=None, build="host", device=None):
 def _remap_tmall_device(log, age, gender, device):
     import torch
     from . import logremap as lr
-    from .targets import device_i32
-    dev = lr.device_of(device, "remap_tmall_log(build='device')")
+    dev = device_of(device, "remap_tmall_log(build='device')")
     with torch.cuda.device(dev):
         raw, wide = lr.upload_columns(log, 6, dev)                 # [6, n]: the one upload
         n = int(raw.shape[1])
@@ -144,7 +140,7 @@ def remap_taobao_log(log, start_ts, end_ts, delta=TAOBAO_SLICE_SECONDS, build="h
     categories) and kept, the log positions of the kept events.  build="device" (needs a GPU): one upload, then slices,
     compaction and remap on the device (csrc/logremap.hip); uid, iid, t_idx and kept are int32 tensors there, the row tables
     numpy."""
-    _check_build(build)
+    check_build(build)
     start_ts, end_ts, delta = int(start_ts), int(end_ts), int(delta)
     if delta <= 0 or end_ts < start_ts:
         raise ValueError("remap_taobao_log: delta must be positive and end_ts >= start_ts")
@@ -172,7 +168,7 @@ def remap_taobao_log(log, start_ts, end_ts, delta=TAOBAO_SLICE_SECONDS, build="h
 def _remap_taobao_device(log, start_ts, end_ts, delta, device):
     import torch
     from . import logremap as lr
-    dev = lr.device_of(device, "remap_taobao_log(build='device')")
+    dev = device_of(device, "remap_taobao_log(build='device')")
     if not -2 ** 31 <= start_ts <= end_ts < 2 ** 31:
         raise ValueError("the device remap takes int32 times: start_ts / end_ts lie outside")
     with torch.cuda.device(dev):
@@ -262,7 +258,7 @@ def remap_ccmr_log(log, movie_info, n_users, n_items, vocab=CCMR_VOCAB, start_da
     build="device" (needs a GPU): log and movie_info are uploaded once and everything is computed there (csrc/ccmr.hip, then
     score_log_compact for the two halves), the same integers; the per-event arrays are int32 tensors on the device, the row
     tables numpy, downloaded once together with the status words."""
-    _check_build(build)
+    check_build(build)
     U, I, vocab = int(n_users), int(n_items), tuple(int(v) for v in vocab)
     delta = int(delta_days)
     if U <= 0 or I <= 0 or len(vocab) != 4 or min(vocab) < 1 or delta <= 0:
@@ -309,7 +305,7 @@ def _remap_ccmr_device(log, movie_info, U, I, vocab, start_day, delta, size, dev
     import torch
     from . import _lib
     from . import logremap as lr
-    dev = lr.device_of(device, "remap_ccmr_log(build='device')")
+    dev = device_of(device, "remap_ccmr_log(build='device')")
     if size >= 2 ** 31:
         raise ValueError("the device remap takes int32 ids: feature_size %d lies outside" % size)
     with torch.cuda.device(dev):
@@ -510,20 +506,100 @@ def _check_remap(remap, build):
         raise ValueError("remap='device' needs build='device': its columns are born on the device and stay there")
 
 
-def _host_cols(cols):
-    """the remap's three columns as numpy, for the host target rule (a download where the remap ran on the device)"""
-    from .targets import _host
-    return tuple(_host(c) for c in cols)
+class _LogFront(object):
+    """A remap dict's per-event columns where the pipeline's stages want them, every copy made when first asked for and once:
+    host() is numpy (a download where the remap ran on the device; the dict's very arrays where it did not), device() int32
+    tensors (an upload where the remap ran on the host, RuntimeError without a GPU; the dict's very tensors where it did
+    not).  names: uid, iid, t_idx by default; time_key is the dict's where the remap returns one and column 5 of the raw log
+    for Tmall's host remap, which does not -- this is the one place that knows."""
+    LOG, LOG4 = ("uid", "iid", "t_idx"), ("uid", "iid", "time_key", "t_idx")
+
+    def __init__(self, r, targets, device=None, raw_log=None):
+        self.r, self.targets, self.device_arg, self._raw_log = r, targets, device, raw_log
+        self._host, self._dev, self._upload_to, self._neg_lists = {}, {}, None, None
+
+    def _column(self, k):
+        if k == "time_key" and k not in self.r:
+            return np.asarray(self._raw_log)[:, 5]
+        return self.r[k]
+
+    def host(self, names=LOG):
+        for k in names:
+            if k not in self._host:
+                self._host[k] = to_host(self._column(k))
+        return tuple(self._host[k] for k in names)
+
+    def device(self, names=LOG):
+        for k in names:
+            if k not in self._dev:
+                a = self._column(k)
+                if not is_tensor(a):
+                    if self._upload_to is None:
+                        self._upload_to = device_of(self.device_arg, "targets='device'", instead="targets='host' does not")
+                    a = device_i32(a, self._upload_to)
+                self._dev[k] = a
+        return tuple(self._dev[k] for k in names)
+
+    def stage(self, build, names=LOG):
+        """the columns for a stage that runs where `build` says.  A device stage shares the copy that is on the device anyway
+        -- the remap's own, or the upload the device targets make: one upload serves the graph, the lines and the histories --;
+        every other stage takes the host arrays, which a device stage uploads itself."""
+        shared = build == "device" and (self.targets == "device" or is_tensor(self.r["uid"]))
+        return self.device(names) if shared else self.host(names)
+
+    def neg_lists(self):
+        """CCMR's user_neg_dict from the remap's negative events, built where the targets are"""
+        if self._neg_lists is None:
+            from .targets import UserNegLists
+            r = self.r
+            self._neg_lists = UserNegLists.from_events(r["neg_uid"], r["neg_iid"], r["n_users"], build=self.targets,
+                                                       device=self.device_arg)
+        return self._neg_lists
 
 
-def _device_log(r, device=None):
-    """the remapped log's three columns uploaded once -> int32 tensors"""
-    import torch
-    if not torch.cuda.is_available():
-        raise RuntimeError("targets='device' needs an AMD GPU (HIP); targets='host' does not")
-    dev = torch.device(device if device is not None else "cuda:%d" % torch.cuda.current_device())
-    from .targets import device_i32
-    return tuple(device_i32(r[k], dev) for k in ("uid", "iid", "t_idx"))
+def _graph_of(front, c, seed, build, draws):
+    from .graph import TemporalGraph
+    r = front.r
+    return TemporalGraph.from_log(*front.stage(build), r["n_users"], r["n_items"], c["graph_time_slice_num"], r["user_rows"],
+                                  r["item_rows"], max_1hop=c["max_1hop"], max_2hop=c["max_2hop"], seed=seed, build=build,
+                                  draws=draws)
+
+
+def _split_lines(front, c, splits, seed_of, draws, sample_factor, neg_lists=False, store=None):
+    """{split: its target lines} over `splits` (name, key of the prediction time, key of the negatives' number in the data
+    set's constants c) IN THAT ORDER, which matters under draws="stream".  seed_of(pred_time): the split's seed.  Device
+    targets are TargetStore objects built from the front's device columns, host targets gen_target_lines of its host columns;
+    neg_lists: with the front's negative lists (CCMR).  store(name, pred_time, neg, lines): what the dict holds instead."""
+    from .targets import TargetStore
+    r, out = front.r, {}
+    for name, pt, neg in splits:
+        pt, neg = c[pt], c[neg]
+        cols = front.device() if front.targets == "device" else front.host()
+        own = front.neg_lists() if neg_lists else None
+        if front.targets == "device":
+            lines = TargetStore.from_log(*cols, r["n_users"], r["n_items"], pt, neg, c["start_time"], seed_of(pt), build="device",
+                                         sample_factor=_split_factor(sample_factor, name), neg_lists=own)
+        else:
+            lines = gen_target_lines(*cols, r["n_users"], r["n_items"], pt, neg, c["start_time"], seed_of(pt), draws=draws,
+                                     neg_lists=own)
+        out[name] = lines if store is None else store(name, pt, neg, lines)
+    return out
+
+
+def _point_store_of(front, c, batch_size, dual, build):
+    """_split_lines' store=: the PointLogStore of a split's lines.  batch_size: a dict per split or one number; default 200
+    for train and the data set's eval_batch_size for the others."""
+    from .pointdata import PointLogStore
+    r = front.r
+
+    def store(name, pt, neg, lines):
+        B = batch_size.get(name) if isinstance(batch_size, dict) else batch_size
+        if B is None:
+            B = 200 if name == "train" else c["eval_batch_size"]
+        uid, iid, time_key, t_idx = front.stage(build, front.LOG4)
+        return PointLogStore(uid, iid, time_key, t_idx, lines, c["start_time"], pt, POINT_HIST_MAX_LEN, neg, B, r["user_rows"],
+                             r["item_rows"], dual, build=build, device=front.device_arg)
+    return store
 
 
 def tmall_pipeline(log, seed=11, build="host", draws="stream", targets="host", sample_factor=None, remap="host"):
@@ -535,32 +611,11 @@ def tmall_pipeline(log, seed=11, build="host", draws="stream", targets="host", s
     sampling.py does.  remap: "host" (the default) remap_tmall_log in numpy; "device" (needs build="device") the RAW log is
     uploaded once, remapped there (csrc/logremap.hip), and the graph and the targets are built from those columns -- the dict
     then holds device tensors under uid / iid / t_idx / time_key."""
-    from .graph import TemporalGraph
     _check_targets(targets, draws, sample_factor)
     _check_remap(remap, build)
-    r = remap_tmall_log(log, build=remap)
-    c = TMALL
-    if remap == "device":
-        cols = (r["uid"], r["iid"], r["t_idx"])
-    else:
-        cols = _device_log(r) if targets == "device" and build == "device" else (r["uid"], r["iid"], r["t_idx"])
-    g = TemporalGraph.from_log(cols[0], cols[1], cols[2], r["n_users"], r["n_items"], c["graph_time_slice_num"],
-                               r["user_rows"], r["item_rows"], max_1hop=c["max_1hop"], max_2hop=c["max_2hop"], seed=seed,
-                               build=build, draws=draws)
-    if targets == "device" and build != "device":
-        cols = _device_log(r)
-    host_cols = _host_cols(cols) if remap == "device" and targets != "device" else (r["uid"], r["iid"], r["t_idx"])
-    out = {}
-    for name, pt, neg in TMALL_SPLITS:
-        pt, neg = c[pt], c[neg]
-        if targets == "device":
-            from .targets import TargetStore
-            out[name] = TargetStore.from_log(cols[0], cols[1], cols[2], r["n_users"], r["n_items"], pt, neg, c["start_time"],
-                                             seed + pt, build="device", sample_factor=_split_factor(sample_factor, name))
-        else:
-            out[name] = gen_target_lines(host_cols[0], host_cols[1], host_cols[2], r["n_users"], r["n_items"], pt, neg,
-                                         c["start_time"], seed + pt, draws=draws)
-    return g, r, out
+    front = _LogFront(remap_tmall_log(log, build=remap), targets)
+    g = _graph_of(front, TMALL, seed, build, draws)
+    return g, front.r, _split_lines(front, TMALL, TMALL_SPLITS, lambda pt: seed + pt, draws, sample_factor)
 
 
 # constants of the CCMR run: graph_storage.py:16-25 (41 graph slices, caps 10 / 100), gen_target.py:14-23,309-311 (start index 0,
@@ -568,32 +623,6 @@ def tmall_pipeline(log, seed=11, build="host", draws="stream", targets="host", s
 CCMR = dict(obj_per_time_slice=10, time_slice_num=41, graph_time_slice_num=41, start_time=0, user_fnum=1, item_fnum=5,
             pred_time_train=38, pred_time_validation=39, pred_time_test=40, eb_dim=16, hidden_size=32, eval_batch_size=100,
             train_neg=99, test_neg=99, max_1hop=10, max_2hop=100, start_date=CCMR_START_DATE, delta_days=CCMR_DELTA_DAYS)
-
-
-def _ccmr_front(log, movie_info, n_users, n_items, vocab, build, draws, targets, remap, sample_factor, device=None):
-    """the remap, its columns where the builds want them, and the negative lists -> (r, cols, host_cols, neg_lists)"""
-    from .targets import UserNegLists
-    _check_targets(targets, draws, sample_factor)
-    _check_remap(remap, build)
-    c = CCMR
-    r = remap_ccmr_log(log, movie_info, n_users, n_items, vocab, c["start_date"], c["delta_days"], build=remap, device=device)
-    if remap == "device":
-        cols = (r["uid"], r["iid"], r["t_idx"])
-    else:
-        cols = _device_log(r, device) if targets == "device" else (r["uid"], r["iid"], r["t_idx"])
-    host_cols = None if targets == "device" else _host_cols(cols)
-    neg_lists = UserNegLists.from_events(r["neg_uid"], r["neg_iid"], r["n_users"], build=targets, device=device)
-    return r, cols, host_cols, neg_lists
-
-
-def _ccmr_lines(r, cols, host_cols, neg_lists, name, pt, neg, seed, draws, targets, sample_factor):
-    c = CCMR
-    if targets == "device":
-        from .targets import TargetStore
-        return TargetStore.from_log(cols[0], cols[1], cols[2], r["n_users"], r["n_items"], pt, neg, c["start_time"], seed,
-                                    build="device", sample_factor=_split_factor(sample_factor, name), neg_lists=neg_lists)
-    return gen_target_lines(host_cols[0], host_cols[1], host_cols[2], r["n_users"], r["n_items"], pt, neg, c["start_time"], seed,
-                            draws=draws, neg_lists=neg_lists)
 
 
 # the reference's order: target_40, _39, _38 on ONE TargetGen (gen_target.py:309-311) -- it matters under draws="stream"
@@ -611,18 +640,12 @@ def ccmr_pipeline(log, movie_info, n_users, n_items, vocab=CCMR_VOCAB, seed=11, 
     reference's one TargetGen does; under draws="stream" the splits are generated in the reference's order, test first, from
     one stream per call with the pads carried along in the lists.  build / draws / targets / sample_factor / remap:
     tmall_pipeline's."""
-    from .graph import TemporalGraph
-    c = CCMR
-    r, cols, host_cols, neg_lists = _ccmr_front(log, movie_info, n_users, n_items, vocab, build, draws, targets, remap,
-                                                sample_factor)
-    gcols = cols if build == "device" or remap == "device" else (r["uid"], r["iid"], r["t_idx"])
-    g = TemporalGraph.from_log(gcols[0], gcols[1], gcols[2], r["n_users"], r["n_items"], c["graph_time_slice_num"],
-                               r["user_rows"], r["item_rows"], max_1hop=c["max_1hop"], max_2hop=c["max_2hop"], seed=seed,
-                               build=build, draws=draws)
-    out = {}
-    for name, pt, neg in CCMR_SPLITS:
-        out[name] = _ccmr_lines(r, cols, host_cols, neg_lists, name, c[pt], c[neg], seed, draws, targets, sample_factor)
-    return g, r, out
+    _check_targets(targets, draws, sample_factor)
+    _check_remap(remap, build)
+    front = _LogFront(remap_ccmr_log(log, movie_info, n_users, n_items, vocab, CCMR["start_date"], CCMR["delta_days"], build=remap),
+                      targets)
+    g = _graph_of(front, CCMR, seed, build, draws)
+    return g, front.r, _split_lines(front, CCMR, CCMR_SPLITS, lambda pt: seed, draws, sample_factor, neg_lists=True)
 
 
 def ccmr_point_stores(log, movie_info, n_users, n_items, vocab=CCMR_VOCAB, seed=11, dual=True, batch_size=None, build="device",
@@ -632,25 +655,12 @@ def ccmr_point_stores(log, movie_info, n_users, n_items, vocab=CCMR_VOCAB, seed=
     stable in log order -- gen_user_item_hist_dict_ccmr's stable sorted on time_int (gen_target.py:149-152) --, which is what
     PointLogStore does with the remap's time_key, and cut at the reference's 300.  batch_size: a dict per split or one number;
     default 200 for train and CCMR's eval_batch_size for the others (multiples of 1 + 99)."""
-    from .pointdata import PointLogStore
-    c = CCMR
-    r, cols, host_cols, neg_lists = _ccmr_front(log, movie_info, n_users, n_items, vocab, build, draws, targets, remap,
-                                                sample_factor, device)
-    if remap == "device" or (targets == "device" and build == "device"):
-        from .targets import device_i32
-        log4 = (cols[0], cols[1], device_i32(r["time_key"], cols[0].device), cols[2])
-    else:
-        log4 = (r["uid"], r["iid"], r["time_key"], r["t_idx"])
-    stores = {}
-    for name, pt, neg in CCMR_SPLITS:
-        pt, neg = c[pt], c[neg]
-        lines = _ccmr_lines(r, cols, host_cols, neg_lists, name, pt, neg, seed, draws, targets, sample_factor)
-        B = batch_size.get(name) if isinstance(batch_size, dict) else batch_size
-        if B is None:
-            B = 200 if name == "train" else c["eval_batch_size"]
-        stores[name] = PointLogStore(log4[0], log4[1], log4[2], log4[3], lines, c["start_time"], pt, POINT_HIST_MAX_LEN, neg, B,
-                                     r["user_rows"], r["item_rows"], dual, build=build, device=device)
-    return stores, r
+    _check_targets(targets, draws, sample_factor)
+    _check_remap(remap, build)
+    front = _LogFront(remap_ccmr_log(log, movie_info, n_users, n_items, vocab, CCMR["start_date"], CCMR["delta_days"], build=remap,
+                                     device=device), targets, device)
+    return _split_lines(front, CCMR, CCMR_SPLITS, lambda pt: seed, draws, sample_factor, neg_lists=True,
+                        store=_point_store_of(front, CCMR, batch_size, dual, build)), front.r
 
 
 # ---- the point baselines' history files (gen_target.py:223-275, gen_history_point.py:22-65) ------------------------------------
@@ -727,35 +737,8 @@ def tmall_point_stores(log, seed=11, dual=True, batch_size=None, build="device",
     sample_factor: tmall_pipeline's -- with targets="device" the lines are built on the device and handed over as tensors.
     remap: tmall_pipeline's -- with remap="device" (needs build="device") the raw log is uploaded once and the remap's device
     columns, time_key among them, serve the lines and the histories."""
-    from .pointdata import PointLogStore
     _check_targets(targets, draws, sample_factor)
     _check_remap(remap, build)
-    r = remap_tmall_log(log, build=remap, device=device)
-    c = TMALL
-    if remap == "device":
-        cols = (r["uid"], r["iid"], r["t_idx"])
-        log4 = (cols[0], cols[1], r["time_key"], cols[2])
-        host_cols = _host_cols(cols) if targets != "device" else None
-    else:
-        cols = _device_log(r, device) if targets == "device" else None
-        log4 = (r["uid"], r["iid"], np.asarray(log)[:, 5], r["t_idx"])
-        host_cols = log4[0], log4[1], log4[3]
-        if targets == "device" and build == "device":              # the uploaded log serves the histories too
-            from .targets import device_i32
-            log4 = (cols[0], cols[1], device_i32(log4[2], cols[0].device), cols[2])
-    stores = {}
-    for name, pt, neg in TMALL_SPLITS:
-        pt, neg = c[pt], c[neg]
-        if targets == "device":
-            from .targets import TargetStore
-            lines = TargetStore.from_log(cols[0], cols[1], cols[2], r["n_users"], r["n_items"], pt, neg, c["start_time"],
-                                         seed + pt, build="device", sample_factor=_split_factor(sample_factor, name))
-        else:
-            lines = gen_target_lines(host_cols[0], host_cols[1], host_cols[2], r["n_users"], r["n_items"], pt, neg,
-                                     c["start_time"], seed + pt, draws=draws)
-        B = batch_size.get(name) if isinstance(batch_size, dict) else batch_size
-        if B is None:
-            B = 200 if name == "train" else c["eval_batch_size"]
-        stores[name] = PointLogStore(log4[0], log4[1], log4[2], log4[3], lines, c["start_time"], pt,
-                                     POINT_HIST_MAX_LEN, neg, B, r["user_rows"], r["item_rows"], dual, build=build, device=device)
-    return stores, r
+    front = _LogFront(remap_tmall_log(log, build=remap, device=device), targets, device, raw_log=log)
+    return _split_lines(front, TMALL, TMALL_SPLITS, lambda pt: seed + pt, draws, sample_factor,
+                        store=_point_store_of(front, TMALL, batch_size, dual, build)), front.r

@@ -14,6 +14,7 @@ import torch
 
 from . import _lib
 from .model import DeviceBatch, _ptr, carve_batch, flat_batch_size
+from .placement import NO_CPU_PATH, check_build, device_i32, device_of, upload_named
 
 
 def _csr(lists_per_cell):
@@ -128,8 +129,10 @@ class TemporalGraph(object):
         build: "host" numpy; "device" (needs draws="cell" and a GPU) csrc/graphbuild.hip: the same arrays, word for word,
           built in HBM from the uploaded log -- the graph is born resident (to_device uploads nothing) and downloads its
           arrays the first time cell(), save() or the degree lists are asked for."""
-        if build not in ("host", "device") or draws not in ("stream", "cell"):
-            raise ValueError("build is 'host' or 'device', draws 'stream' or 'cell': got %r, %r" % (build, draws))
+        bad = "build is 'host' or 'device', draws 'stream' or 'cell': got %r, %r" % (build, draws)
+        check_build(build, bad)
+        if draws not in ("stream", "cell"):
+            raise ValueError(bad)
         if build == "device":
             if draws != "cell":
                 raise ValueError("build='device' needs draws='cell': the sequential stream of draws='stream' has no device form")
@@ -291,14 +294,11 @@ class TemporalGraph(object):
                          seed, device=None, timings=None):
         """from_log(build="device"): score_graph_build_1hop, then per side score_graph_build_2hop twice (count, fill), items
         first.  timings: a dict that receives the seconds of the three stages (synchronised; tools/graph_build_time.py)."""
-        if not torch.cuda.is_available():
-            raise RuntimeError("TemporalGraph.from_log(build='device') needs an AMD GPU (HIP); build='host' does not")
+        dev = device_of(device, "TemporalGraph.from_log(build='device')")
         import time
-        dev = torch.device(device if device is not None else "cuda:%d" % torch.cuda.current_device())
         lib = _lib.load()
         S, U, I = int(time_slice_num), int(n_users), int(n_items)
         # (a log already uploaded -- int32 tensors -- is used where it is: one upload serves the graph and the target lines)
-        from .targets import device_i32
         up = lambda a: device_i32(a, dev)
         with torch.cuda.device(dev):
             d_uid, d_iid, d_t = up(uid), up(iid), up(t_idx)
@@ -429,24 +429,17 @@ class TemporalGraph(object):
             raise ValueError("WRONG GRAPH_HANDLER MODE: {}".format(mode))          # graph_loader.py:248
         if mode == "is" and self._built is None and (self.user_degrees is None or self.item_degrees is None):
             raise ValueError("mode 'is' needs the 2-hop degree lists")
-        if not torch.cuda.is_available():
-            raise RuntimeError("TemporalGraph.to_device needs an AMD GPU (HIP); batch assembly has no CPU path")
-        dev = torch.device(device if device is not None else "cuda:%d" % torch.cuda.current_device())
-        t = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)
+        dev = device_of(device, "TemporalGraph.to_device", instead=NO_CPU_PATH)
         if self._built is not None and dev == self._built_device:
             # built on this device (from_log(build="device")): the arrays are there already, the degree lists included
             d = {k: v for k, v in self._built.items() if mode == "is" or not k.endswith("_deg2")}
         else:
-            d = {"u_" + k: t(v) for k, v in self.user_csr.items()}
-            d.update({"i_" + k: t(v) for k, v in self.item_csr.items()})
-            # an empty neighbour array still needs a valid pointer
-            for k in list(d):
-                if d[k].numel() == 0:
-                    d[k] = torch.zeros((1,), dtype=d[k].dtype, device=dev)
-            d["user_rows"], d["item_rows"] = t(self.user_rows), t(self.item_rows)
+            host = {"user_rows": self.user_rows, "item_rows": self.item_rows}
+            host.update({"u_" + k: v for k, v in self.user_csr.items()})
+            host.update({"i_" + k: v for k, v in self.item_csr.items()})
             if mode == "is":
-                for k, a in (("u_deg2", self.user_degrees), ("i_deg2", self.item_degrees)):
-                    d[k] = t(np.asarray(a, dtype=np.int32)) if len(a) else torch.zeros((1,), dtype=torch.int32, device=dev)
+                host.update(u_deg2=np.asarray(self.user_degrees, dtype=np.int32), i_deg2=np.asarray(self.item_degrees, dtype=np.int32))
+            d = upload_named(host, host.get, dev)
         self._dev = d
         self.device = dev
         self.mode = mode

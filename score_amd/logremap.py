@@ -7,13 +7,7 @@ import ctypes as C
 
 import numpy as np
 
-
-def device_of(device=None, what="build='device'"):
-    """the torch device of a device build; RuntimeError without a GPU"""
-    import torch
-    if not torch.cuda.is_available():
-        raise RuntimeError("%s needs an AMD GPU (HIP); build='host' does not" % what)
-    return torch.device(device if device is not None else "cuda:%d" % torch.cuda.current_device())
+from .placement import device_of                                   # (tools take it from here)
 
 
 def upload_columns(log, n_cols, dev):

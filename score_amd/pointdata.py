@@ -36,6 +36,8 @@ import pickle
 
 import numpy as np
 
+from .placement import NO_CPU_PATH, check_build, device_as, device_i32, device_of, is_tensor, to_host, upload_named
+
 
 class DataLoaderUserSeq(object):
     def __init__(self, batch_size, max_len, target_file, user_seq_file, neg_sample_num, user_feat_dict_file,
@@ -281,18 +283,11 @@ class PointSeqStore(object):
 
     def to_device(self, device=None):
         import ctypes as C
-        import torch
         from . import _lib
-        if not torch.cuda.is_available():
-            raise RuntimeError("PointSeqStore.to_device needs an AMD GPU (HIP); batch assembly has no CPU path")
-        dev = torch.device(device if device is not None else "cuda:%d" % torch.cuda.current_device())
+        dev = device_of(device, "PointSeqStore.to_device", instead=NO_CPU_PATH)
         names = ("user_off", "user_seq", "user_len", "item_off", "item_seq", "item_len", "target_user", "target_item",
                  "user_rows", "item_rows")
-        d = {}
-        for k in names:
-            a = getattr(self, k)
-            if a is not None:       # (an empty array still needs a valid pointer)
-                d[k] = torch.from_numpy(np.ascontiguousarray(a)).to(dev) if a.size else torch.zeros((1,), dtype=torch.int32, device=dev)
+        d = upload_named(names, lambda k: getattr(self, k), dev)
         ptr = lambda k: C.c_void_p(d[k].data_ptr()) if k in d else C.c_void_p(0)
         self._dev, self.device = d, dev
         self.struct = _lib.PointStore(C.sizeof(_lib.PointStore), *[ptr(k) for k in names], self.n_lines,
@@ -357,8 +352,7 @@ class PointLogStore(object):
             raise ValueError("batch size should be a multiple of %d (1 + neg_sample_num)" % per_line)
         if self.hist_max_len <= 0:
             raise ValueError("hist_max_len must be positive")
-        if build not in ("device", "host"):
-            raise ValueError("build must be 'device' or 'host'")
+        check_build(build, "build must be 'device' or 'host'")
         self.lines_per_batch = self.batch_size // per_line
         self.dual, self.build = bool(dual), build
         self.start_time, self.pred_time = int(start_time), int(pred_time)
@@ -371,8 +365,7 @@ class PointLogStore(object):
         if not (np.array_equal(self.user_rows[:, 0], np.arange(1, U + 1)) and
                 np.array_equal(self.item_rows[:, 0], np.arange(U + 1, U + I + 1))):
             raise ValueError("column 0 of user_rows / item_rows must be the ids 1 .. U / U + 1 .. U + I")
-        from .targets import _host, _is_tensor, device_i32
-        if all(_is_tensor(a) and a.is_cuda for a in (uid, iid, time_key, t_idx)):
+        if all(is_tensor(a) and a.is_cuda for a in (uid, iid, time_key, t_idx)):
             # the log as int32 tensors already on the device (one upload serves the graph, the targets and the histories):
             # the range checks read six extremes back
             import torch
@@ -384,7 +377,7 @@ class PointLogStore(object):
             sizes = [int(c.numel()) for c in cols]
             ext = torch.stack([f(c) for c in cols[:3] for f in (torch.amin, torch.amax)]).cpu().tolist() if min(sizes) else None
         else:
-            cols = [np.ascontiguousarray(np.asarray(_host(a)).reshape(-1)) for a in (uid, iid, time_key, t_idx)]
+            cols = [np.ascontiguousarray(np.asarray(to_host(a)).reshape(-1)) for a in (uid, iid, time_key, t_idx)]
             sizes = [len(c) for c in cols]
             ext = [int(f()) for c in cols[:3] for f in (c.min, c.max)] if min(sizes) else None
         if ext is None or any(n != sizes[0] for n in sizes) or sizes[0] >= 2 ** 31:
@@ -500,11 +493,9 @@ class PointLogStore(object):
         import ctypes as C
         import torch
         from . import _lib
-        if not torch.cuda.is_available():
-            raise RuntimeError("PointLogStore(build='device') needs an AMD GPU (HIP); build='host' does not")
-        dev = torch.device(device if device is not None else "cuda:%d" % torch.cuda.current_device())
+        dev = device_of(device, "PointLogStore(build='device')")
         lib = _lib.load()
-        uid, iid, time_key, t_idx = [c.to(dev) if torch.is_tensor(c) else torch.from_numpy(c).to(dev) for c in self._log]
+        uid, iid, time_key, t_idx = [device_i32(c, dev) for c in self._log]
         n, U, I = int(uid.numel()), self.n_users, self.n_items
         temp, temp_bytes = _lib.workspace("score_point_hist", dev, n)
         stream = _lib.current_stream(dev)
@@ -526,7 +517,7 @@ class PointLogStore(object):
             setattr(self, k, v)
         if self.n_batches:       # the one read-back of the build
             parts = self._extremes(self.user_hist_len, self.item_hist_len,
-                                   lambda a, i: a[i.to(dev) if torch.is_tensor(i) else torch.from_numpy(i).to(dev)],
+                                   lambda a, i: a[device_as(i, dev)],
                                    torch.maximum, torch.minimum, lambda a: a.amax(dim=1), lambda a: a.amin(dim=1))
             if self._first_bad_line is not None:                   # (a target store on the device: its id-range check)
                 parts = tuple(parts) + (self._first_bad_line.to(dev),)
@@ -565,31 +556,16 @@ class PointLogStore(object):
 
     def _upload(self, dev, have):
         import ctypes as C
-        import torch
         from . import _lib
         names = self.HIST + ("line_user", "line_items", "line_last_item", "user_rows", "item_rows")
-        d = {}
-        for k in names:
-            a = have.get(k, getattr(self, k))
-            if a is None:
-                continue
-            if isinstance(a, np.ndarray):        # (an empty array still needs a valid pointer)
-                a = torch.from_numpy(np.ascontiguousarray(a)).to(dev) if a.size else torch.zeros((1,), dtype=torch.int32, device=dev)
-            elif a.numel() == 0:
-                a = torch.zeros((1,), dtype=torch.int32, device=dev)
-            else:
-                a = a.to(dev)
-            d[k] = a
+        d = upload_named(names, lambda k: have.get(k, getattr(self, k)), dev)
         ptr = lambda k: C.c_void_p(d[k].data_ptr()) if k in d else C.c_void_p(0)
         self._dev, self.device = d, dev
         self.struct = _lib.PointLogStore(C.sizeof(_lib.PointLogStore), *[ptr(k) for k in names], self.n_lines, self.n_users,
                                          self.n_items, self.per_line, self.hist_max_len)
 
     def to_device(self, device=None):
-        import torch
-        if not torch.cuda.is_available():
-            raise RuntimeError("PointLogStore.to_device needs an AMD GPU (HIP); batch assembly has no CPU path")
-        dev = torch.device(device if device is not None else "cuda:%d" % torch.cuda.current_device())
+        dev = device_of(device, "PointLogStore.to_device", instead=NO_CPU_PATH)
         have = {}
         if self._dev is not None:                # (a device build on another device: its tensors move)
             have = {k: v.to(dev) for k, v in self._dev.items() if k in self.HIST}
@@ -644,8 +620,7 @@ class DeviceDataLoaderUserSeq(object):
             raise ValueError("batch size should be a multiple of %d (1 + neg_sample_num)" % per_line)
         if store is not None:
             store.check(batch_size, max_len, neg_sample_num, self.dual)
-        if not torch.cuda.is_available():
-            raise RuntimeError("%s needs an AMD GPU (HIP); batch assembly has no CPU path" % type(self).__name__)
+        device_of(what=type(self).__name__, instead=NO_CPU_PATH)           # (which device: the model's or the store's, below)
         if store is None:
             store = PointSeqStore(target_file, user_seq_file, item_seq_file, max_len, neg_sample_num, batch_size,
                                   user_feat_dict_file, item_feat_dict_file)

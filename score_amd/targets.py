@@ -10,23 +10,8 @@ import ctypes as C
 import numpy as np
 
 from . import dataprep
-
-
-def _is_tensor(a):
-    return type(a).__module__.startswith("torch") and hasattr(a, "data_ptr")
-
-
-def _host(a):
-    return a.cpu().numpy() if _is_tensor(a) else np.asarray(a)
-
-
-def device_i32(a, dev):
-    """a column of the log as a flat int32 tensor on `dev`: a tensor is used where it is (converted or moved only if it has
-    to be), anything else goes through numpy and is uploaded"""
-    import torch
-    if _is_tensor(a):
-        return a.to(device=dev, dtype=torch.int32).contiguous().view(-1)
-    return torch.from_numpy(np.ascontiguousarray(np.asarray(a).ravel(), dtype=np.int32)).to(dev)
+from .placement import check_build, device_as, device_i32, device_of
+from .placement import is_tensor as _is_tensor, to_host as _host
 
 
 def pop_items_device(graph, pop_standard, max_iid=None):
@@ -76,8 +61,7 @@ class UserNegLists(object):
         """neg_uid / neg_iid: the negative events in log order (remap_ccmr_log's).  An event whose uid lies outside
         1 .. n_users joins no list.  build="device" (needs a GPU): score_neg_lists_build on int32 tensors (uploaded if they are
         not there yet); off and items stay on the device."""
-        if build not in ("host", "device"):
-            raise ValueError("build is 'host' or 'device': got %r" % (build,))
+        check_build(build)
         U = int(n_users)
         if U <= 0:
             raise ValueError("n_users must be positive")
@@ -93,10 +77,7 @@ class UserNegLists(object):
             return cls(off, i[order].astype(np.int32), U)
         import torch
         from . import _lib
-        if not torch.cuda.is_available():
-            raise RuntimeError("UserNegLists.from_events(build='device') needs an AMD GPU (HIP); build='host' does not")
-        dev = torch.device(device if device is not None else
-                           neg_uid.device if _is_tensor(neg_uid) else "cuda:%d" % torch.cuda.current_device())
+        dev = device_of(device, "UserNegLists.from_events(build='device')", like=neg_uid)
         lib = _lib.load()
         with torch.cuda.device(dev):
             d_u, d_i = device_i32(neg_uid, dev), device_i32(neg_iid, dev)
@@ -118,12 +99,7 @@ class UserNegLists(object):
 
     def device_tensors(self, device):
         """(off int64, items int32) as tensors on `device`: the object's own where it lives there"""
-        import torch
-        dev = torch.device(device)
-        if self.on_device:
-            return self.off.to(dev), self.items.to(dev)
-        return (torch.from_numpy(np.ascontiguousarray(self.off, dtype=np.int64)).to(dev),
-                torch.from_numpy(np.ascontiguousarray(self.items, dtype=np.int32)).to(dev))
+        return device_as(self.off, device, np.int64), device_as(self.items, device, np.int32)
 
     def lists(self):
         """{uid: [iid, ...]} of the users with at least one entry: the dict form"""
@@ -175,8 +151,7 @@ class TargetStore(object):
         soon as any user is eligible.  neg_lists: a UserNegLists (CCMR): gen_target_lines' -- a line's first negatives are the
         user's own, the draws fill the rest; on the device score_target_build_lists, the lists uploaded where they are not
         there yet."""
-        if build not in ("host", "device"):
-            raise ValueError("build is 'host' or 'device': got %r" % (build,))
+        check_build(build)
         if sample_factor is not None and int(sample_factor) < 1:
             raise ValueError("sample_factor must be at least 1: got %r" % (sample_factor,))
         U, I, neg = int(n_users), int(n_items), int(neg_sample_num)
@@ -198,10 +173,7 @@ class TargetStore(object):
             return cls._from_lines(lines, 1 + neg)
         import torch
         from . import _lib
-        if not torch.cuda.is_available():
-            raise RuntimeError("TargetStore.from_log(build='device') needs an AMD GPU (HIP); build='host' does not")
-        dev = torch.device(device if device is not None else
-                           uid.device if _is_tensor(uid) else "cuda:%d" % torch.cuda.current_device())
+        dev = device_of(device, "TargetStore.from_log(build='device')", like=uid)
         lib = _lib.load()
 
         up = lambda a: device_i32(a, dev)
@@ -263,12 +235,7 @@ class TargetStore(object):
 
     def device_tensors(self, device):
         """(line_user, line_items) as int32 tensors on `device`: the store's own where it lives there"""
-        import torch
-        dev = torch.device(device)
-        if self.on_device:
-            return self.line_user.to(dev), self.line_items.to(dev)
-        to = lambda a: torch.from_numpy(np.ascontiguousarray(a, dtype=np.int32)).to(dev)
-        return to(self.line_user), to(self.line_items)
+        return device_as(self.line_user, device, np.int32), device_as(self.line_items, device, np.int32)
 
     def lines(self):
         """[(uid, [pos, neg...])], what dataprep.gen_target_lines yields; a device store downloads on first use"""
