@@ -2086,7 +2086,8 @@ class SASRec(GRU4Rec):
     the same rows for t = 2 .. T - 1 (label 0) and on [final | target_item | target_user], which gives y_pred; the loss is the sum
     of the three log-loss means and the L2 term.  rep_t = Y_t [t < user_seq_length], final = sum_t rep_t.  GRU4Rec's constructor,
     5-tuple, loader and train / eval / save / restore; hidden_size is accepted and ignored.  max_time_len >= 3 and
-    item_fnum * eb_dim <= 128 (ValueError beyond).  Every batch computes all T positions (skip_masked_slices has no effect);
+    item_fnum * eb_dim <= 128, and a sample's attention buffers inside one workgroup's 160 KiB of LDS -- T <= 137 at C = 4, T <= 63
+    at C = 128 -- (ValueError beyond, before a device is touched).  Every batch computes all T positions (skip_masked_slices has no effect);
     the positions the loader padded take part in the attention and in both sequence means, as in the reference.
 
     dropout_masks, where given, is (m0 [R, 200], m1 [R, 80], ma [2, B, T, T]) with R = B (T - 1) + B (T - 2) + B rows ordered
@@ -2108,6 +2109,12 @@ class SASRec(GRU4Rec):
         if int(item_fnum) * int(eb_dim) > self.CMAX:
             raise ValueError("SASRec: item_fnum * eb_dim = %d is above %d, the widest row the attention kernels cover"
                              % (int(item_fnum) * int(eb_dim), self.CMAX))
+        try:      # the library's own verdict (host code: no device is touched): a sample's attention buffers inside one workgroup's LDS
+            _lib.param_layout(_lib.make_config(feature_size, eb_dim, hidden_size, max_time_len, 1, user_fnum, item_fnum, self.model_type))
+        except _lib.ScoreHipError:
+            raise ValueError("SASRec: max_time_len = %d at item_fnum * eb_dim = %d is not a shape the attention kernels cover (a "
+                             "sample's buffers must fit the 160 KiB of LDS of one workgroup; eb_dim a multiple of 4)"
+                             % (int(max_time_len), int(item_fnum) * int(eb_dim)))
         GRU4Rec.__init__(self, feature_size, eb_dim, hidden_size, max_time_len, user_fnum, item_fnum, seed=seed, device=device)
 
     def _mask_shapes(self, B):
