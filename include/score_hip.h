@@ -726,6 +726,55 @@ int score_rank_workspace_bytes(const score_config_t* cfg, int32_t L, int32_t C, 
 int score_rank_forward(const score_config_t* cfg, const score_state_t* st, const score_rank_batch_t* rb,
                        float reg_lambda, float* y_pred /* [L*C] */, float* loss /* [4] as workspace.loss */, void* stream);
 
+/* ---- top-K over a whole item catalogue (csrc/catalog.hip) -------------------------------------------------------------------
+ * "Which k items of the catalogue does the model put first for this user": the line-form split above with the WHOLE catalogue
+ * as every line's candidate set.  The candidate half of fc1's pre-activation then depends on nothing but the catalogue and the
+ * weights:
+ *     z1[l, n] = zline[l] + zcat[n],     zcat[n] = bn1(item_n) . W1[item rows]
+ * score_catalog_build fills zcat [N, 200] (caller-owned) from the table, bn1 and fc1; it is valid until the table or the dense
+ * variables change.  score_catalog_topk runs the history encoder at B = L, zline, and then per (line, chunk of the catalogue)
+ * one workgroup that holds fc2 / fc3 resident, walks its chunk and keeps its k best; a workgroup per line merges the chunks.
+ * SCORE_MODEL_GRU4REC and SCORE_MODEL_CASER only, under the shape conditions of score_rank_forward (SCORE_E_SHAPE otherwise);
+ * N <= 2^30.
+ *
+ * Order: descending fc3 logit (the argument of y_pred's sigmoid: it orders as y_pred does and still separates candidates where
+ * the fp32 sigmoid saturates), ties to the lower catalogue index, a NaN logit behind every number.  This is a total order: the
+ * result does not depend on the cut into chunks.  An index listed in the line's exclusions is never selected; a line with fewer
+ * than k selectable items is filled with index -1 and logit -inf.  1 <= k <= SCORE_CATALOG_KMAX (SCORE_E_BADARG beyond).
+ * all_logits (optional) receives every pair's logit at l * N + n, excluded items included.
+ * Ids outside the table: read as row 0 and reported in score_state_t.id_status, bit 5 for item_rows (score_catalog_build), bits
+ * 0 and 4 for user_seq and target_user.  Every refusal -- a null pointer, L, N <= 0 (SCORE_E_BADARG), model type and shape
+ * (SCORE_E_SHAPE), a workspace below score_catalog_plan's workspace_bytes (SCORE_E_WORKSPACE) -- comes before any launch.
+ * The workspace: score_workspace_layout at B = L, and behind it zline [L, 200], a block of zero ids and the chunks' lists. */
+#define SCORE_CATALOG_KMAX 128
+typedef struct {
+  const int32_t* item_rows;    /* [N, Fi] device: an item's table rows, as target_item of a sample                            */
+  int32_t N;
+  float* zcat;                 /* [N, 200] device, caller-owned: written by score_catalog_build, read by score_catalog_topk   */
+} score_catalog_t;
+typedef struct {
+  const int32_t* user_seq;     /* [L, T, Fi]  as score_rank_batch_t                                                           */
+  const int32_t* length;       /* [L]                                                                                         */
+  const int32_t* target_user;  /* [L, Fu]                                                                                     */
+  int32_t L, active_slices;
+  const int64_t* excl_off;     /* [L + 1] device offsets into excl_idx, or null: no exclusions                                */
+  const int32_t* excl_idx;     /* catalogue indices in [0, N), ascending within a line                                        */
+} score_catalog_lines_t;
+int score_catalog_build(const score_config_t* cfg, const score_state_t* st, const score_catalog_t* cat, void* stream);
+/* The cut of the catalogue, host only and a function of (L, N, k) alone: a scoring workgroup walks `chunk` items (a positive
+ * multiple of 16 -- of 32, the step of the scoring kernel), the catalogue falls into nchunk = ceil(N / chunk) chunks.  The rule:
+ * chunk = max(256, ceil(N / max(1, floor(512 / L))) rounded up to 32) -- one resident round of at most 512 workgroups where the
+ * catalogue is large enough, never fewer than 256 items each; k takes no part in it at present.  *workspace_bytes: what
+ * score_state_t.workspace must hold for score_catalog_topk. */
+int score_catalog_plan(const score_config_t* cfg, int32_t L, int32_t N, int32_t k, int32_t* chunk, int32_t* nchunk,
+                       int64_t* workspace_bytes);
+int score_catalog_topk(const score_config_t* cfg, const score_state_t* st, const score_catalog_t* cat,
+                       const score_catalog_lines_t* lines, int32_t k, int32_t* top_idx /* [L, k] */, float* top_logit /* [L, k] */,
+                       float* all_logits /* [L, N] or null */, void* stream);
+/* sizeof / late-field offsets of the two structures above and SCORE_CATALOG_KMAX, for a binding's layout check (as
+ * score_abi_struct_sizes): returns the number of values written (6), SCORE_E_BADARG for a null pointer or n too small. */
+int score_catalog_struct_sizes(int64_t* out, int32_t n);
+
 /* ---- one training step in one call (csrc/step.hip) -----------------------------------------------------------------------
  * The steady-state step of model.train (score.py:101-116) for a caller that runs the time-tiled table optimizer with the
  * look-ahead (score_adam_catchup_ids_through) and sorts the next batch's index plan a step ahead: exactly

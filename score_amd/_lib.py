@@ -42,6 +42,20 @@ class RankBatch(C.Structure):
                 ("L", C.c_int32), ("C", C.c_int32), ("active_slices", C.c_int32)]
 
 
+class Catalog(C.Structure):
+    """score_catalog_t: an item catalogue's table rows and its half of fc1's pre-activation (score_catalog_build)"""
+    _fields_ = [("item_rows", c_i), ("N", C.c_int32), ("zcat", c_f)]
+
+
+class CatalogLines(C.Structure):
+    """score_catalog_lines_t: L users' lines and their excluded catalogue indices (score_catalog_topk)"""
+    _fields_ = [("user_seq", c_i), ("length", c_i), ("target_user", c_i), ("L", C.c_int32), ("active_slices", C.c_int32),
+                ("excl_off", C.c_void_p), ("excl_idx", c_i)]
+
+
+CATALOG_KMAX = 128      # SCORE_CATALOG_KMAX
+
+
 class Workspace(C.Structure):
     _fields_ = [(n, C.c_int64) for n in
                 ("total_bytes", "xside", "atten_info", "rsave", "query", "head_inp", "att_score",
@@ -281,6 +295,12 @@ _SIGS = {
                        C.POINTER(C.c_void_p), C.c_void_p],
     "score_rank_workspace_bytes": [C.POINTER(Config), C.c_int32, C.c_int32, C.POINTER(C.c_int64)],
     "score_rank_forward": [C.POINTER(Config), C.POINTER(State), C.POINTER(RankBatch), C.c_float, c_f, c_f, C.c_void_p],
+    "score_catalog_build": [C.POINTER(Config), C.POINTER(State), C.POINTER(Catalog), C.c_void_p],
+    "score_catalog_plan": [C.POINTER(Config), C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int32),
+                           C.POINTER(C.c_int64)],
+    "score_catalog_topk": [C.POINTER(Config), C.POINTER(State), C.POINTER(Catalog), C.POINTER(CatalogLines), C.c_int32, c_i, c_f, c_f,
+                           C.c_void_p],
+    "score_catalog_struct_sizes": [C.POINTER(C.c_int64), C.c_int32],
 }
 # (score_rank_workspace_bytes returns a status; the size comes back through its last argument)
 _STATUS_RETURN = ("score_rank_workspace_bytes",)
@@ -414,6 +434,14 @@ def rank_workspace_bytes(cfg, L, n_cand):
     n = C.c_int64(0)
     check(load().score_rank_workspace_bytes(C.byref(cfg), int(L), int(n_cand), C.byref(n)), "score_rank_workspace_bytes")
     return n.value
+
+
+def catalog_plan(cfg, L, N, k):
+    """(chunk, nchunk, workspace bytes) of score_catalog_topk for L lines against N items: score_catalog_plan"""
+    chunk, nchunk, n = C.c_int32(0), C.c_int32(0), C.c_int64(0)
+    check(load().score_catalog_plan(C.byref(cfg), int(L), int(N), int(k), C.byref(chunk), C.byref(nchunk), C.byref(n)),
+          "score_catalog_plan")
+    return chunk.value, nchunk.value, n.value
 
 
 def workspace_field(cfg, B, name):

@@ -2037,6 +2037,45 @@ int rank_dims(const score_config_t* cfg, int L, int C, Dims* d) {
   if (!score_rank_head_fits(L, C, d->Dhead, d->off_ti, d->Di, d->D, FC1, FC2)) return SCORE_E_SHAPE;
   return 0;
 }
+// What score_rank_forward and score_catalog_topk share, in front of their heads: the zero ids, the lines as a batch of L samples
+// (*lb), pass_fill, fwd_open, the history encoder and the side stream's join.  c->d is set; label: [>= L] int32 (not read in
+// front of the head)
+int rank_prefix(Pass* c, FwdState* f, score_batch_t* lb, const score_state_t* st, const int32_t* user_seq, const int32_t* length,
+                const int32_t* target_user, const int32_t* label, int L, int active_slices, int32_t* zero_ids, int64_t n_zero_ids,
+                void* stream) {
+  const Dims& d = c->d;
+  hipStream_t s = (hipStream_t)stream;
+  HIPTRY(hipMemsetAsync(zero_ids, 0, (size_t)n_zero_ids * sizeof(int32_t), s));
+  // the lines as a batch of L samples: user_seq rides as user_1hop [L, T, 1, Fi], as in a point model's score_batch_t
+  memset(lb, 0, sizeof(*lb));
+  lb->user_1hop = user_seq; lb->user_2hop = lb->item_1hop = lb->item_2hop = zero_ids;
+  lb->target_user = target_user; lb->target_item = zero_ids; lb->label = label ? label : zero_ids; lb->length = length;
+  lb->B = L; lb->active_slices = active_slices;
+  SCORE_TRY(pass_fill(c, st, lb, stream));
+  SCORE_TRY(fwd_open(*c, f));
+  float* ws = c->ws;
+  if (d.family == FAM_G4R) {       // (fwd_g4r's launches in front of the head)
+    HIPTRY(hipStreamWaitEvent(s, f->sd->wx, 0));
+    G(g4r_grus_fwd(*c));
+    G(score_launch_copy2d(L, c->H, ws + c->w.gru_final[1], c->H, ws + c->w.head_inp, d.Dhead, s));
+  } else {                         // (fwd_caser's)
+    CaserArgs a;
+    caser_args(*c, nullptr, &a);
+    G(score_caser_fwd(a, s));
+  }
+  HIPTRY(hipStreamWaitEvent(s, f->sd->join, 0));       // (the target-user rows and the L2 partial sums come from the side stream)
+  return 0;
+}
+// the head's side of RankArgs: what the line kernel and the tile kernel read of the model
+void rank_head_args(const Pass& c, const score_state_t* st, int L, int C, RankArgs* a) {
+  const Dims& d = c.d; const float* W = c.W; const Params& P = c.P;
+  memset(a, 0, sizeof(*a));
+  a->L = L; a->C = C; a->Dh = d.Dhead; a->off_ti = d.off_ti; a->Di = d.Di; a->D = d.D; a->N1 = FC1; a->N2 = FC2;
+  a->head = c.ws + c.w.head_inp; a->table = st->table;
+  a->gamma = W + P.bn_g; a->beta = W + P.bn_b; a->rs = c.rs;
+  a->W1 = W + P.fc_w[0]; a->b1 = W + P.fc_b[0]; a->W2 = W + P.fc_w[1]; a->b2 = W + P.fc_b[1]; a->W3 = W + P.fc_w[2]; a->b3 = W + P.fc_b[2];
+  a->n_rows = c.n_rows; a->id_status = st->id_status;
+}
 }  // namespace
 
 extern "C" int score_rank_workspace_bytes(const score_config_t* cfg, int32_t L, int32_t C, int64_t* bytes) {
@@ -2062,38 +2101,124 @@ extern "C" int score_rank_forward(const score_config_t* cfg, const score_state_t
   build_rank_ws(d, L, C, &r);
   if (r.total * 4 > st->workspace_bytes) return SCORE_E_WORKSPACE;
   hipStream_t s = (hipStream_t)stream;
-  int32_t* zero_ids = reinterpret_cast<int32_t*>(st->workspace + r.zero_ids);
-  HIPTRY(hipMemsetAsync(zero_ids, 0, (size_t)r.n_zero_ids * sizeof(int32_t), s));
-  // the lines as a batch of L samples: user_seq rides as user_1hop [L, T, 1, Fi], as in a point model's score_batch_t
   score_batch_t lb;
-  memset(&lb, 0, sizeof(lb));
-  lb.user_1hop = rb->user_seq; lb.user_2hop = lb.item_1hop = lb.item_2hop = zero_ids;
-  lb.target_user = rb->target_user; lb.target_item = zero_ids; lb.label = rb->label; lb.length = rb->length;
-  lb.B = L; lb.active_slices = rb->active_slices;
-  SCORE_TRY(pass_fill(&c, st, &lb, stream));
   FwdState f = {reg_lambda, 1.f, nullptr, nullptr, 0, nullptr, nullptr, false};
-  SCORE_TRY(fwd_open(c, &f));
-  float* ws = c.ws; const float* W = c.W; const Params& P = c.P;
-  if (d.family == FAM_G4R) {       // (fwd_g4r's launches in front of the head)
-    HIPTRY(hipStreamWaitEvent(s, f.sd->wx, 0));
-    G(g4r_grus_fwd(c));
-    G(score_launch_copy2d(L, c.H, ws + c.w.gru_final[1], c.H, ws + c.w.head_inp, d.Dhead, s));
-  } else {                         // (fwd_caser's)
-    CaserArgs a;
-    caser_args(c, nullptr, &a);
-    G(score_caser_fwd(a, s));
-  }
-  HIPTRY(hipStreamWaitEvent(s, f.sd->join, 0));       // (the target-user rows and the L2 partial sums come from the side stream)
+  SCORE_TRY(rank_prefix(&c, &f, &lb, st, rb->user_seq, rb->length, rb->target_user, rb->label, L, rb->active_slices,
+                        reinterpret_cast<int32_t*>(st->workspace + r.zero_ids), r.n_zero_ids, stream));
+  float* ws = c.ws;
   RankArgs a;
-  memset(&a, 0, sizeof(a));
-  a.L = L; a.C = C; a.Dh = d.Dhead; a.off_ti = d.off_ti; a.Di = d.Di; a.D = d.D; a.N1 = FC1; a.N2 = FC2;
-  a.head = ws + c.w.head_inp; a.table = st->table; a.cand = rb->cand_items; a.label = rb->label;
-  a.gamma = W + P.bn_g; a.beta = W + P.bn_b; a.rs = c.rs;
-  a.W1 = W + P.fc_w[0]; a.b1 = W + P.fc_b[0]; a.W2 = W + P.fc_w[1]; a.b2 = W + P.fc_b[1]; a.W3 = W + P.fc_w[2]; a.b3 = W + P.fc_b[2];
+  rank_head_args(c, st, L, C, &a);
+  a.cand = rb->cand_items; a.label = rb->label;
   a.zline = ws + r.zline; a.y = y_pred; a.lossb = ws + r.lossb;
-  a.n_rows = c.n_rows; a.id_status = st->id_status;
   G(score_rank_head(a, s));
   return loss_tail_at(c, f.sd, reg_lambda, L * C, ws + r.lossb, loss, global_batch(st, L * C));
+}
+
+// ---------------------------------------------------------------- top-K over a whole item catalogue (GRU4Rec, Caser; catalog.hip)
+// score_catalog_build: zcat [N, 200], the catalogue's half of fc1's pre-activation.  score_catalog_topk: the prefix of the
+// ranking pass at B = L, the line kernel alone, then a scoring workgroup per (line, chunk) and a merge per line.
+namespace {
+// Behind the workspace of a batch of L samples (build_ws at B = L, untouched): zline [L, FC1], the zero ids (as RankWS) and the
+// chunks' lists, [L, nchunk, k] 64-bit keys
+struct CatalogWS { int64_t zline, zero_ids, n_zero_ids, part, total; int chunk, nchunk; };
+void build_catalog_ws(const Dims& d, int L, int N, int k, CatalogWS* r) {
+  WS w;
+  build_ws(d, L, &w);
+  score_catalog_chunks(L, N, k, &r->chunk, &r->nchunk);
+  Taker take = {w.total};
+  r->zline = take((int64_t)L * FC1);
+  r->n_zero_ids = (int64_t)L * d.T * (d.Fu > d.Fi ? d.Fu : d.Fi);
+  r->zero_ids = take(r->n_zero_ids);
+  r->part = take((int64_t)L * r->nchunk * k * 2);
+  r->total = take.cur;
+}
+const int32_t CATALOG_NMAX = 1 << 30;        // (a step past the last item stays inside int32)
+int catalog_dims(const score_config_t* cfg, int L, int N, int k, Dims* d) {
+  SCORE_TRY(rank_dims(cfg, L, 1, d));
+  if (N <= 0 || k < 1 || k > SCORE_CATALOG_KMAX) return SCORE_E_BADARG;
+  if (N > CATALOG_NMAX) return SCORE_E_SHAPE;
+  int chunk, nchunk;
+  score_catalog_chunks(L, N, k, &chunk, &nchunk);
+  if ((int64_t)L * nchunk >= (1LL << 31)) return SCORE_E_SHAPE;
+  return 0;
+}
+void catalog_model_args(const Dims& d, const score_state_t* st, const score_catalog_t* cat, CatalogArgs* a) {
+  Params P;
+  build_layout(d, nullptr, 0, &P);
+  const float* W = st->w;
+  memset(a, 0, sizeof(*a));
+  a->N = cat->N; a->Di = d.Di; a->D = d.D; a->off_ti = d.off_ti; a->N1 = FC1;
+  a->table = st->table; a->item_rows = cat->item_rows; a->zcat = cat->zcat;
+  a->gamma = W + P.bn_g; a->beta = W + P.bn_b; a->rs = (float)(1.0 / sqrt(1.0 + 1e-3));
+  a->W1 = W + P.fc_w[0]; a->W2 = W + P.fc_w[1]; a->b2 = W + P.fc_b[1]; a->W3 = W + P.fc_w[2]; a->b3 = W + P.fc_b[2];
+  a->n_rows = clamp_rows(st->n_table_rows); a->id_status = st->id_status;
+}
+}  // namespace
+
+extern "C" int score_catalog_plan(const score_config_t* cfg, int32_t L, int32_t N, int32_t k, int32_t* chunk, int32_t* nchunk,
+                                  int64_t* workspace_bytes) {
+  if (!cfg || !chunk || !nchunk || !workspace_bytes) return SCORE_E_BADARG;
+  Dims d;
+  SCORE_TRY(catalog_dims(cfg, L, N, k, &d));
+  CatalogWS r;
+  build_catalog_ws(d, L, N, k, &r);
+  *chunk = r.chunk; *nchunk = r.nchunk; *workspace_bytes = r.total * 4;
+  return 0;
+}
+
+extern "C" int score_catalog_build(const score_config_t* cfg, const score_state_t* st, const score_catalog_t* cat, void* stream) {
+  if (!cfg || !st || !cat) return SCORE_E_BADARG;
+  Dims d;
+  SCORE_TRY(rank_dims(cfg, 1, 1, &d));
+  if (!st->table || !st->w || !cat->item_rows || !cat->zcat || cat->N <= 0) return SCORE_E_BADARG;
+  if (cat->N > CATALOG_NMAX) return SCORE_E_SHAPE;
+  CatalogArgs a;
+  catalog_model_args(d, st, cat, &a);
+  return score_catalog_zcat(a, (hipStream_t)stream);
+}
+
+extern "C" int score_catalog_topk(const score_config_t* cfg, const score_state_t* st, const score_catalog_t* cat,
+                                  const score_catalog_lines_t* ln, int32_t k, int32_t* top_idx, float* top_logit, float* all_logits,
+                                  void* stream) {
+  if (!cfg || !st || !cat || !ln || !top_idx || !top_logit) return SCORE_E_BADARG;
+  Pass c;
+  SCORE_TRY(catalog_dims(cfg, ln->L, cat->N, k, &c.d));
+  if (!st->table || !st->w || !st->workspace || !cat->item_rows || !cat->zcat) return SCORE_E_BADARG;
+  if (!ln->user_seq || !ln->length || !ln->target_user || (ln->excl_off && !ln->excl_idx)) return SCORE_E_BADARG;
+  const Dims& d = c.d;
+  const int L = ln->L;
+  CatalogWS r;
+  build_catalog_ws(d, L, cat->N, k, &r);
+  if (r.total * 4 > st->workspace_bytes) return SCORE_E_WORKSPACE;
+  hipStream_t s = (hipStream_t)stream;
+  score_batch_t lb;
+  FwdState f = {0.f, 1.f, nullptr, nullptr, 0, nullptr, nullptr, false};
+  SCORE_TRY(rank_prefix(&c, &f, &lb, st, ln->user_seq, ln->length, ln->target_user, nullptr, L, ln->active_slices,
+                        reinterpret_cast<int32_t*>(st->workspace + r.zero_ids), r.n_zero_ids, stream));
+  float* ws = c.ws;
+  RankArgs ra;
+  rank_head_args(c, st, L, 1, &ra);
+  ra.zline = ws + r.zline;
+  G(score_rank_line(ra, s));
+  CatalogArgs a;
+  catalog_model_args(d, st, cat, &a);
+  a.L = L; a.k = k; a.chunk = r.chunk; a.nchunk = r.nchunk;
+  a.zline = ws + r.zline; a.excl_off = ln->excl_off; a.excl_idx = ln->excl_idx;
+  a.part = reinterpret_cast<unsigned long long*>(ws + r.part);
+  a.top_idx = top_idx; a.top_logit = top_logit; a.all_logits = all_logits;
+  return score_catalog_select(a, s);
+}
+
+// sizes and late-field offsets of the catalogue call's structures, as score_abi_struct_sizes gives them for the others: -> the
+// number of values written, SCORE_E_BADARG for a null pointer or n too small.  Host only.
+extern "C" int score_catalog_struct_sizes(int64_t* out, int32_t n) {
+  const int64_t v[] = {(int64_t)sizeof(score_catalog_t), (int64_t)sizeof(score_catalog_lines_t),
+                       (int64_t)offsetof(score_catalog_t, zcat), (int64_t)offsetof(score_catalog_lines_t, excl_off),
+                       (int64_t)offsetof(score_catalog_lines_t, excl_idx), (int64_t)SCORE_CATALOG_KMAX};
+  const int32_t have = (int32_t)(sizeof(v) / sizeof(v[0]));
+  if (!out || n < have) return SCORE_E_BADARG;
+  for (int32_t i = 0; i < have; ++i) out[i] = v[i];
+  return have;
 }
 
 // ---------------------------------------------------------------- the layer-by-layer backward pass

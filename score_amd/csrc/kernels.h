@@ -331,6 +331,30 @@ struct RankArgs {
 };
 bool score_rank_head_fits(int L, int C, int Dh, int off_ti, int Di, int D, int N1, int N2);
 int score_rank_head(const RankArgs& a, hipStream_t s);
+int score_rank_line(const RankArgs& a, hipStream_t s);       // the line kernel alone (zline; a.C is not read): the catalogue pass
+// catalog.hip: top-K over a whole item catalogue (score_catalog_build / score_catalog_topk).  fc1's pre-activation of the pair
+// (line l, catalogue item n) is zline[l] + zcat[n]; zcat [N, 200] = bn1(item_n) . W1[item rows] is a per-catalogue constant.
+// score_catalog_zcat fills it (a workgroup per 16 items; ids >= n_rows read as row 0, bit 5 of *id_status).
+// score_catalog_select: a workgroup per (line, chunk of the catalogue) holds fc2 / fc3 resident, walks its chunk and keeps its k
+// best pairs -- ordered by (logit descending, index ascending; NaN behind every number) as 64-bit keys, see catalog.hip -- in
+// part [L, nchunk, k]; then a workgroup per line merges the nchunk lists into top_idx / top_logit [L, k] (-1 / -inf padding).
+// excl_off / excl_idx (optional): per line, ascending catalogue indices that are never selected.  all_logits (optional) [L, N].
+// Fixed head widths: fc1 = 200, fc2 = 80 outputs.
+struct CatalogArgs {
+  int L, N, k, chunk, nchunk;
+  int Di, D, off_ti, N1;                 // the item columns [off_ti, off_ti + Di) of the head input; N1 = 200
+  const float* table; const int32_t* item_rows;
+  const float* gamma; const float* beta; float rs;
+  const float* W1; const float* W2; const float* b2; const float* W3; const float* b3;
+  float* zcat; const float* zline;
+  const int64_t* excl_off; const int32_t* excl_idx;
+  unsigned long long* part;
+  int32_t* top_idx; float* top_logit; float* all_logits;
+  uint32_t n_rows; int32_t* id_status;
+};
+void score_catalog_chunks(int L, int N, int k, int* chunk, int* nchunk);
+int score_catalog_zcat(const CatalogArgs& a, hipStream_t s);
+int score_catalog_select(const CatalogArgs& a, hipStream_t s);
 // delf.hip: the DELF point baseline (point_model.py:200-249) between the gather and the scatter.  Per side (0: user_seq rows
 // against target_item through dense; 1: item_seq rows against target_user through dense_1) X [B * T, C] with row stride ldx,
 // the saved keys [B * T, C] (live rows only), attention weights att [B, T], rep [B, C]; backward: ds [B, T] (gradient at the

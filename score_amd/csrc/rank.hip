@@ -170,6 +170,14 @@ bool score_rank_head_fits(int L, int C, int Dh, int off_ti, int Di, int D, int N
   return rank_tile_lds(Di, N1, N2) <= 150 * 1024 && rank_line_lds(Dh, N1) <= 48 * 1024;
 }
 
+// The line kernel alone: zline [L, N1] for a caller that pairs the lines with something else than C candidates each (catalog.hip)
+int score_rank_line(const RankArgs& a, hipStream_t s) {
+  if (!score_rank_head_fits(a.L, 1, a.Dh, a.off_ti, a.Di, a.D, a.N1, a.N2)) return SCORE_E_SHAPE;
+  hipLaunchKernelGGL(rank_line_kernel, dim3(a.L), dim3(64 * RL_NW), rank_line_lds(a.Dh, a.N1), s, a);
+  SCORE_CHECK_LAUNCH();
+  return 0;
+}
+
 // Returns SCORE_E_SHAPE for a shape the two kernels do not cover (score_rank_head_fits)
 int score_rank_head(const RankArgs& a, hipStream_t s) {
   if (!score_rank_head_fits(a.L, a.C, a.Dh, a.off_ti, a.Di, a.D, a.N1, a.N2)) return SCORE_E_SHAPE;

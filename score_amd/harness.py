@@ -339,3 +339,78 @@ def evaluate_device(model, batches, reg_lambda, neg_sample_num=TEST_NEG_SAMPLE_N
     if loss != loss and hasattr(model, "check_ids"):
         model.check_ids()       # (a NaN loss is how an id outside the table shows: raised HERE, not blamed on the next train step)
     return (logloss, auc, ndcg_5, ndcg_10, hr_1, hr_5, hr_10, mrr, loss)
+
+
+def catalog_quality_device(top_idx, target_idx):
+    """The six numbers of get_ranking_quality, in its order -- (NDCG@5, NDCG@10, HR@1, HR@5, HR@10, MRR) -- from top-k lists over a
+    whole catalogue (model.recommend_async): top_idx [n_lines, k] catalogue indices, best first, target_idx [n_lines] the
+    positive's index.  The positive's rank is its position in the list; a positive that is not in the list counts 0 everywhere,
+    so MRR is truncated at k.  Needs k >= 10.  Tensors on any device; one 6-float read-back."""
+    import torch
+    top = top_idx.reshape(top_idx.shape[0], -1)
+    n, k = top.shape
+    if k < 10:
+        raise ValueError("catalog_quality_device needs lists of k >= 10 items, got k = %d" % k)
+    tgt = target_idx.reshape(-1).to(device=top.device, dtype=top.dtype)
+    if tgt.numel() != n or n == 0:
+        raise ValueError("top_idx [n_lines, k] and target_idx [n_lines] must name the same, non-zero number of lines")
+    hit = top == tgt[:, None]
+    found = hit.any(1)
+    r = hit.to(torch.int32).argmax(1).to(torch.float64)              # 0-based rank of the first hit (0 where there is none)
+    gain = math.log(2) / torch.log(r + 2)
+    zero = torch.zeros_like(gain)
+    f = lambda cond: (found & cond).to(torch.float64).mean()
+    out = torch.stack([torch.where(found & (r < 5), gain, zero).mean(), torch.where(found & (r < 10), gain, zero).mean(),
+                       f(r < 1), f(r < 5), f(r < 10), torch.where(found, 1.0 / (r + 1), zero).mean()])
+    return tuple(float(x) for x in out.cpu().tolist())
+
+
+def evaluate_catalog(model, batches, catalog, neg_sample_num=TEST_NEG_SAMPLE_NUM, k=10, exclude_history=None, return_lists=False):
+    """Ranking metrics against the WHOLE catalogue instead of the sampled negatives: for every target line of a loader's eval
+    batches (lines of 1 + neg_sample_num samples, the first candidate the positive) the model's k best items of `catalog`
+    (model.recommend_async), then catalog_quality_device on the positive's position -> its six numbers.
+
+    exclude_history: a PointLogStore -- the items of each user's history are excluded from the user's list, the positive
+    itself never.  return_lists: also the lists and the positives' catalogue indices, (six, top_idx [n_lines, k], target_idx)."""
+    import torch
+    tops, tgts = [], []
+    for batch_data in batches:
+        db = model.device_batch(batch_data)
+        lines = model.lines_of(db, neg_sample_num)
+        L = int(lines[1].numel())
+        pos_ids = db.tensors[5].view(L, 1 + neg_sample_num, -1)[:, 0, 0].contiguous()
+        tgt, found = catalog.indices_of(pos_ids)
+        if not bool(found.all().item()):
+            raise ValueError("evaluate_catalog: a line's positive item is not in the catalogue")
+        exclude = None
+        if exclude_history is not None:
+            exclude = _history_exclusions(exclude_history, lines[2][:, 0], pos_ids)
+        top = model.recommend_async(lines, catalog, k=k, exclude=exclude, active_slices=db.active_slices)[0]
+        tops.append(top.clone()); tgts.append(tgt.to(torch.int32))
+    top, tgt = torch.cat(tops), torch.cat(tgts)
+    six = catalog_quality_device(top, tgt)
+    if hasattr(model, "check_ids"):
+        model.check_ids()
+    return (six, top, tgt) if return_lists else six
+
+
+def _history_exclusions(store, user_ids, keep_ids):
+    """CSR pair (offsets [L + 1], item ids) of the L users' histories in a PointLogStore -- user u's run of user_hist_seq, all of
+    it, not only the part a batch reads -- without each line's own keep id.  A user id the store does not know has none."""
+    import torch
+    dev = user_ids.device
+    as_dev = lambda a: (a if torch.is_tensor(a) else torch.from_numpy(np.ascontiguousarray(a))).to(dev)
+    off, seq = as_dev(store.user_hist_off).to(torch.int64), as_dev(store.user_hist_seq).reshape(-1)
+    U = int(off.numel()) - 1
+    u = user_ids.to(torch.int64)
+    known = (u >= 1) & (u <= U)
+    uc = u.clamp(1, U)
+    start = off[uc - 1]
+    n = torch.where(known, off[uc] - start, torch.zeros_like(start))
+    out_off = torch.cat([torch.zeros((1,), dtype=torch.int64, device=dev), torch.cumsum(n, 0)])
+    total = int(out_off[-1].item())
+    j = torch.arange(total, device=dev, dtype=torch.int64)
+    line = torch.searchsorted(out_off, j, right=True) - 1
+    items = seq[start[line] + (j - out_off[line])].to(torch.int64)
+    items = torch.where(items == keep_ids.to(torch.int64)[line], torch.full_like(items, -1), items)     # (-1: in no catalogue)
+    return out_off, items

@@ -231,6 +231,9 @@ def active_slices(model, max_len, min_len=None):
     return 0 if a >= T else a
 
 
+_active_slices_of = active_slices        # (for the methods that take an `active_slices` argument of their own)
+
+
 def rank_lines(B, neg_sample_num):
     """(L, C) of a batch of B samples made of target lines of C = 1 + neg_sample_num candidates each"""
     n_cand = 1 + int(neg_sample_num)
@@ -242,6 +245,7 @@ def rank_lines(B, neg_sample_num):
 class SCOREBASE(object):
     model_type = None
     feed_spec = SLICE_FEED
+    weights_version = 0          # moves whenever the table or a dense variable may have changed (what an ItemCatalog was built at)
     reads_length = True          # False: the model's graph does not use the length tensor -- every slice is computed (Caser)
     zero_length_reads_all = True  # (two length tensors) a length <= 0 makes the batch compute all T slices: DELF's rule, not DEEMS's
     dropout_towers = 1           # build_fc_net heads with dropout masks of their own (DEEMS: 2, masks [2, B, 200] / [2, B, 80])
@@ -478,6 +482,7 @@ class SCOREBASE(object):
     def table(self, t):
         self._flush_adam()
         self._tbl, self._tiled, self._tiled_ready = t, None, False
+        self.weights_version += 1
 
     # the flat dense variables and their Adam slots.  Their ApplyAdam may have run on the side stream (apply_adam: behind the dense
     # gradient's finishers, beside the table's touched-row update): whoever reads or writes them through here waits for it first
@@ -489,6 +494,7 @@ class SCOREBASE(object):
     @w.setter
     def w(self, t):
         self._w = t
+        self.weights_version += 1
 
     @property
     def w_m(self):
@@ -651,6 +657,7 @@ class SCOREBASE(object):
         self.row0 = emb[0].copy()
         self.table.copy_(torch.from_numpy(emb))
         self.table[0].zero_()
+        self.weights_version += 1
 
     # Where a dense variable -- or its gradient, or one of its Adam slots -- crosses the Python boundary (get_params, set_params,
     # get_grads, save, restore), it has TF's name and TF's shape.  For most models that is the library's own shape; a model whose
@@ -673,6 +680,7 @@ class SCOREBASE(object):
 
     def _set_dense(self, params):
         self._import_all(self.w, params)
+        self.weights_version += 1
 
     def get_params(self):
         """dict TF variable name -> ndarray (emb_mtx carries its masked row 0 value)."""
@@ -1480,6 +1488,7 @@ class SCOREBASE(object):
         self.beta1_power = np.float32(self.beta1_power * np.float32(ADAM_B1))
         self.beta2_power = np.float32(self.beta2_power * np.float32(ADAM_B2))
         self.step += 1
+        self.weights_version = getattr(self, "weights_version", 0) + 1      # (the variables have moved: ItemCatalog)
 
     # "auto" = two alternating plan buffers below this many occurrences per batch.  With two, the next batch's sort (~100 us) runs
     # beside this step's passes instead of behind its scatter: at few occurrences per batch that sort is the longest cycle of the
@@ -1861,16 +1870,10 @@ class SCOREBASE(object):
         db = self.device_batch(batch_data)
         L, n_cand = rank_lines(db.B, neg_sample_num)
         t = db.tensors
-        per_line = []
-        for i in (0, 7, 4):                      # user_seq (as user_1hop), user_seq_length, target_user
-            rows = t[i].view(L, n_cand, -1)
-            first = rows[:, 0].contiguous()
-            per_line.append(first)
-            if verify:
-                per_line.append((rows != first[:, None]).any())
+        per_line = self.lines_of(db, neg_sample_num)      # user_seq (as user_1hop), user_seq_length, target_user
         if verify:
-            bad = torch.stack(per_line[1::2]).tolist()
-            per_line = per_line[0::2]
+            bad = torch.stack([(t[i].view(L, n_cand, -1) != first.reshape(L, 1, -1)).any()
+                               for i, first in zip((0, 7, 4), per_line)]).tolist()
             sl = self.feed_spec.slots
             for i, b in zip((0, 7, 4), bad):
                 if b:
@@ -1896,6 +1899,94 @@ class SCOREBASE(object):
         if loss != loss:
             self.check_ids()
         return pred.reshape([-1, ]).tolist(), label.reshape([-1, ]).tolist(), loss
+
+    # ------------------------------------------------------------------ top-K over an item catalogue (score_catalog_topk)
+    def lines_of(self, batch_data, neg_sample_num=TEST_NEG_SAMPLE_NUM):
+        """The line form of an eval batch made of target lines (rank_async): (user_seq [L, T, Fi], user_seq_length [L],
+        target_user [L, Fu]) as int32 device tensors -- every C-th row, C = 1 + neg_sample_num, by one strided copy each."""
+        if self.rank_unsupported is not None:
+            raise NotImplementedError("%s has no line-form ranking pass: %s" % (type(self).__name__, self.rank_unsupported))
+        db = self.device_batch(batch_data)
+        L, n_cand = rank_lines(db.B, neg_sample_num)
+        t, c = db.tensors, self.cfg
+        T, Fi, Fu = int(c.max_time_len), int(c.item_fnum), int(c.user_fnum)
+        first = lambda x: x.view(L, n_cand, -1)[:, 0].contiguous()
+        return first(t[0]).view(L, T, Fi), first(t[7]).view(L), first(t[4]).view(L, Fu)
+
+    def _catalog_buffers(self, L, N, k):
+        """the workspace of score_catalog_topk, one per (L, N, k); the last few are kept (as _rank_buffers)"""
+        key = ("catalog", L, N, k)
+        ent = self._rank_ws.pop(key, None)
+        if ent is None:
+            nbytes = _lib.catalog_plan(self.cfg, L, N, k)[2]
+            while len(self._rank_ws) >= self.max_workspaces:
+                torch.cuda.synchronize(self.device)
+                self._rank_ws.pop(next(iter(self._rank_ws)))
+            ent = torch.empty(((nbytes + 3) // 4,), dtype=torch.float32, device=self.device)
+        self._rank_ws[key] = ent
+        return ent
+
+    def recommend_async(self, lines, catalog, k=10, exclude=None, all_logits=False, active_slices=None):
+        """The k items of `catalog` (an ItemCatalog of this model) the model puts first for each of L users: (idx [L, k] int32
+        catalogue indices, logits [L, k]) as device tensors, plus all_logits [L, N] when asked for.  Ordered by descending fc3
+        logit -- the argument of y_pred's sigmoid --, ties to the lower index; an excluded item is never returned, and a line
+        with fewer than k items left is filled with index -1 and logit -inf (include/score_hip.h: score_catalog_topk).
+
+        lines: (user_seq [L, T, Fi], user_seq_length [L], target_user [L, Fu]), host arrays or device tensors (lines_of takes
+        them from an eval batch).  exclude: per line the item ids (column 0 of the catalogue's rows) not to return -- a list of L
+        arrays, or a CSR pair (offsets [L + 1], ids); ids the catalogue does not hold are dropped, order and repeats do not
+        matter.  active_slices: None = from the longest length (one read-back), 0 = all T, or score_batch_t's value.
+        GRU4Rec and Caser; the catalogue is rebuilt first if the model's weights have moved since it was built."""
+        if self.rank_unsupported is not None:
+            raise NotImplementedError("%s has no catalogue pass: %s" % (type(self).__name__, self.rank_unsupported))
+        if not isinstance(catalog, ItemCatalog) or catalog.model is not self:
+            raise ValueError("catalog must be an ItemCatalog built for this model")
+        k = int(k)
+        if not 1 <= k <= _lib.CATALOG_KMAX:
+            raise ValueError("k = %d outside [1, %d]" % (k, _lib.CATALOG_KMAX))
+        if len(lines) != 3:
+            raise ValueError("lines must be (user_seq, user_seq_length, target_user)")
+        c = self.cfg
+        T, Fi, Fu = int(c.max_time_len), int(c.item_fnum), int(c.user_fnum)
+        i32 = lambda x: (x if torch.is_tensor(x) else torch.from_numpy(np.ascontiguousarray(np.asarray(x)))).to(
+            device=self.device, dtype=torch.int32).contiguous()
+        useq, length, tuser = (i32(x) for x in lines)
+        L = int(length.numel())
+        if L == 0:
+            raise ValueError("no lines")
+        for name, x, shape in (("user_seq", useq, (L, T, Fi)), ("user_seq_length", length, (L,)), ("target_user", tuser, (L, Fu))):
+            if tuple(x.shape) != shape:
+                raise ValueError("lines: %s has shape %s, expected %s" % (name, tuple(x.shape), shape))
+        if active_slices is None:
+            active_slices = _active_slices_of(self, int(length.max().item()))
+        N = catalog.N
+        excl_off = excl_idx = None
+        if exclude is not None:
+            excl_off, excl_idx = catalog.exclusions(exclude, L)
+        ws = self._catalog_buffers(L, N, k)
+        idx = torch.empty((L, k), dtype=torch.int32, device=self.device)
+        logit = torch.empty((L, k), dtype=torch.float32, device=self.device)
+        full = torch.empty((L, N), dtype=torch.float32, device=self.device) if all_logits else None
+        ln = _lib.CatalogLines(_ptr(useq), _ptr(length), _ptr(tuser), L, int(active_slices),
+                               _ptr(excl_off) if excl_off is not None else None, _ptr(excl_idx) if excl_idx is not None else None)
+        with self._Pin(self):
+            catalog.refresh()            # (flushes the time-tiled optimizer for the whole table: every item row is read)
+            st = self._state(ws)
+            cat = catalog.struct()
+            rc = self.lib.score_catalog_topk(C.byref(self.cfg), C.byref(st), C.byref(cat), C.byref(ln), k, _ptr(idx), _ptr(logit),
+                                             _ptr(full) if full is not None else None, self._stream())
+        _lib.check(rc, "score_catalog_topk")
+        return (idx, logit, full) if all_logits else (idx, logit)
+
+    def recommend(self, lines, catalog, k=10, exclude=None, active_slices=None):
+        """recommend_async, read back: per line the item ids (column 0 of the catalogue's rows) and sigmoid(logit) as lists,
+        best first, the -1 padding dropped -> (ids, scores).  Raises as rank does when an id outside the table was fed."""
+        idx, logit = self.recommend_async(lines, catalog, k=k, exclude=exclude, active_slices=active_slices)
+        ids = catalog.ids[idx.clamp(min=0).long()]
+        idx, ids, y = idx.cpu().numpy(), ids.cpu().numpy(), torch.sigmoid(logit).cpu().numpy()
+        self.check_ids()
+        keep = idx >= 0
+        return [ids[l][keep[l]].tolist() for l in range(idx.shape[0])], [y[l][keep[l]].tolist() for l in range(idx.shape[0])]
 
     def save(self, sess, path):
         """All global variables incl. the Adam slots, under the TF variable names."""
@@ -2121,6 +2212,85 @@ class SASRec(GRU4Rec):
         T = int(self.cfg.max_time_len)
         R = B * (T - 1) + B * (T - 2) + B
         return ((R, 200), (R, 80), (2, B, T, T))
+
+
+class ItemCatalog(object):
+    """An item catalogue of a GRU4Rec / Caser model on the device, for recommend / recommend_async: the items' table rows
+    item_rows [N, Fi] (column 0 the item ids, strictly ascending -- PointLogStore.item_rows and PointSeqStore.item_rows are such
+    tables; checked once, here) and zcat [N, 200], the catalogue's half of fc1's pre-activation (score_catalog_build).  zcat
+    depends on the table, bn1 and fc1: the catalogue records model.weights_version at its build and refresh() -- which every
+    recommend call goes through -- rebuilds it when the counter has moved (train*, set_params, restore move it)."""
+
+    def __init__(self, model, item_rows):
+        if model.rank_unsupported is not None:
+            raise NotImplementedError("%s has no catalogue pass: %s" % (type(model).__name__, model.rank_unsupported))
+        rows = item_rows if torch.is_tensor(item_rows) else torch.from_numpy(np.ascontiguousarray(np.asarray(item_rows)))
+        rows = rows.to(device=model.device, dtype=torch.int32).contiguous()
+        Fi = int(model.cfg.item_fnum)
+        if rows.dim() != 2 or rows.shape[1] != Fi or rows.shape[0] == 0:
+            raise ValueError("item_rows has shape %s, expected [N, %d] with N > 0" % (tuple(rows.shape), Fi))
+        ids = rows[:, 0].contiguous()
+        if ids.numel() > 1 and not bool((ids[1:] > ids[:-1]).all().item()):
+            raise ValueError("item_rows: column 0 (the item ids) must be strictly ascending")
+        self.model, self.rows, self.ids, self.N = model, rows, ids, int(rows.shape[0])
+        self.zcat = torch.empty((self.N, 200), dtype=torch.float32, device=model.device)
+        self.version = None          # model.weights_version of the build; None: not built
+        self.builds = 0
+
+    def struct(self):
+        return _lib.Catalog(_ptr(self.rows), self.N, _ptr(self.zcat))
+
+    def refresh(self):
+        """zcat at the model's present weights, on the current stream: the whole table brought up to date first (every item row
+        is read), then a build if the weights have moved since the last one"""
+        m = self.model
+        m._flush_adam()
+        if self.version == m.weights_version:
+            return False
+        with m._Pin(m):
+            ws = m._workspace(1)[1]          # (score_catalog_build reads table, w and id_status of the state only)
+            st = m._state(ws)
+            cat = self.struct()
+            rc = m.lib.score_catalog_build(C.byref(m.cfg), C.byref(st), C.byref(cat), m._stream())
+        _lib.check(rc, "score_catalog_build")
+        self.version = m.weights_version
+        self.builds += 1
+        return True
+
+    def indices_of(self, item_ids):
+        """(catalogue index of each id, whether the catalogue holds it) for a device tensor of item ids"""
+        ids = item_ids.to(device=self.ids.device, dtype=torch.int32).contiguous()
+        pos = torch.searchsorted(self.ids, ids).clamp(max=self.N - 1)
+        return pos, self.ids[pos] == ids
+
+    def exclusions(self, exclude, L):
+        """exclude -- a list of L arrays of item ids, or a CSR pair (offsets [L + 1], ids) -- as score_catalog_lines_t takes it:
+        (excl_off int64 [L + 1], excl_idx int32) on the device, the ids mapped to catalogue indices (those the catalogue does not
+        hold dropped), ascending and without repeats within a line.  The mapping runs on the device."""
+        dev = self.ids.device
+        host = lambda x: np.asarray(x.cpu() if torch.is_tensor(x) else x)
+        if len(exclude) == 2 and not isinstance(exclude, list) and np.ndim(host(exclude[0])) == 1 and \
+                host(exclude[0]).size == L + 1:
+            off = (exclude[0] if torch.is_tensor(exclude[0]) else torch.from_numpy(np.ascontiguousarray(host(exclude[0])))).to(
+                device=dev, dtype=torch.int64)
+            ids = (exclude[1] if torch.is_tensor(exclude[1]) else torch.from_numpy(np.ascontiguousarray(host(exclude[1])))).to(dev)
+        else:
+            if len(exclude) != L:
+                raise ValueError("exclude must hold one array of item ids per line (%d), or be a CSR pair (offsets, ids)" % L)
+            parts = [host(x).reshape(-1).astype(np.int64) for x in exclude]
+            off = torch.from_numpy(np.concatenate([[0], np.cumsum([p.size for p in parts])]).astype(np.int64)).to(dev)
+            ids = torch.from_numpy(np.concatenate(parts) if parts else np.zeros((0,), dtype=np.int64)).to(dev)
+        n = int(ids.numel())
+        if n == 0:
+            return torch.zeros((L + 1,), dtype=torch.int64, device=dev), torch.zeros((1,), dtype=torch.int32, device=dev)
+        line = torch.searchsorted(off, torch.arange(n, device=dev, dtype=torch.int64), right=True) - 1
+        pos, found = self.indices_of(ids)
+        key = torch.unique(line[found] * self.N + pos[found].long())            # sorted: by line, then by index
+        excl_off = torch.searchsorted(key, torch.arange(L + 1, device=dev, dtype=torch.int64) * self.N)
+        excl_idx = (key % self.N).to(torch.int32)
+        if excl_idx.numel() == 0:
+            excl_idx = torch.zeros((1,), dtype=torch.int32, device=dev)
+        return excl_off.contiguous(), excl_idx.contiguous()
 
 
 MODELS = {"SCORE": SCORE, "RIA": RIA, "RCA": RCA, "SCORE_USER": SCORE_USER, "SCORE_ITEM": SCORE_ITEM, "RRN": RRN, "GCMC": GCMC,
