@@ -450,7 +450,7 @@ typedef struct {
   float beta1, beta2, eps;
   int32_t reserved2;
   const int32_t* id_status;       /* optional guard word (score_guard_t.id_status).  While it is non-zero:
-                                     score_adam_touched(_rows) applies nothing -- its rows go back to state 1 with
+                                     score_adam_touched applies nothing -- its rows go back to state 1 with
                                      row_step = step - 1 (they were current up to there), alpha_ring is not written --
                                      and the catch-up entry points replay nothing (the steps they would replay may be
                                      ones that were suppressed): the table, m and v stay as the last applied step left them */
@@ -469,12 +469,6 @@ int score_adam_touched_and_dense(const score_adam_table_t* t, uint32_t step, flo
  * row_step (the batch's rows were brought up to `upto` before that pass); a row that was in state 0 -- m = v = 0: its owed
  * updates are identities and any count is right for it -- gets row_step = upto, which keeps it inside the ring. */
 int score_adam_unmark(const score_adam_table_t* t, uint32_t upto, void* stream);
-/* score_adam_touched driven by a row LIST instead of a scan of the state bytes: rows[0 .. *n_rows_dev) (device int32,
- * the count is read on the device; max_rows bounds it for the launch) names every row that may be in state 2 -- what
- * score_index_plan(dedup = 2) leaves in the workspace (plan_unique_rows / plan_meta[0]).  Entries not in state 2 are
- * skipped (the dummy row 0); rows in state 2 that the list misses would be left for score_adam_touched. */
-int score_adam_touched_rows(const score_adam_table_t* t, const int32_t* rows, const int32_t* n_rows_dev, int64_t max_rows,
-                            uint32_t step, float alpha, void* stream);
 /* every value of ids[0..n_ids) that names a live row (values outside [0, n_rows) are ignored, so a whole flat batch
  * buffer may be passed): replay the zero-gradient steps row_step+1 .. upto of that row */
 int score_adam_catchup_ids(const score_adam_table_t* t, const int32_t* ids, int64_t n_ids, uint32_t upto, void* stream);
@@ -525,9 +519,7 @@ typedef struct {
                            bit 12 (4096) = NO second stream: everything score_forward / score_backward would fork onto
                            the context's side stream runs on `stream`, in launch order (same results bit for bit; what
                            a suspected stream race is compared against -- score_amd.model inlines its own streams too);
-                           bit 14 (16384) = (layer-by-layer pass) the recurrences' weight-gradient products at the END of the
-                           launch stream's chain, behind the row scatter (the round-5 placement), instead of on the side stream
-                           beside the co-attention backward and the scatter (round 6; same bits); bit 13 (8192) =
+                           bit 14 (16384) = unused, ignored; bit 13 (8192) =
                            (SCORE_MODEL_GRU4REC) the two stacked recurrences one layer per launch with the projection GEMM between
                            them (the composed form: what H outside {16, 32, 64} runs anyway) instead of csrc/gru_stack.hip;
                            (SCORE_MODEL_DEEMS) its two recurrences one launch per side instead of one grouped launch;
@@ -565,16 +557,21 @@ typedef struct {
                            to loss[0] / loss[1] and the bits to loss[3], so whoever reads the loss learns of it;
                            score_id_status() is the synchronous query.  Ids of time slices >= active_slices are never
                            dereferenced and not checked.                                                         */
-  void* grads_done_event; /* optional hipEvent_t (score_backward): the pass's last four launches -- slab reduce, folded attention
-                           layer's gradient, column sums: everything that FINISHES grad_w -- then run on the context's side
-                           stream behind the weight-gradient products, and this event is recorded behind them.  grad_table is
-                           complete on `stream` when score_backward returns as before; grad_w only once the event has fired:
-                           the caller runs what needs the row gradients alone (score_adam_touched) on `stream` meanwhile and
-                           makes `stream` wait for the event before score_adam on the dense variables (or anything else that
-                           reads grad_w).  Round 6: the finishers are forked in FRONT of the row scatter (beside it), so the
-                           event says nothing about the scatter -- which reads the co-attention weights: the dense variables
-                           may only be updated behind the event AND behind `stream`'s own launches of the pass (i.e. on `stream`,
-                           or on a stream that also waits for stage boundary 4).  NULL: everything on `stream`, as before. */
+  void* grads_done_event; /* optional hipEvent_t (score_backward): everything that FINISHES grad_w -- the slab reduce, the folded
+                           attention layer's gradient, the column sums -- runs on the context's side stream, and this event is
+                           recorded behind it.  Where the finishers are forked:
+                             - the layer-by-layer pass under scatter_mode 0 (or 1) with weight-gradient products queued: behind
+                               target_bwd_kernel, the last launch that feeds them, in FRONT of the row scatter, which runs
+                               beside them (and beside the products) on `stream`;
+                             - otherwise -- scatter_mode 2, the row-sharded pass, or a pass with no queued products: behind the
+                               end-of-pass products, which follow the row scatter on `stream`;
+                             - the per-sample whole-model pass: with the products, behind the backward kernel, in front of the
+                               row scatter.
+                           grad_table is complete on `stream` when score_backward returns; grad_w only once the event has fired.
+                           The event says NOTHING about the row scatter, and the scatter reads the co-attention weights: the dense
+                           variables may only be updated (and grad_w read) behind the event AND behind `stream`'s own launches of
+                           the pass -- on `stream`, after making it wait for the event, or on another stream that waits for the
+                           event and for stage boundary 4.  NULL: everything on `stream`. */
   void* loss_done_event;  /* optional hipEvent_t (score_forward): the loss reduction (one workgroup: loss[0..3] from the per-sample
                            terms and the L2 partial sums) then runs on the context's side stream behind the head, and this event is
                            recorded behind it -- the head's successor on `stream` (score_backward's first launch) no longer queues
@@ -616,11 +613,11 @@ int score_persample_form(const score_config_t* cfg, const score_state_t* st, int
 
 /* Index plan of a batch (depends on the indices only; run it before score_backward, on
  * any stream ordered before it).  Radix-sorts all R*B row uses by (owner shard, row).
- * n_shards > 1 (table row-sharded, owner = row % n_shards) or dedup != 0 additionally
+ * n_shards > 1 (table row-sharded, owner = row % n_shards) or dedup == 1 additionally
  * de-duplicates them: unique rows grouped by owner -> what to request from each shard --
  * and writes the six index tensors remapped to unique positions, so the same kernels run
- * on the gathered [U, D] mini-table.  dedup == 2 (one shard): only the unique row list and its count are written
- * (plan_unique_rows, plan_meta[0]; no remapped tensors) -- the rows score_adam_touched_rows updates.  Replaces nothing in the reference (it has no multi-device code);
+ * on the gathered [U, D] mini-table.  dedup is 0 or 1 (SCORE_E_BADARG otherwise).
+ * Replaces nothing in the reference (it has no multi-device code);
  * it is the index-routing step BASELINE.json's north_star asks for. */
 int score_index_plan(const score_config_t* cfg, const score_state_t* st, const score_batch_t* batch,
                      int32_t n_shards, int32_t dedup, void* stream);
@@ -676,8 +673,8 @@ int score_forward(const score_config_t* cfg, const score_state_t* st, const scor
  * stream, on the same stream and context: otherwise the pass records one event more at its start).
  * stage_events: null, or SIX handles: [0] start, [1] after the head, [2] after the temporal
  * attention, [3] after the GRUs, [4] after the co-attention/embedding scatter, [5] after the
- * weight-gradient products (all X^T dY of the pass run here, as grouped launches; with score_state_t.grads_done_event the
- * event sits behind the products, the finishers that follow them run on the side stream).
+ * weight-gradient products (all X^T dY of the pass, as grouped launches: where they ran on the side stream beside the scatter,
+ * behind `stream`'s wait for them; the finishers of grad_w are a separate matter, see score_state_t.grads_done_event).
  * grad_w between the two calls: score_backward's zero fill / first writers of grad_w run on the context's side stream, forked
  * where score_forward of the same step began -- i.e. they may execute any time after score_forward was CALLED.  Nothing may
  * read or write grad_w on `stream` (or anywhere else) between score_forward and the completion of score_backward of the same

@@ -263,7 +263,6 @@ _SIGS = {
     "score_adam_touched_and_dense": [C.POINTER(AdamTable), C.c_uint32, C.c_float, c_f, c_f, c_f, c_f, C.c_int64, C.c_int64,
                                      C.c_float, C.c_void_p, C.c_void_p],
     "score_adam_unmark": [C.POINTER(AdamTable), C.c_uint32, C.c_void_p],
-    "score_adam_touched_rows": [C.POINTER(AdamTable), c_i, c_i, C.c_int64, C.c_uint32, C.c_float, C.c_void_p],
     "score_adam_catchup_ids": [C.POINTER(AdamTable), c_i, C.c_int64, C.c_uint32, C.c_void_p],
     "score_adam_catchup_ids_through": [C.POINTER(AdamTable), c_i, C.c_int64, C.c_uint32, C.c_float, C.c_void_p],
     "score_adam_catchup_rows": [C.POINTER(AdamTable), C.c_int64, C.c_int64, C.c_uint32, C.c_void_p],

@@ -632,14 +632,14 @@ static int side_stream(const score_state_t* st, SideStream** out) {
 enum {
   DF_GRU_STEPWISE = 1, DF_HEAD_FUSED_ANY_B = 2, DF_GRU_F32_REC = 4, DF_NO_PANEL = 8, DF_PANEL_DX = 16, DF_SORT_LIB = 32,
   DF_HEAD_UNFUSED = 64, DF_ATTN_UNFUSED = 128, DF_SORT_OWN = 256, DF_NO_PS = 512, DF_PS_FWD_ONLY = 1024, DF_PS_BWD_ONLY = 2048,
-  DF_ONE_STREAM = 4096, DF_G4R_COMPOSED = 8192, DF_PRODUCTS_LATE = 16384, DF_COATTN_ALL_ROWS = 32768,
+  DF_ONE_STREAM = 4096, DF_G4R_COMPOSED = 8192, DF_COATTN_ALL_ROWS = 32768,
   DF_COATTN_META_AHEAD = 65536
 };
 // (DF_G4R_COMPOSED / Flags.g4r_composed, bit 13, reads "one recurrence per launch": GRU4Rec's composed form, and DEEMS's two
 //  recurrences as one launch per side instead of one grouped launch)
 struct Flags {
   bool gru_stepwise, head_fused_any_b, gru_f32_rec, no_panel, panel_dx, sort_lib, head_unfused, attn_unfused, sort_own, no_ps,
-      ps_fwd_only, ps_bwd_only, one_stream, g4r_composed, products_late, coattn_all_rows, coattn_meta_ahead;
+      ps_fwd_only, ps_bwd_only, one_stream, g4r_composed, coattn_all_rows, coattn_meta_ahead;
 };
 static inline Flags flags_of(const score_state_t* st) {
   auto on = [st](int bit) { return (st->debug_flags & bit) != 0; };
@@ -648,7 +648,7 @@ static inline Flags flags_of(const score_state_t* st) {
   o.no_panel = on(DF_NO_PANEL); o.panel_dx = on(DF_PANEL_DX); o.sort_lib = on(DF_SORT_LIB); o.sort_own = on(DF_SORT_OWN);
   o.head_unfused = on(DF_HEAD_UNFUSED); o.attn_unfused = on(DF_ATTN_UNFUSED); o.no_ps = on(DF_NO_PS);
   o.ps_fwd_only = on(DF_PS_FWD_ONLY); o.ps_bwd_only = on(DF_PS_BWD_ONLY); o.one_stream = on(DF_ONE_STREAM);
-  o.g4r_composed = on(DF_G4R_COMPOSED); o.products_late = on(DF_PRODUCTS_LATE); o.coattn_all_rows = on(DF_COATTN_ALL_ROWS);
+  o.g4r_composed = on(DF_G4R_COMPOSED); o.coattn_all_rows = on(DF_COATTN_ALL_ROWS);
   o.coattn_meta_ahead = on(DF_COATTN_META_AHEAD);
   return o;
 }
@@ -1357,7 +1357,7 @@ extern "C" int score_index_plan(const score_config_t* cfg, const score_state_t* 
                                 int32_t n_shards, int32_t dedup, void* stream) {
   Dims d;
   SCORE_TRY(make_dims(cfg, &d));
-  if (!st || !bt || !st->workspace || bt->B <= 0 || n_shards < 1 || n_shards > 64) return SCORE_E_BADARG;
+  if (!st || !bt || !st->workspace || bt->B <= 0 || n_shards < 1 || n_shards > 64 || (dedup != 0 && dedup != 1)) return SCORE_E_BADARG;
   const int TA = active_T(d, bt);
   const int B = bt->B, BT = B * TA;
   WS w;
@@ -1404,7 +1404,7 @@ extern "C" int score_index_plan(const score_config_t* cfg, const score_state_t* 
     G(score_launch_plan_unique(ra, keys_out, vals_out, off + 1, keys_in, reinterpret_cast<uint32_t*>(ws + w.uid),
                                vals_in, reinterpret_cast<int32_t*>(ws + w.unique_rows),
                                reinterpret_cast<int32_t*>(ws + w.meta), n_shards, shift, ws + w.sort_temp,
-                               (size_t)w.sort_temp_bytes, s, n_shards > 1 || dedup != 2));
+                               (size_t)w.sort_temp_bytes, s));
   }
   return 0;
 }
@@ -2484,10 +2484,10 @@ int bwd_close(const Pass& c, BwdState* b) {
   // (profiles/r05_cfg3_sequence.txt), instead of at the END of the launch stream's chain in front of the table's touched-row update
   // (125 us there beside the look-ahead catch-up; 65 us alone).  The join recorded behind them is the one the launch stream waits
   // for behind the scatter (below), so whatever the caller queues next on the launch stream is also behind their last read of the
-  // workspace.  Flags.products_late (debug_flags bit 14): the round-5 placement (A/B).  The sharded path keeps that placement too:
-  // its caller runs the gradient exchange on streams of its own beside the scatter (score_amd/dist.py).
+  // workspace.  The sharded path (scatter_mode 2) keeps the round-5 placement, at the end of the launch stream's chain: its caller
+  // runs the gradient exchange on streams of its own beside the scatter (score_amd/dist.py).  So does a pass with nothing queued.
   ReduceGroup rg; rg.n = rg.blocks = 0;
-  const bool products_early = st->scatter_mode != 2 && !c.fl.products_late && gq.n > 0;
+  const bool products_early = st->scatter_mode != 2 && gq.n > 0;
   // ... and with them the finishers of the dense gradient (slab reduce, column sums), when the caller takes them on the side stream
   // (score_state_t.grads_done_event): forked behind target_bwd_kernel, the last launch that feeds them, instead of behind the row
   // scatter -- they ran beside the table's touched-row update, 58 + 28 us there against 20 + 12 alone, with the dense ApplyAdam and

@@ -206,8 +206,7 @@ struct PullArgs {
 struct PlanRemapArgs { int32_t* out[6]; int F[6]; int K; int T, TA; };
 int score_launch_plan_unique(const PlanRemapArgs& ra, const uint32_t* keys, const uint32_t* vals, int64_t n,
                              uint32_t* flags_scratch, uint32_t* uid, uint32_t* unique_keys, int32_t* unique_rows,
-                             int32_t* meta, int G, int shift, void* temp, size_t temp_bytes, hipStream_t s,
-                             bool remap = true);
+                             int32_t* meta, int G, int shift, void* temp, size_t temp_bytes, hipStream_t s);
 int score_scan_temp_bytes(int64_t n, size_t* bytes);
 int score_plan_temp_bytes(int64_t n, int end_bit, size_t* bytes);
 int score_launch_plan(const PlanFillArgs& a, int key_bits, uint32_t* keys_in, uint32_t* vals_in, uint32_t* keys_out,

@@ -295,15 +295,10 @@ class SCOREBASE(object):
         # update (cfg-3: ~40 us off the launch stream); below, the step is bound by the host's launch calls and the table's and
         # the dense variables' updates stay ONE launch behind finishers on the launch stream
         self.overlap_finishers_min_rows = 6144       # (the CCMR shape's 7,600 rows gain 1.7 % from it, the Tmall default's 2,200 lose 4 %)
-        self.dense_adam_on_side = True       # (with the finishers overlap) the dense variables' ApplyAdam on the host's side stream
         self.loss_on_side = True            # the loss reduction of a training step on the engine's side stream (score_state_t.loss_done_event)
         self._early_loss = None      # set for the length of a train() call: the loss copied out right behind the forward pass
         self._early_loss_state = {"stream": None, "host": None, "event": None}
-        self._sweep_st = None        # stream of the window slice when it runs beside the forward pass (adam_sweep_at = "f1")
-        self._fwd_stage_event = None
         self._pinned_stream = self._pinned_handle = None
-        self._row_list = None
-        self._dense_pending = None      # event behind the dense variables' ApplyAdam when it ran on the side stream (apply_adam)
         self._ps_form = {}
         self._train_stream = None        # the stream the last forward_backward ran on (who else must wait for side-stream updates)
         self._plan_ready = None          # (batch, event, workspace, active slices) of an index plan launched a step ahead
@@ -323,12 +318,10 @@ class SCOREBASE(object):
         self.plan_two_workspaces = "auto"
         self._plan_events = [None, None]
         self._plan_stream = None
-        self._fin_early = False
         self._ev_loss_dev = None
         self.fast_step = True           # train / train_async: the steady-state step of the per-sample form as one library call (_train_step_fast)
         self._step_args = self._step_T = self._step_side = None
         self._pb_cache = {}
-        self._ev_dense = None
         self.w = torch.zeros((self.n_w,), **f32)
         self._alloc_optimizer()
         self._ws = {}              # (B, slot) -> (layout, buffer), least recently used first
@@ -371,15 +364,13 @@ class SCOREBASE(object):
         # (threads: the walk is one cache miss per boxed int, so it scales with cores until the memory system is busy --
         #  cfg-3 batch on the GPU box's host: 8.9 ms with 1 thread, 2.5 with 4, 1.6 with 8, 1.35 with 16)
         # where the time-tiled optimizer's window slice starts: "2" (stage boundary 2 of the backward pass, beside the
-        # recurrence), "1" / "3" / "4", "plan" (behind the occurrence sort), "f1" (behind the fused gather, on a stream of its
-        # own); "auto": "2" for the per-sample form (what its one-call step queues) and "plan" for the layer-by-layer pass --
-        # since round 6 moved the recurrences' weight-gradient products beside the scatter, the backward pass has no slack
-        # left for a 100-us HBM-bound scan beside its input-gradient product (cfg-3, one box, interleaved: plan 892 - 895 k
-        # samples/s, "2" 884 - 888 k, "1" 874 - 886 k, "3" 858 - 864 k, "4" 854 - 861 k, "f1" 850 k: profiles/r06_probes.md);
-        # the touched-row update from the plan's unique-row list instead of a state-byte scan
-        # (measured +8 us net: off).  Both change WHERE work runs, never a result (tests/test_gpu_adam_tiled.py)
+        # recurrence), "1" / "3" / "4", "plan" (behind the occurrence sort); "auto": "2" for the per-sample form (what its
+        # one-call step queues) and "plan" for the layer-by-layer pass -- since round 6 moved the recurrences' weight-gradient
+        # products beside the scatter, the backward pass has no slack left for a 100-us HBM-bound scan beside its
+        # input-gradient product (cfg-3, one box, interleaved: plan 892 - 895 k samples/s, "2" 884 - 888 k, "1" 874 - 886 k,
+        # "3" 858 - 864 k, "4" 854 - 861 k: profiles/r06_probes.md).  It changes WHERE work runs, never a result
+        # (tests/test_gpu_adam_tiled.py)
         self.adam_sweep_at = "auto"
-        self.adam_touched_list = False
         self.feed_threads = int(os.environ.get("SCORE_FEED_THREADS", str(max(1, min(16, _usable_cpus())))))
         self._stage, self._stage_lock = {}, threading.Lock()
         self._init_params(seed)
@@ -484,11 +475,9 @@ class SCOREBASE(object):
         self._tbl, self._tiled, self._tiled_ready = t, None, False
         self.weights_version += 1
 
-    # the flat dense variables and their Adam slots.  Their ApplyAdam may have run on the side stream (apply_adam: behind the dense
-    # gradient's finishers, beside the table's touched-row update): whoever reads or writes them through here waits for it first
+    # the flat dense variables (a property only for the setter: replacing the buffer moves the weights)
     @property
     def w(self):
-        self._join_dense()
         return self._w
 
     @w.setter
@@ -496,35 +485,19 @@ class SCOREBASE(object):
         self._w = t
         self.weights_version += 1
 
-    @property
-    def w_m(self):
-        self._join_dense()
-        return self._w_m
-
-    @w_m.setter
-    def w_m(self, t):
-        self._w_m = t
+    # where the window slice of the time-tiled optimizer starts (see __init__)
+    SWEEP_AT = ("auto", "plan", "1", "2", "3", "4")
 
     @property
-    def w_v(self):
-        self._join_dense()
-        return self._w_v
+    def adam_sweep_at(self):
+        return self._adam_sweep_at
 
-    @w_v.setter
-    def w_v(self, t):
-        self._w_v = t
-
-    def _join_dense(self):
-        ev, self._dense_pending = self._dense_pending, None
-        if ev is not None:
-            self._grads_pending = None          # (the update ran behind the finishers: they are through as well)
-            cur = self._cur()
-            cur.wait_event(ev)
-            # (touched from inside a `with torch.cuda.stream(x)` block of the caller: x waits above, and so must the stream the
-            #  training sequence runs on -- its next forward pass reads the variables too, and the pending event is gone by then)
-            own = self._train_stream
-            if own is not None and own.cuda_stream != cur.cuda_stream:
-                own.wait_event(ev)
+    @adam_sweep_at.setter
+    def adam_sweep_at(self, v):
+        s = str(v)                          # (bench.py --set adam_sweep_at=3 arrives as an int)
+        if s not in self.SWEEP_AT:
+            raise ValueError("adam_sweep_at must be one of %s, not %r" % (", ".join(self.SWEEP_AT), v))
+        self._adam_sweep_at = s
 
     @property
     def w_g(self):
@@ -565,11 +538,11 @@ class SCOREBASE(object):
         return self._tbl_v
 
     def __del__(self):
-        # Work this object queued on its OWN streams (the dense variables' ApplyAdam and the index plan on the host's side stream,
-        # the window slice, the early loss copy) may still be running: the caching allocator knows a tensor only by the stream
+        # Work this object queued on its OWN streams (the index plan and the window slice on the host's side stream, the early
+        # loss copy) may still be running: the caching allocator knows a tensor only by the stream
         # it was allocated on and would hand the dying model's buffers to the next allocation while those kernels still write
         # them (seen as two "identical" models diverging by a few ulp when one of them inherited such a block).  Wait first.
-        for st in (getattr(self, "_side", None), getattr(self, "_sweep_st", None), getattr(self, "_plan_stream", None),
+        for st in (getattr(self, "_side", None), getattr(self, "_plan_stream", None),
                    (getattr(self, "_early_loss_state", None) or {}).get("stream")):
             try:
                 if st is not None:
@@ -709,7 +682,6 @@ class SCOREBASE(object):
             self.table_flags.clamp_(max=1)
         self._flags_marked = False
         self._row_grads = False
-        self._row_list = None        # (the unique-row list of a plan describes THAT backward pass's marks only)
 
     def _begin_row_grads(self):
         self._drop_row_marks()
@@ -754,9 +726,8 @@ class SCOREBASE(object):
         self._ws[key] = ent          # most recently used last
         return ent
 
-    def _state(self, ws, joined=True):
-        # (the property: joins a dense ApplyAdam still running on a side stream; joined = False: the caller orders the streams itself)
-        w = self.w if joined else self._w
+    def _state(self, ws):
+        w = self._w
         key = (ws.data_ptr(), self._tbl.data_ptr(), w.data_ptr(), self.table_flags.data_ptr())
         ent = self._st_cache.get(key)
         if ent is None:
@@ -904,8 +875,7 @@ class SCOREBASE(object):
         return buf[off:off + n].view(*shape)
 
     # ------------------------------------------------------------------ forward / backward / update
-    def _forward(self, db, reg_lambda, keep_prob, masks, gather_event=None, sweep=False, stage_event=None,
-                 loss_event=None):
+    def _forward(self, db, reg_lambda, keep_prob, masks, gather_event=None, sweep=False, loss_event=None):
         lay, ws = self._workspace(db.B)
         st = self._state(ws)
         if loss_event is not None:
@@ -942,15 +912,9 @@ class SCOREBASE(object):
                     raise ValueError("dropout masks must be shaped %s" % ", ".join(str(list(w)) for w in want))
                 st.drop_mask2 = m2.data_ptr()
         seed = (self._drop_seed * 0x9E3779B1 + self.step * 0x85EBCA77) & 0xFFFFFFFFFFFFFFFF
-        events = self.fwd_events
-        if stage_event is not None:          # (k, event): score_forward records it at its stage boundary k
-            events = list(events) if events else [None] * 5
-            if events[stage_event[0]] is None:
-                events[stage_event[0]] = stage_event[1]
-            self._fwd_stage_event = events[stage_event[0]]
         rc = self.lib.score_forward(C.byref(self.cfg), C.byref(st), C.byref(db.struct), float(reg_lambda),
                                     float(keep_prob), _ptr(m0), _ptr(m1), C.c_uint64(seed),
-                                    self._event_array(events), self._stream())
+                                    self._event_array(self.fwd_events), self._stream())
         _lib.check(rc, "score_forward")
         self._keep = (m0, m1, m2)
         return lay, ws, st
@@ -972,12 +936,12 @@ class SCOREBASE(object):
         cur = self._cur()
         self._train_stream = cur
         # debug_flags bit 12 (4096, score_hip.h): NO second stream anywhere -- the engine's forks, the index plan, the window
-        # slice, the look-ahead, the dense ApplyAdam and the early loss copy all run on the launch stream, in launch order
+        # slice, the look-ahead and the early loss copy all run on the launch stream, in launch order
         # (tests/test_gpu_model.py compares the overlap modes with it bit for bit; the first thing to try on a suspected race)
         inline = bool(int(self.debug_flags) & 4096)
         if inline != self._inline_on or (inline and self._side is not None and self._side.cuda_stream != cur.cuda_stream):
             torch.cuda.synchronize(self.device)
-            self._side = self._sweep_st = self._early_loss_state["stream"] = None
+            self._side = self._early_loss_state["stream"] = None
             self._plan_ready = None
             self._inline_on = inline
         if self.scatter_mode == 0:
@@ -993,18 +957,12 @@ class SCOREBASE(object):
         if early:
             ev_start = self._rec("start", cur)
         # time-tiled optimizer: this step's slice of the table (rows nobody in the batch touches: any time between the
-        # batch rows' catch-up and the touched-row update will do).  "f1": behind the fused gather, i.e. beside the forward
-        # recurrence, which is matrix-bound and fills half the CUs; 1 .. 4: at that stage boundary of the backward pass
+        # batch rows' catch-up and the touched-row update will do).  "plan": behind the occurrence sort; 1 .. 4: at that stage
+        # boundary of the backward pass
         self._ps_last = self.persample_form(db.B, db.active_slices)
-        sweep_at = str(self.adam_sweep_at)
-        if sweep_at not in ("plan", "f1", "1", "2", "3", "4"):
-            sweep_at = "2" if self._ps_last else "plan"      # ("auto"; an unknown value must not leave the window slice unlaunched)
-        fwd_stage = None
-        if sweep_at == "f1" and self._tiled_on():
-            if self._ev_stage is None:
-                self._ev_stage = self._ev_new()
-                self._ev_stage.record(cur)              # materialise the hipEvent_t
-            fwd_stage = (1, self._ev_stage)
+        sweep_at = self.adam_sweep_at
+        if sweep_at == "auto":
+            sweep_at = "2" if self._ps_last else "plan"
         # the loss reduction (one workgroup, no reader inside the step) on the engine's side stream: score_backward's first
         # launch then follows the head directly (score_state_t.loss_done_event; score_backward joins that stream, so the
         # loss is final on this stream behind the pass)
@@ -1017,20 +975,10 @@ class SCOREBASE(object):
             # (train() reads the loss on the host behind this event -- from pinned memory the per-sample kernel wrote, or through a
             #  copy on another stream that only waits for it: an ordinary event then, with its system-scope release; train_async:
             #  it only orders streams, and a device event does)
-            host_reads = self._early_loss is not None
-            if host_reads:
-                if self._ev_loss is None:
-                    self._ev_loss = torch.cuda.Event()
-                    self._ev_loss.record(cur)               # materialise the hipEvent_t
-                ev_loss = self._ev_loss
-            else:
-                if self._ev_loss_dev is None:
-                    self._ev_loss_dev = self._ev_new()
-                    self._ev_loss_dev.record(cur)
-                ev_loss = self._ev_loss_dev
+            ev_loss = self._ensure_ev("_ev_loss" if self._early_loss is not None else "_ev_loss_dev")
         lay, ws, st = self._forward(db, reg_lambda, keep_prob, dropout_masks,
                                     gather_event=self._ev_gather if (self.scatter_mode == 0 and not early) else None,
-                                    sweep=True, stage_event=fwd_stage, loss_event=ev_loss)
+                                    sweep=True, loss_event=ev_loss)
         if self._early_loss is not None and st.loss_host:
             self._early_loss["event"] = ev_loss
         elif self._early_loss is not None:
@@ -1046,20 +994,14 @@ class SCOREBASE(object):
             with torch.cuda.stream(el["stream"]), self._Unpin(self):
                 el["host"].copy_(ws[lay.loss:lay.loss + 4], non_blocking=True)
                 el["event"] = self._rec("early_loss", el["stream"])
-        if fwd_stage is not None and self._pending_sweep is not None:
-            if self._sweep_st is None:
-                self._sweep_st = cur if inline else torch.cuda.Stream(device=self.device)      # (its own stream: the occurrence sort must not queue behind it)
-            self._sweep_st.wait_event(self._fwd_stage_event)
-            self._launch_sweep(self._sweep_st)
         if self.scatter_mode == 0:
             # occurrence sort for the pull-form scatter: depends on the indices only.  It runs on a side
             # stream from the start of the forward (see above), under the gather / GRUs / attention / head and
             # the first half of the backward, and score_backward waits for it just before the row scatter
             # (its workspace regions are its own; the previous step's scatter, their last reader, is behind
             # the event the side stream waits for)
-            want_list = self._tiled_on() and bool(self.adam_touched_list)
             pr, self._plan_ready = self._plan_ready, None
-            plan_here = pr is not None and pr[0] is db and pr[3] == db.active_slices and not want_list and (
+            plan_here = pr is not None and pr[0] is db and pr[3] == db.active_slices and (
                 pr[2] == ws.data_ptr() or pr[2] == self._plan_buffer(db.B, 1))
             if plan_here:
                 if pr[2] != ws.data_ptr():
@@ -1068,21 +1010,14 @@ class SCOREBASE(object):
                 # row scatter (_plan_ahead): since the per-sample kernels, the six launches of the sort (~110 us with their gaps)
                 # are longer than the forward and backward kernels they used to hide under
                 plan_done = pr[1]
-                row_list = None
                 st.plan_done_event = C.c_void_p(plan_done.cuda_event)
                 self._plan_done = plan_done
                 early = None
         if self.scatter_mode == 0 and early is not None:
             self._side.wait_event(ev_start if early else self._ev_gather)
-            # (dedup = 2: also the list of the batch's unique rows, for score_adam_touched_rows -- the touched-row update
-            #  driven by that list instead of a scan of the table's state bytes.  OFF by default: measured on one box,
-            #  alternating runs (tools/ab_env.sh), the update itself is 8 - 10 us shorter but the three extra plan kernels
-            #  on the side stream cost the input projections / recurrence beside them 16 - 18 us: 1.306 vs 1.298 ms/step.
-            #  model.adam_touched_list = True turns it on.)
             # (the side stream is handed to the call: entering and leaving a `with torch.cuda.stream(...)` block was ~10 us)
-            _lib.check(self.lib.score_index_plan(C.byref(self.cfg), C.byref(st), C.byref(db.struct), 1,
-                                                 2 if want_list else 0, self._side_handle), "score_index_plan")
-            row_list = (lay, ws) if want_list else None
+            _lib.check(self.lib.score_index_plan(C.byref(self.cfg), C.byref(st), C.byref(db.struct), 1, 0, self._side_handle),
+                       "score_index_plan")
             plan_done = self._rec("plan", self._side)
             st.plan_done_event = C.c_void_p(plan_done.cuda_event)
             self._plan_done = plan_done                  # keep the event alive until the backward has run
@@ -1097,7 +1032,6 @@ class SCOREBASE(object):
             self._launch_sweep(self._side)
         if self.scatter_mode == 0:
             self._begin_row_grads()         # the pull kernels mark what they write; no zero fill
-            self._row_list = row_list       # (the rows they will mark, listed by the plan)
         else:
             self._drop_row_marks()
             self.table_g.zero_()
@@ -1105,40 +1039,29 @@ class SCOREBASE(object):
         ev_sweep_start = None
         if sweep_at in ("1", "2", "3", "4"):
             # the slice starts at a stage boundary of the backward pass (score_backward records the event there)
-            if self._ev_stage is None:
-                self._ev_stage = self._ev_new()
-                self._ev_stage.record(cur)              # materialise the hipEvent_t
             events = list(events) if events else [None] * 6
             k = int(sweep_at)
             if events[k] is None:
-                events[k] = self._ev_stage
+                events[k] = self._ensure_ev("_ev_stage")
             ev_sweep_start = events[k]
         self._b4_recorded = None
         self._b4_any = None
         if self._look_ahead and self.scatter_mode == 0 and (self._tiled_on() or self.plan_ahead):
             # boundary 4 (the row scatter has marked every row that gets this step's gradient): apply_adam(next_batch=)
             # starts the next batch's catch-up there, on the side stream
-            if self._ev_b4 is None:
-                self._ev_b4 = self._ev_new()
-                self._ev_b4.record(cur)
             events = list(events) if events else [None] * 6
             if events[4] is None:
-                events[4] = self._ev_b4
+                events[4] = self._ensure_ev("_ev_b4")
             self._b4_recorded = events[4]
             self._b4_any = events[4]
         self._join_grads()                    # (a previous pass's finishers: they wrote the buffer this pass writes)
         if (self.scatter_mode == 0 and not self._use_dev_scalars and not self._graph_on and side_ok
                 and (self._tiled_on() or self.persample_form(db.B, db.active_slices))):
-            if self._ev_grads is None:
-                self._ev_grads = self._ev_new()
-                self._ev_grads.record(cur)              # materialise the hipEvent_t
-            st.grads_done_event = C.c_void_p(self._ev_grads.cuda_event)
-            self._grads_pending = self._ev_grads
-            # (score_backward then forks the finishers in FRONT of the row scatter, csrc/engine.hip "fin_early": the dense variables'
-            #  update may not follow them on another stream any more -- the scatter reads the co-attention weights)
-            self._fin_early = not self._ps_last and not (int(self.debug_flags) & 16384)
-        else:
-            self._fin_early = False
+            # (score_backward forks the finishers in FRONT of the row scatter, csrc/engine.hip "fin_early": the dense variables'
+            #  update may not follow them on another stream -- the scatter reads the co-attention weights; apply_adam runs it on
+            #  the launch stream behind _join_grads)
+            self._grads_pending = self._ensure_ev("_ev_grads")
+            st.grads_done_event = C.c_void_p(self._grads_pending.cuda_event)
         rc = self.lib.score_backward(C.byref(self.cfg), C.byref(st), C.byref(db.struct), float(keep_prob),
                                      _ptr(self._w_g), _ptr(self.table_g), self._event_array(events),
                                      self._stream())
@@ -1179,46 +1102,12 @@ class SCOREBASE(object):
             if not self._ps_last:
                 side_work()
             if self._tiled_on() and self._row_grads:
-                if self._grads_pending is not None:
-                    # the dense gradient's finishers are still running on the side stream: the table's touched rows (row
-                    # gradients only) first, the dense variables behind the finishers' event -- on the host's side stream
-                    # (idle by now: the look-ahead catch-up was started at boundary 4), so that the launch stream goes from the
-                    # touched rows straight into the next step; whoever touches the dense variables next waits (self.w)
-                    if self._ps_last:
-                        # (the per-sample form: ONE launch for the touched rows and the dense variables, behind the finishers' event --
-                        #  they end before the row scatter does, tools/kernel_sequence.sh)
-                        self._join_grads()
-                        if not self._adam_table_tiled(lr, dense=(reg_lambda,)):
-                            self.adam_dense(lr, reg_lambda)
-                        side_work()
-                        self.adam_advance()
-                        return
-                    if self._fin_early:
-                        # round 6: the finishers ran beside the scatter and are through by now -- the touched rows and the dense
-                        # variables in ONE launch on the launch stream, behind the scatter (no stream hop in front of the next pass)
-                        self._join_grads()
-                        if not self._adam_table_tiled(lr, dense=(reg_lambda,)):
-                            self.adam_dense(lr, reg_lambda)
-                        self.adam_advance()
-                        return
-                    self._adam_table_tiled(lr)
-                    # (the per-sample form: on the launch stream.  There the finishers are forked right behind the backward KERNEL, i.e.
-                    #  in front of the row scatter -- and pull_kernel reads the co-attention weights: a dense update behind the
-                    #  finishers' event alone, on another stream, races with it.  That was the ulp drift of two identical models under
-                    #  tests/test_gpu_bad_ids.py earlier in round 5.  The layer-by-layer pass forks its finishers behind the scatter.)
-                    side = self._side if (self.dense_adam_on_side and not self._ps_last) else None
-                    if side is not None:
-                        side.wait_event(self._grads_pending)
-                        self.adam_dense(lr, reg_lambda, stream=side)
-                        if self._ev_dense is None:
-                            self._ev_dense = self._ev_new()
-                        self._ev_dense.record(side)
-                        self._dense_pending = self._ev_dense
-                    else:
-                        self._join_grads()
-                        self.adam_dense(lr, reg_lambda)
-                # (else the touched rows and the dense variables in one launch: nothing stands between them)
-                elif not self._adam_table_tiled(lr, dense=(reg_lambda,)):
+                # the touched rows and the dense variables in ONE launch on the launch stream, behind the scatter and behind the
+                # dense gradient's finishers (on the engine's side stream, beside the scatter: through by now) -- no stream hop in
+                # front of the next pass.  (A dense update on another stream behind the finishers' event alone would race with
+                # pull_kernel, which reads the co-attention weights: include/score_hip.h, grads_done_event.)
+                self._join_grads()
+                if not self._adam_table_tiled(lr, dense=(reg_lambda,)):
                     self.adam_dense(lr, reg_lambda)
             elif (self._row_grads and not self._use_dev_scalars and not self._adam_dirty and self._ps_last):
                 # the per-step sweep of a small table (cfg-2) and the dense variables in ONE launch (score_adam_rows_and_dense)
@@ -1264,8 +1153,8 @@ class SCOREBASE(object):
         """rows_untouched: the caller launches nothing that replays rows on `cur` (the batch's rows were caught up a step ahead);
         a slice the one-call step queued LAST on the side stream then needs no wait: what follows on the side stream queues
         behind it, the forward pass reads rows it skips, the touched-row update publishes counts it cannot mistake"""
-        if self._ev_sweep is not None and rows_untouched and self._sweep_on_side and str(self.adam_sweep_at) != "f1":
-            pass            # (adam_sweep_at "f1" puts this step's slice on a stream of its own: it would not queue behind that one)
+        if self._ev_sweep is not None and rows_untouched and self._sweep_on_side:
+            pass
         elif self._ev_sweep is not None:
             cur.wait_event(self._ev_sweep)
             self._ev_sweep = None
@@ -1363,7 +1252,7 @@ class SCOREBASE(object):
         status word guards this step's optimizer kernels, which run meanwhile): the forward pass of the batch reports them."""
         ev4 = getattr(self, "_b4_any", None)
         if (not isinstance(nxt, DeviceBatch) or nxt.flat is None or ev4 is None or self._side is None or self.scatter_mode != 0
-                or self._graph_on or self._use_dev_scalars or (self._tiled_on() and self.adam_touched_list)):
+                or self._graph_on or self._use_dev_scalars):
             return
         lay, ws = self._workspace(nxt.B)
         st = self._st_ahead
@@ -1396,16 +1285,8 @@ class SCOREBASE(object):
             # (only reached with no row lagging: _flush_adam ran, or nothing tiled has happened yet)
             row_step.fill_(int(self.step))
             self._tiled_ready = True
-        rl, self._row_list = getattr(self, "_row_list", None), None
         did_dense = False
-        if rl is not None:
-            lay, ws = rl          # (the plan's buffers: its side-stream work is behind the event score_backward waited for)
-            rows = ws[lay.plan_unique_rows:]
-            meta = ws[lay.plan_meta:]
-            _lib.check(self.lib.score_adam_touched_rows(C.byref(T), _ptr(rows), _ptr(meta), int(lay.n_occurrences) + 1,
-                                                        int(self.step) + 1, self._alpha(lr), self._stream()),
-                       "score_adam_touched_rows")
-        elif dense is not None and not self._use_dev_scalars:
+        if dense is not None and not self._use_dev_scalars:
             _lib.check(self.lib.score_adam_touched_and_dense(
                 C.byref(T), int(self.step) + 1, self._alpha(lr), _ptr(self.w), _ptr(self.w_m), _ptr(self.w_v), _ptr(self._w_g),
                 self.n_w, self.n_reg, float(dense[0]),
@@ -1464,15 +1345,8 @@ class SCOREBASE(object):
             self._flags_marked = False
         _lib.check(rc, "score_adam(table)")
 
-    def adam_dense(self, lr, reg_lambda, stream=None):
-        """ApplyAdam over the flat dense variables (L2 term folded in) on the current stream.
-        stream (apply_adam only): a side stream the caller has ordered behind the dense gradient's finishers."""
-        if stream is not None:
-            rc = self.lib.score_adam(_ptr(self._w), _ptr(self._w_m), _ptr(self._w_v), _ptr(self._w_g), self.n_w,
-                                     self.n_reg, float(reg_lambda), self._alpha(lr), ADAM_B1, ADAM_B2, ADAM_EPS,
-                                     self._guard_dense, C.c_void_p(stream.cuda_stream))
-            _lib.check(rc, "score_adam(dense)")
-            return
+    def adam_dense(self, lr, reg_lambda):
+        """ApplyAdam over the flat dense variables (L2 term folded in) on the current stream."""
         if self._use_dev_scalars:
             rc = self.lib.score_adam_dev(_ptr(self.w), _ptr(self.w_m), _ptr(self.w_v), _ptr(self.w_g), self.n_w,
                                          self.n_reg, float(reg_lambda), _ptr(self._scalars), ADAM_B1, ADAM_B2, ADAM_EPS,
@@ -1533,7 +1407,7 @@ class SCOREBASE(object):
         the one announced, stage events, an evaluation in between, ...): the caller then takes the call-by-call path, and the two
         can alternate step by step (tests/test_gpu_persample.py)."""
         if (not self.fast_step or self._graph_on or self._use_dev_scalars or self.scatter_mode != 0 or self.bwd_events
-                or self.catchup_events or int(self.debug_flags) or str(self.adam_sweep_at) not in ("2", "auto") or self.adam_touched_list
+                or self.catchup_events or int(self.debug_flags) or self.adam_sweep_at not in ("2", "auto")
                 or self._tiled is None or not self._tiled_ready or not self._adam_dirty or self._flags_marked or self._row_grads
                 or self._pending_sweep is not None or self._side is None or not isinstance(db, DeviceBatch) or db.flat is None
                 or not self._look_ahead or not self._tiled_on()):
@@ -1555,7 +1429,6 @@ class SCOREBASE(object):
         cur = self._cur()
         if self._inline_on or (self._train_stream is not None and self._train_stream.cuda_stream != cur.cuda_stream):
             return None
-        self._join_dense()
         self._join_grads()
         st = self._state(ws)
         st.plan_workspace = pr[2] if slot == 1 else None
@@ -1571,7 +1444,7 @@ class SCOREBASE(object):
             self._step_T = T
         # (the buffers re-read every call: set_params replaces them; the side stream when it has been replaced -- the inline mode
         #  switched on and off --; the events are created once and never replaced)
-        p.w, p.w_m, p.w_v, p.w_g = self._w.data_ptr(), self._w_m.data_ptr(), self._w_v.data_ptr(), self._w_g.data_ptr()
+        p.w, p.w_m, p.w_v, p.w_g = self._w.data_ptr(), self.w_m.data_ptr(), self.w_v.data_ptr(), self._w_g.data_ptr()
         if self._step_side is not self._side:
             self._step_side = self._side
             p.skipped = self._id_status.data_ptr() + 4 if self._guard_on else None
@@ -1641,7 +1514,6 @@ class SCOREBASE(object):
         self._b4_recorded, self._b4_any = None, self._ev_b4
         self._row_grads = self._flags_marked = False
         self._adam_dirty = True
-        self._row_list = None
         self._grads_pending = None
         if nxt is not None:
             self._ahead = (nxt, ah[1], 0)
@@ -1702,8 +1574,7 @@ class SCOREBASE(object):
         key = (db.B, db.active_slices, float(reg_lambda), float(keep_prob), int(self.global_batch), int(self.gemm_mode),
                int(self.debug_flags))
         ent = self._graphs.get(key)
-        self._join_dense()               # (eager steps before: nothing of theirs may be pending on a side stream when a capture begins)
-        self._join_grads()
+        self._join_grads()               # (eager steps before: nothing of theirs may be pending on a side stream when a capture begins)
         self._use_dev_scalars = True
         try:
             self._write_step_scalars(lr)
@@ -1786,7 +1657,6 @@ class SCOREBASE(object):
         call takes them off the step count and the beta powers again.  Parameters, Adam slots, step and beta powers
         are then bit for bit what they were before the offending call.  Callers of train_async / eval_async call
         this at their own sync points."""
-        self._join_dense()        # (the dense variables' update may be on the side stream: it is what counts a suppressed step)
         bits, skipped = [int(x) for x in self._id_status.tolist()]
         if bits:
             self._id_status.zero_()

@@ -124,6 +124,22 @@ def test_step_entry_point_rejects_missing_arguments():
     assert lib.score_train_step(C.byref(cfg), C.byref(st), C.byref(bt), C.byref(p), None) == -1      # (no table, no events)
 
 
+def test_index_plan_takes_dedup_0_or_1_only():
+    """score_index_plan: dedup is 0 or 1; 2 (the retired unique-row-list form) and every other value -> SCORE_E_BADARG.  Config,
+    state, workspace and batch are valid -- the same call with 0 and with 1 succeeds --, so the argument check is what answers"""
+    from oracle import score_oracle as so
+    from score_amd.model import SCORE
+    from helpers import random_batch, batch_tuple
+    cfg = so.Cfg(501, 4, 8, 3, 2, 3, 4, "SCORE")
+    m = SCORE(cfg.N, cfg.D, cfg.H, cfg.T, cfg.K, cfg.Fu, cfg.Fi)
+    db = m.device_batch(batch_tuple(random_batch(np.random.default_rng(0), cfg, 5)))
+    st = m._state(m._workspace(db.B)[1])
+    plan = lambda dedup: m.lib.score_index_plan(C.byref(m.cfg), C.byref(st), C.byref(db.struct), 1, dedup, m._stream())
+    assert plan(0) == 0 and plan(1) == 0
+    assert plan(2) == -1 and plan(3) == -1 and plan(-1) == -1
+    torch.cuda.synchronize()
+
+
 def test_device_only_events_order_streams():
     """score_event_create / _record / score_stream_wait_event / _query / _synchronize (round 6: events without the system-scope
     fence, for stream-to-stream ordering) through _lib.DevEvent -- the duck type torch.cuda.Stream.wait_event accepts: a consumer

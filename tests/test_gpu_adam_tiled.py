@@ -328,42 +328,24 @@ def test_g6_optimizer_alone_on_the_oracles_gradients(window):
         assert e <= (5e-7 if k == "emb_mtx" else 1e-6), (step, k, e)
 
 
-def test_row_list_and_state_scan_forms_of_the_touched_update_agree():
-    """score_adam_touched_rows (driven by the plan's unique-row list, model.adam_touched_list = True) against
-    score_adam_touched (scan of the state bytes, the default): the same rows get the same update -- bit-identical tables --
-    also when a backward pass nobody applied sits between two steps"""
-    cfg = so.Cfg(6000, 32, 32, 6, 4, 2, 3, "SCORE")
-    a, b = make(cfg, 5), make(cfg, 5)
-    a.adam_touched_list = True
-    bs = batches(cfg, 14, 24, seed=11, hot_rows=400)
-    for i, bt in enumerate(bs):
-        la = a.train(None, bt, 1e-2, 1e-4)
-        assert a._row_list is None                       # consumed by the step
-        lb = b.train(None, bt, 1e-2, 1e-4)
-        assert la == lb
-        if i == 6:
-            a.forward_backward(bs[0], 1e-4, 1.0)         # marks + a row list that no optimizer step consumes
-            assert a._row_list is not None
-            b.forward_backward(bs[0], 1e-4, 1.0)
-            assert b._row_list is None
-    assert same_state(a, b)
-
-
-@pytest.mark.parametrize("where", ["f1", "plan", "4", "2"])
+@pytest.mark.parametrize("where", ["plan", "1", "2", "3", "4"])
 def test_window_slice_placement_does_not_change_the_tables(where):
-    """model.adam_sweep_at: the step's window slice beside the forward recurrence on its own stream (f1), behind the
-    occurrence sort (plan) or at the last stage boundary of the backward pass (4) instead of boundary 2 -- rows nobody in the
-    batch touches, any time between the batch rows' catch-up and the touched-row update: bit-identical tables and losses"""
+    """model.adam_sweep_at: the step's window slice behind the occurrence sort (plan) or at stage boundary 1 .. 4 of the backward
+    pass, against the default ("auto": boundary 2 for this per-sample shape) -- rows nobody in the batch touches, any time between
+    the batch rows' catch-up and the touched-row update: bit-identical tables and losses.  A value outside the supported set
+    (the retired "f1" among them) is refused, an int is taken as its digit (bench.py --set adam_sweep_at=3)"""
     cfg = so.Cfg(6000, 32, 32, 6, 4, 2, 3, "SCORE")
     a, b = make(cfg, 5), make(cfg, 5)
+    with pytest.raises(ValueError):
+        a.adam_sweep_at = "f1"
+    a.adam_sweep_at = 3
+    assert a.adam_sweep_at == "3" and b.adam_sweep_at == "auto"
     a.adam_sweep_at = where
     bs = batches(cfg, 16, 24, seed=13, hot_rows=400)
     for i, bt in enumerate(bs):
         la = a.train(None, bt, 1e-2, 1e-4, keep_prob=0.8)
         lb = b.train(None, bt, 1e-2, 1e-4, keep_prob=0.8)
         assert la == lb, (i, la, lb)
-    if where == "f1":
-        assert a._sweep_st is not None              # (the slice did run on its own stream)
     assert same_state(a, b)
 
 
@@ -402,16 +384,15 @@ def test_look_ahead_catchup_of_the_next_batch_is_bitwise_the_same():
 
 
 def test_side_stream_finishers_and_loss_do_not_change_a_bit():
-    """score_state_t.grads_done_event (the dense gradient's end-of-pass finishers on the engine's side stream, under the table's
-    touched-row update) and .loss_done_event (the loss reduction there, beside the backward pass's first launches) only MOVE
-    launches: with both forced on at a small shape (they engage from overlap_finishers_min_rows (b, t) rows on), losses --
+    """score_state_t.grads_done_event (the dense gradient's finishers on the engine's side stream, beside the row scatter) and
+    .loss_done_event (the loss reduction there, beside the backward pass's first launches) only MOVE launches: with both forced on at a small shape (they engage from overlap_finishers_min_rows (b, t) rows on), losses --
     train_async's device scalar and train()'s early read-back --, gradients and optimizer state equal the run with both off,
     bit for bit; so do an evaluation in between and a forward_backward whose gradients the caller reads."""
     cfg = so.Cfg(3000, 16, 16, 4, 3, 2, 3, "SCORE")
     off, on = make(cfg, 5), make(cfg, 5)
     off.overlap_finishers_min_rows = 10 ** 9
     on.overlap_finishers_min_rows = 0
-    assert on.loss_on_side and off.loss_on_side and on.dense_adam_on_side    # (the dense ApplyAdam then runs on the side stream too)
+    assert on.loss_on_side and off.loss_on_side
     bs = batches(cfg, 16, 5, seed=21, hot_rows=150)
     d_off, d_on = [off.device_batch(b) for b in bs], [on.device_batch(b) for b in bs]
     for i in range(14):
@@ -433,12 +414,11 @@ def test_side_stream_finishers_and_loss_do_not_change_a_bit():
     assert same_state(off, on)
 
 
-@pytest.mark.parametrize("mode", ["persample", "layered", "finishers", "slice_f1", "slice_plan", "slice_2", "sweep", "wide",
-                                  "wide_finishers"])
+@pytest.mark.parametrize("mode", ["persample", "layered", "finishers", "slice_plan", "slice_2", "sweep", "wide", "wide_finishers"])
 def test_everything_inline_on_the_launch_stream_equals_every_overlap_mode(mode):
     """debug_flags bit 12 (4096, score_hip.h): NO second stream anywhere -- the engine's forks, the index plan (and the one
-    sorted a step ahead), the window slice, the look-ahead catch-up, the dense ApplyAdam and the early loss copy all run on
-    the launch stream in launch order.  Every overlap mode only MOVES launches: losses, predictions and the whole optimizer
+    sorted a step ahead), the window slice, the look-ahead catch-up and the early loss copy all run on the launch stream in
+    launch order.  Every overlap mode only MOVES launches: losses, predictions and the whole optimizer
     state equal the inline run's bit for bit, hints right or wrong, with evaluations and table reads in between."""
     H = 32 if mode in ("persample", "layered") else 16
     cfg = so.Cfg(3000, 16, H, 5, 3, 2, 3, "SCORE")
@@ -451,8 +431,6 @@ def test_everything_inline_on_the_launch_stream_equals_every_overlap_mode(mode):
             m.debug_flags = 512
         if mode in ("finishers", "wide_finishers"):
             m.overlap_finishers_min_rows = 0
-        if mode == "slice_f1":
-            m.adam_sweep_at = "f1"
         if mode == "slice_plan":
             m.adam_sweep_at = "plan"
         if mode == "slice_2":             # (the per-sample form's placement, here on the layer-by-layer pass: "auto" gives that one "plan")
@@ -475,7 +453,6 @@ def test_everything_inline_on_the_launch_stream_equals_every_overlap_mode(mode):
         assert la == lb, (mode, i, la, lb)
         cur = torch.cuda.current_stream().cuda_stream
         assert b._side is None or b._side.cuda_stream == cur
-        assert b._sweep_st is None or b._sweep_st.cuda_stream == cur
         if i == 8:
             assert a.eval(None, da[4], 1e-4)[0] == b.eval(None, db_[4], 1e-4)[0]
         if i == 13:
@@ -492,8 +469,8 @@ def test_everything_inline_on_the_launch_stream_equals_every_overlap_mode(mode):
 
 def test_three_hundred_overlapped_steps_equal_the_inline_run_at_a_wide_shape():
     """a soak for the layer-by-layer pass's overlap (D = 64, H = 128: cfg-3's kernels): the touched-row update beside the window
-    slice and the look-ahead catch-up (publish protocol, round 5), finishers and dense ApplyAdam on side streams -- 300 steps
-    with look-ahead hints against a twin with everything inline on the launch stream (debug_flags bit 12): the same bits"""
+    slice and the look-ahead catch-up (publish protocol, round 5), the dense gradient's finishers on the engine's side stream beside
+    the row scatter -- 300 steps with look-ahead hints against a twin with everything inline on the launch stream (debug_flags bit 12): the same bits"""
     cfg = so.Cfg(60000, 64, 128, 6, 4, 3, 4, "SCORE")
     a, b = make(cfg, 6), make(cfg, 6)
     for m in (a, b):

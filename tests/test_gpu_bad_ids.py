@@ -130,7 +130,7 @@ def test_no_variable_is_updated_by_a_step_that_raises(mode):
     for x in (m, twin):
         if mode in ("tiled", "overlap"):
             x.adam_tiled_min_bytes = 0
-        if mode == "overlap":       # the finishers, the loss reduction and the dense ApplyAdam on the side streams (what large batches take:
+        if mode == "overlap":       # the finishers and the loss reduction on the engine's side stream (what large batches take:
             x.overlap_finishers_min_rows = 0      # the layer-by-layer pass -- this shape would run as the per-sample kernels, whose
             x.debug_flags = 512                   # own side placement the sweep / tiled modes exercise)
         if mode == "graph":
@@ -140,7 +140,7 @@ def test_no_variable_is_updated_by_a_step_that_raises(mode):
     if mode in ("tiled", "overlap"):
         assert m._tiled_on() and m._adam_dirty
     if mode == "overlap":
-        assert m._ev_grads is not None and m._fin_early      # (finishers on the engine's side stream; touched rows + dense variables in one launch behind them)
+        assert m._ev_grads is not None and not m._ps_last    # (the layer-by-layer pass with its finishers on the engine's side stream; touched rows + dense variables in one launch behind them)
     snap = _snapshot(m)
     with pytest.raises(ValueError) as ei:
         m.train(None, batch_tuple(bad), 1e-3, 1e-4)
