@@ -772,6 +772,35 @@ int score_catalog_topk(const score_config_t* cfg, const score_state_t* st, const
  * score_abi_struct_sizes): returns the number of values written (6), SCORE_E_BADARG for a null pointer or n too small. */
 int score_catalog_struct_sizes(int64_t* out, int32_t n);
 
+/* ---- ... within per-line candidate lists --------------------------------------------------------------------------------------
+ * "Which k of THESE items": every line brings a list of catalogue indices -- a category, the items in stock, what a retrieval
+ * stage handed over, the 1 + 99 candidates of the sampled evaluation protocol -- and score_catalog_topk_in scores only those
+ * pairs, against the same zcat, and returns the k best of them: the order, the -1 / -inf padding, the exclusions (an excluded
+ * candidate is never returned) and the bits of a pair's logit are those of score_catalog_topk, wherever the item stands in a list.
+ * The list contract: catalogue indices in [0, N), STRICTLY ASCENDING within a line -- no repeats.  A list that breaks it may
+ * return an item twice and may miss exclusions; an index outside [0, N) is never selected, reads nothing outside zcat and gets
+ * NaN in cand_logits.  Lines may have any length, 0 included (such a line is all padding).
+ * max_count sizes the plan -- score_catalog_plan's rule with the longest list in N's place: a scoring workgroup walks `chunk`
+ * list positions, and the last of a line's nchunk workgroups walks to the end of the list however long it is, so an understated
+ * max_count costs time, never results.  cand_logits (optional) receives every listed pair's logit at its place in cand_idx,
+ * excluded candidates included.  Refusals, all before any launch: a null pointer, max_count <= 0, k outside
+ * [1, SCORE_CATALOG_KMAX] (SCORE_E_BADARG), a model type other than GRU4Rec / Caser (SCORE_E_SHAPE), a workspace below
+ * score_catalog_cands_plan's workspace_bytes (SCORE_E_WORKSPACE). */
+typedef struct {
+  const int64_t* cand_off;     /* [L + 1] device offsets into cand_idx                                                        */
+  const int32_t* cand_idx;     /* catalogue indices in [0, N), strictly ascending within a line; non-null                     */
+  int32_t max_count;           /* the plan's size: >= 1; normally the longest line's count                                    */
+} score_catalog_cands_t;
+int score_catalog_cands_plan(const score_config_t* cfg, int32_t L, int32_t max_count, int32_t k, int32_t* chunk, int32_t* nchunk,
+                             int64_t* workspace_bytes);
+int score_catalog_topk_in(const score_config_t* cfg, const score_state_t* st, const score_catalog_t* cat,
+                          const score_catalog_lines_t* lines, const score_catalog_cands_t* cands, int32_t k,
+                          int32_t* top_idx /* [L, k] */, float* top_logit /* [L, k] */,
+                          float* cand_logits /* [cand_off[L]] aligned with cand_idx, or null */, void* stream);
+/* sizeof(score_catalog_cands_t) and the offsets of its three fields: returns the number of values written (4), SCORE_E_BADARG
+ * for a null pointer or n too small. */
+int score_catalog_cands_struct_sizes(int64_t* out, int32_t n);
+
 /* ---- one training step in one call (csrc/step.hip) -----------------------------------------------------------------------
  * The steady-state step of model.train (score.py:101-116) for a caller that runs the time-tiled table optimizer with the
  * look-ahead (score_adam_catchup_ids_through) and sorts the next batch's index plan a step ahead: exactly

@@ -53,6 +53,11 @@ class CatalogLines(C.Structure):
                 ("excl_off", C.c_void_p), ("excl_idx", c_i)]
 
 
+class CatalogCands(C.Structure):
+    """score_catalog_cands_t: per line a list of catalogue indices, CSR (score_catalog_topk_in)"""
+    _fields_ = [("cand_off", C.c_void_p), ("cand_idx", c_i), ("max_count", C.c_int32)]
+
+
 CATALOG_KMAX = 128      # SCORE_CATALOG_KMAX
 
 
@@ -300,6 +305,11 @@ _SIGS = {
     "score_catalog_topk": [C.POINTER(Config), C.POINTER(State), C.POINTER(Catalog), C.POINTER(CatalogLines), C.c_int32, c_i, c_f, c_f,
                            C.c_void_p],
     "score_catalog_struct_sizes": [C.POINTER(C.c_int64), C.c_int32],
+    "score_catalog_cands_plan": [C.POINTER(Config), C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int32),
+                                 C.POINTER(C.c_int64)],
+    "score_catalog_topk_in": [C.POINTER(Config), C.POINTER(State), C.POINTER(Catalog), C.POINTER(CatalogLines),
+                              C.POINTER(CatalogCands), C.c_int32, c_i, c_f, c_f, C.c_void_p],
+    "score_catalog_cands_struct_sizes": [C.POINTER(C.c_int64), C.c_int32],
 }
 # (score_rank_workspace_bytes returns a status; the size comes back through its last argument)
 _STATUS_RETURN = ("score_rank_workspace_bytes",)
@@ -440,6 +450,14 @@ def catalog_plan(cfg, L, N, k):
     chunk, nchunk, n = C.c_int32(0), C.c_int32(0), C.c_int64(0)
     check(load().score_catalog_plan(C.byref(cfg), int(L), int(N), int(k), C.byref(chunk), C.byref(nchunk), C.byref(n)),
           "score_catalog_plan")
+    return chunk.value, nchunk.value, n.value
+
+
+def catalog_cands_plan(cfg, L, max_count, k):
+    """(chunk, nchunk, workspace bytes) of score_catalog_topk_in for L lines of at most max_count candidates"""
+    chunk, nchunk, n = C.c_int32(0), C.c_int32(0), C.c_int64(0)
+    check(load().score_catalog_cands_plan(C.byref(cfg), int(L), int(max_count), int(k), C.byref(chunk), C.byref(nchunk), C.byref(n)),
+          "score_catalog_cands_plan")
     return chunk.value, nchunk.value, n.value
 
 

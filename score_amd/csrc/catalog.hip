@@ -5,7 +5,8 @@
 // catalog_zcat_kernel computes zcat [N, 200] once per catalogue and weight state: the first stage of rank_tile_kernel without a
 // line.  catalog_score_kernel, a workgroup per (line, chunk of the catalogue), then has per pair relu(zline + zcat[n]), fc2
 // (200 x 80), fc3 and a comparison against the K-th best so far; catalog_merge_kernel, a workgroup per line, reduces the
-// chunks' lists.
+// chunks' lists.  score_catalog_topk_in scores, per line, only a list of catalogue indices: the same kernel body instantiated
+// with CAND, which walks list positions and gathers its rows through the list (see catalog_score_kernel).
 //
 // The order.  Pairs are ordered by descending fc3 logit, ties by ascending catalogue index, NaN behind every number: a TOTAL
 // order, held as one 64-bit key per pair -- (the logit's bits made monotone, NaN -> 0) << 32 | ~index -- whose unsigned
@@ -123,11 +124,14 @@ __global__ __launch_bounds__(64 * HF_NW) void catalog_zcat_kernel(const CatalogA
 
 inline size_t catalog_zcat_lds(int Di) { return (size_t)HF_ROWS * (((Di + 15) & ~15) + 4) * sizeof(float); }
 
-// LDS of the scoring kernel, in floats: relu(z1) and relu(z2) of a step, two buffers each; the line's zline; the staged exclusions
+// LDS of the scoring kernel, in floats: relu(z1) and relu(z2) of a step, two buffers each; the line's zline; the staged exclusions;
+// behind them, in the candidate form only, CT_CSLOTS steps' catalogue indices
+constexpr int CT_CSLOTS = 4;                  // a step's indices live from two steps ahead of its rows to the selection a step behind
 constexpr int CT_SM_F1 = 0, CT_SM_F2 = CT_SM_F1 + 2 * CT_ROWS * CT_LD1, CT_SM_ZL = CT_SM_F2 + 2 * CT_ROWS * CT_LD2,
-              CT_SM_EX = CT_SM_ZL + CT_N1, CT_SM_FLOATS = CT_SM_EX + CT_EXCL;
-static_assert(CT_SM_F2 % 4 == 0 && CT_SM_ZL % 4 == 0 && CT_SM_EX % 4 == 0, "16-byte carve offsets");
-static_assert(2 * CT_SM_FLOATS * 4 <= 160 * 1024, "two workgroups per compute unit");
+              CT_SM_EX = CT_SM_ZL + CT_N1, CT_SM_FLOATS = CT_SM_EX + CT_EXCL, CT_SM_CI = CT_SM_FLOATS,
+              CT_SM_FLOATS_IN = CT_SM_CI + CT_CSLOTS * CT_ROWS;
+static_assert(CT_SM_F2 % 4 == 0 && CT_SM_ZL % 4 == 0 && CT_SM_EX % 4 == 0 && CT_SM_CI % 4 == 0, "16-byte carve offsets");
+static_assert(2 * CT_SM_FLOATS * 4 <= 160 * 1024 && 2 * CT_SM_FLOATS_IN * 4 <= 160 * 1024, "two workgroups per compute unit");
 
 // Workgroup blockIdx.x = l * nchunk + ch: line l against the catalogue items [ch * chunk, min(N, (ch + 1) * chunk)), CT_ROWS a
 // step.  Waves 0 .. 4 hold fc2 as MFMA B fragments in registers, one column tile each (52 values a lane: W2 is read ONCE per
@@ -136,6 +140,15 @@ static_assert(2 * CT_SM_FLOATS * 4 <= 160 * 1024, "two workgroups per compute un
 // registers and works one step behind the matrix waves, on the other relu(z2) buffer: fc3 as rank_tile_kernel sums it (four
 // lanes a pair, fixed order), then only the pairs whose key beats the current K-th -- rare after the first steps -- are looked
 // up in the line's exclusions and inserted.  One barrier per step.
+//
+// CAND, the candidate form (score_catalog_topk_in): [c0, c1) are POSITIONS of line l's list cand_idx[cand_off[l] ..
+// cand_off[l + 1]) -- the last chunk's workgroup walks to the list's end, however long -- and a step's rows are
+// zcat[cand_idx[pos]]; the key carries that catalogue index, so the merge and the outputs are those of the whole form.  The
+// dependent index load stays off the step: while step t runs, the selection wave puts the 32 indices of step t + 2 into slot
+// (t + 2) % CT_CSLOTS of an LDS array (four slots: the selection reads step t - 1's while fetch reads step t + 1's), ordered by
+// the step's one barrier; only the first two steps' indices are read straight from global memory.  An index outside [0, N)
+// reads row 0, gets no key and NaN in cand_logits.  A workgroup whose range is empty writes k empty keys and returns.
+template <bool CAND>
 __global__ __launch_bounds__(64 * CT_NW) void catalog_score_kernel(const CatalogArgs a) {
   extern __shared__ __attribute__((aligned(16))) float sm[];
   float* f1s = sm + CT_SM_F1;
@@ -146,7 +159,25 @@ __global__ __launch_bounds__(64 * CT_NW) void catalog_score_kernel(const Catalog
   const int lc = lane & 15, lq = lane >> 4;
   const int N = a.N, k = a.k;
   const int l = (int)blockIdx.x / a.nchunk, ch = (int)blockIdx.x - l * a.nchunk;
-  const int c0 = ch * a.chunk, c1 = min(N, c0 + a.chunk);
+  int c0_, c1_;
+  const int32_t* cand = nullptr;              // line l's list (CAND)
+  int* cis = nullptr;                         // [CT_CSLOTS][CT_ROWS] catalogue indices of the steps in flight (CAND)
+  if constexpr (CAND) {
+    const int64_t lo = a.cand_off[l], cnt64 = a.cand_off[l + 1] - lo;
+    const int cnt = (int)(cnt64 < (int64_t)0x7FFFFF00 ? (cnt64 > 0 ? cnt64 : 0) : 0x7FFFFF00);
+    cand = a.cand_idx + lo;
+    cis = reinterpret_cast<int*>(sm + CT_SM_CI);
+    c0_ = (int)min((int64_t)ch * a.chunk, (int64_t)cnt);
+    c1_ = ch == a.nchunk - 1 ? cnt : (int)min((int64_t)c0_ + a.chunk, (int64_t)cnt);
+    if (c1_ <= c0_) {                          // (workgroup-uniform, in front of the first barrier)
+      ct_u64* out = a.part + ((int64_t)l * a.nchunk + ch) * k;
+      if (tid < k) out[tid] = 0ull;
+      return;
+    }
+  } else {
+    c0_ = ch * a.chunk; c1_ = min(N, c0_ + a.chunk);
+  }
+  const int c0 = c0_, c1 = c1_;
   const int nstep = (c1 - c0 + CT_ROWS - 1) / CT_ROWS;
 
   for (int e = tid; e < CT_N1; e += 64 * CT_NW) zl[e] = a.zline[(int64_t)l * CT_N1 + e];
@@ -159,8 +190,15 @@ __global__ __launch_bounds__(64 * CT_NW) void catalog_score_kernel(const Catalog
   if (a.excl_off) {
     const int64_t lo = a.excl_off[l], hi = a.excl_off[l + 1];
     const uint32_t* ex = reinterpret_cast<const uint32_t*>(a.excl_idx) + lo;
-    xa = lo + dp_lower_bound(ex, hi - lo, (uint32_t)c0);
-    xb = lo + dp_lower_bound(ex, hi - lo, (uint32_t)c1);
+    if constexpr (CAND) {            // between the range's first and last candidate, by value (each clamped into the catalogue)
+      const int v0 = min(max(cand[c0], 0), N), v1 = min(max(cand[c1 - 1], -1), N - 1) + 1;
+      xa = lo + dp_lower_bound(ex, hi - lo, (uint32_t)v0);
+      xb = lo + dp_lower_bound(ex, hi - lo, (uint32_t)v1);
+      if (xb < xa) xb = xa;
+    } else {
+      xa = lo + dp_lower_bound(ex, hi - lo, (uint32_t)c0);
+      xb = lo + dp_lower_bound(ex, hi - lo, (uint32_t)c1);
+    }
   }
   const int xn = (int)(xb - xa < (int64_t)0x7FFFFFFF ? xb - xa : 0x7FFFFFFF);
   const bool staged = xn <= CT_EXCL;
@@ -188,12 +226,19 @@ __global__ __launch_bounds__(64 * CT_NW) void catalog_score_kernel(const Catalog
 
   // a step's zcat rows: CT_Q4 16-byte groups per matrix-wave thread; rows past the chunk's end read its last row
   float4 pre[CT_Q4];
-  auto fetch = [&](int step) {
+  // (CAND: the row of the list position's catalogue index, from the step's LDS slot -- step 0's from the list itself)
+  auto fetch = [&](int step, bool first) {
 #pragma unroll
     for (int j = 0; j < CT_Q4; ++j) {
       const int e = tid + 64 * CT_MW * j;
       const int i = e / (CT_N1 / 4), c4 = e - i * (CT_N1 / 4);
-      const int n = min(c0 + step * CT_ROWS + i, c1 - 1);
+      int n;
+      if constexpr (CAND) {
+        n = first ? cand[min(c0 + i, c1 - 1)] : cis[(step & (CT_CSLOTS - 1)) * CT_ROWS + i];
+        n = (uint32_t)n < (uint32_t)N ? n : 0;
+      } else {
+        n = min(c0 + step * CT_ROWS + i, c1 - 1);
+      }
       pre[j] = ld4(a.zcat + (int64_t)n * CT_N1 + c4 * 4);
     }
   };
@@ -213,7 +258,7 @@ __global__ __launch_bounds__(64 * CT_NW) void catalog_score_kernel(const Catalog
 
   ct_u64 e0 = 0ull, e1 = 0ull, thr = 0ull;       // the selection wave's list and its K-th key (0: fewer than K so far)
   const uint32_t* ex = staged ? exs : reinterpret_cast<const uint32_t*>(a.excl_idx) + xa;
-  auto select = [&](const float* f2, int base) {
+  auto select = [&](const float* f2, int base, const int* ci) {
 #pragma unroll
     for (int p = 0; p < CT_ROWS / 16; ++p) {
       const int i = lane >> 2, part = lane & 3;
@@ -224,9 +269,17 @@ __global__ __launch_bounds__(64 * CT_NW) void catalog_score_kernel(const Catalog
       s += __shfl_xor(s, 1, 64);
       s += __shfl_xor(s, 2, 64);
       const float logit = s + bias3;
-      const int n = base + p * 16 + i;
-      const bool mine = part == 0 && n < c1;
-      if (mine && a.all_logits) a.all_logits[(int64_t)l * N + n] = logit;
+      int n = base + p * 16 + i;
+      bool mine = part == 0 && n < c1;
+      if constexpr (CAND) {          // n: a list position; the key takes its catalogue index, none outside the catalogue
+        const int at = n;
+        n = ci[p * 16 + i];
+        const bool inside = (uint32_t)n < (uint32_t)N;
+        if (mine && a.all_logits) a.all_logits[(cand - a.cand_idx) + at] = inside ? logit : __uint_as_float(0x7FC00000u);
+        mine = mine && inside;
+      } else {
+        if (mine && a.all_logits) a.all_logits[(int64_t)l * N + n] = logit;
+      }
       const ct_u64 key = mine ? ct_key(logit, n) : 0ull;
       ct_u64 m = __ballot(key > thr);
       while (m) {
@@ -243,14 +296,17 @@ __global__ __launch_bounds__(64 * CT_NW) void catalog_score_kernel(const Catalog
     }
   };
 
-  if (wave < CT_MW) fetch(0);
+  if constexpr (CAND) {            // the first two steps' indices (the selection wave: a lane each)
+    if (wave == CT_MW) cis[lane] = cand[min(c0 + lane, c1 - 1)];
+  }
+  if (wave < CT_MW) fetch(0, true);
   __syncthreads();                 // zl, the padding and the exclusions are in LDS
   if (wave < CT_MW) store(0);
   __syncthreads();
   for (int t = 0; t <= nstep; ++t) {
     if (wave < CT_MW) {
       if (t < nstep) {
-        if (t + 1 < nstep) fetch(t + 1);
+        if (t + 1 < nstep) fetch(t + 1, false);
         hf_f32x4 acc0 = {0.f, 0.f, 0.f, 0.f}, acc1 = {0.f, 0.f, 0.f, 0.f};
         const float* x0 = f1s + (t & 1) * (CT_ROWS * CT_LD1) + lc * CT_LD1 + lq * CT_KQ;
         const float* x1 = x0 + 16 * CT_LD1;
@@ -275,8 +331,15 @@ __global__ __launch_bounds__(64 * CT_NW) void catalog_score_kernel(const Catalog
         }
         if (t + 1 < nstep) store((t + 1) & 1);
       }
+    } else if constexpr (CAND) {   // step t + 2's indices: requested in front of the selection, into their slot behind it
+      int ahead = 0;
+      const bool get = lane < CT_ROWS && t + 2 < nstep;
+      if (get) ahead = cand[min(c0 + (t + 2) * CT_ROWS + lane, c1 - 1)];
+      if (t >= 1)
+        select(f2s + ((t - 1) & 1) * (CT_ROWS * CT_LD2), c0 + (t - 1) * CT_ROWS, cis + ((t - 1) & (CT_CSLOTS - 1)) * CT_ROWS);
+      if (get) cis[((t + 2) & (CT_CSLOTS - 1)) * CT_ROWS + lane] = ahead;
     } else if (t >= 1) {
-      select(f2s + ((t - 1) & 1) * (CT_ROWS * CT_LD2), c0 + (t - 1) * CT_ROWS);
+      select(f2s + ((t - 1) & 1) * (CT_ROWS * CT_LD2), c0 + (t - 1) * CT_ROWS, nullptr);
     }
     __syncthreads();
   }
@@ -359,12 +422,35 @@ int score_catalog_select(const CatalogArgs& a, hipStream_t s) {
   const size_t lds = (size_t)CT_SM_FLOATS * sizeof(float);
   static thread_local bool attr_set = false;
   if (!attr_set) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(catalog_score_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
+    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(catalog_score_kernel<false>), hipFuncAttributeMaxDynamicSharedMemorySize,
                                        (int)lds);
     if (e != hipSuccess) return (int)e;
     attr_set = true;
   }
-  hipLaunchKernelGGL(catalog_score_kernel, dim3((unsigned)(a.L * a.nchunk)), dim3(64 * CT_NW), lds, s, a);
+  hipLaunchKernelGGL(catalog_score_kernel<false>, dim3((unsigned)(a.L * a.nchunk)), dim3(64 * CT_NW), lds, s, a);
+  SCORE_CHECK_LAUNCH();
+  hipLaunchKernelGGL(catalog_merge_kernel, dim3((unsigned)a.L), dim3(64), 0, s, a);
+  SCORE_CHECK_LAUNCH();
+  return 0;
+}
+
+// The candidate form: the plan is that of a catalogue of a.max_count items (score_catalog_chunks with the longest list in N's
+// place); a.all_logits is cand_logits, aligned with cand_idx
+int score_catalog_select_in(const CatalogArgs& a, hipStream_t s) {
+  if (a.L <= 0 || a.N <= 0 || a.N1 != CT_N1 || a.k < 1 || a.k > SCORE_CATALOG_KMAX || a.max_count <= 0) return SCORE_E_SHAPE;
+  if (!a.cand_off || !a.cand_idx) return SCORE_E_BADARG;
+  if (a.chunk <= 0 || a.chunk % CT_ROWS || (int64_t)a.nchunk * a.chunk < a.max_count ||
+      (int64_t)(a.nchunk - 1) * a.chunk >= a.max_count || (int64_t)a.L * a.nchunk >= (1LL << 31))
+    return SCORE_E_SHAPE;
+  const size_t lds = (size_t)CT_SM_FLOATS_IN * sizeof(float);
+  static thread_local bool attr_set = false;
+  if (!attr_set) {
+    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(catalog_score_kernel<true>),
+                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    if (e != hipSuccess) return (int)e;
+    attr_set = true;
+  }
+  hipLaunchKernelGGL(catalog_score_kernel<true>, dim3((unsigned)(a.L * a.nchunk)), dim3(64 * CT_NW), lds, s, a);
   SCORE_CHECK_LAUNCH();
   hipLaunchKernelGGL(catalog_merge_kernel, dim3((unsigned)a.L), dim3(64), 0, s, a);
   SCORE_CHECK_LAUNCH();

@@ -2153,6 +2153,42 @@ void catalog_model_args(const Dims& d, const score_state_t* st, const score_cata
   a->W1 = W + P.fc_w[0]; a->W2 = W + P.fc_w[1]; a->b2 = W + P.fc_b[1]; a->W3 = W + P.fc_w[2]; a->b3 = W + P.fc_b[2];
   a->n_rows = clamp_rows(st->n_table_rows); a->id_status = st->id_status;
 }
+// score_catalog_topk (cands null: every line against the whole catalogue, logits = all_logits [L, N]) and
+// score_catalog_topk_in (every line against its own list, logits = cand_logits): the checks, rank_prefix, the line kernel and the
+// selection.  span, what the plan cuts: N, or the lists' max_count
+int catalog_topk(const score_config_t* cfg, const score_state_t* st, const score_catalog_t* cat, const score_catalog_lines_t* ln,
+                 const score_catalog_cands_t* cands, int32_t k, int32_t* top_idx, float* top_logit, float* logits, void* stream) {
+  Pass c;
+  SCORE_TRY(catalog_dims(cfg, ln->L, cat->N, k, &c.d));
+  if (cands) SCORE_TRY(catalog_dims(cfg, ln->L, cands->max_count, k, &c.d));
+  if (!st->table || !st->w || !st->workspace || !cat->item_rows || !cat->zcat) return SCORE_E_BADARG;
+  if (!ln->user_seq || !ln->length || !ln->target_user || (ln->excl_off && !ln->excl_idx)) return SCORE_E_BADARG;
+  if (cands && (!cands->cand_off || !cands->cand_idx)) return SCORE_E_BADARG;
+  const Dims& d = c.d;
+  const int L = ln->L;
+  CatalogWS r;
+  build_catalog_ws(d, L, cands ? cands->max_count : cat->N, k, &r);
+  if (r.total * 4 > st->workspace_bytes) return SCORE_E_WORKSPACE;
+  hipStream_t s = (hipStream_t)stream;
+  score_batch_t lb;
+  FwdState f = {0.f, 1.f, nullptr, nullptr, 0, nullptr, nullptr, false};
+  SCORE_TRY(rank_prefix(&c, &f, &lb, st, ln->user_seq, ln->length, ln->target_user, nullptr, L, ln->active_slices,
+                        reinterpret_cast<int32_t*>(st->workspace + r.zero_ids), r.n_zero_ids, stream));
+  float* ws = c.ws;
+  RankArgs ra;
+  rank_head_args(c, st, L, 1, &ra);
+  ra.zline = ws + r.zline;
+  G(score_rank_line(ra, s));
+  CatalogArgs a;
+  catalog_model_args(d, st, cat, &a);
+  a.L = L; a.k = k; a.chunk = r.chunk; a.nchunk = r.nchunk;
+  a.zline = ws + r.zline; a.excl_off = ln->excl_off; a.excl_idx = ln->excl_idx;
+  a.part = reinterpret_cast<unsigned long long*>(ws + r.part);
+  a.top_idx = top_idx; a.top_logit = top_logit; a.all_logits = logits;
+  if (!cands) return score_catalog_select(a, s);
+  a.cand_off = cands->cand_off; a.cand_idx = cands->cand_idx; a.max_count = cands->max_count;
+  return score_catalog_select_in(a, s);
+}
 }  // namespace
 
 extern "C" int score_catalog_plan(const score_config_t* cfg, int32_t L, int32_t N, int32_t k, int32_t* chunk, int32_t* nchunk,
@@ -2181,32 +2217,29 @@ extern "C" int score_catalog_topk(const score_config_t* cfg, const score_state_t
                                   const score_catalog_lines_t* ln, int32_t k, int32_t* top_idx, float* top_logit, float* all_logits,
                                   void* stream) {
   if (!cfg || !st || !cat || !ln || !top_idx || !top_logit) return SCORE_E_BADARG;
-  Pass c;
-  SCORE_TRY(catalog_dims(cfg, ln->L, cat->N, k, &c.d));
-  if (!st->table || !st->w || !st->workspace || !cat->item_rows || !cat->zcat) return SCORE_E_BADARG;
-  if (!ln->user_seq || !ln->length || !ln->target_user || (ln->excl_off && !ln->excl_idx)) return SCORE_E_BADARG;
-  const Dims& d = c.d;
-  const int L = ln->L;
-  CatalogWS r;
-  build_catalog_ws(d, L, cat->N, k, &r);
-  if (r.total * 4 > st->workspace_bytes) return SCORE_E_WORKSPACE;
-  hipStream_t s = (hipStream_t)stream;
-  score_batch_t lb;
-  FwdState f = {0.f, 1.f, nullptr, nullptr, 0, nullptr, nullptr, false};
-  SCORE_TRY(rank_prefix(&c, &f, &lb, st, ln->user_seq, ln->length, ln->target_user, nullptr, L, ln->active_slices,
-                        reinterpret_cast<int32_t*>(st->workspace + r.zero_ids), r.n_zero_ids, stream));
-  float* ws = c.ws;
-  RankArgs ra;
-  rank_head_args(c, st, L, 1, &ra);
-  ra.zline = ws + r.zline;
-  G(score_rank_line(ra, s));
-  CatalogArgs a;
-  catalog_model_args(d, st, cat, &a);
-  a.L = L; a.k = k; a.chunk = r.chunk; a.nchunk = r.nchunk;
-  a.zline = ws + r.zline; a.excl_off = ln->excl_off; a.excl_idx = ln->excl_idx;
-  a.part = reinterpret_cast<unsigned long long*>(ws + r.part);
-  a.top_idx = top_idx; a.top_logit = top_logit; a.all_logits = all_logits;
-  return score_catalog_select(a, s);
+  return catalog_topk(cfg, st, cat, ln, nullptr, k, top_idx, top_logit, all_logits, stream);
+}
+
+// ---- ... within per-line candidate lists.  The plan: score_catalog_plan's with the longest list in N's place
+extern "C" int score_catalog_cands_plan(const score_config_t* cfg, int32_t L, int32_t max_count, int32_t k, int32_t* chunk,
+                                        int32_t* nchunk, int64_t* workspace_bytes) {
+  return score_catalog_plan(cfg, L, max_count, k, chunk, nchunk, workspace_bytes);
+}
+
+extern "C" int score_catalog_topk_in(const score_config_t* cfg, const score_state_t* st, const score_catalog_t* cat,
+                                     const score_catalog_lines_t* ln, const score_catalog_cands_t* cands, int32_t k,
+                                     int32_t* top_idx, float* top_logit, float* cand_logits, void* stream) {
+  if (!cfg || !st || !cat || !ln || !cands || !top_idx || !top_logit) return SCORE_E_BADARG;
+  return catalog_topk(cfg, st, cat, ln, cands, k, top_idx, top_logit, cand_logits, stream);
+}
+
+extern "C" int score_catalog_cands_struct_sizes(int64_t* out, int32_t n) {
+  const int64_t v[] = {(int64_t)sizeof(score_catalog_cands_t), (int64_t)offsetof(score_catalog_cands_t, cand_off),
+                       (int64_t)offsetof(score_catalog_cands_t, cand_idx), (int64_t)offsetof(score_catalog_cands_t, max_count)};
+  const int32_t have = (int32_t)(sizeof(v) / sizeof(v[0]));
+  if (!out || n < have) return SCORE_E_BADARG;
+  for (int32_t i = 0; i < have; ++i) out[i] = v[i];
+  return have;
 }
 
 // sizes and late-field offsets of the catalogue call's structures, as score_abi_struct_sizes gives them for the others: -> the

@@ -350,10 +350,14 @@ struct CatalogArgs {
   unsigned long long* part;
   int32_t* top_idx; float* top_logit; float* all_logits;
   uint32_t n_rows; int32_t* id_status;
+  // score_catalog_select_in (the candidate form): per line the catalogue indices cand_idx[cand_off[l] .. cand_off[l + 1]),
+  // strictly ascending; chunk / nchunk cut max_count list POSITIONS, all_logits is aligned with cand_idx
+  const int64_t* cand_off; const int32_t* cand_idx; int max_count;
 };
 void score_catalog_chunks(int L, int N, int k, int* chunk, int* nchunk);
 int score_catalog_zcat(const CatalogArgs& a, hipStream_t s);
 int score_catalog_select(const CatalogArgs& a, hipStream_t s);
+int score_catalog_select_in(const CatalogArgs& a, hipStream_t s);
 // delf.hip: the DELF point baseline (point_model.py:200-249) between the gather and the scatter.  Per side (0: user_seq rows
 // against target_item through dense; 1: item_seq rows against target_user through dense_1) X [B * T, C] with row stride ldx,
 // the saved keys [B * T, C] (live rows only), attention weights att [B, T], rep [B, C]; backward: ds [B, T] (gradient at the

@@ -365,14 +365,21 @@ def catalog_quality_device(top_idx, target_idx):
     return tuple(float(x) for x in out.cpu().tolist())
 
 
-def evaluate_catalog(model, batches, catalog, neg_sample_num=TEST_NEG_SAMPLE_NUM, k=10, exclude_history=None, return_lists=False):
+def evaluate_catalog(model, batches, catalog, neg_sample_num=TEST_NEG_SAMPLE_NUM, k=10, exclude_history=None, return_lists=False,
+                     candidates=None):
     """Ranking metrics against the WHOLE catalogue instead of the sampled negatives: for every target line of a loader's eval
     batches (lines of 1 + neg_sample_num samples, the first candidate the positive) the model's k best items of `catalog`
     (model.recommend_async), then catalog_quality_device on the positive's position -> its six numbers.
 
     exclude_history: a PointLogStore -- the items of each user's history are excluded from the user's list, the positive
-    itself never.  return_lists: also the lists and the positives' catalogue indices, (six, top_idx [n_lines, k], target_idx)."""
+    itself never.  return_lists: also the lists and the positives' catalogue indices, (six, top_idx [n_lines, k], target_idx).
+
+    candidates="line": every line is restricted to its own 1 + neg_sample_num items -- the reference's sampled protocol on the
+    catalogue route (repeated negatives collapse; negatives the catalogue does not hold drop out; the positive is always in the
+    list).  None: the whole catalogue.  Anything else raises ValueError."""
     import torch
+    if candidates is not None and candidates != "line":
+        raise ValueError("evaluate_catalog: candidates must be None or \"line\", got %r" % (candidates,))
     tops, tgts = [], []
     for batch_data in batches:
         db = model.device_batch(batch_data)
@@ -385,7 +392,12 @@ def evaluate_catalog(model, batches, catalog, neg_sample_num=TEST_NEG_SAMPLE_NUM
         exclude = None
         if exclude_history is not None:
             exclude = _history_exclusions(exclude_history, lines[2][:, 0], pos_ids)
-        top = model.recommend_async(lines, catalog, k=k, exclude=exclude, active_slices=db.active_slices)[0]
+        own = None
+        if candidates == "line":
+            n_cand = 1 + neg_sample_num
+            own = (torch.arange(L + 1, device=pos_ids.device, dtype=torch.int64) * n_cand,
+                   db.tensors[5].view(L, n_cand, -1)[:, :, 0].reshape(-1))
+        top = model.recommend_async(lines, catalog, k=k, exclude=exclude, active_slices=db.active_slices, candidates=own)[0]
         tops.append(top.clone()); tgts.append(tgt.to(torch.int32))
     top, tgt = torch.cat(tops), torch.cat(tgts)
     six = catalog_quality_device(top, tgt)

@@ -1796,7 +1796,8 @@ class SCOREBASE(object):
         self._rank_ws[key] = ent
         return ent
 
-    def recommend_async(self, lines, catalog, k=10, exclude=None, all_logits=False, active_slices=None):
+    def recommend_async(self, lines, catalog, k=10, exclude=None, all_logits=False, active_slices=None, candidates=None,
+                        max_candidates=None):
         """The k items of `catalog` (an ItemCatalog of this model) the model puts first for each of L users: (idx [L, k] int32
         catalogue indices, logits [L, k]) as device tensors, plus all_logits [L, N] when asked for.  Ordered by descending fc3
         logit -- the argument of y_pred's sigmoid --, ties to the lower index; an excluded item is never returned, and a line
@@ -1806,7 +1807,14 @@ class SCOREBASE(object):
         them from an eval batch).  exclude: per line the item ids (column 0 of the catalogue's rows) not to return -- a list of L
         arrays, or a CSR pair (offsets [L + 1], ids); ids the catalogue does not hold are dropped, order and repeats do not
         matter.  active_slices: None = from the longest length (one read-back), 0 = all T, or score_batch_t's value.
-        GRU4Rec and Caser; the catalogue is rebuilt first if the model's weights have moved since it was built."""
+        GRU4Rec and Caser; the catalogue is rebuilt first if the model's weights have moved since it was built.
+
+        candidates: per line the item ids to choose AMONG, in the two forms of exclude (ItemCatalog.candidates maps them), or
+        what ItemCatalog.candidates returned; only those pairs are scored (score_catalog_topk_in) -- same order, padding and
+        exclusions, and the same bits per pair as without.  A line without candidates is all padding.  max_candidates: the size
+        the launch is planned for, given to skip the read-back of the longest line's count (too small costs time, never
+        results).  With all_logits the third result is then (cand_off [L + 1], cand_idx, cand_logits): the listed pairs'
+        logits, aligned with cand_idx."""
         if self.rank_unsupported is not None:
             raise NotImplementedError("%s has no catalogue pass: %s" % (type(self).__name__, self.rank_unsupported))
         if not isinstance(catalog, ItemCatalog) or catalog.model is not self:
@@ -1833,12 +1841,14 @@ class SCOREBASE(object):
         excl_off = excl_idx = None
         if exclude is not None:
             excl_off, excl_idx = catalog.exclusions(exclude, L)
-        ws = self._catalog_buffers(L, N, k)
         idx = torch.empty((L, k), dtype=torch.int32, device=self.device)
         logit = torch.empty((L, k), dtype=torch.float32, device=self.device)
-        full = torch.empty((L, N), dtype=torch.float32, device=self.device) if all_logits else None
         ln = _lib.CatalogLines(_ptr(useq), _ptr(length), _ptr(tuser), L, int(active_slices),
                                _ptr(excl_off) if excl_off is not None else None, _ptr(excl_idx) if excl_idx is not None else None)
+        if candidates is not None:
+            return self._recommend_in(catalog, ln, L, k, candidates, max_candidates, all_logits, idx, logit)
+        ws = self._catalog_buffers(L, N, k)
+        full = torch.empty((L, N), dtype=torch.float32, device=self.device) if all_logits else None
         with self._Pin(self):
             catalog.refresh()            # (flushes the time-tiled optimizer for the whole table: every item row is read)
             st = self._state(ws)
@@ -1848,10 +1858,46 @@ class SCOREBASE(object):
         _lib.check(rc, "score_catalog_topk")
         return (idx, logit, full) if all_logits else (idx, logit)
 
-    def recommend(self, lines, catalog, k=10, exclude=None, active_slices=None):
+    def _recommend_in(self, catalog, ln, L, k, candidates, max_candidates, all_logits, idx, logit):
+        """recommend_async's call with candidate lists (score_catalog_topk_in); ln: the lines, whose tensors the caller holds"""
+        if isinstance(candidates, tuple) and len(candidates) == 3 and torch.is_tensor(candidates[1]) and \
+                candidates[1].dtype == torch.int32 and not torch.is_tensor(candidates[2]):
+            cand_off, cand_idx, longest = candidates                 # (what ItemCatalog.candidates returned)
+            if int(cand_off.numel()) != L + 1:
+                raise ValueError("candidates: offsets for %d lines, expected %d" % (int(cand_off.numel()) - 1, L))
+        elif max_candidates is not None:
+            cand_off, cand_idx = catalog._line_indices(candidates, L, "candidates")
+            longest = None
+        else:
+            cand_off, cand_idx, longest = catalog.candidates(candidates, L)
+        max_count = int(max_candidates) if max_candidates is not None else int(longest)
+        if max_count < 1:
+            raise ValueError("max_candidates = %d, expected >= 1" % max_count)
+        key = ("catalog_in", L, max_count, k)
+        ws = self._rank_ws.pop(key, None)
+        if ws is None:
+            nbytes = _lib.catalog_cands_plan(self.cfg, L, max_count, k)[2]
+            while len(self._rank_ws) >= self.max_workspaces:
+                torch.cuda.synchronize(self.device)
+                self._rank_ws.pop(next(iter(self._rank_ws)))
+            ws = torch.empty(((nbytes + 3) // 4,), dtype=torch.float32, device=self.device)
+        self._rank_ws[key] = ws
+        own = torch.empty((max(1, int(cand_idx.numel())),), dtype=torch.float32, device=self.device) if all_logits else None
+        cd = _lib.CatalogCands(_ptr(cand_off), _ptr(cand_idx), max_count)
+        with self._Pin(self):
+            catalog.refresh()
+            st = self._state(ws)
+            cat = catalog.struct()
+            rc = self.lib.score_catalog_topk_in(C.byref(self.cfg), C.byref(st), C.byref(cat), C.byref(ln), C.byref(cd), k, _ptr(idx),
+                                                _ptr(logit), _ptr(own) if own is not None else None, self._stream())
+        _lib.check(rc, "score_catalog_topk_in")
+        return (idx, logit, (cand_off, cand_idx, own)) if all_logits else (idx, logit)
+
+    def recommend(self, lines, catalog, k=10, exclude=None, active_slices=None, candidates=None):
         """recommend_async, read back: per line the item ids (column 0 of the catalogue's rows) and sigmoid(logit) as lists,
-        best first, the -1 padding dropped -> (ids, scores).  Raises as rank does when an id outside the table was fed."""
-        idx, logit = self.recommend_async(lines, catalog, k=k, exclude=exclude, active_slices=active_slices)
+        best first, the -1 padding dropped -> (ids, scores).  candidates: as recommend_async takes them.  Raises as rank does
+        when an id outside the table was fed."""
+        idx, logit = self.recommend_async(lines, catalog, k=k, exclude=exclude, active_slices=active_slices, candidates=candidates)
         ids = catalog.ids[idx.clamp(min=0).long()]
         idx, ids, y = idx.cpu().numpy(), ids.cpu().numpy(), torch.sigmoid(logit).cpu().numpy()
         self.check_ids()
@@ -2133,21 +2179,22 @@ class ItemCatalog(object):
         pos = torch.searchsorted(self.ids, ids).clamp(max=self.N - 1)
         return pos, self.ids[pos] == ids
 
-    def exclusions(self, exclude, L):
-        """exclude -- a list of L arrays of item ids, or a CSR pair (offsets [L + 1], ids) -- as score_catalog_lines_t takes it:
-        (excl_off int64 [L + 1], excl_idx int32) on the device, the ids mapped to catalogue indices (those the catalogue does not
-        hold dropped), ascending and without repeats within a line.  The mapping runs on the device."""
+    def _line_indices(self, lists, L, what):
+        """Per-line lists of item ids -- a list of L arrays, or a CSR pair (offsets [L + 1], ids) -- as the library takes them:
+        (off int64 [L + 1], idx int32) on the device, the ids mapped to catalogue indices (those the catalogue does not hold
+        dropped), ascending and without repeats within a line; idx is never empty (one unused 0 when nothing is left).  The
+        mapping runs on the device."""
         dev = self.ids.device
         host = lambda x: np.asarray(x.cpu() if torch.is_tensor(x) else x)
-        if len(exclude) == 2 and not isinstance(exclude, list) and np.ndim(host(exclude[0])) == 1 and \
-                host(exclude[0]).size == L + 1:
-            off = (exclude[0] if torch.is_tensor(exclude[0]) else torch.from_numpy(np.ascontiguousarray(host(exclude[0])))).to(
+        if len(lists) == 2 and not isinstance(lists, list) and np.ndim(host(lists[0])) == 1 and \
+                host(lists[0]).size == L + 1:
+            off = (lists[0] if torch.is_tensor(lists[0]) else torch.from_numpy(np.ascontiguousarray(host(lists[0])))).to(
                 device=dev, dtype=torch.int64)
-            ids = (exclude[1] if torch.is_tensor(exclude[1]) else torch.from_numpy(np.ascontiguousarray(host(exclude[1])))).to(dev)
+            ids = (lists[1] if torch.is_tensor(lists[1]) else torch.from_numpy(np.ascontiguousarray(host(lists[1])))).to(dev)
         else:
-            if len(exclude) != L:
-                raise ValueError("exclude must hold one array of item ids per line (%d), or be a CSR pair (offsets, ids)" % L)
-            parts = [host(x).reshape(-1).astype(np.int64) for x in exclude]
+            if len(lists) != L:
+                raise ValueError("%s must hold one array of item ids per line (%d), or be a CSR pair (offsets, ids)" % (what, L))
+            parts = [host(x).reshape(-1).astype(np.int64) for x in lists]
             off = torch.from_numpy(np.concatenate([[0], np.cumsum([p.size for p in parts])]).astype(np.int64)).to(dev)
             ids = torch.from_numpy(np.concatenate(parts) if parts else np.zeros((0,), dtype=np.int64)).to(dev)
         n = int(ids.numel())
@@ -2156,11 +2203,24 @@ class ItemCatalog(object):
         line = torch.searchsorted(off, torch.arange(n, device=dev, dtype=torch.int64), right=True) - 1
         pos, found = self.indices_of(ids)
         key = torch.unique(line[found] * self.N + pos[found].long())            # sorted: by line, then by index
-        excl_off = torch.searchsorted(key, torch.arange(L + 1, device=dev, dtype=torch.int64) * self.N)
-        excl_idx = (key % self.N).to(torch.int32)
-        if excl_idx.numel() == 0:
-            excl_idx = torch.zeros((1,), dtype=torch.int32, device=dev)
-        return excl_off.contiguous(), excl_idx.contiguous()
+        out_off = torch.searchsorted(key, torch.arange(L + 1, device=dev, dtype=torch.int64) * self.N)
+        out_idx = (key % self.N).to(torch.int32)
+        if out_idx.numel() == 0:
+            out_idx = torch.zeros((1,), dtype=torch.int32, device=dev)
+        return out_off.contiguous(), out_idx.contiguous()
+
+    def exclusions(self, exclude, L):
+        """exclude -- a list of L arrays of item ids, or a CSR pair (offsets [L + 1], ids) -- as score_catalog_lines_t takes it:
+        (excl_off int64 [L + 1], excl_idx int32) on the device, the ids mapped to catalogue indices (those the catalogue does not
+        hold dropped), ascending and without repeats within a line.  The mapping runs on the device."""
+        return self._line_indices(exclude, L, "exclude")
+
+    def candidates(self, candidates, L):
+        """candidates -- the two forms exclude takes -- as score_catalog_cands_t takes it: (cand_off int64 [L + 1], cand_idx
+        int32, max_count), the same mapping as exclusions (ids the catalogue does not hold dropped, each line ascending without
+        repeats).  max_count, the longest line's count (at least 1: the plan's size), costs one read-back."""
+        off, idx = self._line_indices(candidates, L, "candidates")
+        return off, idx, max(1, int((off[1:] - off[:-1]).max().item()))
 
 
 MODELS = {"SCORE": SCORE, "RIA": RIA, "RCA": RCA, "SCORE_USER": SCORE_USER, "SCORE_ITEM": SCORE_ITEM, "RRN": RRN, "GCMC": GCMC,
