@@ -306,6 +306,13 @@ int score_coattn_fwd(const float* table, int64_t n_rows, int32_t D, int32_t F, i
                      float* out1, int32_t ld1, float* out2, int32_t ld2,
                      float* info, int32_t ldi, float* rsave, int32_t mode, void* stream);
 
+/* The time slices per chunk that the forward above (F1 = 0) or score_forward's launch of both co-attention calls
+ * (feature counts F0, F1) takes for B samples of T computed slices: mode 0 with K <= 10, one float4 per lane and id
+ * lists that fit an instance run csrc/embed.hip coattn_fwd_kernel_units, where a wave works through a chunk of
+ * consecutive slices of one sample.  0 = the shape runs coattn_fwd_kernel (one unit per wave); < 0 = bad argument.
+ * A function of the shape alone, never of a timing. */
+int score_coattn_fwd_chunk(int32_t D, int32_t K, int32_t B, int32_t T, int32_t F0, int32_t F1);
+
 /* Backward of the above.  g1/g2/ginfo are the gradients of out1/out2/info with
  * the same strides.  Scatter-adds row gradients into grad_table [n_rows, D]
  * (row 0 skipped: mask, score.py:47), writes dzsum [BT] (sum_i dz_i, feeds the
@@ -528,7 +535,12 @@ typedef struct {
                            dz = 0 times its row: the same bits on a finite table; csrc/embed.hip);
                            bit 16 (65536) = the co-attention backward requests a unit's ids and saved scalars one unit ahead,
                            behind the pass-1 rows of the unit before, instead of at the top of the unit's own iteration
-                           (same registers, same arithmetic, same bits; K <= 10 only; measured inside the noise at cfg-3).
+                           (same registers, same arithmetic, same bits; K <= 10 only; measured inside the noise at cfg-3);
+                           bit 17 (131072) = the fused gather + co-attention forward runs one unit per wave
+                           (coattn_fwd_kernel) where it would work through a chunk of slices per wave
+                           (coattn_fwd_kernel_units, see score_coattn_fwd_chunk): same bits, the A/B arm;
+                           bits 20 .. 23 = no switch but a number, for measurements: a chunk length 1 .. 15 to take in
+                           place of score_coattn_fwd_chunk's (0 = the rule).
                            The ONLY switches of the launch sequence: the library reads no environment variable       */
   uint8_t* row_flags;   /* optional [n_table_rows] row state of the dense table optimizer (see
                            score_adam_rows): score_backward (scatter_mode 0) marks every row it

@@ -71,7 +71,9 @@ class Workspace(C.Structure):
 class State(C.Structure):
     # debug_flags: the A/B switches of the launch sequence, described bit by bit in include/score_hip.h (score_state_t);
     # the co-attention backward's are bit 15 (32768: the rows of relu-inactive neighbours are loaded too) and bit 16
-    # (65536: a unit's ids and saved scalars are requested one unit ahead, not in the unit's own iteration)
+    # (65536: a unit's ids and saved scalars are requested one unit ahead, not in the unit's own iteration); the
+    # co-attention forward's is bit 17 (131072: one unit per wave, coattn_fwd_kernel, where the several-units form would
+    # run), and bits 20 .. 23 hold a chunk length for it to measure with (0: the launcher's rule)
     _fields_ = [("table", c_f), ("n_table_rows", C.c_int64), ("w", c_f), ("workspace", c_f),
                 ("workspace_bytes", C.c_int64), ("scatter_mode", C.c_int32), ("global_batch", C.c_int32),
                 ("gemm_mode", C.c_int32), ("debug_flags", C.c_int32), ("row_flags", C.c_void_p),
@@ -240,6 +242,7 @@ _SIGS = {
     "score_coattn_fwd": [c_f, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, c_i, c_i,
                          c_f, c_f, c_f, c_f, C.c_int32, c_f, C.c_int32, c_f, C.c_int32, c_f, C.c_int32,
                          C.c_void_p],
+    "score_coattn_fwd_chunk": [C.c_int32] * 6,
     "score_coattn_bwd": [c_f, c_f, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, c_i, c_i,
                          c_f, c_f, c_f, C.c_int32, c_f, C.c_int32, c_f, C.c_int32, c_f, c_f, c_f, C.c_int64,
                          C.c_int32, C.c_void_p],

@@ -685,7 +685,215 @@ __global__ __launch_bounds__(256, (KMAX <= 10 && SPL == 1) ? 4 : 1) void coattn_
   }
 }
 
-#define COATTN_DISPATCH(KERNEL, EXTRA, SPLV, KV, ...)                                     \
+// ------------------------------------------------------------------ forward, several units per wave
+// The forward in the form of the backward's NM > 0 instances (mode 0, one slot per lane, K <= 10): a group works through
+// a CHUNK of up to CoattnArgs.CH consecutive time slices of ONE sample instead of one unit.
+//  * What does not depend on the slice is loaded once per chunk, together with the first unit's ids: w1 / w2, the lane's
+//    partial of the target term (cpart: target ids -> table row, or cc.tgt) and its slice of w_t.
+//  * A unit's K*F ids of each index tensor are held one element per lane (MetaList, as in the backward) and handed out
+//    by ds_bpermute where the row address is formed: 2 NM registers, not 2 KMAX.  Ids outside the table become row 0 on
+//    the lane that loaded them, where they are also noted for id_status (one atomicOr per chunk).
+//  * The ids of the chunk's next unit are requested right behind the 2K rows of the current one and arrive with them;
+//    behind the chunk's last unit the request goes to unit 0 and is dropped.
+// So a unit costs one dependent round trip (its rows), a chunk two more in front (ids + constants, then the target row).
+// A unit's stores are issued in front of the next unit's row requests: loads and stores leave vmcnt in issue order, so the
+// wait for those rows (vmcnt = the id requests behind them) asks nothing of the stores that the rows' own latency has
+// not long covered.  Arithmetic, its order and the stores are those of coattn_fwd_kernel: bit-identical outputs.
+template <int I>
+__device__ __forceinline__ void unit_ids_load1(MetaList<int32_t>& la, MetaList<int32_t>& lb, const int32_t* __restrict__ i1,
+                                               const int32_t* __restrict__ i2, int KF, int per, int gc) {
+  const int e = I * per + gc;
+  const int ei = e < KF ? e : KF - 1;
+  meta_at<I>(la) = i1[ei];
+  meta_at<I>(lb) = i2[ei];
+}
+// the id lists alone of the unit whose index-tensor position is ui (every load unconditional, to a clamped, valid position)
+template <int NM>
+__device__ __forceinline__ void unit_ids_load(MetaList<int32_t>& la, MetaList<int32_t>& lb, const CoattnArgs& a, const CoattnCall& cc,
+                                              int64_t ui, int gl) {
+  const int KF = a.K * cc.F, per = cc.F << cc.ksh;
+  const int32_t* __restrict__ i1 = cc.idx1 + ui * KF;
+  const int32_t* __restrict__ i2 = cc.idx2 + ui * KF;
+  const int gc = gl < per ? gl : per - 1;
+  unit_ids_load1<0>(la, lb, i1, i2, KF, per, gc);
+  if constexpr (NM > 1) unit_ids_load1<1>(la, lb, i1, i2, KF, per, gc);
+  if constexpr (NM > 2) unit_ids_load1<2>(la, lb, i1, i2, KF, per, gc);
+  if constexpr (NM > 3) unit_ids_load1<3>(la, lb, i1, i2, KF, per, gc);
+}
+template <int I>
+__device__ __forceinline__ void unit_ids_clamp1(MetaList<int32_t>& la, MetaList<int32_t>& lb, uint32_t n_rows, bool& bad1, bool& bad2) {
+  const int32_t x = meta_at<I>(la), y = meta_at<I>(lb);
+  const bool b1 = (uint32_t)x >= n_rows, b2 = (uint32_t)y >= n_rows;
+  bad1 |= b1; bad2 |= b2;
+  meta_at<I>(la) = b1 ? 0 : x;
+  meta_at<I>(lb) = b2 ? 0 : y;
+}
+template <int NM>
+__device__ __forceinline__ void unit_ids_clamp(MetaList<int32_t>& la, MetaList<int32_t>& lb, uint32_t n_rows, bool& bad1, bool& bad2) {
+  unit_ids_clamp1<0>(la, lb, n_rows, bad1, bad2);
+  if constexpr (NM > 1) unit_ids_clamp1<1>(la, lb, n_rows, bad1, bad2);
+  if constexpr (NM > 2) unit_ids_clamp1<2>(la, lb, n_rows, bad1, bad2);
+  if constexpr (NM > 3) unit_ids_clamp1<3>(la, lb, n_rows, bad1, bad2);
+}
+
+template <int KMAX, int NM>
+__global__ __launch_bounds__(256, 4) void coattn_fwd_kernel_units(const CoattnArgs a) {
+  const int ci = (int)blockIdx.x >= a.c[1].first_block ? 1 : 0;
+  const CoattnCall& cc = a.c[ci];
+  const int GS = cc.GS, nslots = cc.nslots, F = cc.F, K = a.K, D4 = a.D4, ksh = cc.ksh;
+  const int lane = threadIdx.x & 63;
+  const int wave = (((int)blockIdx.x - cc.first_block) * (int)blockDim.x + (int)threadIdx.x) >> 6;
+  const int upw = 64 / GS;
+  const int gl = lane & (GS - 1);
+  const int gbase = lane - gl;      // first lane of this lane's group
+  const int chunk = wave * upw + lane / GS;
+  const bool chunk_ok = chunk < a.n_chunks;
+  const int c = chunk_ok ? chunk : 0;  // clamp: inactive groups still take part in shuffles
+  const int b_idx = c / a.cps;
+  const int t0 = (c - b_idx * a.cps) * a.CH;
+  const int nt = chunk_ok ? min(a.CH, a.T - t0) : 0;      // the last chunk of a sample is short
+  // unit i of the chunk is (b_idx, t0 + i) over the ACTIVE time slices; the index tensors keep their [B, Tidx, K, F] strides
+  const int Dx = nslots * 4;
+  const int D = D4 * 4;
+  const float* __restrict__ table = a.table;
+  const float* __restrict__ W = cc.W;
+  const uint32_t NR = a.n_rows;
+
+  const bool sok = gl < nslots;
+  const int sc = sok ? gl : 0;
+  const int f = sc / D4;
+  const int coff = (sc - f * D4) * 4;
+
+  // once per chunk, all of it requested before anything is used: w1 / w2 / w_t, the target, the first unit's ids
+  MetaList<int32_t> ca, cb, na, nb;      // the current and the next unit's id lists
+  const float4 w1 = ld4(W + Dx + sc * 4);
+  const float4 w2 = ld4(W + 2 * Dx + sc * 4);
+  const float4 wt = ld4(W + sc * 4);
+  float4 tv;
+  uint32_t tr = 0;
+  if (cc.tidx) tr = (uint32_t)cc.tidx[(int64_t)b_idx * F + f];
+  else tv = ld4(cc.tgt + (int64_t)b_idx * cc.ldt + sc * 4);
+  unit_ids_load<NM>(ca, cb, a, cc, (int64_t)b_idx * a.Tidx + t0, gl);
+  const float bias = cc.bias[0];
+  __builtin_amdgcn_sched_barrier(0);
+  if (cc.tidx) {      // (an id outside the table is the dummy row here; target_fwd_kernel reports it)
+    tr = tr >= NR ? 0u : tr;
+    tv = ld4(table + (int64_t)tr * D + coff);
+  }
+  // c = w_t . target + bias (constant over t and i): the lane's partial, reduced with every unit's scores
+  float cpart = 0.f;
+  if (chunk_ok && sok) cpart += dot4(tv, wt);
+
+  bool bad1 = false, bad2 = false;
+  unit_ids_clamp<NM>(ca, cb, NR, bad1, bad2);
+  for (int i = 0; i < a.CH; ++i) {
+    const bool unit_ok = i < nt;
+    if (!__any(unit_ok)) break;      // (the groups of a wave own chunks of their own: the longest decides)
+    const bool ok = unit_ok && sok;
+    // Every address of the unit is formed here, from copies of the sample and slice numbers that the compiler cannot look
+    // through: hoisted out of the loop, the per-lane 64-bit pointers of the four outputs and the two id lists are 12
+    // registers and more that live through all of it, and were spilled (44 registers, the rows' addresses with them).
+    int bq = b_idx, tq = t0 + i, gq = gl, fq = f, cq = coff;
+    asm volatile("" : "+v"(bq), "+v"(tq), "+v"(gq), "+v"(fq), "+v"(cq));
+    const int u = bq * a.T + tq;
+    const int64_t uin = i + 1 < nt ? (int64_t)bq * a.Tidx + tq + 1 : 0;
+    // the 2K rows (16 B per lane each), then the next unit's ids; nothing is consumed before all of it is requested.
+    // Inactive lanes / units and k >= K read a valid clamped address and are zeroed by a select afterwards.
+    int32_t ra[KMAX], rb[KMAX];
+    unit_ids<KMAX, NM>(ra, ca, K, F, ksh, fq, gbase);
+    unit_ids<KMAX, NM>(rb, cb, K, F, ksh, fq, gbase);
+    float4 v1[KMAX], yv[KMAX];
+#pragma unroll
+    for (int k = 0; k < KMAX; ++k) {
+      v1[k] = ld4(table + (int64_t)ra[k] * D + cq);
+      yv[k] = ld4(table + (int64_t)rb[k] * D + cq);
+    }
+    unit_ids_load<NM>(na, nb, a, cc, uin, gq);
+    __builtin_amdgcn_sched_barrier(0);
+    // (w1 / w2 as the loop holds them: the compiler kept a second, pairwise copy of both for packed arithmetic through the
+    //  whole loop, eight more registers while the rows are in flight)
+    float4 w1q = w1, w2q = w2;
+    asm volatile("" : "+v"(w1q.x), "+v"(w1q.y), "+v"(w1q.z), "+v"(w1q.w), "+v"(w2q.x), "+v"(w2q.y), "+v"(w2q.z), "+v"(w2q.w));
+    // coattn_fwd_kernel zeroes the rows of dead lanes and of k >= K by selects, eight per neighbour.  The same bits with one:
+    // a dead lane's score partial is what the arithmetic makes of zero rows (zpart: 0 unless w1 / w2 are not finite), it
+    // stores nothing else; k >= K enters neither the scores nor out1 (both test k < K), and out2's sum skips it (adding
+    // +0 never changes a sum that started at +0).
+    const float4 z = make_float4(0.f, 0.f, 0.f, 0.f);
+    float zpart = 0.f;
+    zpart += dot4(z, w1q) + dot4(z, w2q);
+    float4 sum2 = z;
+    float part[KMAX];
+#pragma unroll
+    for (int k = 0; k < KMAX; ++k) {
+      part[k] = 0.f;
+      if (k < K) sum2 = add4(sum2, yv[k]);
+      part[k] += dot4(v1[k], w1q) + dot4(yv[k], w2q);
+      part[k] = ok ? part[k] : zpart;
+    }
+    float red[KMAX + 1];          // the K partial scores and the target term: reduced across the group together
+#pragma unroll
+    for (int k = 0; k < KMAX; ++k) red[k] = (k < K) ? part[k] : 0.f;
+    red[KMAX] = cpart;
+    group_sum_n<KMAX + 1>(red, GS);
+    const float cst = red[KMAX] + bias;
+    // The next unit's ids are taken up HERE, in front of this unit's stores: they were requested right behind the rows and
+    // have long arrived.  Taken up at the top of the next iteration, the wait for them stood behind the stores and, the
+    // atten_info loop storing a number of times the compiler cannot count, drained them: vmcnt(0), a round trip per unit.
+    unit_ids_clamp<NM>(na, nb, NR, bad1, bad2);
+    // (an empty statement that needs the clamped ids: without it the clamp, and the wait with it, sank behind the stores)
+    asm volatile("" : "+v"(na.r0), "+v"(nb.r0));
+    if constexpr (NM > 1) asm volatile("" : "+v"(na.r1), "+v"(nb.r1));
+    static_assert(NM <= 2, "instances: one or two registers per id list");
+    __builtin_amdgcn_sched_barrier(0);
+    float r[KMAX];
+    float rmax = 0.f, rsum = 0.f;  // relu output >= 0
+#pragma unroll
+    for (int k = 0; k < KMAX; ++k) {
+      r[k] = 0.f;
+      if (k < K) {
+        r[k] = fmaxf(red[k] + cst, 0.f);
+        rmax = fmaxf(rmax, r[k]);
+        rsum += r[k];
+      }
+    }
+    // atten_info = [K*r_0..K*r_{K-1}, sum_i r_i (K times)]  (score.py:165-166)
+    if (unit_ok) {
+      for (int e = gq; e < 2 * K; e += GS) {
+        float val = rsum;
+        float rv = 0.f;
+#pragma unroll
+        for (int k = 0; k < KMAX; ++k)
+          if (e == k) rv = r[k];
+        if (e < K) {
+          val = (float)K * rv;
+          cc.rsave[(int64_t)u * K + e] = rv;
+        }
+        cc.info[(int64_t)u * cc.ldi + e] = val;
+      }
+    }
+    float p[KMAX];
+    float den = 0.f;
+#pragma unroll
+    for (int k = 0; k < KMAX; ++k) {
+      p[k] = (k < K) ? expf(r[k] - rmax) : 0.f;
+      den += p[k];
+    }
+    const float inv_den = 1.0f / den;
+    if (ok) {
+      float4 o = make_float4(0.f, 0.f, 0.f, 0.f);
+#pragma unroll
+      for (int k = 0; k < KMAX; ++k)
+        if (k < K) o = fma4(p[k] * inv_den, v1[k], o);
+      st4(cc.out1 + (int64_t)u * cc.ld1 + gq * 4, o);
+      const float fk = (float)K;
+      st4(cc.out2 + (int64_t)u * cc.ld2 + gq * 4, make_float4(sum2.x / fk, sum2.y / fk, sum2.z / fk, sum2.w / fk));
+    }
+    ca = na; cb = nb;
+  }
+  if (a.id_status && (bad1 || bad2)) atomicOr(a.id_status, (bad1 ? 1 << cc.bit1 : 0) | (bad2 ? 1 << cc.bit2 : 0));
+}
+
+#define COATTN_DISPATCH(KERNEL, EXTRA, SPLV, KV, ...)                                  \
   do {                                                                                    \
     if (SPLV == 1) {                                                                      \
       if (KV <= 4) { hipLaunchKernelGGL((KERNEL<4, 1 EXTRA>), __VA_ARGS__); }             \
@@ -739,6 +947,53 @@ static int coattn_check(const void* table, int64_t n_rows, int D, int F, int K, 
   return 0;
 }
 
+// The forward's several-units-per-wave form (coattn_fwd_kernel_units): registers per id list of a call (ids only: the
+// backward's lists also hold 3K scalars), 0 where a feature set does not fit a group
+static inline int coattn_fwd_id_regs(int GS, int F, int K) {
+  const int ksh = coattn_ksh(GS, F);
+  return ksh < 0 ? 0 : (K + (1 << ksh) - 1) >> ksh;
+}
+// Registers per list of the instance that serves every call of a launch; 0: coattn_fwd_kernel (mode != 0, K > 10, more
+// than one slot per lane, lists longer than an instance holds).  Instances: one or two registers at K <= 4, one at
+// K <= 10 -- with two or four, the KMAX = 10 kernel no longer fits 128 registers (8 and 13 spilled: the lists are 2 x 2
+// per register, and the selects between them hold more), and a spilled loop is what this form is there to avoid.
+static int coattn_fwd_units_regs(int D, int K, int mode, int ncalls, const int* F) {
+  if (mode != 0 || K > 10) return 0;
+  int need = 1;
+  for (int c = 0; c < ncalls; ++c) {
+    int GS, SPL, nslots;
+    coattn_geom(D, F[c], &GS, &SPL, &nslots);
+    const int n = coattn_fwd_id_regs(GS, F[c], K);
+    if (SPL != 1 || n == 0 || n > (K <= 4 ? 2 : 1)) return 0;
+    need = n > need ? n : need;
+  }
+  return need;
+}
+// Time slices per chunk, from the shape alone.  A wave makes two round trips per chunk (ids and constants, then the
+// target row) and one per unit, so longer chunks mean fewer trips per unit -- and fewer waves, each with more to do
+// behind the others.  COATTN_FWD_SLOTS waves are resident at once (256 CUs x 4 SIMDs x 4 waves of <= 128 VGPRs).  Two
+// slices where that still leaves two full rounds of them, one slice otherwise: a launch that cannot fill the machine
+// twice is over soonest with every unit in flight at once.  Measured at cfg-3 (B = 1024, 18 slices, 2 calls; the kernel
+// in the step, then alone on the low-duplication probe; coattn_fwd_kernel: 94.2 and 172.0 us): 1 slice 85.9 / 169.7 us,
+// 2: 78.3 / 171.4, 3: 80.2 / 174.6, 4: 80.1 / 174.6, 6: 79.0 and 81.7 / 179.7 and 180.8, 9: 86.9 / 187.0 -- past two,
+// nothing more comes off the step's kernel, and the memory-bound probe loses a little with every slice added
+// (profiles/coattn_fwd_units.md section 4).
+static const int COATTN_FWD_SLOTS = 4096;
+int score_coattn_fwd_chunk_rule(int D, int K, int B, int T, int ncalls, const int* F) {
+  if (coattn_fwd_units_regs(D, K, 0, ncalls, F) == 0) return 0;
+  int64_t waves = 0;      // with two slices per chunk
+  for (int c = 0; c < ncalls; ++c) {
+    int GS, SPL, nslots;
+    coattn_geom(D, F[c], &GS, &SPL, &nslots);
+    waves += cdiv64((int64_t)B * ((T + 1) / 2), 64 / GS);
+  }
+  return waves >= 2 * COATTN_FWD_SLOTS ? 2 : 1;
+}
+template <int KMAX, int NM>
+static void coattn_fwd_units_launch(int total, hipStream_t s, const CoattnArgs& a) {
+  hipLaunchKernelGGL((coattn_fwd_kernel_units<KMAX, NM>), dim3(total), dim3(256), 0, s, a);
+}
+
 // Launch 1 or 2 calls (ncalls) of the forward in a single grid.
 int score_coattn_fwd_multi(CoattnArgs& a, int ncalls, int D, int B, hipStream_t s) {
   int spl = 1, total = 0;
@@ -746,6 +1001,31 @@ int score_coattn_fwd_multi(CoattnArgs& a, int ncalls, int D, int B, hipStream_t 
   a.n_units = B * a.T;
   if (a.Tidx <= 0) a.Tidx = a.T;
   if (a.n_rows == 0) a.n_rows = 0x80000000u;      // (no row count given: int32 ids >= 0 pass)
+  // several units per wave wherever an instance holds the id lists of every call (a.CH > 0 on entry: that chunk length
+  // instead of the rule's, for measurements)
+  const int Fs[2] = {a.c[0].F, a.c[ncalls > 1 ? 1 : 0].F};
+  const int nm = a.fwd_one_unit ? 0 : coattn_fwd_units_regs(D, a.K, a.mode, ncalls, Fs);
+  if (nm > 0) {
+    if (a.CH <= 0) a.CH = score_coattn_fwd_chunk_rule(D, a.K, B, a.T, ncalls, Fs);
+    a.cps = (a.T + a.CH - 1) / a.CH;
+    a.n_chunks = B * a.cps;
+    for (int c = 0; c < 2; ++c) {
+      if (c >= ncalls) { a.c[c] = a.c[0]; a.c[c].first_block = 0x7fffffff; continue; }
+      int SPLc;
+      coattn_geom(D, a.c[c].F, &a.c[c].GS, &SPLc, &a.c[c].nslots);
+      a.c[c].ksh = coattn_ksh(a.c[c].GS, a.c[c].F);
+      a.c[c].first_block = total;
+      total += (int)cdiv64(cdiv64(a.n_chunks, 64 / a.c[c].GS), 4);
+    }
+    if (a.K <= 4) {
+      if (nm == 1) coattn_fwd_units_launch<4, 1>(total, s, a);
+      else coattn_fwd_units_launch<4, 2>(total, s, a);
+    } else {
+      coattn_fwd_units_launch<10, 1>(total, s, a);
+    }
+    SCORE_CHECK_LAUNCH();
+    return 0;
+  }
   for (int c = 0; c < 2; ++c) {
     if (c >= ncalls) { a.c[c] = a.c[0]; a.c[c].first_block = 0x7fffffff; continue; }
     int SPLc;
@@ -813,6 +1093,12 @@ int score_coattn_bwd_multi(CoattnArgs& a, int ncalls, int D, int B, float* const
     }
   }
   return 0;
+}
+
+extern "C" int score_coattn_fwd_chunk(int32_t D, int32_t K, int32_t B, int32_t T, int32_t F0, int32_t F1) {
+  if (D <= 0 || (D & 3) || K <= 0 || B <= 0 || T <= 0 || F0 <= 0 || F1 < 0) return SCORE_E_BADARG;
+  const int F[2] = {F0, F1};
+  return score_coattn_fwd_chunk_rule(D, K, B, T, F1 > 0 ? 2 : 1, F);
 }
 
 // ABI wrappers: one call; `tgt` is [B, F*D] contiguous

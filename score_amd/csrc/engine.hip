@@ -633,13 +633,15 @@ enum {
   DF_GRU_STEPWISE = 1, DF_HEAD_FUSED_ANY_B = 2, DF_GRU_F32_REC = 4, DF_NO_PANEL = 8, DF_PANEL_DX = 16, DF_SORT_LIB = 32,
   DF_HEAD_UNFUSED = 64, DF_ATTN_UNFUSED = 128, DF_SORT_OWN = 256, DF_NO_PS = 512, DF_PS_FWD_ONLY = 1024, DF_PS_BWD_ONLY = 2048,
   DF_ONE_STREAM = 4096, DF_G4R_COMPOSED = 8192, DF_COATTN_ALL_ROWS = 32768,
-  DF_COATTN_META_AHEAD = 65536
+  DF_COATTN_META_AHEAD = 65536, DF_COATTN_FWD_ONE_UNIT = 131072
 };
+// (bits 20 .. 23 are no switch but a number: the chunk length of the co-attention forward, 0 = the launcher's rule)
+static inline int coattn_fwd_ch_of(const score_state_t* st) { return (st->debug_flags >> 20) & 15; }
 // (DF_G4R_COMPOSED / Flags.g4r_composed, bit 13, reads "one recurrence per launch": GRU4Rec's composed form, and DEEMS's two
 //  recurrences as one launch per side instead of one grouped launch)
 struct Flags {
   bool gru_stepwise, head_fused_any_b, gru_f32_rec, no_panel, panel_dx, sort_lib, head_unfused, attn_unfused, sort_own, no_ps,
-      ps_fwd_only, ps_bwd_only, one_stream, g4r_composed, coattn_all_rows, coattn_meta_ahead;
+      ps_fwd_only, ps_bwd_only, one_stream, g4r_composed, coattn_all_rows, coattn_meta_ahead, coattn_fwd_one_unit;
 };
 static inline Flags flags_of(const score_state_t* st) {
   auto on = [st](int bit) { return (st->debug_flags & bit) != 0; };
@@ -649,7 +651,7 @@ static inline Flags flags_of(const score_state_t* st) {
   o.head_unfused = on(DF_HEAD_UNFUSED); o.attn_unfused = on(DF_ATTN_UNFUSED); o.no_ps = on(DF_NO_PS);
   o.ps_fwd_only = on(DF_PS_FWD_ONLY); o.ps_bwd_only = on(DF_PS_BWD_ONLY); o.one_stream = on(DF_ONE_STREAM);
   o.g4r_composed = on(DF_G4R_COMPOSED); o.coattn_all_rows = on(DF_COATTN_ALL_ROWS);
-  o.coattn_meta_ahead = on(DF_COATTN_META_AHEAD);
+  o.coattn_meta_ahead = on(DF_COATTN_META_AHEAD); o.coattn_fwd_one_unit = on(DF_COATTN_FWD_ONE_UNIT);
   return o;
 }
 // Flags.one_stream (debug_flags bit 12): no second stream at all -- everything the passes would fork runs on the caller's
@@ -1709,6 +1711,8 @@ int fwd_open(const Pass& c, FwdState* f) {
       cc.bias = d.coattn ? W + P.ca_b[i] : nullptr;
       cc.out1 = ws + w.xside[0] + k.col1[i]; cc.out2 = ws + w.xside[1] + k.col2[i]; cc.info = ws + w.info + k.info_col[i];
     }
+    ca.fwd_one_unit = c.fl.coattn_fwd_one_unit ? 1 : 0;      // (debug_flags bit 17: one unit per wave, A/B)
+    ca.CH = coattn_fwd_ch_of(st);                            // (bits 20 .. 23: a chunk length to measure; 0 = the rule)
     G(score_coattn_fwd_multi(ca, 2, d.D, B, s));
   }
   if (st->gather_done_event) HIPTRY(hipEventRecord((hipEvent_t)st->gather_done_event, s));

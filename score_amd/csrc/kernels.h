@@ -104,7 +104,12 @@ struct CoattnArgs {
   int all_rows;                               // backward, A/B (debug_flags bit 15): the rows of relu-inactive k are loaded too
   int meta_ahead;                             // backward, A/B (debug_flags bit 16): a unit's ids and saved scalars are requested one
                                               // unit ahead, not at the top of its own iteration
+  int fwd_one_unit;                           // forward, A/B (debug_flags bit 17): coattn_fwd_kernel, one unit per wave, wherever
+                                              // the launcher would take coattn_fwd_kernel_units
+  int CH, cps, n_chunks;                      // forward (set by the launcher): time slices per chunk of coattn_fwd_kernel_units,
+                                              // chunks per sample = ceil(T / CH), chunks per call = B * cps
 };
+int score_coattn_fwd_chunk_rule(int D, int K, int B, int T, int ncalls, const int* F);   // CH of a shape; 0: the one-unit kernel
 int score_coattn_fwd_multi(CoattnArgs& a, int ncalls, int D, int B, hipStream_t s);
 int score_coattn_bwd_multi(CoattnArgs& a, int ncalls, int D, int B, float* const dW[2], float* scratch,
                            int64_t scratch_floats, int atomic_scatter, ColsumJobs* cq, hipStream_t s);
