@@ -813,6 +813,26 @@ int score_catalog_topk_in(const score_config_t* cfg, const score_state_t* st, co
  * for a null pointer or n too small. */
 int score_catalog_cands_struct_sizes(int64_t* out, int32_t n);
 
+/* ---- ... with the users' histories excluded, built on the device (csrc/histexcl.hip) -----------------------------------------
+ * score_catalog_lines_t.excl_off / excl_idx for L users of a score_point_log_store_t (declared below): line l's list is the set
+ * of catalogue indices j with cat_ids[j] anywhere in user user_ids[l]'s WHOLE segment user_hist_seq[off[u - 1] .. off[u]) -- not
+ * only the kept or windowed part -- and cat_ids[j] != keep_ids[l] (keep_ids NULL: nothing is kept back).  Written strictly
+ * ascending and without repeats into excl_idx[excl_off[l] .. excl_off[l + 1]); excl_off [L + 1] is exact.  A user id outside
+ * 1 .. n_users and a user without events have empty lists.  cat_ids [N]: the catalogue's id column, strictly ascending (signed).
+ * Only user_hist_off / user_hist_seq / n_users of the store are read.
+ * A pure function of its inputs: a bitmap per (line, range of the catalogue) in LDS, set by binary search per history entry
+ * (an idempotent OR, the only atomic), read off in index order; offsets by a count, a reduce-then-scan and a fill.  No host wait,
+ * no workgroup waits on another.  If the total exceeds `capacity` (entries of excl_idx) nothing is written at or past it and bit 0
+ * of *status is set (other bits and an exact fit leave *status alone: the caller clears it); excl_off stays exact.
+ * score_catalog_history_exclusions_plan, host only: *range = catalogue indices a workgroup covers, *n_ranges = ceil(N / range),
+ * *threads = history entries a workgroup takes a stride (a segment of any length is walked), *temp_bytes = the workspace;
+ * max_events (the longest segment, >= 0) takes no part in the rule at present.  Any of the four pointers may be NULL.
+ * Refusals, all before any launch: a null pointer, struct_bytes, L, N <= 0, capacity < 0 (SCORE_E_BADARG); L * n_ranges >= 2^31
+ * (SCORE_E_SHAPE); temp_bytes below the plan's (SCORE_E_WORKSPACE). */
+/* (score_catalog_history_exclusions itself is declared behind the store's struct, below) */
+int score_catalog_history_exclusions_plan(int32_t L, int32_t N, int64_t max_events, int32_t* range, int32_t* n_ranges,
+                                          int32_t* threads, int64_t* temp_bytes);
+
 /* ---- one training step in one call (csrc/step.hip) -----------------------------------------------------------------------
  * The steady-state step of model.train (score.py:101-116) for a caller that runs the time-tiled table optimizer with the
  * look-ahead (score_adam_catchup_ids_through) and sorts the next batch's index plan a step ahead: exactly
@@ -973,6 +993,26 @@ typedef struct {
 int score_point_batch_assemble_log(const score_point_log_store_t* store, int64_t first_line, int32_t n_lines, int32_t per_line,
                                    int32_t T, int32_t Fu, int32_t Fi, const score_batch_out_t* out, int32_t* length2,
                                    void* stream);
+
+/* Lines for arbitrary users, one launch that writes these four tensors and nothing else: for line l with user u = user_ids[l]
+ * exactly what score_point_batch_assemble_log writes for the first sample of a single-form line whose line_user is u -- the last
+ * min(user_hist_len[u - 1], T) ids of the kept history as rows of item_rows, padded by repeating the last; length =
+ * user_hist_len[u - 1]; target_user = user_rows[u - 1] -- and known[l] = 1.  A user of 1 .. n_users without events is a cold
+ * user: zeros, length 0, known 1.  An id outside 1 .. n_users: zeros, length 0, known 0.  The same user may occur several times.
+ * Plain stores, no atomics.  The user side and the two row tables are required; line_user, line_items, line_last_item and the
+ * item side may be NULL.  Refusals, all before the launch: a null pointer, struct_bytes, L, T, Fu, Fi <= 0 (SCORE_E_BADARG);
+ * T * Fi > 8192, L * T * Fi >= 2^31 (SCORE_E_SHAPE). */
+int score_point_user_lines(const score_point_log_store_t* store, const int32_t* user_ids, int32_t L, int32_t T, int32_t Fu,
+                           int32_t Fi, int32_t* user_seq /* [L, T, Fi] */, int32_t* length /* [L] */,
+                           int32_t* target_user /* [L, Fu] */, int32_t* known /* [L] */, void* stream);
+
+/* The L users' history exclusions for score_catalog_topk / score_catalog_topk_in (csrc/histexcl.hip; the contract stands with
+ * score_catalog_history_exclusions_plan, above). */
+int score_catalog_history_exclusions(const score_point_log_store_t* store, const int32_t* user_ids,
+                                     const int32_t* keep_ids /* [L] or NULL */, int32_t L,
+                                     const int32_t* cat_ids /* [N], strictly ascending */, int32_t N,
+                                     int64_t* excl_off /* [L + 1] */, int32_t* excl_idx, int64_t capacity, int32_t* status,
+                                     void* temp, int64_t temp_bytes, void* stream);
 
 /* ---- the temporal graph store from the behaviour log, on the device (csrc/graphbuild.hip) ---- */
 

@@ -313,6 +313,12 @@ _SIGS = {
     "score_catalog_topk_in": [C.POINTER(Config), C.POINTER(State), C.POINTER(Catalog), C.POINTER(CatalogLines),
                               C.POINTER(CatalogCands), C.c_int32, c_i, c_f, c_f, C.c_void_p],
     "score_catalog_cands_struct_sizes": [C.POINTER(C.c_int64), C.c_int32],
+    "score_point_user_lines": [C.POINTER(PointLogStore), c_i, C.c_int32, C.c_int32, C.c_int32, C.c_int32, c_i, c_i, c_i, c_i,
+                               C.c_void_p],
+    "score_catalog_history_exclusions_plan": [C.c_int32, C.c_int32, C.c_int64, C.POINTER(C.c_int32), C.POINTER(C.c_int32),
+                                              C.POINTER(C.c_int32), C.POINTER(C.c_int64)],
+    "score_catalog_history_exclusions": [C.POINTER(PointLogStore), c_i, c_i, C.c_int32, c_i, C.c_int32, C.c_void_p, c_i, C.c_int64,
+                                         c_i, C.c_void_p, C.c_int64, C.c_void_p],
 }
 # (score_rank_workspace_bytes returns a status; the size comes back through its last argument)
 _STATUS_RETURN = ("score_rank_workspace_bytes",)
@@ -462,6 +468,15 @@ def catalog_cands_plan(cfg, L, max_count, k):
     check(load().score_catalog_cands_plan(C.byref(cfg), int(L), int(max_count), int(k), C.byref(chunk), C.byref(nchunk), C.byref(n)),
           "score_catalog_cands_plan")
     return chunk.value, nchunk.value, n.value
+
+
+def history_exclusions_plan(L, N, max_events=0):
+    """(range, n_ranges, threads, temp bytes) of score_catalog_history_exclusions for L lines against N items:
+    score_catalog_history_exclusions_plan"""
+    rng, nr, th, n = C.c_int32(0), C.c_int32(0), C.c_int32(0), C.c_int64(0)
+    check(load().score_catalog_history_exclusions_plan(int(L), int(N), int(max_events), C.byref(rng), C.byref(nr), C.byref(th),
+                                                       C.byref(n)), "score_catalog_history_exclusions_plan")
+    return rng.value, nr.value, th.value, n.value
 
 
 def workspace_field(cfg, B, name):

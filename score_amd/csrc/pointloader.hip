@@ -286,3 +286,56 @@ extern "C" int score_point_batch_assemble_log(const score_point_log_store_t* st,
   SCORE_CHECK_LAUNCH();
   return 0;
 }
+
+// ---- lines for arbitrary users (PointLogStore.user_lines) -----------------------------------------------------------------------
+// What part 0 of point_assemble_log_kernel writes for the FIRST sample of a single-form line whose line_user is user_ids[l], and
+// nothing else: no expanded batch, no zeroed 2-hop spans.  A workgroup per line; known[l] = the id lies in 1 .. n_users.  Plain
+// stores only.
+struct PointUserLines {
+  const int64_t* user_off; const int32_t* user_seq; const int32_t* user_len;
+  const int32_t* user_ids; const int32_t* user_rows; const int32_t* item_rows;
+  int64_t n_users, n_items;
+  int32_t* out_seq; int32_t* length; int32_t* out_user; int32_t* known;
+  int T, Fu, Fi;
+};
+
+__global__ __launch_bounds__(PL_THREADS) void point_user_lines_kernel(PointUserLines a) {
+  __shared__ int32_t lds[PL_LDS_WORDS];
+  const int tid = (int)threadIdx.x;
+  const int64_t l = blockIdx.x;
+  const int pu = a.T * a.Fi;
+  const int64_t U = a.n_users, I = a.n_items;
+  const PlLogHist hu{a.user_ids, a.user_off, a.user_seq, a.user_len, 1, U, U + 1, I};
+  pl_resolve(lds, hu, a.item_rows, l, 1, a.T, a.Fi);
+  __syncthreads();
+  pl_put_span(a.out_seq + l * pu, lds, pu, pu);
+  const int64_t eu = (int64_t)a.user_ids[l] - 1;
+  const bool ok = eu >= 0 && eu < U;
+  for (int f = tid; f < a.Fu; f += PL_THREADS) a.out_user[l * a.Fu + f] = ok ? a.user_rows[eu * a.Fu + f] : 0;
+  if (tid == 0) {
+    a.length[l] = ok ? a.user_len[eu] : 0;
+    a.known[l] = ok ? 1 : 0;
+  }
+}
+
+extern "C" int score_point_user_lines(const score_point_log_store_t* st, const int32_t* user_ids, int32_t L, int32_t T, int32_t Fu,
+                                      int32_t Fi, int32_t* user_seq, int32_t* length, int32_t* target_user, int32_t* known,
+                                      void* stream) {
+  if (!st || !user_ids || !user_seq || !length || !target_user || !known) return SCORE_E_BADARG;
+  if (st->struct_bytes != (int64_t)sizeof(score_point_log_store_t)) return SCORE_E_BADARG;
+  if (L <= 0 || T <= 0 || Fu <= 0 || Fi <= 0) return SCORE_E_BADARG;
+  if (!st->user_hist_off || !st->user_hist_seq || !st->user_hist_len || !st->user_rows || !st->item_rows || st->n_users <= 0 ||
+      st->n_items <= 0)
+    return SCORE_E_BADARG;
+  if ((int64_t)T * Fi > PL_LDS_WORDS || (int64_t)L * T * Fi >= ((int64_t)1 << 31) || (int64_t)L * Fu >= ((int64_t)1 << 31))
+    return SCORE_E_SHAPE;
+  PointUserLines a;
+  a.user_off = st->user_hist_off; a.user_seq = st->user_hist_seq; a.user_len = st->user_hist_len;
+  a.user_ids = user_ids; a.user_rows = st->user_rows; a.item_rows = st->item_rows;
+  a.n_users = st->n_users; a.n_items = st->n_items;
+  a.out_seq = user_seq; a.length = length; a.out_user = target_user; a.known = known;
+  a.T = T; a.Fu = Fu; a.Fi = Fi;
+  hipLaunchKernelGGL(point_user_lines_kernel, dim3((unsigned)L), dim3(PL_THREADS), 0, (hipStream_t)stream, a);
+  SCORE_CHECK_LAUNCH();
+  return 0;
+}

@@ -406,6 +406,48 @@ def evaluate_catalog(model, batches, catalog, neg_sample_num=TEST_NEG_SAMPLE_NUM
     return (six, top, tgt) if return_lists else six
 
 
+def evaluate_catalog_users(model, store, catalog, k=10, exclude_history=True, candidates=None, lines_per_call=100,
+                           return_lists=False):
+    """evaluate_catalog over a PointLogStore's own target lines without a loader: a line's user is line_user, its positive the
+    first of its line_items, taken straight from the store's tensors, lines_per_call lines a call of
+    model.recommend_users_async -- no expanded batch, no strided copies, no read-back per batch.  exclude_history: each user's
+    history in the store is excluded, the positive itself never.  candidates="line": every line is restricted to its own
+    1 + neg_sample_num items.  Returns what evaluate_catalog(loader batches of the same store, catalog, exclude_history=store or
+    None, ...) returns: the six numbers, with return_lists also (top_idx [n_lines, k], target_idx [n_lines])."""
+    import torch
+    if candidates is not None and candidates != "line":
+        raise ValueError("evaluate_catalog_users: candidates must be None or \"line\", got %r" % (candidates,))
+    if getattr(model, "rank_unsupported", None) is not None:
+        raise NotImplementedError("%s has no catalogue pass: %s" % (type(model).__name__, model.rank_unsupported))
+    if store._dev is None:
+        raise ValueError("evaluate_catalog_users: the store must be on a device (build='device' or .to_device())")
+    n_lines, per_line, step = int(store.n_lines), int(store.per_line), int(lines_per_call)
+    if n_lines <= 0 or step <= 0:
+        raise ValueError("evaluate_catalog_users: no target lines, or lines_per_call <= 0")
+    users = store._dev["line_user"][:n_lines]
+    items = store._dev["line_items"][:n_lines * per_line].view(n_lines, per_line)
+    tops, tgts, founds = [], [], []
+    for a in range(0, n_lines, step):
+        b = min(n_lines, a + step)
+        L = b - a
+        pos_ids = items[a:b, 0].contiguous()
+        tgt, found = catalog.indices_of(pos_ids)
+        own, longest = None, None
+        if candidates == "line":
+            own = (torch.arange(L + 1, device=pos_ids.device, dtype=torch.int64) * per_line, items[a:b].reshape(-1))
+            longest = per_line
+        top = model.recommend_users_async(users[a:b], store, catalog, k=k, exclude_history=bool(exclude_history), keep=pos_ids,
+                                          candidates=own, max_candidates=longest)[0]
+        tops.append(top.clone()); tgts.append(tgt.to(torch.int32)); founds.append(found.all())
+    if not bool(torch.stack(founds).all().item()):
+        raise ValueError("evaluate_catalog_users: a line's positive item is not in the catalogue")
+    top, tgt = torch.cat(tops), torch.cat(tgts)
+    six = catalog_quality_device(top, tgt)
+    if hasattr(model, "check_ids"):
+        model.check_ids()
+    return (six, top, tgt) if return_lists else six
+
+
 def _history_exclusions(store, user_ids, keep_ids):
     """CSR pair (offsets [L + 1], item ids) of the L users' histories in a PointLogStore -- user u's run of user_hist_seq, all of
     it, not only the part a batch reads -- without each line's own keep id.  A user id the store does not know has none."""

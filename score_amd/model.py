@@ -1796,8 +1796,8 @@ class SCOREBASE(object):
         self._rank_ws[key] = ent
         return ent
 
-    def recommend_async(self, lines, catalog, k=10, exclude=None, all_logits=False, active_slices=None, candidates=None,
-                        max_candidates=None):
+    def recommend_async(self, lines, catalog, k=10, exclude=None, exclude_idx=None, all_logits=False, active_slices=None,
+                        candidates=None, max_candidates=None):
         """The k items of `catalog` (an ItemCatalog of this model) the model puts first for each of L users: (idx [L, k] int32
         catalogue indices, logits [L, k]) as device tensors, plus all_logits [L, N] when asked for.  Ordered by descending fc3
         logit -- the argument of y_pred's sigmoid --, ties to the lower index; an excluded item is never returned, and a line
@@ -1814,9 +1814,15 @@ class SCOREBASE(object):
         exclusions, and the same bits per pair as without.  A line without candidates is all padding.  max_candidates: the size
         the launch is planned for, given to skip the read-back of the longest line's count (too small costs time, never
         results).  With all_logits the third result is then (cand_off [L + 1], cand_idx, cand_logits): the listed pairs'
-        logits, aligned with cand_idx."""
+        logits, aligned with cand_idx.
+
+        exclude_idx: the exclusions as the library takes them, (excl_off int64 [L + 1], excl_idx int32) device tensors of
+        catalogue INDICES, strictly ascending within a line (ItemCatalog.history_exclusions returns such a pair); nothing is
+        mapped or read back.  Not together with exclude (ValueError)."""
         if self.rank_unsupported is not None:
             raise NotImplementedError("%s has no catalogue pass: %s" % (type(self).__name__, self.rank_unsupported))
+        if exclude is not None and exclude_idx is not None:
+            raise ValueError("exclude (item ids) and exclude_idx (catalogue indices) are mutually exclusive")
         if not isinstance(catalog, ItemCatalog) or catalog.model is not self:
             raise ValueError("catalog must be an ItemCatalog built for this model")
         k = int(k)
@@ -1841,6 +1847,13 @@ class SCOREBASE(object):
         excl_off = excl_idx = None
         if exclude is not None:
             excl_off, excl_idx = catalog.exclusions(exclude, L)
+        elif exclude_idx is not None:
+            excl_off, excl_idx = exclude_idx
+            if not (torch.is_tensor(excl_off) and torch.is_tensor(excl_idx) and excl_off.dtype == torch.int64 and
+                    excl_idx.dtype == torch.int32 and excl_off.device == self.device and excl_idx.device == self.device and
+                    excl_off.is_contiguous() and excl_idx.is_contiguous() and int(excl_off.numel()) == L + 1 and
+                    int(excl_idx.numel()) >= 1):
+                raise ValueError("exclude_idx must be (int64 [%d], int32 [>= 1]) contiguous tensors on %s" % (L + 1, self.device))
         idx = torch.empty((L, k), dtype=torch.int32, device=self.device)
         logit = torch.empty((L, k), dtype=torch.float32, device=self.device)
         ln = _lib.CatalogLines(_ptr(useq), _ptr(length), _ptr(tuser), L, int(active_slices),
@@ -1903,6 +1916,56 @@ class SCOREBASE(object):
         self.check_ids()
         keep = idx >= 0
         return [ids[l][keep[l]].tolist() for l in range(idx.shape[0])], [y[l][keep[l]].tolist() for l in range(idx.shape[0])]
+
+    # ------------------------------------------------------------------ ... by user id (score_point_user_lines,
+    # score_catalog_history_exclusions)
+    def recommend_users_async(self, user_ids, store, catalog, k=10, exclude_history=True, keep=None, candidates=None,
+                              max_candidates=None, all_logits=False):
+        """recommend_async for users named by id: `store`, a PointLogStore on this model's device, has their histories and rows;
+        the lines (store.user_lines) and, with exclude_history, each user's history as exclusions
+        (catalog.history_exclusions: every item of the user's window of the log, not only what a batch reads) are built on the
+        device and handed to score_catalog_topk / score_catalog_topk_in through recommend_async.  user_ids [L]: a device tensor
+        or host array.  keep [L]: per line an item id that is never excluded (an evaluation's positive).  candidates /
+        max_candidates / all_logits: as recommend_async takes them.  -> (idx [L, k], logits [L, k], known [L] int32), plus
+        recommend_async's third result with all_logits.  A user the store does not know (known 0) is scored as a cold user
+        with a zero user row and raises nothing here.  active_slices is a bound, min(T, store.max_user_len): with
+        candidates=None, or max_candidates given, the call queues work and returns without a host wait."""
+        if self.rank_unsupported is not None:
+            raise NotImplementedError("%s has no catalogue pass: %s" % (type(self).__name__, self.rank_unsupported))
+        if not isinstance(catalog, ItemCatalog) or catalog.model is not self:
+            raise ValueError("catalog must be an ItemCatalog built for this model")
+        c = self.cfg
+        T, Fi, Fu = int(c.max_time_len), int(c.item_fnum), int(c.user_fnum)
+        if (int(store.Fu), int(store.Fi)) != (Fu, Fi):
+            raise ValueError("the store has (user_fnum, item_fnum) = %r, the model %r" % ((store.Fu, store.Fi), (Fu, Fi)))
+        if store._dev is None or store.device != self.device:
+            raise ValueError("the store must be on the model's device %s (build='device' or .to_device())" % (self.device,))
+        catalog.check_store(store)
+        uid = (user_ids if torch.is_tensor(user_ids) else torch.from_numpy(np.ascontiguousarray(np.asarray(user_ids)))).to(
+            device=self.device, dtype=torch.int32).contiguous().view(-1)
+        useq, length, tuser, known = store.user_lines(uid, T)
+        excl = catalog.history_exclusions(store, uid, keep) if exclude_history else None
+        out = self.recommend_async((useq, length, tuser), catalog, k=k, exclude_idx=excl, all_logits=all_logits,
+                                   active_slices=_active_slices_of(self, min(T, store.max_user_len)), candidates=candidates,
+                                   max_candidates=max_candidates)
+        return (out[0], out[1], known) + tuple(out[2:])
+
+    def recommend_users(self, user_ids, store, catalog, k=10, exclude_history=True, keep=None, candidates=None):
+        """recommend_users_async, read back as recommend reads back: (ids, scores) per line, best first, the -1 padding
+        dropped.  ValueError naming the first user id the store does not know; raises as rank does when an id outside the table
+        was fed."""
+        idx, logit, known = self.recommend_users_async(user_ids, store, catalog, k=k, exclude_history=exclude_history, keep=keep,
+                                                       candidates=candidates)[:3]
+        ids = catalog.ids[idx.clamp(min=0).long()]
+        idx, ids, y, known = idx.cpu().numpy(), ids.cpu().numpy(), torch.sigmoid(logit).cpu().numpy(), known.cpu().numpy()
+        if not known.all():
+            l = int(np.flatnonzero(known == 0)[0])
+            uid = user_ids.reshape(-1)[l].item() if torch.is_tensor(user_ids) else np.asarray(user_ids).reshape(-1)[l]
+            raise ValueError("recommend_users: user id %d (line %d) is not one of the store's users 1 .. %d"
+                             % (int(uid), l, store.n_users))
+        self.check_ids()
+        keep_ = idx >= 0
+        return [ids[l][keep_[l]].tolist() for l in range(idx.shape[0])], [y[l][keep_[l]].tolist() for l in range(idx.shape[0])]
 
     def save(self, sess, path):
         """All global variables incl. the Adam slots, under the TF variable names."""
@@ -2214,6 +2277,65 @@ class ItemCatalog(object):
         (excl_off int64 [L + 1], excl_idx int32) on the device, the ids mapped to catalogue indices (those the catalogue does not
         hold dropped), ascending and without repeats within a line.  The mapping runs on the device."""
         return self._line_indices(exclude, L, "exclude")
+
+    def check_store(self, store):
+        """ValueError unless `store` (a PointLogStore on the catalogue's device) describes the catalogue's items as the catalogue
+        does: every catalogue id is one of the store's items and its row in store.item_rows is the catalogue's.  Compared on the
+        device once per store (one read-back), then remembered."""
+        seen = self.__dict__.setdefault("_stores_ok", {})
+        if seen.get(id(store)) is store._dev:
+            return
+        rows = store._dev["item_rows"] if store._dev is not None else None
+        if rows is None or rows.device != self.rows.device or rows.dim() != 2 or rows.shape[1] != self.rows.shape[1]:
+            raise ValueError("the store's item_rows %s do not go with the catalogue's rows %s on %s"
+                             % (None if rows is None else tuple(rows.shape), tuple(self.rows.shape), self.rows.device))
+        at = self.ids.long() - (store.n_users + 1)
+        inside = (at >= 0) & (at < store.n_items)
+        same = inside & (rows[at.clamp(0, store.n_items - 1)] == self.rows).all(1)
+        if not bool(same.all().item()):
+            raise ValueError("the catalogue holds an item the store does not know, or with another feature row")
+        seen.clear()                 # (one store at a time is remembered: the entry holds the store's tensors alive)
+        seen[id(store)] = store._dev
+
+    def history_exclusions(self, store, user_ids, keep_ids=None):
+        """(excl_off int64 [L + 1], excl_idx int32) on the device, as score_catalog_lines_t and recommend_async(exclude_idx=)
+        take them: per line the catalogue indices of every item in user user_ids[l]'s whole history segment of `store` (a
+        PointLogStore on the catalogue's device), without the line's keep id; ascending, no repeats; an unknown user's list is
+        empty (score_catalog_history_exclusions).  The buffer holds max(1, L * min(store.max_user_events, N)) indices -- an
+        upper bound, so nothing is read back."""
+        if store._dev is None or store.device != self.ids.device:
+            raise ValueError("the store must be on the catalogue's device %s" % (self.ids.device,))
+        dev = self.ids.device
+        i32 = lambda x: (x if torch.is_tensor(x) else torch.from_numpy(np.ascontiguousarray(np.asarray(x)))).to(
+            device=dev, dtype=torch.int32).contiguous().view(-1)
+        uid = i32(user_ids)
+        L = int(uid.numel())
+        if L == 0:
+            raise ValueError("no users")
+        keep = None
+        if keep_ids is not None:
+            keep = i32(keep_ids)
+            if int(keep.numel()) != L:
+                raise ValueError("keep_ids names %d lines, user_ids %d" % (int(keep.numel()), L))
+        cache = self.__dict__.setdefault("_excl_ws", {})
+        ent = cache.get(L)
+        if ent is None:
+            nbytes = _lib.history_exclusions_plan(L, self.N, store.max_user_events)[3]
+            if len(cache) >= 4:
+                torch.cuda.synchronize(dev)
+                cache.pop(next(iter(cache)))
+            ent = cache[L] = (torch.empty((nbytes,), dtype=torch.uint8, device=dev), nbytes)
+        status = self.__dict__.get("_excl_status")
+        if status is None:
+            status = self._excl_status = torch.zeros((1,), dtype=torch.int32, device=dev)
+        cap = max(1, L * min(int(store.max_user_events), self.N))
+        excl_off = torch.empty((L + 1,), dtype=torch.int64, device=dev)
+        excl_idx = torch.empty((cap,), dtype=torch.int32, device=dev)
+        rc = self.model.lib.score_catalog_history_exclusions(C.byref(store.struct), _ptr(uid), _ptr(keep) if keep is not None else None,
+                                                             L, _ptr(self.ids), self.N, _ptr(excl_off), _ptr(excl_idx), cap,
+                                                             _ptr(status), _ptr(ent[0]), ent[1], _lib.current_stream(dev))
+        _lib.check(rc, "score_catalog_history_exclusions")
+        return excl_off, excl_idx
 
     def candidates(self, candidates, L):
         """candidates -- the two forms exclude takes -- as score_catalog_cands_t takes it: (cand_off int64 [L + 1], cand_idx

@@ -574,6 +574,87 @@ class PointLogStore(object):
         self._upload(dev, have)
         return self
 
+    # ---- lines for arbitrary users (csrc/pointloader.hip: score_point_user_lines) ----------------------------------------
+    def _user_extremes(self):
+        """(longest user segment, longest kept length): one read-back per store, at the first ask, then cached"""
+        ext = getattr(self, "_user_ext", None)
+        if ext is None:
+            off, ln = self.user_hist_off, self.user_hist_len
+            if isinstance(off, np.ndarray):
+                ext = (int(np.diff(off).max()), int(ln.max()))
+            else:
+                import torch
+                ext = tuple(int(v) for v in torch.stack([(off[1:] - off[:-1]).amax(), ln.amax().to(off.dtype)]).cpu().tolist())
+            self._user_ext = ext
+        return ext
+
+    @property
+    def max_user_events(self):
+        """the longest user segment of user_hist_seq (all events of the window, not only the kept ones)"""
+        return self._user_extremes()[0]
+
+    @property
+    def max_user_len(self):
+        """the longest kept length, max(user_hist_len)"""
+        return self._user_extremes()[1]
+
+    def _check_max_len(self, max_len):
+        T = int(max_len)
+        if T <= 0 or T * self.Fi > 8192:
+            raise ValueError("max_len %d: max_len * Fi must lie in 1 .. 8192" % T)
+        return T
+
+    def host_user_lines(self, user_ids, max_len):
+        """user_lines in numpy, from .arrays(): (user_seq [L, T, Fi], length [L], target_user [L, Fu], known [L]) int32.  Line
+        l is what the loaders write for the first sample of a target line of user user_ids[l] at max_len T: the last
+        min(user_hist_len, T) ids of the kept history as rows of item_rows, padded by repeating the last; the untruncated kept
+        length; the user's row.  A user without events: zeros, length 0, known 1; an id outside 1 .. n_users: zeros, length 0,
+        known 0.  Needs no GPU."""
+        T = self._check_max_len(max_len)
+        a = self.arrays()
+        off, seq, ln = a["user_hist_off"], a["user_hist_seq"], a["user_hist_len"]
+        U, I = self.n_users, self.n_items
+        u = np.asarray(to_host(user_ids)).reshape(-1).astype(np.int64)
+        known = (u >= 1) & (u <= U)
+        e = np.where(known, u - 1, 0)
+        length = np.where(known, ln[e], 0).astype(np.int64)
+        m = np.clip(np.minimum(length, T), 0, None)
+        b = np.maximum(off[e + 1] - m, off[e])
+        m = np.minimum(m, off[e + 1] - b)
+        pos = b[:, None] + np.minimum(np.arange(T)[None, :], np.maximum(m - 1, 0)[:, None])
+        ids = seq[np.clip(pos, 0, max(len(seq) - 1, 0))].astype(np.int64) if len(seq) else np.zeros(pos.shape, dtype=np.int64)
+        row = ids - (U + 1)
+        ok = (m > 0)[:, None] & (row >= 0) & (row < I)
+        user_seq = np.where(ok[:, :, None], self.item_rows[np.clip(row, 0, I - 1)], 0).astype(np.int32)
+        target_user = np.where(known[:, None], self.user_rows[e], 0).astype(np.int32)
+        return user_seq, length.astype(np.int32), target_user, known.astype(np.int32)
+
+    def user_lines(self, user_ids, max_len):
+        """(user_seq [L, T, Fi], length [L], target_user [L, Fu], known [L]) int32 device tensors for ANY users of the store --
+        what model.lines_of takes from a loader batch, without a target line, an expanded batch or a read-back: one launch
+        (score_point_user_lines) on the current stream into one buffer.  user_ids: a device tensor or host array [L]; the same
+        user may occur several times.  The contract is host_user_lines'.  The store must be on a device (build="device" or
+        .to_device()): RuntimeError otherwise."""
+        import ctypes as C
+        import torch
+        from . import _lib
+        if self._dev is None:
+            raise RuntimeError("PointLogStore.user_lines: the store is not on a device (build='device' or .to_device() first)")
+        T = self._check_max_len(max_len)
+        uid = device_i32(user_ids, self.device).reshape(-1)
+        L = int(uid.numel())
+        if L == 0:
+            raise ValueError("no users")
+        Fu, Fi = self.Fu, self.Fi
+        flat = torch.empty((L * (T * Fi + Fu + 2),), dtype=torch.int32, device=self.device)
+        sizes = (L * T * Fi, L * Fu, L, L)
+        user_seq, target_user, length, known = torch.split(flat, sizes)
+        ptr = lambda t: C.c_void_p(t.data_ptr())
+        rc = _lib.load().score_point_user_lines(C.byref(self.struct), ptr(uid), L, T, Fu, Fi, ptr(user_seq), ptr(length),
+                                                ptr(target_user), ptr(known), _lib.current_stream(self.device))
+        _lib.check(rc, "score_point_user_lines")
+        return user_seq.view(L, T, Fi), length, target_user.view(L, Fu), known
+
     def store_bytes(self):
         """bytes of the arrays a batch reads (the row tables excluded: both forms hold them)"""
         total = 0

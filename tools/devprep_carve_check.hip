@@ -1,8 +1,8 @@
 // hipcc --offload-arch=gfx950 -std=c++17 -Xarch_host -fsanitize=address,undefined tools/devprep_carve_check.hip score_amd/csrc/sort.hip -o /tmp/devprep_carve_check && /tmp/devprep_carve_check
 //
-// The eight workspace layouts of the device data builds (csrc/devprep.h's Carver) on the host, no GPU: each is carved with a null
+// The nine workspace layouts of the device data builds and of the history exclusions (csrc/devprep.h's Carver) on the host, no GPU: each is carved with a null
 // base (sizes only: every pointer must stay null) and over a malloc of exactly that size (every range inside the block, one
-// behind the other, and written to, so the sanitizer sees a range that leaves the block).  The five files are included as they
+// behind the other, and written to, so the sanitizer sees a range that leaves the block).  The six files are included as they
 // are, each in a namespace of its own; the sizes are also held against the public *_temp_bytes.
 #include <cstdio>
 #include <cstdlib>
@@ -29,6 +29,9 @@ namespace lr {
 }
 namespace cc {
 #include "../score_amd/csrc/ccmr.hip"
+}
+namespace hx {
+#include "../score_amd/csrc/histexcl.hip"
 }
 
 static int g_failed = 0;
@@ -72,6 +75,12 @@ int main() {
     }
     check("score_ccmr_prep", n, score_ccmr_prep_temp_bytes(n, I), [&](void* t) { return cc::prep_carve(t, n, I).total_bytes; });
     check("score_neg_lists", n, score_neg_lists_temp_bytes(n), [&](void* t) { return cc::neg_carve(t, n).total_bytes; });
+    if (n > 0) {      // L = n lines against a catalogue of I items: n * ceil(I / range) counts
+      int32_t nr = 0;
+      int64_t want = -1;
+      const int rc = score_catalog_history_exclusions_plan((int32_t)n, I, 0, nullptr, &nr, nullptr, &want);
+      check("score_catalog_history_exclusions", n, rc == 0 ? want : -1, [&](void* t) { return hx::excl_carve(t, n * nr).total_bytes; });
+    }
   }
   std::printf(g_failed ? "%d FAILED\n" : "all layouts hold\n", g_failed);
   return g_failed ? 1 : 0;

@@ -22,6 +22,8 @@ FIGURES = ("next_free_vgpr", "next_free_sgpr", "accum_offset", "group_segment_fi
 
 def assembly(tree, src, out):
     hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
+    if not os.path.exists(os.path.join(tree, "score_amd", "csrc", src)):
+        return ""                        # (a file one tree does not have: all of its functions count as added / removed)
     subprocess.check_call([hipcc] + build.FLAGS + ["--cuda-device-only", "-S", os.path.join(tree, "score_amd", "csrc", src), "-o", out])
     return open(out).read()
 
