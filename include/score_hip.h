@@ -813,6 +813,52 @@ int score_catalog_topk_in(const score_config_t* cfg, const score_state_t* st, co
  * for a null pointer or n too small. */
 int score_catalog_cands_struct_sizes(int64_t* out, int32_t n);
 
+/* ---- ... the exact rank of given items (the counting form) ---------------------------------------------------------------------
+ * "Where does item t stand for this user": per line up to SCORE_CATALOG_TMAX target catalogue indices, and for each the number
+ * of scored items AHEAD of it.  The same sweep as score_catalog_topk / score_catalog_topk_in with a counter in place of the
+ * k-best list: no list, no merge, no [L, N] array.
+ * Definitions, for line l, target index t, S_l the scored items -- the whole catalogue (score_catalog_ranks), or the line's
+ * candidate list restricted to [0, N) (score_catalog_ranks_in) -- and E_l the line's exclusions (lines->excl_*, unchanged):
+ *   ahead      number of n in S_l \ E_l that stand in front of t in score_catalog_topk's order: fc3 logit descending, ties to the
+ *              lower catalogue index, NaN behind every number, -0 as +0.  t never counts against itself.  This is the 0-based
+ *              place t has, or would have, in an unbounded top-k list of the line, whether or not t is excluded or listed.
+ *   tgt_logit  the fc3 logit of the pair (l, t): the bits score_catalog_topk's all_logits holds for it.
+ *   state      1: t is in S_l \ E_l.   2: t is in S_l and excluded.   0: t is inside [0, N) but not in S_l (candidate form only;
+ *              ahead is still counted against the list).   -1: t is outside [0, N): ahead -1, tgt_logit NaN, nothing scored
+ *              for it.
+ *   n_scored   [L]: |S_l \ E_l| (a candidate listed twice counts twice; the list contract forbids it).
+ * Targets are a CSR pair as the exclusions are: tgt_idx[tgt_off[l] .. tgt_off[l + 1]), in any order, repeats allowed, a line may
+ * have none; ahead / tgt_logit / state are aligned with tgt_idx.  At most max_targets per line, 1 <= max_targets <=
+ * SCORE_CATALOG_TMAX.  A line with more is a caller error the call survives: its first max_targets are counted, the others get
+ * ahead -1, state -1 and NaN, and bit 1 of score_state_t.id_status is set (user_2hop's bit, which no line-form call sets
+ * otherwise: its 2-hop ids are a block of zeros).
+ * The target logits come from one extra step in every scoring workgroup (the targets' zcat rows through the same fc2 / fc3
+ * sums), the counts from integer partials per chunk that a workgroup per line adds: a pure function of the inputs, the same
+ * bits every run.  span sizes the plan as N (score_catalog_ranks) or max_count (score_catalog_ranks_in) does: chunk and nchunk
+ * are score_catalog_plan's.  Refusals, all before any launch: a null pointer, max_targets outside [1, SCORE_CATALOG_TMAX], L,
+ * N, max_count <= 0 (SCORE_E_BADARG), a model type other than GRU4Rec / Caser (SCORE_E_SHAPE), a workspace below
+ * score_catalog_ranks_plan's workspace_bytes (SCORE_E_WORKSPACE).  The workspace: score_workspace_layout at B = L, behind it
+ * zline [L, 200], a block of zero ids and the chunks' integer partials. */
+#define SCORE_CATALOG_TMAX 32
+typedef struct {
+  const int64_t* tgt_off;      /* [L + 1] device offsets into tgt_idx                                                         */
+  const int32_t* tgt_idx;      /* catalogue indices, any order, repeats allowed; outside [0, N): state -1; non-null           */
+  int32_t max_targets;         /* 1 .. SCORE_CATALOG_TMAX: no line has more                                                   */
+} score_catalog_targets_t;
+int score_catalog_ranks_plan(const score_config_t* cfg, int32_t L, int32_t span /* N or max_count */, int32_t* chunk,
+                             int32_t* nchunk, int64_t* workspace_bytes);
+int score_catalog_ranks(const score_config_t* cfg, const score_state_t* st, const score_catalog_t* cat,
+                        const score_catalog_lines_t* lines, const score_catalog_targets_t* targets,
+                        int32_t* ahead /* [tgt_off[L]] */, float* tgt_logit /* [tgt_off[L]] */, int32_t* state /* [tgt_off[L]] */,
+                        int32_t* n_scored /* [L] */, void* stream);
+int score_catalog_ranks_in(const score_config_t* cfg, const score_state_t* st, const score_catalog_t* cat,
+                           const score_catalog_lines_t* lines, const score_catalog_cands_t* cands,
+                           const score_catalog_targets_t* targets, int32_t* ahead, float* tgt_logit, int32_t* state,
+                           int32_t* n_scored, void* stream);
+/* sizeof(score_catalog_targets_t), the offsets of its three fields and SCORE_CATALOG_TMAX: returns the number of values written
+ * (5), SCORE_E_BADARG for a null pointer or n too small. */
+int score_catalog_ranks_struct_sizes(int64_t* out, int32_t n);
+
 /* ---- ... with the users' histories excluded, built on the device (csrc/histexcl.hip) -----------------------------------------
  * score_catalog_lines_t.excl_off / excl_idx for L users of a score_point_log_store_t (declared below): line l's list is the set
  * of catalogue indices j with cat_ids[j] anywhere in user user_ids[l]'s WHOLE segment user_hist_seq[off[u - 1] .. off[u]) -- not

@@ -58,7 +58,13 @@ class CatalogCands(C.Structure):
     _fields_ = [("cand_off", C.c_void_p), ("cand_idx", c_i), ("max_count", C.c_int32)]
 
 
+class CatalogTargets(C.Structure):
+    """score_catalog_targets_t: per line the catalogue indices to rank, CSR (score_catalog_ranks / score_catalog_ranks_in)"""
+    _fields_ = [("tgt_off", C.c_void_p), ("tgt_idx", c_i), ("max_targets", C.c_int32)]
+
+
 CATALOG_KMAX = 128      # SCORE_CATALOG_KMAX
+CATALOG_TMAX = 32       # SCORE_CATALOG_TMAX
 
 
 class Workspace(C.Structure):
@@ -313,6 +319,13 @@ _SIGS = {
     "score_catalog_topk_in": [C.POINTER(Config), C.POINTER(State), C.POINTER(Catalog), C.POINTER(CatalogLines),
                               C.POINTER(CatalogCands), C.c_int32, c_i, c_f, c_f, C.c_void_p],
     "score_catalog_cands_struct_sizes": [C.POINTER(C.c_int64), C.c_int32],
+    "score_catalog_ranks_plan": [C.POINTER(Config), C.c_int32, C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int32),
+                                 C.POINTER(C.c_int64)],
+    "score_catalog_ranks": [C.POINTER(Config), C.POINTER(State), C.POINTER(Catalog), C.POINTER(CatalogLines),
+                            C.POINTER(CatalogTargets), c_i, c_f, c_i, c_i, C.c_void_p],
+    "score_catalog_ranks_in": [C.POINTER(Config), C.POINTER(State), C.POINTER(Catalog), C.POINTER(CatalogLines),
+                               C.POINTER(CatalogCands), C.POINTER(CatalogTargets), c_i, c_f, c_i, c_i, C.c_void_p],
+    "score_catalog_ranks_struct_sizes": [C.POINTER(C.c_int64), C.c_int32],
     "score_point_user_lines": [C.POINTER(PointLogStore), c_i, C.c_int32, C.c_int32, C.c_int32, C.c_int32, c_i, c_i, c_i, c_i,
                                C.c_void_p],
     "score_catalog_history_exclusions_plan": [C.c_int32, C.c_int32, C.c_int64, C.POINTER(C.c_int32), C.POINTER(C.c_int32),
@@ -467,6 +480,14 @@ def catalog_cands_plan(cfg, L, max_count, k):
     chunk, nchunk, n = C.c_int32(0), C.c_int32(0), C.c_int64(0)
     check(load().score_catalog_cands_plan(C.byref(cfg), int(L), int(max_count), int(k), C.byref(chunk), C.byref(nchunk), C.byref(n)),
           "score_catalog_cands_plan")
+    return chunk.value, nchunk.value, n.value
+
+
+def catalog_ranks_plan(cfg, L, span):
+    """(chunk, nchunk, workspace bytes) of score_catalog_ranks (span = N) / score_catalog_ranks_in (span = max_count)"""
+    chunk, nchunk, n = C.c_int32(0), C.c_int32(0), C.c_int64(0)
+    check(load().score_catalog_ranks_plan(C.byref(cfg), int(L), int(span), C.byref(chunk), C.byref(nchunk), C.byref(n)),
+          "score_catalog_ranks_plan")
     return chunk.value, nchunk.value, n.value
 
 

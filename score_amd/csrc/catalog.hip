@@ -132,6 +132,13 @@ constexpr int CT_SM_F1 = 0, CT_SM_F2 = CT_SM_F1 + 2 * CT_ROWS * CT_LD1, CT_SM_ZL
               CT_SM_FLOATS_IN = CT_SM_CI + CT_CSLOTS * CT_ROWS;
 static_assert(CT_SM_F2 % 4 == 0 && CT_SM_ZL % 4 == 0 && CT_SM_EX % 4 == 0 && CT_SM_CI % 4 == 0, "16-byte carve offsets");
 static_assert(2 * CT_SM_FLOATS * 4 <= 160 * 1024 && 2 * CT_SM_FLOATS_IN * 4 <= 160 * 1024, "two workgroups per compute unit");
+// the counting form (RANKS) adds, behind either carve, one flag per row of a step: the row is in the line's exclusions
+constexpr int CT_SM_RK = CT_ROWS;
+static_assert(CT_SM_FLOATS % 4 == 0 && CT_SM_FLOATS_IN % 4 == 0, "16-byte carve offsets");
+static_assert(2 * (CT_SM_FLOATS + CT_SM_RK) * 4 <= 160 * 1024 && 2 * (CT_SM_FLOATS_IN + CT_SM_RK) * 4 <= 160 * 1024,
+              "two workgroups per compute unit, counting form");
+static_assert(SCORE_CATALOG_TMAX == CT_ROWS, "a line's targets are one step of rows");
+static_assert(SCORE_CATALOG_RPART >= 2 * SCORE_CATALOG_TMAX + 1, "32 counts, 32 flags, the live count");
 
 // Workgroup blockIdx.x = l * nchunk + ch: line l against the catalogue items [ch * chunk, min(N, (ch + 1) * chunk)), CT_ROWS a
 // step.  Waves 0 .. 4 hold fc2 as MFMA B fragments in registers, one column tile each (52 values a lane: W2 is read ONCE per
@@ -148,8 +155,22 @@ static_assert(2 * CT_SM_FLOATS * 4 <= 160 * 1024 && 2 * CT_SM_FLOATS_IN * 4 <= 1
 // (t + 2) % CT_CSLOTS of an LDS array (four slots: the selection reads step t - 1's while fetch reads step t + 1's), ordered by
 // the step's one barrier; only the first two steps' indices are read straight from global memory.  An index outside [0, N)
 // reads row 0, gets no key and NaN in cand_logits.  A workgroup whose range is empty writes k empty keys and returns.
-template <bool CAND>
-__global__ __launch_bounds__(64 * CT_NW) void catalog_score_kernel(const CatalogArgs a) {
+//
+// RANKS, the counting form (score_catalog_ranks / score_catalog_ranks_in): "how many pairs of the line stand ahead of target
+// j", for up to 32 targets a line, in place of the K best.  The targets' own logits come from a PROLOGUE step in every
+// workgroup -- the loop starts at t = -1 with the rows zcat[tgt_idx[..]] in buffer 1, the same MFMA steps and the same
+// four-lane fc3 sum as any row, so their bits are the pair's own (row sums, above) -- and their keys stay in lanes 0 .. 31 of
+// the selection wave.  (The other route, a score_catalog_topk_in launch over the target lists, was not taken: it brings W2 in
+// again for every line and adds two launches, where the prologue is one step among at least eight and needs no array.)
+// Behind it the selection wave takes every live pair of a step: the exclusion test (whole form, staged: the step's excluded
+// rows as 32 flags in LDS, set from a cursor that walks the ascending staged list -- no search, no global load; otherwise the
+// search select does), then per target popc(ballot(key > target's key)) into lane j's counter, the live count, and a note
+// when a pair IS the target (1: counted, 2: excluded).  The chunk's partials go to rpart; catalog_ranks_reduce_kernel adds
+// them.  Chunk 0's workgroup writes tgt_logit, and for that runs its prologue even where a candidate list is empty.
+// (RANKS asks for three waves a SIMD, i.e. at most 168 registers: without the bound the allocator takes 182 and the second
+// workgroup of a compute unit no longer fits; 0 sets nothing, so the top-K instantiations compile as they did.)
+template <bool CAND, bool RANKS = false>
+__global__ __launch_bounds__(64 * CT_NW) __attribute__((amdgpu_waves_per_eu(RANKS ? 3 : 0))) void catalog_score_kernel(const CatalogArgs a) {
   extern __shared__ __attribute__((aligned(16))) float sm[];
   float* f1s = sm + CT_SM_F1;
   float* f2s = sm + CT_SM_F2;
@@ -162,6 +183,19 @@ __global__ __launch_bounds__(64 * CT_NW) void catalog_score_kernel(const Catalog
   int c0_, c1_;
   const int32_t* cand = nullptr;              // line l's list (CAND)
   int* cis = nullptr;                         // [CT_CSLOTS][CT_ROWS] catalogue indices of the steps in flight (CAND)
+  // RANKS: the line's targets tgt_idx[tlo .. tlo + nt), the first max_targets of them; a longer line is reported (bit 1)
+  int64_t tlo = 0;
+  int nt = 0;
+  int32_t* rp = nullptr;                      // this workgroup's partials
+  int* xfl = nullptr;                         // [CT_ROWS] the step's rows that are excluded (whole form, staged)
+  if constexpr (RANKS) {
+    tlo = a.tgt_off[l];
+    const int64_t c = a.tgt_off[l + 1] - tlo;
+    nt = (int)(c < (int64_t)a.max_targets ? (c > 0 ? c : 0) : a.max_targets);
+    if (c > (int64_t)a.max_targets && a.id_status && tid == 0 && ch == 0) atomicOr(a.id_status, 1 << 1);
+    rp = a.rpart + ((int64_t)l * a.nchunk + ch) * SCORE_CATALOG_RPART;
+    xfl = reinterpret_cast<int*>(sm + (CAND ? CT_SM_FLOATS_IN : CT_SM_FLOATS));
+  }
   if constexpr (CAND) {
     const int64_t lo = a.cand_off[l], cnt64 = a.cand_off[l + 1] - lo;
     const int cnt = (int)(cnt64 < (int64_t)0x7FFFFF00 ? (cnt64 > 0 ? cnt64 : 0) : 0x7FFFFF00);
@@ -170,9 +204,17 @@ __global__ __launch_bounds__(64 * CT_NW) void catalog_score_kernel(const Catalog
     c0_ = (int)min((int64_t)ch * a.chunk, (int64_t)cnt);
     c1_ = ch == a.nchunk - 1 ? cnt : (int)min((int64_t)c0_ + a.chunk, (int64_t)cnt);
     if (c1_ <= c0_) {                          // (workgroup-uniform, in front of the first barrier)
-      ct_u64* out = a.part + ((int64_t)l * a.nchunk + ch) * k;
-      if (tid < k) out[tid] = 0ull;
-      return;
+      if constexpr (RANKS) {                   // nothing counted; chunk 0 goes on, through the prologue alone (nstep = 0)
+        if (ch != 0) {
+          if (tid < SCORE_CATALOG_RPART) rp[tid] = 0;
+          return;
+        }
+        c1_ = c0_;
+      } else {
+        ct_u64* out = a.part + ((int64_t)l * a.nchunk + ch) * k;
+        if (tid < k) out[tid] = 0ull;
+        return;
+      }
     }
   } else {
     c0_ = ch * a.chunk; c1_ = min(N, c0_ + a.chunk);
@@ -187,7 +229,7 @@ __global__ __launch_bounds__(64 * CT_NW) void catalog_score_kernel(const Catalog
   }
   // the line's exclusions that fall into this chunk: [xa, xb) of excl_idx
   int64_t xa = 0, xb = 0;
-  if (a.excl_off) {
+  if (a.excl_off && (!RANKS || c1 > c0)) {     // (RANKS: chunk 0 of an empty list has no candidate to take a bound from)
     const int64_t lo = a.excl_off[l], hi = a.excl_off[l + 1];
     const uint32_t* ex = reinterpret_cast<const uint32_t*>(a.excl_idx) + lo;
     if constexpr (CAND) {            // between the range's first and last candidate, by value (each clamped into the catalogue)
@@ -256,6 +298,18 @@ __global__ __launch_bounds__(64 * CT_NW) void catalog_score_kernel(const Catalog
     }
   };
 
+  // RANKS, the prologue's rows: zcat[tgt_idx[tlo + i]], row 0 for a target outside the catalogue and behind the last target
+  auto fetch_targets = [&]() {
+#pragma unroll
+    for (int j = 0; j < CT_Q4; ++j) {
+      const int e = tid + 64 * CT_MW * j;
+      const int i = e / (CT_N1 / 4), c4 = e - i * (CT_N1 / 4);
+      int n = i < nt ? a.tgt_idx[tlo + i] : 0;
+      n = (uint32_t)n < (uint32_t)N ? n : 0;
+      pre[j] = ld4(a.zcat + (int64_t)n * CT_N1 + c4 * 4);
+    }
+  };
+
   ct_u64 e0 = 0ull, e1 = 0ull, thr = 0ull;       // the selection wave's list and its K-th key (0: fewer than K so far)
   const uint32_t* ex = staged ? exs : reinterpret_cast<const uint32_t*>(a.excl_idx) + xa;
   auto select = [&](const float* f2, int base, const int* ci) {
@@ -296,14 +350,105 @@ __global__ __launch_bounds__(64 * CT_NW) void catalog_score_kernel(const Catalog
     }
   };
 
+  // RANKS.  Lane j < nt of the selection wave: target j's catalogue index, its key (all ones while unknown and for a target
+  // outside the catalogue: nothing is ahead of it), the pairs ahead of it so far, its hit flags; every lane: the pairs counted
+  int tn = -1, cnt = 0, hit = 0, nlive = 0, xc = 0;       // xc: the staged exclusions in front of the step (whole form)
+  ct_u64 tkey = ~0ull;
+  // the prologue's fc3: select's sum over the 32 target rows, row j's logit to lane j
+  auto targets = [&](const float* f2) {
+    float lg[CT_ROWS / 16];
+#pragma unroll
+    for (int p = 0; p < CT_ROWS / 16; ++p) {
+      const int i = lane >> 2, part = lane & 3;
+      const float* row = f2 + (p * 16 + i) * CT_LD2 + part;
+      float s = 0.f;
+#pragma unroll
+      for (int q = 0; q < CT_N2 / 4; ++q) s = fmaf(row[4 * q], w3[q], s);
+      s += __shfl_xor(s, 1, 64);
+      s += __shfl_xor(s, 2, 64);
+      lg[p] = s + bias3;
+    }
+    const float v0 = __shfl(lg[0], 4 * (lane & 15), 64), v1 = __shfl(lg[1], 4 * (lane & 15), 64);
+    const float logit = (lane & 16) ? v1 : v0;
+    const bool inside = lane < nt && (uint32_t)tn < (uint32_t)N;
+    if (inside) tkey = ct_key(logit, tn);
+    if (ch == 0 && lane < nt) a.tgt_logit[tlo + lane] = inside ? logit : __uint_as_float(0x7FC00000u);
+  };
+  auto count = [&](const float* f2, int base, const int* ci) {
+    if constexpr (!CAND) {
+      if (staged) {                // the step's rows [base, base + 32) that are excluded: exs[xc ..) up to the first index behind them
+        if (lane < CT_ROWS) xfl[lane] = 0;
+        for (;;) {
+          const int e = xc + lane;
+          const uint32_t v = e < xn ? exs[e] : 0xFFFFFFFFu;
+          if ((uint32_t)(v - (uint32_t)base) < (uint32_t)CT_ROWS) xfl[v - (uint32_t)base] = 1;
+          const ct_u64 m = __ballot(e < xn && v < (uint32_t)(base + CT_ROWS));
+          xc += __popcll(m);
+          if (m != ~0ull) break;                 // (64 in a row only where an index repeats)
+        }
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");      // one wave: the flags are read by other lanes than set them
+        __builtin_amdgcn_wave_barrier();
+        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+      }
+    }
+#pragma unroll
+    for (int p = 0; p < CT_ROWS / 16; ++p) {
+      const int i = lane >> 2, part = lane & 3;
+      const float* row = f2 + (p * 16 + i) * CT_LD2 + part;
+      float s = 0.f;
+#pragma unroll
+      for (int q = 0; q < CT_N2 / 4; ++q) s = fmaf(row[4 * q], w3[q], s);
+      s += __shfl_xor(s, 1, 64);
+      s += __shfl_xor(s, 2, 64);
+      const float logit = s + bias3;
+      int n = base + p * 16 + i;
+      bool mine = part == 0 && n < c1;
+      if constexpr (CAND) {
+        n = ci[p * 16 + i];
+        mine = mine && (uint32_t)n < (uint32_t)N;
+      }
+      bool out = false;            // the pair is in the line's exclusions
+      if (mine) {
+        if (!CAND && staged) {
+          out = xfl[p * 16 + i] != 0;
+        } else {
+          const int64_t pos = dp_lower_bound(ex, xn, (uint32_t)n);
+          out = pos < xn && ex[pos] == (uint32_t)n;
+        }
+      }
+      const ct_u64 key = (mine && !out) ? ct_key(logit, n) : 0ull;
+      nlive += __popcll(__ballot(mine && !out));
+      for (int j = 0; j < nt; ++j) {
+        const ct_u64 tk = __shfl(tkey, j, 64);
+        const int tj = __shfl(tn, j, 64);
+        const ct_u64 ahead = __ballot(key > tk);
+        const ct_u64 met = __ballot(mine && n == tj), met_out = __ballot(mine && out && n == tj);
+        if (lane == j) {
+          cnt += __popcll(ahead);
+          if (met) hit |= met_out ? 2 : 1;
+        }
+      }
+    }
+    if constexpr (!CAND) {
+      if (staged) __builtin_amdgcn_wave_barrier();       // (the flags are cleared for the next step behind this step's reads)
+    }
+  };
+  (void)targets; (void)count; (void)fetch_targets; (void)select;
+  (void)cnt; (void)hit; (void)nlive; (void)xc; (void)tkey; (void)xfl; (void)rp;
+
   if constexpr (CAND) {            // the first two steps' indices (the selection wave: a lane each)
-    if (wave == CT_MW) cis[lane] = cand[min(c0 + lane, c1 - 1)];
+    if (wave == CT_MW) cis[lane] = (!RANKS || c1 > c0) ? cand[min(c0 + lane, c1 - 1)] : 0;
   }
-  if (wave < CT_MW) fetch(0, true);
+  if constexpr (RANKS) {
+    if (wave == CT_MW && lane < nt) tn = a.tgt_idx[tlo + lane];
+    if (wave < CT_MW) fetch_targets();
+  } else {
+    if (wave < CT_MW) fetch(0, true);
+  }
   __syncthreads();                 // zl, the padding and the exclusions are in LDS
-  if (wave < CT_MW) store(0);
+  if (wave < CT_MW) store(RANKS ? 1 : 0);
   __syncthreads();
-  for (int t = 0; t <= nstep; ++t) {
+  for (int t = RANKS ? -1 : 0; t <= nstep; ++t) {
     if (wave < CT_MW) {
       if (t < nstep) {
         if (t + 1 < nstep) fetch(t + 1, false);
@@ -335,19 +480,65 @@ __global__ __launch_bounds__(64 * CT_NW) void catalog_score_kernel(const Catalog
       int ahead = 0;
       const bool get = lane < CT_ROWS && t + 2 < nstep;
       if (get) ahead = cand[min(c0 + (t + 2) * CT_ROWS + lane, c1 - 1)];
+      if constexpr (RANKS) {
+        if (t >= 1)
+          count(f2s + ((t - 1) & 1) * (CT_ROWS * CT_LD2), c0 + (t - 1) * CT_ROWS, cis + ((t - 1) & (CT_CSLOTS - 1)) * CT_ROWS);
+        else if (t == 0)
+          targets(f2s + CT_ROWS * CT_LD2);
+      } else {
       if (t >= 1)
         select(f2s + ((t - 1) & 1) * (CT_ROWS * CT_LD2), c0 + (t - 1) * CT_ROWS, cis + ((t - 1) & (CT_CSLOTS - 1)) * CT_ROWS);
+      }
       if (get) cis[((t + 2) & (CT_CSLOTS - 1)) * CT_ROWS + lane] = ahead;
+    } else if constexpr (RANKS) {
+      if (t >= 1)
+        count(f2s + ((t - 1) & 1) * (CT_ROWS * CT_LD2), c0 + (t - 1) * CT_ROWS, nullptr);
+      else if (t == 0)
+        targets(f2s + CT_ROWS * CT_LD2);
     } else if (t >= 1) {
       select(f2s + ((t - 1) & 1) * (CT_ROWS * CT_LD2), c0 + (t - 1) * CT_ROWS, nullptr);
     }
     __syncthreads();
   }
+  if constexpr (RANKS) {           // the chunk's partials: counts, flags, the pairs counted
+    if (wave == CT_MW) {
+      if (lane < CT_ROWS) { rp[lane] = cnt; rp[CT_ROWS + lane] = hit; }
+      if (lane == 0) rp[2 * CT_ROWS] = nlive;
+    }
+  } else {
   if (wave == CT_MW) {             // the chunk's list, descending, empty slots (key 0) behind
     ct_u64* out = a.part + ((int64_t)l * a.nchunk + ch) * k;
     if (lane < k) out[lane] = e0;
     if (lane + 64 < k) out[lane + 64] = e1;
   }
+  }
+}
+
+// The counting form's reduce, a wave per line: the chunks' partials added in chunk order (integers: any order gives the same),
+// then per target ahead and state, per line n_scored.  A target outside [0, N): ahead -1, state -1; one behind the first
+// max_targets of its line: the same, and NaN for its logit (chunk 0 wrote the others').
+__global__ __launch_bounds__(64) void catalog_ranks_reduce_kernel(const CatalogArgs a) {
+  const int lane = threadIdx.x, l = blockIdx.x;
+  const int64_t tlo = a.tgt_off[l], c = a.tgt_off[l + 1] - tlo;
+  const int nt = (int)(c < (int64_t)a.max_targets ? (c > 0 ? c : 0) : a.max_targets);
+  const int32_t* p = a.rpart + (int64_t)l * a.nchunk * SCORE_CATALOG_RPART;
+  int cnt = 0, hit = 0, live = 0;
+  for (int ch = 0; ch < a.nchunk; ++ch) {
+    const int32_t* q = p + (int64_t)ch * SCORE_CATALOG_RPART;
+    if (lane < CT_ROWS) { cnt += q[lane]; hit |= q[CT_ROWS + lane]; }
+    if (lane == 0) live += q[2 * CT_ROWS];
+  }
+  if (lane < nt) {
+    const bool inside = (uint32_t)a.tgt_idx[tlo + lane] < (uint32_t)a.N;
+    a.ahead[tlo + lane] = inside ? cnt : -1;
+    a.state[tlo + lane] = !inside ? -1 : (hit & 2) ? 2 : (hit & 1);
+  }
+  for (int64_t e = nt + lane; e < c; e += 64) {
+    a.ahead[tlo + e] = -1;
+    a.state[tlo + e] = -1;
+    a.tgt_logit[tlo + e] = __uint_as_float(0x7FC00000u);
+  }
+  if (lane == 0) a.n_scored[l] = live;
 }
 
 // One wave per line: the nchunk lists through the same insertion.  A list is descending, so behind the first 64 of its keys
@@ -456,3 +647,34 @@ int score_catalog_select_in(const CatalogArgs& a, hipStream_t s) {
   SCORE_CHECK_LAUNCH();
   return 0;
 }
+
+// The counting form (score_catalog_ranks / score_catalog_ranks_in): the same cut and the same grid, RANKS instantiations, then a
+// wave per line over the chunks' partials.  span: what the plan cuts, a.N or a.max_count
+namespace {
+template <bool CAND>
+int catalog_count_launch(const CatalogArgs& a, int span, hipStream_t s) {
+  if (a.L <= 0 || a.N <= 0 || a.N1 != CT_N1 || span <= 0) return SCORE_E_SHAPE;
+  if (!a.tgt_off || !a.tgt_idx || !a.rpart || !a.ahead || !a.tgt_logit || !a.state || !a.n_scored) return SCORE_E_BADARG;
+  if (a.max_targets < 1 || a.max_targets > SCORE_CATALOG_TMAX) return SCORE_E_BADARG;
+  if (CAND && (!a.cand_off || !a.cand_idx)) return SCORE_E_BADARG;
+  if (a.chunk <= 0 || a.chunk % CT_ROWS || (int64_t)a.nchunk * a.chunk < span || (int64_t)(a.nchunk - 1) * a.chunk >= span ||
+      (int64_t)a.L * a.nchunk >= (1LL << 31))
+    return SCORE_E_SHAPE;
+  const size_t lds = (size_t)((CAND ? CT_SM_FLOATS_IN : CT_SM_FLOATS) + CT_SM_RK) * sizeof(float);
+  static thread_local bool attr_set = false;
+  if (!attr_set) {
+    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(catalog_score_kernel<CAND, true>),
+                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    if (e != hipSuccess) return (int)e;
+    attr_set = true;
+  }
+  hipLaunchKernelGGL((catalog_score_kernel<CAND, true>), dim3((unsigned)(a.L * a.nchunk)), dim3(64 * CT_NW), lds, s, a);
+  SCORE_CHECK_LAUNCH();
+  hipLaunchKernelGGL(catalog_ranks_reduce_kernel, dim3((unsigned)a.L), dim3(64), 0, s, a);
+  SCORE_CHECK_LAUNCH();
+  return 0;
+}
+}  // namespace
+
+int score_catalog_count(const CatalogArgs& a, hipStream_t s) { return catalog_count_launch<false>(a, a.N, s); }
+int score_catalog_count_in(const CatalogArgs& a, hipStream_t s) { return catalog_count_launch<true>(a, a.max_count, s); }

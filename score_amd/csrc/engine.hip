@@ -2246,6 +2246,97 @@ extern "C" int score_catalog_cands_struct_sizes(int64_t* out, int32_t n) {
   return have;
 }
 
+// ---- ... the exact rank of given items: catalog_topk's front half, then the counting form of the scoring kernel and its reduce
+namespace {
+// Behind the workspace of a batch of L samples: zline [L, FC1], the zero ids (as CatalogWS) and the chunks' integer partials,
+// [L, nchunk, SCORE_CATALOG_RPART] int32
+struct CatalogRanksWS { int64_t zline, zero_ids, n_zero_ids, rpart, total; int chunk, nchunk; };
+void build_catalog_ranks_ws(const Dims& d, int L, int span, CatalogRanksWS* r) {
+  WS w;
+  build_ws(d, L, &w);
+  score_catalog_chunks(L, span, 1, &r->chunk, &r->nchunk);
+  Taker take = {w.total};
+  r->zline = take((int64_t)L * FC1);
+  r->n_zero_ids = (int64_t)L * d.T * (d.Fu > d.Fi ? d.Fu : d.Fi);
+  r->zero_ids = take(r->n_zero_ids);
+  r->rpart = take((int64_t)L * r->nchunk * SCORE_CATALOG_RPART);
+  r->total = take.cur;
+}
+int catalog_ranks(const score_config_t* cfg, const score_state_t* st, const score_catalog_t* cat, const score_catalog_lines_t* ln,
+                  const score_catalog_cands_t* cands, const score_catalog_targets_t* tg, int32_t* ahead, float* tgt_logit,
+                  int32_t* state, int32_t* n_scored, void* stream) {
+  if (tg->max_targets < 1 || tg->max_targets > SCORE_CATALOG_TMAX) return SCORE_E_BADARG;
+  Pass c;
+  SCORE_TRY(catalog_dims(cfg, ln->L, cat->N, 1, &c.d));
+  if (cands) SCORE_TRY(catalog_dims(cfg, ln->L, cands->max_count, 1, &c.d));
+  if (!st->table || !st->w || !st->workspace || !cat->item_rows || !cat->zcat) return SCORE_E_BADARG;
+  if (!ln->user_seq || !ln->length || !ln->target_user || (ln->excl_off && !ln->excl_idx)) return SCORE_E_BADARG;
+  if (cands && (!cands->cand_off || !cands->cand_idx)) return SCORE_E_BADARG;
+  if (!tg->tgt_off || !tg->tgt_idx) return SCORE_E_BADARG;
+  const Dims& d = c.d;
+  const int L = ln->L;
+  CatalogRanksWS r;
+  build_catalog_ranks_ws(d, L, cands ? cands->max_count : cat->N, &r);
+  if (r.total * 4 > st->workspace_bytes) return SCORE_E_WORKSPACE;
+  hipStream_t s = (hipStream_t)stream;
+  score_batch_t lb;
+  FwdState f = {0.f, 1.f, nullptr, nullptr, 0, nullptr, nullptr, false};
+  SCORE_TRY(rank_prefix(&c, &f, &lb, st, ln->user_seq, ln->length, ln->target_user, nullptr, L, ln->active_slices,
+                        reinterpret_cast<int32_t*>(st->workspace + r.zero_ids), r.n_zero_ids, stream));
+  float* ws = c.ws;
+  RankArgs ra;
+  rank_head_args(c, st, L, 1, &ra);
+  ra.zline = ws + r.zline;
+  G(score_rank_line(ra, s));
+  CatalogArgs a;
+  catalog_model_args(d, st, cat, &a);
+  a.L = L; a.k = 1; a.chunk = r.chunk; a.nchunk = r.nchunk;
+  a.zline = ws + r.zline; a.excl_off = ln->excl_off; a.excl_idx = ln->excl_idx;
+  a.tgt_off = tg->tgt_off; a.tgt_idx = tg->tgt_idx; a.max_targets = tg->max_targets;
+  a.rpart = reinterpret_cast<int32_t*>(ws + r.rpart);
+  a.ahead = ahead; a.tgt_logit = tgt_logit; a.state = state; a.n_scored = n_scored;
+  if (!cands) return score_catalog_count(a, s);
+  a.cand_off = cands->cand_off; a.cand_idx = cands->cand_idx; a.max_count = cands->max_count;
+  return score_catalog_count_in(a, s);
+}
+}  // namespace
+
+extern "C" int score_catalog_ranks_plan(const score_config_t* cfg, int32_t L, int32_t span, int32_t* chunk, int32_t* nchunk,
+                                        int64_t* workspace_bytes) {
+  if (!cfg || !chunk || !nchunk || !workspace_bytes) return SCORE_E_BADARG;
+  Dims d;
+  SCORE_TRY(catalog_dims(cfg, L, span, 1, &d));
+  CatalogRanksWS r;
+  build_catalog_ranks_ws(d, L, span, &r);
+  *chunk = r.chunk; *nchunk = r.nchunk; *workspace_bytes = r.total * 4;
+  return 0;
+}
+
+extern "C" int score_catalog_ranks(const score_config_t* cfg, const score_state_t* st, const score_catalog_t* cat,
+                                   const score_catalog_lines_t* ln, const score_catalog_targets_t* tg, int32_t* ahead,
+                                   float* tgt_logit, int32_t* state, int32_t* n_scored, void* stream) {
+  if (!cfg || !st || !cat || !ln || !tg || !ahead || !tgt_logit || !state || !n_scored) return SCORE_E_BADARG;
+  return catalog_ranks(cfg, st, cat, ln, nullptr, tg, ahead, tgt_logit, state, n_scored, stream);
+}
+
+extern "C" int score_catalog_ranks_in(const score_config_t* cfg, const score_state_t* st, const score_catalog_t* cat,
+                                      const score_catalog_lines_t* ln, const score_catalog_cands_t* cands,
+                                      const score_catalog_targets_t* tg, int32_t* ahead, float* tgt_logit, int32_t* state,
+                                      int32_t* n_scored, void* stream) {
+  if (!cfg || !st || !cat || !ln || !cands || !tg || !ahead || !tgt_logit || !state || !n_scored) return SCORE_E_BADARG;
+  return catalog_ranks(cfg, st, cat, ln, cands, tg, ahead, tgt_logit, state, n_scored, stream);
+}
+
+extern "C" int score_catalog_ranks_struct_sizes(int64_t* out, int32_t n) {
+  const int64_t v[] = {(int64_t)sizeof(score_catalog_targets_t), (int64_t)offsetof(score_catalog_targets_t, tgt_off),
+                       (int64_t)offsetof(score_catalog_targets_t, tgt_idx), (int64_t)offsetof(score_catalog_targets_t, max_targets),
+                       (int64_t)SCORE_CATALOG_TMAX};
+  const int32_t have = (int32_t)(sizeof(v) / sizeof(v[0]));
+  if (!out || n < have) return SCORE_E_BADARG;
+  for (int32_t i = 0; i < have; ++i) out[i] = v[i];
+  return have;
+}
+
 // sizes and late-field offsets of the catalogue call's structures, as score_abi_struct_sizes gives them for the others: -> the
 // number of values written, SCORE_E_BADARG for a null pointer or n too small.  Host only.
 extern "C" int score_catalog_struct_sizes(int64_t* out, int32_t n) {

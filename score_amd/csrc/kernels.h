@@ -358,11 +358,22 @@ struct CatalogArgs {
   // score_catalog_select_in (the candidate form): per line the catalogue indices cand_idx[cand_off[l] .. cand_off[l + 1]),
   // strictly ascending; chunk / nchunk cut max_count list POSITIONS, all_logits is aligned with cand_idx
   const int64_t* cand_off; const int32_t* cand_idx; int max_count;
+  // score_catalog_count / score_catalog_count_in (the counting form, score_catalog_ranks*): per line the targets
+  // tgt_idx[tgt_off[l] .. tgt_off[l + 1]), the first max_targets of them counted; rpart [L, nchunk, SCORE_CATALOG_RPART] the
+  // chunks' integer partials; ahead / tgt_logit / state aligned with tgt_idx, n_scored [L].  (Behind every field the top-K
+  // kernels read, so that their argument offsets stay where they were.)
+  const int64_t* tgt_off; const int32_t* tgt_idx; int max_targets;
+  int32_t* rpart; int32_t* ahead; float* tgt_logit; int32_t* state; int32_t* n_scored;
 };
+// a chunk's partials of the counting form, int32: 32 counts of pairs ahead, 32 hit flags (1: the target was met and counted,
+// 2: met and excluded), the number of pairs counted; padded to a multiple of 16 bytes
+constexpr int SCORE_CATALOG_RPART = 68;
 void score_catalog_chunks(int L, int N, int k, int* chunk, int* nchunk);
 int score_catalog_zcat(const CatalogArgs& a, hipStream_t s);
 int score_catalog_select(const CatalogArgs& a, hipStream_t s);
 int score_catalog_select_in(const CatalogArgs& a, hipStream_t s);
+int score_catalog_count(const CatalogArgs& a, hipStream_t s);        // the whole catalogue: plan of a.N
+int score_catalog_count_in(const CatalogArgs& a, hipStream_t s);     // the lines' candidate lists: plan of a.max_count
 // delf.hip: the DELF point baseline (point_model.py:200-249) between the gather and the scatter.  Per side (0: user_seq rows
 // against target_item through dense; 1: item_seq rows against target_user through dense_1) X [B * T, C] with row stride ldx,
 // the saved keys [B * T, C] (live rows only), attention weights att [B, T], rep [B, C]; backward: ds [B, T] (gradient at the

@@ -345,7 +345,8 @@ def catalog_quality_device(top_idx, target_idx):
     """The six numbers of get_ranking_quality, in its order -- (NDCG@5, NDCG@10, HR@1, HR@5, HR@10, MRR) -- from top-k lists over a
     whole catalogue (model.recommend_async): top_idx [n_lines, k] catalogue indices, best first, target_idx [n_lines] the
     positive's index.  The positive's rank is its position in the list; a positive that is not in the list counts 0 everywhere,
-    so MRR is truncated at k.  Needs k >= 10.  Tensors on any device; one 6-float read-back."""
+    so MRR is truncated at k.  Needs k >= 10.  Tensors on any device; one 6-float read-back.  (rank_quality_device takes exact
+    ranks from model.item_ranks_async instead: no truncation.)"""
     import torch
     top = top_idx.reshape(top_idx.shape[0], -1)
     n, k = top.shape
@@ -446,6 +447,108 @@ def evaluate_catalog_users(model, store, catalog, k=10, exclude_history=True, ca
     if hasattr(model, "check_ids"):
         model.check_ids()
     return (six, top, tgt) if return_lists else six
+
+
+def rank_quality_device(ahead, state=None):
+    """(NDCG@5, NDCG@10, HR@1, HR@5, HR@10, MRR, mean_rank) from exact ranks (model.item_ranks_async): ahead [n] the number of
+    items in front of each target, i.e. its 0-based rank r.  catalog_quality_device's formulas on r = ahead -- gain
+    log 2 / log(r + 2) under the cutoff, 1 / (r + 1) for MRR, which is NOT truncated here -- and mean_rank, the mean of r + 1
+    over the targets that count.  A target with ahead < 0 (not in the catalogue) counts 0 in the six and not in mean_rank, as a
+    miss does there; with `state` given so does one with state <= 0 (not among the line's scored items).  An excluded target
+    (state 2) counts with its rank against the rest.  Tensors on any device; one 7-float read-back."""
+    import torch
+    r = ahead.reshape(-1)
+    if r.numel() == 0:
+        raise ValueError("rank_quality_device: no targets")
+    found = r >= 0
+    if state is not None:
+        st = state.reshape(-1).to(r.device)
+        if st.numel() != r.numel():
+            raise ValueError("rank_quality_device: ahead and state must name the same targets")
+        found = found & (st > 0)
+    r = r.clamp(min=0).to(torch.float64)
+    gain = math.log(2) / torch.log(r + 2)
+    zero = torch.zeros_like(gain)
+    f = lambda cond: (found & cond).to(torch.float64).mean()
+    n_found = found.to(torch.float64).sum()
+    mean_rank = torch.where(found, r + 1, zero).sum() / n_found.clamp(min=1)
+    out = torch.stack([torch.where(found & (r < 5), gain, zero).mean(), torch.where(found & (r < 10), gain, zero).mean(),
+                       f(r < 1), f(r < 5), f(r < 10), torch.where(found, 1.0 / (r + 1), zero).mean(), mean_rank])
+    return tuple(float(x) for x in out.cpu().tolist())
+
+
+def evaluate_catalog_ranks(model, batches, catalog, neg_sample_num=TEST_NEG_SAMPLE_NUM, exclude_history=None, candidates=None):
+    """evaluate_catalog with the positive's EXACT rank in place of its position in a top-k list: for every target line of a
+    loader's eval batches the positive is the single target of model.item_ranks_async, then rank_quality_device -> its seven
+    numbers.  The first five equal evaluate_catalog's at any k >= 10; MRR is not truncated.  exclude_history, candidates: as
+    evaluate_catalog takes them (the positive itself is never excluded)."""
+    import torch
+    if candidates is not None and candidates != "line":
+        raise ValueError("evaluate_catalog_ranks: candidates must be None or \"line\", got %r" % (candidates,))
+    aheads, states = [], []
+    for batch_data in batches:
+        db = model.device_batch(batch_data)
+        lines = model.lines_of(db, neg_sample_num)
+        L = int(lines[1].numel())
+        pos_ids = db.tensors[5].view(L, 1 + neg_sample_num, -1)[:, 0, 0].contiguous()
+        tgt, found = catalog.indices_of(pos_ids)
+        if not bool(found.all().item()):
+            raise ValueError("evaluate_catalog_ranks: a line's positive item is not in the catalogue")
+        exclude = None
+        if exclude_history is not None:
+            exclude = _history_exclusions(exclude_history, lines[2][:, 0], pos_ids)
+        own = None
+        if candidates == "line":
+            n_cand = 1 + neg_sample_num
+            own = (torch.arange(L + 1, device=pos_ids.device, dtype=torch.int64) * n_cand,
+                   db.tensors[5].view(L, n_cand, -1)[:, :, 0].reshape(-1))
+        targets = (torch.arange(L + 1, device=pos_ids.device, dtype=torch.int64), tgt.to(torch.int32).contiguous(), 1)
+        out = model.item_ranks_async(lines, catalog, targets, exclude=exclude, active_slices=db.active_slices, candidates=own)
+        aheads.append(out[0].clone()); states.append(out[2].clone())
+    seven = rank_quality_device(torch.cat(aheads), torch.cat(states))
+    if hasattr(model, "check_ids"):
+        model.check_ids()
+    return seven
+
+
+def evaluate_catalog_ranks_users(model, store, catalog, exclude_history=True, candidates=None, lines_per_call=100):
+    """evaluate_catalog_ranks over a PointLogStore's own target lines without a loader, the route of evaluate_catalog_users:
+    lines_per_call lines a call of model.item_ranks_users_async, the line's positive its single target, no read-back per call.
+    The user's whole history is excluded (exclude_history); a positive inside it is ranked against the rest (state 2), which is
+    the rank it has in evaluate_catalog_users' lists, where it alone is kept.  -> rank_quality_device's seven numbers."""
+    import torch
+    if candidates is not None and candidates != "line":
+        raise ValueError("evaluate_catalog_ranks_users: candidates must be None or \"line\", got %r" % (candidates,))
+    if getattr(model, "rank_unsupported", None) is not None:
+        raise NotImplementedError("%s has no catalogue pass: %s" % (type(model).__name__, model.rank_unsupported))
+    if store._dev is None:
+        raise ValueError("evaluate_catalog_ranks_users: the store must be on a device (build='device' or .to_device())")
+    n_lines, per_line, step = int(store.n_lines), int(store.per_line), int(lines_per_call)
+    if n_lines <= 0 or step <= 0:
+        raise ValueError("evaluate_catalog_ranks_users: no target lines, or lines_per_call <= 0")
+    users = store._dev["line_user"][:n_lines]
+    items = store._dev["line_items"][:n_lines * per_line].view(n_lines, per_line)
+    aheads, states, founds = [], [], []
+    for a in range(0, n_lines, step):
+        b = min(n_lines, a + step)
+        L = b - a
+        pos_ids = items[a:b, 0].contiguous()
+        tgt, found = catalog.indices_of(pos_ids)
+        own, longest = None, None
+        if candidates == "line":
+            own = (torch.arange(L + 1, device=pos_ids.device, dtype=torch.int64) * per_line, items[a:b].reshape(-1))
+            longest = per_line
+        targets = (torch.arange(L + 1, device=pos_ids.device, dtype=torch.int64),
+                   torch.where(found, tgt, torch.full_like(tgt, -1)).to(torch.int32).contiguous(), 1)
+        out = model.item_ranks_users_async(users[a:b], store, catalog, targets, exclude_history=bool(exclude_history),
+                                           candidates=own, max_candidates=longest)
+        aheads.append(out[0].clone()); states.append(out[2].clone()); founds.append(found.all())
+    if not bool(torch.stack(founds).all().item()):
+        raise ValueError("evaluate_catalog_ranks_users: a line's positive item is not in the catalogue")
+    seven = rank_quality_device(torch.cat(aheads), torch.cat(states))
+    if hasattr(model, "check_ids"):
+        model.check_ids()
+    return seven
 
 
 def _history_exclusions(store, user_ids, keep_ids):

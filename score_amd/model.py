@@ -1967,6 +1967,151 @@ class SCOREBASE(object):
         keep_ = idx >= 0
         return [ids[l][keep_[l]].tolist() for l in range(idx.shape[0])], [y[l][keep_[l]].tolist() for l in range(idx.shape[0])]
 
+    # ------------------------------------------------------------------ the exact rank of given items (score_catalog_ranks)
+    def item_ranks_async(self, lines, catalog, targets, exclude=None, exclude_idx=None, active_slices=None, candidates=None,
+                         max_candidates=None):
+        """Where given items stand for each of L users among ALL scored items of `catalog`: per line up to 32 targets, and for
+        each the number of scored, non-excluded items AHEAD of it in recommend_async's order (descending fc3 logit, ties to the
+        lower index, NaN last) -- its 0-based place in an unbounded recommend list, whether or not the target itself is excluded
+        or listed (include/score_hip.h: score_catalog_ranks / score_catalog_ranks_in).  One sweep of the catalogue with a
+        counter: no list, no [L, N] array.
+
+        lines, exclude, exclude_idx, active_slices, candidates, max_candidates: as recommend_async takes them.  targets: per
+        line the item ids to rank, in the two forms of exclude (ItemCatalog.targets maps them: order and repeats kept, an id the
+        catalogue does not hold becomes -1), or what ItemCatalog.targets returned.
+
+        -> (ahead int32, logits float32, state int32, n_scored int32 [L], tgt_off int64 [L + 1]) device tensors; the first
+        three are aligned with the targets, line l's at tgt_off[l] .. tgt_off[l + 1].  state: 1 scored and counted, 2 scored
+        but excluded, 0 in the catalogue but not among the line's candidates, -1 not in the catalogue (ahead -1, logit NaN).
+        n_scored: the line's scored, non-excluded items.  logits: the pair's own, bit for bit recommend_async's."""
+        if self.rank_unsupported is not None:
+            raise NotImplementedError("%s has no catalogue pass: %s" % (type(self).__name__, self.rank_unsupported))
+        if exclude is not None and exclude_idx is not None:
+            raise ValueError("exclude (item ids) and exclude_idx (catalogue indices) are mutually exclusive")
+        if not isinstance(catalog, ItemCatalog) or catalog.model is not self:
+            raise ValueError("catalog must be an ItemCatalog built for this model")
+        if len(lines) != 3:
+            raise ValueError("lines must be (user_seq, user_seq_length, target_user)")
+        c = self.cfg
+        T, Fi, Fu = int(c.max_time_len), int(c.item_fnum), int(c.user_fnum)
+        i32 = lambda x: (x if torch.is_tensor(x) else torch.from_numpy(np.ascontiguousarray(np.asarray(x)))).to(
+            device=self.device, dtype=torch.int32).contiguous()
+        useq, length, tuser = (i32(x) for x in lines)
+        L = int(length.numel())
+        if L == 0:
+            raise ValueError("no lines")
+        for name, x, shape in (("user_seq", useq, (L, T, Fi)), ("user_seq_length", length, (L,)), ("target_user", tuser, (L, Fu))):
+            if tuple(x.shape) != shape:
+                raise ValueError("lines: %s has shape %s, expected %s" % (name, tuple(x.shape), shape))
+        if isinstance(targets, tuple) and len(targets) == 3 and torch.is_tensor(targets[1]) and \
+                targets[1].dtype == torch.int32 and not torch.is_tensor(targets[2]):
+            tgt_off, tgt_idx, longest_t = targets                   # (what ItemCatalog.targets returned)
+            if int(tgt_off.numel()) != L + 1:
+                raise ValueError("targets: offsets for %d lines, expected %d" % (int(tgt_off.numel()) - 1, L))
+            if not 0 <= int(longest_t) <= _lib.CATALOG_TMAX:
+                raise ValueError("targets: %d on a line, at most %d" % (int(longest_t), _lib.CATALOG_TMAX))
+        else:
+            tgt_off, tgt_idx, longest_t = catalog.targets(targets, L)
+        if active_slices is None:
+            active_slices = _active_slices_of(self, int(length.max().item()))
+        N = catalog.N
+        excl_off = excl_idx = None
+        if exclude is not None:
+            excl_off, excl_idx = catalog.exclusions(exclude, L)
+        elif exclude_idx is not None:
+            excl_off, excl_idx = exclude_idx
+            if not (torch.is_tensor(excl_off) and torch.is_tensor(excl_idx) and excl_off.dtype == torch.int64 and
+                    excl_idx.dtype == torch.int32 and excl_off.device == self.device and excl_idx.device == self.device and
+                    excl_off.is_contiguous() and excl_idx.is_contiguous() and int(excl_off.numel()) == L + 1 and
+                    int(excl_idx.numel()) >= 1):
+                raise ValueError("exclude_idx must be (int64 [%d], int32 [>= 1]) contiguous tensors on %s" % (L + 1, self.device))
+        cand_off = cand_idx = None
+        span = N
+        if candidates is not None:
+            if isinstance(candidates, tuple) and len(candidates) == 3 and torch.is_tensor(candidates[1]) and \
+                    candidates[1].dtype == torch.int32 and not torch.is_tensor(candidates[2]):
+                cand_off, cand_idx, longest = candidates
+                if int(cand_off.numel()) != L + 1:
+                    raise ValueError("candidates: offsets for %d lines, expected %d" % (int(cand_off.numel()) - 1, L))
+            elif max_candidates is not None:
+                cand_off, cand_idx = catalog._line_indices(candidates, L, "candidates")
+                longest = None
+            else:
+                cand_off, cand_idx, longest = catalog.candidates(candidates, L)
+            span = int(max_candidates) if max_candidates is not None else int(longest)
+            if span < 1:
+                raise ValueError("max_candidates = %d, expected >= 1" % span)
+        key = ("catalog_ranks", L, span)
+        ws = self._rank_ws.pop(key, None)
+        if ws is None:
+            nbytes = _lib.catalog_ranks_plan(self.cfg, L, span)[2]
+            while len(self._rank_ws) >= self.max_workspaces:
+                torch.cuda.synchronize(self.device)
+                self._rank_ws.pop(next(iter(self._rank_ws)))
+            ws = torch.empty(((nbytes + 3) // 4,), dtype=torch.float32, device=self.device)
+        self._rank_ws[key] = ws
+        n_t = int(tgt_idx.numel())                                   # (never 0: ItemCatalog.targets pads an empty set)
+        ahead = torch.empty((n_t,), dtype=torch.int32, device=self.device)
+        logit = torch.empty((n_t,), dtype=torch.float32, device=self.device)
+        state = torch.empty((n_t,), dtype=torch.int32, device=self.device)
+        n_scored = torch.empty((L,), dtype=torch.int32, device=self.device)
+        ln = _lib.CatalogLines(_ptr(useq), _ptr(length), _ptr(tuser), L, int(active_slices),
+                               _ptr(excl_off) if excl_off is not None else None, _ptr(excl_idx) if excl_idx is not None else None)
+        tg = _lib.CatalogTargets(_ptr(tgt_off), _ptr(tgt_idx), max(1, int(longest_t)))
+        with self._Pin(self):
+            catalog.refresh()
+            st = self._state(ws)
+            cat = catalog.struct()
+            if cand_off is None:
+                what = "score_catalog_ranks"
+                rc = self.lib.score_catalog_ranks(C.byref(self.cfg), C.byref(st), C.byref(cat), C.byref(ln), C.byref(tg),
+                                                  _ptr(ahead), _ptr(logit), _ptr(state), _ptr(n_scored), self._stream())
+            else:
+                what = "score_catalog_ranks_in"
+                cd = _lib.CatalogCands(_ptr(cand_off), _ptr(cand_idx), span)
+                rc = self.lib.score_catalog_ranks_in(C.byref(self.cfg), C.byref(st), C.byref(cat), C.byref(ln), C.byref(cd),
+                                                     C.byref(tg), _ptr(ahead), _ptr(logit), _ptr(state), _ptr(n_scored),
+                                                     self._stream())
+        _lib.check(rc, what)
+        return ahead, logit, state, n_scored, tgt_off
+
+    def item_ranks(self, lines, catalog, targets, exclude=None, active_slices=None, candidates=None):
+        """item_ranks_async, read back: per line lists (ahead, logit, state) aligned with the line's targets, and n_scored per
+        line -> (ahead, logits, state, n_scored).  Raises as rank does when an id outside the table was fed."""
+        ahead, logit, state, n_scored, off = self.item_ranks_async(lines, catalog, targets, exclude=exclude,
+                                                                   active_slices=active_slices, candidates=candidates)
+        ahead, logit, state, n_scored, off = (x.cpu().numpy() for x in (ahead, logit, state, n_scored, off))
+        self.check_ids()
+        cut = lambda x: [x[off[l]:off[l + 1]].tolist() for l in range(len(off) - 1)]
+        return cut(ahead), cut(logit), cut(state), n_scored.tolist()
+
+    def item_ranks_users_async(self, user_ids, store, catalog, targets, exclude_history=True, candidates=None,
+                               max_candidates=None):
+        """item_ranks_async for users named by id, the route of recommend_users_async: the lines from store.user_lines and, with
+        exclude_history, each user's WHOLE history as exclusions (catalog.history_exclusions, nothing kept back), both built on
+        the device -- with `targets` as ItemCatalog.targets returned it, and candidates=None or max_candidates given, no host
+        wait.  A target inside the user's history is ranked against the rest and comes back with state 2.
+        -> (ahead, logits, state, n_scored, tgt_off, known [L] int32); an unknown user (known 0) is scored as a cold user."""
+        if self.rank_unsupported is not None:
+            raise NotImplementedError("%s has no catalogue pass: %s" % (type(self).__name__, self.rank_unsupported))
+        if not isinstance(catalog, ItemCatalog) or catalog.model is not self:
+            raise ValueError("catalog must be an ItemCatalog built for this model")
+        c = self.cfg
+        T, Fi, Fu = int(c.max_time_len), int(c.item_fnum), int(c.user_fnum)
+        if (int(store.Fu), int(store.Fi)) != (Fu, Fi):
+            raise ValueError("the store has (user_fnum, item_fnum) = %r, the model %r" % ((store.Fu, store.Fi), (Fu, Fi)))
+        if store._dev is None or store.device != self.device:
+            raise ValueError("the store must be on the model's device %s (build='device' or .to_device())" % (self.device,))
+        catalog.check_store(store)
+        uid = (user_ids if torch.is_tensor(user_ids) else torch.from_numpy(np.ascontiguousarray(np.asarray(user_ids)))).to(
+            device=self.device, dtype=torch.int32).contiguous().view(-1)
+        useq, length, tuser, known = store.user_lines(uid, T)
+        excl = catalog.history_exclusions(store, uid, None) if exclude_history else None
+        out = self.item_ranks_async((useq, length, tuser), catalog, targets, exclude_idx=excl,
+                                    active_slices=_active_slices_of(self, min(T, store.max_user_len)), candidates=candidates,
+                                    max_candidates=max_candidates)
+        return tuple(out) + (known,)
+
     def save(self, sess, path):
         """All global variables incl. the Adam slots, under the TF variable names."""
         if self._guard_on:
@@ -2277,6 +2422,38 @@ class ItemCatalog(object):
         (excl_off int64 [L + 1], excl_idx int32) on the device, the ids mapped to catalogue indices (those the catalogue does not
         hold dropped), ascending and without repeats within a line.  The mapping runs on the device."""
         return self._line_indices(exclude, L, "exclude")
+
+    def targets(self, lists, L):
+        """targets -- per line the item ids to rank, in the two forms exclude takes -- as score_catalog_targets_t takes it:
+        (tgt_off int64 [L + 1], tgt_idx int32, longest) on the device.  Unlike the exclusions nothing is sorted or dropped:
+        order and repeats are kept, an id the catalogue does not hold becomes index -1 (state -1 in the result); tgt_idx is
+        never empty (one unused -1 when no line has a target).  longest, the longest line's count, costs one read-back;
+        ValueError when a line has more than 32 (SCORE_CATALOG_TMAX)."""
+        dev = self.ids.device
+        host = lambda x: np.asarray(x.cpu() if torch.is_tensor(x) else x)
+        if len(lists) == 2 and not isinstance(lists, list) and np.ndim(host(lists[0])) == 1 and \
+                host(lists[0]).size == L + 1:
+            off = (lists[0] if torch.is_tensor(lists[0]) else torch.from_numpy(np.ascontiguousarray(host(lists[0])))).to(
+                device=dev, dtype=torch.int64).contiguous()
+            ids = (lists[1] if torch.is_tensor(lists[1]) else torch.from_numpy(np.ascontiguousarray(host(lists[1])))).to(dev)
+            ids = ids.reshape(-1)
+        else:
+            if len(lists) != L:
+                raise ValueError("targets must hold one array of item ids per line (%d), or be a CSR pair (offsets, ids)" % L)
+            parts = [host(x).reshape(-1).astype(np.int64) for x in lists]
+            off = torch.from_numpy(np.concatenate([[0], np.cumsum([p.size for p in parts])]).astype(np.int64)).to(dev)
+            ids = torch.from_numpy(np.concatenate(parts) if parts else np.zeros((0,), dtype=np.int64)).to(dev)
+        longest = int((off[1:] - off[:-1]).max().item()) if L > 0 else 0
+        if longest > _lib.CATALOG_TMAX:
+            raise ValueError("targets: %d on a line, at most %d (SCORE_CATALOG_TMAX)" % (longest, _lib.CATALOG_TMAX))
+        n = int(off[-1].item()) if L > 0 else 0
+        if n == 0:
+            return off, torch.full((1,), -1, dtype=torch.int32, device=dev), 0
+        ids = ids[:n].to(torch.int64)
+        inside = (ids >= -2 ** 31) & (ids < 2 ** 31)
+        pos, found = self.indices_of(torch.where(inside, ids, torch.zeros_like(ids)))
+        idx = torch.where(found & inside, pos, torch.full_like(pos, -1)).to(torch.int32)
+        return off, idx.contiguous(), longest
 
     def check_store(self, store):
         """ValueError unless `store` (a PointLogStore on the catalogue's device) describes the catalogue's items as the catalogue
