@@ -539,6 +539,8 @@ typedef struct {
                            bit 17 (131072) = the fused gather + co-attention forward runs one unit per wave
                            (coattn_fwd_kernel) where it would work through a chunk of slices per wave
                            (coattn_fwd_kernel_units, see score_coattn_fwd_chunk): same bits, the A/B arm;
+                           bit 18 (262144) = the embedding-gradient scatter runs pull_kernel where score_pull_form would
+                           choose pull_kernel_lanes (one occurrence per lane; csrc/scatter.hip): same bits, the A/B arm;
                            bits 20 .. 23 = no switch but a number, for measurements: a chunk length 1 .. 15 to take in
                            place of score_coattn_fwd_chunk's (0 = the rule).
                            The ONLY switches of the launch sequence: the library reads no environment variable       */
@@ -650,6 +652,16 @@ int64_t score_sort_pairs_temp_bytes(int64_t n);
 int score_segment_sum_rows(const int32_t* rows, const float* src, int64_t n, int32_t D, int64_t n_out_rows,
                            float* out, uint8_t* row_flags, void* scratch, int64_t scratch_bytes, void* stream);
 int64_t score_segment_sum_scratch_bytes(int64_t n, int32_t D);
+
+/* Which kernel the embedding-gradient scatter of score_backward takes (host only, no GPU needed).  1 = pull_kernel_lanes,
+ * the form with one occurrence's metadata per lane, 32-bit offsets from one base pointer and the co-attention weight
+ * slices in LDS; 0 = pull_kernel.  The lanes form needs: mode 1 (constant coefficients: RCA / RRN) or 2 (co-attention
+ * coefficients) -- not 0, the owner-side row sum; D in {16, 32, 64}; and span_bytes, the distance from the lowest
+ * activation-gradient / coefficient pointer of the launch to the end of the highest, in (0, 4 GiB].  debug_flags bit 18
+ * overrides it.  Both kernels give the same bits.  score_pull_last_form: what this process's latest scatter launch took
+ * (-1 before the first). */
+int score_pull_form(int32_t D, int32_t mode, int64_t span_bytes);
+int score_pull_last_form(void);
 
 /* The owner's usual way to combine the row gradients it receives: one call per source rank, in rank
  * order, each with that rank's rows (unique inside a call -- they come from score_index_plan's

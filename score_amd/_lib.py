@@ -79,7 +79,8 @@ class State(C.Structure):
     # the co-attention backward's are bit 15 (32768: the rows of relu-inactive neighbours are loaded too) and bit 16
     # (65536: a unit's ids and saved scalars are requested one unit ahead, not in the unit's own iteration); the
     # co-attention forward's is bit 17 (131072: one unit per wave, coattn_fwd_kernel, where the several-units form would
-    # run), and bits 20 .. 23 hold a chunk length for it to measure with (0: the launcher's rule)
+    # run), and bits 20 .. 23 hold a chunk length for it to measure with (0: the launcher's rule); the row scatter's is
+    # bit 18 (262144: pull_kernel where score_pull_form would choose pull_kernel_lanes)
     _fields_ = [("table", c_f), ("n_table_rows", C.c_int64), ("w", c_f), ("workspace", c_f),
                 ("workspace_bytes", C.c_int64), ("scatter_mode", C.c_int32), ("global_batch", C.c_int32),
                 ("gemm_mode", C.c_int32), ("debug_flags", C.c_int32), ("row_flags", C.c_void_p),
@@ -287,6 +288,8 @@ _SIGS = {
     "score_segment_sum_rows": [c_i, c_f, C.c_int64, C.c_int32, C.c_int64, c_f, C.c_void_p, C.c_void_p, C.c_int64,
                                C.c_void_p],
     "score_segment_sum_scratch_bytes": [C.c_int64, C.c_int32],
+    "score_pull_form": [C.c_int32, C.c_int32, C.c_int64],
+    "score_pull_last_form": [],
     "score_rows_accumulate": [c_i, c_f, C.c_int64, C.c_int32, C.c_int64, c_f, C.c_void_p, C.c_void_p],
     "score_rows_accumulate_multi": [c_i, c_f, C.POINTER(C.c_int64), C.c_int32, C.c_int32, C.c_int64, c_f, C.c_void_p, C.c_void_p],
     "score_auc_logloss": [c_f, c_i, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p],

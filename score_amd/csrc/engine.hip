@@ -633,7 +633,7 @@ enum {
   DF_GRU_STEPWISE = 1, DF_HEAD_FUSED_ANY_B = 2, DF_GRU_F32_REC = 4, DF_NO_PANEL = 8, DF_PANEL_DX = 16, DF_SORT_LIB = 32,
   DF_HEAD_UNFUSED = 64, DF_ATTN_UNFUSED = 128, DF_SORT_OWN = 256, DF_NO_PS = 512, DF_PS_FWD_ONLY = 1024, DF_PS_BWD_ONLY = 2048,
   DF_ONE_STREAM = 4096, DF_G4R_COMPOSED = 8192, DF_COATTN_ALL_ROWS = 32768,
-  DF_COATTN_META_AHEAD = 65536, DF_COATTN_FWD_ONE_UNIT = 131072
+  DF_COATTN_META_AHEAD = 65536, DF_COATTN_FWD_ONE_UNIT = 131072, DF_PULL_OLD_FORM = 262144
 };
 // (bits 20 .. 23 are no switch but a number: the chunk length of the co-attention forward, 0 = the launcher's rule)
 static inline int coattn_fwd_ch_of(const score_state_t* st) { return (st->debug_flags >> 20) & 15; }
@@ -641,7 +641,7 @@ static inline int coattn_fwd_ch_of(const score_state_t* st) { return (st->debug_
 //  recurrences as one launch per side instead of one grouped launch)
 struct Flags {
   bool gru_stepwise, head_fused_any_b, gru_f32_rec, no_panel, panel_dx, sort_lib, head_unfused, attn_unfused, sort_own, no_ps,
-      ps_fwd_only, ps_bwd_only, one_stream, g4r_composed, coattn_all_rows, coattn_meta_ahead, coattn_fwd_one_unit;
+      ps_fwd_only, ps_bwd_only, one_stream, g4r_composed, coattn_all_rows, coattn_meta_ahead, coattn_fwd_one_unit, pull_old_form;
 };
 static inline Flags flags_of(const score_state_t* st) {
   auto on = [st](int bit) { return (st->debug_flags & bit) != 0; };
@@ -652,6 +652,7 @@ static inline Flags flags_of(const score_state_t* st) {
   o.ps_fwd_only = on(DF_PS_FWD_ONLY); o.ps_bwd_only = on(DF_PS_BWD_ONLY); o.one_stream = on(DF_ONE_STREAM);
   o.g4r_composed = on(DF_G4R_COMPOSED); o.coattn_all_rows = on(DF_COATTN_ALL_ROWS);
   o.coattn_meta_ahead = on(DF_COATTN_META_AHEAD); o.coattn_fwd_one_unit = on(DF_COATTN_FWD_ONE_UNIT);
+  o.pull_old_form = on(DF_PULL_OLD_FORM);
   return o;
 }
 // Flags.one_stream (debug_flags bit 12): no second stream at all -- everything the passes would fork runs on the caller's
@@ -1085,6 +1086,9 @@ static int row_scatter(const Pass& c, float* plan, float* grad_table) {
   pa.D = d.D; pa.K = d.K; pa.zero_is_dummy = 1;
   pa.flags = c.st->scatter_mode == 0 ? c.st->row_flags : nullptr;
   pa.uid = c.st->scatter_mode == 2 ? reinterpret_cast<const uint32_t*>(ws + w.uid) : nullptr;
+  pa.force_old = c.fl.pull_old_form ? 1 : 0;               // (debug_flags bit 18: pull_kernel, A/B against pull_kernel_lanes)
+  const int nf[6] = {d.Fi, d.Fi, d.Fu, d.Fu, d.Fu, d.Fi};  // features of the six index tensors, as score_index_plan enumerates them
+  for (int g = 0; g < 6; ++g) { pa.nf[g] = nf[g]; pa.rows[g] = g < 4 ? (int64_t)c.B * c.T : (int64_t)c.B; }
   const float invK = 1.0f / (float)d.K;
   const float* Gm[6] = {ws + w.dxside[0], ws + w.dxside[1], ws + w.dxside[0], ws + w.dxside[1], ws + w.dtgt, ws + w.dtgt};
   const int ldg[6] = {d.I, d.I, d.I, d.I, d.Dq, d.Dq};

@@ -207,6 +207,10 @@ struct PullArgs {
   int D, K, LPRp;
   int zero_is_dummy;       // key 0 is the masked dummy row (score.py:44-47): no gradient
   uint8_t* flags;          // optional per-destination-row state byte: 2 = written this step
+  // what the one-occurrence-per-lane form (pull_kernel_lanes) needs to bound its 32-bit offsets and to stage Wv: the
+  // features and the G rows (bt values) of each segment.  All zero (a caller that does not know): the present kernel.
+  int nf[6]; int64_t rows[6];
+  int force_old;           // debug_flags bit 18: the present kernel whatever the geometry
 };
 struct PlanRemapArgs { int32_t* out[6]; int F[6]; int K; int T, TA; };
 int score_launch_plan_unique(const PlanRemapArgs& ra, const uint32_t* keys, const uint32_t* vals, int64_t n,
@@ -221,6 +225,12 @@ int score_launch_plan_own(const PlanFillArgs& a, int key_bits, uint32_t* keys_in
                           uint32_t* vals_out, void* temp, size_t temp_bytes, hipStream_t s);
 size_t score_sort_temp_bytes(int64_t n);
 int score_pull_window(int64_t n);
+// Which pull kernel a launch takes.  pull_kernel_lanes<MODE, LPR, TU> (an occurrence's key, descriptor, coefficients and
+// offsets on ONE lane of its group, handed out by DPP; 32-bit offsets from one base; Wv in LDS) when ALL of: the
+// contribution form is 1 or 2 (not the owner-side row sum); D is 16, 32 or 64 (a group of D/4 lanes fills whole DPP
+// banks of one 16-lane row); the caller gave nf[] / rows[] for all six segments; every byte the occurrences can reach
+// in G / cA / cB lies below 4 GiB from the lowest of those pointers (score_pull_form); PullArgs.force_old is 0.
+// Otherwise pull_kernel<MODE>.  Both forms give the same bits.
 int score_launch_pull(PullArgs& a, const uint32_t* keys, const uint32_t* vals, int64_t n, float* out,
                       float* partials, int64_t partial_floats, hipStream_t s);
 

@@ -13,6 +13,7 @@
 // that a second kernel adds in window order, so the result is bitwise reproducible.
 #include <cstring>
 #include <cstdlib>
+#include <type_traits>
 #include <rocprim/device/device_radix_sort.hpp>
 #include <rocprim/device/device_scan.hpp>
 #include "common.h"
@@ -327,6 +328,224 @@ __global__ __launch_bounds__(256) void pull_kernel(const PullArgs a, const uint3
   }
 }
 
+// ------------------------------------------------------------------ pull, one occurrence per lane
+// The same walk with a window's metadata held once per group instead of once per lane.  In a trip of TU occurrences lane
+// j of a group (LPR = D/4 lanes inside one 16-lane DPP row) loads key, descriptor and destination of occurrence j (and,
+// where the trip is longer than the group, of j + LPR, ... in a register each),
+// decodes it, loads ITS cA / cB and forms the 32-bit byte offset of its gradient row from one uniform base; each
+// occurrence's values then reach the group's lanes by a DPP broadcast (no memory, no LDS).  Whether an occurrence starts a
+// run, and what happens to the accumulator in front of it (store to the row / to pfirst / drop the dummy row's), is
+// decided on its lane too, from its left neighbour's key: the per-occurrence body is row load, mul, fma, add and one
+// branch on a head.  Wv (at most 6 x 8 x D floats) is staged in LDS.  Windows, groups, the order of the additions and
+// every decision are pull_kernel's: the two give the same bits (tests/test_gpu_pull_lanes.py).
+struct PullLaneSeg { uint32_t goff, ldg4, caoff, cboff; float constA; int useA; };   // byte offsets from PullLanes.base
+struct PullLanes {
+  const char* base;            // lowest of the G / cA / cB pointers a launch can touch
+  PullLaneSeg seg[6];
+  const float* Wv[6];          // as pull_kernel's table: the targets' fall back to the first call's
+  int nf[6];
+};
+typedef __attribute__((address_space(1))) char gchar;
+typedef __attribute__((address_space(1))) score_v4f gv4f;
+
+// value of lane U of the caller's group (LPR consecutive lanes inside one DPP row), in every lane of the group
+template <int LPR, int U>
+__device__ __forceinline__ int grp_bcast_c(int v) {
+  // (bound_ctrl with every lane written: no "old" operand for the compiler to set up in front of each one)
+  if (LPR == 16) return __builtin_amdgcn_update_dpp(0, v, 0x150 + U, 0xf, 0xf, true);           // row_newbcast:U
+  if (LPR == 8) {   // two groups a row: banks 0-1 take lane U, banks 2-3 lane U + 8
+    const int r = __builtin_amdgcn_update_dpp(0, v, 0x150 + (U & 7), 0xf, 0x3, false);
+    return __builtin_amdgcn_update_dpp(r, v, 0x150 + (U & 7) + 8, 0xf, 0xc, false);
+  }
+  return __builtin_amdgcn_update_dpp(0, v, (U & 3) * 0x55, 0xf, 0xf, true);                     // quad_perm:[U,U,U,U]
+}
+template <int LPR>
+__device__ __forceinline__ int grp_bcast(int v, int u) {   // u is a constant after unrolling
+  switch (u) {
+    case 0: return grp_bcast_c<LPR, 0>(v);   case 1: return grp_bcast_c<LPR, 1>(v);
+    case 2: return grp_bcast_c<LPR, 2>(v);   case 3: return grp_bcast_c<LPR, 3>(v);
+    case 4: return grp_bcast_c<LPR, 4>(v);   case 5: return grp_bcast_c<LPR, 5>(v);
+    case 6: return grp_bcast_c<LPR, 6>(v);   case 7: return grp_bcast_c<LPR, 7>(v);
+    case 8: return grp_bcast_c<LPR, 8>(v);   case 9: return grp_bcast_c<LPR, 9>(v);
+    case 10: return grp_bcast_c<LPR, 10>(v); case 11: return grp_bcast_c<LPR, 11>(v);
+    case 12: return grp_bcast_c<LPR, 12>(v); case 13: return grp_bcast_c<LPR, 13>(v);
+    case 14: return grp_bcast_c<LPR, 14>(v); default: return grp_bcast_c<LPR, 15>(v);
+  }
+}
+
+template <int MODE, int LPR, int TU>
+__global__ __launch_bounds__(256) void pull_kernel_lanes(const PullArgs a, const PullLanes la,
+                                                         const uint32_t* __restrict__ keys,
+                                                         const uint32_t* __restrict__ vals, int64_t n, int WS,
+                                                         float* __restrict__ out, float* __restrict__ pfirst,
+                                                         float* __restrict__ plast) {
+#pragma clang fp contract(off)   // mul, fma, add as written: pull_kernel's roundings
+  static_assert(MODE == 1 || MODE == 2, "model segments only");
+  static_assert((LPR == 4 || LPR == 8 || LPR == 16) && (TU == 8 || TU == 16), "a group inside one DPP row");
+  constexpr int D = LPR * 4, GPB = 256 / LPR;
+  constexpr int NM = TU > LPR ? TU / LPR : 1;            // metadata registers per lane (a trip is longer than a narrow group)
+  const int j = threadIdx.x % LPR;                       // this lane's occurrences of a trip, and its float4 of the row
+  const int64_t w = (int64_t)blockIdx.x * GPB + threadIdx.x / LPR;
+  __shared__ PullLaneSeg tab[6];
+  __shared__ float4 wvs[MODE == 2 ? 6 * 8 * LPR : 1];    // [segment][feature][D/4]
+  if (threadIdx.x == 0) {
+#pragma unroll
+    for (int sg = 0; sg < 6; ++sg) tab[sg] = la.seg[sg];
+  }
+  if (MODE == 2) {
+    // exactly the slices pull_kernel can address: f < nf[sg] (<= 8).  The six requests together, then the six writes (a
+    // load inside each condition was six round trips in front of every workgroup's first window)
+    float4 t[6];
+#pragma unroll
+    for (int sg = 0; sg < 6; ++sg)
+      t[sg] = ld4_global(la.Wv[sg] + ((int)threadIdx.x < la.nf[sg] * LPR ? threadIdx.x * 4 : 0));
+#pragma unroll
+    for (int sg = 0; sg < 6; ++sg)
+      if ((int)threadIdx.x < la.nf[sg] * LPR) wvs[sg * 8 * LPR + threadIdx.x] = t[sg];
+  }
+  __syncthreads();
+  const int64_t start = w * WS;
+  if (start >= n) return;
+  const int64_t end = start + WS < n ? start + WS : n;
+  const int len = (int)(end - start);
+  const uint32_t* __restrict__ kp = keys + start;
+  const uint32_t* __restrict__ vp = vals + start;
+  const uint32_t* __restrict__ dp = a.uid ? a.uid + start : kp;   // a run's destination: its unique position or its key
+  // everything the window's start needs in one round trip, the first trip's metadata with it
+  uint32_t lastk = kp[len - 1], leftk = keys[start > 0 ? start - 1 : 0];
+  uint32_t cur = kp[0], cur_dst = dp[0];
+  uint32_t key[NM], desc[NM], dstv[NM];
+#pragma unroll
+  for (int r = 0; r < NM; ++r) {
+    const int pos = r * LPR + j < len - 1 ? r * LPR + j : len - 1;
+    key[r] = kp[pos]; desc[r] = vp[pos]; dstv[r] = dp[pos];
+  }
+  // (held here: the compiler otherwise moves all but lastk's load behind the return below, a second and third round trip)
+  asm volatile("" : "+v"(leftk), "+v"(cur), "+v"(cur_dst));
+#pragma unroll
+  for (int r = 0; r < NM; ++r) asm volatile("" : "+v"(key[r]), "+v"(desc[r]), "+v"(dstv[r]));
+  if (a.zero_is_dummy && lastk == 0) return;             // keys ascend: a window of dummy-row uses only
+  const bool first_open = start > 0 && leftk == cur;
+  const bool dummy = a.zero_is_dummy != 0;
+  bool is_first = true;
+  float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
+  const gchar* base = (const gchar*)la.base;
+  const int gsh = (threadIdx.x & 63) & ~(LPR - 1);       // first lane of the group within the wave
+  auto store_out = [&](uint32_t dst) {
+    st4(out + (int64_t)dst * D + j * 4, acc);
+    if (a.flags && j == 0) a.flags[dst] = 2;
+  };
+  for (int t0 = 0; t0 < len; t0 += TU) {
+    // ---- this lane's occurrences: number r * LPR + j of the trip in register r
+    uint32_t goff[NM];
+    int wvi[NM];
+    float ca[NM], cb[NM], pa[NM], pb[NM];
+    int useA[NM];
+#pragma unroll
+    for (int r = 0; r < NM; ++r) {
+      int seg = desc[r] >> 29;
+      seg = seg > 5 ? 5 : seg;
+      const uint32_t f = (desc[r] >> 26) & 7, k = (desc[r] >> 21) & 31, bt = desc[r] & 0x1FFFFF;
+      const PullLaneSeg si = tab[seg];
+      goff[r] = si.goff + bt * si.ldg4 + f * (D * 4);
+      wvi[r] = seg * 8 * LPR + (int)f * LPR;
+      ca[r] = si.constA; cb[r] = 0.f; useA[r] = si.useA; pa[r] = 0.f; pb[r] = 0.f;
+      if (MODE == 2) {
+        const uint32_t co = (bt * (uint32_t)a.K + k) * 4;
+        pa[r] = *(const gfloat*)(base + (uint64_t)(si.caoff + co));
+        pb[r] = *(const gfloat*)(base + (uint64_t)(si.cboff + co));
+      }
+    }
+    // ---- the trip's rows, all requested together; the next trip's metadata behind them
+    score_v4f g[TU];
+#pragma unroll
+    for (int u = 0; u < TU; ++u) {
+      const uint32_t o = (uint32_t)grp_bcast<LPR>((int)goff[u / LPR], u % LPR) + j * 16;
+      g[u] = *(const gv4f*)(base + (uint64_t)o);
+    }
+    uint32_t nkey[NM], ndesc[NM], ndst[NM];
+#pragma unroll
+    for (int r = 0; r < NM; ++r) {
+      const int pos = t0 + TU + r * LPR + j < len - 1 ? t0 + TU + r * LPR + j : len - 1;
+      nkey[r] = kp[pos]; ndesc[r] = vp[pos]; ndst[r] = dp[pos];
+    }
+    // ---- what happens in front of each of this lane's occurrences
+    const int cnt = len - t0;                            // occurrences of this trip (>= TU except in the list's last window)
+    uint32_t prevk[NM], prevd[NM], gm = 0;               // gm: the group's run heads, bit = number in the trip
+    bool head[NM];
+#pragma unroll
+    for (int r = 0; r < NM; ++r) {
+      const bool valid = r * LPR + j < TU && r * LPR + j < cnt;
+      // the left neighbour's key and destination: row_shr:1 inside the register, the last lane of the register before
+      // (or the run carried into the trip) for the group's first lane
+      const uint32_t ck = r == 0 ? cur : (uint32_t)grp_bcast<LPR>((int)key[r > 0 ? r - 1 : 0], LPR - 1);
+      const uint32_t cd = r == 0 ? cur_dst : (uint32_t)grp_bcast<LPR>((int)dstv[r > 0 ? r - 1 : 0], LPR - 1);
+      prevk[r] = (uint32_t)__builtin_amdgcn_update_dpp((int)ck, (int)key[r], 0x111, 0xf, 0xf, false);
+      prevd[r] = (uint32_t)__builtin_amdgcn_update_dpp((int)cd, (int)dstv[r], 0x111, 0xf, 0xf, false);
+      prevk[r] = j == 0 ? ck : prevk[r];
+      prevd[r] = j == 0 ? cd : prevd[r];
+      head[r] = valid && key[r] != prevk[r];
+      gm |= ((uint32_t)(__ballot(head[r]) >> gsh) & ((1u << (TU < LPR ? TU : LPR)) - 1u)) << (r * LPR);
+    }
+    // bits 0-1: 0 same run; 1 store the row; 2 store the window's first partial sum; 3 the dummy row's, dropped
+    // bit 2: inside the list; bits 3..: the Wv slice in LDS
+    int meta[NM];
+#pragma unroll
+    for (int r = 0; r < NM; ++r) {
+      const bool valid = r * LPR + j < TU && r * LPR + j < cnt;
+      int act = 0;
+      if (head[r])
+        act = (prevk[r] == 0 && dummy) ? 3 : ((is_first && first_open && (gm & ((1u << (r * LPR + j)) - 1u)) == 0) ? 2 : 1);
+      meta[r] = act | (valid ? 4 : 0) | (wvi[r] << 3);
+      if (MODE == 2) {
+        ca[r] = (useA[r] & 1) ? pa[r] : ca[r];
+        cb[r] = (useA[r] & 2) ? pb[r] : 0.f;
+      }
+    }
+    is_first = is_first && gm == 0;
+    cur = (uint32_t)grp_bcast<LPR>((int)key[NM - 1], (TU - 1) % LPR);    // (positions past the end are clamped onto the last occurrence)
+    cur_dst = (uint32_t)grp_bcast<LPR>((int)dstv[NM - 1], (TU - 1) % LPR);
+    // ---- the occurrences in order
+    auto consume = [&](auto chk) {
+      constexpr bool CHECK = decltype(chk)::value;
+      // (the Wv slice of occurrence u + 1 is read from LDS while u is worked on)
+      int m = grp_bcast<LPR>(meta[0], 0);
+      float4 wv = make_float4(0.f, 0.f, 0.f, 0.f), wv_n = wv;
+      if (MODE == 2) wv = wvs[(m >> 3) + j];
+#pragma unroll
+      for (int u = 0; u < TU; ++u) {
+        const int m_n = u + 1 < TU ? grp_bcast<LPR>(meta[(u + 1 < TU ? u + 1 : u) / LPR], (u + 1) % LPR) : 0;
+        if (MODE == 2 && u + 1 < TU) wv_n = wvs[(m_n >> 3) + j];
+        const uint32_t d_u = (uint32_t)grp_bcast<LPR>((int)prevd[u / LPR], u % LPR);
+        const float ca_u = __int_as_float(grp_bcast<LPR>(__float_as_int(ca[u / LPR]), u % LPR));
+        if (m & 3) {
+          if ((m & 3) == 1) store_out(d_u);
+          else if ((m & 3) == 2) st4(pfirst + w * D + j * 4, acc);
+          acc = make_float4(0.f, 0.f, 0.f, 0.f);
+        }
+        float4 r;
+        r.x = ca_u * g[u].x; r.y = ca_u * g[u].y; r.z = ca_u * g[u].z; r.w = ca_u * g[u].w;
+        if (MODE == 2) {
+          const float cb_u = __int_as_float(grp_bcast<LPR>(__float_as_int(cb[u / LPR]), u % LPR));
+          r = fma4(cb_u, wv, r);
+        }
+        if (!CHECK || (m & 4)) { acc.x = acc.x + r.x; acc.y = acc.y + r.y; acc.z = acc.z + r.z; acc.w = acc.w + r.w; }
+        m = m_n; wv = wv_n;
+      }
+    };
+    if (cnt >= TU) consume(std::false_type());
+    else consume(std::true_type());
+#pragma unroll
+    for (int r = 0; r < NM; ++r) { key[r] = nkey[r]; desc[r] = ndesc[r]; dstv[r] = ndst[r]; }
+  }
+  if (cur != 0 || !dummy) {
+    const bool open_right = end < n && keys[end] == cur;
+    if (is_first && first_open) st4(pfirst + w * D + j * 4, acc);
+    else if (open_right) st4(plast + w * D + j * 4, acc);
+    else store_out(cur_dst);
+  }
+}
+
 // first index in [lo, n) whose key differs from `key` (keys ascending, keys[lo-1] == key).  Most runs end within a
 // window or two: gallop (lo+1, +2, +4, ...) to bracket the end, then bisect the bracket -- a plain bisection of
 // [lo, n) is ~21 dependent loads for every open window.
@@ -425,6 +644,67 @@ __global__ __launch_bounds__(256) void pull_fixup_kernel(const PullArgs a, const
 // chip still gets >= ~16k independent groups
 int score_pull_window(int64_t n) { return n >= (1 << 20) ? 64 : n >= (1 << 19) ? 32 : n >= (1 << 18) ? 16 : 8; }
 
+// 1: a launch of contribution form `mode` at row width D, whose G / cA / cB bytes span `span_bytes` from the lowest
+// pointer, takes pull_kernel_lanes; 0: pull_kernel.  (The launcher also wants nf[] / rows[] and force_old == 0.)
+extern "C" int score_pull_form(int32_t D, int32_t mode, int64_t span_bytes) {
+  if (mode != 1 && mode != 2) return 0;
+  if (D != 16 && D != 32 && D != 64) return 0;
+  return span_bytes > 0 && span_bytes <= ((int64_t)1 << 32) ? 1 : 0;
+}
+static int g_pull_last_form = -1;
+extern "C" int score_pull_last_form(void) { return g_pull_last_form; }   // form of this process's latest launch (-1: none yet)
+
+// the lanes form's table and the span of what it can reach; false: the caller's arguments do not allow it
+static bool pull_lanes_table(const PullArgs& a, int mode, PullLanes* L, int64_t* span) {
+  const char* lo = nullptr; const char* hi = nullptr;
+  const float* Ge[6]; const float* cAe[6]; const float* cBe[6];
+  for (int sg = 0; sg < 6; ++sg) {
+    if (a.nf[sg] <= 0 || a.nf[sg] > 8 || a.rows[sg] <= 0 || a.rows[sg] > (1 << 21)) return false;
+    const int c = sg < 4 ? ((sg & 2) ? 2 : 0) : 0;            // pull_kernel's table, entry for entry
+    Ge[sg] = a.G[sg] ? a.G[sg] : a.G[4];
+    cAe[sg] = a.cA[c]; cBe[sg] = a.cB[c];
+    L->Wv[sg] = a.Wv[sg < 4 ? sg : sg - 4];
+    L->nf[sg] = a.nf[sg];
+    if (!Ge[sg] || a.ldg[sg] < 0 || a.gcol[sg] < 0) return false;
+    if (mode == 2 && (!cAe[sg] || !cBe[sg] || !L->Wv[sg])) return false;
+  }
+  auto reach = [&](const float* p, int64_t floats) {
+    const char* b = reinterpret_cast<const char*>(p);
+    if (!lo || b < lo) lo = b;
+    if (!hi || b + floats * 4 > hi) hi = b + floats * 4;
+  };
+  for (int sg = 0; sg < 6; ++sg) {
+    reach(Ge[sg], (a.rows[sg] - 1) * a.ldg[sg] + a.gcol[sg] + (int64_t)a.nf[sg] * a.D);
+    if (mode == 2) { reach(cAe[sg], a.rows[sg] * a.K); reach(cBe[sg], a.rows[sg] * a.K); }
+  }
+  *span = hi - lo;
+  if (*span > ((int64_t)1 << 32)) return false;
+  L->base = lo;
+  for (int sg = 0; sg < 6; ++sg) {
+    PullLaneSeg& t = L->seg[sg];
+    t.goff = (uint32_t)(reinterpret_cast<const char*>(Ge[sg]) - lo) + (uint32_t)a.gcol[sg] * 4u;
+    t.ldg4 = (uint32_t)a.ldg[sg] * 4u;
+    t.caoff = mode == 2 ? (uint32_t)(reinterpret_cast<const char*>(cAe[sg]) - lo) : 0u;
+    t.cboff = mode == 2 ? (uint32_t)(reinterpret_cast<const char*>(cBe[sg]) - lo) : 0u;
+    t.constA = a.constA[sg];
+    t.useA = (sg < 4 && a.cA[sg] ? 1 : 0) | (sg < 4 && a.cB[sg] ? 2 : 0);
+  }
+  return true;
+}
+
+template <int MODE>
+static void pull_lanes_launch(const PullArgs& a, const PullLanes& L, int LPR, int WS, unsigned blocks, const uint32_t* keys,
+                              const uint32_t* vals, int64_t n, float* out, float* pfirst, float* plast, hipStream_t s) {
+#define PULL_LANES_GO(lpr, tu) \
+  hipLaunchKernelGGL((pull_kernel_lanes<MODE, lpr, tu>), dim3(blocks), dim3(256), 0, s, a, L, keys, vals, n, WS, out, pfirst, plast)
+  // a trip of 16 occurrences where the window holds as many, of 8 in the windows of 8 -- and for groups of four lanes,
+  // where sixteen would take four metadata registers a lane and 154 VGPRs
+  if (LPR == 4) PULL_LANES_GO(4, 8);
+  else if (LPR == 8) { if (WS < 16) PULL_LANES_GO(8, 8); else PULL_LANES_GO(8, 16); }
+  else { if (WS < 16) PULL_LANES_GO(16, 8); else PULL_LANES_GO(16, 16); }
+#undef PULL_LANES_GO
+}
+
 int score_launch_pull(PullArgs& a, const uint32_t* keys, const uint32_t* vals, int64_t n, float* out,
                       float* partials, int64_t partial_floats, hipStream_t s) {
   const int WS = score_pull_window(n);
@@ -442,7 +722,15 @@ int score_launch_pull(PullArgs& a, const uint32_t* keys, const uint32_t* vals, i
   // contribution form: owner-side row sum (descriptors are source slots), constant coefficients, or the
   // co-attention's per-(unit, k) coefficients
   const int mode = (a.G[1] == nullptr && a.ldg[0] == 0) ? 0 : (a.cA[0] ? 2 : 1);
-  if (mode == 0) hipLaunchKernelGGL(pull_kernel<0>, dim3(blocks), dim3(256), 0, s, a, keys, vals, n, WS, out, pfirst, plast);
+  PullLanes L;
+  int64_t span = 0;
+  const bool lanes = !a.force_old && mode != 0 && pull_lanes_table(a, mode, &L, &span) && score_pull_form(a.D, mode, span);
+  g_pull_last_form = lanes ? 1 : 0;
+  if (lanes) {
+    if (mode == 1) pull_lanes_launch<1>(a, L, LPR, WS, blocks, keys, vals, n, out, pfirst, plast, s);
+    else pull_lanes_launch<2>(a, L, LPR, WS, blocks, keys, vals, n, out, pfirst, plast, s);
+  }
+  else if (mode == 0) hipLaunchKernelGGL(pull_kernel<0>, dim3(blocks), dim3(256), 0, s, a, keys, vals, n, WS, out, pfirst, plast);
   else if (mode == 1) hipLaunchKernelGGL(pull_kernel<1>, dim3(blocks), dim3(256), 0, s, a, keys, vals, n, WS, out, pfirst, plast);
   else hipLaunchKernelGGL(pull_kernel<2>, dim3(blocks), dim3(256), 0, s, a, keys, vals, n, WS, out, pfirst, plast);
   SCORE_CHECK_LAUNCH();
