@@ -470,28 +470,26 @@ def rank_workspace_bytes(cfg, L, n_cand):
     return n.value
 
 
+def _catalog_plan(name, cfg, *sizes):
+    """(chunk, nchunk, workspace bytes) from the plan function `name` of the library at (L, span[, k])"""
+    chunk, nchunk, n = C.c_int32(0), C.c_int32(0), C.c_int64(0)
+    check(getattr(load(), name)(C.byref(cfg), *[int(x) for x in sizes], C.byref(chunk), C.byref(nchunk), C.byref(n)), name)
+    return chunk.value, nchunk.value, n.value
+
+
 def catalog_plan(cfg, L, N, k):
     """(chunk, nchunk, workspace bytes) of score_catalog_topk for L lines against N items: score_catalog_plan"""
-    chunk, nchunk, n = C.c_int32(0), C.c_int32(0), C.c_int64(0)
-    check(load().score_catalog_plan(C.byref(cfg), int(L), int(N), int(k), C.byref(chunk), C.byref(nchunk), C.byref(n)),
-          "score_catalog_plan")
-    return chunk.value, nchunk.value, n.value
+    return _catalog_plan("score_catalog_plan", cfg, L, N, k)
 
 
 def catalog_cands_plan(cfg, L, max_count, k):
     """(chunk, nchunk, workspace bytes) of score_catalog_topk_in for L lines of at most max_count candidates"""
-    chunk, nchunk, n = C.c_int32(0), C.c_int32(0), C.c_int64(0)
-    check(load().score_catalog_cands_plan(C.byref(cfg), int(L), int(max_count), int(k), C.byref(chunk), C.byref(nchunk), C.byref(n)),
-          "score_catalog_cands_plan")
-    return chunk.value, nchunk.value, n.value
+    return _catalog_plan("score_catalog_cands_plan", cfg, L, max_count, k)
 
 
 def catalog_ranks_plan(cfg, L, span):
     """(chunk, nchunk, workspace bytes) of score_catalog_ranks (span = N) / score_catalog_ranks_in (span = max_count)"""
-    chunk, nchunk, n = C.c_int32(0), C.c_int32(0), C.c_int64(0)
-    check(load().score_catalog_ranks_plan(C.byref(cfg), int(L), int(span), C.byref(chunk), C.byref(nchunk), C.byref(n)),
-          "score_catalog_ranks_plan")
-    return chunk.value, nchunk.value, n.value
+    return _catalog_plan("score_catalog_ranks_plan", cfg, L, span)
 
 
 def history_exclusions_plan(L, N, max_events=0):

@@ -605,76 +605,41 @@ int score_catalog_zcat(const CatalogArgs& a, hipStream_t s) {
   return 0;
 }
 
-int score_catalog_select(const CatalogArgs& a, hipStream_t s) {
-  if (a.L <= 0 || a.N <= 0 || a.N1 != CT_N1 || a.k < 1 || a.k > SCORE_CATALOG_KMAX) return SCORE_E_SHAPE;
-  if (a.chunk <= 0 || a.chunk % CT_ROWS || (int64_t)a.nchunk * a.chunk < a.N || (int64_t)(a.nchunk - 1) * a.chunk >= a.N ||
-      (int64_t)a.L * a.nchunk >= (1LL << 31))
-    return SCORE_E_SHAPE;
-  const size_t lds = (size_t)CT_SM_FLOATS * sizeof(float);
-  static thread_local bool attr_set = false;
-  if (!attr_set) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(catalog_score_kernel<false>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                       (int)lds);
-    if (e != hipSuccess) return (int)e;
-    attr_set = true;
-  }
-  hipLaunchKernelGGL(catalog_score_kernel<false>, dim3((unsigned)(a.L * a.nchunk)), dim3(64 * CT_NW), lds, s, a);
-  SCORE_CHECK_LAUNCH();
-  hipLaunchKernelGGL(catalog_merge_kernel, dim3((unsigned)a.L), dim3(64), 0, s, a);
-  SCORE_CHECK_LAUNCH();
-  return 0;
-}
 
-// The candidate form: the plan is that of a catalogue of a.max_count items (score_catalog_chunks with the longest list in N's
-// place); a.all_logits is cand_logits, aligned with cand_idx
-int score_catalog_select_in(const CatalogArgs& a, hipStream_t s) {
-  if (a.L <= 0 || a.N <= 0 || a.N1 != CT_N1 || a.k < 1 || a.k > SCORE_CATALOG_KMAX || a.max_count <= 0) return SCORE_E_SHAPE;
-  if (!a.cand_off || !a.cand_idx) return SCORE_E_BADARG;
-  if (a.chunk <= 0 || a.chunk % CT_ROWS || (int64_t)a.nchunk * a.chunk < a.max_count ||
-      (int64_t)(a.nchunk - 1) * a.chunk >= a.max_count || (int64_t)a.L * a.nchunk >= (1LL << 31))
-    return SCORE_E_SHAPE;
-  const size_t lds = (size_t)CT_SM_FLOATS_IN * sizeof(float);
-  static thread_local bool attr_set = false;
-  if (!attr_set) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(catalog_score_kernel<true>),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) return (int)e;
-    attr_set = true;
-  }
-  hipLaunchKernelGGL(catalog_score_kernel<true>, dim3((unsigned)(a.L * a.nchunk)), dim3(64 * CT_NW), lds, s, a);
-  SCORE_CHECK_LAUNCH();
-  hipLaunchKernelGGL(catalog_merge_kernel, dim3((unsigned)a.L), dim3(64), 0, s, a);
-  SCORE_CHECK_LAUNCH();
-  return 0;
-}
-
-// The counting form (score_catalog_ranks / score_catalog_ranks_in): the same cut and the same grid, RANKS instantiations, then a
-// wave per line over the chunks' partials.  span: what the plan cuts, a.N or a.max_count
+// Every sweep of the catalogue, in its four forms: CAND, the lines' candidate lists in the whole catalogue's place (the plan is
+// that of a catalogue of a.max_count items, chunk / nchunk cut list positions, a.all_logits is cand_logits, aligned with cand_idx);
+// RANKS, the counting form (score_catalog_ranks*) in the selecting one's place.  The form's checks, the cut against the span the
+// plan was made for, the scoring kernel on a workgroup per (line, chunk), then a wave per line over the chunks' lists or partials.
 namespace {
-template <bool CAND>
-int catalog_count_launch(const CatalogArgs& a, int span, hipStream_t s) {
+template <bool CAND, bool RANKS>
+int catalog_sweep_launch(const CatalogArgs& a, hipStream_t s) {
+  const int span = CAND ? a.max_count : a.N;
   if (a.L <= 0 || a.N <= 0 || a.N1 != CT_N1 || span <= 0) return SCORE_E_SHAPE;
-  if (!a.tgt_off || !a.tgt_idx || !a.rpart || !a.ahead || !a.tgt_logit || !a.state || !a.n_scored) return SCORE_E_BADARG;
-  if (a.max_targets < 1 || a.max_targets > SCORE_CATALOG_TMAX) return SCORE_E_BADARG;
+  if (!RANKS && (a.k < 1 || a.k > SCORE_CATALOG_KMAX)) return SCORE_E_SHAPE;
+  if (RANKS && (!a.tgt_off || !a.tgt_idx || !a.rpart || !a.ahead || !a.tgt_logit || !a.state || !a.n_scored)) return SCORE_E_BADARG;
+  if (RANKS && (a.max_targets < 1 || a.max_targets > SCORE_CATALOG_TMAX)) return SCORE_E_BADARG;
   if (CAND && (!a.cand_off || !a.cand_idx)) return SCORE_E_BADARG;
   if (a.chunk <= 0 || a.chunk % CT_ROWS || (int64_t)a.nchunk * a.chunk < span || (int64_t)(a.nchunk - 1) * a.chunk >= span ||
       (int64_t)a.L * a.nchunk >= (1LL << 31))
     return SCORE_E_SHAPE;
-  const size_t lds = (size_t)((CAND ? CT_SM_FLOATS_IN : CT_SM_FLOATS) + CT_SM_RK) * sizeof(float);
+  const size_t lds = (size_t)((CAND ? CT_SM_FLOATS_IN : CT_SM_FLOATS) + (RANKS ? CT_SM_RK : 0)) * sizeof(float);
   static thread_local bool attr_set = false;
   if (!attr_set) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(catalog_score_kernel<CAND, true>),
+    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(catalog_score_kernel<CAND, RANKS>),
                                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     if (e != hipSuccess) return (int)e;
     attr_set = true;
   }
-  hipLaunchKernelGGL((catalog_score_kernel<CAND, true>), dim3((unsigned)(a.L * a.nchunk)), dim3(64 * CT_NW), lds, s, a);
+  hipLaunchKernelGGL((catalog_score_kernel<CAND, RANKS>), dim3((unsigned)(a.L * a.nchunk)), dim3(64 * CT_NW), lds, s, a);
   SCORE_CHECK_LAUNCH();
-  hipLaunchKernelGGL(catalog_ranks_reduce_kernel, dim3((unsigned)a.L), dim3(64), 0, s, a);
+  if (RANKS) hipLaunchKernelGGL(catalog_ranks_reduce_kernel, dim3((unsigned)a.L), dim3(64), 0, s, a);
+  else hipLaunchKernelGGL(catalog_merge_kernel, dim3((unsigned)a.L), dim3(64), 0, s, a);
   SCORE_CHECK_LAUNCH();
   return 0;
 }
 }  // namespace
 
-int score_catalog_count(const CatalogArgs& a, hipStream_t s) { return catalog_count_launch<false>(a, a.N, s); }
-int score_catalog_count_in(const CatalogArgs& a, hipStream_t s) { return catalog_count_launch<true>(a, a.max_count, s); }
+int score_catalog_sweep(const CatalogArgs& a, bool cand, bool ranks, hipStream_t s) {
+  if (ranks) return cand ? catalog_sweep_launch<true, true>(a, s) : catalog_sweep_launch<false, true>(a, s);
+  return cand ? catalog_sweep_launch<true, false>(a, s) : catalog_sweep_launch<false, false>(a, s);
+}

@@ -2023,19 +2023,25 @@ extern "C" int score_forward(const score_config_t* cfg, const score_state_t* st,
 // launches score_forward makes for a batch of L samples, up to the head --, then the line-form head and the loss reduction over
 // the L * C terms.
 namespace {
-// Behind the workspace of a batch of L samples (build_ws at B = L, untouched): the lines' part of fc1's pre-activation [L, FC1], the
-// per-sample loss terms [L * C], and zero ids for the three index tensors a point model's batch does not have and for the target
-// item of the B = L pass (int32 [L * T * max(Fu, Fi)]; the head input's item columns get row 0 there and are not read)
-struct RankWS { int64_t zline, lossb, zero_ids, n_zero_ids, total; };
-void build_rank_ws(const Dims& d, int L, int C, RankWS* r) {
+// What every line-form pass keeps behind the workspace of a batch of L samples (build_ws at B = L, untouched): the lines' part of
+// fc1's pre-activation [L, FC1], then `mid` floats of the pass's own (none at 0), then zero ids for the three index tensors a point
+// model's batch does not have and for the target item of the B = L pass (int32 [L * T * max(Fu, Fi)]; the head input's item columns
+// get row 0 there and are not read).  -> the Taker behind them, for what the pass carves next
+struct LineWS { int64_t zline, mid, zero_ids, n_zero_ids; };
+Taker carve_line_ws(const Dims& d, int L, int64_t mid, LineWS* r) {
   WS w;
   build_ws(d, L, &w);
   Taker take = {w.total};
   r->zline = take((int64_t)L * FC1);
-  r->lossb = take((int64_t)L * C);
+  r->mid = mid > 0 ? take(mid) : 0;
   r->n_zero_ids = (int64_t)L * d.T * (d.Fu > d.Fi ? d.Fu : d.Fi);
   r->zero_ids = take(r->n_zero_ids);
-  r->total = take.cur;
+  return take;
+}
+// the ranking pass: mid = the per-sample loss terms [L * C]
+struct RankWS : LineWS { int64_t total; };
+void build_rank_ws(const Dims& d, int L, int C, RankWS* r) {
+  r->total = carve_line_ws(d, L, (int64_t)L * C, r).cur;
 }
 // the model types and shapes the pass covers, and its argument checks that need no device
 int rank_dims(const score_config_t* cfg, int L, int C, Dims* d) {
@@ -2117,28 +2123,32 @@ extern "C" int score_rank_forward(const score_config_t* cfg, const score_state_t
   RankArgs a;
   rank_head_args(c, st, L, C, &a);
   a.cand = rb->cand_items; a.label = rb->label;
-  a.zline = ws + r.zline; a.y = y_pred; a.lossb = ws + r.lossb;
+  a.zline = ws + r.zline; a.y = y_pred; a.lossb = ws + r.mid;
   G(score_rank_head(a, s));
-  return loss_tail_at(c, f.sd, reg_lambda, L * C, ws + r.lossb, loss, global_batch(st, L * C));
+  return loss_tail_at(c, f.sd, reg_lambda, L * C, ws + r.mid, loss, global_batch(st, L * C));
 }
 
 // ---------------------------------------------------------------- top-K over a whole item catalogue (GRU4Rec, Caser; catalog.hip)
 // score_catalog_build: zcat [N, 200], the catalogue's half of fc1's pre-activation.  score_catalog_topk: the prefix of the
 // ranking pass at B = L, the line kernel alone, then a scoring workgroup per (line, chunk) and a merge per line.
 namespace {
-// Behind the workspace of a batch of L samples (build_ws at B = L, untouched): zline [L, FC1], the zero ids (as RankWS) and the
-// chunks' lists, [L, nchunk, k] 64-bit keys
-struct CatalogWS { int64_t zline, zero_ids, n_zero_ids, part, total; int chunk, nchunk; };
-void build_catalog_ws(const Dims& d, int L, int N, int k, CatalogWS* r) {
-  WS w;
-  build_ws(d, L, &w);
-  score_catalog_chunks(L, N, k, &r->chunk, &r->nchunk);
-  Taker take = {w.total};
-  r->zline = take((int64_t)L * FC1);
-  r->n_zero_ids = (int64_t)L * d.T * (d.Fu > d.Fi ? d.Fu : d.Fi);
-  r->zero_ids = take(r->n_zero_ids);
-  r->part = take((int64_t)L * r->nchunk * k * 2);
+// The workspace of every catalogue pass: zline and the zero ids (LineWS, nothing between them), then the per-chunk region -- the
+// selecting form's lists, [L, nchunk, k] 64-bit keys, or the counting form's integer partials, [L, nchunk, SCORE_CATALOG_RPART]
+// int32.  span, what the plan cuts: N, or the candidate lists' max_count
+struct CatalogWS : LineWS { int64_t part, total; int chunk, nchunk; };
+void build_catalog_ws(const Dims& d, int L, int span, int k, bool counting, CatalogWS* r) {
+  score_catalog_chunks(L, span, counting ? 1 : k, &r->chunk, &r->nchunk);
+  Taker take = carve_line_ws(d, L, 0, r);
+  r->part = take((int64_t)L * r->nchunk * (counting ? (int64_t)SCORE_CATALOG_RPART : (int64_t)k * 2));
   r->total = take.cur;
+}
+// what a *_struct_sizes function does with its value list: -> the number of values written, SCORE_E_BADARG for a null pointer or n
+// too small
+template <int32_t HAVE>
+int copy_sizes(const int64_t (&v)[HAVE], int64_t* out, int32_t n) {
+  if (!out || n < HAVE) return SCORE_E_BADARG;
+  for (int32_t i = 0; i < HAVE; ++i) out[i] = v[i];
+  return HAVE;
 }
 const int32_t CATALOG_NMAX = 1 << 30;        // (a step past the last item stays inside int32)
 int catalog_dims(const score_config_t* cfg, int L, int N, int k, Dims* d) {
@@ -2161,23 +2171,25 @@ void catalog_model_args(const Dims& d, const score_state_t* st, const score_cata
   a->W1 = W + P.fc_w[0]; a->W2 = W + P.fc_w[1]; a->b2 = W + P.fc_b[1]; a->W3 = W + P.fc_w[2]; a->b3 = W + P.fc_b[2];
   a->n_rows = clamp_rows(st->n_table_rows); a->id_status = st->id_status;
 }
-// score_catalog_topk (cands null: every line against the whole catalogue, logits = all_logits [L, N]) and
-// score_catalog_topk_in (every line against its own list, logits = cand_logits): the checks, rank_prefix, the line kernel and the
-// selection.  span, what the plan cuts: N, or the lists' max_count
-int catalog_topk(const score_config_t* cfg, const score_state_t* st, const score_catalog_t* cat, const score_catalog_lines_t* ln,
-                 const score_catalog_cands_t* cands, int32_t k, int32_t* top_idx, float* top_logit, float* logits, void* stream) {
+// The front half of every catalogue pass -- THE place to extend for a new form: the checks (cands null: every line
+// against the whole catalogue; else against its own list), the workspace, rank_prefix, the line kernel, and *a with the model's
+// side and every field the forms share.  k: 1 for the counting form.  own_ok: the form's own pointer checks, tested where they
+// have always stood, behind the shape checks and in front of the workspace's.  -> *part, the per-chunk region
+int catalog_front(const score_config_t* cfg, const score_state_t* st, const score_catalog_t* cat, const score_catalog_lines_t* ln,
+                  const score_catalog_cands_t* cands, int32_t k, bool counting, bool own_ok, void* stream, CatalogArgs* a,
+                  float** part) {
   Pass c;
   SCORE_TRY(catalog_dims(cfg, ln->L, cat->N, k, &c.d));
   if (cands) SCORE_TRY(catalog_dims(cfg, ln->L, cands->max_count, k, &c.d));
   if (!st->table || !st->w || !st->workspace || !cat->item_rows || !cat->zcat) return SCORE_E_BADARG;
   if (!ln->user_seq || !ln->length || !ln->target_user || (ln->excl_off && !ln->excl_idx)) return SCORE_E_BADARG;
   if (cands && (!cands->cand_off || !cands->cand_idx)) return SCORE_E_BADARG;
+  if (!own_ok) return SCORE_E_BADARG;
   const Dims& d = c.d;
   const int L = ln->L;
   CatalogWS r;
-  build_catalog_ws(d, L, cands ? cands->max_count : cat->N, k, &r);
+  build_catalog_ws(d, L, cands ? cands->max_count : cat->N, k, counting, &r);
   if (r.total * 4 > st->workspace_bytes) return SCORE_E_WORKSPACE;
-  hipStream_t s = (hipStream_t)stream;
   score_batch_t lb;
   FwdState f = {0.f, 1.f, nullptr, nullptr, 0, nullptr, nullptr, false};
   SCORE_TRY(rank_prefix(&c, &f, &lb, st, ln->user_seq, ln->length, ln->target_user, nullptr, L, ln->active_slices,
@@ -2186,28 +2198,55 @@ int catalog_topk(const score_config_t* cfg, const score_state_t* st, const score
   RankArgs ra;
   rank_head_args(c, st, L, 1, &ra);
   ra.zline = ws + r.zline;
-  G(score_rank_line(ra, s));
+  G(score_rank_line(ra, (hipStream_t)stream));
+  catalog_model_args(d, st, cat, a);
+  a->L = L; a->k = k; a->chunk = r.chunk; a->nchunk = r.nchunk;
+  a->zline = ws + r.zline; a->excl_off = ln->excl_off; a->excl_idx = ln->excl_idx;
+  if (cands) { a->cand_off = cands->cand_off; a->cand_idx = cands->cand_idx; a->max_count = cands->max_count; }
+  *part = ws + r.part;
+  return 0;
+}
+// score_catalog_topk (cands null; logits = all_logits [L, N]) and score_catalog_topk_in (logits = cand_logits): the front, then
+// the selection
+int catalog_topk(const score_config_t* cfg, const score_state_t* st, const score_catalog_t* cat, const score_catalog_lines_t* ln,
+                 const score_catalog_cands_t* cands, int32_t k, int32_t* top_idx, float* top_logit, float* logits, void* stream) {
   CatalogArgs a;
-  catalog_model_args(d, st, cat, &a);
-  a.L = L; a.k = k; a.chunk = r.chunk; a.nchunk = r.nchunk;
-  a.zline = ws + r.zline; a.excl_off = ln->excl_off; a.excl_idx = ln->excl_idx;
-  a.part = reinterpret_cast<unsigned long long*>(ws + r.part);
+  float* part;
+  SCORE_TRY(catalog_front(cfg, st, cat, ln, cands, k, false, true, stream, &a, &part));
+  a.part = reinterpret_cast<unsigned long long*>(part);
   a.top_idx = top_idx; a.top_logit = top_logit; a.all_logits = logits;
-  if (!cands) return score_catalog_select(a, s);
-  a.cand_off = cands->cand_off; a.cand_idx = cands->cand_idx; a.max_count = cands->max_count;
-  return score_catalog_select_in(a, s);
+  return score_catalog_sweep(a, cands != nullptr, false, (hipStream_t)stream);
+}
+// score_catalog_ranks / score_catalog_ranks_in, the exact rank of given items: the front, then the counting form of the scoring
+// kernel and its reduce
+int catalog_ranks(const score_config_t* cfg, const score_state_t* st, const score_catalog_t* cat, const score_catalog_lines_t* ln,
+                  const score_catalog_cands_t* cands, const score_catalog_targets_t* tg, int32_t* ahead, float* tgt_logit,
+                  int32_t* state, int32_t* n_scored, void* stream) {
+  if (tg->max_targets < 1 || tg->max_targets > SCORE_CATALOG_TMAX) return SCORE_E_BADARG;
+  CatalogArgs a;
+  float* part;
+  SCORE_TRY(catalog_front(cfg, st, cat, ln, cands, 1, true, tg->tgt_off && tg->tgt_idx, stream, &a, &part));
+  a.tgt_off = tg->tgt_off; a.tgt_idx = tg->tgt_idx; a.max_targets = tg->max_targets;
+  a.rpart = reinterpret_cast<int32_t*>(part);
+  a.ahead = ahead; a.tgt_logit = tgt_logit; a.state = state; a.n_scored = n_scored;
+  return score_catalog_sweep(a, cands != nullptr, true, (hipStream_t)stream);
+}
+// score_catalog_plan / score_catalog_ranks_plan (k = 1, counting)
+int catalog_plan(const score_config_t* cfg, int32_t L, int32_t span, int32_t k, bool counting, int32_t* chunk, int32_t* nchunk,
+                 int64_t* workspace_bytes) {
+  if (!cfg || !chunk || !nchunk || !workspace_bytes) return SCORE_E_BADARG;
+  Dims d;
+  SCORE_TRY(catalog_dims(cfg, L, span, k, &d));
+  CatalogWS r;
+  build_catalog_ws(d, L, span, k, counting, &r);
+  *chunk = r.chunk; *nchunk = r.nchunk; *workspace_bytes = r.total * 4;
+  return 0;
 }
 }  // namespace
 
 extern "C" int score_catalog_plan(const score_config_t* cfg, int32_t L, int32_t N, int32_t k, int32_t* chunk, int32_t* nchunk,
                                   int64_t* workspace_bytes) {
-  if (!cfg || !chunk || !nchunk || !workspace_bytes) return SCORE_E_BADARG;
-  Dims d;
-  SCORE_TRY(catalog_dims(cfg, L, N, k, &d));
-  CatalogWS r;
-  build_catalog_ws(d, L, N, k, &r);
-  *chunk = r.chunk; *nchunk = r.nchunk; *workspace_bytes = r.total * 4;
-  return 0;
+  return catalog_plan(cfg, L, N, k, false, chunk, nchunk, workspace_bytes);
 }
 
 extern "C" int score_catalog_build(const score_config_t* cfg, const score_state_t* st, const score_catalog_t* cat, void* stream) {
@@ -2244,76 +2283,13 @@ extern "C" int score_catalog_topk_in(const score_config_t* cfg, const score_stat
 extern "C" int score_catalog_cands_struct_sizes(int64_t* out, int32_t n) {
   const int64_t v[] = {(int64_t)sizeof(score_catalog_cands_t), (int64_t)offsetof(score_catalog_cands_t, cand_off),
                        (int64_t)offsetof(score_catalog_cands_t, cand_idx), (int64_t)offsetof(score_catalog_cands_t, max_count)};
-  const int32_t have = (int32_t)(sizeof(v) / sizeof(v[0]));
-  if (!out || n < have) return SCORE_E_BADARG;
-  for (int32_t i = 0; i < have; ++i) out[i] = v[i];
-  return have;
+  return copy_sizes(v, out, n);
 }
 
-// ---- ... the exact rank of given items: catalog_topk's front half, then the counting form of the scoring kernel and its reduce
-namespace {
-// Behind the workspace of a batch of L samples: zline [L, FC1], the zero ids (as CatalogWS) and the chunks' integer partials,
-// [L, nchunk, SCORE_CATALOG_RPART] int32
-struct CatalogRanksWS { int64_t zline, zero_ids, n_zero_ids, rpart, total; int chunk, nchunk; };
-void build_catalog_ranks_ws(const Dims& d, int L, int span, CatalogRanksWS* r) {
-  WS w;
-  build_ws(d, L, &w);
-  score_catalog_chunks(L, span, 1, &r->chunk, &r->nchunk);
-  Taker take = {w.total};
-  r->zline = take((int64_t)L * FC1);
-  r->n_zero_ids = (int64_t)L * d.T * (d.Fu > d.Fi ? d.Fu : d.Fi);
-  r->zero_ids = take(r->n_zero_ids);
-  r->rpart = take((int64_t)L * r->nchunk * SCORE_CATALOG_RPART);
-  r->total = take.cur;
-}
-int catalog_ranks(const score_config_t* cfg, const score_state_t* st, const score_catalog_t* cat, const score_catalog_lines_t* ln,
-                  const score_catalog_cands_t* cands, const score_catalog_targets_t* tg, int32_t* ahead, float* tgt_logit,
-                  int32_t* state, int32_t* n_scored, void* stream) {
-  if (tg->max_targets < 1 || tg->max_targets > SCORE_CATALOG_TMAX) return SCORE_E_BADARG;
-  Pass c;
-  SCORE_TRY(catalog_dims(cfg, ln->L, cat->N, 1, &c.d));
-  if (cands) SCORE_TRY(catalog_dims(cfg, ln->L, cands->max_count, 1, &c.d));
-  if (!st->table || !st->w || !st->workspace || !cat->item_rows || !cat->zcat) return SCORE_E_BADARG;
-  if (!ln->user_seq || !ln->length || !ln->target_user || (ln->excl_off && !ln->excl_idx)) return SCORE_E_BADARG;
-  if (cands && (!cands->cand_off || !cands->cand_idx)) return SCORE_E_BADARG;
-  if (!tg->tgt_off || !tg->tgt_idx) return SCORE_E_BADARG;
-  const Dims& d = c.d;
-  const int L = ln->L;
-  CatalogRanksWS r;
-  build_catalog_ranks_ws(d, L, cands ? cands->max_count : cat->N, &r);
-  if (r.total * 4 > st->workspace_bytes) return SCORE_E_WORKSPACE;
-  hipStream_t s = (hipStream_t)stream;
-  score_batch_t lb;
-  FwdState f = {0.f, 1.f, nullptr, nullptr, 0, nullptr, nullptr, false};
-  SCORE_TRY(rank_prefix(&c, &f, &lb, st, ln->user_seq, ln->length, ln->target_user, nullptr, L, ln->active_slices,
-                        reinterpret_cast<int32_t*>(st->workspace + r.zero_ids), r.n_zero_ids, stream));
-  float* ws = c.ws;
-  RankArgs ra;
-  rank_head_args(c, st, L, 1, &ra);
-  ra.zline = ws + r.zline;
-  G(score_rank_line(ra, s));
-  CatalogArgs a;
-  catalog_model_args(d, st, cat, &a);
-  a.L = L; a.k = 1; a.chunk = r.chunk; a.nchunk = r.nchunk;
-  a.zline = ws + r.zline; a.excl_off = ln->excl_off; a.excl_idx = ln->excl_idx;
-  a.tgt_off = tg->tgt_off; a.tgt_idx = tg->tgt_idx; a.max_targets = tg->max_targets;
-  a.rpart = reinterpret_cast<int32_t*>(ws + r.rpart);
-  a.ahead = ahead; a.tgt_logit = tgt_logit; a.state = state; a.n_scored = n_scored;
-  if (!cands) return score_catalog_count(a, s);
-  a.cand_off = cands->cand_off; a.cand_idx = cands->cand_idx; a.max_count = cands->max_count;
-  return score_catalog_count_in(a, s);
-}
-}  // namespace
-
+// ---- ... the exact rank of given items (catalog_ranks)
 extern "C" int score_catalog_ranks_plan(const score_config_t* cfg, int32_t L, int32_t span, int32_t* chunk, int32_t* nchunk,
                                         int64_t* workspace_bytes) {
-  if (!cfg || !chunk || !nchunk || !workspace_bytes) return SCORE_E_BADARG;
-  Dims d;
-  SCORE_TRY(catalog_dims(cfg, L, span, 1, &d));
-  CatalogRanksWS r;
-  build_catalog_ranks_ws(d, L, span, &r);
-  *chunk = r.chunk; *nchunk = r.nchunk; *workspace_bytes = r.total * 4;
-  return 0;
+  return catalog_plan(cfg, L, span, 1, true, chunk, nchunk, workspace_bytes);
 }
 
 extern "C" int score_catalog_ranks(const score_config_t* cfg, const score_state_t* st, const score_catalog_t* cat,
@@ -2335,10 +2311,7 @@ extern "C" int score_catalog_ranks_struct_sizes(int64_t* out, int32_t n) {
   const int64_t v[] = {(int64_t)sizeof(score_catalog_targets_t), (int64_t)offsetof(score_catalog_targets_t, tgt_off),
                        (int64_t)offsetof(score_catalog_targets_t, tgt_idx), (int64_t)offsetof(score_catalog_targets_t, max_targets),
                        (int64_t)SCORE_CATALOG_TMAX};
-  const int32_t have = (int32_t)(sizeof(v) / sizeof(v[0]));
-  if (!out || n < have) return SCORE_E_BADARG;
-  for (int32_t i = 0; i < have; ++i) out[i] = v[i];
-  return have;
+  return copy_sizes(v, out, n);
 }
 
 // sizes and late-field offsets of the catalogue call's structures, as score_abi_struct_sizes gives them for the others: -> the
@@ -2347,10 +2320,7 @@ extern "C" int score_catalog_struct_sizes(int64_t* out, int32_t n) {
   const int64_t v[] = {(int64_t)sizeof(score_catalog_t), (int64_t)sizeof(score_catalog_lines_t),
                        (int64_t)offsetof(score_catalog_t, zcat), (int64_t)offsetof(score_catalog_lines_t, excl_off),
                        (int64_t)offsetof(score_catalog_lines_t, excl_idx), (int64_t)SCORE_CATALOG_KMAX};
-  const int32_t have = (int32_t)(sizeof(v) / sizeof(v[0]));
-  if (!out || n < have) return SCORE_E_BADARG;
-  for (int32_t i = 0; i < have; ++i) out[i] = v[i];
-  return have;
+  return copy_sizes(v, out, n);
 }
 
 // ---------------------------------------------------------------- the layer-by-layer backward pass

@@ -349,7 +349,7 @@ int score_rank_line(const RankArgs& a, hipStream_t s);       // the line kernel 
 // catalog.hip: top-K over a whole item catalogue (score_catalog_build / score_catalog_topk).  fc1's pre-activation of the pair
 // (line l, catalogue item n) is zline[l] + zcat[n]; zcat [N, 200] = bn1(item_n) . W1[item rows] is a per-catalogue constant.
 // score_catalog_zcat fills it (a workgroup per 16 items; ids >= n_rows read as row 0, bit 5 of *id_status).
-// score_catalog_select: a workgroup per (line, chunk of the catalogue) holds fc2 / fc3 resident, walks its chunk and keeps its k
+// score_catalog_sweep, selecting: a workgroup per (line, chunk of the catalogue) holds fc2 / fc3 resident, walks its chunk and keeps its k
 // best pairs -- ordered by (logit descending, index ascending; NaN behind every number) as 64-bit keys, see catalog.hip -- in
 // part [L, nchunk, k]; then a workgroup per line merges the nchunk lists into top_idx / top_logit [L, k] (-1 / -inf padding).
 // excl_off / excl_idx (optional): per line, ascending catalogue indices that are never selected.  all_logits (optional) [L, N].
@@ -365,10 +365,10 @@ struct CatalogArgs {
   unsigned long long* part;
   int32_t* top_idx; float* top_logit; float* all_logits;
   uint32_t n_rows; int32_t* id_status;
-  // score_catalog_select_in (the candidate form): per line the catalogue indices cand_idx[cand_off[l] .. cand_off[l + 1]),
+  // the candidate form (score_catalog_sweep, cand): per line the catalogue indices cand_idx[cand_off[l] .. cand_off[l + 1]),
   // strictly ascending; chunk / nchunk cut max_count list POSITIONS, all_logits is aligned with cand_idx
   const int64_t* cand_off; const int32_t* cand_idx; int max_count;
-  // score_catalog_count / score_catalog_count_in (the counting form, score_catalog_ranks*): per line the targets
+  // the counting form (score_catalog_sweep, ranks; score_catalog_ranks*): per line the targets
   // tgt_idx[tgt_off[l] .. tgt_off[l + 1]), the first max_targets of them counted; rpart [L, nchunk, SCORE_CATALOG_RPART] the
   // chunks' integer partials; ahead / tgt_logit / state aligned with tgt_idx, n_scored [L].  (Behind every field the top-K
   // kernels read, so that their argument offsets stay where they were.)
@@ -380,10 +380,9 @@ struct CatalogArgs {
 constexpr int SCORE_CATALOG_RPART = 68;
 void score_catalog_chunks(int L, int N, int k, int* chunk, int* nchunk);
 int score_catalog_zcat(const CatalogArgs& a, hipStream_t s);
-int score_catalog_select(const CatalogArgs& a, hipStream_t s);
-int score_catalog_select_in(const CatalogArgs& a, hipStream_t s);
-int score_catalog_count(const CatalogArgs& a, hipStream_t s);        // the whole catalogue: plan of a.N
-int score_catalog_count_in(const CatalogArgs& a, hipStream_t s);     // the lines' candidate lists: plan of a.max_count
+// the sweep and its second launch.  cand: the lines' candidate lists (plan of a.max_count), else the whole catalogue (plan of a.N);
+// ranks: the counting form, else the selecting one
+int score_catalog_sweep(const CatalogArgs& a, bool cand, bool ranks, hipStream_t s);
 // delf.hip: the DELF point baseline (point_model.py:200-249) between the gather and the scatter.  Per side (0: user_seq rows
 // against target_item through dense; 1: item_seq rows against target_user through dense_1) X [B * T, C] with row stride ldx,
 // the saved keys [B * T, C] (live rows only), attention weights att [B, T], rep [B, C]; backward: ds [B, T] (gradient at the

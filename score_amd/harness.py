@@ -366,6 +366,78 @@ def catalog_quality_device(top_idx, target_idx):
     return tuple(float(x) for x in out.cpu().tolist())
 
 
+# ---- the four evaluate_catalog* functions: two line sources (_loader_lines, _store_lines) times two measures (the k best through
+# recommend*_async and catalog_quality_device; the exact rank through item_ranks*_async and rank_quality_device)
+def _check_candidates(name, candidates):
+    if candidates is not None and candidates != "line":
+        raise ValueError("%s: candidates must be None or \"line\", got %r" % (name, candidates))
+
+
+def _loader_lines(name, model, batches, catalog, neg_sample_num, exclude_history, candidates):
+    """The target lines of a loader's eval batches (lines of 1 + neg_sample_num samples, the first candidate the positive), per
+    batch: (lines, active_slices, L, the positives' item ids, their catalogue indices, exclude: with exclude_history the users'
+    histories without the positive, own: with candidates="line" each line's own items).  ValueError, per batch, for a positive
+    the catalogue does not hold."""
+    import torch
+    n_cand = 1 + neg_sample_num
+    for batch_data in batches:
+        db = model.device_batch(batch_data)
+        lines = model.lines_of(db, neg_sample_num)
+        L = int(lines[1].numel())
+        pos_ids = db.tensors[5].view(L, n_cand, -1)[:, 0, 0].contiguous()
+        tgt, found = catalog.indices_of(pos_ids)
+        if not bool(found.all().item()):
+            raise ValueError("%s: a line's positive item is not in the catalogue" % name)
+        exclude = None
+        if exclude_history is not None:
+            exclude = _history_exclusions(exclude_history, lines[2][:, 0], pos_ids)
+        own = None
+        if candidates == "line":
+            own = (torch.arange(L + 1, device=pos_ids.device, dtype=torch.int64) * n_cand,
+                   db.tensors[5].view(L, n_cand, -1)[:, :, 0].reshape(-1))
+        yield lines, db.active_slices, L, pos_ids, tgt, exclude, own
+
+
+def _store_lines(name, model, store, catalog, candidates, lines_per_call):
+    """A PointLogStore's own target lines, straight from the store's tensors (no expanded batch, no strided copies, nothing read
+    back), lines_per_call at a time: (the lines' users, L, the positives' item ids -- the first of each line's line_items --,
+    their catalogue indices, which of them the catalogue holds, own: with candidates="line" each line's own items,
+    max_candidates for them)"""
+    import torch
+    if getattr(model, "rank_unsupported", None) is not None:
+        raise NotImplementedError("%s has no catalogue pass: %s" % (type(model).__name__, model.rank_unsupported))
+    if store._dev is None:
+        raise ValueError("%s: the store must be on a device (build='device' or .to_device())" % name)
+    n_lines, per_line, step = int(store.n_lines), int(store.per_line), int(lines_per_call)
+    if n_lines <= 0 or step <= 0:
+        raise ValueError("%s: no target lines, or lines_per_call <= 0" % name)
+    users = store._dev["line_user"][:n_lines]
+    items = store._dev["line_items"][:n_lines * per_line].view(n_lines, per_line)
+    for a in range(0, n_lines, step):
+        b = min(n_lines, a + step)
+        L = b - a
+        pos_ids = items[a:b, 0].contiguous()
+        tgt, found = catalog.indices_of(pos_ids)
+        own, longest = None, None
+        if candidates == "line":
+            own = (torch.arange(L + 1, device=pos_ids.device, dtype=torch.int64) * per_line, items[a:b].reshape(-1))
+            longest = per_line
+        yield users[a:b], L, pos_ids, tgt, found, own, longest
+
+
+def _catalog_measure(name, model, founds, measure, *lists):
+    """The end of the four: each list of per-call tensors concatenated, measure(*them), check_ids -> (the numbers, the tensors).
+    founds (the store forms): one flag a call, read back here, once; ValueError unless all are set"""
+    import torch
+    if founds is not None and not bool(torch.stack(founds).all().item()):
+        raise ValueError("%s: a line's positive item is not in the catalogue" % name)
+    whole = [torch.cat(x) for x in lists]
+    numbers = measure(*whole)
+    if hasattr(model, "check_ids"):
+        model.check_ids()
+    return numbers, whole
+
+
 def evaluate_catalog(model, batches, catalog, neg_sample_num=TEST_NEG_SAMPLE_NUM, k=10, exclude_history=None, return_lists=False,
                      candidates=None):
     """Ranking metrics against the WHOLE catalogue instead of the sampled negatives: for every target line of a loader's eval
@@ -379,31 +451,13 @@ def evaluate_catalog(model, batches, catalog, neg_sample_num=TEST_NEG_SAMPLE_NUM
     catalogue route (repeated negatives collapse; negatives the catalogue does not hold drop out; the positive is always in the
     list).  None: the whole catalogue.  Anything else raises ValueError."""
     import torch
-    if candidates is not None and candidates != "line":
-        raise ValueError("evaluate_catalog: candidates must be None or \"line\", got %r" % (candidates,))
+    _check_candidates("evaluate_catalog", candidates)
     tops, tgts = [], []
-    for batch_data in batches:
-        db = model.device_batch(batch_data)
-        lines = model.lines_of(db, neg_sample_num)
-        L = int(lines[1].numel())
-        pos_ids = db.tensors[5].view(L, 1 + neg_sample_num, -1)[:, 0, 0].contiguous()
-        tgt, found = catalog.indices_of(pos_ids)
-        if not bool(found.all().item()):
-            raise ValueError("evaluate_catalog: a line's positive item is not in the catalogue")
-        exclude = None
-        if exclude_history is not None:
-            exclude = _history_exclusions(exclude_history, lines[2][:, 0], pos_ids)
-        own = None
-        if candidates == "line":
-            n_cand = 1 + neg_sample_num
-            own = (torch.arange(L + 1, device=pos_ids.device, dtype=torch.int64) * n_cand,
-                   db.tensors[5].view(L, n_cand, -1)[:, :, 0].reshape(-1))
-        top = model.recommend_async(lines, catalog, k=k, exclude=exclude, active_slices=db.active_slices, candidates=own)[0]
+    for lines, active, L, pos_ids, tgt, exclude, own in _loader_lines("evaluate_catalog", model, batches, catalog, neg_sample_num,
+                                                                      exclude_history, candidates):
+        top = model.recommend_async(lines, catalog, k=k, exclude=exclude, active_slices=active, candidates=own)[0]
         tops.append(top.clone()); tgts.append(tgt.to(torch.int32))
-    top, tgt = torch.cat(tops), torch.cat(tgts)
-    six = catalog_quality_device(top, tgt)
-    if hasattr(model, "check_ids"):
-        model.check_ids()
+    six, (top, tgt) = _catalog_measure("evaluate_catalog", model, None, catalog_quality_device, tops, tgts)
     return (six, top, tgt) if return_lists else six
 
 
@@ -416,36 +470,14 @@ def evaluate_catalog_users(model, store, catalog, k=10, exclude_history=True, ca
     1 + neg_sample_num items.  Returns what evaluate_catalog(loader batches of the same store, catalog, exclude_history=store or
     None, ...) returns: the six numbers, with return_lists also (top_idx [n_lines, k], target_idx [n_lines])."""
     import torch
-    if candidates is not None and candidates != "line":
-        raise ValueError("evaluate_catalog_users: candidates must be None or \"line\", got %r" % (candidates,))
-    if getattr(model, "rank_unsupported", None) is not None:
-        raise NotImplementedError("%s has no catalogue pass: %s" % (type(model).__name__, model.rank_unsupported))
-    if store._dev is None:
-        raise ValueError("evaluate_catalog_users: the store must be on a device (build='device' or .to_device())")
-    n_lines, per_line, step = int(store.n_lines), int(store.per_line), int(lines_per_call)
-    if n_lines <= 0 or step <= 0:
-        raise ValueError("evaluate_catalog_users: no target lines, or lines_per_call <= 0")
-    users = store._dev["line_user"][:n_lines]
-    items = store._dev["line_items"][:n_lines * per_line].view(n_lines, per_line)
+    _check_candidates("evaluate_catalog_users", candidates)
     tops, tgts, founds = [], [], []
-    for a in range(0, n_lines, step):
-        b = min(n_lines, a + step)
-        L = b - a
-        pos_ids = items[a:b, 0].contiguous()
-        tgt, found = catalog.indices_of(pos_ids)
-        own, longest = None, None
-        if candidates == "line":
-            own = (torch.arange(L + 1, device=pos_ids.device, dtype=torch.int64) * per_line, items[a:b].reshape(-1))
-            longest = per_line
-        top = model.recommend_users_async(users[a:b], store, catalog, k=k, exclude_history=bool(exclude_history), keep=pos_ids,
+    for users, L, pos_ids, tgt, found, own, longest in _store_lines("evaluate_catalog_users", model, store, catalog, candidates,
+                                                                    lines_per_call):
+        top = model.recommend_users_async(users, store, catalog, k=k, exclude_history=bool(exclude_history), keep=pos_ids,
                                           candidates=own, max_candidates=longest)[0]
         tops.append(top.clone()); tgts.append(tgt.to(torch.int32)); founds.append(found.all())
-    if not bool(torch.stack(founds).all().item()):
-        raise ValueError("evaluate_catalog_users: a line's positive item is not in the catalogue")
-    top, tgt = torch.cat(tops), torch.cat(tgts)
-    six = catalog_quality_device(top, tgt)
-    if hasattr(model, "check_ids"):
-        model.check_ids()
+    six, (top, tgt) = _catalog_measure("evaluate_catalog_users", model, founds, catalog_quality_device, tops, tgts)
     return (six, top, tgt) if return_lists else six
 
 
@@ -483,32 +515,14 @@ def evaluate_catalog_ranks(model, batches, catalog, neg_sample_num=TEST_NEG_SAMP
     numbers.  The first five equal evaluate_catalog's at any k >= 10; MRR is not truncated.  exclude_history, candidates: as
     evaluate_catalog takes them (the positive itself is never excluded)."""
     import torch
-    if candidates is not None and candidates != "line":
-        raise ValueError("evaluate_catalog_ranks: candidates must be None or \"line\", got %r" % (candidates,))
+    _check_candidates("evaluate_catalog_ranks", candidates)
     aheads, states = [], []
-    for batch_data in batches:
-        db = model.device_batch(batch_data)
-        lines = model.lines_of(db, neg_sample_num)
-        L = int(lines[1].numel())
-        pos_ids = db.tensors[5].view(L, 1 + neg_sample_num, -1)[:, 0, 0].contiguous()
-        tgt, found = catalog.indices_of(pos_ids)
-        if not bool(found.all().item()):
-            raise ValueError("evaluate_catalog_ranks: a line's positive item is not in the catalogue")
-        exclude = None
-        if exclude_history is not None:
-            exclude = _history_exclusions(exclude_history, lines[2][:, 0], pos_ids)
-        own = None
-        if candidates == "line":
-            n_cand = 1 + neg_sample_num
-            own = (torch.arange(L + 1, device=pos_ids.device, dtype=torch.int64) * n_cand,
-                   db.tensors[5].view(L, n_cand, -1)[:, :, 0].reshape(-1))
+    for lines, active, L, pos_ids, tgt, exclude, own in _loader_lines("evaluate_catalog_ranks", model, batches, catalog,
+                                                                      neg_sample_num, exclude_history, candidates):
         targets = (torch.arange(L + 1, device=pos_ids.device, dtype=torch.int64), tgt.to(torch.int32).contiguous(), 1)
-        out = model.item_ranks_async(lines, catalog, targets, exclude=exclude, active_slices=db.active_slices, candidates=own)
+        out = model.item_ranks_async(lines, catalog, targets, exclude=exclude, active_slices=active, candidates=own)
         aheads.append(out[0].clone()); states.append(out[2].clone())
-    seven = rank_quality_device(torch.cat(aheads), torch.cat(states))
-    if hasattr(model, "check_ids"):
-        model.check_ids()
-    return seven
+    return _catalog_measure("evaluate_catalog_ranks", model, None, rank_quality_device, aheads, states)[0]
 
 
 def evaluate_catalog_ranks_users(model, store, catalog, exclude_history=True, candidates=None, lines_per_call=100):
@@ -517,38 +531,16 @@ def evaluate_catalog_ranks_users(model, store, catalog, exclude_history=True, ca
     The user's whole history is excluded (exclude_history); a positive inside it is ranked against the rest (state 2), which is
     the rank it has in evaluate_catalog_users' lists, where it alone is kept.  -> rank_quality_device's seven numbers."""
     import torch
-    if candidates is not None and candidates != "line":
-        raise ValueError("evaluate_catalog_ranks_users: candidates must be None or \"line\", got %r" % (candidates,))
-    if getattr(model, "rank_unsupported", None) is not None:
-        raise NotImplementedError("%s has no catalogue pass: %s" % (type(model).__name__, model.rank_unsupported))
-    if store._dev is None:
-        raise ValueError("evaluate_catalog_ranks_users: the store must be on a device (build='device' or .to_device())")
-    n_lines, per_line, step = int(store.n_lines), int(store.per_line), int(lines_per_call)
-    if n_lines <= 0 or step <= 0:
-        raise ValueError("evaluate_catalog_ranks_users: no target lines, or lines_per_call <= 0")
-    users = store._dev["line_user"][:n_lines]
-    items = store._dev["line_items"][:n_lines * per_line].view(n_lines, per_line)
+    _check_candidates("evaluate_catalog_ranks_users", candidates)
     aheads, states, founds = [], [], []
-    for a in range(0, n_lines, step):
-        b = min(n_lines, a + step)
-        L = b - a
-        pos_ids = items[a:b, 0].contiguous()
-        tgt, found = catalog.indices_of(pos_ids)
-        own, longest = None, None
-        if candidates == "line":
-            own = (torch.arange(L + 1, device=pos_ids.device, dtype=torch.int64) * per_line, items[a:b].reshape(-1))
-            longest = per_line
+    for users, L, pos_ids, tgt, found, own, longest in _store_lines("evaluate_catalog_ranks_users", model, store, catalog,
+                                                                    candidates, lines_per_call):
         targets = (torch.arange(L + 1, device=pos_ids.device, dtype=torch.int64),
-                   torch.where(found, tgt, torch.full_like(tgt, -1)).to(torch.int32).contiguous(), 1)
-        out = model.item_ranks_users_async(users[a:b], store, catalog, targets, exclude_history=bool(exclude_history),
+                   torch.where(found, tgt, torch.full_like(tgt, -1)).to(torch.int32).contiguous(), 1)      # (-1: not held)
+        out = model.item_ranks_users_async(users, store, catalog, targets, exclude_history=bool(exclude_history),
                                            candidates=own, max_candidates=longest)
         aheads.append(out[0].clone()); states.append(out[2].clone()); founds.append(found.all())
-    if not bool(torch.stack(founds).all().item()):
-        raise ValueError("evaluate_catalog_ranks_users: a line's positive item is not in the catalogue")
-    seven = rank_quality_device(torch.cat(aheads), torch.cat(states))
-    if hasattr(model, "check_ids"):
-        model.check_ids()
-    return seven
+    return _catalog_measure("evaluate_catalog_ranks_users", model, founds, rank_quality_device, aheads, states)[0]
 
 
 def _history_exclusions(store, user_ids, keep_ids):

@@ -234,6 +234,17 @@ def active_slices(model, max_len, min_len=None):
 _active_slices_of = active_slices        # (for the methods that take an `active_slices` argument of their own)
 
 
+def _is_mapped(lists, L, what):
+    """whether `lists` is what ItemCatalog.candidates / .targets returned, (off [L + 1], idx int32 tensor, the longest line's
+    count as a number), not item ids still to be mapped; ValueError when it is and its offsets are not those of L lines"""
+    if not (isinstance(lists, tuple) and len(lists) == 3 and torch.is_tensor(lists[1]) and lists[1].dtype == torch.int32 and
+            not torch.is_tensor(lists[2])):
+        return False
+    if int(lists[0].numel()) != L + 1:
+        raise ValueError("%s: offsets for %d lines, expected %d" % (what, int(lists[0].numel()) - 1, L))
+    return True
+
+
 def rank_lines(B, neg_sample_num):
     """(L, C) of a batch of B samples made of target lines of C = 1 + neg_sample_num candidates each"""
     n_cand = 1 + int(neg_sample_num)
@@ -1709,19 +1720,25 @@ class SCOREBASE(object):
     rank_unsupported = ("its recurrences and attention read per-sample neighbour sets of the target user AND the target item, so "
                         "nothing of a sample is shared along a target line")
 
-    def _rank_buffers(self, L, n_cand):
-        """(workspace, y_pred [L * n_cand], loss [4]) of the line-form pass, one set per (L, n_cand); the last few are kept"""
-        key = (L, n_cand)
+    def _line_workspace(self, key, bytes_fn, extra=()):
+        """The workspace cache of every line-form pass (rank_async and the catalogue calls): (workspace,) + one float32 tensor per
+        shape of `extra`, one set per key; bytes_fn() plans a missing one.  The last max_workspaces are kept: before one goes,
+        the device is synchronized (as _workspace: kernels on other streams may still use it).  A key names the form and every
+        size its plan depends on, so two forms share a set only where their plans are the same."""
         ent = self._rank_ws.pop(key, None)
         if ent is None:
-            nbytes = _lib.rank_workspace_bytes(self.cfg, L, n_cand)
-            while len(self._rank_ws) >= self.max_workspaces:       # (as _workspace: kernels on other streams may still use it)
+            nbytes = bytes_fn()
+            while len(self._rank_ws) >= self.max_workspaces:
                 torch.cuda.synchronize(self.device)
                 self._rank_ws.pop(next(iter(self._rank_ws)))
             f32 = dict(dtype=torch.float32, device=self.device)
-            ent = (torch.empty(((nbytes + 3) // 4,), **f32), torch.empty((L * n_cand,), **f32), torch.empty((4,), **f32))
+            ent = (torch.empty(((nbytes + 3) // 4,), **f32),) + tuple(torch.empty(shape, **f32) for shape in extra)
         self._rank_ws[key] = ent
         return ent
+
+    def _rank_buffers(self, L, n_cand):
+        """(workspace, y_pred [L * n_cand], loss [4]) of the line-form pass, one set per (L, n_cand)"""
+        return self._line_workspace((L, n_cand), lambda: _lib.rank_workspace_bytes(self.cfg, L, n_cand), ((L * n_cand,), (4,)))
 
     def rank_async(self, batch_data, reg_lambda, neg_sample_num=TEST_NEG_SAMPLE_NUM, verify=False):
         """eval_async for batches made of target LINES: every run of C = 1 + neg_sample_num samples shares its user_seq,
@@ -1783,18 +1800,108 @@ class SCOREBASE(object):
         first = lambda x: x.view(L, n_cand, -1)[:, 0].contiguous()
         return first(t[0]).view(L, T, Fi), first(t[7]).view(L), first(t[4]).view(L, Fu)
 
-    def _catalog_buffers(self, L, N, k):
-        """the workspace of score_catalog_topk, one per (L, N, k); the last few are kept (as _rank_buffers)"""
-        key = ("catalog", L, N, k)
-        ent = self._rank_ws.pop(key, None)
-        if ent is None:
-            nbytes = _lib.catalog_plan(self.cfg, L, N, k)[2]
-            while len(self._rank_ws) >= self.max_workspaces:
-                torch.cuda.synchronize(self.device)
-                self._rank_ws.pop(next(iter(self._rank_ws)))
-            ent = torch.empty(((nbytes + 3) // 4,), dtype=torch.float32, device=self.device)
-        self._rank_ws[key] = ent
-        return ent
+    # ---- the call layer under recommend* and item_ranks*: one prologue, one candidates resolver, one by-user prologue, one
+    # read-back.  A new catalogue call is these plus its own outputs and library call.
+    def _catalog_call(self, lines, catalog, exclude, exclude_idx, active_slices, k=None, targets=None):
+        """What every catalogue call does first, refusals in their one order: the model type, exclude with exclude_idx, the
+        catalogue, k (where the call has one), the lines -- coerced to int32 device tensors, shapes checked --, the targets (where
+        the call has them: mapped, or checked as ItemCatalog.targets returned them), active_slices (one read-back at None), the
+        exclusions.  -> (the tensors score_catalog_lines_t points to: the caller holds them until the call is queued, L, the
+        CatalogLines struct, k, (tgt_off, tgt_idx, longest) or None)"""
+        if self.rank_unsupported is not None:
+            raise NotImplementedError("%s has no catalogue pass: %s" % (type(self).__name__, self.rank_unsupported))
+        if exclude is not None and exclude_idx is not None:
+            raise ValueError("exclude (item ids) and exclude_idx (catalogue indices) are mutually exclusive")
+        if not isinstance(catalog, ItemCatalog) or catalog.model is not self:
+            raise ValueError("catalog must be an ItemCatalog built for this model")
+        if k is not None:
+            k = int(k)
+            if not 1 <= k <= _lib.CATALOG_KMAX:
+                raise ValueError("k = %d outside [1, %d]" % (k, _lib.CATALOG_KMAX))
+        if len(lines) != 3:
+            raise ValueError("lines must be (user_seq, user_seq_length, target_user)")
+        c = self.cfg
+        T, Fi, Fu = int(c.max_time_len), int(c.item_fnum), int(c.user_fnum)
+        i32 = lambda x: (x if torch.is_tensor(x) else torch.from_numpy(np.ascontiguousarray(np.asarray(x)))).to(
+            device=self.device, dtype=torch.int32).contiguous()
+        useq, length, tuser = (i32(x) for x in lines)
+        L = int(length.numel())
+        if L == 0:
+            raise ValueError("no lines")
+        for name, x, shape in (("user_seq", useq, (L, T, Fi)), ("user_seq_length", length, (L,)), ("target_user", tuser, (L, Fu))):
+            if tuple(x.shape) != shape:
+                raise ValueError("lines: %s has shape %s, expected %s" % (name, tuple(x.shape), shape))
+        if targets is not None:
+            if _is_mapped(targets, L, "targets"):
+                if not 0 <= int(targets[2]) <= _lib.CATALOG_TMAX:
+                    raise ValueError("targets: %d on a line, at most %d" % (int(targets[2]), _lib.CATALOG_TMAX))
+            else:
+                targets = catalog.targets(targets, L)
+        if active_slices is None:
+            active_slices = _active_slices_of(self, int(length.max().item()))
+        excl_off = excl_idx = None
+        if exclude is not None:
+            excl_off, excl_idx = catalog.exclusions(exclude, L)
+        elif exclude_idx is not None:
+            excl_off, excl_idx = exclude_idx
+            if not (torch.is_tensor(excl_off) and torch.is_tensor(excl_idx) and excl_off.dtype == torch.int64 and
+                    excl_idx.dtype == torch.int32 and excl_off.device == self.device and excl_idx.device == self.device and
+                    excl_off.is_contiguous() and excl_idx.is_contiguous() and int(excl_off.numel()) == L + 1 and
+                    int(excl_idx.numel()) >= 1):
+                raise ValueError("exclude_idx must be (int64 [%d], int32 [>= 1]) contiguous tensors on %s" % (L + 1, self.device))
+        ln = _lib.CatalogLines(_ptr(useq), _ptr(length), _ptr(tuser), L, int(active_slices),
+                               _ptr(excl_off) if excl_off is not None else None, _ptr(excl_idx) if excl_idx is not None else None)
+        return (useq, length, tuser, excl_off, excl_idx), L, ln, k, targets
+
+    @staticmethod
+    def _catalog_candidates(catalog, candidates, max_candidates, L):
+        """candidates in any of the three forms a catalogue call takes -> (cand_off, cand_idx, span, the size the launch is
+        planned for: max_candidates where given -- then nothing is read back --, else the longest line's count; the
+        score_catalog_cands_t argument of the *_in entry point as a 1-tuple).  None, the whole catalogue: (None, None, N, ())"""
+        if candidates is None:
+            return None, None, catalog.N, ()
+        if _is_mapped(candidates, L, "candidates"):
+            cand_off, cand_idx, longest = candidates
+        elif max_candidates is not None:
+            cand_off, cand_idx = catalog._line_indices(candidates, L, "candidates")
+            longest = None
+        else:
+            cand_off, cand_idx, longest = catalog.candidates(candidates, L)
+        max_count = int(max_candidates) if max_candidates is not None else int(longest)
+        if max_count < 1:
+            raise ValueError("max_candidates = %d, expected >= 1" % max_count)
+        return cand_off, cand_idx, max_count, (C.byref(_lib.CatalogCands(_ptr(cand_off), _ptr(cand_idx), max_count)),)
+
+    def _catalog_user_lines(self, user_ids, store, catalog):
+        """What the by-user calls do first: the model type, the catalogue and the store checked, then -> (user ids int32 [L] on
+        the device, store.user_lines' (user_seq, length, target_user), known [L], active_slices: the bound min(T,
+        store.max_user_len), so nothing is read back)"""
+        if self.rank_unsupported is not None:
+            raise NotImplementedError("%s has no catalogue pass: %s" % (type(self).__name__, self.rank_unsupported))
+        if not isinstance(catalog, ItemCatalog) or catalog.model is not self:
+            raise ValueError("catalog must be an ItemCatalog built for this model")
+        c = self.cfg
+        T, Fi, Fu = int(c.max_time_len), int(c.item_fnum), int(c.user_fnum)
+        if (int(store.Fu), int(store.Fi)) != (Fu, Fi):
+            raise ValueError("the store has (user_fnum, item_fnum) = %r, the model %r" % ((store.Fu, store.Fi), (Fu, Fi)))
+        if store._dev is None or store.device != self.device:
+            raise ValueError("the store must be on the model's device %s (build='device' or .to_device())" % (self.device,))
+        catalog.check_store(store)
+        uid = (user_ids if torch.is_tensor(user_ids) else torch.from_numpy(np.ascontiguousarray(np.asarray(user_ids)))).to(
+            device=self.device, dtype=torch.int32).contiguous().view(-1)
+        useq, length, tuser, known = store.user_lines(uid, T)
+        return uid, (useq, length, tuser), known, _active_slices_of(self, min(T, store.max_user_len))
+
+    def _recommend_lists(self, catalog, idx, logit, check=None):
+        """(idx, logit) of a recommend call read back: per line the item ids and sigmoid(logit) as lists, the -1 padding dropped;
+        check(), where given, runs behind the copies and in front of check_ids"""
+        ids = catalog.ids[idx.clamp(min=0).long()]
+        idx, ids, y = idx.cpu().numpy(), ids.cpu().numpy(), torch.sigmoid(logit).cpu().numpy()
+        if check is not None:
+            check()
+        self.check_ids()
+        keep = idx >= 0
+        return [ids[l][keep[l]].tolist() for l in range(idx.shape[0])], [y[l][keep[l]].tolist() for l in range(idx.shape[0])]
 
     def recommend_async(self, lines, catalog, k=10, exclude=None, exclude_idx=None, all_logits=False, active_slices=None,
                         candidates=None, max_candidates=None):
@@ -1819,103 +1926,33 @@ class SCOREBASE(object):
         exclude_idx: the exclusions as the library takes them, (excl_off int64 [L + 1], excl_idx int32) device tensors of
         catalogue INDICES, strictly ascending within a line (ItemCatalog.history_exclusions returns such a pair); nothing is
         mapped or read back.  Not together with exclude (ValueError)."""
-        if self.rank_unsupported is not None:
-            raise NotImplementedError("%s has no catalogue pass: %s" % (type(self).__name__, self.rank_unsupported))
-        if exclude is not None and exclude_idx is not None:
-            raise ValueError("exclude (item ids) and exclude_idx (catalogue indices) are mutually exclusive")
-        if not isinstance(catalog, ItemCatalog) or catalog.model is not self:
-            raise ValueError("catalog must be an ItemCatalog built for this model")
-        k = int(k)
-        if not 1 <= k <= _lib.CATALOG_KMAX:
-            raise ValueError("k = %d outside [1, %d]" % (k, _lib.CATALOG_KMAX))
-        if len(lines) != 3:
-            raise ValueError("lines must be (user_seq, user_seq_length, target_user)")
-        c = self.cfg
-        T, Fi, Fu = int(c.max_time_len), int(c.item_fnum), int(c.user_fnum)
-        i32 = lambda x: (x if torch.is_tensor(x) else torch.from_numpy(np.ascontiguousarray(np.asarray(x)))).to(
-            device=self.device, dtype=torch.int32).contiguous()
-        useq, length, tuser = (i32(x) for x in lines)
-        L = int(length.numel())
-        if L == 0:
-            raise ValueError("no lines")
-        for name, x, shape in (("user_seq", useq, (L, T, Fi)), ("user_seq_length", length, (L,)), ("target_user", tuser, (L, Fu))):
-            if tuple(x.shape) != shape:
-                raise ValueError("lines: %s has shape %s, expected %s" % (name, tuple(x.shape), shape))
-        if active_slices is None:
-            active_slices = _active_slices_of(self, int(length.max().item()))
-        N = catalog.N
-        excl_off = excl_idx = None
-        if exclude is not None:
-            excl_off, excl_idx = catalog.exclusions(exclude, L)
-        elif exclude_idx is not None:
-            excl_off, excl_idx = exclude_idx
-            if not (torch.is_tensor(excl_off) and torch.is_tensor(excl_idx) and excl_off.dtype == torch.int64 and
-                    excl_idx.dtype == torch.int32 and excl_off.device == self.device and excl_idx.device == self.device and
-                    excl_off.is_contiguous() and excl_idx.is_contiguous() and int(excl_off.numel()) == L + 1 and
-                    int(excl_idx.numel()) >= 1):
-                raise ValueError("exclude_idx must be (int64 [%d], int32 [>= 1]) contiguous tensors on %s" % (L + 1, self.device))
+        held, L, ln, k, _ = self._catalog_call(lines, catalog, exclude, exclude_idx, active_slices, k=k)      # (held: alive until the call is queued)
         idx = torch.empty((L, k), dtype=torch.int32, device=self.device)
         logit = torch.empty((L, k), dtype=torch.float32, device=self.device)
-        ln = _lib.CatalogLines(_ptr(useq), _ptr(length), _ptr(tuser), L, int(active_slices),
-                               _ptr(excl_off) if excl_off is not None else None, _ptr(excl_idx) if excl_idx is not None else None)
-        if candidates is not None:
-            return self._recommend_in(catalog, ln, L, k, candidates, max_candidates, all_logits, idx, logit)
-        ws = self._catalog_buffers(L, N, k)
-        full = torch.empty((L, N), dtype=torch.float32, device=self.device) if all_logits else None
+        cand_off, cand_idx, span, cd = self._catalog_candidates(catalog, candidates, max_candidates, L)
+        what, plan = ("score_catalog_topk_in", _lib.catalog_cands_plan) if cd else ("score_catalog_topk", _lib.catalog_plan)
+        ws, = self._line_workspace(("catalog", L, span, k), lambda: plan(self.cfg, L, span, k)[2])
+        out = None
+        if all_logits:
+            n_out = (max(1, int(cand_idx.numel())),) if cd else (L, span)
+            out = torch.empty(n_out, dtype=torch.float32, device=self.device)
         with self._Pin(self):
             catalog.refresh()            # (flushes the time-tiled optimizer for the whole table: every item row is read)
             st = self._state(ws)
             cat = catalog.struct()
-            rc = self.lib.score_catalog_topk(C.byref(self.cfg), C.byref(st), C.byref(cat), C.byref(ln), k, _ptr(idx), _ptr(logit),
-                                             _ptr(full) if full is not None else None, self._stream())
-        _lib.check(rc, "score_catalog_topk")
-        return (idx, logit, full) if all_logits else (idx, logit)
-
-    def _recommend_in(self, catalog, ln, L, k, candidates, max_candidates, all_logits, idx, logit):
-        """recommend_async's call with candidate lists (score_catalog_topk_in); ln: the lines, whose tensors the caller holds"""
-        if isinstance(candidates, tuple) and len(candidates) == 3 and torch.is_tensor(candidates[1]) and \
-                candidates[1].dtype == torch.int32 and not torch.is_tensor(candidates[2]):
-            cand_off, cand_idx, longest = candidates                 # (what ItemCatalog.candidates returned)
-            if int(cand_off.numel()) != L + 1:
-                raise ValueError("candidates: offsets for %d lines, expected %d" % (int(cand_off.numel()) - 1, L))
-        elif max_candidates is not None:
-            cand_off, cand_idx = catalog._line_indices(candidates, L, "candidates")
-            longest = None
-        else:
-            cand_off, cand_idx, longest = catalog.candidates(candidates, L)
-        max_count = int(max_candidates) if max_candidates is not None else int(longest)
-        if max_count < 1:
-            raise ValueError("max_candidates = %d, expected >= 1" % max_count)
-        key = ("catalog_in", L, max_count, k)
-        ws = self._rank_ws.pop(key, None)
-        if ws is None:
-            nbytes = _lib.catalog_cands_plan(self.cfg, L, max_count, k)[2]
-            while len(self._rank_ws) >= self.max_workspaces:
-                torch.cuda.synchronize(self.device)
-                self._rank_ws.pop(next(iter(self._rank_ws)))
-            ws = torch.empty(((nbytes + 3) // 4,), dtype=torch.float32, device=self.device)
-        self._rank_ws[key] = ws
-        own = torch.empty((max(1, int(cand_idx.numel())),), dtype=torch.float32, device=self.device) if all_logits else None
-        cd = _lib.CatalogCands(_ptr(cand_off), _ptr(cand_idx), max_count)
-        with self._Pin(self):
-            catalog.refresh()
-            st = self._state(ws)
-            cat = catalog.struct()
-            rc = self.lib.score_catalog_topk_in(C.byref(self.cfg), C.byref(st), C.byref(cat), C.byref(ln), C.byref(cd), k, _ptr(idx),
-                                                _ptr(logit), _ptr(own) if own is not None else None, self._stream())
-        _lib.check(rc, "score_catalog_topk_in")
-        return (idx, logit, (cand_off, cand_idx, own)) if all_logits else (idx, logit)
+            rc = getattr(self.lib, what)(C.byref(self.cfg), C.byref(st), C.byref(cat), C.byref(ln), *cd, k, _ptr(idx),
+                                         _ptr(logit), _ptr(out) if out is not None else None, self._stream())
+        _lib.check(rc, what)
+        if not all_logits:
+            return idx, logit
+        return idx, logit, ((cand_off, cand_idx, out) if cd else out)
 
     def recommend(self, lines, catalog, k=10, exclude=None, active_slices=None, candidates=None):
         """recommend_async, read back: per line the item ids (column 0 of the catalogue's rows) and sigmoid(logit) as lists,
         best first, the -1 padding dropped -> (ids, scores).  candidates: as recommend_async takes them.  Raises as rank does
         when an id outside the table was fed."""
         idx, logit = self.recommend_async(lines, catalog, k=k, exclude=exclude, active_slices=active_slices, candidates=candidates)
-        ids = catalog.ids[idx.clamp(min=0).long()]
-        idx, ids, y = idx.cpu().numpy(), ids.cpu().numpy(), torch.sigmoid(logit).cpu().numpy()
-        self.check_ids()
-        keep = idx >= 0
-        return [ids[l][keep[l]].tolist() for l in range(idx.shape[0])], [y[l][keep[l]].tolist() for l in range(idx.shape[0])]
+        return self._recommend_lists(catalog, idx, logit)
 
     # ------------------------------------------------------------------ ... by user id (score_point_user_lines,
     # score_catalog_history_exclusions)
@@ -1930,24 +1967,10 @@ class SCOREBASE(object):
         recommend_async's third result with all_logits.  A user the store does not know (known 0) is scored as a cold user
         with a zero user row and raises nothing here.  active_slices is a bound, min(T, store.max_user_len): with
         candidates=None, or max_candidates given, the call queues work and returns without a host wait."""
-        if self.rank_unsupported is not None:
-            raise NotImplementedError("%s has no catalogue pass: %s" % (type(self).__name__, self.rank_unsupported))
-        if not isinstance(catalog, ItemCatalog) or catalog.model is not self:
-            raise ValueError("catalog must be an ItemCatalog built for this model")
-        c = self.cfg
-        T, Fi, Fu = int(c.max_time_len), int(c.item_fnum), int(c.user_fnum)
-        if (int(store.Fu), int(store.Fi)) != (Fu, Fi):
-            raise ValueError("the store has (user_fnum, item_fnum) = %r, the model %r" % ((store.Fu, store.Fi), (Fu, Fi)))
-        if store._dev is None or store.device != self.device:
-            raise ValueError("the store must be on the model's device %s (build='device' or .to_device())" % (self.device,))
-        catalog.check_store(store)
-        uid = (user_ids if torch.is_tensor(user_ids) else torch.from_numpy(np.ascontiguousarray(np.asarray(user_ids)))).to(
-            device=self.device, dtype=torch.int32).contiguous().view(-1)
-        useq, length, tuser, known = store.user_lines(uid, T)
+        uid, lines, known, active = self._catalog_user_lines(user_ids, store, catalog)
         excl = catalog.history_exclusions(store, uid, keep) if exclude_history else None
-        out = self.recommend_async((useq, length, tuser), catalog, k=k, exclude_idx=excl, all_logits=all_logits,
-                                   active_slices=_active_slices_of(self, min(T, store.max_user_len)), candidates=candidates,
-                                   max_candidates=max_candidates)
+        out = self.recommend_async(lines, catalog, k=k, exclude_idx=excl, all_logits=all_logits, active_slices=active,
+                                   candidates=candidates, max_candidates=max_candidates)
         return (out[0], out[1], known) + tuple(out[2:])
 
     def recommend_users(self, user_ids, store, catalog, k=10, exclude_history=True, keep=None, candidates=None):
@@ -1956,16 +1979,15 @@ class SCOREBASE(object):
         was fed."""
         idx, logit, known = self.recommend_users_async(user_ids, store, catalog, k=k, exclude_history=exclude_history, keep=keep,
                                                        candidates=candidates)[:3]
-        ids = catalog.ids[idx.clamp(min=0).long()]
-        idx, ids, y, known = idx.cpu().numpy(), ids.cpu().numpy(), torch.sigmoid(logit).cpu().numpy(), known.cpu().numpy()
-        if not known.all():
-            l = int(np.flatnonzero(known == 0)[0])
-            uid = user_ids.reshape(-1)[l].item() if torch.is_tensor(user_ids) else np.asarray(user_ids).reshape(-1)[l]
-            raise ValueError("recommend_users: user id %d (line %d) is not one of the store's users 1 .. %d"
-                             % (int(uid), l, store.n_users))
-        self.check_ids()
-        keep_ = idx >= 0
-        return [ids[l][keep_[l]].tolist() for l in range(idx.shape[0])], [y[l][keep_[l]].tolist() for l in range(idx.shape[0])]
+
+        def all_known():
+            kn = known.cpu().numpy()
+            if not kn.all():
+                l = int(np.flatnonzero(kn == 0)[0])
+                uid = user_ids.reshape(-1)[l].item() if torch.is_tensor(user_ids) else np.asarray(user_ids).reshape(-1)[l]
+                raise ValueError("recommend_users: user id %d (line %d) is not one of the store's users 1 .. %d"
+                                 % (int(uid), l, store.n_users))
+        return self._recommend_lists(catalog, idx, logit, check=all_known)
 
     # ------------------------------------------------------------------ the exact rank of given items (score_catalog_ranks)
     def item_ranks_async(self, lines, catalog, targets, exclude=None, exclude_idx=None, active_slices=None, candidates=None,
@@ -1984,94 +2006,23 @@ class SCOREBASE(object):
         three are aligned with the targets, line l's at tgt_off[l] .. tgt_off[l + 1].  state: 1 scored and counted, 2 scored
         but excluded, 0 in the catalogue but not among the line's candidates, -1 not in the catalogue (ahead -1, logit NaN).
         n_scored: the line's scored, non-excluded items.  logits: the pair's own, bit for bit recommend_async's."""
-        if self.rank_unsupported is not None:
-            raise NotImplementedError("%s has no catalogue pass: %s" % (type(self).__name__, self.rank_unsupported))
-        if exclude is not None and exclude_idx is not None:
-            raise ValueError("exclude (item ids) and exclude_idx (catalogue indices) are mutually exclusive")
-        if not isinstance(catalog, ItemCatalog) or catalog.model is not self:
-            raise ValueError("catalog must be an ItemCatalog built for this model")
-        if len(lines) != 3:
-            raise ValueError("lines must be (user_seq, user_seq_length, target_user)")
-        c = self.cfg
-        T, Fi, Fu = int(c.max_time_len), int(c.item_fnum), int(c.user_fnum)
-        i32 = lambda x: (x if torch.is_tensor(x) else torch.from_numpy(np.ascontiguousarray(np.asarray(x)))).to(
-            device=self.device, dtype=torch.int32).contiguous()
-        useq, length, tuser = (i32(x) for x in lines)
-        L = int(length.numel())
-        if L == 0:
-            raise ValueError("no lines")
-        for name, x, shape in (("user_seq", useq, (L, T, Fi)), ("user_seq_length", length, (L,)), ("target_user", tuser, (L, Fu))):
-            if tuple(x.shape) != shape:
-                raise ValueError("lines: %s has shape %s, expected %s" % (name, tuple(x.shape), shape))
-        if isinstance(targets, tuple) and len(targets) == 3 and torch.is_tensor(targets[1]) and \
-                targets[1].dtype == torch.int32 and not torch.is_tensor(targets[2]):
-            tgt_off, tgt_idx, longest_t = targets                   # (what ItemCatalog.targets returned)
-            if int(tgt_off.numel()) != L + 1:
-                raise ValueError("targets: offsets for %d lines, expected %d" % (int(tgt_off.numel()) - 1, L))
-            if not 0 <= int(longest_t) <= _lib.CATALOG_TMAX:
-                raise ValueError("targets: %d on a line, at most %d" % (int(longest_t), _lib.CATALOG_TMAX))
-        else:
-            tgt_off, tgt_idx, longest_t = catalog.targets(targets, L)
-        if active_slices is None:
-            active_slices = _active_slices_of(self, int(length.max().item()))
-        N = catalog.N
-        excl_off = excl_idx = None
-        if exclude is not None:
-            excl_off, excl_idx = catalog.exclusions(exclude, L)
-        elif exclude_idx is not None:
-            excl_off, excl_idx = exclude_idx
-            if not (torch.is_tensor(excl_off) and torch.is_tensor(excl_idx) and excl_off.dtype == torch.int64 and
-                    excl_idx.dtype == torch.int32 and excl_off.device == self.device and excl_idx.device == self.device and
-                    excl_off.is_contiguous() and excl_idx.is_contiguous() and int(excl_off.numel()) == L + 1 and
-                    int(excl_idx.numel()) >= 1):
-                raise ValueError("exclude_idx must be (int64 [%d], int32 [>= 1]) contiguous tensors on %s" % (L + 1, self.device))
-        cand_off = cand_idx = None
-        span = N
-        if candidates is not None:
-            if isinstance(candidates, tuple) and len(candidates) == 3 and torch.is_tensor(candidates[1]) and \
-                    candidates[1].dtype == torch.int32 and not torch.is_tensor(candidates[2]):
-                cand_off, cand_idx, longest = candidates
-                if int(cand_off.numel()) != L + 1:
-                    raise ValueError("candidates: offsets for %d lines, expected %d" % (int(cand_off.numel()) - 1, L))
-            elif max_candidates is not None:
-                cand_off, cand_idx = catalog._line_indices(candidates, L, "candidates")
-                longest = None
-            else:
-                cand_off, cand_idx, longest = catalog.candidates(candidates, L)
-            span = int(max_candidates) if max_candidates is not None else int(longest)
-            if span < 1:
-                raise ValueError("max_candidates = %d, expected >= 1" % span)
-        key = ("catalog_ranks", L, span)
-        ws = self._rank_ws.pop(key, None)
-        if ws is None:
-            nbytes = _lib.catalog_ranks_plan(self.cfg, L, span)[2]
-            while len(self._rank_ws) >= self.max_workspaces:
-                torch.cuda.synchronize(self.device)
-                self._rank_ws.pop(next(iter(self._rank_ws)))
-            ws = torch.empty(((nbytes + 3) // 4,), dtype=torch.float32, device=self.device)
-        self._rank_ws[key] = ws
+        held, L, ln, _, (tgt_off, tgt_idx, longest_t) = self._catalog_call(lines, catalog, exclude, exclude_idx, active_slices,
+                                                                           targets=targets)
+        cand_off, cand_idx, span, cd = self._catalog_candidates(catalog, candidates, max_candidates, L)
+        what = "score_catalog_ranks_in" if cd else "score_catalog_ranks"
+        ws, = self._line_workspace(("catalog_ranks", L, span), lambda: _lib.catalog_ranks_plan(self.cfg, L, span)[2])
         n_t = int(tgt_idx.numel())                                   # (never 0: ItemCatalog.targets pads an empty set)
         ahead = torch.empty((n_t,), dtype=torch.int32, device=self.device)
         logit = torch.empty((n_t,), dtype=torch.float32, device=self.device)
         state = torch.empty((n_t,), dtype=torch.int32, device=self.device)
         n_scored = torch.empty((L,), dtype=torch.int32, device=self.device)
-        ln = _lib.CatalogLines(_ptr(useq), _ptr(length), _ptr(tuser), L, int(active_slices),
-                               _ptr(excl_off) if excl_off is not None else None, _ptr(excl_idx) if excl_idx is not None else None)
         tg = _lib.CatalogTargets(_ptr(tgt_off), _ptr(tgt_idx), max(1, int(longest_t)))
         with self._Pin(self):
             catalog.refresh()
             st = self._state(ws)
             cat = catalog.struct()
-            if cand_off is None:
-                what = "score_catalog_ranks"
-                rc = self.lib.score_catalog_ranks(C.byref(self.cfg), C.byref(st), C.byref(cat), C.byref(ln), C.byref(tg),
-                                                  _ptr(ahead), _ptr(logit), _ptr(state), _ptr(n_scored), self._stream())
-            else:
-                what = "score_catalog_ranks_in"
-                cd = _lib.CatalogCands(_ptr(cand_off), _ptr(cand_idx), span)
-                rc = self.lib.score_catalog_ranks_in(C.byref(self.cfg), C.byref(st), C.byref(cat), C.byref(ln), C.byref(cd),
-                                                     C.byref(tg), _ptr(ahead), _ptr(logit), _ptr(state), _ptr(n_scored),
-                                                     self._stream())
+            rc = getattr(self.lib, what)(C.byref(self.cfg), C.byref(st), C.byref(cat), C.byref(ln), *cd, C.byref(tg),
+                                         _ptr(ahead), _ptr(logit), _ptr(state), _ptr(n_scored), self._stream())
         _lib.check(rc, what)
         return ahead, logit, state, n_scored, tgt_off
 
@@ -2092,23 +2043,9 @@ class SCOREBASE(object):
         the device -- with `targets` as ItemCatalog.targets returned it, and candidates=None or max_candidates given, no host
         wait.  A target inside the user's history is ranked against the rest and comes back with state 2.
         -> (ahead, logits, state, n_scored, tgt_off, known [L] int32); an unknown user (known 0) is scored as a cold user."""
-        if self.rank_unsupported is not None:
-            raise NotImplementedError("%s has no catalogue pass: %s" % (type(self).__name__, self.rank_unsupported))
-        if not isinstance(catalog, ItemCatalog) or catalog.model is not self:
-            raise ValueError("catalog must be an ItemCatalog built for this model")
-        c = self.cfg
-        T, Fi, Fu = int(c.max_time_len), int(c.item_fnum), int(c.user_fnum)
-        if (int(store.Fu), int(store.Fi)) != (Fu, Fi):
-            raise ValueError("the store has (user_fnum, item_fnum) = %r, the model %r" % ((store.Fu, store.Fi), (Fu, Fi)))
-        if store._dev is None or store.device != self.device:
-            raise ValueError("the store must be on the model's device %s (build='device' or .to_device())" % (self.device,))
-        catalog.check_store(store)
-        uid = (user_ids if torch.is_tensor(user_ids) else torch.from_numpy(np.ascontiguousarray(np.asarray(user_ids)))).to(
-            device=self.device, dtype=torch.int32).contiguous().view(-1)
-        useq, length, tuser, known = store.user_lines(uid, T)
+        uid, lines, known, active = self._catalog_user_lines(user_ids, store, catalog)
         excl = catalog.history_exclusions(store, uid, None) if exclude_history else None
-        out = self.item_ranks_async((useq, length, tuser), catalog, targets, exclude_idx=excl,
-                                    active_slices=_active_slices_of(self, min(T, store.max_user_len)), candidates=candidates,
+        out = self.item_ranks_async(lines, catalog, targets, exclude_idx=excl, active_slices=active, candidates=candidates,
                                     max_candidates=max_candidates)
         return tuple(out) + (known,)
 
@@ -2387,24 +2324,30 @@ class ItemCatalog(object):
         pos = torch.searchsorted(self.ids, ids).clamp(max=self.N - 1)
         return pos, self.ids[pos] == ids
 
+    def _line_lists(self, lists, L, what):
+        """Per-line lists of item ids in either form a catalogue call takes them -- a list of L arrays, or a CSR pair (offsets
+        [L + 1], ids) -- as (off int64 [L + 1] contiguous, ids flat) on the device, nothing mapped yet"""
+        dev = self.ids.device
+        host = lambda x: np.asarray(x.cpu() if torch.is_tensor(x) else x)
+        if len(lists) == 2 and not isinstance(lists, list) and np.ndim(host(lists[0])) == 1 and \
+                host(lists[0]).size == L + 1:
+            off = (lists[0] if torch.is_tensor(lists[0]) else torch.from_numpy(np.ascontiguousarray(host(lists[0])))).to(
+                device=dev, dtype=torch.int64).contiguous()
+            ids = (lists[1] if torch.is_tensor(lists[1]) else torch.from_numpy(np.ascontiguousarray(host(lists[1])))).to(dev)
+            return off, ids.reshape(-1)
+        if len(lists) != L:
+            raise ValueError("%s must hold one array of item ids per line (%d), or be a CSR pair (offsets, ids)" % (what, L))
+        parts = [host(x).reshape(-1).astype(np.int64) for x in lists]
+        off = torch.from_numpy(np.concatenate([[0], np.cumsum([p.size for p in parts])]).astype(np.int64)).to(dev)
+        return off, torch.from_numpy(np.concatenate(parts) if parts else np.zeros((0,), dtype=np.int64)).to(dev)
+
     def _line_indices(self, lists, L, what):
         """Per-line lists of item ids -- a list of L arrays, or a CSR pair (offsets [L + 1], ids) -- as the library takes them:
         (off int64 [L + 1], idx int32) on the device, the ids mapped to catalogue indices (those the catalogue does not hold
         dropped), ascending and without repeats within a line; idx is never empty (one unused 0 when nothing is left).  The
         mapping runs on the device."""
         dev = self.ids.device
-        host = lambda x: np.asarray(x.cpu() if torch.is_tensor(x) else x)
-        if len(lists) == 2 and not isinstance(lists, list) and np.ndim(host(lists[0])) == 1 and \
-                host(lists[0]).size == L + 1:
-            off = (lists[0] if torch.is_tensor(lists[0]) else torch.from_numpy(np.ascontiguousarray(host(lists[0])))).to(
-                device=dev, dtype=torch.int64)
-            ids = (lists[1] if torch.is_tensor(lists[1]) else torch.from_numpy(np.ascontiguousarray(host(lists[1])))).to(dev)
-        else:
-            if len(lists) != L:
-                raise ValueError("%s must hold one array of item ids per line (%d), or be a CSR pair (offsets, ids)" % (what, L))
-            parts = [host(x).reshape(-1).astype(np.int64) for x in lists]
-            off = torch.from_numpy(np.concatenate([[0], np.cumsum([p.size for p in parts])]).astype(np.int64)).to(dev)
-            ids = torch.from_numpy(np.concatenate(parts) if parts else np.zeros((0,), dtype=np.int64)).to(dev)
+        off, ids = self._line_lists(lists, L, what)
         n = int(ids.numel())
         if n == 0:
             return torch.zeros((L + 1,), dtype=torch.int64, device=dev), torch.zeros((1,), dtype=torch.int32, device=dev)
@@ -2430,19 +2373,7 @@ class ItemCatalog(object):
         never empty (one unused -1 when no line has a target).  longest, the longest line's count, costs one read-back;
         ValueError when a line has more than 32 (SCORE_CATALOG_TMAX)."""
         dev = self.ids.device
-        host = lambda x: np.asarray(x.cpu() if torch.is_tensor(x) else x)
-        if len(lists) == 2 and not isinstance(lists, list) and np.ndim(host(lists[0])) == 1 and \
-                host(lists[0]).size == L + 1:
-            off = (lists[0] if torch.is_tensor(lists[0]) else torch.from_numpy(np.ascontiguousarray(host(lists[0])))).to(
-                device=dev, dtype=torch.int64).contiguous()
-            ids = (lists[1] if torch.is_tensor(lists[1]) else torch.from_numpy(np.ascontiguousarray(host(lists[1])))).to(dev)
-            ids = ids.reshape(-1)
-        else:
-            if len(lists) != L:
-                raise ValueError("targets must hold one array of item ids per line (%d), or be a CSR pair (offsets, ids)" % L)
-            parts = [host(x).reshape(-1).astype(np.int64) for x in lists]
-            off = torch.from_numpy(np.concatenate([[0], np.cumsum([p.size for p in parts])]).astype(np.int64)).to(dev)
-            ids = torch.from_numpy(np.concatenate(parts) if parts else np.zeros((0,), dtype=np.int64)).to(dev)
+        off, ids = self._line_lists(lists, L, "targets")
         longest = int((off[1:] - off[:-1]).max().item()) if L > 0 else 0
         if longest > _lib.CATALOG_TMAX:
             raise ValueError("targets: %d on a line, at most %d (SCORE_CATALOG_TMAX)" % (longest, _lib.CATALOG_TMAX))
