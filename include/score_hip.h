@@ -663,6 +663,20 @@ int64_t score_segment_sum_scratch_bytes(int64_t n, int32_t D);
 int score_pull_form(int32_t D, int32_t mode, int64_t span_bytes);
 int score_pull_last_form(void);
 
+/* Which forms the head and the temporal attention of the launch-stream pass took in this process's latest score_forward (bits
+ * 0 .. 15) and latest score_backward (bits 16 .. 19 and 2 .. 4); -1 before the first of either.  Written on the host by the
+ * launchers, read-only, like score_pull_last_form (with a captured graph: the forms of the capture).  A pass clears its fields
+ * when it starts, so 0 in a field also stands for a stage the pass does not have or did not reach (the per-sample kernels,
+ * a model type without attention / without build_fc_net's head).
+ *   bits  0 ..  1  head forward     0 layer by layer, 1 head_fwd_fused_kernel in one launch, 2 in two launches
+ *   bits  2 ..  4  head backward    0 layer by layer, else ny of head_bwd_fused_kernel's grid (1, 2, 4)
+ *   bits  5 ..  7  attention fwd    0 separate launches, else S of attn_fwd_fused_kernel (samples per workgroup: 1, 2, 4)
+ *   bits  8 .. 15  attention fwd    KQ of the attn_fwd_fused_kernel instance (36, 44, 52, 84, 148; 0 with separate launches)
+ *   bits 16 .. 18  attention bwd    0 separate launches, else S of attn_inp_bwd_fused_kernel
+ *   bit  19        attention bwd    1 the pooling / softmax / dense_5 / dense_4 backward ran inside attn_inp_bwd_fused_kernel
+ *   bit  20        a score_forward has run        bit 21   a score_backward has run */
+int score_head_last_forms(void);
+
 /* The owner's usual way to combine the row gradients it receives: one call per source rank, in rank
  * order, each with that rank's rows (unique inside a call -- they come from score_index_plan's
  * de-duplication) and gradients.  The first writer of a row this step stores, later ones add:

@@ -27,7 +27,9 @@ __device__ __forceinline__ float gru_dpr(float drh, float hp, float r, bool live
 }
 
 // dense(activation=relu) + tf.nn.dropout (x / keep * Bernoulli(keep)) of element (row, col) of an [., N] layer: the
-// element numbering is the GEMM epilogue's (kernels.h), so a fused kernel drops what the layer-by-layer path drops
+// element numbering is the GEMM epilogue's (kernels.h), so a fused kernel drops what the layer-by-layer path drops.
+// `row` must be a row of the layer (< B): an explicit mask is exactly [B, N] bytes, so a kernel that computes the rows of a
+// ragged 16-row tile past the batch hands in min(row, B - 1) -- what it computes for those rows is never stored
 __device__ __forceinline__ float relu_dropout(float v, float bias, int drop, float keep, const uint8_t* mask, uint64_t seed,
                                               int row, int col, int N) {
   v = fmaxf(v + bias, 0.f);

@@ -117,7 +117,7 @@ __global__ __launch_bounds__(2 * DM_NTH) void deems_head_fwd_kernel(const DeemsA
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
         const int i = lq * 4 + r, row = b0 + i;
-        const float v = relu_dropout(acc[q][r], bias1[q], drop, a.keep, t.mask0, seed0, row, col, N1);
+        const float v = relu_dropout(acc[q][r], bias1[q], drop, a.keep, t.mask0, seed0, min(row, a.B - 1), col, N1);
         f1s[i * LD1 + col] = v;
         if (row < a.B) t.f1[(int64_t)row * N1 + col] = v;
       }
@@ -141,7 +141,7 @@ __global__ __launch_bounds__(2 * DM_NTH) void deems_head_fwd_kernel(const DeemsA
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
         const int i = lq * 4 + r, row = b0 + i;
-        const float v = relu_dropout(acc[q][r], bias2[q], drop, a.keep, t.mask1, seed1, row, col, N2);
+        const float v = relu_dropout(acc[q][r], bias2[q], drop, a.keep, t.mask1, seed1, min(row, a.B - 1), col, N2);
         f2s[i * LD2 + col] = v;
         if (row < a.B) t.f2[(int64_t)row * N2 + col] = v;
       }

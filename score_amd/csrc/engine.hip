@@ -1998,6 +1998,7 @@ extern "C" int score_forward(const score_config_t* cfg, const score_state_t* st,
   if ((c.d.family == FAM_DELF || c.d.family == FAM_DEEMS) && !bt->length2) return SCORE_E_BADARG;        // (item_seq_length: the model types that read it)
   if (!(keep_prob > 0.f) || keep_prob > 1.f) return SCORE_E_BADARG;
   SCORE_TRY(pass_fill(&c, st, bt, stream));
+  score_head_forms_begin(0);
   {
     PsPlan pp;       // the reference's own shapes: the whole pass as one kernel per sample (persample.h)
     if (!c.fl.ps_bwd_only && ps_path(c.d, st, bt, c.T, &pp))
@@ -2851,6 +2852,7 @@ extern "C" int score_backward(const score_config_t* cfg, const score_state_t* st
     return SCORE_E_BADARG;
   if ((c.d.family == FAM_DELF || c.d.family == FAM_DEEMS) && (!bt->length || !bt->length2)) return SCORE_E_BADARG;
   SCORE_TRY(pass_fill(&c, st, bt, stream));
+  score_head_forms_begin(1);
   {
     PsPlan pp;
     if (!c.fl.ps_fwd_only && ps_path(c.d, st, bt, c.T, &pp))

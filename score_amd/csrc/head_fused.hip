@@ -109,7 +109,7 @@ __global__ __launch_bounds__(64 * HF_NW) void head_fwd_fused_kernel(const HeadFw
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
           const int row = b0 + lq * 4 + r;
-          const float v = relu_dropout(acc[0][r], bias, a.drop, a.keep, a.mask0, seed0, row, col, N1);
+          const float v = relu_dropout(acc[0][r], bias, a.drop, a.keep, a.mask0, seed0, min(row, a.B - 1), col, N1);
           if (row < a.B) a.f1[(int64_t)row * N1 + col] = v;
         }
       }
@@ -140,7 +140,7 @@ __global__ __launch_bounds__(64 * HF_NW) void head_fwd_fused_kernel(const HeadFw
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
         const int i = lq * 4 + r, row = b0 + i;
-        const float v = relu_dropout(acc[t][r], bias, a.drop, a.keep, a.mask0, seed0, row, col, N1);
+        const float v = relu_dropout(acc[t][r], bias, a.drop, a.keep, a.mask0, seed0, min(row, a.B - 1), col, N1);
         f1s[i * LD1 + col] = v;
         if (row < a.B) a.f1[(int64_t)row * N1 + col] = v;
       }
@@ -162,7 +162,7 @@ __global__ __launch_bounds__(64 * HF_NW) void head_fwd_fused_kernel(const HeadFw
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
         const int i = lq * 4 + r, row = b0 + i;
-        const float v = relu_dropout(acc[0][r], bias, a.drop, a.keep, a.mask1, seed1, row, col, N2);
+        const float v = relu_dropout(acc[0][r], bias, a.drop, a.keep, a.mask1, seed1, min(row, a.B - 1), col, N2);
         f2s[i * LD2 + col] = v;
         if (row < a.B) a.f2[(int64_t)row * N2 + col] = v;
       }
@@ -666,6 +666,21 @@ __global__ __launch_bounds__(64 * HF_NW) void head_bwd_fused_kernel(const HeadBw
 
 }  // namespace
 
+// score_head_last_forms (include/score_hip.h): the forms the launchers below gave the latest score_forward / score_backward of
+// the process -- process-global words written on the host, like score_pull_last_form.  A pass clears its word when it starts
+// (score_head_forms_begin), a launcher that has launched writes its field; a stage that ran layer by layer / as separate
+// launches, or not at all, leaves 0.
+static int g_forms_fwd = -1, g_forms_bwd = -1;
+void score_head_forms_begin(int backward) { (backward ? g_forms_bwd : g_forms_fwd) = 0; }
+extern "C" int score_head_last_forms(void) {
+  if (g_forms_fwd < 0 && g_forms_bwd < 0) return -1;
+  return (g_forms_fwd >= 0 ? g_forms_fwd | (1 << 20) : 0) | (g_forms_bwd >= 0 ? g_forms_bwd | (1 << 21) : 0);
+}
+static inline void forms_set(int* word, int shift, int bits, int value) {
+  if (*word < 0) *word = 0;
+  *word = (*word & ~(((1 << bits) - 1) << shift)) | (value << shift);
+}
+
 // (what score_backward asks to know whether the forward pass has left dz2 behind)
 bool score_head_fwd_fused_fits(int B, int Dh, int N1, int N2) {
   const int LD0 = ((Dh + 15) & ~15) + 4, LD1 = ((N1 + 15) & ~15) + 4, LD2 = ((N2 + 15) & ~15) + 4;
@@ -703,6 +718,7 @@ int score_launch_head_fwd_fused(int B, int Dh, int N1, int N2, const float* x, c
     a.phase = 0;
     hipLaunchKernelGGL(head_fwd_fused_kernel, dim3(mt), dim3(64 * HF_NW), lds, s, a);
     SCORE_CHECK_LAUNCH();
+    forms_set(&g_forms_fwd, 0, 2, 1);
     return 0;
   }
   a.phase = 1;
@@ -711,6 +727,7 @@ int score_launch_head_fwd_fused(int B, int Dh, int N1, int N2, const float* x, c
   a.phase = 2;
   hipLaunchKernelGGL(head_fwd_fused_kernel, dim3(mt), dim3(64 * HF_NW), lds, s, a);
   SCORE_CHECK_LAUNCH();
+  forms_set(&g_forms_fwd, 0, 2, 2);
   return 0;
 }
 
@@ -762,6 +779,8 @@ int score_launch_attn_fwd_fused(int B, int T, int H, int NI, int N1, int N2, con
     default: return SCORE_E_SHAPE;
   }
   SCORE_CHECK_LAUNCH();
+  forms_set(&g_forms_fwd, 5, 3, S);
+  forms_set(&g_forms_fwd, 8, 8, kq);
   return 0;
 }
 
@@ -809,6 +828,8 @@ int score_launch_attn_inp_bwd_fused(int B, int T, int H, int NI, int N1, const f
   a.da1_out = da1_out;
   hipLaunchKernelGGL(attn_inp_bwd_fused_kernel, dim3((B + S - 1) / S), dim3(64 * AF_NW), lds, s, a);
   SCORE_CHECK_LAUNCH();
+  forms_set(&g_forms_bwd, 16, 3, S);
+  forms_set(&g_forms_bwd, 19, 1, pool);
   return 0;
 }
 
@@ -825,5 +846,6 @@ int score_launch_head_bwd_fused(int B, int Dh, int N1, int N2, const float* dz2,
   const int ny = (mt <= 128 && ntile >= 4 * HF_NW) ? (mt <= 64 ? 4 : 2) : 1;
   hipLaunchKernelGGL(head_bwd_fused_kernel, dim3(mt, ny), dim3(64 * HF_NW), 0, s, a);
   SCORE_CHECK_LAUNCH();
+  forms_set(&g_forms_bwd, 2, 3, ny);
   return 0;
 }

@@ -175,6 +175,7 @@ int score_launch_head_fwd_fused(int B, int Dh, int N1, int N2, const float* x, c
                                 float* logit, float* y, float* lossb, float* dlogit, int Bglobal, hipStream_t s,
                                 const uint64_t* seed_dev = nullptr, float* dz2 = nullptr, int single_launch = 0);
 bool score_head_fwd_fused_fits(int B, int Dh, int N1, int N2);
+void score_head_forms_begin(int backward);      // score_forward (0) / score_backward (1) starts: clears its half of score_head_last_forms
 int score_launch_head_bwd_fused(int B, int Dh, int N1, int N2, const float* dz2, const float* W2, const float* f1, float keep,
                                 const float* W1, const float* x, const float* gamma, float rs, float* dz1, float* dbn,
                                 float* dhead, float* tmp, hipStream_t s);

@@ -28,6 +28,19 @@ def test_header_symbols_exported():
     assert sorted(_lib.EXPORTS) == names
 
 
+def test_head_forms_query_is_read_only_and_documented():
+    """score_head_last_forms: host only, -1 until a pass has run in this process (no pass can run here); the header names every
+    field of the packing tests/score_head_cases.py unpacks"""
+    lib = _lib.load()
+    v = lib.score_head_last_forms()
+    assert v == -1 or (0 < v < 1 << 22 and v & (3 << 20))          # (a GPU test of the same process may have run a pass before)
+    assert lib.score_head_last_forms() == v
+    src = open(os.path.join(ROOT, "include", "score_hip.h")).read()
+    doc = src[:src.index("int score_head_last_forms(void);")].rsplit("/*", 1)[1]
+    for field in ("bits  0 ..  1", "bits  2 ..  4", "bits  5 ..  7", "bits  8 .. 15", "bits 16 .. 18", "bit  19", "bit  20", "bit 21"):
+        assert field in doc, field
+
+
 @pytest.mark.parametrize("mt", so.MODEL_TYPES)
 def test_param_layout_matches_oracle_spec(mt):
     # same variables, names, shapes, creation order and L2 filter as score.py (oracle param_spec)
