@@ -677,6 +677,26 @@ int score_pull_last_form(void);
  *   bit  20        a score_forward has run        bit 21   a score_backward has run */
 int score_head_last_forms(void);
 
+/* What the latest product of this process launched (host only; -1 before the first): score_gemm, and the grouped launches the
+ * engine makes for same-shape products.  Written on the host where the launch is decided, read-only, like score_pull_last_form.
+ *   bits  0 ..  1  family     1 gemm_f32_kernel (exact fp32 on the f32 matrix instruction), 2 gemm_bf16x3_kernel
+ *   bits  2 ..  3  WM         wave tile height in 32-row units (f32: block = 64 WM rows; bf16x3: wm, block = 64 wm rows)
+ *   bits  4 ..  5  WN         f32: wave tile width in 32-column units (block = 64 WN columns); bf16x3: 0 (always 128 columns)
+ *   bits  6 ..  7  trans      the operand layout of the kernel instance (0 NN, 1 NT, 2 TN)
+ *   bit   8        grouped    1 several same-shape problems in one launch (never split)
+ *   bits 12 .. 27  K slabs    workgroup layers along K actually launched; 1 = K not split, more = splitk_reduce_kernel follows
+ *                             and applies the epilogue */
+int score_gemm_last_form(void);
+
+/* What the latest recurrence launch of this process was (host only; -1 before the first): score_gru_fwd / score_gru_bwd and
+ * the engine's two-sided launches.  Written on the host where the launch is decided, read-only.
+ *   bits  0 ..  2  family     1 bf16x3 recurrence (H = 128), 2 register-resident weights (H = 16, 32, 64; 128 with the bf16x3
+ *                             form off), 3 streamed weights (H = 256 inside the engine), 4 step by step (grouped products and
+ *                             pointwise launches per slice), 5 state in LDS (every other H through score_gru_fwd / _bwd)
+ *   bits  4 ..  7  waves      waves per workgroup of that launch (register form: 4; 2 for the H = 32 backward from T = 20 on)
+ *   bit   8        direction  0 forward, 1 backward */
+int score_gru_last_form(void);
+
 /* The owner's usual way to combine the row gradients it receives: one call per source rank, in rank
  * order, each with that rank's rows (unique inside a call -- they come from score_index_plan's
  * de-duplication) and gradients.  The first writer of a row this step stores, later ones add:

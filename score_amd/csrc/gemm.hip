@@ -222,6 +222,14 @@ __device__ __forceinline__ void splitk_reduce_group_body(const ReduceGroup& g, i
 }
 __global__ void splitk_reduce_group_kernel(const ReduceGroup g) { splitk_reduce_group_body(g, (int)blockIdx.x); }
 
+// score_gemm_last_form (include/score_hip.h): what the latest product of this process launched -- a process-global word written
+// on the host where the launch is decided, like score_pull_last_form
+static int g_gemm_last_form = -1;
+extern "C" int score_gemm_last_form(void) { return g_gemm_last_form; }
+static void gemm_note_form(int family, int wm, int wn, int trans, int grouped, int slabs) {
+  g_gemm_last_form = family | wm << 2 | wn << 4 | trans << 6 | grouped << 8 | (slabs > 0xFFFF ? 0xFFFF : slabs) << 12;
+}
+
 static void fill_prob(GemmProb* p, int M, int N, int K, const float* A, int lda, const float* B, int ldb, float* C,
                       int ldc, int k_chunk, float* slab, int gx, int gy, int gz) {
   p->A = A; p->B = B; p->C = C; p->slab = slab; p->bias = nullptr; p->M = M; p->N = N; p->K = K; p->lda = lda; p->ldb = ldb;
@@ -281,6 +289,7 @@ extern "C" int score_gemm(int32_t trans, int32_t M, int32_t N, int32_t K, const 
     grp.n = 1;
     fill_prob(&grp.p[0], M, N, K, A, lda, Bm, ldb, C, ldc, kc, sl, (int)g3.x, (int)g3.y, (int)g3.z);
     grp.total_blocks = (grp.p[0].nblocks + 7) & ~7;
+    gemm_note_form(2, wm3, 0, trans, 0, (int)g3.z);
     SCORE_TRY(score_launch_gemm_bf16x3(trans, wm3, grp, bias, flags & KF_MASK, keep_prob, drop_mask, drop_seed, s));
     if (sl) {
       int64_t n = (int64_t)M * N;
@@ -322,6 +331,7 @@ extern "C" int score_gemm(int32_t trans, int32_t M, int32_t N, int32_t K, const 
   grp.n = 1;
   fill_prob(&grp.p[0], M, N, K, A, lda, Bm, ldb, C, ldc, k_chunk, slab, (int)grid.x, (int)grid.y, (int)grid.z);
   grp.total_blocks = (grp.p[0].nblocks + 7) & ~7;
+  gemm_note_form(1, WMs, WNs, trans, 0, (int)grid.z);
 #define LAUNCH(TR, WMv, WNv)                                                                                       \
   hipLaunchKernelGGL((gemm_f32_kernel<TR, WMv, WNv, 16>), dim3(grp.total_blocks), dim3(256), 0, s, grp, bias, flags, \
                      keep_prob, drop_mask, drop_seed)
@@ -375,6 +385,7 @@ int score_gemm_same_shape(int trans, int nprob, int M, int N, int K, const float
         grp.p[i].bias = bias ? bias[i] : nullptr;
         grp.total_blocks += (grp.p[i].nblocks + 7) & ~7;
       }
+      gemm_note_form(2, wm, 0, trans, 1, 1);
       return score_launch_gemm_bf16x3(trans, wm, grp, nullptr, flags, 1.f, nullptr, 0, s);
     }
   }
@@ -392,6 +403,7 @@ int score_gemm_same_shape(int trans, int nprob, int M, int N, int K, const float
     grp.p[i].bias = bias ? bias[i] : nullptr;
     grp.total_blocks += (grp.p[i].nblocks + 7) & ~7;
   }
+  gemm_note_form(1, 1, 1, trans, 1, 1);
 #define LS(TR) hipLaunchKernelGGL((gemm_f32_kernel<TR, 1, 1, 16>), dim3(grp.total_blocks), dim3(256), 0, s, grp, nullptr, \
                                   flags, 1.f, nullptr, 0)
   if (trans == 0) LS(0); else if (trans == 1) LS(1); else LS(2);

@@ -16,6 +16,12 @@ typedef float f32x16 __attribute__((ext_vector_type(16)));
 static bool gru_reg_ok(int H);
 int score_gru_fwd_multi(GruArgs& a, int nsides, hipStream_t s);
 int score_gru_bwd_multi(GruArgs& a, int nsides, hipStream_t s);  // batch rows per workgroup
+// score_gru_last_form (include/score_hip.h): family, waves per workgroup and direction of this process's latest recurrence
+// launch -- a process-global word written on the host where the launch is decided, like score_pull_last_form
+enum { GRUF_X3 = 1, GRUF_REG = 2, GRUF_STREAM = 3, GRUF_STEPS = 4, GRUF_LDS = 5 };
+static int g_gru_last_form = -1;
+extern "C" int score_gru_last_form(void) { return g_gru_last_form; }
+static void gru_note_form(int family, int waves, int backward) { g_gru_last_form = family | waves << 4 | backward << 8; }
 
 // acc(32 x 32 cols starting at j0) = Ash[32][K] (LDS, row stride lds_ld) . Wm[K][ldw] (global)
 __device__ __forceinline__ f32x16 tile_matmul(const float* __restrict__ Ash, int lds_ld, int Kdim,
@@ -130,6 +136,7 @@ extern "C" int score_gru_fwd(int32_t B, int32_t T, int32_t H, const float* xproj
   }
   size_t lds = (size_t)3 * RB * (H + 1) * sizeof(float);
   if (lds > 160 * 1024) return SCORE_E_SHAPE;
+  gru_note_form(GRUF_LDS, 4, 0);
   if (lds > 48 * 1024)
     (void)hipFuncSetAttribute((const void*)gru_fwd_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
   hipLaunchKernelGGL(gru_fwd_kernel, dim3((B + RB - 1) / RB), dim3(256), lds, (hipStream_t)stream, B, T, H, xproj,
@@ -266,6 +273,7 @@ extern "C" int score_gru_bwd(int32_t B, int32_t T, int32_t H, const float* Wg, i
   size_t lds = (size_t)RB * (2 * (H + 1) + (2 * H + 1)) * sizeof(float);
   if (lds > 160 * 1024) return SCORE_E_SHAPE;
   hipStream_t s = (hipStream_t)stream;
+  gru_note_form(GRUF_LDS, 4, 1);
   float* WgT = hprev + (int64_t)B * T * H;  // [2H][H]
   float* WcT = WgT + (int64_t)2 * H * H;    // [H][H]
   hipLaunchKernelGGL(transpose_kernel, dim3((2 * H * H + 255) / 256), dim3(256), 0, s, Wg, H, 2 * H, ldwg, WgT);
@@ -857,10 +865,11 @@ int score_gru_fwd_multi(GruArgs& a, int nsides, hipStream_t s) {
   const int H = a.H;
   const GruRoute rt = gru_route(a, nsides);
   switch (rt.family) {
-    case GRU_X3: return score_gru_fwd_x3(a, nsides, s);
+    case GRU_X3: gru_note_form(GRUF_X3, 8, 0); return score_gru_fwd_x3(a, nsides, s);      // (gru_x3.hip: XNW = 8 waves)
     case GRU_REG: {
       dim3 grid(nsides * ((a.B + RRB - 1) / RRB));
       const GruArgs k = gru_reg_args(a, nsides);
+      gru_note_form(GRUF_REG, rt.nw, 0);
 #define LF(Hv, NWv) hipLaunchKernelGGL((gru_fwd_reg_kernel<Hv, NWv>), grid, dim3(64 * NWv), 0, s, k)
       if (H == 16) LF(16, 4);
       else if (H == 32) LF(32, 4);
@@ -871,8 +880,8 @@ int score_gru_fwd_multi(GruArgs& a, int nsides, hipStream_t s) {
       SCORE_CHECK_LAUNCH();
       return 0;
     }
-    case GRU_STREAM: return score_gru_fwd_stream(a, nsides, s);
-    case GRU_STEPS: return gru_fwd_steps(a, nsides, s);
+    case GRU_STREAM: gru_note_form(GRUF_STREAM, 8, 0); return score_gru_fwd_stream(a, nsides, s);   // (gru_stream.hip: SNW = 8)
+    case GRU_STEPS: gru_note_form(GRUF_STEPS, 4, 0); return gru_fwd_steps(a, nsides, s);            // (pointwise launches of 256)
     case GRU_PER_SIDE: break;
   }
   for (int i = 0; i < nsides; ++i) {
@@ -887,14 +896,18 @@ int score_gru_bwd_multi(GruArgs& a, int nsides, hipStream_t s) {
   const int H = a.H;
   const GruRoute rt = gru_route(a, nsides);
   switch (rt.family) {
-    case GRU_X3: return score_gru_bwd_x3(a, nsides, s);
+    case GRU_X3: gru_note_form(GRUF_X3, 8, 1); return score_gru_bwd_x3(a, nsides, s);
     case GRU_REG: {
       dim3 grid(nsides * ((a.B + RRB - 1) / RRB));
       const GruArgs k = gru_reg_args(a, nsides);
+      // H = 32: two waves from 20 slices on: a shorter step, a longer prologue (each wave holds twice the weights) -- the CCMR
+      // shape (T = 40) 0.5174 -> 0.5064 ms/step, cfg-2 (T = 10) 0.272 -> 0.278; the forward keeps four
+      const int nwb = (H == 32 && a.T >= 20) ? 2 : rt.nw;
+      gru_note_form(GRUF_REG, nwb, 1);
 #define LB(Hv, NWv) hipLaunchKernelGGL((gru_bwd_reg_kernel<Hv, NWv>), grid, dim3(64 * NWv), 0, s, k)
       if (H == 16) LB(16, 4);
-      else if (H == 32) {     // two waves from 20 slices on: a shorter step, a longer prologue (each wave holds twice the weights) -- the CCMR
-        if (a.T >= 20) LB(32, 2);     // shape (T = 40) 0.5174 -> 0.5064 ms/step, cfg-2 (T = 10) 0.272 -> 0.278; the forward keeps four
+      else if (H == 32) {
+        if (nwb == 2) LB(32, 2);
         else LB(32, 4);
       }
       else if (H == 64) LB(64, 4);
@@ -904,8 +917,8 @@ int score_gru_bwd_multi(GruArgs& a, int nsides, hipStream_t s) {
       SCORE_CHECK_LAUNCH();
       return 0;
     }
-    case GRU_STREAM: return score_gru_bwd_stream(a, nsides, s);
-    case GRU_STEPS: return gru_bwd_steps(a, nsides, s);
+    case GRU_STREAM: gru_note_form(GRUF_STREAM, 8, 1); return score_gru_bwd_stream(a, nsides, s);
+    case GRU_STEPS: gru_note_form(GRUF_STEPS, 4, 1); return gru_bwd_steps(a, nsides, s);
     case GRU_PER_SIDE: break;
   }
   for (int i = 0; i < nsides; ++i) {

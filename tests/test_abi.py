@@ -41,6 +41,29 @@ def test_head_forms_query_is_read_only_and_documented():
         assert field in doc, field
 
 
+def test_gemm_and_gru_form_queries_are_read_only_and_documented():
+    """score_gemm_last_form / score_gru_last_form: host only, -1 until a product / a recurrence has been launched in this process
+    (none can be here); the header names every field tests/gemm_cases.py and tests/gru_cases.py unpack"""
+    import gemm_cases
+    import gru_cases
+    lib = _lib.load()
+    g, r = lib.score_gemm_last_form(), lib.score_gru_last_form()
+    # (a GPU test of the same process may have launched before)
+    assert g == -1 or (0 < g < 1 << 28 and gemm_cases.unpack(g)[0].family in (gemm_cases.F32, gemm_cases.X3) and gemm_cases.unpack(g)[0].slabs >= 1)
+    assert r == -1 or (0 < r < 1 << 9 and 1 <= gru_cases.unpack(r).family <= 5 and gru_cases.unpack(r).waves in (2, 4, 8))
+    assert lib.score_gemm_last_form() == g and lib.score_gru_last_form() == r
+    src = open(os.path.join(ROOT, "include", "score_hip.h")).read()
+    doc = src[:src.index("int score_gemm_last_form(void);")].rsplit("/*", 1)[1]
+    for field in ("bits  0 ..  1", "bits  2 ..  3", "bits  4 ..  5", "bits  6 ..  7", "bit   8", "bits 12 .. 27", "-1 before the first"):
+        assert field in doc, field
+    doc = src[:src.index("int score_gru_last_form(void);")].rsplit("/*", 1)[1]
+    for field in ("bits  0 ..  2", "bits  4 ..  7", "bit   8", "-1 before the first"):
+        assert field in doc, field
+    # the packing of the two case modules is the documented one
+    assert gemm_cases.pack(gemm_cases.Form(gemm_cases.X3, 2, 0, 5), 1) == 2 | 2 << 2 | 1 << 6 | 5 << 12
+    assert gru_cases.pack(gru_cases.Form(gru_cases.REG, 2, 1)) == 2 | 2 << 4 | 1 << 8
+
+
 @pytest.mark.parametrize("mt", so.MODEL_TYPES)
 def test_param_layout_matches_oracle_spec(mt):
     # same variables, names, shapes, creation order and L2 filter as score.py (oracle param_spec)
