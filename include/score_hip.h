@@ -648,7 +648,9 @@ int64_t score_sort_pairs_temp_bytes(int64_t n);
 /* out[rows[j], :] = sum over slots j with equal rows[j] of src[j, :] (slot order; rows never
  * named keep their value).  The shard owner uses it to combine the row gradients received
  * from every rank.  row_flags (optional, [n_out_rows]): every row written is marked 2 for
- * score_adam_rows.  scratch: score_segment_sum_scratch_bytes(n, D). */
+ * score_adam_rows.  scratch: score_segment_sum_scratch_bytes(n, D) -- the answer carries 64 bytes of slack, the call itself
+ * returns SCORE_E_WORKSPACE (nothing launched) from 65 bytes below it.  Row 0 is a row like any other here, n_out_rows = 1
+ * included.  D: a multiple of 4 up to 256 (score_pull_geometry has the refusals); n below 2^29; n = 0 does nothing. */
 int score_segment_sum_rows(const int32_t* rows, const float* src, int64_t n, int32_t D, int64_t n_out_rows,
                            float* out, uint8_t* row_flags, void* scratch, int64_t scratch_bytes, void* stream);
 int64_t score_segment_sum_scratch_bytes(int64_t n, int32_t D);
@@ -662,6 +664,21 @@ int64_t score_segment_sum_scratch_bytes(int64_t n, int32_t D);
  * (-1 before the first). */
 int score_pull_form(int32_t D, int32_t mode, int64_t span_bytes);
 int score_pull_last_form(void);
+
+/* The launch geometry of the row scatter (pull kernel + fix-up launch) over n occurrences at row width D, as the launcher
+ * computes it (host only, no GPU needed; the launcher and this query share one function):
+ *   *window            occurrences per window: 8 below 2^18 occurrences, 16 from 2^18, 32 from 2^19, 64 from 2^20
+ *   *lanes_per_row     lanes of a group, four floats each: the power of two at or above D/4 (D = 12: 4 lanes, 3 used)
+ *   *groups_per_block  256 / lanes_per_row: windows per workgroup, and the groups a long chain is split over
+ *   *long_chain        a run that continues through more than this many windows after its first is summed by the whole
+ *                      workgroup in the fix-up launch (chunk = ceil(L / groups_per_block) windows per group, eight loads per
+ *                      trip), a shorter one by the group of its first window
+ * SCORE_E_BADARG: a null pointer, n < 0, D <= 0 or D not a multiple of 4.  SCORE_E_SHAPE: D above 256 (more than 64 lanes).
+ * score_segment_sum_rows refuses those widths the same way: D % 4 != 0 with SCORE_E_BADARG before anything is launched; D
+ * above 256 with SCORE_E_SHAPE from the launcher, after the sort of the row ids inside scratch -- `out` and `row_flags` are
+ * untouched in both cases.  (score_rows_accumulate / _multi refuse D above 256 with SCORE_E_BADARG.) */
+int score_pull_geometry(int64_t n, int32_t D, int32_t* window, int32_t* lanes_per_row, int32_t* groups_per_block,
+                        int32_t* long_chain);
 
 /* Which forms the head and the temporal attention of the launch-stream pass took in this process's latest score_forward (bits
  * 0 .. 15) and latest score_backward (bits 16 .. 19 and 2 .. 4); -1 before the first of either.  Written on the host by the
@@ -708,7 +725,8 @@ int score_rows_accumulate(const int32_t* rows, const float* src, int64_t n, int3
  * (offsets: HOST array of n_sources + 1 entries, offsets[0] = 0; n_sources <= 64), every list unique and ascending (what
  * score_index_plan's unique-row lists are).  The result is bit for bit that of n_sources score_rows_accumulate calls in
  * source order: the slot of the lowest source that names a row adds the later sources' rows in source order (binary search
- * per list) and stores once. */
+ * per list) and stores once -- to a row an earlier call left in state 2 it adds what is there FIRST, ((out + g_p0) + g_p1) ...,
+ * as the per-source calls do.  D: a multiple of 4 up to 256, else SCORE_E_BADARG (both ops). */
 int score_rows_accumulate_multi(const int32_t* rows, const float* src, const int64_t* offsets, int32_t n_sources, int32_t D,
                                 int64_t n_out_rows, float* out, uint8_t* row_flags, void* stream);
 

@@ -290,6 +290,8 @@ _SIGS = {
     "score_segment_sum_scratch_bytes": [C.c_int64, C.c_int32],
     "score_pull_form": [C.c_int32, C.c_int32, C.c_int64],
     "score_pull_last_form": [],
+    "score_pull_geometry": [C.c_int64, C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32),
+                            C.POINTER(C.c_int32)],
     "score_head_last_forms": [],
     "score_gemm_last_form": [],
     "score_gru_last_form": [],

@@ -705,19 +705,36 @@ static void pull_lanes_launch(const PullArgs& a, const PullLanes& L, int LPR, in
 #undef PULL_LANES_GO
 }
 
+// the launch geometry of a scatter over n occurrences at row width D: occurrences per window, lanes per group (the power
+// of two at or above D/4), groups per workgroup.  The launcher and score_pull_geometry both take it from here.
+static int pull_geometry(int64_t n, int D, int* WS, int* LPR, int* gpb) {
+  *WS = score_pull_window(n);
+  *LPR = 1;
+  while (*LPR < D / 4) *LPR <<= 1;
+  if (*LPR > 64) return SCORE_E_SHAPE;
+  *gpb = 256 / *LPR;
+  return 0;
+}
+
+extern "C" int score_pull_geometry(int64_t n, int32_t D, int32_t* window, int32_t* lanes_per_row, int32_t* groups_per_block,
+                                   int32_t* long_chain) {
+  if (!window || !lanes_per_row || !groups_per_block || !long_chain || n < 0 || D <= 0 || (D & 3)) return SCORE_E_BADARG;
+  int WS, LPR, gpb;
+  SCORE_TRY(pull_geometry(n, D, &WS, &LPR, &gpb));
+  *window = WS; *lanes_per_row = LPR; *groups_per_block = gpb; *long_chain = LONG_CHAIN;
+  return 0;
+}
+
 int score_launch_pull(PullArgs& a, const uint32_t* keys, const uint32_t* vals, int64_t n, float* out,
                       float* partials, int64_t partial_floats, hipStream_t s) {
-  const int WS = score_pull_window(n);
-  int LPR = 1;
-  while (LPR < a.D / 4) LPR <<= 1;
-  if (LPR > 64) return SCORE_E_SHAPE;
+  int WS, LPR, gpb;
+  SCORE_TRY(pull_geometry(n, a.D, &WS, &LPR, &gpb));
   a.LPRp = LPR;
   int64_t nw = cdiv64(n, WS);
   // partials: pfirst [nw][D] | plast [nw][D]
   if (2 * nw * a.D > partial_floats) return SCORE_E_WORKSPACE;
   float* pfirst = partials;
   float* plast = partials + nw * a.D;
-  int gpb = 256 / LPR;
   unsigned blocks = (unsigned)cdiv64(nw, gpb);
   // contribution form: owner-side row sum (descriptors are source slots), constant coefficients, or the
   // co-attention's per-(unit, k) coefficients
@@ -838,13 +855,15 @@ __global__ __launch_bounds__(256) void rows_accumulate_multi_kernel(const AccMul
     if (j < a.off[q + 1] && rows[j] == r) return;
   }
   if (ch4 >= D) return;
+  const uint8_t f = flags[r];
   float4 v = ld4(src + i * D + ch4);
+  // a row already written this step by an earlier call: what is there comes first, as in the per-source launches
+  // (((out + g_p0) + g_p1) + ...; added last it was out + (g_p0 + g_p1 + ...), other bits)
+  if (f == 2) v = add4(ld4(out + (int64_t)r * D + ch4), v);
   for (int q = p + 1; q < a.n_sources; ++q) {
     const int64_t j = acc_find(rows, a.off[q], a.off[q + 1], r);
     if (j < a.off[q + 1] && rows[j] == r) v = add4(v, ld4(src + j * D + ch4));
   }
-  const uint8_t f = flags[r];
-  if (f == 2) v = add4(ld4(out + (int64_t)r * D + ch4), v);      // (a row already written this step by an earlier call)
   st4(out + (int64_t)r * D + ch4, v);
   if (ch4 == 0 && f != 2) flags[r] = 2;
 }

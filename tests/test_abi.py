@@ -64,7 +64,31 @@ def test_gemm_and_gru_form_queries_are_read_only_and_documented():
     assert gru_cases.pack(gru_cases.Form(gru_cases.REG, 2, 1)) == 2 | 2 << 4 | 1 << 8
 
 
-@pytest.mark.parametrize("mt", so.MODEL_TYPES)
+def test_pull_geometry_query_is_host_only_and_documented():
+    """score_pull_geometry: what score_launch_pull would use for (n, D), without a GPU and without touching score_pull_last_form;
+    the header names the four outputs, the window thresholds and both refusals (tests/scatter_cases.py restates them)"""
+    import ctypes as C
+    import scatter_cases
+    lib = _lib.load()
+    before = lib.score_pull_last_form()
+    w, l, g, c = (C.c_int32(-1) for _ in range(4))
+    for n, D, want in ((1, 4, (8, 1, 256, 16)), (70000, 16, (8, 4, 64, 16)), (1 << 18, 12, (16, 4, 64, 16)),
+                       (1 << 19, 20, (32, 8, 32, 16)), (1 << 20, 256, (64, 64, 4, 16)), ((1 << 20) - 1, 128, (32, 32, 8, 16))):
+        assert lib.score_pull_geometry(n, D, C.byref(w), C.byref(l), C.byref(g), C.byref(c)) == 0
+        assert (w.value, l.value, g.value, c.value) == want == scatter_cases.geometry(n, D), (n, D)
+    assert lib.score_pull_geometry(8, 260, C.byref(w), C.byref(l), C.byref(g), C.byref(c)) == -2      # SCORE_E_SHAPE, as the launcher
+    assert lib.score_pull_geometry(8, 6, C.byref(w), C.byref(l), C.byref(g), C.byref(c)) == -1
+    assert lib.score_pull_geometry(8, 16, None, None, None, None) == -1
+    assert (w.value, l.value, g.value, c.value) == (32, 32, 8, 16)                                   # a refusal writes nothing
+    assert lib.score_pull_last_form() == before
+    src = open(os.path.join(ROOT, "include", "score_hip.h")).read()
+    doc = src[:src.index("int score_pull_geometry(")].rsplit("/*", 1)[1]
+    for field in ("*window", "*lanes_per_row", "*groups_per_block", "*long_chain", "2^18", "2^19", "2^20", "SCORE_E_BADARG",
+                  "SCORE_E_SHAPE", "D above 256", "score_segment_sum_rows"):
+        assert field in doc, field
+
+
+@pytest.mark.parametrize("mt",so.MODEL_TYPES)
 def test_param_layout_matches_oracle_spec(mt):
     # same variables, names, shapes, creation order and L2 filter as score.py (oracle param_spec)
     cfg = _lib.make_config(1000, 16, 32, 11, 10, 3, 4, mt)
