@@ -714,6 +714,23 @@ int score_gemm_last_form(void);
  *   bit   8        direction  0 forward, 1 backward */
 int score_gru_last_form(void);
 
+/* Which instance of the fused gather + co-attention kernels (csrc/embed.hip) this process's latest forward launch
+ * (backward = 0) and latest backward launch (backward != 0) took: score_coattn_fwd / score_coattn_bwd and the one-grid
+ * launches score_forward / score_backward make for the model's two calls.  Host only; each direction's word is written
+ * where its launch is decided, read-only, and is -1 before the first launch of that direction (a refused call writes nothing).
+ * Forward word:
+ *   bit   0        kernel     0 coattn_fwd_kernel (one unit per group), 1 coattn_fwd_kernel_units (a chunk of slices per group)
+ *   bits  1 ..  6  KMAX       neighbours the instance unrolls (4, 10, 20, 32)
+ *   bits  8 .. 10  SPL / NM   one-unit kernel: float4 slots per lane (1, 2, 4); units kernel: registers per id list (1, 2)
+ *   bits 12 .. 27  CH         time slices per chunk of the units kernel; 0 with the one-unit kernel
+ * Backward word (coattn_bwd_kernel_t<KMAX, SPL, ATOMIC, NM>):
+ *   bits  1 ..  6  KMAX       4, 10, 20, 32
+ *   bits  8 .. 10  SPL        float4 slots per lane: the larger of the launch's calls (1, 2, 4; three slots run as 4)
+ *   bits 12 .. 14  NM         registers per metadata list, one element per lane (1, 2, 4); 0: every lane reads its own ids
+ *   bit  16        ATOMIC     1 the kernel adds the row gradients itself (score_coattn_bwd always), 0 the pull-form scatter follows
+ *   bits 20 .. 21  mode       0 co-attention, 1 sum over the neighbours (RCA) */
+int score_coattn_last_forms(int32_t backward);
+
 /* The owner's usual way to combine the row gradients it receives: one call per source rank, in rank
  * order, each with that rank's rows (unique inside a call -- they come from score_index_plan's
  * de-duplication) and gradients.  The first writer of a row this step stores, later ones add:

@@ -295,6 +295,7 @@ _SIGS = {
     "score_head_last_forms": [],
     "score_gemm_last_form": [],
     "score_gru_last_form": [],
+    "score_coattn_last_forms": [C.c_int32],
     "score_rows_accumulate": [c_i, c_f, C.c_int64, C.c_int32, C.c_int64, c_f, C.c_void_p, C.c_void_p],
     "score_rows_accumulate_multi": [c_i, c_f, C.POINTER(C.c_int64), C.c_int32, C.c_int32, C.c_int64, c_f, C.c_void_p, C.c_void_p],
     "score_auc_logloss": [c_f, c_i, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p],

@@ -893,22 +893,35 @@ __global__ __launch_bounds__(256, 4) void coattn_fwd_kernel_units(const CoattnAr
   if (a.id_status && (bad1 || bad2)) atomicOr(a.id_status, (bad1 ? 1 << cc.bit1 : 0) | (bad2 ? 1 << cc.bit2 : 0));
 }
 
-#define COATTN_DISPATCH(KERNEL, EXTRA, SPLV, KV, ...)                                  \
-  do {                                                                                    \
-    if (SPLV == 1) {                                                                      \
-      if (KV <= 4) { hipLaunchKernelGGL((KERNEL<4, 1 EXTRA>), __VA_ARGS__); }             \
-      else if (KV <= 10) { hipLaunchKernelGGL((KERNEL<10, 1 EXTRA>), __VA_ARGS__); }      \
-      else if (KV <= 20) { hipLaunchKernelGGL((KERNEL<20, 1 EXTRA>), __VA_ARGS__); }      \
-      else { hipLaunchKernelGGL((KERNEL<32, 1 EXTRA>), __VA_ARGS__); }                    \
-    } else if (SPLV == 2) {                                                               \
-      if (KV <= 4) { hipLaunchKernelGGL((KERNEL<4, 2 EXTRA>), __VA_ARGS__); }             \
-      else if (KV <= 10) { hipLaunchKernelGGL((KERNEL<10, 2 EXTRA>), __VA_ARGS__); }      \
-      else if (KV <= 20) { hipLaunchKernelGGL((KERNEL<20, 2 EXTRA>), __VA_ARGS__); }      \
-      else { hipLaunchKernelGGL((KERNEL<32, 2 EXTRA>), __VA_ARGS__); }                    \
-    } else {                                                                              \
-      if (KV <= 10) { hipLaunchKernelGGL((KERNEL<10, 4 EXTRA>), __VA_ARGS__); }           \
-      else { hipLaunchKernelGGL((KERNEL<20, 4 EXTRA>), __VA_ARGS__); }                    \
-    }                                                                                     \
+// score_coattn_last_forms (include/score_hip.h): the instance the latest forward / backward launch of this process took --
+// process-global words written on the host by whatever names the instance (the launch templates from their own parameters,
+// COATTN_DISPATCH in the branch it takes), like score_pull_last_form
+static int g_coattn_last_forms[2] = {-1, -1};
+static int g_coattn_dispatched[2];      // KMAX, SPL of the instance COATTN_DISPATCH took
+extern "C" int score_coattn_last_forms(int32_t backward) { return g_coattn_last_forms[backward ? 1 : 0]; }
+static void coattn_note_fwd(int units, int kmax, int spl_or_nm, int ch) {
+  g_coattn_last_forms[0] = units | kmax << 1 | spl_or_nm << 8 | (ch > 0xFFFF ? 0xFFFF : ch) << 12;
+}
+static void coattn_note_bwd(int kmax, int spl, int nm, int atomic, int mode) {
+  g_coattn_last_forms[1] = kmax << 1 | spl << 8 | nm << 12 | (atomic ? 1 : 0) << 16 | (mode & 3) << 20;
+}
+#define COATTN_TOOK(KM, SP) g_coattn_dispatched[0] = KM; g_coattn_dispatched[1] = SP;
+#define COATTN_DISPATCH(KERNEL, EXTRA, SPLV, KV, ...)                                                   \
+  do {                                                                                                  \
+    if (SPLV == 1) {                                                                                    \
+      if (KV <= 4) { COATTN_TOOK(4, 1) hipLaunchKernelGGL((KERNEL<4, 1 EXTRA>), __VA_ARGS__); }         \
+      else if (KV <= 10) { COATTN_TOOK(10, 1) hipLaunchKernelGGL((KERNEL<10, 1 EXTRA>), __VA_ARGS__); } \
+      else if (KV <= 20) { COATTN_TOOK(20, 1) hipLaunchKernelGGL((KERNEL<20, 1 EXTRA>), __VA_ARGS__); } \
+      else { COATTN_TOOK(32, 1) hipLaunchKernelGGL((KERNEL<32, 1 EXTRA>), __VA_ARGS__); }               \
+    } else if (SPLV == 2) {                                                                             \
+      if (KV <= 4) { COATTN_TOOK(4, 2) hipLaunchKernelGGL((KERNEL<4, 2 EXTRA>), __VA_ARGS__); }         \
+      else if (KV <= 10) { COATTN_TOOK(10, 2) hipLaunchKernelGGL((KERNEL<10, 2 EXTRA>), __VA_ARGS__); } \
+      else if (KV <= 20) { COATTN_TOOK(20, 2) hipLaunchKernelGGL((KERNEL<20, 2 EXTRA>), __VA_ARGS__); } \
+      else { COATTN_TOOK(32, 2) hipLaunchKernelGGL((KERNEL<32, 2 EXTRA>), __VA_ARGS__); }               \
+    } else {                                                                                            \
+      if (KV <= 10) { COATTN_TOOK(10, 4) hipLaunchKernelGGL((KERNEL<10, 4 EXTRA>), __VA_ARGS__); }      \
+      else { COATTN_TOOK(20, 4) hipLaunchKernelGGL((KERNEL<20, 4 EXTRA>), __VA_ARGS__); }               \
+    }                                                                                                   \
   } while (0)
 #define COMMA_TRUE0 , true, 0
 #define COMMA_FALSE0 , false, 0
@@ -917,6 +930,7 @@ __global__ __launch_bounds__(256, 4) void coattn_fwd_kernel_units(const CoattnAr
 // Returns false where no instance holds `need` registers: the caller takes the NM = 0 instance.
 template <int KMAX, int SPL, bool ATOMIC, int NM>
 static void coattn_bwd_launch(int total, size_t lds_bytes, hipStream_t s, const CoattnArgs& a) {
+  coattn_note_bwd(KMAX, SPL, NM, ATOMIC, a.mode);
   hipLaunchKernelGGL((coattn_bwd_kernel_t<KMAX, SPL, ATOMIC, NM>), dim3(total), dim3(256), lds_bytes, s, a);
 }
 template <int SPL, bool ATOMIC>
@@ -991,6 +1005,7 @@ int score_coattn_fwd_chunk_rule(int D, int K, int B, int T, int ncalls, const in
 }
 template <int KMAX, int NM>
 static void coattn_fwd_units_launch(int total, hipStream_t s, const CoattnArgs& a) {
+  coattn_note_fwd(1, KMAX, NM, a.CH);
   hipLaunchKernelGGL((coattn_fwd_kernel_units<KMAX, NM>), dim3(total), dim3(256), 0, s, a);
 }
 
@@ -1036,6 +1051,7 @@ int score_coattn_fwd_multi(CoattnArgs& a, int ncalls, int D, int B, hipStream_t 
   }
   if (spl == 3) spl = 4;
   COATTN_DISPATCH(coattn_fwd_kernel, , spl, a.K, dim3(total), dim3(256), 0, s, a);
+  coattn_note_fwd(0, g_coattn_dispatched[0], g_coattn_dispatched[1], 0);
   SCORE_CHECK_LAUNCH();
   return 0;
 }
@@ -1082,6 +1098,7 @@ int score_coattn_bwd_multi(CoattnArgs& a, int ncalls, int D, int B, float* const
   if (!ahead) {
     if (atomic_scatter) COATTN_DISPATCH(coattn_bwd_kernel_t, COMMA_TRUE0, spl, a.K, dim3(total), dim3(256), lds_bytes, s, a);
     else COATTN_DISPATCH(coattn_bwd_kernel_t, COMMA_FALSE0, spl, a.K, dim3(total), dim3(256), lds_bytes, s, a);
+    coattn_note_bwd(g_coattn_dispatched[0], g_coattn_dispatched[1], 0, atomic_scatter, a.mode);
   }
   SCORE_CHECK_LAUNCH();
   if (a.mode == 0) {

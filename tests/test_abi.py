@@ -64,6 +64,32 @@ def test_gemm_and_gru_form_queries_are_read_only_and_documented():
     assert gru_cases.pack(gru_cases.Form(gru_cases.REG, 2, 1)) == 2 | 2 << 4 | 1 << 8
 
 
+def test_coattn_forms_query_is_read_only_and_documented():
+    """score_coattn_last_forms: host only, one word per direction, -1 until that direction has launched in this process (nothing
+    can launch here, and a refused call writes nothing); the header names every field tests/coattn_cases.py unpacks"""
+    import ctypes as C
+    import coattn_cases
+    lib = _lib.load()
+    f, b = lib.score_coattn_last_forms(0), lib.score_coattn_last_forms(1)
+    # (a GPU test of the same process may have launched before)
+    assert f == -1 or (0 < f < 1 << 28 and coattn_cases.unpack_fwd(f).kmax in (4, 10, 20, 32) and coattn_cases.unpack_fwd(f).reg in (1, 2, 4))
+    assert b == -1 or (0 < b < 1 << 22 and coattn_cases.unpack_bwd(b).kmax in (4, 10, 20, 32) and coattn_cases.unpack_bwd(b).spl in (1, 2, 4)
+                       and coattn_cases.unpack_bwd(b).nm in (0, 1, 2, 4) and coattn_cases.unpack_bwd(b).mode in (0, 1))
+    z = C.c_void_p(0)
+    assert lib.score_coattn_fwd(z, 10, 6, 2, 3, 1, 1, z, z, z, z, z, z, 12, z, 12, z, 6, z, 0, z) == -1      # null table: refused
+    assert lib.score_coattn_bwd(z, z, 10, 6, 2, 3, 1, 1, z, z, z, z, z, 12, z, 12, z, 6, z, z, z, 0, 0, z) == -1
+    assert lib.score_coattn_last_forms(0) == f and lib.score_coattn_last_forms(1) == b and lib.score_coattn_last_forms(7) == b
+    src = open(os.path.join(ROOT, "include", "score_hip.h")).read()
+    doc = src[:src.index("int score_coattn_last_forms(")].rsplit("/*", 1)[1]
+    for field in ("bit   0", "bits  1 ..  6", "bits  8 .. 10", "bits 12 .. 27", "bits 12 .. 14", "bit  16", "bits 20 .. 21",
+                  "-1 before the first"):
+        assert field in doc, field
+    # the packing of the case module is the documented one
+    assert coattn_cases.pack_fwd(coattn_cases.Fwd(1, 10, 1, 2)) == 1 | 10 << 1 | 1 << 8 | 2 << 12
+    assert coattn_cases.pack_bwd(coattn_cases.Bwd(32, 2, 0, 1, 0)) == 32 << 1 | 2 << 8 | 1 << 16
+    assert coattn_cases.pack_bwd(coattn_cases.Bwd(10, 1, 4, 0, 1)) == 10 << 1 | 1 << 8 | 4 << 12 | 1 << 20
+
+
 def test_pull_geometry_query_is_host_only_and_documented():
     """score_pull_geometry: what score_launch_pull would use for (n, D), without a GPU and without touching score_pull_last_form;
     the header names the four outputs, the window thresholds and both refusals (tests/scatter_cases.py restates them)"""
